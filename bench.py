@@ -1,6 +1,8 @@
 """bench.py -- env-steps/s of the WRSN environment step path on N MI355X (one process per GPU).
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W --full   (also every extra measurement, see below)
+    python bench.py ... --dump-outputs DIR                 (also writes what the last timed step returned, DIR/<name>.npy)
 
 Workload (BASELINE.json configs[1]): 4096 independent environments per GPU x 200 nodes x 200 targets x 3 mobile
 chargers, seeded synthetic networks, random policy actions ~U[0,1)^3, auto-reset on terminal.
@@ -8,8 +10,15 @@ A "step" is one VecWRSN.step launch over the whole batch.  With the default step
 is not finished when its share of the launch is used up reports "still running" and goes on in the next launch (the
 duration of a WRSN.step is heavy-tailed; see include/wrsn_hip.h, wrsn_set_step_budget): `value` counts COMPLETED
 WRSN.step() calls only (each with its 4x100x100 observation) -- auto-resets and unfinished steps are not counted.
-The same workload with blocking steps (budget 0, every launch waits for its slowest environment) is measured too and
-reported under "blocking".
+A plain run sets up, warms up, times the K steps and prints the line.  With `--full` the workload with blocking steps
+(budget 0, every launch waits for its slowest environment) is measured too and reported under "blocking", next to the
+per-kernel timing pass (`kernels`, `roofline`), `extended` and the CPU baseline (`cpu_baseline`).
+
+`--dump-outputs DIR` (rank 0): the request tensors of the last timed step (agent_id, reward, terminal, now, status: every
+environment of the shard, as float64), the observations of a fixed seeded sample of its environments (`state`, float32,
+their indices in `state_rows`) and the rollout returns table gathered after the timed region (`rollout_table`, float64).
+The same arguments give the same inputs in every run, so two builds can be compared output for output.
+
 Environments are independent, so ranks shard them with no data-path collective (weak scaling); the only exchange is
 one all-gather of the rollout returns table after the timed region.
 
@@ -71,8 +80,26 @@ def cpu_baseline(scenarios, M, seconds, threads):
     return sum(counts) / dt, sum(counts), dt
 
 
-def measure(torch, dist, dev, scenarios, M, G, rank, seed, budget, steps, warmup, kernel_steps, deadline_us=0, min_seconds=0.0):
-    """One timed run of `steps` VecWRSN.step launches on this rank's shard; returns the local numbers."""
+DUMP_STATE_ROWS = 256        # observations of 256 environments: 41 MB at 4 x 100 x 100 float32 (all 4096 would be 655 MB)
+
+
+def step_outputs(torch, r, table):
+    """What the timed path hands its caller after a step, as host float64 / float32 arrays (see the module docstring)."""
+    import numpy as np
+    out = {k: r[k].cpu().numpy().astype(np.float64) for k in ("agent_id", "reward", "terminal", "now", "status")}
+    B, G = r["state"].shape[0], r["state"].shape[-1]
+    n = max(1, min(B, DUMP_STATE_ROWS, (48 << 20) // (16 * G * G)))
+    rows = np.sort(np.random.RandomState(0).choice(B, n, replace=False))
+    out["state"] = r["state"].index_select(0, torch.from_numpy(rows).to(r["state"].device)).cpu().numpy()
+    out["state_rows"] = rows.astype(np.float64)
+    out["rollout_table"] = table.cpu().numpy().astype(np.float64)
+    return out
+
+
+def measure(torch, dist, dev, scenarios, M, G, rank, seed, budget, steps, warmup, kernel_steps, deadline_us=0, min_seconds=0.0,
+            full=True, dump=False):
+    """One timed run of `steps` VecWRSN.step launches on this rank's shard; returns the local numbers.  full: also the
+    `extended` region and the per-kernel timing pass; dump: also the host copy of what the last timed step returned."""
     from multi_agent_rl_wrsn_amd import RolloutStats, VecWRSN
     B = len(scenarios)
     t_set = time.time()
@@ -105,6 +132,11 @@ def measure(torch, dist, dev, scenarios, M, G, rank, seed, budget, steps, warmup
     res = {"elapsed": elapsed, "env_steps": c1["env_steps"] - c0["env_steps"], "sim_seconds": c1["sim_seconds_total"] - c0["sim_seconds_total"],
            "zero_steps": c1["zero_time_steps"] - c0["zero_time_steps"], "exact_ticks": c1["exact_ticks"],
            "table": RolloutStats.gather_table(env.rollout_table()), "t_set": t_set}   # the path's one exchange step (RCCL all-gather)
+    res["outputs"] = step_outputs(torch, r, res["table"]) if dump else None   # before any further step overwrites them
+    if not full:
+        res["mean_episode_seconds"] = float(env.env_info()["n_ticks"].mean())
+        env.close()
+        return res
     # ---- a timed region of K steps that lasts less than min_seconds is too short for samplers around the run (the driver passes
     #      --steps 20: ~12 ms): a second region of as many steps as min_seconds needs is timed the same way and reported beside it
     res["ext"] = None
@@ -145,6 +177,40 @@ def measure(torch, dist, dev, scenarios, M, G, rank, seed, budget, steps, warmup
     return res
 
 
+def kernel_figures(res, B, N, T, M, G, step_budget, value):
+    """`kernels` and `roofline` of the line (--full), from the per-kernel timing pass of `measure`."""
+    phys_b, obs_b = algorithmic_bytes(N, T, M, G)
+    env_launch, obs_launch, units = res["env_launch"], res["obs_launch"], res["units"]
+    if env_launch >= obs_launch:
+        dom, dur, per_unit = "wrsn_step_kernel", env_launch, phys_b
+    else:
+        dom, dur, per_unit = "wrsn_obs_kernel", obs_launch, obs_b
+    achieved = per_unit * units / dur / 1e9
+    peak = 8000.0
+    # HBM bytes per launch of the dominant kernel from the newest committed rocprofv3 PMC passes (profiles/), attached
+    # only when they were taken on THIS configuration (the file names it); null otherwise
+    traffic = None; traffic_src = None; rocprof_us = None
+    this_cfg = {"envs_per_gpu": B, "nodes": N, "targets": T, "chargers": M, "map_size": G, "step_budget": step_budget}
+    try:
+        for tfile in sorted((f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_traffic.json")), reverse=True):
+            tj = json.load(open(os.path.join(ROOT, "profiles", tfile)))
+            if tj.get("config") == this_cfg and dom in tj.get("kernels", {}):
+                traffic = tj["kernels"][dom]["hbm_bytes_per_launch"]; traffic_src = "profiles/" + tfile
+                rocprof_us = tj["kernels"][dom].get("rocprof_avg_us")     # average duration of that kernel in the --kernel-trace --stats pass of the same command
+                break
+    except Exception:
+        traffic = None
+    kernels = {"wrsn_step_kernel_ms": 1e3 * env_launch, "wrsn_obs_kernel_ms": 1e3 * obs_launch,
+               "launch_order_kernels_ms": 1e3 * res["order_launch"], "env_steps_per_launch": units}
+    roofline = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": peak, "unit": "GB/s", "frac": achieved / peak,
+                "traffic": traffic, "traffic_source": traffic_src, "algorithmic_bytes_per_launch": per_unit * units, "algorithmic_bytes_per_env_step": {"physics": phys_b, "observation": obs_b},
+                "whole_step_achieved_GBps": (phys_b + obs_b) * value / 1e9, "whole_step_frac": (phys_b + obs_b) * value / 1e9 / peak}
+    if rocprof_us:                                              # the same fraction on the committed rocprofv3 duration of that kernel (same configuration)
+        roofline["rocprof_avg_us"] = rocprof_us
+        roofline["frac_rocprof"] = per_unit * units / (rocprof_us * 1e-6) / 1e9 / peak
+    return kernels, roofline
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start the N ranks here, before this process touches the GPU
     (multi_agent_rl_wrsn_amd.sharding.launch_ranks; importing the package loads neither torch's GPU runtime nor the HIP library)."""
@@ -174,6 +240,11 @@ def main():
     ap.add_argument("--min-seconds", type=float, default=0.1,
                     help="when the timed region of --steps launches is shorter than this, a second region long enough is timed too and reported as `extended` (0 = off)")
     ap.add_argument("--no-blocking-run", action="store_true", help="skip the additional blocking-mode (step_budget 0) measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline figure: per-kernel timing pass and roofline, `extended`, the "
+                         "blocking-mode run and the CPU baseline (--kernel-steps, --min-seconds, --no-blocking-run, --cpu-seconds apply)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, rank 0's shard)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus)                                  # never returns
@@ -212,10 +283,11 @@ def main():
             res["ext"]["elapsed_all"], res["ext"]["env_steps_all"], res["ext"]["zero_steps_all"] = float(el[1]), float(cnt[3]), float(cnt[4])
         return float(el[0]), float(cnt[0])
 
-    main_res = measure(torch, dist, dev, scenarios, M, G, rank, args.seed, args.step_budget, args.steps, args.warmup, args.kernel_steps, args.step_deadline_us, args.min_seconds)
+    main_res = measure(torch, dist, dev, scenarios, M, G, rank, args.seed, args.step_budget, args.steps, args.warmup, args.kernel_steps, args.step_deadline_us, args.min_seconds,
+                       full=args.full, dump=args.dump_outputs is not None and rank == 0)
     elapsed, env_steps = reduced(main_res)
     blocking = None
-    if args.step_budget > 0 and not args.no_blocking_run:
+    if args.full and args.step_budget > 0 and not args.no_blocking_run:
         bsteps = max(10, args.steps // 2)
         bres = measure(torch, dist, dev, scenarios, M, G, rank, args.seed, 0, bsteps, max(5, args.warmup // 2), max(2, args.kernel_steps // 2))
         bel, bcnt = reduced(bres)
@@ -226,28 +298,6 @@ def main():
                     "kernels": {"wrsn_step_kernel_ms": 1e3 * bres["env_launch"], "wrsn_obs_kernel_ms": 1e3 * bres["obs_launch"],
                                 "launch_order_kernels_ms": 1e3 * bres["order_launch"], "env_steps_per_launch": bres["units"]},
                     "note": "step_budget 0: every launch runs each WRSN.step to its end and waits for the slowest environment"}
-
-    phys_b, obs_b = algorithmic_bytes(N, T, M, G)
-    env_launch, obs_launch, units = main_res["env_launch"], main_res["obs_launch"], main_res["units"]
-    if env_launch >= obs_launch:
-        dom, dur, per_unit = "wrsn_step_kernel", env_launch, phys_b
-    else:
-        dom, dur, per_unit = "wrsn_obs_kernel", obs_launch, obs_b
-    achieved = per_unit * units / dur / 1e9
-    peak = 8000.0
-    # HBM bytes per launch of the dominant kernel from the newest committed rocprofv3 PMC passes (profiles/), attached
-    # only when they were taken on THIS configuration (the file names it); null otherwise
-    traffic = None; traffic_src = None; rocprof_us = None
-    this_cfg = {"envs_per_gpu": B, "nodes": N, "targets": T, "chargers": M, "map_size": G, "step_budget": args.step_budget}
-    try:
-        for tfile in sorted((f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith("_traffic.json")), reverse=True):
-            tj = json.load(open(os.path.join(ROOT, "profiles", tfile)))
-            if tj.get("config") == this_cfg and dom in tj.get("kernels", {}):
-                traffic = tj["kernels"][dom]["hbm_bytes_per_launch"]; traffic_src = "profiles/" + tfile
-                rocprof_us = tj["kernels"][dom].get("rocprof_avg_us")     # average duration of that kernel in the --kernel-trace --stats pass of the same command
-                break
-    except Exception:
-        traffic = None
 
     if rank == 0:
         value = env_steps / elapsed
@@ -265,15 +315,9 @@ def main():
             "mean_episode_seconds_so_far": main_res["mean_episode_seconds"],
             "mean_return_table_rows": int(main_res["table"].shape[0]),
             "setup_s": {"generate": round(t_gen, 2), "topology+warmup": round(main_res["t_set"], 2)},
-            "kernels": {"wrsn_step_kernel_ms": 1e3 * env_launch, "wrsn_obs_kernel_ms": 1e3 * obs_launch,
-                        "launch_order_kernels_ms": 1e3 * main_res["order_launch"], "env_steps_per_launch": units},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": peak, "unit": "GB/s", "frac": achieved / peak,
-                         "traffic": traffic, "traffic_source": traffic_src, "algorithmic_bytes_per_launch": per_unit * units, "algorithmic_bytes_per_env_step": {"physics": phys_b, "observation": obs_b},
-                         "whole_step_achieved_GBps": (phys_b + obs_b) * value / 1e9, "whole_step_frac": (phys_b + obs_b) * value / 1e9 / peak},
         }
-        if rocprof_us:                                          # the same fraction on the committed rocprofv3 duration of that kernel (same configuration)
-            out["roofline"]["rocprof_avg_us"] = rocprof_us
-            out["roofline"]["frac_rocprof"] = per_unit * units / (rocprof_us * 1e-6) / 1e9 / peak
+        if args.full:
+            out["kernels"], out["roofline"] = kernel_figures(main_res, B, N, T, M, G, args.step_budget, value)
         zshare = main_res["zero_steps_all"] / max(1.0, env_steps)
         out["value_time_advancing"] = value * (1.0 - zshare)   # completed WRSN.step calls that ran simulated time (the rest: bookkeeping returns at t = warm_up_time)
         if main_res.get("ext"):
@@ -283,7 +327,7 @@ def main():
                                "note": "the timed region of --steps %d launches lasted %.1f ms; the same loop over %d launches, timed the same way" % (args.steps, 1e3 * elapsed, x["steps"])}
         if blocking is not None:
             out["blocking"] = blocking
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full and args.cpu_seconds > 0 and world == 1:
             cores = os.cpu_count() or 1
             try:
                 usable = len(os.sched_getaffinity(0))           # what this process may run on (a box hands out a share of the host)
@@ -293,6 +337,11 @@ def main():
             v, n, dt = cpu_baseline(scenarios[:256], M, args.cpu_seconds, threads)
             out["cpu_baseline"] = {"value": v, "unit": "env-steps/s", "cores": threads, "host_cores": cores, "usable_cores": usable, "kind": "port",
                                    "sample": "%d oracle env-steps (incl. get_state) in %.1f s on %d threads, same synthetic networks and action distribution" % (n, dt, threads)}
+        if args.dump_outputs:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in main_res["outputs"].items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
         print(json.dumps(out), flush=True)
     if dist:
         dist.destroy_process_group()

@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE ONLY -- golden vector for the PPO update of the reference (controller/ippo/IPPO.py:229-271), produced by
 RUNNING the reference's own statements in this container.
 
-    python oracle/refharness/gen_update_golden.py        -> tests/golden_policy/update_step.npz
+    python oracle/refharness/gen_update_golden.py        -> tests/golden/policy/update_step.npz
 
 The update is not a function of the reference: it is the loop `for _ in range(self.n_updates_per_iteration):` inside
 `IPPO.train` (IPPO.py:230), behind the roll-out, TensorBoard writers and CSV logging of that method (tensorboard is not installed
@@ -22,6 +22,8 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 REF_ROOT = os.environ.get("WRSN_REFERENCE_ROOT", "/root/reference")
+# the MKL code path tests/conftest.py pins for the test run: the same bits on every x86-64 CPU (before torch is loaded)
+os.environ["MKL_CBWR"] = "COMPATIBLE"
 sys.path.insert(0, HERE)
 from gen_policy_golden import formula_fill  # noqa: E402
 
@@ -73,8 +75,8 @@ def main():
     out = {"shape": np.array([G, SHUFFLE_SEED]), "cases": np.array(sorted(CASES))}
     for case in sorted(CASES):
         run_case(torch, nn, ns, loop_node, UNet, CNNCritic, case, out)
-    os.makedirs(os.path.join(REPO, "tests", "golden_policy"), exist_ok=True)
-    np.savez_compressed(os.path.join(REPO, "tests", "golden_policy", "update_step.npz"), **out)
+    os.makedirs(os.path.join(REPO, "tests", "golden", "policy"), exist_ok=True)
+    np.savez_compressed(os.path.join(REPO, "tests", "golden", "policy", "update_step.npz"), **out)
 
 
 def run_case(torch, nn, ns, loop_node, UNet, CNNCritic, case, out):

@@ -2,7 +2,12 @@ import glob
 import os
 import sys
 
-import numpy as np
+# MKL on the code path that gives the same bits on every x86-64 CPU, set before anything loads torch: by default MKL picks its
+# kernels by CPU vendor and ISA, and the float32 PPO update of tests/golden/policy/update_step.npz (recorded with this setting,
+# oracle/refharness/gen_update_golden.py) amplifies their different rounding far past its tolerances.
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
+import numpy as np  # noqa: E402
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

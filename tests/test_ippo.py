@@ -1,6 +1,6 @@
 """f2 / f4 on the CPU: policy networks and trainer arithmetic against vectors generated from the reference's own modules
 (tests/golden_policy/policy_nets.npz, script oracle/refharness/gen_policy_golden.py), the PPO update against the reference's own update
-loop run on its own networks (tests/golden_policy/update_step.npz, oracle/refharness/gen_update_golden.py), the batch selection, the device-side
+loop run on its own networks (tests/golden/policy/update_step.npz, oracle/refharness/gen_update_golden.py), the batch selection, the device-side
 transition bookkeeping (emulated kernels) against the reference's list bookkeeping restated from controller/ippo/IPPO.py:137-155,
 and the data-parallel gradient exchange on a world-2 gloo group."""
 import os
@@ -67,7 +67,7 @@ def test_update_matches_the_reference_update_loop(case):
     in shuffled minibatches of 8, every ratio clipped (what a roll-out really leaves); `whole`: the unclipped policy gradient."""
     import torch
     from multi_agent_rl_wrsn_amd import PPOLearner
-    z = np.load(os.path.join(ROOT, "tests", "golden_policy", "update_step.npz"))
+    z = np.load(os.path.join(ROOT, "tests", "golden", "policy", "update_step.npz"))
     G, seed = (int(v) for v in z["shape"]); B, MB, EPOCHS = (int(v) for v in z[case + "_shape"])
     torch.manual_seed(0); torch.set_num_threads(4)
     lr = PPOLearner({"lr": 3.0e-4, "clip": 0.2, "batch_size": B, "minibatch_size": MB, "n_updates_per_iteration": EPOCHS, "norm_adv": True,

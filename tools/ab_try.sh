@@ -2,7 +2,7 @@
 # Same-box timing of candidate libraries: tools/ab_try.sh <tag> libA.so libB.so ... (in-tree library = "tree")
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/${1:-try}; mkdir -p $OUT; shift
-ARGS="--cpu-seconds 0 --steps 60 --warmup 20 --no-blocking-run ${BENCH_ARGS:-}"
+ARGS="--full --cpu-seconds 0 --steps 60 --warmup 20 --no-blocking-run ${BENCH_ARGS:-}"
 for rep in 1 2; do
   for lib in "$@"; do
     if [ $lib = tree ]; then unset WRSN_HIP_LIB; else export WRSN_HIP_LIB=$ROOT/$lib; fi

@@ -34,7 +34,7 @@ fe, wr = pmc("fetch", "FETCH_SIZE"), pmc("write", "WRITE_SIZE")
 # dispatches of a kernel per step call (pipelined step calls launch the step / observation kernels twice): per-call figures below
 calls = max(1, dur.get("wrsn_sort_kernel", {}).get("calls", 0))
 res = {"note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes (MI355X_MICROARCH.md HBM section) of "
-               "`python3 bench.py --steps 40 --warmup 10 --cpu-seconds 0 --kernel-steps 5 --no-blocking-run` (default step budget); counters are KiB per dispatch; hbm_bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 "
+               "`python3 bench.py --full --steps 40 --warmup 10 --cpu-seconds 0 --kernel-steps 5 --no-blocking-run` (default step budget); counters are KiB per dispatch; hbm_bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 "
                "(gfx950 FETCH_SIZE tallies 128-B requests at 64 B: doubled, an upper bound for narrower accesses)", "config": cfg, "kernels": {}}
 for k in ("wrsn_step_kernel", "wrsn_obs_kernel"):
     if fe[k][1] and wr[k][1]:
