@@ -95,9 +95,13 @@ enum wrsn_peek_what {
     WRSN_PEEK_NODE_DEGREE = 7,   /* int32  [B,N]   len(Node.neighbors)                            */
     WRSN_PEEK_NODE_NCOVER = 8,   /* int32  [B,N]   len(Node.listTargets)                          */
     WRSN_PEEK_NODE_DIRECT = 9,   /* int32  [B,N]   node in BaseStation.direct_nodes               */
-    WRSN_PEEK_TARGETS_ACTIVE = 11 /* int32 [B,T]   Network.targets_active (Network.py:9,45-55): target covered by a node the last
+    WRSN_PEEK_TARGETS_ACTIVE = 11, /* int32 [B,T]   Network.targets_active (Network.py:9,45-55): target covered by a node the last
                                                     setLevels reached; 0 beyond an environment's own target count.  (10 is
                                                     taken by the per-phase cycle counters of diagnostic builds.)       */
+    WRSN_PEEK_RNG_STATE = 12     /* uint32 [B,627] the environment's MT19937: the 624 state words and the index as
+                                                    random.getstate()[1] lists them, then the draws since the last reset
+                                                    (low, high word).  Handles that run the stochastic kernels only
+                                                    (wrsn_set_scenario_seeded); WRSN_ERR_STATE otherwise. */
 };
 
 /* Create a handle for B environments on cfg->device.  Fails with WRSN_ERR_NO_DEVICE when no HIP
@@ -116,12 +120,26 @@ int wrsn_set_stream(wrsn_t *h, void *hip_stream);
  *   node_spec [nenv] (or one spec broadcast when spec_stride == 0), mc_spec likewise.
  * Builds topology on the device, runs the warm-up (WRSN.py:53) on the device and caches the
  * post-warm-up snapshot reset() restores (the state after run(until=warm_up_time) is a pure
- * function of the scenario).  Synchronous. */
+ * function of the scenario).  Synchronous.  Refuses node_spec.prob_gp != 1 (use
+ * wrsn_set_scenario_seeded). */
 int wrsn_set_scenario(wrsn_t *h, int32_t env0, int32_t nenv,
                       const double *node_xy, const double *target_xy, const double *bs_xy,
                       const int32_t *n_node_env, const int32_t *n_target_env,
                       const wrsn_node_spec *node_spec, int32_t node_spec_stride,
                       const wrsn_mc_spec *mc_spec, int32_t mc_spec_stride);
+
+/* wrsn_set_scenario plus the scenario key `seed` of every environment (HOST pointer [nenv]):
+ * accepts 0 <= prob_gp <= 1.  Node.py:61 draws random.random() once per live node and second and
+ * generates the node's packets only when the draw is below prob_gp; NetworkIO.py:22-23 seeds
+ * Python's MT19937 with random.seed(seed) on every reset.  The handle keeps that generator per
+ * environment (in the post-warm-up snapshot too: every episode starts from the same stream) and
+ * runs the stochastic kernels as soon as one environment has prob_gp != 1; with prob_gp == 1
+ * everywhere it runs the kernels of wrsn_set_scenario and does not track the generator. */
+int wrsn_set_scenario_seeded(wrsn_t *h, int32_t env0, int32_t nenv,
+                             const double *node_xy, const double *target_xy, const double *bs_xy,
+                             const int32_t *n_node_env, const int32_t *n_target_env,
+                             const wrsn_node_spec *node_spec, int32_t node_spec_stride,
+                             const wrsn_mc_spec *mc_spec, int32_t mc_spec_stride, const int64_t *seed);
 
 /* WRSN.reset (WRSN.py:41-83) for the environments whose env_mask byte is non-zero
  * (DEVICE pointer [B]; NULL = all).  Outputs follow the reset request (agent 0, reward 0).  Rows of environments

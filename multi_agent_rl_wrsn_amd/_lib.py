@@ -18,13 +18,14 @@ ERR_NAMES = {0: "WRSN_OK", -1: "WRSN_ERR_ARG", -2: "WRSN_ERR_HIP", -3: "WRSN_ERR
 PEEK_NODE_ENERGY, PEEK_NODE_CS, PEEK_NODE_RR, PEEK_NODE_STATUS, PEEK_NODE_LEVEL = 0, 1, 2, 3, 4
 PEEK_MC, PEEK_ENV, PEEK_NODE_DEGREE, PEEK_NODE_NCOVER, PEEK_NODE_DIRECT = 5, 6, 7, 8, 9
 PEEK_TARGETS_ACTIVE = 11
+PEEK_RNG_STATE = 12          # uint32 [B, 627]: MT19937 words, index (random.getstate()[1]), draws since reset (low, high word)
 MC_FIELDS = ("loc_x", "loc_y", "energy", "status", "type_charging", "cur_x", "cur_y", "cur_t", "n_conn",
              "excl", "prev_minfit", "act0", "act1", "act2", "_r0", "_r1")
 ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max", "charging_time_max",
               "avg_nodes_agent", "now", "alive", "n_ticks", "n_exact", "n_events", "min_fitness", "n_edges", "n_cover")
 
 # every entry point include/wrsn_hip.h declares
-EXPORTS = ("wrsn_create", "wrsn_destroy", "wrsn_set_stream", "wrsn_set_scenario", "wrsn_reset", "wrsn_step",
+EXPORTS = ("wrsn_create", "wrsn_destroy", "wrsn_set_stream", "wrsn_set_scenario", "wrsn_set_scenario_seeded", "wrsn_reset", "wrsn_step",
            "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_render", "wrsn_set_obs_reuse", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_synth_network",
            "wrsn_last_error",
            "wrsn_version")
@@ -75,6 +76,9 @@ def bind(lib):
     lib.wrsn_set_scenario.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(WrsnNodeSpec), C.c_int32,
                                       C.POINTER(WrsnMcSpec), C.c_int32]
     lib.wrsn_set_scenario.restype = C.c_int
+    lib.wrsn_set_scenario_seeded.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.POINTER(WrsnNodeSpec), C.c_int32,
+                                             C.POINTER(WrsnMcSpec), C.c_int32, vp]
+    lib.wrsn_set_scenario_seeded.restype = C.c_int
     lib.wrsn_reset.argtypes = [vp, vp, C.POINTER(WrsnStepOut)]
     lib.wrsn_reset.restype = C.c_int
     lib.wrsn_step.argtypes = [vp, vp, vp, C.c_int32, C.POINTER(WrsnStepOut)]
@@ -203,6 +207,16 @@ class RawHandle:
             nn[e], nt[e] = sc.n_node, sc.n_target
             specs[e] = make_node_spec(sc.node_spec, sc.max_time)
         mcs = make_mc_spec(mc_spec)
+        if any(getattr(sc, "stochastic_packets", False) for sc in scenarios):
+            # prob_gp != 1 somewhere in the batch: every environment of it gets its generator, seeded with the scenario's seed
+            for sc in scenarios:
+                if int(sc.seed) != sc.seed or not (-2 ** 63 <= int(sc.seed) < 2 ** 63):
+                    raise ValueError("seed %r of scenario %r is outside the int64 range" % (sc.seed, sc.name))
+            seeds = np.array([int(sc.seed) for sc in scenarios], dtype=np.int64)
+            check(self.lib, self.lib.wrsn_set_scenario_seeded(self._h, int(env0), n, node_xy.ctypes.data, target_xy.ctypes.data,
+                                                              bs.ctypes.data, nn.ctypes.data, nt.ctypes.data, specs, 1,
+                                                              C.byref(mcs), 0, seeds.ctypes.data))
+            return
         check(self.lib, self.lib.wrsn_set_scenario(self._h, int(env0), n, node_xy.ctypes.data, target_xy.ctypes.data,
                                                    bs.ctypes.data, nn.ctypes.data, nt.ctypes.data, specs, 1,
                                                    C.byref(mcs), 0))
@@ -270,6 +284,8 @@ class RawHandle:
             a = np.empty((B, M, 16), dtype=np.float64)
         elif what == PEEK_ENV:
             a = np.empty((B, 16), dtype=np.float64)
+        elif what == PEEK_RNG_STATE:
+            a = np.empty((B, 627), dtype=np.uint32)
         else:
             raise ValueError("unknown peek selector %r" % (what,))
         check(self.lib, self.lib.wrsn_peek(self._h, int(what), a.ctypes.data))

@@ -87,7 +87,9 @@ struct wrsn_handle {
     int ev_rec;                // a wrsn_step has recorded the events since timing was switched on
     int bp2;                   // B rounded up to a power of two when the launch order is sorted on the device (B <= 8192), else 0
     std::vector<void*> allocs;
-    WrsnDev* d_dev;            // device copy of `dev`: the environment kernels read it through the constant cache
+    WrsnDev* d_dev;            // device copy of `dev`: the environment kernels read it through the constant cache; `sd` follows it
+    WrsnStochDev sd;           // prob_gp < 1: MT19937 state, send costs, prob_gp per environment (allocated by the first seeded call)
+    int stoch;                 // an environment was loaded with prob_gp != 1 through wrsn_set_scenario_seeded: the stochastic kernels run
 };
 
 namespace {
@@ -125,12 +127,13 @@ int alloc_node_arrays(wrsn_handle* h, WrsnNodeArrays* a) {
 // LDS sizes, wave slots and the device copy of the descriptor; again whenever WrsnDev.CC changes
 int configure_launch(wrsn_handle* h) {
     WrsnDev& d = h->dev;
-    h->lds_env = wrsn_lds_bytes(d.NP, d.M, d.CC);
+    h->lds_env = wrsn_lds_bytes(d.NP, d.M, d.CC) + (h->stoch ? wrsn_stoch_lds_bytes(d.NP) : 0);
     {   // wave slots of the step kernel on this device (registers and LDS decide): the budget taper of a launch starts behind the blocks
         // that are resident from the first moment
         int per_cu = 0; hipError_t oe = hipErrorUnknown;
         const int lds_b = h->lds_env + h->lds_pad;
-#define WRSN_OCC(NPL_) oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, wrsn_step_kernel<NPL_, WRSN_KERNEL_INLINE>, 64, (size_t)lds_b)
+#define WRSN_OCC(NPL_) oe = h->stoch ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, wrsn_step_stoch_kernel<NPL_>, 64, (size_t)lds_b) \
+                                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, wrsn_step_kernel<NPL_, WRSN_KERNEL_INLINE>, 64, (size_t)lds_b)
         WRSN_NPL_SWITCH(h->npl, WRSN_OCC, oe = hipErrorUnknown)
 #undef WRSN_OCC
         h->slots = h->cus * 8;
@@ -138,6 +141,7 @@ int configure_launch(wrsn_handle* h) {
         h->waves_per_cu = (oe == hipSuccess) ? per_cu : 0;
     }
     HIPCHK(hipMemcpy(h->d_dev, &h->dev, sizeof(WrsnDev), hipMemcpyHostToDevice));
+    if (h->stoch) HIPCHK(hipMemcpy(h->d_dev + 1, &h->sd, sizeof(WrsnStochDev), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -163,7 +167,7 @@ int launch_env(wrsn_handle* h, int mode, int env0, int nenv, const int32_t* agen
         hipLaunchKernelGGL(wrsn_latch_kernel, dim3((nenv + 255) / 256), dim3(256), 0, h->stream, h->dev, agent_id, action, out);
         if (timed) (void)hipEventRecord(h->ev[1], h->stream);
         const int qbudget = budget > 0 ? budget : (1 << 28);   // the deadline is looked at wherever a work budget is
-#define WRSN_QUEUE(NPL_) hipLaunchKernelGGL((wrsn_step_kernel<NPL_, WRSN_KERNEL_INLINE>), grid, block, lds, h->stream, (const WrsnDev*)h->d_dev, 0, agent_id, action, \
+#define WRSN_QUEUE(NPL_) hipLaunchKernelGGL((h->stoch ? wrsn_step_stoch_kernel<NPL_> : wrsn_step_kernel<NPL_, WRSN_KERNEL_INLINE>), grid, block, lds, h->stream, (const WrsnDev*)h->d_dev, 0, agent_id, action, \
                                            auto_reset, qbudget, epoch, 0, mask, out, 3, h->deadline_ticks, 0)
         WRSN_NPL_SWITCH(h->npl, WRSN_QUEUE, return fail(WRSN_ERR_ARG, "unsupported nodes-per-lane"))
 #undef WRSN_QUEUE
@@ -204,7 +208,8 @@ int launch_env(wrsn_handle* h, int mode, int env0, int nenv, const int32_t* agen
     }
     if (timed) (void)hipEventRecord(h->ev[1], h->stream);
 #define WRSN_LAUNCH(NPL_)                                                                                              \
-    if (mode == WRSN_MODE_WARMUP) hipLaunchKernelGGL(wrsn_warmup_kernel<NPL_>, grid, block, lds, h->stream, (const WrsnDev*)h->d_dev, env0);  \
+  { auto stepk_ = h->stoch ? wrsn_step_stoch_kernel<NPL_> : wrsn_step_kernel<NPL_, WRSN_KERNEL_INLINE>;              \
+    if (mode == WRSN_MODE_WARMUP) hipLaunchKernelGGL((h->stoch ? wrsn_warmup_stoch_kernel<NPL_> : wrsn_warmup_kernel<NPL_>), grid, block, lds, h->stream, (const WrsnDev*)h->d_dev, env0);  \
     else if (pipe) {                                                                                                    \
         /* stages over the launch order: [0, n1) the longest jobs (caller's stream), [n1, n2) the rest of the long half (third stream), */ \
         /* [n2, B) the short half with its own work cap (second stream); n2 <= wave slots: the long half's jobs all start at once       */ \
@@ -213,25 +218,25 @@ int launch_env(wrsn_handle* h, int mode, int env0, int nenv, const int32_t* agen
         const int b_short = budget > 0 ? (budget * h->pipe_short_pct / 100 > 64 ? budget * h->pipe_short_pct / 100 : 64) : 0; \
         (void)hipEventRecord(h->ev_fork, h->stream); (void)hipStreamWaitEvent(h->stream2, h->ev_fork, 0);              \
         if (n1 < n2) (void)hipStreamWaitEvent(h->stream3, h->ev_fork, 0);                                              \
-        hipLaunchKernelGGL((wrsn_step_kernel<NPL_, WRSN_KERNEL_INLINE>), dim3(nenv - n2), block, lds, h->stream2, (const WrsnDev*)h->d_dev, reset_call, agent_id, action, \
+        hipLaunchKernelGGL(stepk_, dim3(nenv - n2), block, lds, h->stream2, (const WrsnDev*)h->d_dev, reset_call, agent_id, action, \
                            auto_reset, b_short, epoch, (h->slots & 0xFFFF) | taper, mask, out, 0, dl, n2);                                     \
         hipLaunchKernelGGL(wrsn_obs_kernel, dim3(nenv - n2), dim3(256), h->lds_obs, h->stream2, h->dev, (const int32_t*)h->dev.render_agent, obs_pipe, h->obs_reuse, (const int32_t*)h->dev.order, n2); \
         (void)hipEventRecord(h->ev_join, h->stream2);                                                                 \
         if (n1 < n2) {                                                                                                 \
-            hipLaunchKernelGGL((wrsn_step_kernel<NPL_, WRSN_KERNEL_INLINE>), dim3(n2 - n1), block, lds, h->stream3, (const WrsnDev*)h->d_dev, reset_call, agent_id, action, \
+            hipLaunchKernelGGL(stepk_, dim3(n2 - n1), block, lds, h->stream3, (const WrsnDev*)h->d_dev, reset_call, agent_id, action, \
                                auto_reset, budget, epoch, (h->slots & 0xFFFF) | taper, mask, out, 0, dl, n1);                                  \
             hipLaunchKernelGGL(wrsn_obs_kernel, dim3(n2 - n1), dim3(256), h->lds_obs, h->stream3, h->dev, (const int32_t*)h->dev.render_agent, obs_pipe, h->obs_reuse, (const int32_t*)h->dev.order, n1); \
             (void)hipEventRecord(h->ev_join3, h->stream3);                                                             \
         }                                                                                                              \
-        hipLaunchKernelGGL((wrsn_step_kernel<NPL_, WRSN_KERNEL_INLINE>), dim3(n1), block, lds, h->stream, (const WrsnDev*)h->d_dev, reset_call, agent_id, action, \
+        hipLaunchKernelGGL(stepk_, dim3(n1), block, lds, h->stream, (const WrsnDev*)h->d_dev, reset_call, agent_id, action, \
                            auto_reset, budget, epoch, (h->slots & 0xFFFF) | taper, mask, out, 0, dl, 0);                                       \
         if (timed) { (void)hipEventRecord(h->ev[2], h->stream); (void)hipEventRecord(h->ev[3], h->stream); }            \
         hipLaunchKernelGGL(wrsn_obs_kernel, dim3(n1), dim3(256), h->lds_obs, h->stream, h->dev, (const int32_t*)h->dev.render_agent, obs_pipe, h->obs_reuse, (const int32_t*)h->dev.order, 0); \
         (void)hipStreamWaitEvent(h->stream, h->ev_join, 0);                                                            \
         if (n1 < n2) (void)hipStreamWaitEvent(h->stream, h->ev_join3, 0);                                              \
     }                                                                                                                  \
-    else hipLaunchKernelGGL((wrsn_step_kernel<NPL_, WRSN_KERNEL_INLINE>), grid, block, lds, h->stream, (const WrsnDev*)h->d_dev, reset_call, agent_id, action, \
-                            auto_reset, budget, epoch, (h->slots & 0xFFFF) | taper, mask, out, 0, dl, 0)
+    else hipLaunchKernelGGL(stepk_, grid, block, lds, h->stream, (const WrsnDev*)h->d_dev, reset_call, agent_id, action, \
+                            auto_reset, budget, epoch, (h->slots & 0xFFFF) | taper, mask, out, 0, dl, 0); }
     WRSN_NPL_SWITCH(h->npl, WRSN_LAUNCH, return fail(WRSN_ERR_ARG, "unsupported nodes-per-lane"))
 #undef WRSN_LAUNCH
     if (pipe) {
@@ -278,6 +283,52 @@ struct Rng {
     double normal() { double u1 = uni(), u2 = uni(); if (u1 < 1e-300) u1 = 1e-300; return std::sqrt(-2.0 * std::log(u1)) * std::cos(6.283185307179586 * u2); }
 };
 
+// random.seed(s) of CPython for an integer s (init_by_array over the little-endian 32-bit words of abs(s)), then index 624 and no
+// draws yet: one environment's block of WrsnStochDev.mt_* (WRSN_MT_STRIDE words)
+void mt_seed(int64_t seed, uint32_t* st) {
+    uint64_t n = seed < 0 ? (uint64_t)0 - (uint64_t)seed : (uint64_t)seed;
+    uint32_t key[2]; int klen = 0;
+    do { key[klen++] = (uint32_t)n; n >>= 32; } while (n != 0);
+    uint32_t* mt = st;
+    mt[0] = 19650218u;
+    for (int i = 1; i < WRSN_MT_N; ++i) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
+    int i = 1, j = 0;
+    for (int k = WRSN_MT_N > klen ? WRSN_MT_N : klen; k; --k) {
+        mt[i] = (mt[i] ^ ((mt[i - 1] ^ (mt[i - 1] >> 30)) * 1664525u)) + key[j] + (uint32_t)j;
+        ++i; ++j;
+        if (i >= WRSN_MT_N) { mt[0] = mt[WRSN_MT_N - 1]; i = 1; }
+        if (j >= klen) j = 0;
+    }
+    for (int k = WRSN_MT_N - 1; k; --k) {
+        mt[i] = (mt[i] ^ ((mt[i - 1] ^ (mt[i - 1] >> 30)) * 1566083941u)) - (uint32_t)i;
+        ++i;
+        if (i >= WRSN_MT_N) { mt[0] = mt[WRSN_MT_N - 1]; i = 1; }
+    }
+    mt[0] = 0x80000000u;
+    st[WRSN_MT_N] = WRSN_MT_N; st[WRSN_MT_N + 1] = 0; st[WRSN_MT_N + 2] = 0; st[WRSN_MT_N + 3] = 0;
+}
+
+// the stochastic block of a handle: MT state (live / snapshot), send costs (live / snapshot), prob_gp = 1 everywhere until set
+int alloc_stoch(wrsn_handle* h) {
+    if (h->sd.mt_live) return 0;
+    const size_t B = h->dev.B, NP = h->dev.NP;
+    int rc;
+    if ((rc = dalloc(h, &h->sd.mt_live, B * WRSN_MT_STRIDE))) return rc;
+    if ((rc = dalloc(h, &h->sd.mt_snap, B * WRSN_MT_STRIDE))) return rc;
+    if ((rc = dalloc(h, &h->sd.es_live, B * NP))) return rc;
+    if ((rc = dalloc(h, &h->sd.es_snap, B * NP))) return rc;
+    if ((rc = dalloc(h, &h->sd.pgp, B))) return rc;
+    std::vector<double> one(B, 1.0);
+    HIPCHK(hipMemcpy(h->sd.pgp, one.data(), B * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_dev + 1, &h->sd, sizeof(WrsnStochDev), hipMemcpyHostToDevice));
+    return 0;
+}
+
+int set_scenario_impl(wrsn_t* h, int32_t env0, int32_t nenv, const double* node_xy, const double* target_xy,
+                      const double* bs_xy, const int32_t* n_node_env, const int32_t* n_target_env,
+                      const wrsn_node_spec* node_spec, int32_t node_spec_stride, const wrsn_mc_spec* mc_spec,
+                      int32_t mc_spec_stride, const int64_t* seed);
+
 }  // namespace
 
 extern "C" {
@@ -307,6 +358,7 @@ int wrsn_create(const wrsn_cfg* cfg, wrsn_t** out) {
     { const char* e = std::getenv("WRSN_PIPE_SHORT_PCT"); h->pipe_short_pct = e ? std::atoi(e) : 40; if (h->pipe_short_pct < 5 || h->pipe_short_pct > 100) h->pipe_short_pct = 40; }
     { const char* e = std::getenv("WRSN_PIPE_LONG_PCT"); h->pipe_long_pct = e ? std::atoi(e) : 50; if (h->pipe_long_pct < 10 || h->pipe_long_pct > 90) h->pipe_long_pct = 50; }
     h->stream2 = nullptr; h->ev2_ok = 0; h->cc_bound = 0; h->cus = 256;
+    h->stoch = 0; std::memset(&h->sd, 0, sizeof(h->sd));
     // the second stream: high priority by default (WRSN_STREAM2_PRIO=0: normal) -- its launch is the SHORT half of a pipelined step call, whose
     // blocks should get wave slots first so that its observations can be rendered while the long half is still being stepped
     hipError_t se = hipErrorUnknown;
@@ -377,7 +429,11 @@ int wrsn_create(const wrsn_cfg* cfg, wrsn_t** out) {
         if ((rc = dalloc(h, &d.row_state, B))) break;
         if ((rc = dalloc(h, &d.queue, 8 + 64))) break;
         if ((rc = dalloc(h, &d.qskip, B))) break;
-        if ((rc = dalloc(h, &h->d_dev, 1))) break;
+        {   // the descriptor the kernels read, and the stochastic block behind it (wrsn_sim.h: Sim::SD)
+            uint8_t* p = nullptr;
+            if ((rc = dalloc(h, &p, sizeof(WrsnDev) + sizeof(WrsnStochDev)))) break;
+            h->d_dev = (WrsnDev*)p;
+        }
     } while (0);
     if (rc) { wrsn_destroy(h); return rc; }
     {   // identity launch order: what a handle too large for the device-side sort (or WRSN_NO_ORDER) keeps
@@ -410,6 +466,27 @@ int wrsn_set_scenario(wrsn_t* h, int32_t env0, int32_t nenv, const double* node_
                       const double* bs_xy, const int32_t* n_node_env, const int32_t* n_target_env,
                       const wrsn_node_spec* node_spec, int32_t node_spec_stride, const wrsn_mc_spec* mc_spec,
                       int32_t mc_spec_stride) {
+    return set_scenario_impl(h, env0, nenv, node_xy, target_xy, bs_xy, n_node_env, n_target_env, node_spec, node_spec_stride, mc_spec,
+                             mc_spec_stride, nullptr);
+}
+
+int wrsn_set_scenario_seeded(wrsn_t* h, int32_t env0, int32_t nenv, const double* node_xy, const double* target_xy,
+                             const double* bs_xy, const int32_t* n_node_env, const int32_t* n_target_env,
+                             const wrsn_node_spec* node_spec, int32_t node_spec_stride, const wrsn_mc_spec* mc_spec,
+                             int32_t mc_spec_stride, const int64_t* seed) {
+    if (!seed) return fail(WRSN_ERR_ARG, "null seed array");
+    return set_scenario_impl(h, env0, nenv, node_xy, target_xy, bs_xy, n_node_env, n_target_env, node_spec, node_spec_stride, mc_spec,
+                             mc_spec_stride, seed);
+}
+
+}  // extern "C"
+
+namespace {
+
+int set_scenario_impl(wrsn_t* h, int32_t env0, int32_t nenv, const double* node_xy, const double* target_xy,
+                      const double* bs_xy, const int32_t* n_node_env, const int32_t* n_target_env,
+                      const wrsn_node_spec* node_spec, int32_t node_spec_stride, const wrsn_mc_spec* mc_spec,
+                      int32_t mc_spec_stride, const int64_t* seed) {
     if (!h || !node_xy || !target_xy || !bs_xy || !node_spec || !mc_spec) return fail(WRSN_ERR_ARG, "null argument");
     const WrsnDev& d = h->dev;
     if (env0 < 0 || nenv < 1 || env0 + nenv > d.B) return fail(WRSN_ERR_ARG, "environment range out of bounds");
@@ -422,7 +499,9 @@ int wrsn_set_scenario(wrsn_t* h, int32_t env0, int32_t nenv, const double* node_
         if (n < 1 || n > d.N || t < 1 || t > d.T) return fail(WRSN_ERR_ARG, "per-environment node/target count out of range");
         const wrsn_node_spec& ns = node_spec[(size_t)e * (node_spec_stride ? 1 : 0)];
         const wrsn_mc_spec& ms = mc_spec[(size_t)e * (mc_spec_stride ? 1 : 0)];
-        if (ns.prob_gp != 1.0) return fail(WRSN_ERR_ARG, "prob_gp != 1 is not supported (Node.py:61 draws Python's MT19937)");
+        if (ns.prob_gp != 1.0 && !seed)
+            return fail(WRSN_ERR_ARG, "prob_gp != 1 needs wrsn_set_scenario_seeded (Node.py:61 draws Python's MT19937, seeded by NetworkIO.py:23)");
+        if (!(ns.prob_gp >= 0.0 && ns.prob_gp <= 1.0)) return fail(WRSN_ERR_ARG, "prob_gp outside [0, 1]");
         for (int i = 0; i < n; ++i) { hx[e * NP + i] = node_xy[((size_t)e * d.N + i) * 2]; hy[e * NP + i] = node_xy[((size_t)e * d.N + i) * 2 + 1]; }
         for (int i = 0; i < t; ++i) { tx[e * TP + i] = target_xy[((size_t)e * d.T + i) * 2]; ty[e * TP + i] = target_xy[((size_t)e * d.T + i) * 2 + 1]; }
         WrsnEnvConst& c = ec[e];
@@ -440,6 +519,21 @@ int wrsn_set_scenario(wrsn_t* h, int32_t env0, int32_t nenv, const double* node_
     HIPCHK(hipMemcpy(d.target_x + (size_t)env0 * TP, tx.data(), tx.size() * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d.target_y + (size_t)env0 * TP, ty.data(), ty.size() * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d.ec + env0, ec.data(), ec.size() * sizeof(WrsnEnvConst), hipMemcpyHostToDevice));
+    int stoch_on = 0;                                          // the handle turns to the stochastic kernels with this call
+    if (seed || h->sd.mt_live) {
+        // prob_gp and the seeded generator of every environment of the range (random.seed(seed), NetworkIO.py:23); environments loaded
+        // through wrsn_set_scenario keep prob_gp 1 and an all-zero state (their draws are counted, never used)
+        int rc0 = alloc_stoch(h); if (rc0) return rc0;
+        std::vector<double> pg(nenv); std::vector<uint32_t> mt((size_t)nenv * WRSN_MT_STRIDE, 0u);
+        for (int e = 0; e < nenv; ++e) {
+            const wrsn_node_spec& ns = node_spec[(size_t)e * (node_spec_stride ? 1 : 0)];
+            pg[e] = seed ? ns.prob_gp : 1.0;
+            if (seed) mt_seed(seed[e], mt.data() + (size_t)e * WRSN_MT_STRIDE);
+            if (pg[e] != 1.0 && !h->stoch) stoch_on = 1;
+        }
+        HIPCHK(hipMemcpy(h->sd.pgp + env0, pg.data(), (size_t)nenv * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->sd.mt_live + (size_t)env0 * WRSN_MT_STRIDE, mt.data(), mt.size() * 4, hipMemcpyHostToDevice));
+    }
     hipLaunchKernelGGL(wrsn_topology_kernel, dim3(nenv), dim3(64), 0, h->stream, h->dev, env0);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -451,7 +545,8 @@ int wrsn_set_scenario(wrsn_t* h, int32_t env0, int32_t nenv, const double* node_
     {   // size the connected-node lists in LDS to the scenarios (WrsnEnvConst.conn_bound, wrsn_topology_kernel)
         for (int e = 0; e < nenv; ++e) if (ec[e].conn_bound > h->cc_bound) h->cc_bound = ec[e].conn_bound;
         int cc = ((h->cc_bound + 3) / 4) * 4; cc = cc < 4 ? 4 : (cc > WRSN_CONN_CAP ? WRSN_CONN_CAP : cc);
-        if (cc != h->dev.CC) { h->dev.CC = cc; int rc2 = configure_launch(h); if (rc2) return rc2; }
+        if (stoch_on) h->stoch = 1;                            // (LDS and wave slots of the stochastic step kernel)
+        if (cc != h->dev.CC || stoch_on) { h->dev.CC = cc; int rc2 = configure_launch(h); if (rc2) return rc2; }
     }
     WrsnStepOutDev none; std::memset(&none, 0, sizeof(none));
     int rc = launch_env(h, WRSN_MODE_WARMUP, env0, nenv, nullptr, nullptr, 0, nullptr, none);
@@ -460,6 +555,10 @@ int wrsn_set_scenario(wrsn_t* h, int32_t env0, int32_t nenv, const double* node_
     h->scenario_set = 1;
     return WRSN_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 int wrsn_reset(wrsn_t* h, const uint8_t* env_mask, const wrsn_step_out* out) {
     if (!h || !out) return fail(WRSN_ERR_ARG, "null argument");
@@ -685,6 +784,13 @@ int wrsn_peek(wrsn_t* h, int32_t what, void* dst) {
         return 0; }
     case 10: {   // diagnostic builds (-DWRSN_PROFILE): int64 [B,25] per-phase cycle totals (+ whole kernel); zeros otherwise
         HIPCHK(hipMemcpy(dst, d.counters, B * 25 * sizeof(int64_t), hipMemcpyDeviceToHost));
+        return 0; }
+    case WRSN_PEEK_RNG_STATE: {
+        if (!h->stoch) return fail(WRSN_ERR_STATE, "the generator is tracked by handles that run the stochastic kernels only (an environment with prob_gp != 1 loaded through wrsn_set_scenario_seeded)");
+        std::vector<uint32_t> tmp(B * WRSN_MT_STRIDE);
+        HIPCHK(hipMemcpy(tmp.data(), h->sd.mt_live, tmp.size() * 4, hipMemcpyDeviceToHost));
+        uint32_t* o = (uint32_t*)dst;
+        for (size_t e = 0; e < B; ++e) std::memcpy(o + e * 627, tmp.data() + e * WRSN_MT_STRIDE, 627 * 4);
         return 0; }
     default: return fail(WRSN_ERR_ARG, "unknown peek selector");
     }

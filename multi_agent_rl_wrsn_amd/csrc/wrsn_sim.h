@@ -262,8 +262,17 @@ WDEV void wrsn_lds_gather8_b64(const double* base, const int (&idx)[8], double (
 // second (exact_walk).  When a grid item needs one of them it stops in front of that item exactly like an environment that ran out
 // of its launch budget (`need_heavy`), the step kernel stores the environment, calls wrsn_step_env_full -- a NOINLINE device function
 // with the full simulator, which loads the environment, runs that one item and suspends (or finishes the step) -- and goes on.
-template <int NPL, bool HEAVY = true>
-struct Sim {
+// STOCH = true: the stochastic variant (prob_gp < 1, Node.py:61) -- one MT19937 draw per live node and second, packets only from the
+// nodes whose draw is below prob_gp.  Everything it adds sits behind `if constexpr (STOCH)`: the prob_gp == 1 instantiations are the
+// code they were.
+// STOCH: prob_gp of the environment (pgp1: == 1, the deterministic paths run and the draws are only counted), index into the MT state
+// words, draws since the last reset, draws counted but not yet applied to the state words (mt_flush); nothing in the other variants
+template <bool STOCH> struct SimStochRegs { double pgp; int pgp1, mt_idx; int64_t mt_cnt, mt_pend; };
+template <> struct SimStochRegs<false> { static constexpr double pgp = 1.0; static constexpr int pgp1 = 1, mt_idx = 0; static constexpr int64_t mt_cnt = 0, mt_pend = 0; };
+template <int NPL, bool HEAVY = true, bool STOCH = false>
+struct Sim : SimStochRegs<STOCH> {
+    using SimStochRegs<STOCH>::pgp; using SimStochRegs<STOCH>::pgp1; using SimStochRegs<STOCH>::mt_idx;
+    using SimStochRegs<STOCH>::mt_cnt; using SimStochRegs<STOCH>::mt_pend;
     // identity / geometry.  Pointers are not kept as members: they are derived on demand from the device descriptor
     // (scalar loads from the constant cache) and from the LDS base, which keeps the hot per-second loop small in
     // registers.
@@ -382,6 +391,163 @@ struct Sim {
                 for (int j = 0; j < NPL; ++j) out[j] = (j == jj) ? v : out[j];
             }
         }
+    }
+
+    // -------------------------------------------------------------- STOCH: Python's random.random() per node and second
+    // LDS behind the carve-up above (wrsn_stoch_lds_bytes): the 624 state words, a scratch copy that serves the draws beyond the next
+    // twist, the send cost of every node's cached route, one generation flag per draw of the current instant.  The stochastic block of
+    // the descriptor sits right behind the WrsnDev copy the kernels read (wrsn_api.hip).
+    WDEV const WrsnStochDev* SD() const { return (const WrsnStochDev*)(dp + 1); }
+    WDEV int stoch_off() const { return (int)((((const char*)(SRRI() + RRCAP()) - (const char*)smem_) + 15) & ~15); }
+    WDEV uint32_t* SMT() const { return (uint32_t*)((char*)smem_ + stoch_off()); }
+    WDEV uint32_t* SMTX() const { return SMT() + WRSN_MT_N; }
+    WDEV double* SES() const { return (double*)(SMTX() + WRSN_MT_N); }
+    WDEV uint8_t* SGEN() const { return (uint8_t*)(SES() + NP); }
+
+    WDEV static uint32_t mt_temper(uint32_t y) {
+        y ^= y >> 11; y ^= (y << 7) & 0x9d2c5680u; y ^= (y << 15) & 0xefc60000u; y ^= y >> 18;
+        return y;
+    }
+    // MT19937 twist of kk in [lo, hi) (CPython's genrand_uint32): every lane reads first, then writes.  Word kk needs the OLD words kk, kk + 1
+    // and the NEW word kk + 397 - 624 (kk >= 227): the three parts [0, 227), [227, 397), [397, 624) each read only words that are final
+    WDEV void mt_twist_part(uint32_t* mt, int lo, int hi) const {
+        uint32_t nv[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int kk = lo + 64 * c + lane, k0 = kk < hi ? kk : lo;
+            const int k1 = k0 + 1 < WRSN_MT_N ? k0 + 1 : 0, km = k0 + 397 < WRSN_MT_N ? k0 + 397 : k0 - 227;
+            const uint32_t y = (mt[k0] & 0x80000000u) | (mt[k1] & 0x7fffffffu);
+            nv[c] = mt[km] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { const int kk = lo + 64 * c + lane; if (kk < hi) mt[kk] = nv[c]; }
+        __syncthreads();
+    }
+    WDEV void mt_twist(uint32_t* mt) const { mt_twist_part(mt, 0, 227); mt_twist_part(mt, 227, 397); mt_twist_part(mt, 397, WRSN_MT_N); }
+    // Generation flags of the first A draws of an instant (rank r = the r-th node to draw) into SGEN()[r].  Draw r takes the words
+    // mt_idx + 2r, mt_idx + 2r + 1 of the stream (the index is always even, so a draw never straddles a twist); the ones beyond the
+    // next twist come from the scratch copy.  The state itself does not move: how many draws the instant takes is known at its end
+    // (mt_take).  Returns the twists the scratch copy went through.
+    WDEV int mt_gen(int A) {
+        uint32_t* mt = SMT(); uint32_t* mx = SMTX();
+        const int n0 = (WRSN_MT_N - mt_idx) >> 1;
+        int tw = 0;
+        for (int r = 0, seg = 0; r < A; ++seg) {
+            const int rend = seg == 0 ? (n0 < A ? n0 : A) : (r + WRSN_MT_N / 2 < A ? r + WRSN_MT_N / 2 : A);
+            const uint32_t* src = mt; int p0 = mt_idx;
+            if (seg > 0) {
+                if (seg == 1) { for (int w = lane; w < WRSN_MT_N; w += 64) mx[w] = mt[w]; __syncthreads(); }
+                mt_twist(mx); ++tw; src = mx; p0 = 0;
+            }
+            for (int q = r + lane; q < rend; q += 64) {
+                const int p = p0 + 2 * (q - r);
+                const uint32_t a = mt_temper(src[p]) >> 5, b = mt_temper(src[p + 1]) >> 6;
+                const double u = ((double)a * 67108864.0 + (double)b) * (1.0 / 9007199254740992.0);   // random.random()
+                SGEN()[q] = (uint8_t)(u < pgp ? 1 : 0);                                             // Node.py:61
+            }
+            r = rend;
+        }
+        __syncthreads();
+        return tw;
+    }
+    // n draws were taken: the state moves like Python's (a twist only when a draw needs one); tw: twists the scratch copy went through
+    // for these draws (mt_gen), -1 none
+    WDEV void mt_take(int64_t n, int tw) {
+        mt_cnt += n;
+        const int64_t tot = (int64_t)mt_idx + 2 * n;
+        const int64_t t = tot > WRSN_MT_N ? (tot - 1) / WRSN_MT_N : 0;
+        if (t > 0 && t == tw) { for (int w = lane; w < WRSN_MT_N; w += 64) SMT()[w] = SMTX()[w]; __syncthreads(); }
+        else for (int64_t k = 0; k < t; ++k) mt_twist(SMT());
+        mt_idx = (int)(tot - t * WRSN_MT_N);
+    }
+    WDEV void mt_flush() { if (mt_pend > 0) { mt_take(mt_pend, -1); mt_pend = 0; } }
+    WDEV int alive_count() const {
+        int c = 0;
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) c += __popcll(__ballot((am >> j) & 1u));
+        return c;
+    }
+    // Generation flags (bit j: slot j) of the live sources in [a, b) when the first of them draws rank r0 and nobody in the range dies
+    // before its own turn; returns the draws of the range
+    WDEV int range_gen(int a, int b, int r0, unsigned& gm) const {
+        gm = 0; int base = r0;
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) {
+            const int i = j * 64 + lane;
+            const bool in = i >= a && i < b && ((am >> j) & 1u);
+            const unsigned long long mk = __ballot(in);
+            const int rank = base + __popcll(mk & ((1ull << lane) - 1ull));
+            if (in && (pgp1 || SGEN()[rank])) gm |= 1u << j;
+            base += __popcll(mk);
+        }
+        return base - r0;
+    }
+    WDEV void stoch_load(bool snap) {
+        const uint32_t* g = (snap ? SD()->mt_snap : SD()->mt_live) + (size_t)env * WRSN_MT_STRIDE;
+        const double* ge = (snap ? SD()->es_snap : SD()->es_live) + (size_t)env * NP;
+        for (int w = lane; w < WRSN_MT_N; w += 64) SMT()[w] = g[w];
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) { const int i = j * 64 + lane; SES()[i] = i < N ? ge[i] : 0.0; }
+        mt_idx = wu((int)g[WRSN_MT_N]);
+        mt_cnt = wu((int64_t)(((uint64_t)g[WRSN_MT_N + 2] << 32) | (uint64_t)g[WRSN_MT_N + 1]));
+        mt_pend = 0;
+        pgp = wu(SD()->pgp[env]); pgp1 = pgp == 1.0 ? 1 : 0;
+        __syncthreads();
+    }
+    WDEV void stoch_store(bool snap) {
+        mt_flush();
+        __syncthreads();
+        uint32_t* g = (snap ? SD()->mt_snap : SD()->mt_live) + (size_t)env * WRSN_MT_STRIDE;
+        for (int w = lane; w < WRSN_MT_N; w += 64) g[w] = SMT()[w];
+        if (lane == 0) { g[WRSN_MT_N] = (uint32_t)mt_idx; g[WRSN_MT_N + 1] = (uint32_t)(uint64_t)mt_cnt; g[WRSN_MT_N + 2] = (uint32_t)((uint64_t)mt_cnt >> 32); }
+        if (dirty & 1) {
+            double* ge = (snap ? SD()->es_snap : SD()->es_live) + (size_t)env * NP;
+#pragma unroll
+            for (int j = 0; j < NPL; ++j) { const int i = j * 64 + lane; if (i < N) ge[i] = SES()[i]; }
+        }
+    }
+    // k+0.5 of a second in which nobody can run dry (the drains of the routing cache, all sources generating, are upper bounds): draw,
+    // then the relay counts of the second over the GENERATING sources only -- c1 / c2 split by source id as in rebuild_cache, integer
+    // counts, so the sums do not depend on the order -- and the drains they give
+    WDEV void stoch_second(const double (&rrh)[NPL], bool any_rr) {
+        const int A = alive_count();
+        const int tw = mt_gen(A);
+        unsigned gm; (void)range_gen(0, N, 0, gm);
+        int32_t* c1 = (int32_t*)SU(); int32_t* c2 = c1 + NP;
+        int ncv[NPL];
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) { const int i = j * 64 + lane; c1[i] = 0; c2[i] = 0; ncv[j] = NFLAGS()[i < N ? i : 0] >> 8; }
+        __syncthreads();
+        {
+            int v[NPL];
+#pragma unroll
+            for (int j = 0; j < NPL; ++j) v[j] = (((gm >> j) & 1u) && ncv[j] > 0) ? SRCV()[j * 64 + lane] : -1;
+            for (int guard = 0; guard < N; ++guard) {
+                bool any = false;
+#pragma unroll
+                for (int j = 0; j < NPL; ++j) {
+                    if (v[j] >= 0) { const int i = j * 64 + lane; atomicAdd((i < v[j]) ? &c1[v[j]] : &c2[v[j]], ncv[j]); v[j] = SRCV()[v[j]]; any = true; }
+                }
+                if (!any) break;
+            }
+        }
+        __syncthreads();
+        const double er = EC()->e_recv;
+#pragma unroll
+        for (int j = 0; j < NPL; ++j) {
+            const int i = j * 64 + lane;
+            if ((am >> j) & 1u) {
+                const double es = SES()[i], per = er + es;
+                const double a1 = (double)c1[i] * per;
+                const double a2 = (double)c2[i] * per + (((gm >> j) & 1u) ? (double)ncv[j] * es : 0.0);
+                E[j] = any_rr ? fmin(E[j] - a1 + rrh[j], cap) - a2 : (E[j] - a1) - a2;
+                LOGBUF()[i] = a1 + a2;
+            }
+        }
+        __syncthreads();
+        mt_take(A, tw);
+        log_pending = 1;
     }
 
     // -------------------------------------------------------------- setup
@@ -750,6 +916,7 @@ struct Sim {
         for (int j = 0; j < NPL; ++j) {                      // send costs of all slots: independent loads, one round trip
             const int i = j * 64 + lane;
             if (rc[j] == -2) es[j] = ES_BS()[i]; else if (wsl[j] >= 0) es[j] = NBP_ES()[(size_t)i * 8 + wsl[j]]; else if (rc[j] == -1) es[j] = 0.0;
+            if constexpr (STOCH) SES()[i] = es[j];           // the masked drains of a stochastic second are counts times these
         }
         __syncthreads();
         {   // relays per second of every node: the routes of a lane's sources are walked together (overlapping LDS round trips)
@@ -827,7 +994,8 @@ struct Sim {
     }
 
     // sources [a, b) in closed form.  Returns false (nothing changed) when some node might be unable to pay.
-    WDEV bool walk_range(int a, int b, const NbRegs& nbr, const double (&es)[NPL], const double (&rrh)[NPL], double (&gain)[NPL], double margin) {
+    // gm (STOCH): generation flags of the range's sources (range_gen); sources that do not generate send nothing
+    WDEV bool walk_range(int a, int b, const NbRegs& nbr, const double (&es)[NPL], const double (&rrh)[NPL], double (&gain)[NPL], double margin, unsigned gm = ~0u) {
         int32_t* c1 = (int32_t*)SU(); int32_t* c2 = c1 + NP;
         const double er = EC()->e_recv;
 #pragma unroll
@@ -837,7 +1005,7 @@ struct Sim {
             // that their LDS round trips overlap
             int v[NPL];
 #pragma unroll
-            for (int j = 0; j < NPL; ++j) { const int q = j * 64 + lane; v[j] = (q >= a && q < b && ((am >> j) & 1u) && nbr.ncov[j] > 0) ? SRCV()[q] : -1; }
+            for (int j = 0; j < NPL; ++j) { const int q = j * 64 + lane; v[j] = (q >= a && q < b && ((am >> j) & 1u) && nbr.ncov[j] > 0 && (!STOCH || ((gm >> j) & 1u))) ? SRCV()[q] : -1; }
             for (int guard = 0; guard < N; ++guard) {
                 bool any = false;
 #pragma unroll
@@ -859,8 +1027,9 @@ struct Sim {
                 if (c1[i] > 0 && e - thr < margin) unsafe = true;
                 if (i >= a && i < b) {                             // the node wakes inside this range (Node.py:60)
                     double e2 = fmin(e + rrh[j], cap); gn[j] = e2 - e; e = e2;
-                    e -= (double)c2[i] * per + (double)nbr.ncov[j] * es[j];
-                    if ((c2[i] > 0 || (nbr.ncov[j] > 0 && es[j] > 0.0)) && e - thr < margin) unsafe = true;
+                    const int own = (!STOCH || ((gm >> j) & 1u)) ? nbr.ncov[j] : 0;
+                    e -= (double)c2[i] * per + (double)own * es[j];
+                    if ((c2[i] > 0 || (own > 0 && es[j] > 0.0)) && e - thr < margin) unsafe = true;
                 } else if (c2[i] > 0) {
                     e -= (double)c2[i] * per;
                     if (e - thr < margin) unsafe = true;
@@ -891,15 +1060,16 @@ struct Sim {
     // half-charges, so the first source after whose packets v is at / below thr is found by replaying v alone: sources
     // whose route passes v cost it (er + es_v) per packet, its own wake adds the half-charge and costs es_v per own
     // packet.  Returns that source (to be walked packet by packet; everything before it is safe), or -1.
-    WDEV int locate_failure(int a, int b, int v, const NbRegs& nbr, const double (&es)[NPL], const double (&rrh)[NPL]) {
+    WDEV int locate_failure(int a, int b, int v, const NbRegs& nbr, const double (&es)[NPL], const double (&rrh)[NPL], unsigned gm = ~0u) {
         double* pv = SU(); int32_t* rq = (int32_t*)(SU() + 8);
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < NPL; ++j) {
             const int q = j * 64 + lane;
-            if (q == v) { pv[0] = E[j]; pv[1] = EC()->e_recv + es[j]; pv[2] = es[j]; pv[3] = rrh[j]; pv[4] = (double)nbr.ncov[j]; }
+            const bool gen = !STOCH || ((gm >> j) & 1u);
+            if (q == v) { pv[0] = E[j]; pv[1] = EC()->e_recv + es[j]; pv[2] = es[j]; pv[3] = rrh[j]; pv[4] = gen ? (double)nbr.ncov[j] : 0.0; }
             int r = 0;
-            if (q >= a && q < b && q != v && ((am >> j) & 1u) && nbr.ncov[j] > 0) {
+            if (q >= a && q < b && q != v && ((am >> j) & 1u) && nbr.ncov[j] > 0 && gen) {
                 int u = SRCV()[q], guard = 0; bool hit = false;
                 while (u >= 0 && !hit && guard++ < N) { hit = (u == v); u = SRCV()[u]; }
                 r = hit ? nbr.ncov[j] : 0;
@@ -923,7 +1093,7 @@ struct Sim {
     // dies after paying).  Only the NEXT packets see a changed network, so the walk stops after the first packet with a
     // death and reports where to go on (SREQ()[3] = next packet, SREQ()[0] = packets of the source); the caller re-routes
     // with the whole wave and calls again.
-    WDEV int walk_single(int q, int p0, double (&es)[NPL], const double (&rrh)[NPL], double (&gain)[NPL]) {
+    WDEV int walk_single(int q, int p0, double (&es)[NPL], const double (&rrh)[NPL], double (&gain)[NPL], bool gen = true) {
         double* recE = SU(); double* recS = SU() + NP; int32_t* recR = (int32_t*)SCSF();
         const double er = EC()->e_recv;
         __syncthreads();
@@ -937,7 +1107,7 @@ struct Sim {
         if (lane == 0) {
             int deaths = 0, nc = 0, p = p0;
             if (SLS()[q] & 1) {
-                nc = NFLAGS()[q] >> 8;
+                nc = (!STOCH || gen) ? NFLAGS()[q] >> 8 : 0;
                 for (; p < nc && deaths == 0; ++p) {
                     int cur = q;
                     for (int hop = 0; hop <= N; ++hop) {
@@ -980,16 +1150,24 @@ struct Sim {
         // [0, N)): that evaluation is not repeated
         int a = 0, hi = N, hint = -1; bool hi_fails = true;  // hi_fails: [a, hi) is known to contain a failure; hint: believed first critical source
         bool first = true;
+        // STOCH: draws of the instant so far -- a source draws when it is alive at its own turn (Node.py:58-61), so a node killed earlier
+        // in the instant by a lower source's packets takes none; the flags of every node alive at the start are drawn up front
+        int dr = 0, tw = -1;
+        if constexpr (STOCH) { if (!pgp1) tw = mt_gen(alive_count()); }
         for (int guard = 0; a < N && guard < 16 * N + 64; ++guard) {
             if (need_recv) { WRSN_PROF_MARK(x0_) (void)walk_receivers(nbr, es); margin = teps; need_recv = false; WRSN_PROF_MARK(x1_) WRSN_PROF_SPAN(16, x0_, x1_) }   // (re-)route; a range is safe iff nobody ends at / below thr
             if (first) {
                 first = false;
-                if (uns_cnt == 1 && N > 2) { WRSN_PROF_CNT(21, 1) const int q = locate_failure(0, N, uns_node, nbr, es, rrh); if (q >= 0) { hi = q + 1; hint = q; } }
+                unsigned gm0 = ~0u;
+                if constexpr (STOCH) (void)range_gen(0, N, dr, gm0);
+                if (uns_cnt == 1 && N > 2) { WRSN_PROF_CNT(21, 1) const int q = locate_failure(0, N, uns_node, nbr, es, rrh, gm0); if (q >= 0) { hi = q + 1; hint = q; } }
             }
             if (hi_fails && hi - a <= 1) {
                 WRSN_PROF_MARK(x2_)
+                bool gen = true;
+                if constexpr (STOCH) { const int al = wu(SLS()[a] & 1); gen = al && (pgp1 || SGEN()[dr]); dr += al; }
                 for (int p0 = 0;;) {                         // packet by packet; after a packet with a death the wave re-routes
-                    const int deaths = walk_single(a, p0, es, rrh, gain);
+                    const int deaths = walk_single(a, p0, es, rrh, gain, gen);
                     const int next_p = SREQ()[3], nc = SREQ()[0];
                     __syncthreads();
                     if (deaths > 0) {
@@ -1012,22 +1190,26 @@ struct Sim {
             const int b = hi_fails ? (use_hint ? hint : a + (hi - a) / 2) : N;
             hint = -1;
             bool okr_ = false;
+            unsigned gm = ~0u; int ndr = 0;
+            if constexpr (STOCH) ndr = range_gen(a, b, dr, gm);
 #if defined(WRSN_PROFILE) && WRSN_PROFILE == 1
             for (int rep_ = 0; rep_ < 2 && !okr_; ++rep_) {      // a failing evaluation has no side effect: the second pass times the same code warm
                 WRSN_PROF_MARK(x4_)
-                okr_ = walk_range(a, b, nbr, es, rrh, gain, margin);
+                okr_ = walk_range(a, b, nbr, es, rrh, gain, margin, gm);
                 WRSN_PROF_MARK(x5_)
                 (void)x4_; (void)x5_;
             }
 #else
-            okr_ = walk_range(a, b, nbr, es, rrh, gain, margin);
+            okr_ = walk_range(a, b, nbr, es, rrh, gain, margin, gm);
 #endif
-            if (okr_) { a = b; if (a >= hi) { hi = N; hi_fails = false; } }
+            if (okr_) { a = b; dr += ndr; if (a >= hi) { hi = N; hi_fails = false; } }
             else {
                 hi = b; hi_fails = true;
                 if (uns_cnt == 1 && hi - a > 2) {            // one starving node: go straight to the source that meets it
                     WRSN_PROF_CNT(21, 1)
-                    const int q = locate_failure(a, hi, uns_node, nbr, es, rrh);
+                    unsigned gmh = ~0u;
+                    if constexpr (STOCH) (void)range_gen(a, hi, dr, gmh);
+                    const int q = locate_failure(a, hi, uns_node, nbr, es, rrh, gmh);
                     if (q >= a) { hi = q + 1; hint = q; }
                 }
             }
@@ -1036,6 +1218,7 @@ struct Sim {
 #pragma unroll
         for (int j = 0; j < NPL; ++j) if ((am >> j) & 1u) LOGBUF()[j * 64 + lane] = e_start[j] + gain[j] - E[j];
         if (any_death) { cache_dirty = 1; levels_dirty = 1; deaths_flag = 1; }
+        if constexpr (STOCH) { if (pgp1) mt_pend += dr; else mt_take(dr, tw); }
         irreg = WRSN_RING; log_pending = 1; safe_ticks = 0; n_exact++; work += 500; dirty |= 7;
         (void)any_rr;
         __syncthreads();
@@ -1088,6 +1271,10 @@ struct Sim {
             if (!fast && t_exact != 0 && n_items > 0 && (long long)wall_clock64() > t_exact) { need_heavy = 2; return; }
         }
         if (fast) {
+            if constexpr (STOCH) {                          // every live node draws (Node.py:61); with prob_gp == 1 they all generate
+                if (!pgp1) { stoch_second(rrh, any_rr); return; }
+                mt_pend += alive_count();
+            }
             if (any_rr) {
 #pragma unroll
                 for (int j = 0; j < NPL; ++j) if ((am >> j) & 1u) E[j] = fmin(E[j] - d1[j] + rrh[j], cap) - d2[j];
@@ -1105,7 +1292,7 @@ struct Sim {
 #pragma unroll
             for (int j = 0; j < NPL; ++j) if ((am >> j) & 1u) E[j] = fmin(E[j] + rrh[j], cap);
         }
-        if (irreg > 0) window_update();
+        if (irreg > 0 || (STOCH && !pgp1)) window_update();   // (a stochastic second's log is never the uniform one)
         log_pending = 0; n_ticks++;
     }
 
@@ -1123,7 +1310,8 @@ struct Sim {
             }
         }
         if (len < WRSN_RING) ring_len = len + 1; else ring_head = (head + 1) % WRSN_RING;
-        irreg--; dirty |= 4;
+        if (!STOCH || irreg > 0) irreg--;
+        dirty |= 4;
     }
 
     // alpha / (dist(node, charger) + beta)^2 (Node.py:137, WRSN.py:122) of connected node k of charger m at the charger's
@@ -1496,7 +1684,8 @@ struct Sim {
             //  looked at first: when nobody runs dry in it, it takes the same single pass)
             const bool irr = irreg > 0;
             bool guarded = false;
-            if (!one && !cache_dirty && !log_pending && !levels_dirty && node_phase == 0 &&
+            // (STOCH with prob_gp < 1: never -- the drains of a second depend on its draws, every second goes through node_half)
+            if (!one && !cache_dirty && !log_pending && !levels_dirty && node_phase == 0 && (!STOCH || pgp1) &&
                 (net_active ? (k == 0 && net_phase == 0) : (k == 2)) && ur_time == kk + 1.0) {
                 // whole seconds that fit before the next charger event / max_time and stay inside the safe horizon
                 double jf = floor(fmin(t_limit, kk + 1.0e6) - kk);
@@ -1512,6 +1701,7 @@ struct Sim {
                     if ((long long)j > left) j = left > 8 ? (int)left : 8;
                 }
                 if (j >= 1) {
+                    if constexpr (STOCH) mt_pend += (int64_t)j * alive_count();   // j seconds, nobody dies: every live node draws once a second
                     if (!any_rr && !ur_flag && !irr && !guarded) {
                         // nothing but the constant per-second drain: closed form
                         const double dj = (double)j;
@@ -2184,11 +2374,82 @@ __global__ void __launch_bounds__(64, WRSN_WAVES_PER_SIMD(NPL)) wrsn_warmup_kern
     s.dirty = 7;
     s.store(dp->snap, 0, 0);
 }
+// The warm-up of the stochastic variant: the kernel above with the generator loaded from the seeded state and stored into the snapshot.
+// (A copy of the text: the prob_gp == 1 kernel compiled through a shared template gets another register allocation than before.)
+template <int NPL>
+__device__ __forceinline__ void wrsn_warmup_stoch_env(const WrsnDev* __restrict__ dp, int env, double* smem) {
+    const int lane = threadIdx.x;
+    Sim<NPL, true, true> s;                                  // (one-off: the full simulator, everything inline)
+    s.bind(dp, env, lane, smem);
+    s.stoch_load(false);                                     // the seeded state wrsn_set_scenario_seeded wrote (random.seed, NetworkIO.py:23)
+    const WrsnEnvConst* ec = s.EC();
+    // NetworkIO.makeNetwork + Node.__init__ (Node.py:12-43) + t = 0 process start-up
+    s.am = 0;
+#pragma unroll
+    for (int j = 0; j < NPL; ++j) {
+        int i = j * 64 + lane;
+        bool real = i < s.N;
+        s.E[j] = real ? ec->capacity : 0.0; s.CS[j] = 0.0; s.d1[j] = 0.0; s.d2[j] = 0.0;
+        int al = (real && ec->capacity > ec->threshold) ? 1 : 0;
+        s.SLS()[i] = al; s.SRCV()[i] = -1;
+        s.am |= (unsigned)al << j;
+    }
+    s.now = 0.0; s.seq = 0; s.last_minfit = 0.0; s.opmax = 0.0;
+    s.n_ticks = s.n_exact = 0;
+    s.alive = 1; s.levels_dirty = 1; s.cache_dirty = 1; s.irreg = WRSN_RING; s.ring_len = 0; s.ring_head = 0;
+    s.safe_ticks = 0; s.frozen = 0; s.log_pending = 0;
+    uint64_t* la = (uint64_t*)s.SAG();
+    for (int w = lane; w < s.M * (int)(sizeof(WrsnAgent) / 8); w += 64) la[w] = 0;
+    uint64_t* lt = (uint64_t*)s.STH();
+    for (int w = lane; w < 2 * s.M * (int)(sizeof(WrsnThread) / 8); w += 64) lt[w] = 0;
+    for (int w = lane; w < s.M * s.CC; w += 64) { s.SCONN()[w] = 0; s.SCONNXY()[2 * w] = 0.0; s.SCONNXY()[2 * w + 1] = 0.0; }
+    for (int w = lane; w <= s.M; w += 64) { s.SCTR()[w] = 0; s.SCP()[w] = 0; s.SCA()[w] = 0; s.SCT()[w] = 0; s.SCS()[w] = 0; }
+    __syncthreads();
+    if (lane == 0) {
+        s.SREQ()[0] = 0; s.SREQ()[1] = 0; s.SREQ()[2] = 0; s.SURN()[0] = 0; s.SRRN()[0] = 0;
+        for (int m = 0; m < s.M; ++m) {                      // MobileCharger.__init__ + WRSN.py:44-49
+            s.SAG()[m].loc[0] = ec->bs[0]; s.SAG()[m].loc[1] = ec->bs[1]; s.SAG()[m].energy = ec->mc_capacity; s.SAG()[m].charging_rate = 0.0;
+            s.SAG()[m].status = 1; s.mc_check_status(m);
+            s.SAG()[m].type_charging = 0; s.SAG()[m].n_conn = 0; s.SAG()[m].cur_thread = -1; s.SAG()[m].n_live = 0;
+            s.SAG()[m].cur[0] = ec->bs[0]; s.SAG()[m].cur[1] = ec->bs[1]; s.SAG()[m].cur[2] = 0.0;
+            s.SAG()[m].excl = 0.0; s.SAG()[m].prev_minfit = 0.0;
+            s.SAG()[m].conn_loc[0] = ec->bs[0]; s.SAG()[m].conn_loc[1] = ec->bs[1];
+        }
+    }
+    // Network.operate -> timeout(0.1); update_reward body at t = 0 (no charger is charging) -> timeout(1); nodes -> timeout(0.5)
+    s.net_active = 1; s.net_phase = 0; s.net_time = s.now + 1.0 / 10.0; s.net_seq = s.seq++;
+    s.ur_time = s.now + 1.0; s.ur_seq = s.seq++;
+    s.node_phase = 0; s.node_time = s.now + 1.0 * 0.5; s.node_seq = s.seq++;
+    s.use_snap = 1;
+    __syncthreads();
+    s.run(true, ec->warm_up_time);                           // env.run(until=warm_up_time): stops before that instant's NORMAL events
+    double fit = s.min_fitness();
+    s.last_minfit = fit; s.fit_dirty = 0; s.map1_valid = 0;
+    if (lane == 0) {
+        for (int m = 0; m < s.M; ++m) {                      // WRSN.py:59-64
+            s.SAG()[m].action[0] = (ec->bs[0] - ec->frame[0]) / (ec->frame[1] - ec->frame[0]);
+            s.SAG()[m].action[1] = (ec->bs[1] - ec->frame[2]) / (ec->frame[3] - ec->frame[2]);
+            s.SAG()[m].action[2] = 0.0;
+            s.SAG()[m].cur_thread = s.new_thread(m, s.SAG()[m].cur[0], s.SAG()[m].cur[1], s.SAG()[m].cur[2]);
+            s.SAG()[m].prev_minfit = fit; s.SAG()[m].excl = 0.0;
+        }
+    }
+    s.dirty = 7;
+    s.store(dp->snap, 0, 0);
+    s.stoch_store(true);                                     // the snapshot reset() restores holds the generator too (NetworkIO.py:22-24)
+}
+template <int NPL>
+__global__ void __launch_bounds__(64, WRSN_WAVES_PER_SIMD(NPL)) wrsn_warmup_stoch_kernel(const WrsnDev* __restrict__ dp, int env0) {
+    extern __shared__ double smem[];
+    const int env = env0 + blockIdx.x;
+    if (env >= dp->B) return;
+    wrsn_warmup_stoch_env<NPL>(dp, env, smem);
+}
 
 // `handoff`: 0 = one block per environment in the launch order (`block0`: the launch covers blocks block0 .. of it); 3 = time-sliced launch.
 //            4 = (wrsn_step_env_full only) go on with the step in flight of this environment, whatever the caller's rows say.
 // Returns (work units spent << 1) | 1 when the HEAVY = false simulator stopped in front of a grid item it has no code for.
-template <int NPL, bool HEAVY>
+template <int NPL, bool HEAVY, bool STOCH = false>
 __device__ __forceinline__ int wrsn_step_env(const WrsnDev* __restrict__ dp, int env, int reset_call, const int32_t* __restrict__ agent_id,
                                              const double* __restrict__ action, int auto_reset, int budget, long long epoch,
                                              const uint8_t* __restrict__ env_mask, const WrsnStepOutDev& out, int handoff, int deadline, double* smem, long long t_end);
@@ -2203,10 +2464,10 @@ __device__ __noinline__ void wrsn_step_env_full(const WrsnDev* dp, int env, long
     (void)wrsn_step_env<NPL, true>(dp, env, 0, nullptr, nullptr, 0, 1, epoch, nullptr, out, 4, 0, smem, 0);
 }
 
-template <int NPL, bool HEAVY>
-__global__ void __launch_bounds__(64, WRSN_WAVES_PER_SIMD(NPL))
-wrsn_step_kernel(const WrsnDev* __restrict__ dp, int reset_call, const int32_t* __restrict__ agent_id, const double* __restrict__ action, int auto_reset,
-                 int budget, long long epoch, int slots, const uint8_t* __restrict__ env_mask, WrsnStepOutDev out, int handoff, int deadline, int block0) {
+template <int NPL, bool HEAVY, bool STOCH>
+__device__ __forceinline__ void wrsn_step_blocks(const WrsnDev* dp, int reset_call, const int32_t* agent_id, const double* action,
+                                                 int auto_reset, int budget, long long epoch, int slots, const uint8_t* env_mask, WrsnStepOutDev out,
+                                                 int handoff, int deadline, int block0) {
     extern __shared__ double smem[];
     // Block b of a step launch takes environment order[b]: the environments sorted by the work their WRSN.step still needs,
     // longest first (wrsn_estimate_kernel / wrsn_sort_kernel run in front of every step launch).  The duration of a WRSN.step is
@@ -2254,7 +2515,7 @@ wrsn_step_kernel(const WrsnDev* __restrict__ dp, int reset_call, const int32_t* 
     }
     if (env < 0 || env >= dp->B) return;
     for (int pass = 0; pass < 256; ++pass) {
-        const int r = wrsn_step_env<NPL, HEAVY>(dp, env, reset_call, agent_id, action, auto_reset, budget, epoch, env_mask, out, handoff, deadline, smem, t_slice_end);   // the one call site
+        const int r = wrsn_step_env<NPL, HEAVY, STOCH>(dp, env, reset_call, agent_id, action, auto_reset, budget, epoch, env_mask, out, handoff, deadline, smem, t_slice_end);   // the one call site
         if (HEAVY || !(r & 1)) break;
         // the common-path simulator stopped in front of a rare service: the full simulator takes that one item, then this one goes on
         __syncthreads();
@@ -2264,8 +2525,21 @@ wrsn_step_kernel(const WrsnDev* __restrict__ dp, int reset_call, const int32_t* 
         if (budget > 0) { budget -= (r >> 1) + 64; if (budget < 16) budget = 16; }
     }
 }
-
 template <int NPL, bool HEAVY>
+__global__ void __launch_bounds__(64, WRSN_WAVES_PER_SIMD(NPL))
+wrsn_step_kernel(const WrsnDev* __restrict__ dp, int reset_call, const int32_t* __restrict__ agent_id, const double* __restrict__ action, int auto_reset,
+                 int budget, long long epoch, int slots, const uint8_t* __restrict__ env_mask, WrsnStepOutDev out, int handoff, int deadline, int block0) {
+    wrsn_step_blocks<NPL, HEAVY, false>(dp, reset_call, agent_id, action, auto_reset, budget, epoch, slots, env_mask, out, handoff, deadline, block0);
+}
+// the stochastic variant (prob_gp < 1): the full simulator with the MT19937 draws; same arguments, same launches
+template <int NPL>
+__global__ void __launch_bounds__(64, WRSN_WAVES_PER_SIMD(NPL))
+wrsn_step_stoch_kernel(const WrsnDev* __restrict__ dp, int reset_call, const int32_t* __restrict__ agent_id, const double* __restrict__ action, int auto_reset,
+                       int budget, long long epoch, int slots, const uint8_t* __restrict__ env_mask, WrsnStepOutDev out, int handoff, int deadline, int block0) {
+    wrsn_step_blocks<NPL, true, true>(dp, reset_call, agent_id, action, auto_reset, budget, epoch, slots, env_mask, out, handoff, deadline, block0);
+}
+
+template <int NPL, bool HEAVY, bool STOCH>
 __device__ __forceinline__ int wrsn_step_env(const WrsnDev* __restrict__ dp, int env, int reset_call, const int32_t* __restrict__ agent_id,
                                              const double* __restrict__ action, int auto_reset, int budget, long long epoch,
                                              const uint8_t* __restrict__ env_mask, const WrsnStepOutDev& out, int handoff, int deadline, double* smem, long long t_end) {
@@ -2288,7 +2562,7 @@ __device__ __forceinline__ int wrsn_step_env(const WrsnDev* __restrict__ dp, int
         if (auto_reset && dp->live.dyn[env].terminal_pending) do_reset = true;
     }
     if (reset_call && lane == 0) dp->live.dyn[env].lat_valid = 0;   // a reset environment holds no latched action
-    Sim<NPL, HEAVY> s;
+    Sim<NPL, HEAVY, STOCH> s;
     s.bind(dp, env, lane, smem);
     if (handoff == 3) { s.t_deadline = t_end; s.t_exact = t_end - (deadline / 2 < WRSN_EXACT_MARGIN ? deadline / 2 : WRSN_EXACT_MARGIN); }   // the time-sliced launch stamped its start itself
     else if (deadline > 0 && budget > 0 && !reset_call) {    // common deadline of the launch: `deadline` ticks after its first wave started
@@ -2309,7 +2583,7 @@ __device__ __forceinline__ int wrsn_step_env(const WrsnDev* __restrict__ dp, int
     const long long wt0_ = wall_clock64();
 #endif
     const WrsnEnvConst* ec = s.EC();
-    { WRSN_P4_MARK(k0_) s.load(do_reset ? dp->snap : dp->live); WRSN_P4_MARK(k1_)
+    { WRSN_P4_MARK(k0_) s.load(do_reset ? dp->snap : dp->live); if constexpr (STOCH) s.stoch_load(do_reset); WRSN_P4_MARK(k1_)
 #if defined(WRSN_PROFILE) && WRSN_PROFILE == 4
       s.prof_[16] += k1_ - k0_; s.prof_[18] += k0_ - kt0_;
 #endif
@@ -2419,7 +2693,7 @@ __device__ __forceinline__ int wrsn_step_env(const WrsnDev* __restrict__ dp, int
             dp->render_agent[env] = agent; dp->row_state[env] = terminal ? 4 : 1;
         }
     }
-    { WRSN_P4_MARK(k4_) s.store(dp->live, terminal, (do_reset || susp) ? 0 : 1, susp); WRSN_P4_MARK(k5_)
+    { WRSN_P4_MARK(k4_) s.store(dp->live, terminal, (do_reset || susp) ? 0 : 1, susp); if constexpr (STOCH) s.stoch_store(false); WRSN_P4_MARK(k5_)
 #if defined(WRSN_PROFILE) && WRSN_PROFILE == 4
       s.prof_[17] += k5_ - k4_;
 #endif

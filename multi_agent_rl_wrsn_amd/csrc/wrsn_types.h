@@ -127,6 +127,19 @@ struct WrsnDev {
                                       //        environment kernel for every row, including the rows it leaves untouched
 };
 
+// prob_gp < 1 (Node.py:61): Python's MT19937 per environment.  A handle that runs the stochastic kernels keeps this block in device
+// memory right behind its WrsnDev copy (the kernels of the prob_gp == 1 path never look at it; their descriptor is unchanged).
+#define WRSN_MT_N 624
+#define WRSN_MT_STRIDE 628               // per environment: 624 state words, index, draw count (low, high word), pad
+struct WrsnStochDev {
+    uint32_t *mt_live, *mt_snap;         // [B][WRSN_MT_STRIDE]  current state / state after the warm-up (reset() restores it)
+    double *es_live, *es_snap;           // [B][NP] send cost of one packet over the cached route (what rebuild_cache derived d1, d2 from)
+    double *pgp;                         // [B]     prob_gp
+};
+// LDS of the stochastic variant on top of wrsn_lds_bytes: state words, a scratch copy for draws beyond the next twist, the send
+// costs, one generation flag per draw of an instant
+static inline int wrsn_stoch_lds_bytes(int NP) { return 2 * WRSN_MT_N * 4 + NP * 8 + ((NP + 15) & ~15) + 16; }
+
 struct WrsnStepOutDev {
     int32_t *agent_id; double *reward; uint8_t *terminal; double *now; float *obs; int32_t *status;
 };

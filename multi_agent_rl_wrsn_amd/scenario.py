@@ -33,6 +33,9 @@ class Scenario:
     max_time: float = DEFAULT_MAX_TIME
     seed: int = 0
     name: str = "scenario"
+    # prob_gp != 1 (Node.py:61: one random.random() per live node and second, packets only below prob_gp) has to be asked for: the
+    # environment then draws from Python's MT19937 seeded with `seed` (NetworkIO.py:22-23) and runs on the stochastic kernels
+    stochastic_packets: bool = False
 
     def __post_init__(self):
         self.node_xy = np.ascontiguousarray(self.node_xy, dtype=np.float64).reshape(-1, 2)
@@ -41,10 +44,17 @@ class Scenario:
         missing = [k for k in NODE_SPEC_KEYS if k not in self.node_spec]
         if missing:
             raise KeyError("node_phy_spe lacks %s" % missing)
-        if float(self.node_spec["prob_gp"]) != 1.0:
+        pgp = float(self.node_spec["prob_gp"])
+        if pgp != 1.0 and not self.stochastic_packets:
             # Node.py:61 draws Python's MT19937 once per alive node per second; every shipped scenario
-            # has prob_gp == 1 (the draw is then irrelevant).  prob_gp < 1 is unpinned and unsupported.
-            raise ValueError("only prob_gp == 1 is supported (all shipped scenarios)")
+            # has prob_gp == 1 (the draw is then irrelevant).  Other values need stochastic_packets=True.
+            raise ValueError("prob_gp != 1 needs Scenario(..., stochastic_packets=True) (all shipped scenarios have prob_gp == 1)")
+        if self.stochastic_packets:
+            if not (0.0 <= pgp <= 1.0):
+                raise ValueError("prob_gp must lie in [0, 1], got %r" % pgp)
+            if int(self.seed) != self.seed or not (-2 ** 63 <= int(self.seed) < 2 ** 63):
+                raise ValueError("seed must be an integer in the int64 range, got %r" % (self.seed,))
+            self.seed = int(self.seed)
 
     @property
     def n_node(self):
@@ -72,13 +82,15 @@ def load_scenario_yaml(path):
     """Read a scenario file in the reference's format (NetworkIO.py:15-17, 19-34).
 
     Raises KeyError('max_time') for the `bacgiang_*` files exactly like the reference does
-    (NetworkIO.py:34)."""
+    (NetworkIO.py:34).  A file with prob_gp != 1 gives a scenario with
+    stochastic_packets=True: the reference runs it, seeded with the file's `seed` (NetworkIO.py:22-23)."""
     import yaml
     with open(path, "r") as f:
         d = yaml.safe_load(f)
     return Scenario(node_xy=np.array(d["nodes"], dtype=np.float64), target_xy=np.array(d["targets"], dtype=np.float64),
                     bs_xy=np.array(d["base_station"], dtype=np.float64), node_spec=dict(d["node_phy_spe"]),
-                    max_time=float(d["max_time"]), seed=int(d["seed"]), name=str(path))
+                    max_time=float(d["max_time"]), seed=int(d["seed"]), name=str(path),
+                    stochastic_packets=float(d["node_phy_spe"]["prob_gp"]) != 1.0)
 
 
 def load_mc_yaml(path):
@@ -101,7 +113,7 @@ def scenario_from_golden(z):
     return sc, mc_spec
 
 
-def synth_scenario(seed, n_node=200, n_target=200, side=None, node_spec=None, max_time=DEFAULT_MAX_TIME):
+def synth_scenario(seed, n_node=200, n_target=200, side=None, node_spec=None, max_time=DEFAULT_MAX_TIME, stochastic_packets=False):
     """Seeded synthetic network of SURVEY.md section 8d: chain-like relay trees rooted at a base station in
     the middle of a side x side field (shipped scenarios: mean degree 2.05-2.26, routes 22-34 hops), with
     every target inside the sensing range of a node that is connected to the base station at t = 0 --
@@ -110,6 +122,7 @@ def synth_scenario(seed, n_node=200, n_target=200, side=None, node_spec=None, ma
     The generator itself is host code behind the C-ABI (`wrsn_synth_network`, csrc/wrsn_api.hip; its own
     xoshiro256** stream keyed by `seed`), so env e of a batch is reproducible from base_seed + e and 4096
     networks take well under a second.  side=None keeps the shipped node density (1000 m for <= 200 nodes).
+    stochastic_packets goes to the Scenario (node_spec with prob_gp != 1 needs it; `seed` then also seeds the packet draws).
     """
     from . import _lib
     spec = dict(DEFAULT_NODE_SPEC if node_spec is None else node_spec)
@@ -119,7 +132,7 @@ def synth_scenario(seed, n_node=200, n_target=200, side=None, node_spec=None, ma
                                            float(spec["com_range"]), float(spec["sen_range"]),
                                            node_xy.ctypes.data, target_xy.ctypes.data, bs.ctypes.data))
     return Scenario(node_xy=node_xy, target_xy=target_xy, bs_xy=bs, node_spec=spec, max_time=max_time, seed=int(seed),
-                    name="synth_n%d_t%d_s%d" % (n_node, n_target, seed))
+                    name="synth_n%d_t%d_s%d" % (n_node, n_target, seed), stochastic_packets=bool(stochastic_packets))
 
 
 def synth_batch(base_seed, n_env, n_node=200, n_target=200, n_unique=None, **kw):
