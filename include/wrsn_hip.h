@@ -253,6 +253,36 @@ int wrsn_kernel_times(wrsn_t *h, float *ms);
 /* Wait for the handle's stream. */
 int wrsn_sync(wrsn_t *h);
 
+/* ENVIRONMENT RECORDS: save, load and clone running environments.  A record is the whole state of one environment -- scenario
+ * constants, topology, the live state and the post-warm-up snapshot reset() restores (WrsnEnvDyn: a step in flight, a latched
+ * action, terminal_pending), the MT19937 generator when the handle keeps one -- plus the row's pending request, behind a header
+ * (magic, format version, struct sizes, NP, TP, ECAP, CCAP, M, n_node, n_target, conn_bound, generator block).  After a load or a
+ * clone a destination behaves exactly as the source would have: bit-identical requests in blocking mode, the launch-mode contract
+ * with a step budget, the pipeline or time slices.  Not carried over: the destination keeps its counters since create (n_steps,
+ * wrsn_counters [3..5], the rollout table) and its diagnostic counters; map 1 reuse starts afresh (wrsn_set_obs_reuse); a following
+ * wrsn_rollout_collect appends nothing for a replaced row.
+ * Index arrays are HOST int32 [n], checked on the host (in range; saved / cloned-from environments hold a scenario; load and clone
+ * destinations distinct; no clone destination is also a source).  Records and request rows are DEVICE memory (16-byte aligned). */
+
+/* Bytes of one record of this handle (a multiple of 256; about 220 KB at 200 nodes with the default capacities). */
+int wrsn_env_record_bytes(wrsn_t *h, int64_t *bytes);
+
+/* Write n records, record i = environment env[i] with its pending request (req->agent_id, reward, terminal, now, status
+ * non-NULL; obs ignored), into dst [n, record bytes].  Asynchronous on the handle's stream. */
+int wrsn_save_envs(wrsn_t *h, const int32_t *env, int32_t n, const wrsn_step_out *req, void *dst);
+
+/* Replace environment env[i] by record i of src (n records back to back) and write its saved request into row env[i] of out (NULL
+ * fields are skipped; with out->obs, rows with agent_id >= 0 are rendered, the others left untouched).  Validates every header
+ * first and changes nothing when one does not fit (WRSN_ERR_ARG naming the field).  A record fits a handle with equal NP, TP, ECAP,
+ * CCAP and M, n_node <= N and n_target <= T; map_size, B and the device may differ.  A record with a generator block loads only
+ * into a handle that keeps generators or holds no scenario yet (which then gets them, and runs the stochastic kernels when a loaded
+ * prob_gp != 1); one without only into a handle without generators.  Synchronous, like wrsn_set_scenario. */
+int wrsn_load_envs(wrsn_t *h, const int32_t *env, int32_t n, const void *src, const wrsn_step_out *out);
+
+/* dst[i] becomes a copy of src[i] (device to device), and row src[i] of out is copied to row dst[i] (obs rendered as for a load;
+ * needs out->agent_id then).  Asynchronous on the handle's stream. */
+int wrsn_clone_envs(wrsn_t *h, const int32_t *src, const int32_t *dst, int32_t n, const wrsn_step_out *out);
+
 /* Device counters, summed over the environments.  HOST pointer to 8 x int64.  Synchronises.
  *   [0] simulated seconds, [1] packet-exact seconds, [2] charger events of the episodes in progress (they restart at
  *       every reset: the warm-up is part of them);

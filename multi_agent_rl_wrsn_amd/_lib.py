@@ -26,7 +26,8 @@ ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max"
 
 # every entry point include/wrsn_hip.h declares
 EXPORTS = ("wrsn_create", "wrsn_destroy", "wrsn_set_stream", "wrsn_set_scenario", "wrsn_set_scenario_seeded", "wrsn_reset", "wrsn_step",
-           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_render", "wrsn_set_obs_reuse", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_synth_network",
+           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_render", "wrsn_set_obs_reuse", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
+           "wrsn_clone_envs", "wrsn_synth_network",
            "wrsn_last_error",
            "wrsn_version")
 
@@ -109,6 +110,14 @@ def bind(lib):
     lib.wrsn_sync.restype = C.c_int
     lib.wrsn_counters.argtypes = [vp, vp]
     lib.wrsn_counters.restype = C.c_int
+    lib.wrsn_env_record_bytes.argtypes = [vp, vp]
+    lib.wrsn_env_record_bytes.restype = C.c_int
+    lib.wrsn_save_envs.argtypes = [vp, vp, C.c_int32, C.POINTER(WrsnStepOut), vp]
+    lib.wrsn_save_envs.restype = C.c_int
+    lib.wrsn_load_envs.argtypes = [vp, vp, C.c_int32, vp, C.POINTER(WrsnStepOut)]
+    lib.wrsn_load_envs.restype = C.c_int
+    lib.wrsn_clone_envs.argtypes = [vp, vp, vp, C.c_int32, C.POINTER(WrsnStepOut)]
+    lib.wrsn_clone_envs.restype = C.c_int
     lib.wrsn_synth_network.argtypes = [C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, vp, vp, vp]
     lib.wrsn_synth_network.restype = C.c_int
     lib.wrsn_last_error.argtypes = []
@@ -290,6 +299,37 @@ class RawHandle:
             raise ValueError("unknown peek selector %r" % (what,))
         check(self.lib, self.lib.wrsn_peek(self._h, int(what), a.ctypes.data))
         return a
+
+    # -- environment records (wrsn_save_envs / wrsn_load_envs / wrsn_clone_envs); index arrays are host int32 arrays
+    def env_record_bytes(self):
+        n = C.c_int64(0)
+        check(self.lib, self.lib.wrsn_env_record_bytes(self._h, C.byref(n)))
+        return int(n.value)
+
+    @staticmethod
+    def _idx(a):
+        import numpy as np
+        return np.ascontiguousarray(np.asarray(a).reshape(-1), dtype=np.int32)
+
+    def save_envs(self, env_idx, dst_ptr, **req_ptrs):
+        """Records of environments env_idx into dst_ptr ([n, env_record_bytes()] bytes, device); req_ptrs: the request rows."""
+        e = self._idx(env_idx)
+        o = self._out(**req_ptrs)
+        check(self.lib, self.lib.wrsn_save_envs(self._h, e.ctypes.data, len(e), C.byref(o), C.c_void_p(dst_ptr)))
+
+    def load_envs(self, env_idx, src_ptr, **out_ptrs):
+        """Replace environments env_idx by the records at src_ptr (device) and write their saved requests into out_ptrs."""
+        e = self._idx(env_idx)
+        o = self._out(**out_ptrs)
+        check(self.lib, self.lib.wrsn_load_envs(self._h, e.ctypes.data, len(e), C.c_void_p(src_ptr), C.byref(o)))
+
+    def clone_envs(self, src_idx, dst_idx, **out_ptrs):
+        """Environment dst_idx[i] becomes a copy of src_idx[i]; request row src -> row dst of out_ptrs."""
+        s, d = self._idx(src_idx), self._idx(dst_idx)
+        if len(s) != len(d):
+            raise ValueError("src and dst differ in length (%d, %d)" % (len(s), len(d)))
+        o = self._out(**out_ptrs)
+        check(self.lib, self.lib.wrsn_clone_envs(self._h, s.ctypes.data, d.ctypes.data, len(s), C.byref(o)))
 
     def counters(self):
         import numpy as np

@@ -14,6 +14,7 @@
 #include "../../include/wrsn_hip.h"
 #include "wrsn_sim.h"
 #include "wrsn_rollout.h"
+#include "wrsn_state.h"
 
 namespace {
 
@@ -90,6 +91,14 @@ struct wrsn_handle {
     WrsnDev* d_dev;            // device copy of `dev`: the environment kernels read it through the constant cache; `sd` follows it
     WrsnStochDev sd;           // prob_gp < 1: MT19937 state, send costs, prob_gp per environment (allocated by the first seeded call)
     int stoch;                 // an environment was loaded with prob_gp != 1 through wrsn_set_scenario_seeded: the stochastic kernels run
+    std::vector<uint8_t> filled;   // per environment: holds a scenario (wrsn_set_scenario*, wrsn_load_envs, wrsn_clone_envs)
+    // environment records (wrsn_state.h): the segment table of this handle's layout (generator block iff sd.mt_live), on the host and in
+    // device memory; staging for the host index arrays, the gathered headers of a load and the charger list of the observation pass
+    WrsnSeg segs[WRSN_REC_MAXSEG]; int nseg; int64_t rec_bytes;
+    WrsnSeg* d_segs;
+    int32_t* d_idx; size_t idx_cap;
+    uint8_t* d_hdr;                // [B] headers (destinations of a load are distinct)
+    int32_t* d_rend;
 };
 
 namespace {
@@ -308,6 +317,8 @@ void mt_seed(int64_t seed, uint32_t* st) {
     st[WRSN_MT_N] = WRSN_MT_N; st[WRSN_MT_N + 1] = 0; st[WRSN_MT_N + 2] = 0; st[WRSN_MT_N + 3] = 0;
 }
 
+int rec_layout(wrsn_handle* h);
+
 // the stochastic block of a handle: MT state (live / snapshot), send costs (live / snapshot), prob_gp = 1 everywhere until set
 int alloc_stoch(wrsn_handle* h) {
     if (h->sd.mt_live) return 0;
@@ -321,6 +332,134 @@ int alloc_stoch(wrsn_handle* h) {
     std::vector<double> one(B, 1.0);
     HIPCHK(hipMemcpy(h->sd.pgp, one.data(), B * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->d_dev + 1, &h->sd, sizeof(WrsnStochDev), hipMemcpyHostToDevice));
+    return rec_layout(h);                                      // records of this handle carry the generator block from now on
+}
+
+// ------------------------------------------------------------------ environment records (wrsn_state.h)
+// The segments of a record in record order: every per-environment slice of the handle's arrays.  with_gen: the generator block too
+// (its base addresses are the handle's, 0 while it has none: then the table only serves to size a record).  Returns the record bytes.
+int64_t rec_segments(const wrsn_handle* h, int with_gen, WrsnSeg* segs, int* nseg) {
+    const WrsnDev& d = h->dev;
+    const int64_t NP = d.NP, TP = d.TP;
+    int ns = 0; int64_t off = WRSN_REC_HDR;
+    auto add = [&](const void* base, int64_t bytes, int kind) {
+        WrsnSeg& g = segs[ns++];
+        g.base = (uint64_t)(uintptr_t)base; g.stride = bytes; g.bytes = (int32_t)bytes; g.c0 = (int32_t)(off / 16); g.pad = 0;
+        g.kind = kind != WRSN_SEG_V16 ? kind : ((g.base % 16 == 0 && bytes % 16 == 0) ? WRSN_SEG_V16 : WRSN_SEG_WORD);
+        off += (bytes + 15) & ~(int64_t)15;
+    };
+    add(d.ec, sizeof(WrsnEnvConst), WRSN_SEG_V16);
+    add(d.node_x, NP * 8, WRSN_SEG_V16); add(d.node_y, NP * 8, WRSN_SEG_V16); add(d.dist_bs, NP * 8, WRSN_SEG_V16);
+    add(d.target_x, TP * 8, WRSN_SEG_V16); add(d.target_y, TP * 8, WRSN_SEG_V16);
+    add(d.nb_off, (NP + 1) * 4, WRSN_SEG_V16); add(d.nb_idx, (int64_t)d.ECAP * 4, WRSN_SEG_V16); add(d.nb_dist, (int64_t)d.ECAP * 8, WRSN_SEG_V16);
+    add(d.tc_off, (TP + 1) * 4, WRSN_SEG_V16); add(d.tc_idx, (int64_t)d.CCAP * 4, WRSN_SEG_V16);
+    add(d.ncov, NP * 4, WRSN_SEG_V16); add(d.nflags, NP * 4, WRSN_SEG_V16); add(d.nbp, NP * 16, WRSN_SEG_V16);
+    add(d.nbp_es, NP * 64, WRSN_SEG_V16); add(d.es_bs, NP * 8, WRSN_SEG_V16); add(d.adjm, NP * 32, WRSN_SEG_V16);
+    add(d.xorder, NP * 4, WRSN_SEG_V16); add(d.tcp, TP * 16, WRSN_SEG_V16);
+    for (int k = 0; k < 2; ++k) {
+        const WrsnNodeArrays& a = k == 0 ? d.live : d.snap;
+        add(a.E, NP * 8, WRSN_SEG_V16); add(a.CS, NP * 8, WRSN_SEG_V16); add(a.RR, NP * 8, WRSN_SEG_V16);
+        add(a.d1, NP * 8, WRSN_SEG_V16); add(a.d2, NP * 8, WRSN_SEG_V16); add(a.ring, WRSN_RING * NP * 8, WRSN_SEG_V16);
+        add(a.logbuf, NP * 8, WRSN_SEG_V16); add(a.ls, NP * 4, WRSN_SEG_V16); add(a.rcv, NP * 4, WRSN_SEG_V16);
+        add(a.conn, WRSN_MAX_MC * WRSN_CONN_CAP * 2, WRSN_SEG_V16); add(a.conn_xy, WRSN_MAX_MC * WRSN_CONN_CAP * 2 * 8, WRSN_SEG_V16);
+        add(a.dyn, sizeof(WrsnEnvDyn), k == 0 ? WRSN_SEG_DYN : WRSN_SEG_V16);
+    }
+    if (with_gen) {
+        add(h->sd.mt_live, WRSN_MT_STRIDE * 4, WRSN_SEG_V16); add(h->sd.mt_snap, WRSN_MT_STRIDE * 4, WRSN_SEG_V16);
+        add(h->sd.es_live, NP * 8, WRSN_SEG_V16); add(h->sd.es_snap, NP * 8, WRSN_SEG_V16); add(h->sd.pgp, 8, WRSN_SEG_V16);
+    }
+    *nseg = ns;
+    return (off + 255) & ~(int64_t)255;
+}
+
+// the handle's own layout (generator block iff it keeps generators), uploaded for the copy kernel
+int rec_layout(wrsn_handle* h) {
+    h->rec_bytes = rec_segments(h, h->sd.mt_live ? 1 : 0, h->segs, &h->nseg);
+    HIPCHK(hipMemcpy(h->d_segs, h->segs, (size_t)h->nseg * sizeof(WrsnSeg), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// what every record of this handle says about its geometry (wrsn_rec_header_kernel adds the environment's own fields)
+WrsnRecHeader rec_template(const wrsn_handle* h) {
+    WrsnRecHeader t; std::memset(&t, 0, sizeof(t));
+    t.magic = WRSN_REC_MAGIC; t.version = WRSN_REC_VERSION; t.ec_bytes = (int32_t)sizeof(WrsnEnvConst); t.dyn_bytes = (int32_t)sizeof(WrsnEnvDyn);
+    t.NP = h->dev.NP; t.TP = h->dev.TP; t.ECAP = h->dev.ECAP; t.CCAP = h->dev.CCAP; t.M = h->dev.M;
+    t.has_gen = h->sd.mt_live ? 1 : 0; t.nseg = h->nseg; t.rec_bytes = h->rec_bytes; t.prob_gp = 1.0;
+    return t;
+}
+
+// Is record i a record this handle can load?  (Geometry, sizes, format; not yet whether its generator block fits the handle.)
+int rec_check(const wrsn_handle* h, const WrsnRecHeader& r, int i) {
+    const WrsnDev& d = h->dev;
+    auto bad = [&](const char* field, long long got, long long want) {
+        return fail(WRSN_ERR_ARG, "record " + std::to_string(i) + ": " + field + " is " + std::to_string(got) + ", this handle needs " + std::to_string(want));
+    };
+    if (r.magic != WRSN_REC_MAGIC) return bad("magic", (long long)r.magic, (long long)WRSN_REC_MAGIC);
+    if (r.version != WRSN_REC_VERSION) return bad("version", (long long)r.version, WRSN_REC_VERSION);
+    if (r.ec_bytes != (int32_t)sizeof(WrsnEnvConst)) return bad("ec_bytes (sizeof(WrsnEnvConst))", r.ec_bytes, (long long)sizeof(WrsnEnvConst));
+    if (r.dyn_bytes != (int32_t)sizeof(WrsnEnvDyn)) return bad("dyn_bytes (sizeof(WrsnEnvDyn))", r.dyn_bytes, (long long)sizeof(WrsnEnvDyn));
+    if (r.NP != d.NP) return bad("NP", r.NP, d.NP);
+    if (r.TP != d.TP) return bad("TP", r.TP, d.TP);
+    if (r.ECAP != d.ECAP) return bad("ECAP", r.ECAP, d.ECAP);
+    if (r.CCAP != d.CCAP) return bad("CCAP", r.CCAP, d.CCAP);
+    if (r.M != d.M) return bad("M", r.M, d.M);
+    if (r.n_node < 1 || r.n_node > d.N) return bad("n_node", r.n_node, d.N);
+    if (r.n_target < 1 || r.n_target > d.T) return bad("n_target", r.n_target, d.T);
+    if (r.conn_bound < 0 || r.conn_bound > WRSN_CONN_CAP) return bad("conn_bound", r.conn_bound, WRSN_CONN_CAP);
+    if (r.has_gen != 0 && r.has_gen != 1) return bad("has_gen", r.has_gen, 1);
+    WrsnSeg tmp[WRSN_REC_MAXSEG]; int ns = 0;
+    const int64_t want = rec_segments(h, r.has_gen, tmp, &ns);
+    if (r.nseg != ns) return bad("nseg", r.nseg, ns);
+    if (r.rec_bytes != want) return bad("rec_bytes", r.rec_bytes, want);
+    if (!(r.prob_gp >= 0.0 && r.prob_gp <= 1.0) || (!r.has_gen && r.prob_gp != 1.0)) return fail(WRSN_ERR_ARG, "record " + std::to_string(i) + ": prob_gp out of range");
+    return 0;
+}
+
+// host index arrays: every index in [0, B); `distinct`: no index twice; `filled`: every environment holds a scenario
+int check_envs(const wrsn_handle* h, const int32_t* env, int32_t n, bool distinct, bool filled, const char* what) {
+    std::vector<uint8_t> seen(distinct ? h->dev.B : 0, 0);
+    for (int32_t i = 0; i < n; ++i) {
+        const int32_t e = env[i];
+        if (e < 0 || e >= h->dev.B) return fail(WRSN_ERR_ARG, std::string(what) + "[" + std::to_string(i) + "] = " + std::to_string(e) + " is out of range");
+        if (filled && !h->filled[e]) return fail(WRSN_ERR_ARG, std::string(what) + "[" + std::to_string(i) + "]: environment " + std::to_string(e) + " holds no scenario");
+        if (distinct) { if (seen[e]) return fail(WRSN_ERR_ARG, std::string(what) + ": environment " + std::to_string(e) + " appears twice"); seen[e] = 1; }
+    }
+    return 0;
+}
+
+// room for `n` staged indices
+int ensure_idx(wrsn_handle* h, size_t n) {
+    if (n <= h->idx_cap) return 0;
+    if (h->d_idx) HIPCHK(hipFree(h->d_idx));
+    h->d_idx = nullptr; h->idx_cap = 0;
+    void* q = nullptr;
+    HIPCHK(hipMalloc(&q, n * sizeof(int32_t)));
+    h->d_idx = (int32_t*)q; h->idx_cap = n;
+    return 0;
+}
+
+// the copy loop over n pairs, in launches of at most 2^30 chunks (32-bit chunk indices); grid capped at eight blocks per CU, grid-stride
+int launch_rec_copy(wrsn_handle* h, int mode, const int32_t* src_env, const int32_t* dst_env, uint8_t* rec, int n) {
+    const int chunks = (int)(h->rec_bytes / 16), per = chunks - WRSN_REC_HDR / 16;
+    const int max_pairs = (1 << 30) / per > 0 ? (1 << 30) / per : 1;
+    for (int i0 = 0; i0 < n; i0 += max_pairs) {
+        const int m = n - i0 < max_pairs ? n - i0 : max_pairs;
+        const long long need = ((long long)m * per + 255) / 256;
+        const int blocks = (int)(need < (long long)h->cus * 8 ? need : (long long)h->cus * 8);
+        hipLaunchKernelGGL(wrsn_rec_copy_kernel, dim3(blocks), dim3(256), (size_t)h->nseg * sizeof(WrsnSeg), h->stream, (const WrsnSeg*)h->d_segs, h->nseg,
+                           mode, src_env, dst_env, rec, (long long)h->rec_bytes, i0, m, chunks);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+
+// request rows of replaced environments (+ their observations when out->obs is set)
+int launch_rec_rows(wrsn_handle* h, const uint8_t* hdr, const int32_t* src_env, const int32_t* dst_env, int n, const wrsn_step_out* out) {
+    WrsnStepOutDev o; o.agent_id = out->agent_id; o.reward = out->reward; o.terminal = out->terminal; o.now = out->now; o.obs = out->obs; o.status = out->status;
+    if (out->obs) HIPCHK(hipMemsetAsync(h->d_rend, 0xFF, (size_t)h->dev.B * sizeof(int32_t), h->stream));
+    hipLaunchKernelGGL(wrsn_rec_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->dev, hdr, src_env, dst_env, n, o, out->obs ? h->d_rend : (int32_t*)nullptr);
+    HIPCHK(hipGetLastError());
+    if (out->obs) return launch_obs(h, h->d_rend, out->obs);
     return 0;
 }
 
@@ -429,6 +568,9 @@ int wrsn_create(const wrsn_cfg* cfg, wrsn_t** out) {
         if ((rc = dalloc(h, &d.row_state, B))) break;
         if ((rc = dalloc(h, &d.queue, 8 + 64))) break;
         if ((rc = dalloc(h, &d.qskip, B))) break;
+        if ((rc = dalloc(h, &h->d_segs, WRSN_REC_MAXSEG))) break;
+        if ((rc = dalloc(h, &h->d_hdr, B * WRSN_REC_HDR))) break;
+        if ((rc = dalloc(h, &h->d_rend, B))) break;
         {   // the descriptor the kernels read, and the stochastic block behind it (wrsn_sim.h: Sim::SD)
             uint8_t* p = nullptr;
             if ((rc = dalloc(h, &p, sizeof(WrsnDev) + sizeof(WrsnStochDev)))) break;
@@ -441,6 +583,8 @@ int wrsn_create(const wrsn_cfg* cfg, wrsn_t** out) {
         if (hipMemcpy(d.order, ident.data(), B * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { wrsn_destroy(h); return fail(WRSN_ERR_HIP, "hipMemcpy"); }
     }
     if (configure_launch(h) != 0) { wrsn_destroy(h); return fail(WRSN_ERR_HIP, "hipMemcpy"); }
+    h->filled.assign(B, 0);
+    if (rec_layout(h) != 0 || ensure_idx(h, 2 * B) != 0) { wrsn_destroy(h); return fail(WRSN_ERR_HIP, "hipMemcpy"); }
     *out = h;
     return WRSN_OK;
 }
@@ -453,6 +597,7 @@ void wrsn_destroy(wrsn_t* h) {
     if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
     if (h->stream3) { (void)hipStreamSynchronize(h->stream3); (void)hipEventDestroy(h->ev_join3); (void)hipStreamDestroy(h->stream3); }
     for (void* p : h->allocs) (void)hipFree(p);
+    if (h->d_idx) (void)hipFree(h->d_idx);
     delete h;
 }
 
@@ -553,6 +698,7 @@ int set_scenario_impl(wrsn_t* h, int32_t env0, int32_t nenv, const double* node_
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     h->scenario_set = 1;
+    for (int e = 0; e < nenv; ++e) h->filled[env0 + e] = 1;
     return WRSN_OK;
 }
 
@@ -809,6 +955,99 @@ int wrsn_counters(wrsn_t* h, int64_t* dst) {
         dst[0] += dy[e].n_ticks; dst[1] += dy[e].n_exact; dst[2] += dy[e].n_events; dst[3] += dy[e].n_steps;
         dst[4] += dy[e].tot_ticks; dst[5] += dy[e].tot_zero_steps;
     }
+    return WRSN_OK;
+}
+
+int wrsn_env_record_bytes(wrsn_t* h, int64_t* bytes) {
+    if (!h || !bytes) return fail(WRSN_ERR_ARG, "null argument");
+    *bytes = h->rec_bytes;
+    return WRSN_OK;
+}
+
+int wrsn_save_envs(wrsn_t* h, const int32_t* env, int32_t n, const wrsn_step_out* req, void* dst) {
+    if (!h || !env || !req || !dst || n < 1) return fail(WRSN_ERR_ARG, "null argument or n < 1");
+    if (!req->agent_id || !req->reward || !req->terminal || !req->now || !req->status)
+        return fail(WRSN_ERR_ARG, "wrsn_save_envs needs the request rows: agent_id, reward, terminal, now and status");
+    if ((uintptr_t)dst % 16) return fail(WRSN_ERR_ARG, "dst must be 16-byte aligned");
+    int rc = check_envs(h, env, n, false, true, "env"); if (rc) return rc;
+    WRSN_ON_DEVICE(h);
+    if ((rc = ensure_idx(h, (size_t)n))) return rc;
+    HIPCHK(hipMemcpyAsync(h->d_idx, env, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    WrsnStepOutDev o; o.agent_id = req->agent_id; o.reward = req->reward; o.terminal = req->terminal; o.now = req->now; o.obs = nullptr; o.status = req->status;
+    hipLaunchKernelGGL(wrsn_rec_header_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->dev, (const double*)h->sd.pgp, rec_template(h),
+                       (const int32_t*)h->d_idx, (int)n, (uint8_t*)dst, (long long)h->rec_bytes, o);
+    HIPCHK(hipGetLastError());
+    return launch_rec_copy(h, WRSN_REC_PACK, h->d_idx, nullptr, (uint8_t*)dst, n);
+}
+
+int wrsn_load_envs(wrsn_t* h, const int32_t* env, int32_t n, const void* src, const wrsn_step_out* out) {
+    if (!h || !env || !src || !out || n < 1) return fail(WRSN_ERR_ARG, "null argument or n < 1");
+    if ((uintptr_t)src % 16) return fail(WRSN_ERR_ARG, "src must be 16-byte aligned");
+    int rc = check_envs(h, env, n, true, false, "env"); if (rc) return rc;
+    WRSN_ON_DEVICE(h);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    // record 0 decides the stride of the records (validated against this handle's geometry first), then every header is gathered and
+    // validated before anything changes
+    WrsnRecHeader r0;
+    HIPCHK(hipMemcpy(&r0, src, sizeof(r0), hipMemcpyDeviceToHost));
+    if ((rc = rec_check(h, r0, 0))) return rc;
+    hipLaunchKernelGGL(wrsn_rec_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, (const uint8_t*)src, (long long)r0.rec_bytes, (int)n, h->d_hdr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));
+    std::vector<WrsnRecHeader> hd(n);
+    HIPCHK(hipMemcpy(hd.data(), h->d_hdr, (size_t)n * sizeof(WrsnRecHeader), hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) {
+        if ((rc = rec_check(h, hd[i], i))) return rc;
+        if (hd[i].has_gen != r0.has_gen) return fail(WRSN_ERR_ARG, "record " + std::to_string(i) + ": has_gen differs from record 0's");
+    }
+    // generator blocks: the stochastic kernels read them for every environment of a stochastic handle, so they go only where the handle
+    // keeps generators (or holds no scenario yet, and then gets them); a record without one goes only where the handle keeps none
+    bool any_filled = false;
+    for (uint8_t f : h->filled) any_filled = any_filled || f;
+    if (r0.has_gen && !h->sd.mt_live && any_filled)
+        return fail(WRSN_ERR_ARG, "has_gen: the records hold a generator block, this handle keeps no generators and already holds a scenario");
+    if (!r0.has_gen && h->sd.mt_live)
+        return fail(WRSN_ERR_ARG, "has_gen: the records hold no generator block, this handle keeps generators");
+    // ---- every record fits: replace the environments
+    if (r0.has_gen && !h->sd.mt_live && (rc = alloc_stoch(h))) return rc;
+    int stoch_on = 0, cb = h->cc_bound;
+    for (int i = 0; i < n; ++i) {
+        if (hd[i].prob_gp != 1.0 && !h->stoch) stoch_on = 1;
+        if (hd[i].conn_bound > cb) cb = hd[i].conn_bound;
+    }
+    h->cc_bound = cb;
+    {   // as wrsn_set_scenario: connected-node lists in LDS sized to the scenarios, the stochastic kernels once prob_gp != 1 somewhere
+        int cc = ((h->cc_bound + 3) / 4) * 4; cc = cc < 4 ? 4 : (cc > WRSN_CONN_CAP ? WRSN_CONN_CAP : cc);
+        if (stoch_on) h->stoch = 1;
+        if (cc != h->dev.CC || stoch_on) { h->dev.CC = cc; if ((rc = configure_launch(h))) return rc; }
+    }
+    HIPCHK(hipMemcpyAsync(h->d_idx, env, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if ((rc = launch_rec_copy(h, WRSN_REC_UNPACK, nullptr, h->d_idx, (uint8_t*)src, n))) return rc;
+    if ((rc = launch_rec_rows(h, h->d_hdr, nullptr, h->d_idx, n, out))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int i = 0; i < n; ++i) h->filled[env[i]] = 1;
+    h->scenario_set = 1;
+    return WRSN_OK;
+}
+
+int wrsn_clone_envs(wrsn_t* h, const int32_t* src, const int32_t* dst, int32_t n, const wrsn_step_out* out) {
+    if (!h || !src || !dst || !out || n < 1) return fail(WRSN_ERR_ARG, "null argument or n < 1");
+    if (out->obs && !out->agent_id) return fail(WRSN_ERR_ARG, "rendering the cloned rows needs out->agent_id");
+    int rc = check_envs(h, src, n, false, true, "src"); if (rc) return rc;
+    if ((rc = check_envs(h, dst, n, true, false, "dst"))) return rc;
+    {
+        std::vector<uint8_t> is_src(h->dev.B, 0);
+        for (int i = 0; i < n; ++i) is_src[src[i]] = 1;
+        for (int i = 0; i < n; ++i)
+            if (is_src[dst[i]]) return fail(WRSN_ERR_ARG, "dst[" + std::to_string(i) + "] = " + std::to_string(dst[i]) + " is also a source");
+    }
+    WRSN_ON_DEVICE(h);
+    if ((rc = ensure_idx(h, 2 * (size_t)n))) return rc;
+    HIPCHK(hipMemcpyAsync(h->d_idx, src, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->d_idx + n, dst, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    if ((rc = launch_rec_copy(h, WRSN_REC_CLONE, h->d_idx, h->d_idx + n, nullptr, n))) return rc;
+    if ((rc = launch_rec_rows(h, nullptr, h->d_idx, h->d_idx + n, n, out))) return rc;
+    for (int i = 0; i < n; ++i) h->filled[dst[i]] = 1;
     return WRSN_OK;
 }
 

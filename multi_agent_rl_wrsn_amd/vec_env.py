@@ -174,6 +174,49 @@ class VecWRSN:
         self._h.rollout_table(out.data_ptr(), zero_after)
         return out
 
+    # -- environment records: save, load and clone running environments (wrsn_save_envs / wrsn_load_envs / wrsn_clone_envs) -------------
+    @staticmethod
+    def _env_list(envs, n):
+        return np.arange(n, dtype=np.int32) if envs is None else np.asarray(envs, dtype=np.int64).reshape(-1).astype(np.int32)
+
+    def record_bytes(self):
+        """Bytes of one environment record of this batch."""
+        return self._h.env_record_bytes()
+
+    def save_envs(self, envs=None):
+        """Records of environments `envs` (default: all) with their pending requests: a device uint8 tensor [n, record_bytes()].
+        Asynchronous; `.cpu()` / `torch.save` it for a checkpoint."""
+        t = self.torch
+        self._bind_stream()
+        idx = self._env_list(envs, self.num_env)
+        rec = t.empty((len(idx), self._h.env_record_bytes()), dtype=t.uint8, device=self.device)
+        p = self._out_ptrs(); p.pop("obs")
+        self._h.save_envs(idx, rec.data_ptr(), **p)
+        return rec
+
+    def load_envs(self, records, envs=None):
+        """Replace environments `envs` (default: 0 .. n-1) by `records` ([n, record_bytes] uint8, host or device, from any batch of the same
+        geometry) and return the request tensors, whose restored rows now hold the saved requests (state rendered for agent_id >= 0)."""
+        t = self.torch
+        self._bind_stream()
+        if records.dim() != 2 or records.dtype != t.uint8:
+            raise ValueError("records must be a uint8 tensor [n, record_bytes]")
+        rec = records.to(device=self.device).contiguous()
+        idx = self._env_list(envs, rec.shape[0])
+        if len(idx) != rec.shape[0]:
+            raise ValueError("%d records for %d environments" % (rec.shape[0], len(idx)))
+        self._h.load_envs(idx, rec.data_ptr(), **self._out_ptrs())
+        return self._result()
+
+    def clone_envs(self, src, dst):
+        """Environment dst[i] becomes a copy of src[i] (device to device, asynchronous); its request row follows.  Returns the request
+        tensors."""
+        self._bind_stream()
+        s = np.asarray(src, dtype=np.int64).reshape(-1).astype(np.int32)
+        d = np.asarray(dst, dtype=np.int64).reshape(-1).astype(np.int32)
+        self._h.clone_envs(s, d, **self._out_ptrs())
+        return self._result()
+
     def synchronize(self):
         self._h.sync()
 

@@ -102,6 +102,31 @@ class _AgentView:
         self.location = None; self.energy = None; self.status = 1; self.cur_action_type = "moving"; self.cur_phy_action = None
 
 
+def _copy(v):
+    if isinstance(v, np.ndarray):
+        return v.copy()
+    if isinstance(v, list):
+        return [_copy(x) for x in v]
+    return v
+
+
+def _copy_request(r):
+    return None if r is None else {k: _copy(v) for k, v in r.items() if k != "info"}
+
+
+class EnvSnapshot:
+    """What `WRSN.save_env` returns: the environment record (device uint8 tensor, `wrsn_save_envs`), copies of the facade's per-agent
+    lists and the request that was current.  Opaque: pass it to `WRSN.load_env` of a WRSN with the same geometry."""
+
+    def __init__(self, record, prev_state, input_action, action, request, now):
+        self.record = record
+        self.agents_prev_state = prev_state
+        self.agents_input_action = input_action
+        self.agents_action = action
+        self.request = request
+        self.now = now
+
+
 class WRSN:
     def __init__(self, scenario_path, agent_type_path, num_agent, map_size=100, warm_up_time=100, density_map=False,
                  device="cuda:0"):
@@ -119,6 +144,7 @@ class WRSN:
         self.agents_prev_state = [None for _ in range(num_agent)]
         self.vec = VecWRSN([self.scenario], self.agent_phy_para, num_agent, map_size, warm_up_time, device=device)
         self._now = 0.0
+        self._request = None
         self.env = _Clock(self)
         self.net = _NetView(self)
         self.agents = [_AgentView(i, self.agent_phy_para) for i in range(num_agent)]
@@ -166,14 +192,14 @@ class WRSN:
         for i in range(self.num_agent):
             self.agents_action[i] = bs_action.copy()
         if aid < 0:
-            return {"agent_id": None, "prev_state": None, "input_action": None, "action": None, "reward": None,
-                    "state": None, "terminal": terminal, "info": self._info()}
+            return self._current({"agent_id": None, "prev_state": None, "input_action": None, "action": None, "reward": None,
+                                  "state": None, "terminal": terminal, "info": self._info()})
         state0 = r["state"][0].to("cpu").numpy().astype(np.float64)
         for i in range(self.num_agent):
             self.agents_prev_state[i] = state0 if i == aid else self.get_state(i)
-        return {"agent_id": aid, "prev_state": self.agents_prev_state[aid], "input_action": self.agents_input_action[aid],
-                "action": self.agents_action[aid], "reward": 0.0, "state": self.agents_prev_state[aid],
-                "terminal": terminal, "info": self._info()}
+        return self._current({"agent_id": aid, "prev_state": self.agents_prev_state[aid], "input_action": self.agents_input_action[aid],
+                              "action": self.agents_action[aid], "reward": 0.0, "state": self.agents_prev_state[aid],
+                              "terminal": terminal, "info": self._info()})
 
     def step(self, agent_id, input_action, _action3=None):
         """WRSN.step (WRSN.py:289-330).  `_action3` is a test hook, not part of the reference's signature: with `density_map=True`
@@ -201,15 +227,44 @@ class WRSN:
         if status < 0:
             raise RuntimeError("environment error status %d (connection-list capacity exceeded?)" % status)
         if bool(r["terminal"][0]):                           # WRSN.py:312-320 (and the all-chargers-dead deviation)
-            return {"agent_id": None, "prev_state": None, "input_action": None, "action": None, "reward": None,
-                    "state": None, "terminal": True, "info": self._info()}
+            return self._current({"agent_id": None, "prev_state": None, "input_action": None, "action": None, "reward": None,
+                                  "state": None, "terminal": True, "info": self._info()})
         aid = int(r["agent_id"][0])
         if aid < 0:
-            return None                                      # the reference falls off the end of step() (WRSN.py:321-330)
+            return self._current(None)                       # the reference falls off the end of step() (WRSN.py:321-330)
         state = r["state"][0].to("cpu").numpy().astype(np.float64)
-        return {"agent_id": aid, "prev_state": self.agents_prev_state[aid], "input_action": self.agents_input_action[aid],
-                "action": self.agents_action[aid], "reward": float(r["reward"][0]), "state": state, "terminal": False,
-                "info": self._info()}
+        return self._current({"agent_id": aid, "prev_state": self.agents_prev_state[aid], "input_action": self.agents_input_action[aid],
+                              "action": self.agents_action[aid], "reward": float(r["reward"][0]), "state": state, "terminal": False,
+                              "info": self._info()})
+
+    def _current(self, request):
+        self._request = request
+        return request
+
+    # -- save / restore the running environment (lookahead: save, try an action, step, restore, try the next) -------------------
+    def save_env(self):
+        """Snapshot of the running environment: its record (wrsn_save_envs, on the device) plus copies of the per-agent lists this
+        facade keeps and of the current request.  Cheap enough to take before every lookahead step."""
+        rec = self.vec.save_envs([0])
+        return EnvSnapshot(rec, _copy(self.agents_prev_state), _copy(self.agents_input_action), _copy(self.agents_action),
+                           _copy_request(self._request), self._now)
+
+    def load_env(self, snap):
+        """Restore a snapshot taken by `save_env` (of this WRSN or one of the same geometry) and return the request dict that was
+        current when it was taken (its `info` views refreshed)."""
+        if not isinstance(snap, EnvSnapshot):
+            raise TypeError("load_env takes what save_env returned")
+        self.vec.load_envs(snap.record, [0])
+        self.vec.synchronize()
+        self.agents_prev_state = _copy(snap.agents_prev_state)
+        self.agents_input_action = _copy(snap.agents_input_action)
+        self.agents_action = _copy(snap.agents_action)
+        self._now = snap.now
+        req = _copy_request(snap.request)
+        if req is not None:
+            req["info"] = self._info()
+        self._request = req
+        return None if req is None else dict(req)
 
     # -- density-map action extraction (WRSN.py:229-287) on the device ------------------------------------------
     def density_map_to_action(self, dmap, id):
