@@ -52,13 +52,17 @@ int npl_for(int n_node) {
 
 }  // namespace
 
-// nodes-per-lane dispatch: `M_(NPL)` for the handle's register-slot count.  Diagnostic builds (tools/ab_build.sh) compile one slot count only
+// nodes-per-lane dispatch (select_kernels): `M_(NPL)` for the handle's register-slot count.  Diagnostic builds (tools/ab_build.sh) compile one slot count only
 // (-DWRSN_ONLY_NPL=4: a quarter of the build time); the product build has all five.
 #ifdef WRSN_ONLY_NPL
 #define WRSN_NPL_SWITCH(npl_, M_, bad_) switch (npl_) { case WRSN_ONLY_NPL: M_(WRSN_ONLY_NPL); break; default: bad_; }
 #else
 #define WRSN_NPL_SWITCH(npl_, M_, bad_) switch (npl_) { case 1: M_(1); break; case 2: M_(2); break; case 4: M_(4); break; case 8: M_(8); break; case 16: M_(16); break; default: bad_; }
 #endif
+
+// every step kernel has one signature, and so has every warm-up kernel: a handle picks its pair once (select_kernels)
+typedef void (*wrsn_step_fn)(const WrsnDev*, int, const int32_t*, const double*, int, int, long long, int, const uint8_t*, WrsnStepOutDev, int, int, int);
+typedef void (*wrsn_warmup_fn)(const WrsnDev*, int);
 
 struct wrsn_handle {
     wrsn_cfg cfg;
@@ -73,7 +77,7 @@ struct wrsn_handle {
     int cus;                   // compute units of the device
     int slots;                 // wave slots of the device for the step kernel (CUs x resident waves per CU): launch-order dependent budgets
     int waves_per_cu;          // what the occupancy query said for this handle's step kernel (diagnostic)
-    long long epoch;           // counter of wrsn_step calls (its parity selects the hand-off list a budgeted call reads / writes)
+    long long epoch;           // counter of wrsn_step calls: an argument of the step kernels that they do not read
     int step_budget;           // work units one wrsn_step launch may spend per environment, 0 = run every step to its end
     int deadline_ticks;        // wrsn_set_step_deadline in 100 MHz wall-clock ticks, 0 = none
     int pipe_mid_pct;          // share of the long half that stays on the caller's stream (the rest: third stream); 100 = two stages
@@ -91,6 +95,8 @@ struct wrsn_handle {
     WrsnDev* d_dev;            // device copy of `dev`: the environment kernels read it through the constant cache; `sd` follows it
     WrsnStochDev sd;           // prob_gp < 1: MT19937 state, send costs, prob_gp per environment (allocated by the first seeded call)
     int stoch;                 // an environment was loaded with prob_gp != 1 through wrsn_set_scenario_seeded: the stochastic kernels run
+    wrsn_step_fn step_kernel;  // the kernels of this handle's `npl` and `stoch` (select_kernels)
+    wrsn_warmup_fn warmup_kernel;
     std::vector<uint8_t> filled;   // per environment: holds a scenario (wrsn_set_scenario*, wrsn_load_envs, wrsn_clone_envs)
     // environment records (wrsn_state.h): the segment table of this handle's layout (generator block iff sd.mt_live), on the host and in
     // device memory; staging for the host index arrays, the gathered headers of a load and the charger list of the observation pass
@@ -133,18 +139,25 @@ int alloc_node_arrays(wrsn_handle* h, WrsnNodeArrays* a) {
     return 0;
 }
 
-// LDS sizes, wave slots and the device copy of the descriptor; again whenever WrsnDev.CC changes
+// the step and warm-up kernels of the handle's nodes-per-lane count, stochastic (prob_gp < 1) or plain
+int select_kernels(wrsn_handle* h) {
+#define WRSN_PICK(NPL_) h->step_kernel = h->stoch ? wrsn_step_stoch_kernel<NPL_> : wrsn_step_kernel<NPL_>; \
+                        h->warmup_kernel = h->stoch ? wrsn_warmup_stoch_kernel<NPL_> : wrsn_warmup_kernel<NPL_>
+    WRSN_NPL_SWITCH(h->npl, WRSN_PICK, return fail(WRSN_ERR_ARG, "unsupported nodes-per-lane"))
+#undef WRSN_PICK
+    return 0;
+}
+
+// kernels, LDS sizes, wave slots and the device copy of the descriptor; again whenever WrsnDev.CC changes or `stoch` is switched on
 int configure_launch(wrsn_handle* h) {
     WrsnDev& d = h->dev;
+    if (int rc = select_kernels(h)) return rc;
     h->lds_env = wrsn_lds_bytes(d.NP, d.M, d.CC) + (h->stoch ? wrsn_stoch_lds_bytes(d.NP) : 0);
     {   // wave slots of the step kernel on this device (registers and LDS decide): the budget taper of a launch starts behind the blocks
         // that are resident from the first moment
-        int per_cu = 0; hipError_t oe = hipErrorUnknown;
+        int per_cu = 0;
         const int lds_b = h->lds_env + h->lds_pad;
-#define WRSN_OCC(NPL_) oe = h->stoch ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, wrsn_step_stoch_kernel<NPL_>, 64, (size_t)lds_b) \
-                                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, wrsn_step_kernel<NPL_, WRSN_KERNEL_INLINE>, 64, (size_t)lds_b)
-        WRSN_NPL_SWITCH(h->npl, WRSN_OCC, oe = hipErrorUnknown)
-#undef WRSN_OCC
+        const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->step_kernel, 64, (size_t)lds_b);
         h->slots = h->cus * 8;
         if (oe == hipSuccess && per_cu >= 1 && per_cu <= 16) h->slots = h->cus * per_cu;
         h->waves_per_cu = (oe == hipSuccess) ? per_cu : 0;
@@ -163,10 +176,9 @@ int launch_env(wrsn_handle* h, int mode, int env0, int nenv, const int32_t* agen
     const int reset_call = (mode == WRSN_MODE_RESET) ? 1 : 0;
     const int budget = (mode == WRSN_MODE_STEP) ? h->step_budget : 0;
     const int dl = (budget > 0 && h->bp2 > 0) ? h->deadline_ticks : 0;     // the sort kernel zeroes the launch stamp
-    const int taper = h->taper;
     dim3 grid(nenv), block(64);
     long long epoch = 0;
-    if (mode == WRSN_MODE_STEP) epoch = ++h->epoch;            // every step call: a hand-off stamp names the one call whose heavy launch owns the environment
+    if (mode == WRSN_MODE_STEP) epoch = ++h->epoch;
     const bool queue = (mode == WRSN_MODE_STEP) && h->deadline_ticks > 0;    // work-queue launch (wrsn_set_step_deadline)
     const bool timed = (mode == WRSN_MODE_STEP) && h->timing && h->ev_ok;
     if (timed) (void)hipEventRecord(h->ev[0], h->stream);
@@ -176,10 +188,8 @@ int launch_env(wrsn_handle* h, int mode, int env0, int nenv, const int32_t* agen
         hipLaunchKernelGGL(wrsn_latch_kernel, dim3((nenv + 255) / 256), dim3(256), 0, h->stream, h->dev, agent_id, action, out);
         if (timed) (void)hipEventRecord(h->ev[1], h->stream);
         const int qbudget = budget > 0 ? budget : (1 << 28);   // the deadline is looked at wherever a work budget is
-#define WRSN_QUEUE(NPL_) hipLaunchKernelGGL((h->stoch ? wrsn_step_stoch_kernel<NPL_> : wrsn_step_kernel<NPL_, WRSN_KERNEL_INLINE>), grid, block, lds, h->stream, (const WrsnDev*)h->d_dev, 0, agent_id, action, \
-                                           auto_reset, qbudget, epoch, 0, mask, out, 3, h->deadline_ticks, 0)
-        WRSN_NPL_SWITCH(h->npl, WRSN_QUEUE, return fail(WRSN_ERR_ARG, "unsupported nodes-per-lane"))
-#undef WRSN_QUEUE
+        hipLaunchKernelGGL(h->step_kernel, grid, block, lds, h->stream, (const WrsnDev*)h->d_dev, 0, agent_id, action,
+                           auto_reset, qbudget, epoch, 0, mask, out, 3, h->deadline_ticks, 0);
         if (timed) { (void)hipEventRecord(h->ev[2], h->stream); (void)hipEventRecord(h->ev[3], h->stream); h->ev_obs = 0; h->ev_rec = 1; }
         HIPCHK(hipGetLastError());
         if (obs_pipe) {
@@ -216,38 +226,38 @@ int launch_env(wrsn_handle* h, int mode, int env0, int nenv, const int32_t* agen
         }
     }
     if (timed) (void)hipEventRecord(h->ev[1], h->stream);
-#define WRSN_LAUNCH(NPL_)                                                                                              \
-  { auto stepk_ = h->stoch ? wrsn_step_stoch_kernel<NPL_> : wrsn_step_kernel<NPL_, WRSN_KERNEL_INLINE>;              \
-    if (mode == WRSN_MODE_WARMUP) hipLaunchKernelGGL((h->stoch ? wrsn_warmup_stoch_kernel<NPL_> : wrsn_warmup_kernel<NPL_>), grid, block, lds, h->stream, (const WrsnDev*)h->d_dev, env0);  \
-    else if (pipe) {                                                                                                    \
-        /* stages over the launch order: [0, n1) the longest jobs (caller's stream), [n1, n2) the rest of the long half (third stream), */ \
-        /* [n2, B) the short half with its own work cap (second stream); n2 <= wave slots: the long half's jobs all start at once       */ \
-        int n2 = (nenv * h->pipe_long_pct / 100 + 63) & ~63; if (n2 > h->slots) n2 = h->slots & ~63; if (n2 < 64) n2 = 64;     \
-        int n1 = (n2 * h->pipe_mid_pct / 100 + 63) & ~63; if (n1 > n2 || !h->stream3) n1 = n2; if (n1 < 64) n1 = 64;            \
-        const int b_short = budget > 0 ? (budget * h->pipe_short_pct / 100 > 64 ? budget * h->pipe_short_pct / 100 : 64) : 0; \
-        (void)hipEventRecord(h->ev_fork, h->stream); (void)hipStreamWaitEvent(h->stream2, h->ev_fork, 0);              \
-        if (n1 < n2) (void)hipStreamWaitEvent(h->stream3, h->ev_fork, 0);                                              \
-        hipLaunchKernelGGL(stepk_, dim3(nenv - n2), block, lds, h->stream2, (const WrsnDev*)h->d_dev, reset_call, agent_id, action, \
-                           auto_reset, b_short, epoch, (h->slots & 0xFFFF) | taper, mask, out, 0, dl, n2);                                     \
-        hipLaunchKernelGGL(wrsn_obs_kernel, dim3(nenv - n2), dim3(256), h->lds_obs, h->stream2, h->dev, (const int32_t*)h->dev.render_agent, obs_pipe, h->obs_reuse, (const int32_t*)h->dev.order, n2); \
-        (void)hipEventRecord(h->ev_join, h->stream2);                                                                 \
-        if (n1 < n2) {                                                                                                 \
-            hipLaunchKernelGGL(stepk_, dim3(n2 - n1), block, lds, h->stream3, (const WrsnDev*)h->d_dev, reset_call, agent_id, action, \
-                               auto_reset, budget, epoch, (h->slots & 0xFFFF) | taper, mask, out, 0, dl, n1);                                  \
-            hipLaunchKernelGGL(wrsn_obs_kernel, dim3(n2 - n1), dim3(256), h->lds_obs, h->stream3, h->dev, (const int32_t*)h->dev.render_agent, obs_pipe, h->obs_reuse, (const int32_t*)h->dev.order, n1); \
-            (void)hipEventRecord(h->ev_join3, h->stream3);                                                             \
-        }                                                                                                              \
-        hipLaunchKernelGGL(stepk_, dim3(n1), block, lds, h->stream, (const WrsnDev*)h->d_dev, reset_call, agent_id, action, \
-                           auto_reset, budget, epoch, (h->slots & 0xFFFF) | taper, mask, out, 0, dl, 0);                                       \
-        if (timed) { (void)hipEventRecord(h->ev[2], h->stream); (void)hipEventRecord(h->ev[3], h->stream); }            \
-        hipLaunchKernelGGL(wrsn_obs_kernel, dim3(n1), dim3(256), h->lds_obs, h->stream, h->dev, (const int32_t*)h->dev.render_agent, obs_pipe, h->obs_reuse, (const int32_t*)h->dev.order, 0); \
-        (void)hipStreamWaitEvent(h->stream, h->ev_join, 0);                                                            \
-        if (n1 < n2) (void)hipStreamWaitEvent(h->stream, h->ev_join3, 0);                                              \
-    }                                                                                                                  \
-    else hipLaunchKernelGGL(stepk_, grid, block, lds, h->stream, (const WrsnDev*)h->d_dev, reset_call, agent_id, action, \
-                            auto_reset, budget, epoch, (h->slots & 0xFFFF) | taper, mask, out, 0, dl, 0); }
-    WRSN_NPL_SWITCH(h->npl, WRSN_LAUNCH, return fail(WRSN_ERR_ARG, "unsupported nodes-per-lane"))
-#undef WRSN_LAUNCH
+    // step launch of blocks [b0, b0 + n) of the launch order on stream `st` with work budget `bud`
+    auto step_launch = [&](hipStream_t st, int b0, int n, int bud) {
+        hipLaunchKernelGGL(h->step_kernel, dim3(n), block, lds, st, (const WrsnDev*)h->d_dev, reset_call, agent_id, action,
+                           auto_reset, bud, epoch, (h->slots & 0xFFFF) | h->taper, mask, out, 0, dl, b0);
+    };
+    auto obs_launch = [&](hipStream_t st, int b0, int n) {
+        hipLaunchKernelGGL(wrsn_obs_kernel, dim3(n), dim3(256), h->lds_obs, st, h->dev, (const int32_t*)h->dev.render_agent, obs_pipe, h->obs_reuse, (const int32_t*)h->dev.order, b0);
+    };
+    if (mode == WRSN_MODE_WARMUP) hipLaunchKernelGGL(h->warmup_kernel, grid, block, lds, h->stream, (const WrsnDev*)h->d_dev, env0);
+    else if (pipe) {
+        // stages over the launch order: [0, n1) the longest jobs (caller's stream), [n1, n2) the rest of the long half (third stream),
+        // [n2, B) the short half with its own work cap (second stream); n2 <= wave slots: the long half's jobs all start at once
+        int n2 = (nenv * h->pipe_long_pct / 100 + 63) & ~63; if (n2 > h->slots) n2 = h->slots & ~63; if (n2 < 64) n2 = 64;
+        int n1 = (n2 * h->pipe_mid_pct / 100 + 63) & ~63; if (n1 > n2 || !h->stream3) n1 = n2; if (n1 < 64) n1 = 64;
+        const int b_short = budget > 0 ? (budget * h->pipe_short_pct / 100 > 64 ? budget * h->pipe_short_pct / 100 : 64) : 0;
+        (void)hipEventRecord(h->ev_fork, h->stream); (void)hipStreamWaitEvent(h->stream2, h->ev_fork, 0);
+        if (n1 < n2) (void)hipStreamWaitEvent(h->stream3, h->ev_fork, 0);
+        step_launch(h->stream2, n2, nenv - n2, b_short);
+        obs_launch(h->stream2, n2, nenv - n2);
+        (void)hipEventRecord(h->ev_join, h->stream2);
+        if (n1 < n2) {
+            step_launch(h->stream3, n1, n2 - n1, budget);
+            obs_launch(h->stream3, n1, n2 - n1);
+            (void)hipEventRecord(h->ev_join3, h->stream3);
+        }
+        step_launch(h->stream, 0, n1, budget);
+        if (timed) { (void)hipEventRecord(h->ev[2], h->stream); (void)hipEventRecord(h->ev[3], h->stream); }
+        obs_launch(h->stream, 0, n1);
+        (void)hipStreamWaitEvent(h->stream, h->ev_join, 0);
+        if (n1 < n2) (void)hipStreamWaitEvent(h->stream, h->ev_join3, 0);
+    }
+    else step_launch(h->stream, 0, nenv, budget);
     if (pipe) {
         if (timed) { (void)hipEventRecord(h->ev[4], h->stream); h->ev_obs = 1; h->ev_rec = 1; }
         HIPCHK(hipGetLastError());
@@ -582,7 +592,7 @@ int wrsn_create(const wrsn_cfg* cfg, wrsn_t** out) {
         std::vector<int32_t> ident(B); for (size_t e = 0; e < B; ++e) ident[e] = (int32_t)e;
         if (hipMemcpy(d.order, ident.data(), B * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { wrsn_destroy(h); return fail(WRSN_ERR_HIP, "hipMemcpy"); }
     }
-    if (configure_launch(h) != 0) { wrsn_destroy(h); return fail(WRSN_ERR_HIP, "hipMemcpy"); }
+    if ((rc = configure_launch(h))) { wrsn_destroy(h); return rc; }
     h->filled.assign(B, 0);
     if (rec_layout(h) != 0 || ensure_idx(h, 2 * B) != 0) { wrsn_destroy(h); return fail(WRSN_ERR_HIP, "hipMemcpy"); }
     *out = h;

@@ -257,11 +257,9 @@ WDEV void wrsn_lds_gather8_b64(const double* base, const int (&idx)[8], double (
 }
 #endif
 
-// Sim<NPL, true> holds everything; Sim<NPL, false> -- the simulator of the step kernel's common path -- has no code for the three rare,
-// register-hungry services: the level BFS after a death (set_levels), the routing-cache rebuild (rebuild_cache) and the packet-exact
-// second (exact_walk).  When a grid item needs one of them it stops in front of that item exactly like an environment that ran out
-// of its launch budget (`need_heavy`), the step kernel stores the environment, calls wrsn_step_env_full -- a NOINLINE device function
-// with the full simulator, which loads the environment, runs that one item and suspends (or finishes the step) -- and goes on.
+// Sim<NPL, STOCH>: the simulator of one environment on one wavefront; every service, the three rare register-hungry ones included
+// (the level BFS after a death, set_levels; the routing-cache rebuild, rebuild_cache; the packet-exact second, exact_walk), is inline
+// in the one kernel that uses it (DESIGN.md 4.1 has the measurements of the forms that kept them out of line).
 // STOCH = true: the stochastic variant (prob_gp < 1, Node.py:61) -- one MT19937 draw per live node and second, packets only from the
 // nodes whose draw is below prob_gp.  Everything it adds sits behind `if constexpr (STOCH)`: the prob_gp == 1 instantiations are the
 // code they were.
@@ -269,7 +267,7 @@ WDEV void wrsn_lds_gather8_b64(const double* base, const int (&idx)[8], double (
 // words, draws since the last reset, draws counted but not yet applied to the state words (mt_flush); nothing in the other variants
 template <bool STOCH> struct SimStochRegs { double pgp; int pgp1, mt_idx; int64_t mt_cnt, mt_pend; };
 template <> struct SimStochRegs<false> { static constexpr double pgp = 1.0; static constexpr int pgp1 = 1, mt_idx = 0; static constexpr int64_t mt_cnt = 0, mt_pend = 0; };
-template <int NPL, bool HEAVY = true, bool STOCH = false>
+template <int NPL, bool STOCH = false>
 struct Sim : SimStochRegs<STOCH> {
     using SimStochRegs<STOCH>::pgp; using SimStochRegs<STOCH>::pgp1; using SimStochRegs<STOCH>::mt_idx;
     using SimStochRegs<STOCH>::mt_cnt; using SimStochRegs<STOCH>::mt_pend;
@@ -298,8 +296,7 @@ struct Sim : SimStochRegs<STOCH> {
     long long t_deadline;                                    // wall clock at which this launch stops taking new grid items (0 = none); wave-uniform
     long long t_exact;                                       // ... at which it stops beginning packet-exact seconds (time-sliced launches; 0 = none)
     int fit_dirty, map1_valid;                               // a grid service ran since last_minfit was evaluated / map 1 of the observation still stands (wave-uniform)
-    int need_heavy;                                          // HEAVY = false: the next grid item needs a service this variant has no code for (1); either
-                                                             // variant: a packet-exact second was put off because the time-sliced launch is about to end (2)
+    int exact_put_off;                                       // non-zero: a packet-exact second was put off because the time-sliced launch is about to end
     int n_items;                                             // grid items completed in this visit (wave-uniform)
     double last_minfit;
     WRSN_PROF_DECL
@@ -563,7 +560,7 @@ struct Sim : SimStochRegs<STOCH> {
         cap = wu(EC()->capacity); thr = wu(EC()->threshold); max_time = wu(EC()->max_time);
         inv_a_b2 = wu((EC()->beta * EC()->beta) / EC()->alpha);
         teps = wu(1e-9 * cap);
-        err = 0; deaths_flag = 0; need_heavy = 0; t_deadline = 0; t_exact = 0;
+        err = 0; deaths_flag = 0; exact_put_off = 0; t_deadline = 0; t_exact = 0;
         if (lane == 0) { Scalar* q = SS(); q->pend = 0; q->pend_idx = 0; q->L = 0; q->ev_valid = 0; q->n_events = 0; }
     }
 
@@ -775,7 +772,6 @@ struct Sim : SimStochRegs<STOCH> {
 
     // -------------------------------------------------------------- Network.setLevels + check_targets (Network.py:37-66, 84-85)
     WDEV void set_levels() { WRSN_PROF_T0
-        if constexpr (!HEAVY) { need_heavy = 1; return; } else {
         int oldlv[NPL];
         if (NPL <= 4) {
             // Up to 256 nodes: node sets are NPL 64-bit masks (one ballot per register slot) and the neighbourhood of a
@@ -881,14 +877,12 @@ struct Sim : SimStochRegs<STOCH> {
         alive = wv_any(bad) ? 0 : 1;
         levels_dirty = 0; work += 100; dirty |= 2;
         WRSN_PROF_ADD(6)
-        }
     }
 
     // -------------------------------------------------------------- routing cache: receivers + per-tick drains
     // rcv_i = Node.find_receiver (Node.py:92-100) / base station (Node.py:108-111); c1/c2 = packets relayed per tick that
     // arrive before / after the node's own half-charge (sources with lower / higher id; Node.py:57-62 runs in id order).
     WDEV void rebuild_cache() { WRSN_PROF_T0
-        if constexpr (!HEAVY) { need_heavy = 1; return; } else {
         int32_t* c1 = (int32_t*)SU(); int32_t* c2 = c1 + NP;
         double es[NPL]; int rc[NPL], wsl[NPL];
         const double er = EC()->e_recv;
@@ -947,7 +941,6 @@ struct Sim : SimStochRegs<STOCH> {
         opmax = wv_max(opm);
         cache_dirty = 0; irreg = WRSN_RING; safe_ticks = 0; work += 80; dirty |= 1;
         WRSN_PROF_ADD(5)
-        }
     }
 
     // -------------------------------------------------------------- exact k+0.5 instant (a node may run dry this second)
@@ -1136,7 +1129,6 @@ struct Sim : SimStochRegs<STOCH> {
     }
 
     WDEV void exact_walk(const double (&rrh)[NPL], bool any_rr) { WRSN_PROF_T0
-        if constexpr (!HEAVY) { need_heavy = 1; (void)rrh; (void)any_rr; return; } else {
         double es[NPL], gain[NPL], e_start[NPL];
 #pragma unroll
         for (int j = 0; j < NPL; ++j) { e_start[j] = E[j]; gain[j] = 0.0; }
@@ -1223,7 +1215,6 @@ struct Sim : SimStochRegs<STOCH> {
         (void)any_rr;
         __syncthreads();
         WRSN_PROF_ADD(4)
-        }
     }
 
     // May a node run dry in the second that starts now?  (Node state at k+0.5 is the state at the start of the second.)  When not:
@@ -1260,15 +1251,14 @@ struct Sim : SimStochRegs<STOCH> {
 
     // -------------------------------------------------------------- k+0.5: Node.operate first half for all nodes (Node.py:57-62)
     WDEV void node_half(const double (&rrh)[NPL], const bool any_rr) {
-        if (cache_dirty) { rebuild_cache(); if (!HEAVY) return; }
+        if (cache_dirty) rebuild_cache();
         bool fast = true;
         if (safe_ticks > 0) { safe_ticks--; }
         else {
             fast = second_is_safe(rrh);
-            if (!HEAVY && !fast) { need_heavy = 1; return; }  // nothing was touched: the full variant takes this item again
             // time-sliced launch about to end: a packet-exact second is not begun (unless nothing else was done in this visit); the
             // environment stops in front of the item and the next launch, in which it is among the first, takes it again
-            if (!fast && t_exact != 0 && n_items > 0 && (long long)wall_clock64() > t_exact) { need_heavy = 2; return; }
+            if (!fast && t_exact != 0 && n_items > 0 && (long long)wall_clock64() > t_exact) { exact_put_off = 2; return; }
         }
         if (fast) {
             if constexpr (STOCH) {                          // every live node draws (Node.py:61); with prob_gp == 1 they all generate
@@ -1727,7 +1717,6 @@ struct Sim : SimStochRegs<STOCH> {
                 if (k == 0) {
                     if (net_phase == 0) {                    // Network.py:75-78
                         if (levels_dirty) set_levels();
-                        if (!HEAVY && need_heavy) { now = now_before; break; }
                         if (alive == 0) frozen = 1;          // terminal at the next return; node state is no longer observable
                         net_phase = 1; net_time = now + 9.0 * 1.0 / 10.0; net_seq = seq++;
                     } else {                                 // Network.py:78-80
@@ -1740,7 +1729,7 @@ struct Sim : SimStochRegs<STOCH> {
                 } else {
                     if (node_phase == 0) {
                         node_half(rrh, any_rr);
-                        if (need_heavy) { now = now_before; break; }
+                        if (exact_put_off) { now = now_before; break; }
                         node_phase = 1;
                     } else { node_full(rrh, any_rr); node_phase = 0; }
                     node_time = now + 1.0 * 0.5; node_seq = seq++;
@@ -2282,13 +2271,42 @@ struct Sim : SimStochRegs<STOCH> {
             }
             __syncthreads();
             WRSN_P4_MARK(r4_) if (req == REQ_GRID) { WRSN_P4_SPAN(14, r3_, r4_) } else if (req == REQ_PRECHECK) { WRSN_P4_SPAN(12, r3_, r4_) } else { WRSN_P4_SPAN(13, r3_, r4_) }
-            if (need_heavy) { suspended = true; break; }     // a packet-exact second put off to the next (time-sliced) launch
+            if (exact_put_off) { suspended = true; break; }     // a packet-exact second put off to the next (time-sliced) launch
         }
         if (!stopped && !suspended) err = -10;               // the service loop ran out: the environment is stuck, report it (status < 0)
         __syncthreads();
         if (lane == 0 && !suspended) ff_sync_all(now);       // bring virtual charger sub-steps up to the return instant
         __syncthreads();
         return suspended;
+    }
+    // -------------------------------------------------------------- warm-up (WRSN.py:41-64): the pieces both warm-up kernels share
+    WDEV void warmup_init_chargers() {                       // lane 0: MobileCharger.__init__ + WRSN.py:44-49
+        const WrsnEnvConst* ec = EC();
+        for (int m = 0; m < M; ++m) {
+            SAG()[m].loc[0] = ec->bs[0]; SAG()[m].loc[1] = ec->bs[1]; SAG()[m].energy = ec->mc_capacity; SAG()[m].charging_rate = 0.0;
+            SAG()[m].status = 1; mc_check_status(m);
+            SAG()[m].type_charging = 0; SAG()[m].n_conn = 0; SAG()[m].cur_thread = -1; SAG()[m].n_live = 0;
+            SAG()[m].cur[0] = ec->bs[0]; SAG()[m].cur[1] = ec->bs[1]; SAG()[m].cur[2] = 0.0;
+            SAG()[m].excl = 0.0; SAG()[m].prev_minfit = 0.0;
+            SAG()[m].conn_loc[0] = ec->bs[0]; SAG()[m].conn_loc[1] = ec->bs[1];
+        }
+    }
+    // Network.operate -> timeout(0.1); update_reward body at t = 0 (no charger is charging) -> timeout(1); nodes -> timeout(0.5)
+    WDEV void warmup_first_items() {
+        net_active = 1; net_phase = 0; net_time = now + 1.0 / 10.0; net_seq = seq++;
+        ur_time = now + 1.0; ur_seq = seq++;
+        node_phase = 0; node_time = now + 1.0 * 0.5; node_seq = seq++;
+        use_snap = 1;
+    }
+    WDEV void warmup_start_chargers(double fit) {            // lane 0, at warm_up_time: WRSN.py:59-64
+        const WrsnEnvConst* ec = EC();
+        for (int m = 0; m < M; ++m) {
+            SAG()[m].action[0] = (ec->bs[0] - ec->frame[0]) / (ec->frame[1] - ec->frame[0]);
+            SAG()[m].action[1] = (ec->bs[1] - ec->frame[2]) / (ec->frame[3] - ec->frame[2]);
+            SAG()[m].action[2] = 0.0;
+            SAG()[m].cur_thread = new_thread(m, SAG()[m].cur[0], SAG()[m].cur[1], SAG()[m].cur[2]);
+            SAG()[m].prev_minfit = fit; SAG()[m].excl = 0.0;
+        }
     }
 };
 
@@ -2303,21 +2321,13 @@ struct Sim : SimStochRegs<STOCH> {
 #ifndef WRSN_WAVES_PER_SIMD
 #define WRSN_WAVES_PER_SIMD(NPL_) ((NPL_) <= 4 ? 2 : 1)
 #endif
-// WRSN_KERNEL_INLINE = true (the product): the step kernel is ONE code object with the rare services inlined.  false builds the r03
-// experiment -- the common-path simulator Sim<NPL, false> in the kernel, the full one behind a noinline call for the one grid item that
-// needs it (wrsn_step_env_full): measured 2 x slower (1.03 ms against 0.51 ms per launch, profiles/r03_ab_load_eventmachine.log), as was
-// the first form of it (the three services as noinline functions taking the node registers through memory: 1.24 ms -- the register
-// allocator puts the spills of a call at the head of the enclosing hot region, not at the rare call site).  tools/ab_build.sh.
-#ifndef WRSN_KERNEL_INLINE
-#define WRSN_KERNEL_INLINE true
-#endif
 template <int NPL>
 __global__ void __launch_bounds__(64, WRSN_WAVES_PER_SIMD(NPL)) wrsn_warmup_kernel(const WrsnDev* __restrict__ dp, int env0) {
     extern __shared__ double smem[];
     const int env = env0 + blockIdx.x;
     const int lane = threadIdx.x;
     if (env >= dp->B) return;
-    Sim<NPL, true> s;                                        // (one-off: the full simulator, everything inline)
+    Sim<NPL> s;
     s.bind(dp, env, lane, smem);
     const WrsnEnvConst* ec = s.EC();
     // NetworkIO.makeNetwork + Node.__init__ (Node.py:12-43) + t = 0 process start-up
@@ -2344,42 +2354,25 @@ __global__ void __launch_bounds__(64, WRSN_WAVES_PER_SIMD(NPL)) wrsn_warmup_kern
     __syncthreads();
     if (lane == 0) {
         s.SREQ()[0] = 0; s.SREQ()[1] = 0; s.SREQ()[2] = 0; s.SURN()[0] = 0; s.SRRN()[0] = 0;
-        for (int m = 0; m < s.M; ++m) {                      // MobileCharger.__init__ + WRSN.py:44-49
-            s.SAG()[m].loc[0] = ec->bs[0]; s.SAG()[m].loc[1] = ec->bs[1]; s.SAG()[m].energy = ec->mc_capacity; s.SAG()[m].charging_rate = 0.0;
-            s.SAG()[m].status = 1; s.mc_check_status(m);
-            s.SAG()[m].type_charging = 0; s.SAG()[m].n_conn = 0; s.SAG()[m].cur_thread = -1; s.SAG()[m].n_live = 0;
-            s.SAG()[m].cur[0] = ec->bs[0]; s.SAG()[m].cur[1] = ec->bs[1]; s.SAG()[m].cur[2] = 0.0;
-            s.SAG()[m].excl = 0.0; s.SAG()[m].prev_minfit = 0.0;
-            s.SAG()[m].conn_loc[0] = ec->bs[0]; s.SAG()[m].conn_loc[1] = ec->bs[1];
-        }
+        s.warmup_init_chargers();
     }
-    // Network.operate -> timeout(0.1); update_reward body at t = 0 (no charger is charging) -> timeout(1); nodes -> timeout(0.5)
-    s.net_active = 1; s.net_phase = 0; s.net_time = s.now + 1.0 / 10.0; s.net_seq = s.seq++;
-    s.ur_time = s.now + 1.0; s.ur_seq = s.seq++;
-    s.node_phase = 0; s.node_time = s.now + 1.0 * 0.5; s.node_seq = s.seq++;
-    s.use_snap = 1;
+    s.warmup_first_items();
     __syncthreads();
     s.run(true, ec->warm_up_time);                           // env.run(until=warm_up_time): stops before that instant's NORMAL events
     double fit = s.min_fitness();
     s.last_minfit = fit; s.fit_dirty = 0; s.map1_valid = 0;
-    if (lane == 0) {
-        for (int m = 0; m < s.M; ++m) {                      // WRSN.py:59-64
-            s.SAG()[m].action[0] = (ec->bs[0] - ec->frame[0]) / (ec->frame[1] - ec->frame[0]);
-            s.SAG()[m].action[1] = (ec->bs[1] - ec->frame[2]) / (ec->frame[3] - ec->frame[2]);
-            s.SAG()[m].action[2] = 0.0;
-            s.SAG()[m].cur_thread = s.new_thread(m, s.SAG()[m].cur[0], s.SAG()[m].cur[1], s.SAG()[m].cur[2]);
-            s.SAG()[m].prev_minfit = fit; s.SAG()[m].excl = 0.0;
-        }
-    }
+    if (lane == 0) s.warmup_start_chargers(fit);
     s.dirty = 7;
     s.store(dp->snap, 0, 0);
 }
 // The warm-up of the stochastic variant: the kernel above with the generator loaded from the seeded state and stored into the snapshot.
-// (A copy of the text: the prob_gp == 1 kernel compiled through a shared template gets another register allocation than before.)
+// (A copy of the text but for the Sim::warmup_* pieces: the prob_gp == 1 kernel compiled through a shared body -- a function template, or
+//  members for the whole start-up and tail -- gets another register allocation and spills more: 400 instead of 257 VGPRs at 16 nodes per
+//  lane.  A fix to the t = 0 start-up outside those pieces has to be made in both.)
 template <int NPL>
 __device__ __forceinline__ void wrsn_warmup_stoch_env(const WrsnDev* __restrict__ dp, int env, double* smem) {
     const int lane = threadIdx.x;
-    Sim<NPL, true, true> s;                                  // (one-off: the full simulator, everything inline)
+    Sim<NPL, true> s;
     s.bind(dp, env, lane, smem);
     s.stoch_load(false);                                     // the seeded state wrsn_set_scenario_seeded wrote (random.seed, NetworkIO.py:23)
     const WrsnEnvConst* ec = s.EC();
@@ -2407,33 +2400,14 @@ __device__ __forceinline__ void wrsn_warmup_stoch_env(const WrsnDev* __restrict_
     __syncthreads();
     if (lane == 0) {
         s.SREQ()[0] = 0; s.SREQ()[1] = 0; s.SREQ()[2] = 0; s.SURN()[0] = 0; s.SRRN()[0] = 0;
-        for (int m = 0; m < s.M; ++m) {                      // MobileCharger.__init__ + WRSN.py:44-49
-            s.SAG()[m].loc[0] = ec->bs[0]; s.SAG()[m].loc[1] = ec->bs[1]; s.SAG()[m].energy = ec->mc_capacity; s.SAG()[m].charging_rate = 0.0;
-            s.SAG()[m].status = 1; s.mc_check_status(m);
-            s.SAG()[m].type_charging = 0; s.SAG()[m].n_conn = 0; s.SAG()[m].cur_thread = -1; s.SAG()[m].n_live = 0;
-            s.SAG()[m].cur[0] = ec->bs[0]; s.SAG()[m].cur[1] = ec->bs[1]; s.SAG()[m].cur[2] = 0.0;
-            s.SAG()[m].excl = 0.0; s.SAG()[m].prev_minfit = 0.0;
-            s.SAG()[m].conn_loc[0] = ec->bs[0]; s.SAG()[m].conn_loc[1] = ec->bs[1];
-        }
+        s.warmup_init_chargers();
     }
-    // Network.operate -> timeout(0.1); update_reward body at t = 0 (no charger is charging) -> timeout(1); nodes -> timeout(0.5)
-    s.net_active = 1; s.net_phase = 0; s.net_time = s.now + 1.0 / 10.0; s.net_seq = s.seq++;
-    s.ur_time = s.now + 1.0; s.ur_seq = s.seq++;
-    s.node_phase = 0; s.node_time = s.now + 1.0 * 0.5; s.node_seq = s.seq++;
-    s.use_snap = 1;
+    s.warmup_first_items();
     __syncthreads();
     s.run(true, ec->warm_up_time);                           // env.run(until=warm_up_time): stops before that instant's NORMAL events
     double fit = s.min_fitness();
     s.last_minfit = fit; s.fit_dirty = 0; s.map1_valid = 0;
-    if (lane == 0) {
-        for (int m = 0; m < s.M; ++m) {                      // WRSN.py:59-64
-            s.SAG()[m].action[0] = (ec->bs[0] - ec->frame[0]) / (ec->frame[1] - ec->frame[0]);
-            s.SAG()[m].action[1] = (ec->bs[1] - ec->frame[2]) / (ec->frame[3] - ec->frame[2]);
-            s.SAG()[m].action[2] = 0.0;
-            s.SAG()[m].cur_thread = s.new_thread(m, s.SAG()[m].cur[0], s.SAG()[m].cur[1], s.SAG()[m].cur[2]);
-            s.SAG()[m].prev_minfit = fit; s.SAG()[m].excl = 0.0;
-        }
-    }
+    if (lane == 0) s.warmup_start_chargers(fit);
     s.dirty = 7;
     s.store(dp->snap, 0, 0);
     s.stoch_store(true);                                     // the snapshot reset() restores holds the generator too (NetworkIO.py:22-24)
@@ -2447,122 +2421,31 @@ __global__ void __launch_bounds__(64, WRSN_WAVES_PER_SIMD(NPL)) wrsn_warmup_stoc
 }
 
 // `handoff`: 0 = one block per environment in the launch order (`block0`: the launch covers blocks block0 .. of it); 3 = time-sliced launch.
-//            4 = (wrsn_step_env_full only) go on with the step in flight of this environment, whatever the caller's rows say.
-// Returns (work units spent << 1) | 1 when the HEAVY = false simulator stopped in front of a grid item it has no code for.
-template <int NPL, bool HEAVY, bool STOCH = false>
-__device__ __forceinline__ int wrsn_step_env(const WrsnDev* __restrict__ dp, int env, int reset_call, const int32_t* __restrict__ agent_id,
-                                             const double* __restrict__ action, int auto_reset, int budget, long long epoch,
-                                             const uint8_t* __restrict__ env_mask, const WrsnStepOutDev& out, int handoff, int deadline, double* smem, long long t_end);
-
-// The full simulator, out of line: one grid item of the step in flight of `env` (budget 1: the item in front of which the common-path
-// simulator stopped -- level BFS, routing rebuild, packet-exact second -- and whatever charger events follow it up to the next grid
-// service), then the environment is stored again, suspended or finished.  Its own register allocation and its own spills; the call
-// sits where the caller holds next to nothing in registers.
-template <int NPL>
-__device__ __noinline__ void wrsn_step_env_full(const WrsnDev* dp, int env, long long epoch, WrsnStepOutDev out) {
-    extern __shared__ double smem[];
-    (void)wrsn_step_env<NPL, true>(dp, env, 0, nullptr, nullptr, 0, 1, epoch, nullptr, out, 4, 0, smem, 0);
-}
-
-template <int NPL, bool HEAVY, bool STOCH>
-__device__ __forceinline__ void wrsn_step_blocks(const WrsnDev* dp, int reset_call, const int32_t* agent_id, const double* action,
-                                                 int auto_reset, int budget, long long epoch, int slots, const uint8_t* env_mask, WrsnStepOutDev out,
-                                                 int handoff, int deadline, int block0) {
-    extern __shared__ double smem[];
-    // Block b of a step launch takes environment order[b]: the environments sorted by the work their WRSN.step still needs,
-    // longest first (wrsn_estimate_kernel / wrsn_sort_kernel run in front of every step launch).  The duration of a WRSN.step is
-    // heavy-tailed and a launch ends with its last wave, so the long jobs have to start first; every environment appears exactly once
-    // in the order, so a launch owns an environment through one block only.
-    // The heavy launch has one block per environment of the batch too; block b takes entry b of the list and the blocks behind the end of the
-    // list leave at once (the host does not know its length).
-    int env = blockIdx.x; long long t_slice_end = 0;
-    if (handoff == 3) {
-        // Time-sliced launch (wrsn_set_step_deadline): the blocks of the launch share ONE deadline (`deadline` ticks after the first of them
-        // started).  Block b takes environment (start + b) mod B of this launch's cyclic order; the hardware hands the blocks to the wave slots
-        // in index order as slots become free, so every slot is busy from the first microsecond on.  A wave runs its WRSN.step until it
-        // returns or the deadline passes (then it stops at the next item boundary, like a wave out of budget).  A block that only starts
-        // when the launch is about to end leaves at once and does NOT touch its environment: the action waits in the latch
-        // (wrsn_latch_kernel), the row says "in flight", and the next launch starts its cyclic order there.
-        const int B = dp->B;
-        if ((int)blockIdx.x >= B) return;
-        // (the launch's start was stamped by wrsn_latch_kernel, a few microseconds ago: thousands of blocks racing for one stamp with an
-        //  atomic -- and for one "last block taken" word -- took 70 us to get going; the word is spread over 64 addresses)
-        const long long tn = (long long)wall_clock64();       // wave-uniform (s_memrealtime)
-        const long long t_end = wu((int64_t)*dp->launch_t0) + deadline;
-        // too late to do anything for this environment in this launch?  (margin: at most a quarter of the time slice)
-        if (tn > t_end - (deadline / 4 < WRSN_PULL_MARGIN ? deadline / 4 : WRSN_PULL_MARGIN) && blockIdx.x != 0) return;
-        if (threadIdx.x == 0) atomicMax(&dp->queue[8 + (blockIdx.x & 63)], (int)blockIdx.x + 1);    // the next launch starts behind the last environment taken
-        env = dp->queue[1] + (int)blockIdx.x; env = env >= B ? env - B : env;
-        if (dp->qskip[env]) return;
-        t_slice_end = t_end;
-    } else if (!reset_call) {
-        // (`block0`: a step call may come as two launches over the two halves of the launch order -- see wrsn_step in wrsn_api.hip)
-        const int bidx = (int)blockIdx.x + block0;
-        env = dp->order[bidx];
-        if (env < 0 || env >= dp->B) return;
-        if (budget > 0) {
-            // blocks are dispatched in index order: a block far behind the first `slots` ones starts late, and what it is
-            // allowed to spend shrinks accordingly so that the launch does not wait for late long jobs
-            // (`slots` packs three launch parameters: wave slots of the device, block at which the taper starts, blocks over which the
-            //  budget falls to zero -- the floor of a quarter applies before that)
-            const int n_slots = slots & 0xFFFF, t_start = (slots >> 16) & 0xFF, t_len = (slots >> 24) & 0xFF;
-            const int k = bidx - t_start * (n_slots / 8);
-#ifndef WRSN_BUDGET_FLOOR
-#define WRSN_BUDGET_FLOOR 4
-#endif
-            if (k > 0) { const int cut = (int)((long long)budget * k / (t_len * (n_slots / 8))); budget = (budget - cut > budget / WRSN_BUDGET_FLOOR) ? budget - cut : budget / WRSN_BUDGET_FLOOR; }
-        }
-    }
-    if (env < 0 || env >= dp->B) return;
-    for (int pass = 0; pass < 256; ++pass) {
-        const int r = wrsn_step_env<NPL, HEAVY, STOCH>(dp, env, reset_call, agent_id, action, auto_reset, budget, epoch, env_mask, out, handoff, deadline, smem, t_slice_end);   // the one call site
-        if (HEAVY || !(r & 1)) break;
-        // the common-path simulator stopped in front of a rare service: the full simulator takes that one item, then this one goes on
-        __syncthreads();
-        wrsn_step_env_full<NPL>(dp, env, epoch, out);
-        __syncthreads();
-        if (wu(dp->live.dyn[env].susp) == 0) break;        // the step ended in there: its request is written
-        if (budget > 0) { budget -= (r >> 1) + 64; if (budget < 16) budget = 16; }
-    }
-}
-template <int NPL, bool HEAVY>
-__global__ void __launch_bounds__(64, WRSN_WAVES_PER_SIMD(NPL))
-wrsn_step_kernel(const WrsnDev* __restrict__ dp, int reset_call, const int32_t* __restrict__ agent_id, const double* __restrict__ action, int auto_reset,
-                 int budget, long long epoch, int slots, const uint8_t* __restrict__ env_mask, WrsnStepOutDev out, int handoff, int deadline, int block0) {
-    wrsn_step_blocks<NPL, HEAVY, false>(dp, reset_call, agent_id, action, auto_reset, budget, epoch, slots, env_mask, out, handoff, deadline, block0);
-}
-// the stochastic variant (prob_gp < 1): the full simulator with the MT19937 draws; same arguments, same launches
-template <int NPL>
-__global__ void __launch_bounds__(64, WRSN_WAVES_PER_SIMD(NPL))
-wrsn_step_stoch_kernel(const WrsnDev* __restrict__ dp, int reset_call, const int32_t* __restrict__ agent_id, const double* __restrict__ action, int auto_reset,
-                       int budget, long long epoch, int slots, const uint8_t* __restrict__ env_mask, WrsnStepOutDev out, int handoff, int deadline, int block0) {
-    wrsn_step_blocks<NPL, true, true>(dp, reset_call, agent_id, action, auto_reset, budget, epoch, slots, env_mask, out, handoff, deadline, block0);
-}
-
-template <int NPL, bool HEAVY, bool STOCH>
-__device__ __forceinline__ int wrsn_step_env(const WrsnDev* __restrict__ dp, int env, int reset_call, const int32_t* __restrict__ agent_id,
-                                             const double* __restrict__ action, int auto_reset, int budget, long long epoch,
-                                             const uint8_t* __restrict__ env_mask, const WrsnStepOutDev& out, int handoff, int deadline, double* smem, long long t_end) {
+//            (4 = go on with the step in flight whatever the caller's rows say: a value no caller passes.)
+template <int NPL, bool STOCH>
+__device__ __forceinline__ void wrsn_step_env(const WrsnDev* __restrict__ dp, int env, int reset_call, const int32_t* __restrict__ agent_id,
+                                              const double* __restrict__ action, int auto_reset, int budget, long long epoch,   // (`epoch`: an unused argument)
+                                              const uint8_t* __restrict__ env_mask, const WrsnStepOutDev& out, int handoff, int deadline, double* smem, long long t_end) {
     const int lane = threadIdx.x;
     bool do_reset = reset_call != 0;
     // a row nobody handles in this launch is not rendered and none of its outputs is touched
-    if (reset_call && env_mask && env_mask[env] == 0) { if (lane == 0) { dp->render_agent[env] = -1; dp->row_state[env] = 0; } return 0; }
+    if (reset_call && env_mask && env_mask[env] == 0) { if (lane == 0) { dp->render_agent[env] = -1; dp->row_state[env] = 0; } return; }
     int aid = -1, resume = 0;
     const double* act_src = action + (size_t)env * 3;
-    if (handoff == 4) resume = 1;                          // the full simulator called for one item of the step in flight
+    if (handoff == 4) resume = 1;                          // a hand-off value no caller passes
     else if (handoff == 3) {                               // time-sliced launch: the action waits in the latch, the caller's row is not looked at
         const WrsnEnvDyn* dy = dp->live.dyn + env;
         resume = dy->susp;
-        if (!resume) { if (!dy->lat_valid) return 0; aid = dy->lat_agent; act_src = dy->lat_action; }
+        if (!resume) { if (!dy->lat_valid) return; aid = dy->lat_agent; act_src = dy->lat_action; }
         if (auto_reset && dy->terminal_pending) do_reset = true;
     } else if (!reset_call) {
         aid = agent_id[env];
-        if (aid == -2) { if (lane == 0) { dp->render_agent[env] = -1; dp->row_state[env] = 0; } return 0; }
+        if (aid == -2) { if (lane == 0) { dp->render_agent[env] = -1; dp->row_state[env] = 0; } return; }
         resume = dp->live.dyn[env].susp;                   // a step in flight goes on; agent_id / action are not looked at
         if (auto_reset && dp->live.dyn[env].terminal_pending) do_reset = true;
     }
     if (reset_call && lane == 0) dp->live.dyn[env].lat_valid = 0;   // a reset environment holds no latched action
-    Sim<NPL, HEAVY, STOCH> s;
+    Sim<NPL, STOCH> s;
     s.bind(dp, env, lane, smem);
     if (handoff == 3) { s.t_deadline = t_end; s.t_exact = t_end - (deadline / 2 < WRSN_EXACT_MARGIN ? deadline / 2 : WRSN_EXACT_MARGIN); }   // the time-sliced launch stamped its start itself
     else if (deadline > 0 && budget > 0 && !reset_call) {    // common deadline of the launch: `deadline` ticks after its first wave started
@@ -2706,7 +2589,72 @@ __device__ __forceinline__ int wrsn_step_env(const WrsnDev* __restrict__ dp, int
     if (lane == 0) { dp->counters[(size_t)env * 24 + 22] = wt0_; dp->counters[(size_t)env * 24 + 23] = wall_clock64(); }
 #endif
 #endif
-    return (!HEAVY && susp && s.need_heavy == 1) ? ((s.work << 1) | 1) : 0;
+}
+
+template <int NPL, bool STOCH>
+__device__ __forceinline__ void wrsn_step_blocks(const WrsnDev* dp, int reset_call, const int32_t* agent_id, const double* action,
+                                                 int auto_reset, int budget, long long epoch, int slots, const uint8_t* env_mask, WrsnStepOutDev out,
+                                                 int handoff, int deadline, int block0) {
+    extern __shared__ double smem[];
+    // Block b of a step launch takes environment order[b]: the environments sorted by the work their WRSN.step still needs,
+    // longest first (wrsn_estimate_kernel / wrsn_sort_kernel run in front of every step launch).  The duration of a WRSN.step is
+    // heavy-tailed and a launch ends with its last wave, so the long jobs have to start first; every environment appears exactly once
+    // in the order, so a launch owns an environment through one block only.
+    // The heavy launch has one block per environment of the batch too; block b takes entry b of the list and the blocks behind the end of the
+    // list leave at once (the host does not know its length).
+    int env = blockIdx.x; long long t_slice_end = 0;
+    if (handoff == 3) {
+        // Time-sliced launch (wrsn_set_step_deadline): the blocks of the launch share ONE deadline (`deadline` ticks after the first of them
+        // started).  Block b takes environment (start + b) mod B of this launch's cyclic order; the hardware hands the blocks to the wave slots
+        // in index order as slots become free, so every slot is busy from the first microsecond on.  A wave runs its WRSN.step until it
+        // returns or the deadline passes (then it stops at the next item boundary, like a wave out of budget).  A block that only starts
+        // when the launch is about to end leaves at once and does NOT touch its environment: the action waits in the latch
+        // (wrsn_latch_kernel), the row says "in flight", and the next launch starts its cyclic order there.
+        const int B = dp->B;
+        if ((int)blockIdx.x >= B) return;
+        // (the launch's start was stamped by wrsn_latch_kernel, a few microseconds ago: thousands of blocks racing for one stamp with an
+        //  atomic -- and for one "last block taken" word -- took 70 us to get going; the word is spread over 64 addresses)
+        const long long tn = (long long)wall_clock64();       // wave-uniform (s_memrealtime)
+        const long long t_end = wu((int64_t)*dp->launch_t0) + deadline;
+        // too late to do anything for this environment in this launch?  (margin: at most a quarter of the time slice)
+        if (tn > t_end - (deadline / 4 < WRSN_PULL_MARGIN ? deadline / 4 : WRSN_PULL_MARGIN) && blockIdx.x != 0) return;
+        if (threadIdx.x == 0) atomicMax(&dp->queue[8 + (blockIdx.x & 63)], (int)blockIdx.x + 1);    // the next launch starts behind the last environment taken
+        env = dp->queue[1] + (int)blockIdx.x; env = env >= B ? env - B : env;
+        if (dp->qskip[env]) return;
+        t_slice_end = t_end;
+    } else if (!reset_call) {
+        // (`block0`: a step call may come as two launches over the two halves of the launch order -- see wrsn_step in wrsn_api.hip)
+        const int bidx = (int)blockIdx.x + block0;
+        env = dp->order[bidx];
+        if (env < 0 || env >= dp->B) return;
+        if (budget > 0) {
+            // blocks are dispatched in index order: a block far behind the first `slots` ones starts late, and what it is
+            // allowed to spend shrinks accordingly so that the launch does not wait for late long jobs
+            // (`slots` packs three launch parameters: wave slots of the device, block at which the taper starts, blocks over which the
+            //  budget falls to zero -- the floor of a quarter applies before that)
+            const int n_slots = slots & 0xFFFF, t_start = (slots >> 16) & 0xFF, t_len = (slots >> 24) & 0xFF;
+            const int k = bidx - t_start * (n_slots / 8);
+#ifndef WRSN_BUDGET_FLOOR
+#define WRSN_BUDGET_FLOOR 4
+#endif
+            if (k > 0) { const int cut = (int)((long long)budget * k / (t_len * (n_slots / 8))); budget = (budget - cut > budget / WRSN_BUDGET_FLOOR) ? budget - cut : budget / WRSN_BUDGET_FLOOR; }
+        }
+    }
+    if (env < 0 || env >= dp->B) return;
+    wrsn_step_env<NPL, STOCH>(dp, env, reset_call, agent_id, action, auto_reset, budget, epoch, env_mask, out, handoff, deadline, smem, t_slice_end);   // the one call site
+}
+template <int NPL>
+__global__ void __launch_bounds__(64, WRSN_WAVES_PER_SIMD(NPL))
+wrsn_step_kernel(const WrsnDev* __restrict__ dp, int reset_call, const int32_t* __restrict__ agent_id, const double* __restrict__ action, int auto_reset,
+                 int budget, long long epoch, int slots, const uint8_t* __restrict__ env_mask, WrsnStepOutDev out, int handoff, int deadline, int block0) {
+    wrsn_step_blocks<NPL, false>(dp, reset_call, agent_id, action, auto_reset, budget, epoch, slots, env_mask, out, handoff, deadline, block0);
+}
+// the stochastic variant (prob_gp < 1): the simulator with the MT19937 draws; same arguments, same launches
+template <int NPL>
+__global__ void __launch_bounds__(64, WRSN_WAVES_PER_SIMD(NPL))
+wrsn_step_stoch_kernel(const WrsnDev* __restrict__ dp, int reset_call, const int32_t* __restrict__ agent_id, const double* __restrict__ action, int auto_reset,
+                       int budget, long long epoch, int slots, const uint8_t* __restrict__ env_mask, WrsnStepOutDev out, int handoff, int deadline, int block0) {
+    wrsn_step_blocks<NPL, true>(dp, reset_call, agent_id, action, auto_reset, budget, epoch, slots, env_mask, out, handoff, deadline, block0);
 }
 
 // ------------------------------------------------------------------ work-queue launches: latch the actions, preset the rows
