@@ -35,6 +35,7 @@ def main():
     ap.add_argument("--step-budget", type=int, default=1250)
     ap.add_argument("--infer-chunk", type=int, default=512)
     ap.add_argument("--inference-dtype", default=None, choices=[None, "bf16", "fp16"], help="reduced-precision roll-out inference (update stays float32)")
+    ap.add_argument("--obs-dtype", default="float32", choices=["float32", "bfloat16"], help="observation format of the environment and the roll-out buffers")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:       # launcher-free multi-rank entry: before this process touches torch or the GPU
         from multi_agent_rl_wrsn_amd.sharding import launch_ranks
@@ -55,7 +56,7 @@ def main():
     torch.cuda.set_device(dev)
     B, N, M = args.envs, args.nodes, 3
     env = VecWRSN([synth_scenario(rank * B + e, N, N) for e in range(B)], None, M, auto_reset=True, step_budget=args.step_budget, device=str(dev),
-                  reuse_obs=True)                             # BatchedIPPO only reads the state tensor (index_select / copies)
+                  reuse_obs=True, obs_dtype=args.obs_dtype)                             # BatchedIPPO only reads the state tensor (index_select / copies)
     algo = BatchedIPPO(dict(batch_size=args.batch_size, minibatch_size=args.minibatch_size, n_updates_per_iteration=args.updates), env,
                        capacity=max(2 * args.batch_size, 4096), infer_chunk=args.infer_chunk, inference_dtype=args.inference_dtype,
                        min_bucket=args.infer_chunk)           # ONE batch shape for every inference pass: MIOpen searches its convolution kernels per shape (seconds each)
@@ -81,7 +82,7 @@ def main():
     out = {"metric": "IPPO roll-out + train, 4096 envs/GPU x 200 nodes x 3 MC (BASELINE configs[2]; configs[3] under torchrun)", "n_gpus": world,
            "returns_table_rows": int(table.shape[0]), "env_steps_all_ranks": steps_all, "env_steps_per_s_with_training_all_ranks": steps_all / wall, "iterations": it, "warmup_iterations": args.warmup_iters,
            "config": {"workload": "%d envs x %d nodes x %d MC, UNet actor + CNN critic per charger, density-map actions, batch %d / minibatch %d / %d epochs" %
-                      (B, N, M, args.batch_size, args.minibatch_size, args.updates), "step_budget": args.step_budget,
+                      (B, N, M, args.batch_size, args.minibatch_size, args.updates), "step_budget": args.step_budget, "obs_dtype": args.obs_dtype,
                       "policy": "float32, channels-last%s" % ("" if not args.inference_dtype else ", %s roll-out inference" % args.inference_dtype)},
            "per_iteration_s": {"environment": t["env_s"] / it, "policy_inference": t["policy_s"] / it, "rollout_glue": t["glue_s"] / it, "ppo_update": t["train_s"] / it,
                                "wall": wall / it},

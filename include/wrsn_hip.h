@@ -73,7 +73,8 @@ typedef struct wrsn_step_out {
     double  *reward;          /* [B]  get_reward (WRSN.py:222-227); 0 when agent_id < 0            */
     uint8_t *terminal;        /* [B]  1 when net.alive == 0 at return (WRSN.py:312)                */
     double  *now;             /* [B]  env.now at return                                            */
-    float   *obs;             /* [B,4,G,G] get_state(agent_id) (WRSN.py:130-186); untouched rows for agent_id < 0 */
+    float   *obs;             /* [B,4,G,G] get_state(agent_id) (WRSN.py:130-186); untouched rows for agent_id < 0;
+                                 uint16 bf16 bit patterns with WRSN_OBS_BF16 (wrsn_set_obs_format) */
     int32_t *status;          /* [B]  0 ok; 1 step fell off the end (reference returns None);
                                       2 every charger dead (reference would hang); 3 auto-reset performed;
                                       4 the step is still in flight (wrsn_set_step_budget), call wrsn_step again;
@@ -203,7 +204,7 @@ int wrsn_rollout_table(wrsn_t *h, double *dst, int32_t zero_after);
  *              (it keeps counting past `capacity`: the excess is dropped, not stored). */
 typedef struct wrsn_transition_buffers {
     int32_t capacity, action_elems;
-    float   *pend_state;      /* [B, M, 4, G, G] */
+    float   *pend_state;      /* [B, M, 4, G, G]  (this, state and next_state: uint16 bf16 patterns with WRSN_OBS_BF16) */
     float   *pend_action;     /* [B, M, action_elems] */
     float   *pend_logp;       /* [B, M] */
     uint8_t *pend_valid;      /* [B, M]  1: the charger has acted in the running episode */
@@ -219,7 +220,7 @@ typedef struct wrsn_transition_buffers {
 
 /* The chargers named by agent_id (DEVICE int32 [B], < 0: row skipped) are about to be given `action` (DEVICE float
  * [B, action_elems], the policy's raw output) chosen with log-probability logp (DEVICE float [B]) on observation obs (DEVICE
- * float [B,4,G,G]): remember them as pending (IPPO.py:141-142).  Call before wrsn_step with the same agent_id. */
+ * [B,4,G,G] in the handle's observation format): remember them as pending (IPPO.py:141-142).  Call before wrsn_step with the same agent_id. */
 int wrsn_rollout_record(wrsn_t *h, const wrsn_transition_buffers *buf, const int32_t *agent_id, const float *action,
                         const float *logp, const float *obs);
 
@@ -230,7 +231,8 @@ int wrsn_rollout_record(wrsn_t *h, const wrsn_transition_buffers *buf, const int
  * the last environment launch did, so a request is consumed once however often this is called. */
 int wrsn_rollout_collect(wrsn_t *h, const wrsn_transition_buffers *buf, const wrsn_step_out *out);
 
-/* Render get_state(agent) for arbitrary agents (DEVICE int32 [B], < 0 = skip) into obs (DEVICE). */
+/* Render get_state(agent) for arbitrary agents (DEVICE int32 [B], < 0 = skip) into obs (DEVICE [B,4,G,G] in the handle's
+ * observation format, wrsn_set_obs_format). */
 int wrsn_render(wrsn_t *h, const int32_t *agent_id, float *obs);
 
 /* Copy internal state to HOST memory (parity tests, `net` / `agents` views).  Synchronises. */
@@ -242,6 +244,19 @@ int wrsn_peek(wrsn_t *h, int32_t what, void *dst);
  * of a row alone when no simulated second has passed since it rendered that row at that address (a WRSN.step that returns at the
  * instant it was called) and writes only maps 2..4.  Results are bit-identical; default off. */
 int wrsn_set_obs_reuse(wrsn_t *h, int32_t on);
+
+/* Observation format of the handle; default WRSN_OBS_F32.  With WRSN_OBS_BF16 every observation the library writes or copies
+ * holds bfloat16 bit patterns, uint16 [.,4,G,G], half the bytes: wrsn_step_out.obs of wrsn_reset, wrsn_step (every launch mode),
+ * wrsn_load_envs and wrsn_clone_envs; the obs of wrsn_render and wrsn_rollout_record; pend_state, state and next_state of
+ * wrsn_transition_buffers (actions, log-probabilities and rewards stay float32).  The declared pointer types stay `float *`: the
+ * pointee type follows the handle's format.  A buffer for B rows is B*4*G*G*2 bytes and no byte beyond it is touched; rows the
+ * float32 format leaves untouched stay untouched.  Every cell is the float32 value of the float32 format rounded to nearest even
+ * (bit for bit; on the device a float32 subnormal may become a zero of its sign).  Rows of 4-column groups are written with 8-byte
+ * stores when map_size is a multiple of 4, with 2-byte stores otherwise.  Allowed between any two calls; affects the launches
+ * enqueued after it.  Map-1 reuse (wrsn_set_obs_reuse) does not carry over a change of format at the same address.  Environment
+ * records do not depend on the format.  Any other value: WRSN_ERR_ARG, handle unchanged. */
+enum wrsn_obs_format { WRSN_OBS_F32 = 0, WRSN_OBS_BF16 = 1 };
+int wrsn_set_obs_format(wrsn_t *h, int32_t format);
 
 /* Per-kernel timing of the step path with HIP events recorded on the handle's stream (the stream the kernels are launched on).
  * wrsn_set_timing(h, 1) makes every following wrsn_step record four events; wrsn_kernel_times waits for the last call and

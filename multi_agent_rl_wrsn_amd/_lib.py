@@ -19,6 +19,7 @@ PEEK_NODE_ENERGY, PEEK_NODE_CS, PEEK_NODE_RR, PEEK_NODE_STATUS, PEEK_NODE_LEVEL 
 PEEK_MC, PEEK_ENV, PEEK_NODE_DEGREE, PEEK_NODE_NCOVER, PEEK_NODE_DIRECT = 5, 6, 7, 8, 9
 PEEK_TARGETS_ACTIVE = 11
 PEEK_RNG_STATE = 12          # uint32 [B, 627]: MT19937 words, index (random.getstate()[1]), draws since reset (low, high word)
+OBS_F32, OBS_BF16 = 0, 1     # wrsn_set_obs_format: float32 cells / bfloat16 bit patterns (uint16) behind every observation pointer
 MC_FIELDS = ("loc_x", "loc_y", "energy", "status", "type_charging", "cur_x", "cur_y", "cur_t", "n_conn",
              "excl", "prev_minfit", "act0", "act1", "act2", "_r0", "_r1")
 ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max", "charging_time_max",
@@ -26,7 +27,7 @@ ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max"
 
 # every entry point include/wrsn_hip.h declares
 EXPORTS = ("wrsn_create", "wrsn_destroy", "wrsn_set_stream", "wrsn_set_scenario", "wrsn_set_scenario_seeded", "wrsn_reset", "wrsn_step",
-           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_render", "wrsn_set_obs_reuse", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
+           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_render", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
            "wrsn_clone_envs", "wrsn_synth_network",
            "wrsn_last_error",
            "wrsn_version")
@@ -98,6 +99,8 @@ def bind(lib):
     lib.wrsn_rollout_collect.restype = C.c_int
     lib.wrsn_set_obs_reuse.argtypes = [vp, C.c_int32]
     lib.wrsn_set_obs_reuse.restype = C.c_int
+    lib.wrsn_set_obs_format.argtypes = [vp, C.c_int32]
+    lib.wrsn_set_obs_format.restype = C.c_int
     lib.wrsn_set_timing.argtypes = [vp, C.c_int32]
     lib.wrsn_set_timing.restype = C.c_int
     lib.wrsn_kernel_times.argtypes = [vp, vp]
@@ -264,6 +267,10 @@ class RawHandle:
 
     def set_obs_reuse(self, on):
         check(self.lib, self.lib.wrsn_set_obs_reuse(self._h, 1 if on else 0))
+
+    def set_obs_format(self, fmt):
+        """OBS_F32 / OBS_BF16 for every observation written or copied by the calls that follow (anything else: WrsnError)."""
+        check(self.lib, self.lib.wrsn_set_obs_format(self._h, int(fmt)))
 
     def set_timing(self, on):
         check(self.lib, self.lib.wrsn_set_timing(self._h, 1 if on else 0))

@@ -86,6 +86,7 @@ struct wrsn_handle {
     int lds_pad;               // extra LDS bytes per environment wave (occupancy experiments); diagnostic
     int taper;                 // packed budget taper (start << 16 | length << 24), OR-ed into the `slots` kernel argument
     int obs_reuse;             // wrsn_set_obs_reuse: the caller keeps the observation rows the library wrote
+    int obs_fmt;               // wrsn_set_obs_format: WRSN_OBS_F32 / WRSN_OBS_BF16, the element type behind every observation pointer
     int timing;                // record HIP events around the kernels of every wrsn_step (wrsn_set_timing)
     hipEvent_t ev[5];          // before the order kernels, after them, after the step kernel, after the continuation, after the observation
     int ev_ok, ev_obs;         // events created / the last call rendered an observation
@@ -232,7 +233,10 @@ int launch_env(wrsn_handle* h, int mode, int env0, int nenv, const int32_t* agen
                            auto_reset, bud, epoch, (h->slots & 0xFFFF) | h->taper, mask, out, 0, dl, b0);
     };
     auto obs_launch = [&](hipStream_t st, int b0, int n) {
-        hipLaunchKernelGGL(wrsn_obs_kernel, dim3(n), dim3(256), h->lds_obs, st, h->dev, (const int32_t*)h->dev.render_agent, obs_pipe, h->obs_reuse, (const int32_t*)h->dev.order, b0);
+        if (h->obs_fmt == WRSN_OBS_BF16)
+            hipLaunchKernelGGL(wrsn_obs_bf16_kernel, dim3(n), dim3(256), h->lds_obs, st, h->dev, (const int32_t*)h->dev.render_agent, (uint16_t*)obs_pipe, h->obs_reuse, (const int32_t*)h->dev.order, b0);
+        else
+            hipLaunchKernelGGL(wrsn_obs_kernel, dim3(n), dim3(256), h->lds_obs, st, h->dev, (const int32_t*)h->dev.render_agent, obs_pipe, h->obs_reuse, (const int32_t*)h->dev.order, b0);
     };
     if (mode == WRSN_MODE_WARMUP) hipLaunchKernelGGL(h->warmup_kernel, grid, block, lds, h->stream, (const WrsnDev*)h->d_dev, env0);
     else if (pipe) {
@@ -275,7 +279,10 @@ int launch_env(wrsn_handle* h, int mode, int env0, int nenv, const int32_t* agen
 }
 
 int launch_obs(wrsn_handle* h, const int32_t* agent_id, float* obs) {
-    hipLaunchKernelGGL(wrsn_obs_kernel, dim3(h->dev.B), dim3(256), h->lds_obs, h->stream, h->dev, agent_id, obs, h->obs_reuse, (const int32_t*)nullptr, 0);
+    if (h->obs_fmt == WRSN_OBS_BF16)                           // `obs` holds bf16 bit patterns then (the C-ABI keeps one pointer type)
+        hipLaunchKernelGGL(wrsn_obs_bf16_kernel, dim3(h->dev.B), dim3(256), h->lds_obs, h->stream, h->dev, agent_id, (uint16_t*)obs, h->obs_reuse, (const int32_t*)nullptr, 0);
+    else
+        hipLaunchKernelGGL(wrsn_obs_kernel, dim3(h->dev.B), dim3(256), h->lds_obs, h->stream, h->dev, agent_id, obs, h->obs_reuse, (const int32_t*)nullptr, 0);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -501,7 +508,7 @@ int wrsn_create(const wrsn_cfg* cfg, wrsn_t** out) {
     DeviceGuard guard_(cfg->device);
     if (!guard_.ok) return fail(WRSN_ERR_HIP, "hipSetDevice failed");
     wrsn_handle* h = new wrsn_handle();
-    h->cfg = *cfg; h->stream = nullptr; h->scenario_set = 0; h->step_budget = 0; h->deadline_ticks = 0; h->epoch = 1; h->obs_reuse = 0; h->timing = 0; h->ev_ok = 0; h->ev_obs = 0; h->ev_rec = 0;
+    h->cfg = *cfg; h->stream = nullptr; h->scenario_set = 0; h->step_budget = 0; h->deadline_ticks = 0; h->epoch = 1; h->obs_reuse = 0; h->obs_fmt = WRSN_OBS_F32; h->timing = 0; h->ev_ok = 0; h->ev_obs = 0; h->ev_rec = 0;
     { const char* e = std::getenv("WRSN_PIPE"); h->pipe = (e && *e == '0') ? 0 : 1; }
     { const char* e = std::getenv("WRSN_PIPE_MID_PCT"); h->pipe_mid_pct = e ? std::atoi(e) : 100; if (h->pipe_mid_pct < 10 || h->pipe_mid_pct > 100) h->pipe_mid_pct = 100; }
     { const char* e = std::getenv("WRSN_PIPE_SHORT_PCT"); h->pipe_short_pct = e ? std::atoi(e) : 40; if (h->pipe_short_pct < 5 || h->pipe_short_pct > 100) h->pipe_short_pct = 40; }
@@ -746,6 +753,13 @@ int wrsn_set_obs_reuse(wrsn_t* h, int32_t on) {
     return WRSN_OK;
 }
 
+int wrsn_set_obs_format(wrsn_t* h, int32_t format) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    if (format != WRSN_OBS_F32 && format != WRSN_OBS_BF16) return fail(WRSN_ERR_ARG, "unknown observation format");
+    h->obs_fmt = format;                                       // read at launch time: the launches enqueued so far keep theirs
+    return WRSN_OK;
+}
+
 int wrsn_set_timing(wrsn_t* h, int32_t on) {
     if (!h) return fail(WRSN_ERR_ARG, "null handle");
     WRSN_ON_DEVICE(h);
@@ -825,7 +839,7 @@ int wrsn_rollout_record(wrsn_t* h, const wrsn_transition_buffers* buf, const int
     if (!h || !agent_id || !action || !logp || !obs) return fail(WRSN_ERR_ARG, "null argument");
     WrsnTrBuffers t; int rc = tr_buffers(buf, &t); if (rc) return rc;
     WRSN_ON_DEVICE(h);
-    hipLaunchKernelGGL(wrsn_tr_record_kernel, dim3(h->dev.B), dim3(256), 0, h->stream, h->dev.B, h->dev.M, h->dev.G, t, agent_id, action, logp, obs);
+    hipLaunchKernelGGL(wrsn_tr_record_kernel, dim3(h->dev.B), dim3(256), 0, h->stream, h->dev.B, h->dev.M, h->dev.G, t, agent_id, action, logp, obs, h->obs_fmt == WRSN_OBS_BF16 ? 2 : 4);
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }
@@ -836,7 +850,7 @@ int wrsn_rollout_collect(wrsn_t* h, const wrsn_transition_buffers* buf, const wr
     WrsnTrBuffers t; int rc = tr_buffers(buf, &t); if (rc) return rc;
     WRSN_ON_DEVICE(h);
     hipLaunchKernelGGL(wrsn_tr_collect_kernel, dim3(h->dev.B), dim3(256), 16, h->stream, h->dev.B, h->dev.M, h->dev.G, t, out->agent_id,
-                       out->reward, out->now, h->dev.row_state, out->obs);
+                       out->reward, out->now, h->dev.row_state, out->obs, h->obs_fmt == WRSN_OBS_BF16 ? 2 : 4);
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }

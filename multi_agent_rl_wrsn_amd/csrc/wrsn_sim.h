@@ -3089,14 +3089,45 @@ typedef float wrsn_v16f __attribute__((ext_vector_type(16)));
 // value of the first active lane for the whole wave (the CPU emulator of tests/emu supplies its own rendezvous)
 WDEV int wrsn_wave_first(int v) { return __builtin_amdgcn_readfirstlane(v); }
 #endif
+// ---- bf16 observations (wrsn_set_obs_format).  The float32 value of every cell is computed exactly as for the float32 format and
+// rounded to nearest even at the store: two values per v_cvt_pk_bf16_f32 on gfx950.  A compiler without a bf16 type (the CPU
+// emulator of tests/emu is built by g++) takes the integer form of the same rounding: bit-identical for every finite value.
+#ifndef WRSN_PK_BF16_DEFINED
+#if defined(__HIPCC__)
+typedef float wrsn_v2f __attribute__((ext_vector_type(2)));
+typedef __bf16 wrsn_v2bf __attribute__((ext_vector_type(2)));
+WDEV uint32_t wrsn_pk_bf16(float lo, float hi) {             // bits of bf16(lo) | bits of bf16(hi) << 16
+    wrsn_v2f v; v.x = lo; v.y = hi;
+    const wrsn_v2bf r = __builtin_convertvector(v, wrsn_v2bf);
+    return __builtin_bit_cast(uint32_t, r);
+}
+WDEV uint16_t wrsn_bf16(float x) { const __bf16 r = (__bf16)x; return __builtin_bit_cast(uint16_t, r); }
+#else
+WDEV uint16_t wrsn_bf16(float x) {
+    uint32_t u; memcpy(&u, &x, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);   // NaN stays a (quiet) NaN
+    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+WDEV uint32_t wrsn_pk_bf16(float lo, float hi) { return (uint32_t)wrsn_bf16(lo) | ((uint32_t)wrsn_bf16(hi) << 16); }
+#endif
+#endif
+struct alignas(8) wrsn_bf16x4 { uint32_t lo, hi; };        // four bf16 cells: one 8-byte store
+WDEV wrsn_bf16x4 wrsn_pk_bf16x4(float a, float b, float c, float e) { wrsn_bf16x4 r; r.lo = wrsn_pk_bf16(a, b); r.hi = wrsn_pk_bf16(c, e); return r; }
+// element type and conversion of an observation cell per format (BF: bf16 bit patterns in uint16, else float32 as computed)
+template <bool BF> struct WrsnObsFmt { typedef float T; static WDEV float cvt(float x) { return x; } };
+template <> struct WrsnObsFmt<true> { typedef uint16_t T; static WDEV uint16_t cvt(float x) { return wrsn_bf16(x); } };
 // `reuse` (wrsn_set_obs_reuse): map 1 depends on node state only.  When no grid item ran since it was last rendered into this very row
 // (a WRSN.step that returns at the instant it was called -- 40 % of the steps of short episodes -- or the same charger asked twice),
 // the row still holds it: only maps 2..4, which depend on the asking charger, are written.
 // `row_map` (optional): block b renders environment row_map[map0 + b] -- a step call renders the half of the batch whose steps are short
 // (by the launch order) while the long half is still being stepped, and the rest afterwards.
-__global__ void __launch_bounds__(256, 4) wrsn_obs_kernel(WrsnDev d, const int32_t* __restrict__ agent_id, float* __restrict__ obs, int reuse,
-                                                           const int32_t* __restrict__ row_map, int map0) {
-    extern __shared__ double smem[];
+// One body, two kernels (below): wrsn_obs_kernel stores float32, wrsn_obs_bf16_kernel the same values as bf16.  The format is a
+// compile-time parameter: the float32 kernel holds no trace of the other one.  The reuse key of a row is its address with the format
+// in the low bit (rows are at least 8-byte aligned): a row rendered in one format is never taken for map 1 of the other.
+template <bool BF>
+__device__ __forceinline__ void wrsn_obs_body(double* smem, const WrsnDev& d, const int32_t* __restrict__ agent_id, void* __restrict__ obs, int reuse,
+                                              const int32_t* __restrict__ row_map, int map0) {
+    typedef typename WrsnObsFmt<BF>::T OT;
     const int env = row_map ? row_map[map0 + (int)blockIdx.x] : (int)blockIdx.x, tid = threadIdx.x;
     if (env < 0 || env >= d.B) return;
     const int aid = agent_id[env];
@@ -3119,9 +3150,10 @@ __global__ void __launch_bounds__(256, 4) wrsn_obs_kernel(WrsnDev d, const int32
     const double unit = 1.0 / G;
     const double hX = ec->charging_range / W, hY = ec->charging_range / H;
     const float inv2hx = (float)(-1.0 / (2.0 * hX * hX)), inv2hy = (float)(-1.0 / (2.0 * hY * hY));
-    float* out = obs + (size_t)env * 4 * G * G;
+    OT* out = (OT*)obs + (size_t)env * 4 * G * G;
     WrsnEnvDyn* dyw = d.live.dyn + env;
-    const bool keep1 = reuse && dyw->map1_valid && dyw->map1_ptr == (uint64_t)(uintptr_t)out;   // block-uniform
+    const uint64_t map1_key = (uint64_t)(uintptr_t)out | (uint64_t)(BF ? 1 : 0);
+    const bool keep1 = reuse && dyw->map1_valid && dyw->map1_ptr == map1_key;   // block-uniform
     // Role of a wave: 0..2 = the 32-row band of map 1 it computes on the matrix cores, 3 = the store wave (rows 96.. of map 1 on the
     // VALU, then maps 2..4).  The roles rotate with the block index so that the (matrix-core-free) store waves of the blocks resident
     // on a CU do not all sit on the same SIMD.
@@ -3289,19 +3321,27 @@ __global__ void __launch_bounds__(256, 4) wrsn_obs_kernel(WrsnDev d, const int32
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
                     const int j = 32 * t + 8 * g4 + 4 * half;
-                    if (j + 3 < G) {
+                    if constexpr (BF) {
+                        // four columns = 8 bytes; aligned whenever G is a multiple of 4 (a row is then a multiple of 8 bytes)
+                        if (j + 3 < G && (G & 3) == 0)
+                            *(wrsn_bf16x4*)(out + (size_t)i * G + j) = wrsn_pk_bf16x4(acc[t][4 * g4], acc[t][4 * g4 + 1], acc[t][4 * g4 + 2], acc[t][4 * g4 + 3]);
+                        else {
+#pragma unroll
+                            for (int q = 0; q < 4; ++q) if (j + q < G) out[(size_t)i * G + j + q] = wrsn_bf16(acc[t][4 * g4 + q]);
+                        }
+                    } else if (j + 3 < G) {
                         float4 v; v.x = acc[t][4 * g4]; v.y = acc[t][4 * g4 + 1]; v.z = acc[t][4 * g4 + 2]; v.w = acc[t][4 * g4 + 3];
                         *(float4*)(out + (size_t)i * G + j) = v;
                     } else {
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) if (j + q < G) out[(size_t)i * G + j + q] = acc[t][4 * g4 + q];
+                        for (int q = 0; q < 4; ++q) if (j + q < G) out[(size_t)i * G + j + q] = WrsnObsFmt<BF>::cvt(acc[t][4 * g4 + q]);
                     }
                 }
             }
         }
     }
     WRSN_OBS_STAMP(4)
-    if (tid == 0 && !keep1) { dyw->map1_valid = 1; dyw->map1_ptr = (uint64_t)(uintptr_t)out; }   // (only consulted with `reuse`)
+    if (tid == 0 && !keep1) { dyw->map1_valid = 1; dyw->map1_ptr = map1_key; }   // (only consulted with `reuse`)
     if (wave == 3 && !keep1) {
         // ---- the store wave, part 1.  Rows 96 .. G-1 of map 1 (4 rows at G = 100: a fourth matrix-core band would be 7/8 idle) as
         // rank-1 updates on the VALU: a lane owns columns l and l + 64, four rows at a time in registers; the same Morton order,
@@ -3332,7 +3372,7 @@ __global__ void __launch_bounds__(256, 4) wrsn_obs_kernel(WrsnDev d, const int32
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                if (rb + q < G) { if (l < G) out[(size_t)(rb + q) * G + l] = a0[q]; if (l + 64 < G) out[(size_t)(rb + q) * G + l + 64] = a1[q]; }
+                if (rb + q < G) { if (l < G) out[(size_t)(rb + q) * G + l] = WrsnObsFmt<BF>::cvt(a0[q]); if (l + 64 < G) out[(size_t)(rb + q) * G + l + 64] = WrsnObsFmt<BF>::cvt(a1[q]); }
             }
         }
     }
@@ -3348,7 +3388,7 @@ __global__ void __launch_bounds__(256, 4) wrsn_obs_kernel(WrsnDev d, const int32
 #pragma unroll
             for (int c = 0; c < 4; ++c) gq[o][c] = (o < M && jq < nq && j + c < G) ? ty[o * WRSN_OBS_LD + j + c] : 0.f;
         }
-        float* o2 = out + (size_t)G * G + j; float* o3 = o2 + (size_t)G * G; float* o4 = o3 + (size_t)G * G;
+        OT* o2 = out + (size_t)G * G + j; OT* o3 = o2 + (size_t)G * G; OT* o4 = o3 + (size_t)G * G;
         const bool vec = ((G & 3) == 0);
         const int npair = (G + 1) >> 1;
         for (;;) {
@@ -3368,13 +3408,22 @@ __global__ void __launch_bounds__(256, 4) wrsn_obs_kernel(WrsnDev d, const int32
                         else { for (int c = 0; c < 4; ++c) v3[c] = fmaf(t, gq[o][c], v3[c]); }
                     }
                 }
-                if (vec) {
+                if constexpr (BF) {
+                    if (vec) {                             // 8 bytes per lane, map and row (a lane's four columns)
+                        *(wrsn_bf16x4*)(o2 + (size_t)i * G) = wrsn_pk_bf16x4(v1[0], v1[1], v1[2], v1[3]);
+                        *(wrsn_bf16x4*)(o3 + (size_t)i * G) = wrsn_pk_bf16x4(v2[0], v2[1], v2[2], v2[3]);
+                        *(wrsn_bf16x4*)(o4 + (size_t)i * G) = wrsn_pk_bf16x4(v3[0], v3[1], v3[2], v3[3]);
+                    } else {
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) if (j + c < G) { o2[(size_t)i * G + c] = wrsn_bf16(v1[c]); o3[(size_t)i * G + c] = wrsn_bf16(v2[c]); o4[(size_t)i * G + c] = wrsn_bf16(v3[c]); }
+                    }
+                } else if (vec) {
                     float4 a; a.x = v1[0]; a.y = v1[1]; a.z = v1[2]; a.w = v1[3]; *(float4*)(o2 + (size_t)i * G) = a;
                     float4 b; b.x = v2[0]; b.y = v2[1]; b.z = v2[2]; b.w = v2[3]; *(float4*)(o3 + (size_t)i * G) = b;
                     float4 d4; d4.x = v3[0]; d4.y = v3[1]; d4.z = v3[2]; d4.w = v3[3]; *(float4*)(o4 + (size_t)i * G) = d4;
                 } else {
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) if (j + c < G) { o2[(size_t)i * G + c] = v1[c]; o3[(size_t)i * G + c] = v2[c]; o4[(size_t)i * G + c] = v3[c]; }
+                    for (int c = 0; c < 4; ++c) if (j + c < G) { o2[(size_t)i * G + c] = WrsnObsFmt<BF>::cvt(v1[c]); o3[(size_t)i * G + c] = WrsnObsFmt<BF>::cvt(v2[c]); o4[(size_t)i * G + c] = WrsnObsFmt<BF>::cvt(v3[c]); }
                 }
             }
         }
@@ -3384,6 +3433,18 @@ __global__ void __launch_bounds__(256, 4) wrsn_obs_kernel(WrsnDev d, const int32
     if (tid == 0) for (int q = 0; q < 5; ++q) d.counters[(size_t)env * 24 + q] = ot_[q + 1] - ot_[q];
     if (tid == 0) d.counters[(size_t)env * 24 + 5] = ot_[0];
 #endif
+}
+
+__global__ void __launch_bounds__(256, 4) wrsn_obs_kernel(WrsnDev d, const int32_t* __restrict__ agent_id, float* __restrict__ obs, int reuse,
+                                                           const int32_t* __restrict__ row_map, int map0) {
+    extern __shared__ double smem[];
+    wrsn_obs_body<false>(smem, d, agent_id, obs, reuse, row_map, map0);
+}
+// obs: uint16 [B,4,G,G] bf16 bit patterns
+__global__ void __launch_bounds__(256, 4) wrsn_obs_bf16_kernel(WrsnDev d, const int32_t* __restrict__ agent_id, uint16_t* __restrict__ obs, int reuse,
+                                                                const int32_t* __restrict__ row_map, int map0) {
+    extern __shared__ double smem[];
+    wrsn_obs_body<true>(smem, d, agent_id, obs, reuse, row_map, map0);
 }
 
 static inline int wrsn_obs_lds_bytes(int G, int NP) { (void)G; return (NP + 2 * WRSN_OBS_CH) * 8 * 4 + 16 * (NP / WRSN_OBS_CH + 2) + WRSN_OBS_AG_FLOATS * 4 + 2 * WRSN_MAX_MC * WRSN_OBS_LD * 4 + 64; }

@@ -132,7 +132,8 @@ def build_networks(map_size=100):
 class TransitionBuffers:
     """Per-charger transition lists of a batched roll-out, filled by the HIP kernels of csrc/wrsn_rollout.h.
 
-    env          : VecWRSN (rendering on)
+    env          : VecWRSN (rendering on); `pend_state`, `state` and `next_state` take the dtype of its `state` (float32 or bfloat16:
+                   the copy kernels move rows in the environment's observation format)
     capacity     : transitions kept per charger (further ones are counted in `count` and dropped)
     action_elems : size of the policy's raw output per decision: 3, or map_size**2 for density-map policies"""
 
@@ -145,13 +146,14 @@ class TransitionBuffers:
         self.capacity, self.action_elems = C, A
         dev = env.device
         f32 = dict(dtype=torch.float32, device=dev)
-        self.pend_state = torch.zeros((B, M, 4, G, G), **f32)
+        obs = dict(dtype=env.state.dtype, device=dev)
+        self.pend_state = torch.zeros((B, M, 4, G, G), **obs)
         self.pend_action = torch.zeros((B, M, A), **f32)
         self.pend_logp = torch.zeros((B, M), **f32)
         self.pend_valid = torch.zeros((B, M), dtype=torch.uint8, device=dev)
-        self.state = torch.zeros((M, C, 4, G, G), **f32)
+        self.state = torch.zeros((M, C, 4, G, G), **obs)
         self.action = torch.zeros((M, C, A), **f32)
-        self.next_state = torch.zeros((M, C, 4, G, G), **f32)
+        self.next_state = torch.zeros((M, C, 4, G, G), **obs)
         self.reward = torch.zeros((M, C), **f32)
         self.logp = torch.zeros((M, C), **f32)
         self.now = torch.zeros((M, C), dtype=torch.float64, device=dev)
@@ -173,7 +175,7 @@ class TransitionBuffers:
         a = agent_ids.to(device=env.device, dtype=t.int32).contiguous()
         x = actions.to(device=env.device, dtype=t.float32).reshape(env.num_env, self.action_elems).contiguous()
         lp = logp.to(device=env.device, dtype=t.float32).reshape(env.num_env).contiguous()
-        st = (env.state if states is None else states.to(device=env.device, dtype=t.float32)).contiguous()
+        st = (env.state if states is None else states.to(device=env.device, dtype=env.state.dtype)).contiguous()
         self._keep = (a, x, lp, st)                           # alive until the kernel has run
         env._h.rollout_record(self._c, a.data_ptr(), x.data_ptr(), lp.data_ptr(), st.data_ptr())
 
@@ -310,7 +312,11 @@ class PPOLearner:
         return torch.cat(lps)
 
     def _forward(self, net, x, inference=False):
+        """One forward pass over a chunk / minibatch of states.  bfloat16 states (VecWRSN(obs_dtype="bfloat16")) go in as they are under
+        autocast; otherwise this chunk alone is widened to float32 (exact), never a whole buffer."""
         torch = self.torch
+        if x.dtype == torch.bfloat16 and not (inference and self.inference_dtype is not None):
+            x = x.float()
         if self._cl:
             x = x.contiguous(memory_format=torch.channels_last)
         if inference and self.inference_dtype is not None:

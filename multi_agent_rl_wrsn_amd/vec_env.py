@@ -20,6 +20,16 @@ def _mc_spec_dict(agent_type):
     return {k: float(agent_type[k]) for k in MC_SPEC_KEYS}
 
 
+def obs_torch_dtype(obs_dtype):
+    """"float32" / "bfloat16" (or the torch dtypes) -> torch dtype of the observation tensors; anything else: ValueError."""
+    import torch
+    if obs_dtype in ("float32", torch.float32):
+        return torch.float32
+    if obs_dtype in ("bfloat16", torch.bfloat16):
+        return torch.bfloat16
+    raise ValueError("obs_dtype must be 'float32' or 'bfloat16' (or torch.float32 / torch.bfloat16), got %r" % (obs_dtype,))
+
+
 class VecWRSN:
     """Batched WRSN environment on one MI355X.
 
@@ -41,11 +51,16 @@ class VecWRSN:
                 environments in a cyclic order, an environment whose step is not finished (or not even begun: its action then waits in a
                 latch inside the library) reports status 4 / agent_id -1 and goes on in the following launches.  Same requests; which
                 launch reports one depends on timing.  May be combined with a step budget (a cap per visit).
+    obs_dtype : "float32" (default) or "bfloat16" (also torch.float32 / torch.bfloat16): the dtype of `state` and of what `render_state`
+                returns, fixed for the life of the object (`wrsn_set_obs_format`).  A bfloat16 cell is the float32 cell rounded to nearest
+                even by the render kernel itself: half the bytes written per step and kept per stored observation.
     """
 
     def __init__(self, scenarios, agent_type=None, num_agent=3, map_size=100, warm_up_time=100, device="cuda:0",
-                 auto_reset=False, render=True, max_degree=0, max_cover=0, step_budget=0, reuse_obs=False, step_deadline_us=0):
+                 auto_reset=False, render=True, max_degree=0, max_cover=0, step_budget=0, reuse_obs=False, step_deadline_us=0,
+                 obs_dtype="float32"):
         import torch
+        self.obs_dtype = obs_torch_dtype(obs_dtype)            # ValueError before anything is created
         if not torch.cuda.is_available():
             raise RuntimeError("VecWRSN needs a HIP device (torch.cuda.is_available() is False); there is no CPU fallback")
         self.torch = torch
@@ -71,6 +86,8 @@ class VecWRSN:
             self._h = _lib.RawHandle(lib, self.num_env, self.n_node, self.n_target, self.num_agent, self.map_size,
                                      self.warm_up_time, dev_index, max_degree, max_cover)
             self._h.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
+            if self.obs_dtype == torch.bfloat16:
+                self._h.set_obs_format(_lib.OBS_BF16)
             if reuse_obs and self.render:
                 self._h.set_obs_reuse(True)
             self.step_budget = int(step_budget)
@@ -87,7 +104,7 @@ class VecWRSN:
             self.terminal = torch.zeros(B, dtype=torch.uint8, device=self.device)
             self.now = torch.zeros(B, dtype=torch.float64, device=self.device)
             self.status = torch.zeros(B, dtype=torch.int32, device=self.device)
-            self.state = torch.zeros((B, 4, G, G), dtype=torch.float32, device=self.device) if self.render else None
+            self.state = torch.zeros((B, 4, G, G), dtype=self.obs_dtype, device=self.device) if self.render else None
             self._in_agent = torch.zeros(B, dtype=torch.int32, device=self.device)
             self._in_action = torch.zeros((B, 3), dtype=torch.float64, device=self.device)
 
@@ -138,12 +155,17 @@ class VecWRSN:
         return self._result()
 
     def render_state(self, agent_ids, out=None):
-        """get_state(agent) (WRSN.py:130-186) for arbitrary agents; rows with agent < 0 are left untouched."""
+        """get_state(agent) (WRSN.py:130-186) for arbitrary agents; rows with agent < 0 are left untouched.  `out`, when given, is a
+        contiguous [B,4,G,G] tensor of this object's `obs_dtype` on its device."""
         t = self.torch
         self._bind_stream()
         a = agent_ids.to(device=self.device, dtype=t.int32).contiguous()
         if out is None:
-            out = t.zeros((self.num_env, 4, self.map_size, self.map_size), dtype=t.float32, device=self.device)
+            out = t.zeros((self.num_env, 4, self.map_size, self.map_size), dtype=self.obs_dtype, device=self.device)
+        elif out.dtype != self.obs_dtype or out.device != self.device or not out.is_contiguous() or \
+                out.numel() != self.num_env * 4 * self.map_size * self.map_size:
+            raise ValueError("out must be a contiguous %s tensor [%d,4,%d,%d] on %s" %
+                             (self.obs_dtype, self.num_env, self.map_size, self.map_size, self.device))
         self._h.render(a.data_ptr(), out.data_ptr())
         return out
 
