@@ -260,8 +260,9 @@ int wrsn_set_obs_format(wrsn_t *h, int32_t format);
 
 /* Per-kernel timing of the step path with HIP events recorded on the handle's stream (the stream the kernels are launched on).
  * wrsn_set_timing(h, 1) makes every following wrsn_step record four events; wrsn_kernel_times waits for the last call and
- * returns, in milliseconds: ms[0] launch-order kernels (work estimate + sort), ms[1] step kernel, ms[2] continuation launch of the
- * two-launch variant (0 otherwise), ms[3] observation kernel (0 when no observation was requested).  Measurement only. */
+ * returns, in milliseconds: ms[0] launch-order kernels (work estimate + sort), ms[1] step kernel, ms[2] always 0 (the continuation
+ * launch it timed no longer exists; the slot stays for the callers that add it to ms[1]), ms[3] observation kernel (0 when no
+ * observation was requested).  Measurement only. */
 int wrsn_set_timing(wrsn_t *h, int32_t on);
 int wrsn_kernel_times(wrsn_t *h, float *ms);
 

@@ -65,47 +65,42 @@ typedef void (*wrsn_step_fn)(const WrsnDev*, int, const int32_t*, const double*,
 typedef void (*wrsn_warmup_fn)(const WrsnDev*, int);
 
 struct wrsn_handle {
-    wrsn_cfg cfg;
-    WrsnDev dev;
-    hipStream_t stream;
-    int npl;
-    int scenario_set;
-    int lds_env, lds_obs;      // LDS bytes of an environment wave, of an observation block
-    int cc_bound;              // largest WrsnEnvConst.conn_bound of the scenarios set so far (-> WrsnDev.CC)
-    hipStream_t stream2, stream3;   // the later stages of a pipelined step call run here, beside the first one on `stream`
-    hipEvent_t ev_fork, ev_join, ev_join3; int ev2_ok;
-    int cus;                   // compute units of the device
-    int slots;                 // wave slots of the device for the step kernel (CUs x resident waves per CU): launch-order dependent budgets
-    int waves_per_cu;          // what the occupancy query said for this handle's step kernel (diagnostic)
-    long long epoch;           // counter of wrsn_step calls: an argument of the step kernels that they do not read
-    int step_budget;           // work units one wrsn_step launch may spend per environment, 0 = run every step to its end
-    int deadline_ticks;        // wrsn_set_step_deadline in 100 MHz wall-clock ticks, 0 = none
-    int pipe_mid_pct;          // share of the long half that stays on the caller's stream (the rest: third stream); 100 = two stages
-    int pipe_short_pct;        // work cap of the short stage in per cent of the step budget (its stragglers go on in the next call)
-    int pipe, pipe_long_pct;   // step calls that render as a two-stage pipeline over the launch order (WRSN_PIPE=0 disables); share of the long stage
-    int lds_pad;               // extra LDS bytes per environment wave (occupancy experiments); diagnostic
-    int taper;                 // packed budget taper (start << 16 | length << 24), OR-ed into the `slots` kernel argument
-    int obs_reuse;             // wrsn_set_obs_reuse: the caller keeps the observation rows the library wrote
-    int obs_fmt;               // wrsn_set_obs_format: WRSN_OBS_F32 / WRSN_OBS_BF16, the element type behind every observation pointer
-    int timing;                // record HIP events around the kernels of every wrsn_step (wrsn_set_timing)
-    hipEvent_t ev[5];          // before the order kernels, after them, after the step kernel, after the continuation, after the observation
-    int ev_ok, ev_obs;         // events created / the last call rendered an observation
-    int ev_rec;                // a wrsn_step has recorded the events since timing was switched on
-    int bp2;                   // B rounded up to a power of two when the launch order is sorted on the device (B <= 8192), else 0
+    wrsn_cfg cfg{};
+    WrsnDev dev{};
+    hipStream_t stream = nullptr;
+    int npl = 0;
+    int scenario_set = 0;
+    int lds_env = 0, lds_obs = 0;   // LDS bytes of an environment wave, of an observation block
+    int cc_bound = 0;               // largest WrsnEnvConst.conn_bound of the scenarios set so far (-> WrsnDev.CC)
+    hipStream_t stream2 = nullptr;  // the short stage of a pipelined step call runs here, beside the long one on `stream`
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr; int ev2_ok = 0;
+    int cus = 256;                  // compute units of the device
+    int slots = 0;                  // wave slots of the device for the step kernel (CUs x resident waves per CU): launch-order dependent budgets
+    long long epoch = 1;            // counter of wrsn_step calls: an argument of the step kernels that they do not read
+    int step_budget = 0;            // work units one wrsn_step launch may spend per environment, 0 = run every step to its end
+    int deadline_ticks = 0;         // wrsn_set_step_deadline in 100 MHz wall-clock ticks, 0 = none
+    int pipe = 1;                   // step calls that render run as a two-stage pipeline over the launch order (WRSN_PIPE=0 disables)
+    int obs_reuse = 0;              // wrsn_set_obs_reuse: the caller keeps the observation rows the library wrote
+    int obs_fmt = WRSN_OBS_F32;     // wrsn_set_obs_format: WRSN_OBS_F32 / WRSN_OBS_BF16, the element type behind every observation pointer
+    int timing = 0;                 // record HIP events around the kernels of every wrsn_step (wrsn_set_timing)
+    hipEvent_t ev[4] = {};          // before the order kernels, after them, after the step kernel, after the observation
+    int ev_ok = 0;                  // events created
+    int ev_mask = 0;                // bit i: the last timed wrsn_step recorded ev[i] (time_mark)
+    int bp2 = 0;                    // B rounded up to a power of two when the launch order is sorted on the device (B <= 8192), else 0
     std::vector<void*> allocs;
-    WrsnDev* d_dev;            // device copy of `dev`: the environment kernels read it through the constant cache; `sd` follows it
-    WrsnStochDev sd;           // prob_gp < 1: MT19937 state, send costs, prob_gp per environment (allocated by the first seeded call)
-    int stoch;                 // an environment was loaded with prob_gp != 1 through wrsn_set_scenario_seeded: the stochastic kernels run
-    wrsn_step_fn step_kernel;  // the kernels of this handle's `npl` and `stoch` (select_kernels)
-    wrsn_warmup_fn warmup_kernel;
-    std::vector<uint8_t> filled;   // per environment: holds a scenario (wrsn_set_scenario*, wrsn_load_envs, wrsn_clone_envs)
+    WrsnDev* d_dev = nullptr;       // device copy of `dev`: the environment kernels read it through the constant cache; `sd` follows it
+    WrsnStochDev sd{};              // prob_gp < 1: MT19937 state, send costs, prob_gp per environment (allocated by the first seeded call)
+    int stoch = 0;                  // an environment was loaded with prob_gp != 1 through wrsn_set_scenario_seeded: the stochastic kernels run
+    wrsn_step_fn step_kernel = nullptr;   // the kernels of this handle's `npl` and `stoch` (select_kernels)
+    wrsn_warmup_fn warmup_kernel = nullptr;
+    std::vector<uint8_t> filled;    // per environment: holds a scenario (wrsn_set_scenario*, wrsn_load_envs, wrsn_clone_envs)
     // environment records (wrsn_state.h): the segment table of this handle's layout (generator block iff sd.mt_live), on the host and in
     // device memory; staging for the host index arrays, the gathered headers of a load and the charger list of the observation pass
-    WrsnSeg segs[WRSN_REC_MAXSEG]; int nseg; int64_t rec_bytes;
-    WrsnSeg* d_segs;
-    int32_t* d_idx; size_t idx_cap;
-    uint8_t* d_hdr;                // [B] headers (destinations of a load are distinct)
-    int32_t* d_rend;
+    WrsnSeg segs[WRSN_REC_MAXSEG] = {}; int nseg = 0; int64_t rec_bytes = 0;
+    WrsnSeg* d_segs = nullptr;
+    int32_t* d_idx = nullptr; size_t idx_cap = 0;
+    uint8_t* d_hdr = nullptr;       // [B] headers (destinations of a load are distinct)
+    int32_t* d_rend = nullptr;
 };
 
 namespace {
@@ -122,22 +117,50 @@ int dalloc(wrsn_handle* h, T** p, size_t count) {
     return 0;
 }
 
-int alloc_node_arrays(wrsn_handle* h, WrsnNodeArrays* a) {
-    const size_t B = h->dev.B, NP = h->dev.NP;
-    int rc;
-    if ((rc = dalloc(h, &a->E, B * NP))) return rc;
-    if ((rc = dalloc(h, &a->CS, B * NP))) return rc;
-    if ((rc = dalloc(h, &a->RR, B * NP))) return rc;
-    if ((rc = dalloc(h, &a->d1, B * NP))) return rc;
-    if ((rc = dalloc(h, &a->d2, B * NP))) return rc;
-    if ((rc = dalloc(h, &a->ring, B * WRSN_RING * NP))) return rc;
-    if ((rc = dalloc(h, &a->logbuf, B * NP))) return rc;
-    if ((rc = dalloc(h, &a->ls, B * NP))) return rc;
-    if ((rc = dalloc(h, &a->rcv, B * NP))) return rc;
-    if ((rc = dalloc(h, &a->conn, B * WRSN_MAX_MC * WRSN_CONN_CAP))) return rc;
-    if ((rc = dalloc(h, &a->conn_xy, B * WRSN_MAX_MC * WRSN_CONN_CAP * 2))) return rc;
-    if ((rc = dalloc(h, &a->dyn, B))) return rc;
-    return 0;
+// THE table of per-environment arrays: every array of a handle that holds one slice per environment, in record order.  The order is
+// fixed by record format version 1 (WRSN_REC_VERSION, wrsn_state.h): an array added here changes the format.  Calls
+// f(pointer, bytes of one environment's slice, copy kind) for the arrays of `parts` until one call returns non-zero, and returns that.
+// Allocation (wrsn_create, alloc_stoch) and the segment table of a record (rec_segments) both come from here and from nowhere else, so an
+// array cannot be part of a handle without being part of its records.  Copy kind: WRSN_SEG_DYN for the live WrsnEnvDyn, else
+// WRSN_SEG_V16 = 16-byte copies where base and size allow.  43 arrays in ENV_ARRAYS_DEV, 5 in ENV_ARRAYS_GEN.
+enum { ENV_ARRAYS_DEV = 1,     // WrsnDev: constants, topology, the `live` and `snap` node arrays
+       ENV_ARRAYS_GEN = 2 };   // WrsnStochDev: the generator block of handles that keep generators
+template <typename H, typename F>
+int for_each_env_array(H* h, int parts, F f) {
+    auto& d = h->dev;
+    const int64_t NP = d.NP, TP = d.TP, ECAP = d.ECAP, CCAP = d.CCAP;
+    int rc = 0;
+    auto a = [&](auto& p, int64_t bytes, int kind = WRSN_SEG_V16) { if (!rc) rc = f(p, bytes, kind); };
+    if (parts & ENV_ARRAYS_DEV) {
+        a(d.ec, sizeof(WrsnEnvConst));
+        a(d.node_x, NP * 8); a(d.node_y, NP * 8); a(d.dist_bs, NP * 8);
+        a(d.target_x, TP * 8); a(d.target_y, TP * 8);
+        a(d.nb_off, (NP + 1) * 4); a(d.nb_idx, ECAP * 4); a(d.nb_dist, ECAP * 8);
+        a(d.tc_off, (TP + 1) * 4); a(d.tc_idx, CCAP * 4);
+        a(d.ncov, NP * 4); a(d.nflags, NP * 4); a(d.nbp, NP * 16);
+        a(d.nbp_es, NP * 64); a(d.es_bs, NP * 8); a(d.adjm, NP * 32);
+        a(d.xorder, NP * 4); a(d.tcp, TP * 16);
+        for (int k = 0; k < 2; ++k) {
+            auto& n = k == 0 ? d.live : d.snap;
+            a(n.E, NP * 8); a(n.CS, NP * 8); a(n.RR, NP * 8);
+            a(n.d1, NP * 8); a(n.d2, NP * 8); a(n.ring, WRSN_RING * NP * 8);
+            a(n.logbuf, NP * 8); a(n.ls, NP * 4); a(n.rcv, NP * 4);
+            a(n.conn, WRSN_MAX_MC * WRSN_CONN_CAP * 2); a(n.conn_xy, WRSN_MAX_MC * WRSN_CONN_CAP * 2 * 8);
+            a(n.dyn, sizeof(WrsnEnvDyn), k == 0 ? WRSN_SEG_DYN : WRSN_SEG_V16);
+        }
+    }
+    if (parts & ENV_ARRAYS_GEN) {
+        auto& s = h->sd;
+        a(s.mt_live, WRSN_MT_STRIDE * 4); a(s.mt_snap, WRSN_MT_STRIDE * 4);
+        a(s.es_live, NP * 8); a(s.es_snap, NP * 8); a(s.pgp, 8);
+    }
+    return rc;
+}
+
+// device memory, zero-filled, for the arrays of `parts`: B slices each
+int alloc_env_arrays(wrsn_handle* h, int parts) {
+    const size_t B = h->dev.B;
+    return for_each_env_array(h, parts, [&](auto*& p, int64_t bytes, int) { return dalloc(h, &p, B * (size_t)bytes / sizeof(*p)); });
 }
 
 // the step and warm-up kernels of the handle's nodes-per-lane count, stochastic (prob_gp < 1) or plain
@@ -157,134 +180,181 @@ int configure_launch(wrsn_handle* h) {
     {   // wave slots of the step kernel on this device (registers and LDS decide): the budget taper of a launch starts behind the blocks
         // that are resident from the first moment
         int per_cu = 0;
-        const int lds_b = h->lds_env + h->lds_pad;
-        const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->step_kernel, 64, (size_t)lds_b);
+        const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->step_kernel, 64, (size_t)h->lds_env);
         h->slots = h->cus * 8;
         if (oe == hipSuccess && per_cu >= 1 && per_cu <= 16) h->slots = h->cus * per_cu;
-        h->waves_per_cu = (oe == hipSuccess) ? per_cu : 0;
     }
     HIPCHK(hipMemcpy(h->d_dev, &h->dev, sizeof(WrsnDev), hipMemcpyHostToDevice));
     if (h->stoch) HIPCHK(hipMemcpy(h->d_dev + 1, &h->sd, sizeof(WrsnStochDev), hipMemcpyHostToDevice));
     return 0;
 }
 
-int launch_obs(wrsn_handle* h, const int32_t* agent_id, float* obs);
+// The scenarios or records that just came in need connected-node lists of `conn_bound` entries, and the stochastic kernels if
+// `want_stoch`: WrsnDev.CC is the largest bound so far rounded up to a multiple of 4 (4..WRSN_CONN_CAP); a change of either is a new
+// launch configuration (LDS and wave slots of the step kernel).
+int fit_launch(wrsn_handle* h, int conn_bound, bool want_stoch) {
+    if (conn_bound > h->cc_bound) h->cc_bound = conn_bound;
+    int cc = ((h->cc_bound + 3) / 4) * 4; cc = cc < 4 ? 4 : (cc > WRSN_CONN_CAP ? WRSN_CONN_CAP : cc);
+    const bool stoch_on = want_stoch && !h->stoch;
+    if (cc == h->dev.CC && !stoch_on) return 0;
+    h->dev.CC = cc; if (stoch_on) h->stoch = 1;
+    return configure_launch(h);
+}
 
-// `obs_pipe` (step calls that render): the observations of this call are launched from here, interleaved with the step launches (below)
-int launch_env(wrsn_handle* h, int mode, int env0, int nenv, const int32_t* agent_id, const double* action,
-               int auto_reset, const uint8_t* mask, const WrsnStepOutDev& out, float* obs_pipe = nullptr) {
-    const int lds = h->lds_env + h->lds_pad;
-    const int reset_call = (mode == WRSN_MODE_RESET) ? 1 : 0;
-    const int budget = (mode == WRSN_MODE_STEP) ? h->step_budget : 0;
-    const int dl = (budget > 0 && h->bp2 > 0) ? h->deadline_ticks : 0;     // the sort kernel zeroes the launch stamp
-    dim3 grid(nenv), block(64);
-    long long epoch = 0;
-    if (mode == WRSN_MODE_STEP) epoch = ++h->epoch;
-    const bool queue = (mode == WRSN_MODE_STEP) && h->deadline_ticks > 0;    // work-queue launch (wrsn_set_step_deadline)
-    const bool timed = (mode == WRSN_MODE_STEP) && h->timing && h->ev_ok;
-    if (timed) (void)hipEventRecord(h->ev[0], h->stream);
-    if (queue) {
-        // latch + preset kernel, then one block per environment in this launch's cyclic order: the blocks that only start when the time slice
-        // is over leave their environments alone
-        hipLaunchKernelGGL(wrsn_latch_kernel, dim3((nenv + 255) / 256), dim3(256), 0, h->stream, h->dev, agent_id, action, out);
-        if (timed) (void)hipEventRecord(h->ev[1], h->stream);
-        const int qbudget = budget > 0 ? budget : (1 << 28);   // the deadline is looked at wherever a work budget is
-        hipLaunchKernelGGL(h->step_kernel, grid, block, lds, h->stream, (const WrsnDev*)h->d_dev, 0, agent_id, action,
-                           auto_reset, qbudget, epoch, 0, mask, out, 3, h->deadline_ticks, 0);
-        if (timed) { (void)hipEventRecord(h->ev[2], h->stream); (void)hipEventRecord(h->ev[3], h->stream); h->ev_obs = 0; h->ev_rec = 1; }
-        HIPCHK(hipGetLastError());
-        if (obs_pipe) {
-            int rc = launch_obs(h, h->dev.render_agent, obs_pipe);
-            if (timed) { (void)hipEventRecord(h->ev[4], h->stream); h->ev_obs = 1; }
-            return rc;
-        }
-        return 0;
-    }
-    // A step call that renders, as a PIPELINE over the two halves of the launch order (longest job first): the short half is stepped on the
-    // second stream and rendered there as soon as it is done -- nearly all of its steps complete, it carries ~60 % of the observations of
-    // the call -- while the long half (work-capped or slow steps, the tail of the launch) is still being stepped on the caller's stream;
-    // only the observations of the long half are left for afterwards.  The step kernel is bound by instruction issue and latency and leaves
-    // the HBM idle, the observation kernel is a 160 KB store stream per row: they overlap well.  Same blocks, same budgets, same results.
-    // (only when the batch is at most two rounds of the wave slots: with more, the short half is the longer one and nothing overlaps --
-    //  4 096 environments of 1 000 nodes on 768 slots: 0.87 M env-steps/s with the pipeline, 0.96 M without)
-    const bool pipe = obs_pipe && mode == WRSN_MODE_STEP && h->pipe && h->ev2_ok && h->bp2 > 0 && nenv >= 512 && nenv == h->dev.B && nenv <= 2 * h->slots;
-    if (mode == WRSN_MODE_STEP && h->bp2 > 0) {
-        // launch order of this call, longest job first (wrsn_estimate_kernel / wrsn_sort_kernel, wrsn_sim.h): two tiny launches
-        hipLaunchKernelGGL(wrsn_estimate_kernel, dim3((h->bp2 + WRSN_EST_THREADS - 1) / WRSN_EST_THREADS), dim3(WRSN_EST_THREADS), 0, h->stream, h->dev, agent_id, action, auto_reset, h->bp2);
-        {
-            const int kpt = h->bp2 / WRSN_SORT_THREADS;        // keys per thread of the sort workgroup (0, 1: plain network in LDS)
-            const size_t lb = (size_t)wrsn_sort_lds_bytes();
-#define WRSN_SORT(K_) hipLaunchKernelGGL((wrsn_sort_kernel<K_>), dim3(1), dim3(WRSN_SORT_THREADS), lb, h->stream, h->dev, h->bp2)
-            switch (kpt) {
-            case 2: WRSN_SORT(2); break;
-            case 4: WRSN_SORT(4); break;
-            case 8: WRSN_SORT(8); break;
-            case 16: WRSN_SORT(16); break;
-            case 32: WRSN_SORT(32); break;
-            default: WRSN_SORT(1); break;
-            }
-#undef WRSN_SORT
-        }
-    }
-    if (timed) (void)hipEventRecord(h->ev[1], h->stream);
-    // step launch of blocks [b0, b0 + n) of the launch order on stream `st` with work budget `bud`
-    auto step_launch = [&](hipStream_t st, int b0, int n, int bud) {
-        hipLaunchKernelGGL(h->step_kernel, dim3(n), block, lds, st, (const WrsnDev*)h->d_dev, reset_call, agent_id, action,
-                           auto_reset, bud, epoch, (h->slots & 0xFFFF) | h->taper, mask, out, 0, dl, b0);
-    };
-    auto obs_launch = [&](hipStream_t st, int b0, int n) {
-        if (h->obs_fmt == WRSN_OBS_BF16)
-            hipLaunchKernelGGL(wrsn_obs_bf16_kernel, dim3(n), dim3(256), h->lds_obs, st, h->dev, (const int32_t*)h->dev.render_agent, (uint16_t*)obs_pipe, h->obs_reuse, (const int32_t*)h->dev.order, b0);
-        else
-            hipLaunchKernelGGL(wrsn_obs_kernel, dim3(n), dim3(256), h->lds_obs, st, h->dev, (const int32_t*)h->dev.render_agent, obs_pipe, h->obs_reuse, (const int32_t*)h->dev.order, b0);
-    };
-    if (mode == WRSN_MODE_WARMUP) hipLaunchKernelGGL(h->warmup_kernel, grid, block, lds, h->stream, (const WrsnDev*)h->d_dev, env0);
-    else if (pipe) {
-        // stages over the launch order: [0, n1) the longest jobs (caller's stream), [n1, n2) the rest of the long half (third stream),
-        // [n2, B) the short half with its own work cap (second stream); n2 <= wave slots: the long half's jobs all start at once
-        int n2 = (nenv * h->pipe_long_pct / 100 + 63) & ~63; if (n2 > h->slots) n2 = h->slots & ~63; if (n2 < 64) n2 = 64;
-        int n1 = (n2 * h->pipe_mid_pct / 100 + 63) & ~63; if (n1 > n2 || !h->stream3) n1 = n2; if (n1 < 64) n1 = 64;
-        const int b_short = budget > 0 ? (budget * h->pipe_short_pct / 100 > 64 ? budget * h->pipe_short_pct / 100 : 64) : 0;
-        (void)hipEventRecord(h->ev_fork, h->stream); (void)hipStreamWaitEvent(h->stream2, h->ev_fork, 0);
-        if (n1 < n2) (void)hipStreamWaitEvent(h->stream3, h->ev_fork, 0);
-        step_launch(h->stream2, n2, nenv - n2, b_short);
-        obs_launch(h->stream2, n2, nenv - n2);
-        (void)hipEventRecord(h->ev_join, h->stream2);
-        if (n1 < n2) {
-            step_launch(h->stream3, n1, n2 - n1, budget);
-            obs_launch(h->stream3, n1, n2 - n1);
-            (void)hipEventRecord(h->ev_join3, h->stream3);
-        }
-        step_launch(h->stream, 0, n1, budget);
-        if (timed) { (void)hipEventRecord(h->ev[2], h->stream); (void)hipEventRecord(h->ev[3], h->stream); }
-        obs_launch(h->stream, 0, n1);
-        (void)hipStreamWaitEvent(h->stream, h->ev_join, 0);
-        if (n1 < n2) (void)hipStreamWaitEvent(h->stream, h->ev_join3, 0);
-    }
-    else step_launch(h->stream, 0, nenv, budget);
-    if (pipe) {
-        if (timed) { (void)hipEventRecord(h->ev[4], h->stream); h->ev_obs = 1; h->ev_rec = 1; }
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    if (timed) (void)hipEventRecord(h->ev[2], h->stream);
-    if (timed) { (void)hipEventRecord(h->ev[3], h->stream); h->ev_obs = 0; h->ev_rec = 1; }
+WrsnStepOutDev step_out_dev(const wrsn_step_out* out, bool with_obs = true) {
+    WrsnStepOutDev o;
+    o.agent_id = out->agent_id; o.reward = out->reward; o.terminal = out->terminal; o.now = out->now; o.status = out->status;
+    o.obs = with_obs ? out->obs : nullptr;
+    return o;
+}
+
+// ------------------------------------------------------------------ launches
+// The one observation launch: blocks [block0, block0 + nblocks) of `order` (nullptr: of the environments themselves) on `stream`, float32
+// or bf16 rows as the handle says (`obs` holds bf16 bit patterns then: the C-ABI keeps one pointer type).
+void launch_obs(wrsn_handle* h, hipStream_t stream, const int32_t* agent_id, float* obs, const int32_t* order, int block0, int nblocks) {
+    if (h->obs_fmt == WRSN_OBS_BF16)
+        hipLaunchKernelGGL(wrsn_obs_bf16_kernel, dim3(nblocks), dim3(256), h->lds_obs, stream, h->dev, agent_id, (uint16_t*)obs, h->obs_reuse, order, block0);
+    else
+        hipLaunchKernelGGL(wrsn_obs_kernel, dim3(nblocks), dim3(256), h->lds_obs, stream, h->dev, agent_id, obs, h->obs_reuse, order, block0);
+}
+
+// the whole batch on the caller's stream
+int launch_obs_all(wrsn_handle* h, const int32_t* agent_id, float* obs) {
+    launch_obs(h, h->stream, agent_id, obs, nullptr, 0, h->dev.B);
     HIPCHK(hipGetLastError());
-    if (obs_pipe) {
-        int rc = launch_obs(h, h->dev.render_agent, obs_pipe);
-        if (timed) { (void)hipEventRecord(h->ev[4], h->stream); h->ev_obs = 1; }
-        return rc;
-    }
     return 0;
 }
 
-int launch_obs(wrsn_handle* h, const int32_t* agent_id, float* obs) {
-    if (h->obs_fmt == WRSN_OBS_BF16)                           // `obs` holds bf16 bit patterns then (the C-ABI keeps one pointer type)
-        hipLaunchKernelGGL(wrsn_obs_bf16_kernel, dim3(h->dev.B), dim3(256), h->lds_obs, h->stream, h->dev, agent_id, (uint16_t*)obs, h->obs_reuse, (const int32_t*)nullptr, 0);
-    else
-        hipLaunchKernelGGL(wrsn_obs_kernel, dim3(h->dev.B), dim3(256), h->lds_obs, h->stream, h->dev, agent_id, obs, h->obs_reuse, (const int32_t*)nullptr, 0);
+// wrsn_set_timing: event i of this wrsn_step on the caller's stream; nothing unless the call is timed
+void time_mark(wrsn_handle* h, int i) {
+    if (!h->timing) return;
+    (void)hipEventRecord(h->ev[i], h->stream);
+    h->ev_mask |= 1 << i;
+}
+
+// what the step-kernel launches of one call have in common
+struct StepCall {
+    int reset_call;
+    const int32_t* agent_id; const double* action; int auto_reset;
+    long long epoch;
+    int slots;                 // wave slots (low 16 bits) | budget taper over the launch order; 0: neither (time-sliced launch)
+    const uint8_t* mask;
+    WrsnStepOutDev out;
+    int handoff, deadline;     // 3 / wall-clock ticks for a time-sliced launch, else 0
+};
+
+// budget taper over the launch order in units of slots / 8 blocks, start << 16 | length << 24: start 8 = after the first `slots` blocks,
+// length 16 = down to zero over two times `slots` blocks (the floor of a quarter applies first)
+const int STEP_TAPER = (8 << 16) | (16 << 24);
+int tapered_slots(const wrsn_handle* h) { return (h->slots & 0xFFFF) | STEP_TAPER; }
+
+// the one step-kernel launch: blocks [block0, block0 + nblocks) of the launch order on `stream` with work budget `budget`
+void launch_step_blocks(wrsn_handle* h, const StepCall& c, hipStream_t stream, int block0, int nblocks, int budget) {
+    hipLaunchKernelGGL(h->step_kernel, dim3(nblocks), dim3(64), h->lds_env, stream, (const WrsnDev*)h->d_dev, c.reset_call, c.agent_id, c.action,
+                       c.auto_reset, budget, c.epoch, c.slots, c.mask, c.out, c.handoff, c.deadline, block0);
+}
+
+int launch_warmup(wrsn_handle* h, int env0, int nenv) {
+    hipLaunchKernelGGL(h->warmup_kernel, dim3(nenv), dim3(64), h->lds_env, h->stream, (const WrsnDev*)h->d_dev, env0);
     HIPCHK(hipGetLastError());
     return 0;
+}
+
+// the step kernel as a reset of the environments of `mask`, then their observations when out.obs is set
+int launch_reset(wrsn_handle* h, const uint8_t* mask, const WrsnStepOutDev& out) {
+    const StepCall c = {1, nullptr, nullptr, 0, 0, tapered_slots(h), mask, out, 0, 0};
+    launch_step_blocks(h, c, h->stream, 0, h->dev.B, 0);
+    HIPCHK(hipGetLastError());
+    return out.obs ? launch_obs_all(h, h->dev.render_agent, out.obs) : 0;
+}
+
+// launch order of a step call, longest job first (wrsn_estimate_kernel / wrsn_sort_kernel, wrsn_sim.h): two tiny launches
+void launch_order(wrsn_handle* h, const StepCall& c) {
+    hipLaunchKernelGGL(wrsn_estimate_kernel, dim3((h->bp2 + WRSN_EST_THREADS - 1) / WRSN_EST_THREADS), dim3(WRSN_EST_THREADS), 0, h->stream, h->dev, c.agent_id, c.action, c.auto_reset, h->bp2);
+    const int kpt = h->bp2 / WRSN_SORT_THREADS;                // keys per thread of the sort workgroup (0, 1: plain network in LDS)
+    const size_t lb = (size_t)wrsn_sort_lds_bytes();
+#define WRSN_SORT(K_) hipLaunchKernelGGL((wrsn_sort_kernel<K_>), dim3(1), dim3(WRSN_SORT_THREADS), lb, h->stream, h->dev, h->bp2)
+    switch (kpt) {
+    case 2: WRSN_SORT(2); break;
+    case 4: WRSN_SORT(4); break;
+    case 8: WRSN_SORT(8); break;
+    case 16: WRSN_SORT(16); break;
+    case 32: WRSN_SORT(32); break;
+    default: WRSN_SORT(1); break;
+    }
+#undef WRSN_SORT
+}
+
+// behind the step launch(es) of a call that is not pipelined: one observation launch over the whole batch when the call renders
+int finish_step(wrsn_handle* h, const StepCall& c) {
+    time_mark(h, 2);
+    HIPCHK(hipGetLastError());
+    if (!c.out.obs) return 0;
+    if (int rc = launch_obs_all(h, h->dev.render_agent, c.out.obs)) return rc;
+    time_mark(h, 3);
+    return 0;
+}
+
+// Time-sliced step call (wrsn_set_step_deadline): latch + preset kernel, then one block per environment in this launch's cyclic order:
+// the blocks that only start when the time slice is over leave their environments alone
+int launch_step_sliced(wrsn_handle* h, StepCall c) {
+    const int B = h->dev.B;
+    hipLaunchKernelGGL(wrsn_latch_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->dev, c.agent_id, c.action, c.out);
+    time_mark(h, 1);
+    c.slots = 0; c.handoff = 3; c.deadline = h->deadline_ticks;
+    launch_step_blocks(h, c, h->stream, 0, B, h->step_budget > 0 ? h->step_budget : (1 << 28));   // the deadline is looked at wherever a work budget is
+    return finish_step(h, c);
+}
+
+int launch_step_single(wrsn_handle* h, const StepCall& c) {
+    launch_step_blocks(h, c, h->stream, 0, h->dev.B, h->step_budget);
+    return finish_step(h, c);
+}
+
+// A step call that renders, as a PIPELINE over the two halves of the launch order (longest job first): the short half is stepped on the
+// second stream and rendered there as soon as it is done -- nearly all of its steps complete, it carries ~60 % of the observations of
+// the call -- while the long half (work-capped or slow steps, the tail of the launch) is still being stepped on the caller's stream;
+// only the observations of the long half are left for afterwards.  The step kernel is bound by instruction issue and latency and leaves
+// the HBM idle, the observation kernel is a 160 KB store stream per row: they overlap well.  Same blocks, same budgets, same results.
+// (only when the batch is at most two rounds of the wave slots: with more, the short half is the longer one and nothing overlaps --
+//  4 096 environments of 1 000 nodes on 768 slots: 0.87 M env-steps/s with the pipeline, 0.96 M without)
+bool step_pipelines(const wrsn_handle* h, const StepCall& c) {
+    const int B = h->dev.B;
+    return c.out.obs && h->pipe && h->ev2_ok && h->bp2 > 0 && B >= 512 && B <= 2 * h->slots;
+}
+
+const int PIPE_LONG_PCT = 50;      // share of the launch order that is the long stage
+const int PIPE_SHORT_PCT = 40;     // work cap of the short stage in per cent of the step budget (its stragglers go on in the next call)
+
+// Stages over the launch order: [0, n2) the long half (caller's stream), [n2, B) the short half with its own work cap (second stream, high
+// priority: its blocks get wave slots first); n2 <= wave slots: the long half's jobs all start at once.  The short half is launched first.
+int launch_step_pipeline(wrsn_handle* h, const StepCall& c) {
+    const int B = h->dev.B, budget = h->step_budget;
+    const int32_t* agent = h->dev.render_agent; const int32_t* order = h->dev.order;
+    int n2 = (B * PIPE_LONG_PCT / 100 + 63) & ~63; if (n2 > h->slots) n2 = h->slots & ~63; if (n2 < 64) n2 = 64;
+    const int b_short = budget > 0 ? (budget * PIPE_SHORT_PCT / 100 > 64 ? budget * PIPE_SHORT_PCT / 100 : 64) : 0;
+    (void)hipEventRecord(h->ev_fork, h->stream); (void)hipStreamWaitEvent(h->stream2, h->ev_fork, 0);
+    launch_step_blocks(h, c, h->stream2, n2, B - n2, b_short);
+    launch_obs(h, h->stream2, agent, c.out.obs, order, n2, B - n2);
+    (void)hipEventRecord(h->ev_join, h->stream2);
+    launch_step_blocks(h, c, h->stream, 0, n2, budget);
+    time_mark(h, 2);
+    launch_obs(h, h->stream, agent, c.out.obs, order, 0, n2);
+    (void)hipStreamWaitEvent(h->stream, h->ev_join, 0);
+    time_mark(h, 3);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// one wrsn_step: the step of every environment and, when out.obs is set, the observations of the new requests
+int launch_step(wrsn_handle* h, const int32_t* agent_id, const double* action, int auto_reset, const WrsnStepOutDev& out) {
+    const StepCall c = {0, agent_id, action, auto_reset, ++h->epoch, tapered_slots(h), nullptr, out, 0, 0};
+    h->ev_mask = 0;
+    time_mark(h, 0);
+    if (h->deadline_ticks > 0) return launch_step_sliced(h, c);
+    if (h->bp2 > 0) launch_order(h, c);
+    time_mark(h, 1);
+    return step_pipelines(h, c) ? launch_step_pipeline(h, c) : launch_step_single(h, c);
 }
 
 // xoshiro256** seeded by splitmix64: the synthetic generator's own counter-free RNG
@@ -334,57 +404,19 @@ void mt_seed(int64_t seed, uint32_t* st) {
     st[WRSN_MT_N] = WRSN_MT_N; st[WRSN_MT_N + 1] = 0; st[WRSN_MT_N + 2] = 0; st[WRSN_MT_N + 3] = 0;
 }
 
-int rec_layout(wrsn_handle* h);
-
-// the stochastic block of a handle: MT state (live / snapshot), send costs (live / snapshot), prob_gp = 1 everywhere until set
-int alloc_stoch(wrsn_handle* h) {
-    if (h->sd.mt_live) return 0;
-    const size_t B = h->dev.B, NP = h->dev.NP;
-    int rc;
-    if ((rc = dalloc(h, &h->sd.mt_live, B * WRSN_MT_STRIDE))) return rc;
-    if ((rc = dalloc(h, &h->sd.mt_snap, B * WRSN_MT_STRIDE))) return rc;
-    if ((rc = dalloc(h, &h->sd.es_live, B * NP))) return rc;
-    if ((rc = dalloc(h, &h->sd.es_snap, B * NP))) return rc;
-    if ((rc = dalloc(h, &h->sd.pgp, B))) return rc;
-    std::vector<double> one(B, 1.0);
-    HIPCHK(hipMemcpy(h->sd.pgp, one.data(), B * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_dev + 1, &h->sd, sizeof(WrsnStochDev), hipMemcpyHostToDevice));
-    return rec_layout(h);                                      // records of this handle carry the generator block from now on
-}
-
 // ------------------------------------------------------------------ environment records (wrsn_state.h)
-// The segments of a record in record order: every per-environment slice of the handle's arrays.  with_gen: the generator block too
-// (its base addresses are the handle's, 0 while it has none: then the table only serves to size a record).  Returns the record bytes.
+// The segments of a record: the per-environment slices of for_each_env_array, in its order, each at the next 16-byte aligned offset behind
+// the header.  with_gen: the generator block too (its base addresses are the handle's, 0 while it has none: then the table only serves to
+// size a record).  Returns the record bytes.
 int64_t rec_segments(const wrsn_handle* h, int with_gen, WrsnSeg* segs, int* nseg) {
-    const WrsnDev& d = h->dev;
-    const int64_t NP = d.NP, TP = d.TP;
     int ns = 0; int64_t off = WRSN_REC_HDR;
-    auto add = [&](const void* base, int64_t bytes, int kind) {
+    for_each_env_array(h, ENV_ARRAYS_DEV | (with_gen ? ENV_ARRAYS_GEN : 0), [&](const void* base, int64_t bytes, int kind) {
         WrsnSeg& g = segs[ns++];
         g.base = (uint64_t)(uintptr_t)base; g.stride = bytes; g.bytes = (int32_t)bytes; g.c0 = (int32_t)(off / 16); g.pad = 0;
         g.kind = kind != WRSN_SEG_V16 ? kind : ((g.base % 16 == 0 && bytes % 16 == 0) ? WRSN_SEG_V16 : WRSN_SEG_WORD);
         off += (bytes + 15) & ~(int64_t)15;
-    };
-    add(d.ec, sizeof(WrsnEnvConst), WRSN_SEG_V16);
-    add(d.node_x, NP * 8, WRSN_SEG_V16); add(d.node_y, NP * 8, WRSN_SEG_V16); add(d.dist_bs, NP * 8, WRSN_SEG_V16);
-    add(d.target_x, TP * 8, WRSN_SEG_V16); add(d.target_y, TP * 8, WRSN_SEG_V16);
-    add(d.nb_off, (NP + 1) * 4, WRSN_SEG_V16); add(d.nb_idx, (int64_t)d.ECAP * 4, WRSN_SEG_V16); add(d.nb_dist, (int64_t)d.ECAP * 8, WRSN_SEG_V16);
-    add(d.tc_off, (TP + 1) * 4, WRSN_SEG_V16); add(d.tc_idx, (int64_t)d.CCAP * 4, WRSN_SEG_V16);
-    add(d.ncov, NP * 4, WRSN_SEG_V16); add(d.nflags, NP * 4, WRSN_SEG_V16); add(d.nbp, NP * 16, WRSN_SEG_V16);
-    add(d.nbp_es, NP * 64, WRSN_SEG_V16); add(d.es_bs, NP * 8, WRSN_SEG_V16); add(d.adjm, NP * 32, WRSN_SEG_V16);
-    add(d.xorder, NP * 4, WRSN_SEG_V16); add(d.tcp, TP * 16, WRSN_SEG_V16);
-    for (int k = 0; k < 2; ++k) {
-        const WrsnNodeArrays& a = k == 0 ? d.live : d.snap;
-        add(a.E, NP * 8, WRSN_SEG_V16); add(a.CS, NP * 8, WRSN_SEG_V16); add(a.RR, NP * 8, WRSN_SEG_V16);
-        add(a.d1, NP * 8, WRSN_SEG_V16); add(a.d2, NP * 8, WRSN_SEG_V16); add(a.ring, WRSN_RING * NP * 8, WRSN_SEG_V16);
-        add(a.logbuf, NP * 8, WRSN_SEG_V16); add(a.ls, NP * 4, WRSN_SEG_V16); add(a.rcv, NP * 4, WRSN_SEG_V16);
-        add(a.conn, WRSN_MAX_MC * WRSN_CONN_CAP * 2, WRSN_SEG_V16); add(a.conn_xy, WRSN_MAX_MC * WRSN_CONN_CAP * 2 * 8, WRSN_SEG_V16);
-        add(a.dyn, sizeof(WrsnEnvDyn), k == 0 ? WRSN_SEG_DYN : WRSN_SEG_V16);
-    }
-    if (with_gen) {
-        add(h->sd.mt_live, WRSN_MT_STRIDE * 4, WRSN_SEG_V16); add(h->sd.mt_snap, WRSN_MT_STRIDE * 4, WRSN_SEG_V16);
-        add(h->sd.es_live, NP * 8, WRSN_SEG_V16); add(h->sd.es_snap, NP * 8, WRSN_SEG_V16); add(h->sd.pgp, 8, WRSN_SEG_V16);
-    }
+        return 0;
+    });
     *nseg = ns;
     return (off + 255) & ~(int64_t)255;
 }
@@ -394,6 +426,17 @@ int rec_layout(wrsn_handle* h) {
     h->rec_bytes = rec_segments(h, h->sd.mt_live ? 1 : 0, h->segs, &h->nseg);
     HIPCHK(hipMemcpy(h->d_segs, h->segs, (size_t)h->nseg * sizeof(WrsnSeg), hipMemcpyHostToDevice));
     return 0;
+}
+
+// the stochastic block of a handle: MT state (live / snapshot), send costs (live / snapshot), prob_gp = 1 everywhere until set
+int alloc_stoch(wrsn_handle* h) {
+    if (h->sd.mt_live) return 0;
+    const size_t B = h->dev.B;
+    if (int rc = alloc_env_arrays(h, ENV_ARRAYS_GEN)) return rc;
+    std::vector<double> one(B, 1.0);
+    HIPCHK(hipMemcpy(h->sd.pgp, one.data(), B * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_dev + 1, &h->sd, sizeof(WrsnStochDev), hipMemcpyHostToDevice));
+    return rec_layout(h);                                      // records of this handle carry the generator block from now on
 }
 
 // what every record of this handle says about its geometry (wrsn_rec_header_kernel adds the environment's own fields)
@@ -472,11 +515,10 @@ int launch_rec_copy(wrsn_handle* h, int mode, const int32_t* src_env, const int3
 
 // request rows of replaced environments (+ their observations when out->obs is set)
 int launch_rec_rows(wrsn_handle* h, const uint8_t* hdr, const int32_t* src_env, const int32_t* dst_env, int n, const wrsn_step_out* out) {
-    WrsnStepOutDev o; o.agent_id = out->agent_id; o.reward = out->reward; o.terminal = out->terminal; o.now = out->now; o.obs = out->obs; o.status = out->status;
     if (out->obs) HIPCHK(hipMemsetAsync(h->d_rend, 0xFF, (size_t)h->dev.B * sizeof(int32_t), h->stream));
-    hipLaunchKernelGGL(wrsn_rec_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->dev, hdr, src_env, dst_env, n, o, out->obs ? h->d_rend : (int32_t*)nullptr);
+    hipLaunchKernelGGL(wrsn_rec_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->dev, hdr, src_env, dst_env, n, step_out_dev(out), out->obs ? h->d_rend : (int32_t*)nullptr);
     HIPCHK(hipGetLastError());
-    if (out->obs) return launch_obs(h, h->d_rend, out->obs);
+    if (out->obs) return launch_obs_all(h, h->d_rend, out->obs);
     return 0;
 }
 
@@ -508,76 +550,38 @@ int wrsn_create(const wrsn_cfg* cfg, wrsn_t** out) {
     DeviceGuard guard_(cfg->device);
     if (!guard_.ok) return fail(WRSN_ERR_HIP, "hipSetDevice failed");
     wrsn_handle* h = new wrsn_handle();
-    h->cfg = *cfg; h->stream = nullptr; h->scenario_set = 0; h->step_budget = 0; h->deadline_ticks = 0; h->epoch = 1; h->obs_reuse = 0; h->obs_fmt = WRSN_OBS_F32; h->timing = 0; h->ev_ok = 0; h->ev_obs = 0; h->ev_rec = 0;
+    h->cfg = *cfg;
     { const char* e = std::getenv("WRSN_PIPE"); h->pipe = (e && *e == '0') ? 0 : 1; }
-    { const char* e = std::getenv("WRSN_PIPE_MID_PCT"); h->pipe_mid_pct = e ? std::atoi(e) : 100; if (h->pipe_mid_pct < 10 || h->pipe_mid_pct > 100) h->pipe_mid_pct = 100; }
-    { const char* e = std::getenv("WRSN_PIPE_SHORT_PCT"); h->pipe_short_pct = e ? std::atoi(e) : 40; if (h->pipe_short_pct < 5 || h->pipe_short_pct > 100) h->pipe_short_pct = 40; }
-    { const char* e = std::getenv("WRSN_PIPE_LONG_PCT"); h->pipe_long_pct = e ? std::atoi(e) : 50; if (h->pipe_long_pct < 10 || h->pipe_long_pct > 90) h->pipe_long_pct = 50; }
-    h->stream2 = nullptr; h->ev2_ok = 0; h->cc_bound = 0; h->cus = 256;
-    h->stoch = 0; std::memset(&h->sd, 0, sizeof(h->sd));
-    // the second stream: high priority by default (WRSN_STREAM2_PRIO=0: normal) -- its launch is the SHORT half of a pipelined step call, whose
+    // the second stream: high priority where the device offers a priority range -- its launch is the SHORT half of a pipelined step call, whose
     // blocks should get wave slots first so that its observations can be rendered while the long half is still being stepped
     hipError_t se = hipErrorUnknown;
-    { const char* e = std::getenv("WRSN_STREAM2_PRIO"); const bool hi = !(e && *e == '0');
-      int lo_p = 0, hi_p = 0;
-      if (hi && hipDeviceGetStreamPriorityRange(&lo_p, &hi_p) == hipSuccess && hi_p != lo_p) se = hipStreamCreateWithPriority(&h->stream2, hipStreamNonBlocking, hi_p);
-      if (se != hipSuccess) se = hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking); }
-    h->stream3 = nullptr;
-    if (se == hipSuccess && hipStreamCreateWithFlags(&h->stream3, hipStreamNonBlocking) == hipSuccess) {
-        if (hipEventCreateWithFlags(&h->ev_join3, hipEventDisableTiming) != hipSuccess) { (void)hipStreamDestroy(h->stream3); h->stream3 = nullptr; }
-    } else h->stream3 = nullptr;
+    int lo_p = 0, hi_p = 0;
+    if (hipDeviceGetStreamPriorityRange(&lo_p, &hi_p) == hipSuccess && hi_p != lo_p) se = hipStreamCreateWithPriority(&h->stream2, hipStreamNonBlocking, hi_p);
+    if (se != hipSuccess) se = hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking);
     if (se == hipSuccess && hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) == hipSuccess) {
         if (hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) == hipSuccess) h->ev2_ok = 1; else (void)hipEventDestroy(h->ev_fork);
     }
-    {   // budget taper over the launch order (units of slots / 8 blocks): start 8 = after the first `slots` blocks, length 16 = down to
-        // zero over two times `slots` blocks (the floor of a quarter applies first); WRSN_TAPER="start,len" overrides (diagnostic)
-        int ts = 8, tl = 16; const char* e = std::getenv("WRSN_TAPER");
-        if (e) { int a = 0, b = 0; if (std::sscanf(e, "%d,%d", &a, &b) == 2 && a >= 0 && a < 256 && b > 0 && b < 256) { ts = a; tl = b; } }
-        h->taper = (ts << 16) | (tl << 24);
-    }
-    { const char* e = std::getenv("WRSN_LDS_PAD"); h->lds_pad = e ? std::atoi(e) : 0; if (h->lds_pad < 0 || h->lds_pad > 100000) h->lds_pad = 0; }
-    { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, cfg->device) == hipSuccess && pr.multiProcessorCount > 0) h->cus = pr.multiProcessorCount; h->slots = h->cus * 8; }
+    { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, cfg->device) == hipSuccess && pr.multiProcessorCount > 0) h->cus = pr.multiProcessorCount; }
     h->npl = npl_for(cfg->n_node);
-    if (h->npl < 0) { delete h; return fail(WRSN_ERR_ARG, "n_node too large"); }
+    if (h->npl < 0) { wrsn_destroy(h); return fail(WRSN_ERR_ARG, "n_node too large"); }
     WrsnDev& d = h->dev;
-    std::memset(&d, 0, sizeof(d));
     d.B = cfg->n_env; d.N = cfg->n_node; d.T = cfg->n_target; d.M = cfg->n_mc; d.G = cfg->map_size;
     d.NP = h->npl * 64; d.TP = ((cfg->n_target + 63) / 64) * 64;
     d.ECAP = (cfg->max_degree > 0 ? cfg->max_degree : 24) * d.NP;
     d.CCAP = (cfg->max_cover > 0 ? cfg->max_cover : 8) * d.NP;
     // observation tile geometry must fit the register tile of wrsn_obs_kernel
     {
-        int CG = (d.G + 3) / 4; int RG = 256 / CG; if (RG < 1) { delete h; return fail(WRSN_ERR_ARG, "map_size too large"); }
-        int RPG = (d.G + RG - 1) / RG; if (RPG > WRSN_OBS_MAXROWS) { delete h; return fail(WRSN_ERR_ARG, "map_size too large for the observation tile"); }
+        int CG = (d.G + 3) / 4; int RG = 256 / CG; if (RG < 1) { wrsn_destroy(h); return fail(WRSN_ERR_ARG, "map_size too large"); }
+        int RPG = (d.G + RG - 1) / RG; if (RPG > WRSN_OBS_MAXROWS) { wrsn_destroy(h); return fail(WRSN_ERR_ARG, "map_size too large for the observation tile"); }
     }
     d.CC = 4;                                                  // raised by wrsn_set_scenario to what the scenarios need
     h->lds_obs = wrsn_obs_lds_bytes(d.G, d.NP);
-    const size_t B = d.B, NP = d.NP;
+    const size_t B = d.B;
     int rc = 0;
     do {
-        if ((rc = dalloc(h, &d.ec, B))) break;
-        if ((rc = dalloc(h, &d.node_x, B * NP))) break;
-        if ((rc = dalloc(h, &d.node_y, B * NP))) break;
-        if ((rc = dalloc(h, &d.dist_bs, B * NP))) break;
-        if ((rc = dalloc(h, &d.target_x, B * d.TP))) break;
-        if ((rc = dalloc(h, &d.target_y, B * d.TP))) break;
-        if ((rc = dalloc(h, &d.nb_off, B * (NP + 1)))) break;
-        if ((rc = dalloc(h, &d.nb_idx, B * (size_t)d.ECAP))) break;
-        if ((rc = dalloc(h, &d.nb_dist, B * (size_t)d.ECAP))) break;
-        if ((rc = dalloc(h, &d.tc_off, B * (size_t)(d.TP + 1)))) break;
-        if ((rc = dalloc(h, &d.tc_idx, B * (size_t)d.CCAP))) break;
-        if ((rc = dalloc(h, &d.ncov, B * NP))) break;
-        if ((rc = dalloc(h, &d.nflags, B * NP))) break;
-        if ((rc = dalloc(h, &d.nbp, B * NP * 4))) break;
-        if ((rc = dalloc(h, &d.nbp_es, B * NP * 8))) break;
-        if ((rc = dalloc(h, &d.es_bs, B * NP))) break;
-        if ((rc = dalloc(h, &d.xorder, B * NP))) break;
-        if ((rc = dalloc(h, &d.adjm, B * NP * 8))) break;
-        if ((rc = dalloc(h, &d.tcp, B * (size_t)d.TP * 4))) break;
-        if ((rc = alloc_node_arrays(h, &d.live))) break;
-        if ((rc = alloc_node_arrays(h, &d.snap))) break;
+        if ((rc = alloc_env_arrays(h, ENV_ARRAYS_DEV))) break;
         if ((rc = dalloc(h, &d.counters, B * 25))) break;
-        { int p2 = 1; while (p2 < d.B) p2 <<= 1; h->bp2 = (d.B <= 8192 && !std::getenv("WRSN_NO_ORDER")) ? p2 : 0; }
+        { int p2 = 1; while (p2 < d.B) p2 <<= 1; h->bp2 = d.B <= 8192 ? p2 : 0; }
         if ((rc = dalloc(h, &d.order_key, (size_t)(h->bp2 > 0 ? h->bp2 : 1)))) break;
         if ((rc = dalloc(h, &d.order, (size_t)(h->bp2 > d.B ? h->bp2 : d.B)))) break;
         if ((rc = dalloc(h, &d.launch_t0, 1))) break;
@@ -595,7 +599,7 @@ int wrsn_create(const wrsn_cfg* cfg, wrsn_t** out) {
         }
     } while (0);
     if (rc) { wrsn_destroy(h); return rc; }
-    {   // identity launch order: what a handle too large for the device-side sort (or WRSN_NO_ORDER) keeps
+    {   // identity launch order: what a handle too large for the device-side sort keeps
         std::vector<int32_t> ident(B); for (size_t e = 0; e < B; ++e) ident[e] = (int32_t)e;
         if (hipMemcpy(d.order, ident.data(), B * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { wrsn_destroy(h); return fail(WRSN_ERR_HIP, "hipMemcpy"); }
     }
@@ -609,10 +613,9 @@ int wrsn_create(const wrsn_cfg* cfg, wrsn_t** out) {
 void wrsn_destroy(wrsn_t* h) {
     if (!h) return;
     DeviceGuard guard_(h->cfg.device);
-    if (h->ev_ok) for (int i = 0; i < 5; ++i) (void)hipEventDestroy(h->ev[i]);
+    if (h->ev_ok) for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);
     if (h->ev2_ok) { (void)hipEventDestroy(h->ev_fork); (void)hipEventDestroy(h->ev_join); }
     if (h->stream2) { (void)hipStreamSynchronize(h->stream2); (void)hipStreamDestroy(h->stream2); }
-    if (h->stream3) { (void)hipStreamSynchronize(h->stream3); (void)hipEventDestroy(h->ev_join3); (void)hipStreamDestroy(h->stream3); }
     for (void* p : h->allocs) (void)hipFree(p);
     if (h->d_idx) (void)hipFree(h->d_idx);
     delete h;
@@ -681,7 +684,7 @@ int set_scenario_impl(wrsn_t* h, int32_t env0, int32_t nenv, const double* node_
     HIPCHK(hipMemcpy(d.target_x + (size_t)env0 * TP, tx.data(), tx.size() * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d.target_y + (size_t)env0 * TP, ty.data(), ty.size() * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(d.ec + env0, ec.data(), ec.size() * sizeof(WrsnEnvConst), hipMemcpyHostToDevice));
-    int stoch_on = 0;                                          // the handle turns to the stochastic kernels with this call
+    bool want_stoch = false;                                   // an environment of this call draws: the stochastic kernels from now on
     if (seed || h->sd.mt_live) {
         // prob_gp and the seeded generator of every environment of the range (random.seed(seed), NetworkIO.py:23); environments loaded
         // through wrsn_set_scenario keep prob_gp 1 and an all-zero state (their draws are counted, never used)
@@ -691,7 +694,7 @@ int set_scenario_impl(wrsn_t* h, int32_t env0, int32_t nenv, const double* node_
             const wrsn_node_spec& ns = node_spec[(size_t)e * (node_spec_stride ? 1 : 0)];
             pg[e] = seed ? ns.prob_gp : 1.0;
             if (seed) mt_seed(seed[e], mt.data() + (size_t)e * WRSN_MT_STRIDE);
-            if (pg[e] != 1.0 && !h->stoch) stoch_on = 1;
+            if (pg[e] != 1.0) want_stoch = true;
         }
         HIPCHK(hipMemcpy(h->sd.pgp + env0, pg.data(), (size_t)nenv * 8, hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(h->sd.mt_live + (size_t)env0 * WRSN_MT_STRIDE, mt.data(), mt.size() * 4, hipMemcpyHostToDevice));
@@ -704,15 +707,11 @@ int set_scenario_impl(wrsn_t* h, int32_t env0, int32_t nenv, const double* node_
         if (ec[e].error == -1) return fail(WRSN_ERR_CAPACITY, "neighbour list capacity exceeded (raise wrsn_cfg.max_degree); env " + std::to_string(env0 + e) + " has " + std::to_string(ec[e].n_edges) + " directed edges");
         if (ec[e].error == -2) return fail(WRSN_ERR_CAPACITY, "coverage list capacity exceeded (raise wrsn_cfg.max_cover); env " + std::to_string(env0 + e));
     }
-    {   // size the connected-node lists in LDS to the scenarios (WrsnEnvConst.conn_bound, wrsn_topology_kernel)
-        for (int e = 0; e < nenv; ++e) if (ec[e].conn_bound > h->cc_bound) h->cc_bound = ec[e].conn_bound;
-        int cc = ((h->cc_bound + 3) / 4) * 4; cc = cc < 4 ? 4 : (cc > WRSN_CONN_CAP ? WRSN_CONN_CAP : cc);
-        if (stoch_on) h->stoch = 1;                            // (LDS and wave slots of the stochastic step kernel)
-        if (cc != h->dev.CC || stoch_on) { h->dev.CC = cc; int rc2 = configure_launch(h); if (rc2) return rc2; }
-    }
-    WrsnStepOutDev none; std::memset(&none, 0, sizeof(none));
-    int rc = launch_env(h, WRSN_MODE_WARMUP, env0, nenv, nullptr, nullptr, 0, nullptr, none);
+    int conn_bound = 0;                                        // (WrsnEnvConst.conn_bound, wrsn_topology_kernel)
+    for (int e = 0; e < nenv; ++e) if (ec[e].conn_bound > conn_bound) conn_bound = ec[e].conn_bound;
+    int rc = fit_launch(h, conn_bound, want_stoch);
     if (rc) return rc;
+    if ((rc = launch_warmup(h, env0, nenv))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     h->scenario_set = 1;
     for (int e = 0; e < nenv; ++e) h->filled[env0 + e] = 1;
@@ -729,12 +728,7 @@ int wrsn_reset(wrsn_t* h, const uint8_t* env_mask, const wrsn_step_out* out) {
     WRSN_ON_DEVICE(h);
     // rows of environments the mask leaves out keep every output, agent_id included; what the render pass draws comes
     // from the list the environment kernel writes (WrsnDev.render_agent), not from the caller's agent_id array
-    WrsnStepOutDev o; o.agent_id = out->agent_id; o.reward = out->reward; o.terminal = out->terminal;
-    o.now = out->now; o.obs = out->obs; o.status = out->status;
-    int rc = launch_env(h, WRSN_MODE_RESET, 0, h->dev.B, nullptr, nullptr, 0, env_mask, o);
-    if (rc) return rc;
-    if (out->obs) return launch_obs(h, h->dev.render_agent, out->obs);
-    return WRSN_OK;
+    return launch_reset(h, env_mask, step_out_dev(out));
 }
 
 int wrsn_step(wrsn_t* h, const int32_t* agent_id, const double* action, int32_t auto_reset, const wrsn_step_out* out) {
@@ -742,9 +736,7 @@ int wrsn_step(wrsn_t* h, const int32_t* agent_id, const double* action, int32_t 
     if (!h->scenario_set) return fail(WRSN_ERR_STATE, "wrsn_set_scenario has not been called");
     WRSN_ON_DEVICE(h);
     // rows with agent_id -2 keep every output (their pending request included)
-    WrsnStepOutDev o; o.agent_id = out->agent_id; o.reward = out->reward; o.terminal = out->terminal;
-    o.now = out->now; o.obs = out->obs; o.status = out->status;
-    return launch_env(h, WRSN_MODE_STEP, 0, h->dev.B, agent_id, action, auto_reset, nullptr, o, out->obs);   // incl. the observations
+    return launch_step(h, agent_id, action, auto_reset, step_out_dev(out));
 }
 
 int wrsn_set_obs_reuse(wrsn_t* h, int32_t on) {
@@ -764,10 +756,10 @@ int wrsn_set_timing(wrsn_t* h, int32_t on) {
     if (!h) return fail(WRSN_ERR_ARG, "null handle");
     WRSN_ON_DEVICE(h);
     if (on && !h->ev_ok) {
-        for (int i = 0; i < 5; ++i) HIPCHK(hipEventCreate(&h->ev[i]));
+        for (hipEvent_t& e : h->ev) HIPCHK(hipEventCreate(&e));
         h->ev_ok = 1;
     }
-    if (!on || !h->timing) h->ev_rec = 0;
+    if (!on || !h->timing) h->ev_mask = 0;
     h->timing = on ? 1 : 0;
     return WRSN_OK;
 }
@@ -775,14 +767,13 @@ int wrsn_set_timing(wrsn_t* h, int32_t on) {
 int wrsn_kernel_times(wrsn_t* h, float* ms) {
     if (!h || !ms) return fail(WRSN_ERR_ARG, "null argument");
     if (!h->ev_ok || !h->timing) return fail(WRSN_ERR_STATE, "wrsn_set_timing(h, 1) first");
-    if (!h->ev_rec) return fail(WRSN_ERR_STATE, "no wrsn_step has run since wrsn_set_timing(h, 1)");
+    if (!h->ev_mask) return fail(WRSN_ERR_STATE, "no wrsn_step has run since wrsn_set_timing(h, 1)");
     WRSN_ON_DEVICE(h);
     HIPCHK(hipStreamSynchronize(h->stream));
     ms[0] = ms[1] = ms[2] = ms[3] = 0.f;
     HIPCHK(hipEventElapsedTime(&ms[0], h->ev[0], h->ev[1]));
     HIPCHK(hipEventElapsedTime(&ms[1], h->ev[1], h->ev[2]));
-    HIPCHK(hipEventElapsedTime(&ms[2], h->ev[2], h->ev[3]));
-    if (h->ev_obs) HIPCHK(hipEventElapsedTime(&ms[3], h->ev[3], h->ev[4]));
+    if (h->ev_mask & (1 << 3)) HIPCHK(hipEventElapsedTime(&ms[3], h->ev[2], h->ev[3]));   // the call rendered; ms[2] stays 0
     return WRSN_OK;
 }
 
@@ -859,7 +850,7 @@ int wrsn_render(wrsn_t* h, const int32_t* agent_id, float* obs) {
     if (!h || !agent_id || !obs) return fail(WRSN_ERR_ARG, "null argument");
     if (!h->scenario_set) return fail(WRSN_ERR_STATE, "wrsn_set_scenario has not been called");
     WRSN_ON_DEVICE(h);
-    return launch_obs(h, agent_id, obs);
+    return launch_obs_all(h, agent_id, obs);
 }
 
 int wrsn_sync(wrsn_t* h) {
@@ -997,9 +988,8 @@ int wrsn_save_envs(wrsn_t* h, const int32_t* env, int32_t n, const wrsn_step_out
     WRSN_ON_DEVICE(h);
     if ((rc = ensure_idx(h, (size_t)n))) return rc;
     HIPCHK(hipMemcpyAsync(h->d_idx, env, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    WrsnStepOutDev o; o.agent_id = req->agent_id; o.reward = req->reward; o.terminal = req->terminal; o.now = req->now; o.obs = nullptr; o.status = req->status;
     hipLaunchKernelGGL(wrsn_rec_header_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->dev, (const double*)h->sd.pgp, rec_template(h),
-                       (const int32_t*)h->d_idx, (int)n, (uint8_t*)dst, (long long)h->rec_bytes, o);
+                       (const int32_t*)h->d_idx, (int)n, (uint8_t*)dst, (long long)h->rec_bytes, step_out_dev(req, false));
     HIPCHK(hipGetLastError());
     return launch_rec_copy(h, WRSN_REC_PACK, h->d_idx, nullptr, (uint8_t*)dst, n);
 }
@@ -1034,17 +1024,12 @@ int wrsn_load_envs(wrsn_t* h, const int32_t* env, int32_t n, const void* src, co
         return fail(WRSN_ERR_ARG, "has_gen: the records hold no generator block, this handle keeps generators");
     // ---- every record fits: replace the environments
     if (r0.has_gen && !h->sd.mt_live && (rc = alloc_stoch(h))) return rc;
-    int stoch_on = 0, cb = h->cc_bound;
+    bool want_stoch = false; int conn_bound = 0;               // as wrsn_set_scenario
     for (int i = 0; i < n; ++i) {
-        if (hd[i].prob_gp != 1.0 && !h->stoch) stoch_on = 1;
-        if (hd[i].conn_bound > cb) cb = hd[i].conn_bound;
+        if (hd[i].prob_gp != 1.0) want_stoch = true;
+        if (hd[i].conn_bound > conn_bound) conn_bound = hd[i].conn_bound;
     }
-    h->cc_bound = cb;
-    {   // as wrsn_set_scenario: connected-node lists in LDS sized to the scenarios, the stochastic kernels once prob_gp != 1 somewhere
-        int cc = ((h->cc_bound + 3) / 4) * 4; cc = cc < 4 ? 4 : (cc > WRSN_CONN_CAP ? WRSN_CONN_CAP : cc);
-        if (stoch_on) h->stoch = 1;
-        if (cc != h->dev.CC || stoch_on) { h->dev.CC = cc; if ((rc = configure_launch(h))) return rc; }
-    }
+    if ((rc = fit_launch(h, conn_bound, want_stoch))) return rc;
     HIPCHK(hipMemcpyAsync(h->d_idx, env, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     if ((rc = launch_rec_copy(h, WRSN_REC_UNPACK, nullptr, h->d_idx, (uint8_t*)src, n))) return rc;
     if ((rc = launch_rec_rows(h, h->d_hdr, nullptr, h->d_idx, n, out))) return rc;

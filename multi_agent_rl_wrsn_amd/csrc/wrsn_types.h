@@ -10,11 +10,6 @@
                                          // sized to the scenario: WrsnDev.CC <= WRSN_CONN_CAP)
 #define WRSN_RING 10                     // Node.log window (Node.py:71-77)
 
-// run modes of the environment kernel
-#define WRSN_MODE_STEP 0
-#define WRSN_MODE_WARMUP 1
-#define WRSN_MODE_RESET 2
-
 // per-environment constants: scenario + charger parameters and what Network.__init__ /
 // WRSN.reset derive from them (Network.py:16-27, WRSN.py:50-52)
 struct WrsnEnvConst {

@@ -285,3 +285,21 @@ def test_ragged_record_round_trips(hip_lib):
         _same(_peeks(a, 0, small), _peeks(b, 0, small)); _same(_peeks(a, 0, small), _peeks(c, 1, small))
         if a.terminal[0] or a.agent_id[0] < 0:
             break
+
+
+def test_record_format_version_1_is_pinned(hip_lib):
+    """The size and segment count of a record are part of format version 1: literals measured when the format was introduced (one
+    environment, one charger, default max_degree / max_cover), not computed by the library under test.  A per-environment array added to
+    or dropped from a handle changes them, and then needs a new WRSN_REC_VERSION."""
+    import struct
+    for name, nbytes, has_gen, nseg in (("hanoi1000n50_m1_warmup10", 116480, 0, 43),                  # 82 nodes, 50 targets: NP 128, TP 64
+                                        ("prob_gp/hanoi1000n50_m1_warmup10_p05", 123648, 1, 48)):     # + the generator block
+        z, sc, mc = _fixture(name)
+        assert (sc.n_node, sc.n_target, int(z["num_agent"])) == (82, 50, 1), name
+        ev = _emu([sc], mc, 1, map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]))
+        assert ev.h.env_record_bytes() == nbytes, name
+        rec = _save(ev, [0])
+        assert rec.shape == (1, nbytes), name
+        magic, version = struct.unpack_from("<II", rec[0].tobytes(), 0)
+        assert (magic, version) == (0x52534E57, 1), name
+        assert struct.unpack_from("<iiq", rec[0].tobytes(), 48) == (has_gen, nseg, nbytes), name
