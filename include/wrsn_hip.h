@@ -78,8 +78,12 @@ typedef struct wrsn_step_out {
     int32_t *status;          /* [B]  0 ok; 1 step fell off the end (reference returns None);
                                       2 every charger dead (reference would hang); 3 auto-reset performed;
                                       4 the step is still in flight (wrsn_set_step_budget), call wrsn_step again;
-                                      negative: per-env error (capacity)                           */
+                                      negative: per-env error (capacity);
+                                      WRSN_STATUS_POOL_INDEX: wrsn_pool_reset found pool_index outside the pool */
 } wrsn_step_out;
+
+/* per-row status of wrsn_pool_reset for a selected row whose pool_index is outside [0, n_records): the row is left as it was */
+#define WRSN_STATUS_POOL_INDEX (-5)
 
 /* what wrsn_peek copies; dst is a HOST pointer, dense [B, ...] in the listed dtype */
 enum wrsn_peek_what {
@@ -99,6 +103,9 @@ enum wrsn_peek_what {
     WRSN_PEEK_TARGETS_ACTIVE = 11, /* int32 [B,T]   Network.targets_active (Network.py:9,45-55): target covered by a node the last
                                                     setLevels reached; 0 beyond an environment's own target count.  (10 is
                                                     taken by the per-phase cycle counters of diagnostic builds.)       */
+    WRSN_PEEK_POOL = 13,         /* int32  [B,2]   scenario pool: the pool record the environment runs (-1 after wrsn_set_scenario* /
+                                                    wrsn_load_envs, the source's value after wrsn_clone_envs) and its swaps since
+                                                    wrsn_pool_set                                  */
     WRSN_PEEK_RNG_STATE = 12     /* uint32 [B,627] the environment's MT19937: the 624 state words and the index as
                                                     random.getstate()[1] lists them, then the draws since the last reset
                                                     (low, high word).  Handles that run the stochastic kernels only
@@ -152,7 +159,9 @@ int wrsn_reset(wrsn_t *h, const uint8_t *env_mask, const wrsn_step_out *out);
  *                              -2 = leave this environment untouched (none of its output rows is written);
  *   action   [B,3] DEVICE double: normalised action, clipped to [0,1] inside (WRSN.py:299).
  * auto_reset != 0: an environment whose previous return was terminal is reset instead of stepped
- * and reports status 3 with the reset request (agent 0, reward 0). */
+ * and reports status 3 with the reset request (agent 0, reward 0).
+ * agent_id MAY be the same array as out->agent_id, in every launch mode: row e of the inputs is read before row e of the outputs is
+ * written, by the one thread block that owns environment e in the launch. */
 int wrsn_step(wrsn_t *h, const int32_t *agent_id, const double *action, int32_t auto_reset,
               const wrsn_step_out *out);
 
@@ -298,6 +307,39 @@ int wrsn_load_envs(wrsn_t *h, const int32_t *env, int32_t n, const void *src, co
 /* dst[i] becomes a copy of src[i] (device to device), and row src[i] of out is copied to row dst[i] (obs rendered as for a load;
  * needs out->agent_id then).  Asynchronous on the handle's stream. */
 int wrsn_clone_envs(wrsn_t *h, const int32_t *src, const int32_t *dst, int32_t n, const wrsn_step_out *out);
+
+/* SCENARIO POOLS: restart finished episodes in another network, on the device.  A record saved right after wrsn_reset is a prepared
+ * scenario (topology, constants, post-warm-up snapshot, reset request); a pool is P of them.
+ *
+ * wrsn_pool_set registers P records (DEVICE, caller-owned, 16-byte aligned, back to back at this handle's record size) as the handle's
+ * pool.  The memory must stay valid and unchanged until the pool is replaced, cleared (records == NULL, n_records == 0) or the handle
+ * destroyed.  Every header is validated as by wrsn_load_envs (WRSN_ERR_ARG naming record and field, nothing changed), the generator
+ * block rule of wrsn_load_envs applies to the pool as a whole, and the launch configuration is fitted to the pool's largest
+ * conn_bound (and to prob_gp != 1 anywhere in it) once, so that no later swap needs a new one.  Zeroes the per-environment swap
+ * counters (WRSN_PEEK_POOL).  `seed` seeds the draw below.  Synchronous. */
+int wrsn_pool_set(wrsn_t *h, const void *records, int32_t n_records, uint64_t seed);
+
+/* Replace the environments the DEVICE selects by pool records, asynchronously on the handle's stream (no host synchronisation, no
+ * host read-back).
+ *   env_mask   DEVICE uint8 [B]: rows with a non-zero byte are selected.  NULL: exactly the rows whose last return was terminal, the
+ *              rows an auto-reset of the next wrsn_step would take.
+ *   pool_index DEVICE int32 [B]: the record for row e, read for selected rows only.  NULL: the handle draws it -- for environment e
+ *              with k swaps since wrsn_pool_set:  z = (seed ^ ((uint64)e << 32 | k)) + 0x9E3779B97F4A7C15;
+ *              z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) * 0x94D049BB133111EB;  z ^= z >> 31;
+ *              index = ((z >> 32) * P) >> 32   (mod 2^64).  Every swap of e increments k, whoever chose the index.
+ *   agent_id   NULL, or DEVICE int32 [B], in/out: selected rows are set to -2, so that the wrsn_step the caller issues next with this
+ *              array leaves them alone in every launch mode and their rows of `out` carry the request below out of that call.
+ *              It must NOT be the same array as out->agent_id (WRSN_ERR_ARG): that row receives the record's charger.
+ * A selected row becomes what wrsn_load_envs of that record into that row would make it (the destination keeps its counters since
+ * create and the rollout table; a step in flight or a latched action of the old occupant is gone; the generator block is replaced
+ * when the handle keeps generators).  Its row of `out` gets the record's saved request (agent_id, reward, now, terminal), status 3
+ * when env_mask is NULL (as an auto-reset reports) and 0 with a mask (as wrsn_reset reports); with out->obs (needs out->agent_id) the
+ * row is rendered in the handle's observation format.  A following wrsn_rollout_collect discards what was pending for the row, as
+ * after a reset.  No byte of state, request row or observation of an unselected row is touched.  A selected row whose pool_index is
+ * outside [0, n_records) is left as it was (agent_id too) and gets status WRSN_STATUS_POOL_INDEX.
+ * WRSN_ERR_STATE: no pool set; an environment of the handle holds no scenario yet (the host cannot know which rows the device
+ * replaces, so every one must be filled); the handle's record layout changed since wrsn_pool_set. */
+int wrsn_pool_reset(wrsn_t *h, const uint8_t *env_mask, const int32_t *pool_index, int32_t *agent_id, const wrsn_step_out *out);
 
 /* Device counters, summed over the environments.  HOST pointer to 8 x int64.  Synchronises.
  *   [0] simulated seconds, [1] packet-exact seconds, [2] charger events of the episodes in progress (they restart at

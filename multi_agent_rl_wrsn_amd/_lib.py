@@ -18,6 +18,8 @@ ERR_NAMES = {0: "WRSN_OK", -1: "WRSN_ERR_ARG", -2: "WRSN_ERR_HIP", -3: "WRSN_ERR
 PEEK_NODE_ENERGY, PEEK_NODE_CS, PEEK_NODE_RR, PEEK_NODE_STATUS, PEEK_NODE_LEVEL = 0, 1, 2, 3, 4
 PEEK_MC, PEEK_ENV, PEEK_NODE_DEGREE, PEEK_NODE_NCOVER, PEEK_NODE_DIRECT = 5, 6, 7, 8, 9
 PEEK_TARGETS_ACTIVE = 11
+PEEK_POOL = 13               # int32 [B, 2]: the pool record the environment runs (-1: none), its swaps since wrsn_pool_set
+STATUS_POOL_INDEX = -5       # per-row status of wrsn_pool_reset: pool_index outside the pool, row left as it was
 PEEK_RNG_STATE = 12          # uint32 [B, 627]: MT19937 words, index (random.getstate()[1]), draws since reset (low, high word)
 OBS_F32, OBS_BF16 = 0, 1     # wrsn_set_obs_format: float32 cells / bfloat16 bit patterns (uint16) behind every observation pointer
 MC_FIELDS = ("loc_x", "loc_y", "energy", "status", "type_charging", "cur_x", "cur_y", "cur_t", "n_conn",
@@ -28,7 +30,7 @@ ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max"
 # every entry point include/wrsn_hip.h declares
 EXPORTS = ("wrsn_create", "wrsn_destroy", "wrsn_set_stream", "wrsn_set_scenario", "wrsn_set_scenario_seeded", "wrsn_reset", "wrsn_step",
            "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_render", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
-           "wrsn_clone_envs", "wrsn_synth_network",
+           "wrsn_clone_envs", "wrsn_pool_set", "wrsn_pool_reset", "wrsn_synth_network",
            "wrsn_last_error",
            "wrsn_version")
 
@@ -121,6 +123,10 @@ def bind(lib):
     lib.wrsn_load_envs.restype = C.c_int
     lib.wrsn_clone_envs.argtypes = [vp, vp, vp, C.c_int32, C.POINTER(WrsnStepOut)]
     lib.wrsn_clone_envs.restype = C.c_int
+    lib.wrsn_pool_set.argtypes = [vp, vp, C.c_int32, C.c_uint64]
+    lib.wrsn_pool_set.restype = C.c_int
+    lib.wrsn_pool_reset.argtypes = [vp, vp, vp, vp, C.POINTER(WrsnStepOut)]
+    lib.wrsn_pool_reset.restype = C.c_int
     lib.wrsn_synth_network.argtypes = [C.c_uint64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, vp, vp, vp]
     lib.wrsn_synth_network.restype = C.c_int
     lib.wrsn_last_error.argtypes = []
@@ -302,6 +308,8 @@ class RawHandle:
             a = np.empty((B, 16), dtype=np.float64)
         elif what == PEEK_RNG_STATE:
             a = np.empty((B, 627), dtype=np.uint32)
+        elif what == PEEK_POOL:
+            a = np.empty((B, 2), dtype=np.int32)
         else:
             raise ValueError("unknown peek selector %r" % (what,))
         check(self.lib, self.lib.wrsn_peek(self._h, int(what), a.ctypes.data))
@@ -338,9 +346,30 @@ class RawHandle:
         o = self._out(**out_ptrs)
         check(self.lib, self.lib.wrsn_clone_envs(self._h, s.ctypes.data, d.ctypes.data, len(s), C.byref(o)))
 
+    # -- scenario pools (wrsn_pool_set / wrsn_pool_reset); every array argument is a device address
+    def pool_set(self, records_ptr, n_records, seed=0):
+        """Register n_records records at records_ptr (device, kept alive and unchanged by the caller) as the pool; (0, 0) clears it."""
+        check(self.lib, self.lib.wrsn_pool_set(self._h, C.c_void_p(records_ptr or None), int(n_records), C.c_uint64(int(seed) & (2 ** 64 - 1))))
+
+    def pool_reset(self, mask_ptr=0, index_ptr=0, agent_ptr=0, **out_ptrs):
+        """Replace the rows of mask_ptr (0: the rows whose last return was terminal) by the records of index_ptr (0: the draw)."""
+        o = self._out(**out_ptrs)
+        check(self.lib, self.lib.wrsn_pool_reset(self._h, C.c_void_p(mask_ptr or None), C.c_void_p(index_ptr or None),
+                                                 C.c_void_p(agent_ptr or None), C.byref(o)))
+
     def counters(self):
         import numpy as np
         a = np.zeros(8, dtype=np.int64)
         check(self.lib, self.lib.wrsn_counters(self._h, a.ctypes.data))
         return {"ticks": int(a[0]), "exact_ticks": int(a[1]), "events": int(a[2]), "env_steps": int(a[3]),
                 "sim_seconds_total": int(a[4]), "zero_time_steps": int(a[5])}
+
+
+def pool_draw(seed, env, k, P):
+    """The pool record wrsn_pool_reset draws for environment `env` at its k-th swap since wrsn_pool_set(seed), pool of P records."""
+    m = (1 << 64) - 1
+    z = ((int(seed) & m) ^ (((int(env) << 32) | int(k)) & m)) + 0x9E3779B97F4A7C15 & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    z ^= z >> 31
+    return ((z >> 32) * int(P)) >> 32

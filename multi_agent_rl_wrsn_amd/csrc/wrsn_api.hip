@@ -101,6 +101,12 @@ struct wrsn_handle {
     int32_t* d_idx = nullptr; size_t idx_cap = 0;
     uint8_t* d_hdr = nullptr;       // [B] headers (destinations of a load are distinct)
     int32_t* d_rend = nullptr;
+    // scenario pool (wrsn_pool_set / wrsn_pool_reset): the caller's records, and what belongs to the HANDLE rather than to an environment's
+    // record: per environment the pool record it runs (-1: none) and its swaps since wrsn_pool_set; the pair list of a pool reset
+    // ([0, B) environments, [B, 2B) records) and its length
+    const uint8_t* pool = nullptr; int pool_n = 0; uint64_t pool_seed = 0; int64_t pool_rec_bytes = 0;
+    int32_t* d_pool_cur = nullptr; int32_t* d_pool_swaps = nullptr;
+    int32_t* d_pairs = nullptr; int32_t* d_pair_n = nullptr;
 };
 
 namespace {
@@ -516,7 +522,8 @@ int launch_rec_copy(wrsn_handle* h, int mode, const int32_t* src_env, const int3
 // request rows of replaced environments (+ their observations when out->obs is set)
 int launch_rec_rows(wrsn_handle* h, const uint8_t* hdr, const int32_t* src_env, const int32_t* dst_env, int n, const wrsn_step_out* out) {
     if (out->obs) HIPCHK(hipMemsetAsync(h->d_rend, 0xFF, (size_t)h->dev.B * sizeof(int32_t), h->stream));
-    hipLaunchKernelGGL(wrsn_rec_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->dev, hdr, src_env, dst_env, n, step_out_dev(out), out->obs ? h->d_rend : (int32_t*)nullptr);
+    hipLaunchKernelGGL(wrsn_rec_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->dev, hdr, (long long)WRSN_REC_HDR, (const int32_t*)nullptr, src_env, dst_env, n,
+                       (const int32_t*)nullptr, step_out_dev(out), out->obs ? h->d_rend : (int32_t*)nullptr, -1, 0, h->d_pool_cur);
     HIPCHK(hipGetLastError());
     if (out->obs) return launch_obs_all(h, h->d_rend, out->obs);
     return 0;
@@ -592,6 +599,10 @@ int wrsn_create(const wrsn_cfg* cfg, wrsn_t** out) {
         if ((rc = dalloc(h, &h->d_segs, WRSN_REC_MAXSEG))) break;
         if ((rc = dalloc(h, &h->d_hdr, B * WRSN_REC_HDR))) break;
         if ((rc = dalloc(h, &h->d_rend, B))) break;
+        if ((rc = dalloc(h, &h->d_pool_cur, B))) break;
+        if ((rc = dalloc(h, &h->d_pool_swaps, B))) break;
+        if ((rc = dalloc(h, &h->d_pairs, 2 * B))) break;
+        if ((rc = dalloc(h, &h->d_pair_n, 1))) break;
         {   // the descriptor the kernels read, and the stochastic block behind it (wrsn_sim.h: Sim::SD)
             uint8_t* p = nullptr;
             if ((rc = dalloc(h, &p, sizeof(WrsnDev) + sizeof(WrsnStochDev)))) break;
@@ -604,6 +615,7 @@ int wrsn_create(const wrsn_cfg* cfg, wrsn_t** out) {
         if (hipMemcpy(d.order, ident.data(), B * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { wrsn_destroy(h); return fail(WRSN_ERR_HIP, "hipMemcpy"); }
     }
     if ((rc = configure_launch(h))) { wrsn_destroy(h); return rc; }
+    if (hipMemset(h->d_pool_cur, 0xFF, B * sizeof(int32_t)) != hipSuccess) { wrsn_destroy(h); return fail(WRSN_ERR_HIP, "hipMemset"); }
     h->filled.assign(B, 0);
     if (rec_layout(h) != 0 || ensure_idx(h, 2 * B) != 0) { wrsn_destroy(h); return fail(WRSN_ERR_HIP, "hipMemcpy"); }
     *out = h;
@@ -713,6 +725,7 @@ int set_scenario_impl(wrsn_t* h, int32_t env0, int32_t nenv, const double* node_
     if (rc) return rc;
     if ((rc = launch_warmup(h, env0, nenv))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemset(h->d_pool_cur + env0, 0xFF, (size_t)nenv * sizeof(int32_t)));   // these environments run no pool record
     h->scenario_set = 1;
     for (int e = 0; e < nenv; ++e) h->filled[env0 + e] = 1;
     return WRSN_OK;
@@ -953,6 +966,13 @@ int wrsn_peek(wrsn_t* h, int32_t what, void* dst) {
         uint32_t* o = (uint32_t*)dst;
         for (size_t e = 0; e < B; ++e) std::memcpy(o + e * 627, tmp.data() + e * WRSN_MT_STRIDE, 627 * 4);
         return 0; }
+    case WRSN_PEEK_POOL: {
+        std::vector<int32_t> cur(B), sw(B);
+        HIPCHK(hipMemcpy(cur.data(), h->d_pool_cur, B * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(sw.data(), h->d_pool_swaps, B * 4, hipMemcpyDeviceToHost));
+        int32_t* o = (int32_t*)dst;
+        for (size_t e = 0; e < B; ++e) { o[2 * e] = cur[e]; o[2 * e + 1] = sw[e]; }
+        return 0; }
     default: return fail(WRSN_ERR_ARG, "unknown peek selector");
     }
 }
@@ -1057,6 +1077,81 @@ int wrsn_clone_envs(wrsn_t* h, const int32_t* src, const int32_t* dst, int32_t n
     if ((rc = launch_rec_copy(h, WRSN_REC_CLONE, h->d_idx, h->d_idx + n, nullptr, n))) return rc;
     if ((rc = launch_rec_rows(h, nullptr, h->d_idx, h->d_idx + n, n, out))) return rc;
     for (int i = 0; i < n; ++i) h->filled[dst[i]] = 1;
+    return WRSN_OK;
+}
+
+int wrsn_pool_set(wrsn_t* h, const void* records, int32_t n_records, uint64_t seed) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    if (!records && n_records == 0) {                          // clear
+        h->pool = nullptr; h->pool_n = 0; h->pool_seed = 0; h->pool_rec_bytes = 0;
+        return WRSN_OK;
+    }
+    if (!records || n_records < 1) return fail(WRSN_ERR_ARG, "null records or n_records < 1");
+    if ((uintptr_t)records % 16) return fail(WRSN_ERR_ARG, "records must be 16-byte aligned");
+    WRSN_ON_DEVICE(h);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    // as wrsn_load_envs: record 0 decides the stride, then every header is gathered (B at a time: the staging holds B) and validated
+    // before anything changes
+    WrsnRecHeader r0;
+    HIPCHK(hipMemcpy(&r0, records, sizeof(r0), hipMemcpyDeviceToHost));
+    int rc = rec_check(h, r0, 0); if (rc) return rc;
+    const int B = h->dev.B;
+    std::vector<WrsnRecHeader> hd((size_t)n_records);
+    for (int i0 = 0; i0 < n_records; i0 += B) {
+        const int m = n_records - i0 < B ? n_records - i0 : B;
+        hipLaunchKernelGGL(wrsn_rec_gather_kernel, dim3((m + 255) / 256), dim3(256), 0, h->stream, (const uint8_t*)records + (size_t)i0 * (size_t)r0.rec_bytes,
+                           (long long)r0.rec_bytes, m, h->d_hdr);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(hipMemcpy(hd.data() + i0, h->d_hdr, (size_t)m * sizeof(WrsnRecHeader), hipMemcpyDeviceToHost));
+    }
+    for (int i = 0; i < n_records; ++i) {
+        if ((rc = rec_check(h, hd[i], i))) return rc;
+        if (hd[i].has_gen != r0.has_gen) return fail(WRSN_ERR_ARG, "record " + std::to_string(i) + ": has_gen differs from record 0's");
+    }
+    bool any_filled = false;
+    for (uint8_t f : h->filled) any_filled = any_filled || f;
+    if (r0.has_gen && !h->sd.mt_live && any_filled)
+        return fail(WRSN_ERR_ARG, "has_gen: the records hold a generator block, this handle keeps no generators and already holds a scenario");
+    if (!r0.has_gen && h->sd.mt_live)
+        return fail(WRSN_ERR_ARG, "has_gen: the records hold no generator block, this handle keeps generators");
+    // ---- every record fits: one launch configuration for whatever a later swap brings in
+    if (r0.has_gen && !h->sd.mt_live && (rc = alloc_stoch(h))) return rc;
+    bool want_stoch = false; int conn_bound = 0;
+    for (int i = 0; i < n_records; ++i) {
+        if (hd[i].prob_gp != 1.0) want_stoch = true;
+        if (hd[i].conn_bound > conn_bound) conn_bound = hd[i].conn_bound;
+    }
+    if ((rc = fit_launch(h, conn_bound, want_stoch))) return rc;
+    HIPCHK(hipMemset(h->d_pool_swaps, 0, (size_t)B * sizeof(int32_t)));
+    h->pool = (const uint8_t*)records; h->pool_n = n_records; h->pool_seed = seed; h->pool_rec_bytes = h->rec_bytes;
+    return WRSN_OK;
+}
+
+int wrsn_pool_reset(wrsn_t* h, const uint8_t* env_mask, const int32_t* pool_index, int32_t* agent_id, const wrsn_step_out* out) {
+    if (!h || !out) return fail(WRSN_ERR_ARG, "null argument");
+    if (!h->pool) return fail(WRSN_ERR_STATE, "no scenario pool is set (wrsn_pool_set)");
+    if (h->pool_rec_bytes != h->rec_bytes) return fail(WRSN_ERR_STATE, "the record layout of the handle changed since wrsn_pool_set: set the pool again");
+    for (size_t e = 0; e < h->filled.size(); ++e)
+        if (!h->filled[e]) return fail(WRSN_ERR_STATE, "environment " + std::to_string(e) + " holds no scenario yet: wrsn_pool_reset needs every environment filled");
+    if (agent_id && agent_id == out->agent_id) return fail(WRSN_ERR_ARG, "agent_id must not be out->agent_id (selected rows get -2 there and the record's charger here)");
+    if (out->obs && !out->agent_id) return fail(WRSN_ERR_ARG, "rendering the replaced rows needs out->agent_id");
+    WRSN_ON_DEVICE(h);
+    const int B = h->dev.B;
+    int32_t* rend = out->obs ? h->d_rend : (int32_t*)nullptr;
+    hipLaunchKernelGGL(wrsn_pool_select_kernel, dim3(1), dim3(64), 0, h->stream, h->dev, env_mask, pool_index, h->pool_n, h->pool_seed, agent_id, h->d_pool_cur,
+                       h->d_pool_swaps, h->d_pairs, h->d_pairs + B, h->d_pair_n, out->status, rend);
+    {   // fixed grid: at most eight blocks per CU, no more than the whole batch needs
+        const int chunks = (int)(h->rec_bytes / 16), per = chunks - WRSN_REC_HDR / 16;
+        const long long need = ((long long)B * per + 255) / 256;
+        const int blocks = (int)(need < (long long)h->cus * 8 ? need : (long long)h->cus * 8);
+        hipLaunchKernelGGL(wrsn_pool_copy_kernel, dim3(blocks), dim3(256), (size_t)h->nseg * sizeof(WrsnSeg), h->stream, (const WrsnSeg*)h->d_segs, h->nseg,
+                           (const int32_t*)h->d_pairs, (const int32_t*)(h->d_pairs + B), (const int32_t*)h->d_pair_n, h->pool, (long long)h->rec_bytes, chunks);
+    }
+    hipLaunchKernelGGL(wrsn_rec_rows_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->dev, h->pool, (long long)h->rec_bytes, (const int32_t*)(h->d_pairs + B),
+                       (const int32_t*)nullptr, (const int32_t*)h->d_pairs, B, (const int32_t*)h->d_pair_n, step_out_dev(out), rend, env_mask ? 0 : 3, 2, (int32_t*)nullptr);
+    HIPCHK(hipGetLastError());
+    if (out->obs) return launch_obs_all(h, h->d_rend, out->obs);
     return WRSN_OK;
 }
 

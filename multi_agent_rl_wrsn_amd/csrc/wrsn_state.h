@@ -76,58 +76,25 @@ WDEV void wrsn_st_u4(WrsnU4 WRSN_GLOBAL_AS* p, const WrsnU4& v) {
 inline void wrsn_st_u4(WrsnU4* p, const WrsnU4& v) { *p = v; }
 #endif
 
-// One copy loop for the three directions.  Pair i (record i0 + i of the call) copies chunks [WRSN_REC_HDR / 16, chunks) of the record
-// layout: source environment src_env[i0 + i] (pack, clone), destination environment dst_env[i0 + i] (unpack, clone), record
-// rec + (i0 + i) * rec_stride (pack, unpack).  Launch: 256 threads, LDS nseg * 32 bytes (the segment table).
-__global__ void __launch_bounds__(256) wrsn_rec_copy_kernel(const WrsnSeg* __restrict__ segs, int nseg, int mode, const int32_t* __restrict__ src_env,
-                                                            const int32_t* __restrict__ dst_env, uint8_t* __restrict__ rec, long long rec_stride,
-                                                            int i0, int n, int chunks) {
-    extern __shared__ double smem[];
-    WrsnSeg* tab = (WrsnSeg*)smem;
-    {
-        const uint64_t* g = (const uint64_t*)segs; uint64_t* l = (uint64_t*)tab;
-        for (int w = threadIdx.x; w < nseg * 4; w += 256) l[w] = g[w];
+// One chunk of the copy loop, shared by wrsn_rec_copy_kernel and wrsn_pool_copy_kernel: 16-byte chunk c of the record layout for pair r
+// (source environment src_env[r] for pack and clone, destination environment dst_env[r] for unpack and clone); rp is the address of
+// the chunk in the pair's record (pack, unpack; NULL for a clone).  `tab` is the segment table in LDS.
+WDEV void wrsn_rec_copy_chunk(const WrsnSeg* tab, int nseg, int mode, const int32_t* __restrict__ src_env, const int32_t* __restrict__ dst_env,
+                              int r, int c, uint8_t* rp) {
+    int lo = 0, hi = nseg - 1;                                  // the last segment that starts at or before chunk c
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tab[mid].c0 <= c) lo = mid; else hi = mid - 1; }
+    const WrsnSeg sg = tab[lo];
+    const int o = (c - sg.c0) * 16;                             // byte offset in the slice
+    if (o >= sg.bytes) {                                        // alignment padding of the record
+        if (mode == WRSN_REC_PACK) { WrsnU4 z; z.x = z.y = z.z = z.w = 0u; wrsn_st_u4(wrsn_global((WrsnU4*)rp), z); }
+        return;
     }
-    __syncthreads();
-    const int hc = WRSN_REC_HDR / 16, per = chunks - hc;      // chunks of one pair
-    const int total = n * per, step = (int)gridDim.x * 256;
-    for (int g = (int)blockIdx.x * 256 + (int)threadIdx.x; g < total; g += step) {
-        const int i = g / per, c = g - i * per + hc, r = i0 + i;
-        int lo = 0, hi = nseg - 1;                              // the last segment that starts at or before chunk c
-        while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (tab[mid].c0 <= c) lo = mid; else hi = mid - 1; }
-        const WrsnSeg sg = tab[lo];
-        const int o = (c - sg.c0) * 16;                         // byte offset in the slice
-        uint8_t* rp = rec ? rec + (size_t)r * (size_t)rec_stride + (size_t)c * 16 : nullptr;
-        if (o >= sg.bytes) {                                    // alignment padding of the record
-            if (mode == WRSN_REC_PACK) { WrsnU4 z; z.x = z.y = z.z = z.w = 0u; wrsn_st_u4(wrsn_global((WrsnU4*)rp), z); }
-            continue;
-        }
-        const uint8_t* sp = mode == WRSN_REC_UNPACK ? rp : (const uint8_t*)(uintptr_t)(sg.base + (uint64_t)src_env[r] * (uint64_t)sg.stride + (uint64_t)o);
-        uint8_t* dp = mode == WRSN_REC_PACK ? rp : (uint8_t*)(uintptr_t)(sg.base + (uint64_t)dst_env[r] * (uint64_t)sg.stride + (uint64_t)o);
-        if (sg.kind == WRSN_SEG_V16 || mode == WRSN_REC_UNPACK) {
-            const WrsnU4 v = wrsn_ld_u4(wrsn_global((const WrsnU4*)sp));   // (the record side is always 16-byte aligned)
-            if (sg.kind == WRSN_SEG_V16) { wrsn_st_u4(wrsn_global((WrsnU4*)dp), v); continue; }
-            const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
-            uint32_t WRSN_GLOBAL_AS* d32 = wrsn_global((uint32_t*)dp);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int ok = o + 4 * k;
-                if (ok >= sg.bytes) break;
-                const int rule = sg.kind == WRSN_SEG_DYN ? wrsn_rec_dyn_word(ok) : 0;
-                if (rule != 1) d32[k] = rule == 2 ? 0u : w4[k];
-            }
-            continue;
-        }
-        // a word-copied slice read from an environment (pack, clone)
-        const uint32_t WRSN_GLOBAL_AS* s32 = wrsn_global((const uint32_t*)sp);
-        uint32_t w4[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) w4[k] = (o + 4 * k < sg.bytes) ? s32[k] : 0u;
-        if (mode == WRSN_REC_PACK) {
-            WrsnU4 v; v.x = w4[0]; v.y = w4[1]; v.z = w4[2]; v.w = w4[3];
-            wrsn_st_u4(wrsn_global((WrsnU4*)dp), v);
-            continue;
-        }
+    const uint8_t* sp = mode == WRSN_REC_UNPACK ? rp : (const uint8_t*)(uintptr_t)(sg.base + (uint64_t)src_env[r] * (uint64_t)sg.stride + (uint64_t)o);
+    uint8_t* dp = mode == WRSN_REC_PACK ? rp : (uint8_t*)(uintptr_t)(sg.base + (uint64_t)dst_env[r] * (uint64_t)sg.stride + (uint64_t)o);
+    if (sg.kind == WRSN_SEG_V16 || mode == WRSN_REC_UNPACK) {
+        const WrsnU4 v = wrsn_ld_u4(wrsn_global((const WrsnU4*)sp));   // (the record side is always 16-byte aligned)
+        if (sg.kind == WRSN_SEG_V16) { wrsn_st_u4(wrsn_global((WrsnU4*)dp), v); return; }
+        const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
         uint32_t WRSN_GLOBAL_AS* d32 = wrsn_global((uint32_t*)dp);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -136,6 +103,50 @@ __global__ void __launch_bounds__(256) wrsn_rec_copy_kernel(const WrsnSeg* __res
             const int rule = sg.kind == WRSN_SEG_DYN ? wrsn_rec_dyn_word(ok) : 0;
             if (rule != 1) d32[k] = rule == 2 ? 0u : w4[k];
         }
+        return;
+    }
+    // a word-copied slice read from an environment (pack, clone)
+    const uint32_t WRSN_GLOBAL_AS* s32 = wrsn_global((const uint32_t*)sp);
+    uint32_t w4[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w4[k] = (o + 4 * k < sg.bytes) ? s32[k] : 0u;
+    if (mode == WRSN_REC_PACK) {
+        WrsnU4 v; v.x = w4[0]; v.y = w4[1]; v.z = w4[2]; v.w = w4[3];
+        wrsn_st_u4(wrsn_global((WrsnU4*)dp), v);
+        return;
+    }
+    uint32_t WRSN_GLOBAL_AS* d32 = wrsn_global((uint32_t*)dp);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int ok = o + 4 * k;
+        if (ok >= sg.bytes) break;
+        const int rule = sg.kind == WRSN_SEG_DYN ? wrsn_rec_dyn_word(ok) : 0;
+        if (rule != 1) d32[k] = rule == 2 ? 0u : w4[k];
+    }
+}
+
+// the segment table of the handle into LDS (every thread of the 256-thread block calls this)
+WDEV void wrsn_rec_load_table(WrsnSeg* tab, const WrsnSeg* __restrict__ segs, int nseg) {
+    const uint64_t* g = (const uint64_t*)segs; uint64_t* l = (uint64_t*)tab;
+    for (int w = threadIdx.x; w < nseg * 4; w += 256) l[w] = g[w];
+    __syncthreads();
+}
+
+// One copy loop for the three directions.  Pair i (record i0 + i of the call) copies chunks [WRSN_REC_HDR / 16, chunks) of the record
+// layout: source environment src_env[i0 + i] (pack, clone), destination environment dst_env[i0 + i] (unpack, clone), record
+// rec + (i0 + i) * rec_stride (pack, unpack).  Launch: 256 threads, LDS nseg * 32 bytes (the segment table).
+__global__ void __launch_bounds__(256) wrsn_rec_copy_kernel(const WrsnSeg* __restrict__ segs, int nseg, int mode, const int32_t* __restrict__ src_env,
+                                                            const int32_t* __restrict__ dst_env, uint8_t* __restrict__ rec, long long rec_stride,
+                                                            int i0, int n, int chunks) {
+    extern __shared__ double smem[];
+    WrsnSeg* tab = (WrsnSeg*)smem;
+    wrsn_rec_load_table(tab, segs, nseg);
+    const int hc = WRSN_REC_HDR / 16, per = chunks - hc;      // chunks of one pair
+    const int total = n * per, step = (int)gridDim.x * 256;
+    for (int g = (int)blockIdx.x * 256 + (int)threadIdx.x; g < total; g += step) {
+        const int i = g / per, c = g - i * per + hc, r = i0 + i;
+        uint8_t* rp = rec ? rec + (size_t)r * (size_t)rec_stride + (size_t)c * 16 : nullptr;
+        wrsn_rec_copy_chunk(tab, nseg, mode, src_env, dst_env, r, c, rp);
     }
 }
 
@@ -163,18 +174,25 @@ __global__ void __launch_bounds__(256) wrsn_rec_gather_kernel(const uint8_t* __r
     for (int k = 0; k < WRSN_REC_HDR / 16; ++k) wrsn_st_u4(wrsn_global(o + k), wrsn_ld_u4(wrsn_global(s + k)));
 }
 
-// The request rows of the environments a load or a clone replaced: from the gathered headers hdr[i] (load) or from row src_env[i] of
-// `out` (clone) into row dst_env[i]; NULL fields of `out` are skipped.  row_state = 0 (a following wrsn_rollout_collect appends nothing
-// for the row); rend[dst] = the request's charger for the observation pass (rows not named keep -1).  One thread per row.
-__global__ void __launch_bounds__(256) wrsn_rec_rows_kernel(WrsnDev d, const uint8_t* __restrict__ hdr, const int32_t* __restrict__ src_env,
-                                                            const int32_t* __restrict__ dst_env, int n, WrsnStepOutDev out, int32_t* __restrict__ rend) {
+// The request rows of the environments a load, a clone or a pool reset replaced: from header i of `hdr` (load: the gathered headers,
+// hdr_stride = WRSN_REC_HDR, rec_idx NULL; pool reset: the pool itself, header rec_idx[i] at hdr_stride = record bytes) or from row
+// src_env[i] of `out` (clone) into row dst_env[i]; NULL fields of `out` are skipped.  n_dev, when set, holds the number of rows in
+// device memory (n is then the launch's upper bound).  status_as < 0: the saved status, else that value.  row_state = row_st
+// (0: a following wrsn_rollout_collect appends nothing for the row; 2: it discards what was pending, as after a reset); rend[dst] = the
+// request's charger for the observation pass (rows not named keep -1).  pool_cur, when set (load, clone): the pool record the
+// destination runs, -1 after a load, the source's after a clone.  One thread per row.
+__global__ void __launch_bounds__(256) wrsn_rec_rows_kernel(WrsnDev d, const uint8_t* __restrict__ hdr, long long hdr_stride, const int32_t* __restrict__ rec_idx,
+                                                            const int32_t* __restrict__ src_env, const int32_t* __restrict__ dst_env, int n,
+                                                            const int32_t* __restrict__ n_dev, WrsnStepOutDev out, int32_t* __restrict__ rend,
+                                                            int status_as, int row_st, int32_t* __restrict__ pool_cur) {
     const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
-    if (i >= n) return;
+    if (i >= n || (n_dev && i >= *n_dev)) return;
     const int e = dst_env[i];
     int aid = -1, st = 0, term = 0; double rw = 0.0, nw = 0.0;
     if (hdr) {
-        const WrsnRecHeader* hd = (const WrsnRecHeader*)(hdr + (size_t)i * WRSN_REC_HDR);
+        const WrsnRecHeader* hd = (const WrsnRecHeader*)(hdr + (size_t)(rec_idx ? rec_idx[i] : i) * (size_t)hdr_stride);
         aid = hd->agent_id; st = hd->status; term = hd->terminal; rw = hd->reward; nw = hd->now;
+        if (pool_cur) pool_cur[e] = -1;
     } else {
         const int s = src_env[i];
         if (out.agent_id) aid = out.agent_id[s];
@@ -182,12 +200,108 @@ __global__ void __launch_bounds__(256) wrsn_rec_rows_kernel(WrsnDev d, const uin
         if (out.terminal) term = out.terminal[s];
         if (out.reward) rw = out.reward[s];
         if (out.now) nw = out.now[s];
+        if (pool_cur) pool_cur[e] = pool_cur[s];
     }
+    if (status_as >= 0) st = status_as;
     if (out.agent_id) out.agent_id[e] = aid;
     if (out.status) out.status[e] = st;
     if (out.terminal) out.terminal[e] = (uint8_t)term;
     if (out.reward) out.reward[e] = rw;
     if (out.now) out.now[e] = nw;
-    d.row_state[e] = 0;
+    d.row_state[e] = row_st;
     if (rend) rend[e] = aid;
+}
+
+// ------------------------------------------------------------------ scenario pools (wrsn_pool_set / wrsn_pool_reset)
+// A pool is P records back to back in caller-owned device memory.  wrsn_pool_reset replaces the environments the DEVICE selects by pool
+// records the DEVICE selects, with no host round trip: wrsn_pool_select_kernel compacts the (environment, record) pairs,
+// wrsn_pool_copy_kernel is the unpack direction of the copy loop above over that list, wrsn_rec_rows_kernel writes the request rows.
+
+#define WRSN_POOL_BAD_INDEX (-5)         // per-row status of a selected row whose pool_index is outside [0, P) (WRSN_STATUS_POOL_INDEX)
+#define WRSN_POOL_STRIPS 8               // 64-row strips whose loads one pass of the select kernel keeps in flight
+
+// The record environment e takes at its k-th swap since wrsn_pool_set(seed): splitmix64 of the (environment, swap) counter, the high 32
+// bits scaled to [0, P).  multi_agent_rl_wrsn_amd.pool_draw is the same function on the host.
+WDEV int wrsn_pool_draw(uint64_t seed, int e, uint32_t k, int P) {
+    uint64_t z = (seed ^ (((uint64_t)(uint32_t)e << 32) | (uint64_t)k)) + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (int)(((z >> 32) * (uint64_t)(uint32_t)P) >> 32);
+}
+
+// Select and compact: ONE wave.  Row e is selected by mask[e] != 0, or with mask == NULL by live.dyn[e].terminal_pending (the rows an
+// auto-reset would take); its record is pool_index[e], or with pool_index == NULL the draw.  The selected rows with a record in [0, P)
+// become the pair list (pair_env[i], pair_rec[i]), i < *count, in ascending environment order: the wave walks the rows in 64-row
+// strips, a ballot of the strip and the popcount of the lanes below give every lane its place, so the order is a pure function of the
+// inputs.  The loads of WRSN_POOL_STRIPS strips are issued before the first ballot.  For every pair: agent_id[e] = -2 (when given: the
+// caller's next wrsn_step leaves the row alone), cur[e] = record, swaps[e] += 1.  A selected row with a bad index gets status
+// WRSN_POOL_BAD_INDEX and nothing else.  rend (when given) is preset to -1 for every row.  Launch: 1 block of 64 threads.
+__global__ void __launch_bounds__(64) wrsn_pool_select_kernel(WrsnDev d, const uint8_t* __restrict__ mask, const int32_t* __restrict__ pool_index, int P,
+                                                              uint64_t seed, int32_t* __restrict__ agent_id, int32_t* __restrict__ cur,
+                                                              int32_t* __restrict__ swaps, int32_t* __restrict__ pair_env, int32_t* __restrict__ pair_rec,
+                                                              int32_t* __restrict__ count, int32_t* __restrict__ status, int32_t* __restrict__ rend) {
+    const int lane = (int)threadIdx.x, B = d.B;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int base = 0;
+    for (int e0 = 0; e0 < B; e0 += 64 * WRSN_POOL_STRIPS) {
+        int sel[WRSN_POOL_STRIPS];
+#pragma unroll
+        for (int s = 0; s < WRSN_POOL_STRIPS; ++s) {
+            const int e = e0 + 64 * s + lane;
+            sel[s] = e < B ? (mask ? (int)mask[e] : d.live.dyn[e].terminal_pending) : 0;
+        }
+#pragma unroll
+        for (int s = 0; s < WRSN_POOL_STRIPS; ++s) {
+            const int e = e0 + 64 * s + lane;
+            if (e0 + 64 * s >= B) break;                       // (wave-uniform)
+            int rec = -1, k = 0, ok = 0;
+            if (sel[s] != 0) {
+                k = swaps[e];
+                rec = pool_index ? pool_index[e] : wrsn_pool_draw(seed, e, (uint32_t)k, P);
+                ok = rec >= 0 && rec < P;
+                if (!ok && status) status[e] = WRSN_POOL_BAD_INDEX;
+            }
+            if (rend && e < B) rend[e] = -1;
+            const unsigned long long m = __ballot(ok);
+            if (ok) {
+                const int pos = base + __popcll(m & below);
+                pair_env[pos] = e; pair_rec[pos] = rec;
+                cur[e] = rec; swaps[e] = k + 1;
+                if (agent_id) agent_id[e] = -2;
+            }
+            base += __popcll(m);
+        }
+    }
+    if (lane == 0) *count = base;
+}
+
+// The unpack direction of the copy loop over a pair list whose length is in device memory: pair i replaces environment dst_env[i] by
+// record rec_idx[i] of the pool (pool + rec_idx[i] * rec_stride).  The grid is fixed by the host (it does not know the length) and
+// grid-stride; with no pair every block leaves at once.  Launch: 256 threads, LDS nseg * 32 bytes.
+__global__ void __launch_bounds__(256) wrsn_pool_copy_kernel(const WrsnSeg* __restrict__ segs, int nseg, const int32_t* __restrict__ dst_env,
+                                                             const int32_t* __restrict__ rec_idx, const int32_t* __restrict__ n_dev,
+                                                             const uint8_t* __restrict__ pool, long long rec_stride, int chunks) {
+    extern __shared__ double smem[];
+    const int n = *n_dev;
+    if (n <= 0) return;                                         // (uniform over the grid)
+    WrsnSeg* tab = (WrsnSeg*)smem;
+    wrsn_rec_load_table(tab, segs, nseg);
+    const int hc = WRSN_REC_HDR / 16, per = chunks - hc;      // chunks of one pair
+    const long long total = (long long)n * per;
+    if (total < (1ll << 31)) {                                  // 32-bit chunk indices, as in wrsn_rec_copy_kernel
+        const unsigned tot = (unsigned)total, step = gridDim.x * 256u;
+        for (unsigned g = blockIdx.x * 256u + threadIdx.x; g < tot; g += step) {
+            const int i = (int)(g / (unsigned)per), c = (int)(g - (unsigned)i * (unsigned)per) + hc;
+            uint8_t* rp = (uint8_t*)pool + (size_t)rec_idx[i] * (size_t)rec_stride + (size_t)c * 16;
+            wrsn_rec_copy_chunk(tab, nseg, WRSN_REC_UNPACK, nullptr, dst_env, i, c, rp);
+        }
+    } else {
+        const long long step = (long long)gridDim.x * 256;
+        for (long long g = (long long)blockIdx.x * 256 + (long long)threadIdx.x; g < total; g += step) {
+            const int i = (int)(g / per), c = (int)(g - (long long)i * per) + hc;
+            uint8_t* rp = (uint8_t*)pool + (size_t)rec_idx[i] * (size_t)rec_stride + (size_t)c * 16;
+            wrsn_rec_copy_chunk(tab, nseg, WRSN_REC_UNPACK, nullptr, dst_env, i, c, rp);
+        }
+    }
 }

@@ -78,8 +78,7 @@ class VecWRSN:
         self.warm_up_time = float(warm_up_time)
         self.auto_reset = bool(auto_reset)
         self.render = bool(render)
-        self.n_node = max(s.n_node for s in scenarios)
-        self.n_target = max(s.n_target for s in scenarios)
+        self.n_node, self.n_target = self._sizes(scenarios)
         lib = _lib.load()
         dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
         with torch.cuda.device(dev_index):
@@ -107,6 +106,11 @@ class VecWRSN:
             self.state = torch.zeros((B, 4, G, G), dtype=self.obs_dtype, device=self.device) if self.render else None
             self._in_agent = torch.zeros(B, dtype=torch.int32, device=self.device)
             self._in_action = torch.zeros((B, 3), dtype=torch.float64, device=self.device)
+            self._pool = None                                 # the records of set_pool, alive as long as the handle reads them
+
+    def _sizes(self, scenarios):
+        """Node and target count the handle is created for."""
+        return max(s.n_node for s in scenarios), max(s.n_target for s in scenarios)
 
     # -- plumbing -----------------------------------------------------------------------------------------
     def _out_ptrs(self):
@@ -150,6 +154,13 @@ class VecWRSN:
         x = actions
         if not (x.dtype == t.float64 and x.device == self.device and x.is_contiguous() and x.numel() == 3 * self.num_env):
             self._in_action.copy_(x.to(device=self.device, dtype=t.float64).reshape(-1, 3)); x = self._in_action
+        if self._pool is not None and self.auto_reset:
+            # rows whose last return was terminal restart in a drawn pool record, on the device: wrsn_pool_reset marks them -2 in a copy
+            # of the ids (never the caller's tensor, never this object's `agent_id` output), the step then leaves them alone and their
+            # rows carry the status-3 request of the new network out of this call
+            if a is not self._in_agent:
+                self._in_agent.copy_(a); a = self._in_agent
+            self._h.pool_reset(0, 0, a.data_ptr(), **self._out_ptrs())
         self._keep_in = (a, x)                                # alive until the launch has run
         self._h.step(a.data_ptr(), x.data_ptr(), self.auto_reset, **self._out_ptrs())
         return self._result()
@@ -239,6 +250,45 @@ class VecWRSN:
         self._h.clone_envs(s, d, **self._out_ptrs())
         return self._result()
 
+    # -- scenario pools: finished episodes restart in another network, on the device (wrsn_pool_set / wrsn_pool_reset) ----------------
+    def set_pool(self, records, seed=0):
+        """Register `records` ([P, record_bytes()] uint8, e.g. from `build_scenario_pool`; None clears) as this batch's scenario pool.
+        With `auto_reset=True` every `step` from now on restarts the environments whose last return was terminal in a pool record
+        drawn on the device (`pool_draw(seed, env, swaps so far, P)`) instead of their own scenario: the same protocol, a status-3 row
+        with the reset request, of a new network."""
+        t = self.torch
+        self._bind_stream()
+        if records is None:
+            self._h.pool_set(0, 0, 0)
+            self._pool = None
+            return
+        if records.dim() != 2 or records.dtype != t.uint8:
+            raise ValueError("records must be a uint8 tensor [P, record_bytes]")
+        rec = records.to(device=self.device).contiguous()
+        if rec.shape[1] != self._h.env_record_bytes():
+            raise ValueError("records of %d bytes, this batch's are %d" % (rec.shape[1], self._h.env_record_bytes()))
+        self._h.pool_set(rec.data_ptr(), rec.shape[0], seed)
+        self._pool = rec
+
+    def pool_reset(self, mask=None, index=None):
+        """Replace the environments with mask != 0 (None: those whose last return was terminal) by the pool records `index` (int tensor
+        [B], read for the selected rows; None: drawn on the device).  Asynchronous, no host round trip.  Returns the request tensors:
+        replaced rows hold their record's reset request (status 0 with a mask, 3 without), every other row is untouched."""
+        t = self.torch
+        self._bind_stream()
+        mptr = iptr = 0
+        if mask is not None:
+            self._mask = mask.to(device=self.device, dtype=t.uint8).contiguous(); mptr = self._mask.data_ptr()
+        if index is not None:
+            self._pool_index = index.to(device=self.device, dtype=t.int32).contiguous(); iptr = self._pool_index.data_ptr()
+        self._h.pool_reset(mptr, iptr, 0, **self._out_ptrs())
+        return self._result()
+
+    def pool_info(self):
+        """Per environment: the pool record it runs (-1: its own scenario or a loaded record) and its swaps since `set_pool` (host copies)."""
+        a = self._h.peek(_lib.PEEK_POOL)
+        return {"record": a[:, 0].copy(), "swaps": a[:, 1].copy()}
+
     def synchronize(self):
         self._h.sync()
 
@@ -271,3 +321,43 @@ class VecWRSN:
         if getattr(self, "_h", None) is not None:
             self._h.close()
             self._h = None
+
+
+def build_scenario_pool(scenarios, agent_type=None, num_agent=3, map_size=100, warm_up_time=100, device="cuda:0", n_node=None, n_target=None,
+                        chunk=256, **capacities):
+    """Records of `scenarios` right after `reset()`: a uint8 device tensor [P, record_bytes] for `VecWRSN.set_pool` of a batch with the
+    same geometry (num_agent, the node / target classes of n_node / n_target, max_degree / max_cover in `capacities`).  The scenarios
+    are run `chunk` at a time through a temporary VecWRSN created for n_node nodes and n_target targets (default: the largest of
+    `scenarios`), so scenarios of different sizes share one pool as long as they fit."""
+    import torch
+    scenarios = list(scenarios)
+    if not scenarios:
+        raise ValueError("no scenarios")
+    n_node = int(n_node) if n_node else max(s.n_node for s in scenarios)
+    n_target = int(n_target) if n_target else max(s.n_target for s in scenarios)
+    chunk = max(1, min(int(chunk), len(scenarios)))
+    env = _PoolBuilder(scenarios[:chunk], n_node, n_target, agent_type=agent_type, num_agent=num_agent, map_size=map_size,
+                       warm_up_time=warm_up_time, device=device, render=False, **capacities)
+    parts = []
+    try:
+        for i0 in range(0, len(scenarios), chunk):
+            part = scenarios[i0:i0 + chunk]
+            if i0:
+                env._h.set_scenarios(part, env.mc_spec)
+            env.reset()
+            parts.append(env.save_envs(range(len(part))))
+        env.synchronize()
+    finally:
+        env.close()
+    return torch.cat(parts, 0) if len(parts) > 1 else parts[0]
+
+
+class _PoolBuilder(VecWRSN):
+    """A VecWRSN whose handle is created for a stated node / target count rather than the largest of its scenarios."""
+
+    def __init__(self, scenarios, n_node, n_target, **kw):
+        self._geometry = (n_node, n_target)
+        super().__init__(scenarios, **kw)
+
+    def _sizes(self, scenarios):
+        return self._geometry
