@@ -244,6 +244,45 @@ int wrsn_rollout_collect(wrsn_t *h, const wrsn_transition_buffers *buf, const wr
  * observation format, wrsn_set_obs_format). */
 int wrsn_render(wrsn_t *h, const int32_t *agent_id, float *obs);
 
+/* ENTITY OBSERVATION: the numbers get_state(agent) rasterises, instead of the 4 x G x G image.  Map 1 of get_state is one separable
+ * Gaussian per live node with weight w_n at the node's down-mapped position (WRSN.py:137-147), maps 2..4 are at most M rank-1 terms
+ * built from the chargers (WRSN.py:149-185).  With entity buffers registered, every call that renders also writes those terms as
+ * float32 rows: per node, per charger and per environment, about 6.6 KB per row at 200 nodes x 3 chargers.
+ * With W = xmax - xmin, H = ymax - ymin, a_b2 = alpha / beta^2 and `a` the asking charger of the row:
+ *   node n    [0] u = (x - xmin) / W   [1] v = (y - ymin) / H   [2] w_n = (CS / a_b2) / ((E - thr) / (cap - thr))   (WRSN.py:146)
+ *             [3] (E - thr) / (cap - thr)   [4] CS / a_b2   [5] RR / a_b2   [6] Node.level as WRSN_PEEK_NODE_LEVEL reports it   [7] 1
+ *             a dead node (Node.status == 0) keeps [0], [1] and has 0 in [2..7]; rows n >= n_node of a smaller environment of a
+ *             ragged batch are all zero (they are written);
+ *   charger o [0], [1] loc, down-mapped   [2] energy / capacity   [3] o == a   [4] status != 0   [5] cur_action_type == "charging"
+ *             [6], [7] cur_phy_action x, y, down-mapped   [8] cur_phy_action[2] / charging_time_max
+ *             [9] the map-4 amplitude as the reference writes it (WRSN.py:184, mixed index and all):
+ *                 euclid(loc_o, (cur_o[0], cur_a[1])) / velocity / moving_time_max; 0 for o == a        [10], [11] 0, reserved
+ *   env       [0] hX = charging_range / W   [1] hY = charging_range / H   (bandwidths of maps 1, 3, 4)
+ *             [2] 0.5 min(W, H) / W   [3] 0.5 min(W, H) / H   (bandwidths of map 2)   [4] a   [5] n_node   [6], [7] 0
+ * Every value is computed in float64 from the fields the render kernel reads and rounded once, to float32, at the store: an image and
+ * an entity row written by the same call describe the same instant. */
+#define WRSN_ENT_NODE_F 8
+#define WRSN_ENT_MC_F  12
+#define WRSN_ENT_ENV_F  8
+typedef struct wrsn_entity_out {   /* DEVICE, caller-owned, 16-byte aligned, float32 */
+    float *node;              /* [B, N, 8]  N = cfg.n_node, node-id order */
+    float *mc;                /* [B, M, 12] charger-id order              */
+    float *env;               /* [B, 8]                                   */
+} wrsn_entity_out;
+
+/* Register (or, with ent == NULL, drop: the default) the entity buffers of the handle.  Once registered, every call that decides which
+ * rows to render writes the entity rows of exactly those rows, whether or not out->obs is given: wrsn_reset, wrsn_step in every launch
+ * mode (blocking, step budget, two-stage pipeline, time slices), wrsn_load_envs, wrsn_clone_envs (needs out->agent_id, as for obs) and
+ * wrsn_pool_reset.  Rows such a call leaves unrendered (terminal, status 4, agent_id -2, masked out, unselected pool rows) are not
+ * touched by a single byte.  wrsn_render writes no entity rows.  Independent of wrsn_set_obs_format (always float32) and of
+ * wrsn_set_obs_reuse; not part of an environment record; allowed between any two calls, affects the launches enqueued after it.  The
+ * memory must stay valid while registered.  A pointer that is NULL or not 16-byte aligned: WRSN_ERR_ARG, handle unchanged. */
+int wrsn_set_entity_out(wrsn_t *h, const wrsn_entity_out *ent);
+
+/* Entity rows for arbitrary agents (DEVICE int32 [B], < 0 = skip) into `ent`, like wrsn_render for the image; the registered buffers
+ * are neither needed nor touched.  Asynchronous on the handle's stream. */
+int wrsn_entities(wrsn_t *h, const int32_t *agent_id, const wrsn_entity_out *ent);
+
 /* Copy internal state to HOST memory (parity tests, `net` / `agents` views).  Synchronises. */
 int wrsn_peek(wrsn_t *h, int32_t what, void *dst);
 
@@ -270,8 +309,8 @@ int wrsn_set_obs_format(wrsn_t *h, int32_t format);
 /* Per-kernel timing of the step path with HIP events recorded on the handle's stream (the stream the kernels are launched on).
  * wrsn_set_timing(h, 1) makes every following wrsn_step record four events; wrsn_kernel_times waits for the last call and
  * returns, in milliseconds: ms[0] launch-order kernels (work estimate + sort), ms[1] step kernel, ms[2] always 0 (the continuation
- * launch it timed no longer exists; the slot stays for the callers that add it to ms[1]), ms[3] observation kernel (0 when no
- * observation was requested).  Measurement only. */
+ * launch it timed no longer exists; the slot stays for the callers that add it to ms[1]), ms[3] observation kernel plus, with entity
+ * buffers registered (wrsn_set_entity_out), the entity launch behind it (0 when the call rendered neither).  Measurement only. */
 int wrsn_set_timing(wrsn_t *h, int32_t on);
 int wrsn_kernel_times(wrsn_t *h, float *ms);
 

@@ -22,6 +22,14 @@ PEEK_POOL = 13               # int32 [B, 2]: the pool record the environment run
 STATUS_POOL_INDEX = -5       # per-row status of wrsn_pool_reset: pool_index outside the pool, row left as it was
 PEEK_RNG_STATE = 12          # uint32 [B, 627]: MT19937 words, index (random.getstate()[1]), draws since reset (low, high word)
 OBS_F32, OBS_BF16 = 0, 1     # wrsn_set_obs_format: float32 cells / bfloat16 bit patterns (uint16) behind every observation pointer
+# entity observation (wrsn_set_entity_out / wrsn_entities): floats per node, charger and environment row, and what each slot holds
+ENT_NODE_F, ENT_MC_F, ENT_ENV_F = 8, 12, 8
+ENT_NODE_FIELDS = ("u", "v", "weight", "energy_frac", "cs", "rr", "level", "alive")
+ENT_MC_FIELDS = ("loc_u", "loc_v", "energy_frac", "is_self", "alive", "charging", "cur_u", "cur_v", "cur_time", "move_time", "_r0", "_r1")
+ENT_ENV_FIELDS = ("h_x", "h_y", "h_self_x", "h_self_y", "agent", "n_node", "_r0", "_r1")
+ENT_NODE = {k: i for i, k in enumerate(ENT_NODE_FIELDS)}      # ENT_NODE["weight"] == 2: the slot of a field, no magic numbers at the caller
+ENT_MC = {k: i for i, k in enumerate(ENT_MC_FIELDS) if not k.startswith("_")}
+ENT_ENV = {k: i for i, k in enumerate(ENT_ENV_FIELDS) if not k.startswith("_")}
 MC_FIELDS = ("loc_x", "loc_y", "energy", "status", "type_charging", "cur_x", "cur_y", "cur_t", "n_conn",
              "excl", "prev_minfit", "act0", "act1", "act2", "_r0", "_r1")
 ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max", "charging_time_max",
@@ -29,7 +37,7 @@ ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max"
 
 # every entry point include/wrsn_hip.h declares
 EXPORTS = ("wrsn_create", "wrsn_destroy", "wrsn_set_stream", "wrsn_set_scenario", "wrsn_set_scenario_seeded", "wrsn_reset", "wrsn_step",
-           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_render", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
+           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
            "wrsn_clone_envs", "wrsn_pool_set", "wrsn_pool_reset", "wrsn_synth_network",
            "wrsn_last_error",
            "wrsn_version")
@@ -54,6 +62,10 @@ class WrsnMcSpec(C.Structure):
 class WrsnStepOut(C.Structure):
     _fields_ = [("agent_id", C.c_void_p), ("reward", C.c_void_p), ("terminal", C.c_void_p), ("now", C.c_void_p),
                 ("obs", C.c_void_p), ("status", C.c_void_p)]
+
+
+class WrsnEntityOut(C.Structure):
+    _fields_ = [("node", C.c_void_p), ("mc", C.c_void_p), ("env", C.c_void_p)]
 
 
 class WrsnTransitionBuffers(C.Structure):
@@ -109,6 +121,10 @@ def bind(lib):
     lib.wrsn_kernel_times.restype = C.c_int
     lib.wrsn_render.argtypes = [vp, vp, vp]
     lib.wrsn_render.restype = C.c_int
+    lib.wrsn_set_entity_out.argtypes = [vp, C.POINTER(WrsnEntityOut)]
+    lib.wrsn_set_entity_out.restype = C.c_int
+    lib.wrsn_entities.argtypes = [vp, vp, C.POINTER(WrsnEntityOut)]
+    lib.wrsn_entities.restype = C.c_int
     lib.wrsn_peek.argtypes = [vp, C.c_int32, vp]
     lib.wrsn_peek.restype = C.c_int
     lib.wrsn_sync.argtypes = [vp]
@@ -289,6 +305,19 @@ class RawHandle:
 
     def render(self, agent_ptr, obs_ptr):
         check(self.lib, self.lib.wrsn_render(self._h, C.c_void_p(agent_ptr), C.c_void_p(obs_ptr)))
+
+    def set_entity_out(self, node_ptr=0, mc_ptr=0, env_ptr=0):
+        """Register the entity buffers ([B,N,8], [B,M,12], [B,8] float32, device, 16-byte aligned); no argument drops them."""
+        if not (node_ptr or mc_ptr or env_ptr):
+            check(self.lib, self.lib.wrsn_set_entity_out(self._h, None))
+            return
+        e = WrsnEntityOut(node_ptr or None, mc_ptr or None, env_ptr or None)
+        check(self.lib, self.lib.wrsn_set_entity_out(self._h, C.byref(e)))
+
+    def entities(self, agent_ptr, node_ptr, mc_ptr, env_ptr):
+        """Entity rows of the chargers at agent_ptr (int32 [B], < 0: row skipped) into the three buffers."""
+        e = WrsnEntityOut(node_ptr or None, mc_ptr or None, env_ptr or None)
+        check(self.lib, self.lib.wrsn_entities(self._h, C.c_void_p(agent_ptr), C.byref(e)))
 
     def sync(self):
         check(self.lib, self.lib.wrsn_sync(self._h))

@@ -107,6 +107,7 @@ struct wrsn_handle {
     const uint8_t* pool = nullptr; int pool_n = 0; uint64_t pool_seed = 0; int64_t pool_rec_bytes = 0;
     int32_t* d_pool_cur = nullptr; int32_t* d_pool_swaps = nullptr;
     int32_t* d_pairs = nullptr; int32_t* d_pair_n = nullptr;
+    WrsnEntityOut ent{};            // wrsn_set_entity_out: the caller's entity-observation buffers (node == nullptr: off, the default)
 };
 
 namespace {
@@ -224,9 +225,21 @@ void launch_obs(wrsn_handle* h, hipStream_t stream, const int32_t* agent_id, flo
         hipLaunchKernelGGL(wrsn_obs_kernel, dim3(nblocks), dim3(256), h->lds_obs, stream, h->dev, agent_id, obs, h->obs_reuse, order, block0);
 }
 
-// the whole batch on the caller's stream
-int launch_obs_all(wrsn_handle* h, const int32_t* agent_id, float* obs) {
-    launch_obs(h, h->stream, agent_id, obs, nullptr, 0, h->dev.B);
+// The one entity-observation launch, next to launch_obs on the same stream with the same rows: nothing unless buffers are registered
+// (wrsn_set_entity_out) or `to` names some (wrsn_entities).  K nodes per thread: the smallest of 1, 2, 4 with K * 256 >= N.
+void launch_entities(wrsn_handle* h, hipStream_t stream, const int32_t* agent_id, const int32_t* order, int block0, int nblocks, const WrsnEntityOut* to = nullptr) {
+    const WrsnEntityOut& e = to ? *to : h->ent;
+    if (!e.node) return;
+    const int k = (h->dev.N + 255) / 256;
+    if (k <= 1) hipLaunchKernelGGL(wrsn_entity_kernel<1>, dim3(nblocks), dim3(256), 0, stream, h->dev, agent_id, e, order, block0);
+    else if (k == 2) hipLaunchKernelGGL(wrsn_entity_kernel<2>, dim3(nblocks), dim3(256), 0, stream, h->dev, agent_id, e, order, block0);
+    else hipLaunchKernelGGL(wrsn_entity_kernel<4>, dim3(nblocks), dim3(256), 0, stream, h->dev, agent_id, e, order, block0);
+}
+
+// the rows of `agent_id` over the whole batch on the caller's stream: the image when `obs` is given, then the entity rows when registered
+int launch_render_all(wrsn_handle* h, const int32_t* agent_id, float* obs) {
+    if (obs) launch_obs(h, h->stream, agent_id, obs, nullptr, 0, h->dev.B);
+    launch_entities(h, h->stream, agent_id, nullptr, 0, h->dev.B);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -271,7 +284,7 @@ int launch_reset(wrsn_handle* h, const uint8_t* mask, const WrsnStepOutDev& out)
     const StepCall c = {1, nullptr, nullptr, 0, 0, tapered_slots(h), mask, out, 0, 0};
     launch_step_blocks(h, c, h->stream, 0, h->dev.B, 0);
     HIPCHK(hipGetLastError());
-    return out.obs ? launch_obs_all(h, h->dev.render_agent, out.obs) : 0;
+    return (out.obs || h->ent.node) ? launch_render_all(h, h->dev.render_agent, out.obs) : 0;
 }
 
 // launch order of a step call, longest job first (wrsn_estimate_kernel / wrsn_sort_kernel, wrsn_sim.h): two tiny launches
@@ -291,12 +304,13 @@ void launch_order(wrsn_handle* h, const StepCall& c) {
 #undef WRSN_SORT
 }
 
-// behind the step launch(es) of a call that is not pipelined: one observation launch over the whole batch when the call renders
+// behind the step launch(es) of a call that is not pipelined: one observation launch over the whole batch when the call renders, one
+// entity launch when entity buffers are registered
 int finish_step(wrsn_handle* h, const StepCall& c) {
     time_mark(h, 2);
     HIPCHK(hipGetLastError());
-    if (!c.out.obs) return 0;
-    if (int rc = launch_obs_all(h, h->dev.render_agent, c.out.obs)) return rc;
+    if (!c.out.obs && !h->ent.node) return 0;
+    if (int rc = launch_render_all(h, h->dev.render_agent, c.out.obs)) return rc;
     time_mark(h, 3);
     return 0;
 }
@@ -342,10 +356,12 @@ int launch_step_pipeline(wrsn_handle* h, const StepCall& c) {
     (void)hipEventRecord(h->ev_fork, h->stream); (void)hipStreamWaitEvent(h->stream2, h->ev_fork, 0);
     launch_step_blocks(h, c, h->stream2, n2, B - n2, b_short);
     launch_obs(h, h->stream2, agent, c.out.obs, order, n2, B - n2);
+    launch_entities(h, h->stream2, agent, order, n2, B - n2);
     (void)hipEventRecord(h->ev_join, h->stream2);
     launch_step_blocks(h, c, h->stream, 0, n2, budget);
     time_mark(h, 2);
     launch_obs(h, h->stream, agent, c.out.obs, order, 0, n2);
+    launch_entities(h, h->stream, agent, order, 0, n2);
     (void)hipStreamWaitEvent(h->stream, h->ev_join, 0);
     time_mark(h, 3);
     HIPCHK(hipGetLastError());
@@ -519,13 +535,14 @@ int launch_rec_copy(wrsn_handle* h, int mode, const int32_t* src_env, const int3
     return 0;
 }
 
-// request rows of replaced environments (+ their observations when out->obs is set)
+// request rows of replaced environments (+ their observations when out->obs is set, their entity rows when registered)
 int launch_rec_rows(wrsn_handle* h, const uint8_t* hdr, const int32_t* src_env, const int32_t* dst_env, int n, const wrsn_step_out* out) {
-    if (out->obs) HIPCHK(hipMemsetAsync(h->d_rend, 0xFF, (size_t)h->dev.B * sizeof(int32_t), h->stream));
+    const bool renders = out->obs || h->ent.node;
+    if (renders) HIPCHK(hipMemsetAsync(h->d_rend, 0xFF, (size_t)h->dev.B * sizeof(int32_t), h->stream));
     hipLaunchKernelGGL(wrsn_rec_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->dev, hdr, (long long)WRSN_REC_HDR, (const int32_t*)nullptr, src_env, dst_env, n,
-                       (const int32_t*)nullptr, step_out_dev(out), out->obs ? h->d_rend : (int32_t*)nullptr, -1, 0, h->d_pool_cur);
+                       (const int32_t*)nullptr, step_out_dev(out), renders ? h->d_rend : (int32_t*)nullptr, -1, 0, h->d_pool_cur);
     HIPCHK(hipGetLastError());
-    if (out->obs) return launch_obs_all(h, h->d_rend, out->obs);
+    if (renders) return launch_render_all(h, h->d_rend, out->obs);
     return 0;
 }
 
@@ -863,7 +880,34 @@ int wrsn_render(wrsn_t* h, const int32_t* agent_id, float* obs) {
     if (!h || !agent_id || !obs) return fail(WRSN_ERR_ARG, "null argument");
     if (!h->scenario_set) return fail(WRSN_ERR_STATE, "wrsn_set_scenario has not been called");
     WRSN_ON_DEVICE(h);
-    return launch_obs_all(h, agent_id, obs);
+    launch_obs(h, h->stream, agent_id, obs, nullptr, 0, h->dev.B);   // the image alone: entity rows of arbitrary agents are wrsn_entities
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+static int entity_out(const wrsn_entity_out* ent, WrsnEntityOut* e) {
+    if (!ent->node || !ent->mc || !ent->env) return fail(WRSN_ERR_ARG, "wrsn_entity_out: node, mc and env must all be given");
+    if (((uintptr_t)ent->node | (uintptr_t)ent->mc | (uintptr_t)ent->env) % 16) return fail(WRSN_ERR_ARG, "wrsn_entity_out: node, mc and env must be 16-byte aligned");
+    e->node = ent->node; e->mc = ent->mc; e->env = ent->env;
+    return 0;
+}
+
+int wrsn_set_entity_out(wrsn_t* h, const wrsn_entity_out* ent) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    WrsnEntityOut e{};
+    if (ent) { const int rc = entity_out(ent, &e); if (rc) return rc; }
+    h->ent = e;                                                // read at launch time: the launches enqueued so far keep theirs
+    return WRSN_OK;
+}
+
+int wrsn_entities(wrsn_t* h, const int32_t* agent_id, const wrsn_entity_out* ent) {
+    if (!h || !agent_id || !ent) return fail(WRSN_ERR_ARG, "null argument");
+    if (!h->scenario_set) return fail(WRSN_ERR_STATE, "wrsn_set_scenario has not been called");
+    WrsnEntityOut e{}; const int rc = entity_out(ent, &e); if (rc) return rc;
+    WRSN_ON_DEVICE(h);
+    launch_entities(h, h->stream, agent_id, nullptr, 0, h->dev.B, &e);
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
 }
 
 int wrsn_sync(wrsn_t* h) {
@@ -1061,7 +1105,7 @@ int wrsn_load_envs(wrsn_t* h, const int32_t* env, int32_t n, const void* src, co
 
 int wrsn_clone_envs(wrsn_t* h, const int32_t* src, const int32_t* dst, int32_t n, const wrsn_step_out* out) {
     if (!h || !src || !dst || !out || n < 1) return fail(WRSN_ERR_ARG, "null argument or n < 1");
-    if (out->obs && !out->agent_id) return fail(WRSN_ERR_ARG, "rendering the cloned rows needs out->agent_id");
+    if ((out->obs || h->ent.node) && !out->agent_id) return fail(WRSN_ERR_ARG, "rendering the cloned rows needs out->agent_id");
     int rc = check_envs(h, src, n, false, true, "src"); if (rc) return rc;
     if ((rc = check_envs(h, dst, n, true, false, "dst"))) return rc;
     {
@@ -1138,7 +1182,8 @@ int wrsn_pool_reset(wrsn_t* h, const uint8_t* env_mask, const int32_t* pool_inde
     if (out->obs && !out->agent_id) return fail(WRSN_ERR_ARG, "rendering the replaced rows needs out->agent_id");
     WRSN_ON_DEVICE(h);
     const int B = h->dev.B;
-    int32_t* rend = out->obs ? h->d_rend : (int32_t*)nullptr;
+    const bool renders = out->obs || h->ent.node;              // (the entity rows take the charger from the record's header)
+    int32_t* rend = renders ? h->d_rend : (int32_t*)nullptr;
     hipLaunchKernelGGL(wrsn_pool_select_kernel, dim3(1), dim3(64), 0, h->stream, h->dev, env_mask, pool_index, h->pool_n, h->pool_seed, agent_id, h->d_pool_cur,
                        h->d_pool_swaps, h->d_pairs, h->d_pairs + B, h->d_pair_n, out->status, rend);
     {   // fixed grid: at most eight blocks per CU, no more than the whole batch needs
@@ -1151,7 +1196,7 @@ int wrsn_pool_reset(wrsn_t* h, const uint8_t* env_mask, const int32_t* pool_inde
     hipLaunchKernelGGL(wrsn_rec_rows_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->dev, h->pool, (long long)h->rec_bytes, (const int32_t*)(h->d_pairs + B),
                        (const int32_t*)nullptr, (const int32_t*)h->d_pairs, B, (const int32_t*)h->d_pair_n, step_out_dev(out), rend, env_mask ? 0 : 3, 2, (int32_t*)nullptr);
     HIPCHK(hipGetLastError());
-    if (out->obs) return launch_obs_all(h, h->d_rend, out->obs);
+    if (renders) return launch_render_all(h, h->d_rend, out->obs);
     return WRSN_OK;
 }
 

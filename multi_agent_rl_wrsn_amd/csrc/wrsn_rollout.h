@@ -15,8 +15,12 @@
 // copied in the element size of the handle's observation format (`obs_es`: 4 = float32, 2 = bf16 bit patterns):
 //   wrsn_tr_record_kernel   pending[env][agent] <- (observation row, action row, log-prob)       one block per environment
 //   wrsn_tr_collect_kernel  transition[agent][slot] <- (pending state/action/log-prob, reward, observation row)
+//
+// Below them, wrsn_entity_kernel: the ENTITY observation (wrsn_set_entity_out / wrsn_entities), the per-node, per-charger and
+// per-environment terms get_state(agent) is made of (WRSN.py:130-186) as float32 rows instead of the 4 x G x G image.
 #pragma once
 #include <stdint.h>
+#include "wrsn_state.h"
 
 struct WrsnTrBuffers {                    // mirrors wrsn_transition_buffers of include/wrsn_hip.h (device pointers)
     int32_t capacity, action_elems;
@@ -85,4 +89,93 @@ __global__ void __launch_bounds__(256) wrsn_tr_collect_kernel(int B, int M, int 
     wrsn_tr_copy_obs(t.next_state, q, obs, (size_t)e, S, obs_es, threadIdx.x);
     wrsn_tr_copy(t.action + q * A, t.pend_action + pslot * A, A, threadIdx.x, 256);
     if (threadIdx.x == 0) { t.reward[q] = (float)reward[e]; t.logp[q] = t.pend_logp[pslot]; t.now[q] = now[e]; t.env[q] = e; }
+}
+
+// ------------------------------------------------------------------ entity observation (wrsn_set_entity_out / wrsn_entities)
+// get_state(agent) rasterises a small set of numbers: one weighted Gaussian per live node (map 1) and at most M rank-1 terms built from the
+// chargers (maps 2..4).  This kernel writes those numbers themselves, float32, for the rows the render pass of a call draws:
+//   node [B][N][8]   u, v (position in the frame), w_n (the map-1 weight, WRSN.py:146), (E - thr) / (cap - thr), CS / (alpha/beta^2),
+//                    RR / (alpha/beta^2), level, 1; a dead node keeps u, v and has 0 elsewhere; rows beyond the environment's own
+//                    n_node are all zero (N = the handle's node count: the row stride);
+//   mc   [B][M][12]  loc (frame), energy / capacity, is the asking charger, status != 0, charging, cur_phy_action x, y (frame),
+//                    cur_phy_action[2] / charging_time_max, the map-4 amplitude with the reference's mixed index (WRSN.py:184;
+//                    0 for the asking charger), 0, 0;
+//   env  [B][8]      hX, hY (bandwidths of maps 1, 3, 4), the two bandwidths of map 2, asking charger, n_node, 0, 0.
+// Every value is a float64 expression of the fields wrsn_obs_body reads, rounded once at the store.  A gather with no reduction and no
+// LDS: one 256-thread block per row (block b takes row_map[map0 + b], or b), nodes in id order, K nodes per thread (K * 256 >= N), the
+// loads of all K issued -- with clamped indices, not predicates -- before the first use; a node row leaves as two 16-byte stores, a
+// charger row as three from one thread, the environment row as two.  It reads no map1_ptr / map1_valid and writes nothing but its rows.
+struct WrsnEntityOut { float* node; float* mc; float* env; };   // mirrors wrsn_entity_out of include/wrsn_hip.h (device pointers)
+#define WRSN_ENT_NODE_F 8
+#define WRSN_ENT_MC_F 12
+#define WRSN_ENT_ENV_F 8
+
+WDEV void wrsn_ent_store4(float* p, float a, float b, float c, float e) {
+    WrsnU4 v;
+    v.x = (uint32_t)__float_as_int(a); v.y = (uint32_t)__float_as_int(b); v.z = (uint32_t)__float_as_int(c); v.w = (uint32_t)__float_as_int(e);
+    wrsn_st_u4(wrsn_global((WrsnU4*)p), v);
+}
+
+template <int K>
+__global__ void __launch_bounds__(256) wrsn_entity_kernel(WrsnDev d, const int32_t* __restrict__ agent_id, WrsnEntityOut out,
+                                                          const int32_t* __restrict__ row_map, int map0) {
+    const int tid = (int)threadIdx.x;
+    const int env = __builtin_amdgcn_readfirstlane(row_map ? row_map[map0 + (int)blockIdx.x] : (int)blockIdx.x);
+    if (env < 0 || env >= d.B) return;
+    const int aid = __builtin_amdgcn_readfirstlane(agent_id[env]);
+    if (aid < 0 || aid >= d.M) return;
+    const int NP = d.NP, NR = d.N, M = d.M;                    // NR: node rows of an output row (the handle's node count <= NP)
+    const size_t nb = (size_t)env * NP;
+    // ---- every load of the K nodes of this thread, then the constants: one memory round trip
+    const auto gls = wrsn_global(d.live.ls + nb);
+    const auto gx = wrsn_global(d.node_x + nb), gy = wrsn_global(d.node_y + nb);
+    const auto gE = wrsn_global(d.live.E + nb), gCS = wrsn_global(d.live.CS + nb), gRR = wrsn_global(d.live.RR + nb);
+    int lsw[K]; double px[K], py[K], en[K], cs[K], rr[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int n = tid + 256 * k, src = n < NR ? n : NR - 1;   // clamped: rows beyond NR are not stored
+        lsw[k] = gls[src]; px[k] = gx[src]; py[k] = gy[src]; en[k] = gE[src]; cs[k] = gCS[src]; rr[k] = gRR[src];
+    }
+    const WrsnEnvConst WRSN_GLOBAL_AS* ec = wrsn_global((const WrsnEnvConst*)(d.ec + env));
+    const int N = ec->n_node;
+    const double fx0 = ec->frame[0], fy0 = ec->frame[2];
+    const double W = ec->frame[1] - fx0, H = ec->frame[3] - fy0;
+    const double invW = 1.0 / W, invH = 1.0 / H;
+    const double a_b2 = ec->alpha / (ec->beta * ec->beta), thr = ec->threshold, span = ec->capacity - ec->threshold;
+    const double inv_ab2 = 1.0 / a_b2, inv_span = 1.0 / span;
+    float* orow = out.node + (size_t)env * NR * WRSN_ENT_NODE_F;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int n = tid + 256 * k;
+        if (n >= NR) break;
+        // selects, not branches: nothing the loads above could be sunk into (a dead node's quotient is computed and dropped)
+        const bool in = n < N, live = in && (lsw[k] & 1);
+        const double de = en[k] - thr;
+        float f[8];
+        f[0] = in ? (float)((px[k] - fx0) * invW) : 0.f; f[1] = in ? (float)((py[k] - fy0) * invH) : 0.f;
+        f[2] = live ? (float)((cs[k] * span) / (a_b2 * de)) : 0.f;   // the weight as wrsn_obs_body forms it: one division
+        f[3] = live ? (float)(de * inv_span) : 0.f;
+        f[4] = live ? (float)(cs[k] * inv_ab2) : 0.f; f[5] = live ? (float)(rr[k] * inv_ab2) : 0.f;
+        f[6] = live ? (float)((lsw[k] >> 1) - 1) : 0.f; f[7] = live ? 1.f : 0.f;
+        wrsn_ent_store4(orow + (size_t)n * WRSN_ENT_NODE_F, f[0], f[1], f[2], f[3]);
+        wrsn_ent_store4(orow + (size_t)n * WRSN_ENT_NODE_F + 4, f[4], f[5], f[6], f[7]);
+    }
+    // ---- the chargers: thread o writes charger o; thread M the environment row
+    if (tid < M) {
+        const WrsnAgent WRSN_GLOBAL_AS* ag = wrsn_global((const WrsnAgent*)d.live.dyn[env].ag);
+        const int o = tid;
+        const double lx = ag[o].loc[0], ly = ag[o].loc[1], eo = ag[o].energy, c0 = ag[o].cur[0], c1 = ag[o].cur[1], c2 = ag[o].cur[2];
+        const double ay = ag[aid].cur[1];
+        const int st = ag[o].status, ch = ag[o].type_charging;
+        const double amp = o == aid ? 0.0 : (dist2(lx, ly, c0, ay) / ec->velocity) / ec->moving_time_max;   // mixed index as in WRSN.py:184
+        float* q = out.mc + ((size_t)env * M + o) * WRSN_ENT_MC_F;
+        wrsn_ent_store4(q, (float)((lx - fx0) * invW), (float)((ly - fy0) * invH), (float)(eo / ec->mc_capacity), o == aid ? 1.f : 0.f);
+        wrsn_ent_store4(q + 4, st != 0 ? 1.f : 0.f, ch != 0 ? 1.f : 0.f, (float)((c0 - fx0) * invW), (float)((c1 - fy0) * invH));
+        wrsn_ent_store4(q + 8, (float)(c2 / ec->charging_time_max), (float)amp, 0.f, 0.f);
+    } else if (tid == M) {
+        const double tmp = H < W ? H : W;
+        float* q = out.env + (size_t)env * WRSN_ENT_ENV_F;
+        wrsn_ent_store4(q, (float)(ec->charging_range * invW), (float)(ec->charging_range * invH), (float)(0.5 * tmp * invW), (float)(0.5 * tmp * invH));
+        wrsn_ent_store4(q + 4, (float)aid, (float)N, 0.f, 0.f);
+    }
 }

@@ -54,11 +54,15 @@ class VecWRSN:
     obs_dtype : "float32" (default) or "bfloat16" (also torch.float32 / torch.bfloat16): the dtype of `state` and of what `render_state`
                 returns, fixed for the life of the object (`wrsn_set_obs_format`).  A bfloat16 cell is the float32 cell rounded to nearest
                 even by the render kernel itself: half the bytes written per step and kept per stored observation.
+    entities  : True = the entity observation (`wrsn_set_entity_out`): every call that renders also writes, for the rows it renders, the
+                numbers `state` is a picture of -- `nodes` [B,N,8], `chargers` [B,M,12] and `env_feat` [B,8], float32, slots named by
+                `ENT_NODE` / `ENT_MC` / `ENT_ENV` -- and the returned dict holds them.  Legal with `render=False` (no image at all: the
+                observation for MLP, set and graph policies) and with every launch option.  Rows a call does not render keep their bytes.
     """
 
     def __init__(self, scenarios, agent_type=None, num_agent=3, map_size=100, warm_up_time=100, device="cuda:0",
                  auto_reset=False, render=True, max_degree=0, max_cover=0, step_budget=0, reuse_obs=False, step_deadline_us=0,
-                 obs_dtype="float32"):
+                 obs_dtype="float32", entities=False):
         import torch
         self.obs_dtype = obs_torch_dtype(obs_dtype)            # ValueError before anything is created
         if not torch.cuda.is_available():
@@ -106,6 +110,11 @@ class VecWRSN:
             self.state = torch.zeros((B, 4, G, G), dtype=self.obs_dtype, device=self.device) if self.render else None
             self._in_agent = torch.zeros(B, dtype=torch.int32, device=self.device)
             self._in_action = torch.zeros((B, 3), dtype=torch.float64, device=self.device)
+            self.entities = bool(entities)
+            self.nodes_feat = self.chargers_feat = self.env_feat = None
+            if self.entities:
+                self.nodes_feat, self.chargers_feat, self.env_feat = self._entity_tensors()
+                self._h.set_entity_out(self.nodes_feat.data_ptr(), self.chargers_feat.data_ptr(), self.env_feat.data_ptr())
             self._pool = None                                 # the records of set_pool, alive as long as the handle reads them
 
     def _sizes(self, scenarios):
@@ -119,8 +128,17 @@ class VecWRSN:
                     obs=(self.state.data_ptr() if self.state is not None else 0))
 
     def _result(self):
-        return {"agent_id": self.agent_id, "reward": self.reward, "terminal": self.terminal, "now": self.now,
-                "status": self.status, "state": self.state}
+        r = {"agent_id": self.agent_id, "reward": self.reward, "terminal": self.terminal, "now": self.now,
+             "status": self.status, "state": self.state}
+        if self.entities:
+            r.update(nodes=self.nodes_feat, chargers=self.chargers_feat, env_feat=self.env_feat)
+        return r
+
+    def _entity_tensors(self):
+        t = self.torch
+        return (t.zeros((self.num_env, self.n_node, _lib.ENT_NODE_F), dtype=t.float32, device=self.device),
+                t.zeros((self.num_env, self.num_agent, _lib.ENT_MC_F), dtype=t.float32, device=self.device),
+                t.zeros((self.num_env, _lib.ENT_ENV_F), dtype=t.float32, device=self.device))
 
     def _bind_stream(self):
         self._h.set_stream(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -178,6 +196,25 @@ class VecWRSN:
             raise ValueError("out must be a contiguous %s tensor [%d,4,%d,%d] on %s" %
                              (self.obs_dtype, self.num_env, self.map_size, self.map_size, self.device))
         self._h.render(a.data_ptr(), out.data_ptr())
+        return out
+
+    def entity_state(self, agent_ids, out=None):
+        """The entity observation of arbitrary agents (`wrsn_entities`; works with or without `entities=True`): a dict of `nodes`
+        [B,N,8], `chargers` [B,M,12] and `env_feat` [B,8]; rows with agent < 0 are left untouched.  `out`, when given, is such a dict of
+        contiguous float32 tensors on this device."""
+        t = self.torch
+        self._bind_stream()
+        a = agent_ids.to(device=self.device, dtype=t.int32).contiguous()
+        if out is None:
+            out = dict(zip(("nodes", "chargers", "env_feat"), self._entity_tensors()))
+        else:
+            want = {"nodes": (self.num_env, self.n_node, _lib.ENT_NODE_F), "chargers": (self.num_env, self.num_agent, _lib.ENT_MC_F),
+                    "env_feat": (self.num_env, _lib.ENT_ENV_F)}
+            for k, shape in want.items():
+                x = out[k]
+                if x.dtype != t.float32 or x.device != self.device or not x.is_contiguous() or tuple(x.shape) != shape:
+                    raise ValueError("out[%r] must be a contiguous float32 tensor %s on %s" % (k, list(shape), self.device))
+        self._h.entities(a.data_ptr(), out["nodes"].data_ptr(), out["chargers"].data_ptr(), out["env_feat"].data_ptr())
         return out
 
     def set_step_budget(self, work_units):
