@@ -163,7 +163,7 @@ class MinimizeRecorder:
         self.module.minimize = self.orig
 
 
-def run_case(name, s, mc, M, actions, max_steps, WRSN, map_size=100, warm_up=100, density_map=False):
+def run_case(name, s, mc, M, actions, max_steps, WRSN, map_size=100, warm_up=100, density_map=False, obs_full_decisions=OBS_FULL_DECISIONS):
     tf = tempfile.NamedTemporaryFile("w", suffix=".yaml", delete=False)
     yaml.safe_dump(s, tf); tf.close()
     tm = tempfile.NamedTemporaryFile("w", suffix=".yaml", delete=False)
@@ -213,7 +213,7 @@ def run_case(name, s, mc, M, actions, max_steps, WRSN, map_size=100, warm_up=100
         rec["terminal"].append(int(req["terminal"]))
         if req["state"] is not None:
             rec["obs_sample"].append(req["state"][:, ::OBS_STRIDE, ::OBS_STRIDE].copy())
-            if len(obs_full) < OBS_FULL_DECISIONS:
+            if len(obs_full) < obs_full_decisions:
                 obs_full.append(req["state"].copy())
         else:
             rec["obs_sample"].append(np.full((4, len(range(0, map_size, OBS_STRIDE)), len(range(0, map_size, OBS_STRIDE))), np.nan))
@@ -332,6 +332,21 @@ def main():
         ("redundant_m2_density_map64", red, mc, 2, map_policy(32, 64), 20, dict(density_map=True, map_size=64)),
     ]
     for name, sc_, mc_, M_, pol, n_, kw in dens:
+        if sel and not any(x in name for x in sel):
+            continue
+        run_case(name, sc_, mc_, M_, pol, n_, WRSN, **kw)
+    # ---- the d > d0 arm of the packet cost (Node.py:107,114-115: et + emp d^4 past d0 = sqrt(efs / emp) = 87.7 m; the shipped
+    # com_range of 80 m never reaches it) and the `|` chain of WRSN.py:307-311 with more than three live chargers
+    def com100(name):
+        s = dict(scen(name)); s["node_phy_spe"] = dict(s["node_phy_spe"], com_range=100.0)
+        return s
+    wide = [
+        ("hanoi1000n50_m3_com100", com100("hanoi1000n50"), mc, 3, rnd(41), 30, {}),
+        ("hanoi1000n100_m5_com100", com100("hanoi1000n100"), mc, 5, rnd(43), 30, {}),
+        # (35 decisions of strided samples: two full observations keep the file within 1 MiB)
+        ("hanoi1000n50_m8_s42", scen("hanoi1000n50"), mc, 8, rnd(42), 40, dict(obs_full_decisions=2)),
+    ]
+    for name, sc_, mc_, M_, pol, n_, kw in wide:
         if sel and not any(x in name for x in sel):
             continue
         run_case(name, sc_, mc_, M_, pol, n_, WRSN, **kw)

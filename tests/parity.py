@@ -97,6 +97,224 @@ def check_decision(z, k, got, where="", noise=None):
             assert np.max(np.abs(np.asarray(got["obs"], dtype=np.float64) - full)) <= 1e-5 * max(1.0, float(np.abs(full).max())), (tag, "obs full")
 
 
+class RequestCheck:
+    """One batch stepped side by side with one OracleWRSN per environment: the comparison of every fresh request, on plain
+    numpy values, so that the emulator (EmuSide) and the GPU (VecSide) feed the same code.  Per environment it keeps
+      * `tainted`: an alive node carried a rounding-residue energyCS at some decision of this episode -- the fitness of THAT instant may
+        have gone into agents_prev_fitness (WRSN.py:304) and comes back in the reward of a later decision, when the residue is gone;
+      * the device's own min_fitness at its last fresh return / reset, and the agent the call in flight gave an action to: WRSN.py:304
+        stores the fitness of exactly that state (no simulated time passes between a return and the next call), so at the fresh return
+        of that call prev_minfit[agent] must be the remembered number, bit for bit -- the device copies it (wrsn_sim.h: `prev_minfit =
+        last_minfit`), it does not compute it a second time -- in blocking, budgeted, pipelined and time-sliced launches alike.
+    `hatch=False`: a reward that differs fails, whatever the residues (tests whose seeds need no hatch)."""
+
+    def __init__(self, scs, hatch=True):
+        B = len(scs)
+        self.scs = scs; self.hatch = hatch
+        self.tainted = np.zeros(B, dtype=bool); self.minfit = np.full(B, np.nan); self.given = np.full(B, -1, dtype=np.int64)
+        self.n_cmp = self.n_noise = self.n_prov = self.n_flight = 0; self.worst_rew = self.worst_obs = 0.0
+        self._topo = {}
+
+    def remember(self, envs, view, reset=False):
+        """after a reset of `envs` (reset=True: a new episode) or a fresh return: the fitness the next action's prev_minfit must be"""
+        for e in envs:
+            self.minfit[e] = view["env_info"]["min_fitness"][e]; self.given[e] = -1
+            if reset: self.tainted[e] = False
+
+    def submit(self, e, agent):
+        """the call about to be made gives environment e (not in flight) an action for `agent` (None / -1: just run)"""
+        self.given[e] = -1 if agent is None else int(agent)
+
+    def _fitness_topology(self, e):
+        import fitness_ref
+        if e not in self._topo:
+            s = self.scs[e]
+            self._topo[e] = fitness_ref.Topology(s.node_xy, s.target_xy, s.bs_xy, float(s.node_spec["com_range"]), float(s.node_spec["sen_range"]))
+        return self._topo[e]
+
+    def fresh(self, step, e, x, oracle, view):
+        """environment e returned a request (status != 4): `x` is the oracle's return of the same WRSN.step, `view` the device's arrays
+        (see EmuSide.view).  Raises AssertionError on a mismatch; returns False when the reward hangs on a rounding residue (counted)."""
+        n = self.scs[e].n_node
+        ag, now, rew, term = view["agent_id"], view["now"], view["reward"], view["terminal"]
+        nd, gm, gi = view["nodes"], view["mcs"], view["env_info"]
+        self.n_cmp += 1
+        assert int(ag[e]) == (-1 if x["agent_id"] is None else x["agent_id"]), ("agent", step, e, int(ag[e]), x["agent_id"])
+        assert bool(term[e]) == x["terminal"] and close(float(now[e]), x["now"], rtol=1e-9), ("time/terminal", step, e, now[e], x["now"])
+        given = int(self.given[e])
+        if given >= 0:                                          # provenance of prev_minfit (WRSN.py:304), terminal return included
+            got_prev = gm["prev_minfit"][e][given]
+            assert got_prev == self.minfit[e] or (np.isnan(got_prev) and np.isnan(self.minfit[e])), \
+                ("prev_minfit is not the fitness reported when the action was given", step, e, given, got_prev, self.minfit[e])
+            self.n_prov += 1
+        self.remember([e], view)
+        if x["terminal"]:
+            return True
+        on = oracle.nodes(); om = oracle.mcs(); oi = oracle.env_info()
+        gst, gen, gcs = nd["status"][e][:n], nd["energy"][e][:n], nd["cs"][e][:n]
+        assert np.array_equal(gst, on["status"]), ("status", step, e)
+        assert np.array_equal(nd["level"][e][:n], on["level"]), ("level", step, e)
+        assert close(gen, on["energy"]), ("energy", step, e)
+        assert close(gcs, on["cs"], atol=1e-9), ("cs", step, e)
+        ocs = on["cs"]; alive_ = gst == 1
+        scale = max(np.abs(gcs).max(), 1e-30)
+        noisy = alive_ & (((np.abs(gcs) < 1e-9 * scale) & (gcs != 0)) | ((np.abs(ocs) < 1e-9 * scale) & (ocs != 0)))
+        self.tainted[e] |= bool(noisy.any())
+        # charger state: excl does not depend on the residue (a sum of energy differences), so neither check is excused in a tainted episode
+        assert close(gm["excl"][e], om["excl"], atol=1e-7), ("excl", step, e, gm["excl"][e], om["excl"])
+        assert close(gm["energy"][e], om["energy"], atol=1e-6), ("charger energy", step, e, gm["energy"][e], om["energy"])
+        if given >= 0 and not self.tainted[e]:
+            assert close(gm["prev_minfit"][e][given], om["prev_minfit"][given]), ("prev_minfit", step, e, given, gm["prev_minfit"][e][given], om["prev_minfit"][given])
+        if x["agent_id"] is None:
+            return True
+        a_ = x["agent_id"]
+        d = abs(float(rew[e]) - x["reward"]); self.worst_rew = max(self.worst_rew, d / max(1e-9, abs(x["reward"])) if abs(x["reward"]) > 1e-6 else 0.0)
+        # get_reward (WRSN.py:222-227) = (0.8 (fit - prev) + 0.2 excl / avg) / (ctm + mtm): the two terms can nearly cancel, so
+        # the 1e-5 is taken relative to their magnitudes, not to the (possibly tiny) difference
+        scale_ = (0.8 * abs(oi["min_fitness"] - om["prev_minfit"][a_]) + 0.2 * abs(om["excl"][a_]) / oi["avg_nodes_agent"]) / (oi["charging_time_max"] + oi["moving_time_max"])
+        if abs(float(rew[e]) - x["reward"]) > 1e-5 * max(abs(x["reward"]), scale_) + 1e-12:
+            # The reference divides by energyCS in get_network_fitness (WRSN.py:196-209).  Once a node has been idle for
+            # 10 s its energyCS is the rounding residue of the sliding mean (Node.py:71-77), +-1e-16 instead of 0, and
+            # (E - thr) / energyCS is +-1e19 with the sign of that residue: a negative one turns the node into a
+            # bottleneck.  The residue depends on the last bit of every packet cost (SciPy/BLAS distances included), so
+            # no two implementations -- or BLAS builds -- agree on it.  Such requests are counted, not failed.
+            if self.hatch and (noisy.any() or self.tainted[e]):
+                # the escape hatch is pinned: node state (status, energies) matched above, and the device's fitness / reward must be
+                # exactly what the reference's algorithm (tests/fitness_ref.py: WRSN.py:188-227) gives on the device's OWN node state
+                # -- with a prev_minfit whose provenance was checked above
+                import fitness_ref
+                fit = fitness_ref.network_fitness(self._fitness_topology(e), gen, gcs, gst, float(self.scs[e].node_spec["threshold"]))
+                assert close(gi["min_fitness"][e], fit.min(), rtol=1e-9), ("fitness on own state", step, e, gi["min_fitness"][e], fit.min())
+                want = fitness_ref.reward(fit.min(), gm["prev_minfit"][e][a_], gm["excl"][e][a_], gi["avg_nodes_agent"][e], gi["charging_time_max"][e], gi["moving_time_max"][e])
+                sc_ = (0.8 * abs(fit.min() - gm["prev_minfit"][e][a_]) + 0.2 * abs(gm["excl"][e][a_]) / gi["avg_nodes_agent"][e]) / (gi["charging_time_max"][e] + gi["moving_time_max"][e])
+                assert abs(float(rew[e]) - want) <= 1e-5 * max(abs(want), sc_) + 1e-12, ("reward on own state", step, e, float(rew[e]), want)
+                self.n_noise += 1
+                return False
+            print("REWARD MISMATCH step %s env %d agent %d: gpu %.12g oracle %.12g" % (step, e, int(ag[e]), rew[e], x["reward"]))
+            print("  gpu   excl %s prev_minfit %s min_fitness %.12g" % (gm["excl"][e], gm["prev_minfit"][e], gi["min_fitness"][e]))
+            print("  oracle excl %s prev_minfit %s min_fitness %.12g" % (om["excl"], om.get("prev_minfit"), oi["min_fitness"]))
+            raise AssertionError("reward mismatch (see output)")
+        ref = x["state"]
+        if ref is not None and view.get("obs") is not None:
+            o = view["obs"](e)
+            err = np.max(np.abs(o - ref)) / max(1.0, np.abs(ref).max()); self.worst_obs = max(self.worst_obs, err)
+            assert err <= 1e-5, ("obs", step, e, err)
+        return True
+
+
+class EmuSide:
+    """tests/emu's EmuVec behind the interface RequestCheck's callers drive (reset / step / view / topology)."""
+
+    def __init__(self, scs, mc, M, step_budget=0, step_deadline_us=0, **kw):
+        from emu_env import EmuVec
+        self.ev = EmuVec(scs, mc, M, **kw)
+        if step_budget: self.ev.h.set_step_budget(step_budget)
+        if step_deadline_us: self.ev.h.set_step_deadline(step_deadline_us)
+
+    def reset(self, mask=None):
+        ev = self.ev
+        if mask is None: ev.reset()
+        else:
+            m = np.ascontiguousarray(mask, dtype=np.uint8); ev.h.reset(m.ctypes.data, **ev._ptrs(True))
+
+    def step(self, ids, act):
+        self.ev.step(ids, act)
+
+    def view(self):
+        ev = self.ev
+        return {"status": ev.status.copy(), "agent_id": ev.agent_id.copy(), "now": ev.now.copy(), "reward": ev.reward.copy(), "terminal": ev.terminal.copy(),
+                "nodes": ev.nodes(), "mcs": ev.mcs(), "env_info": ev.env_info(), "obs": lambda e: ev.obs[e].astype(np.float64)}
+
+    def topology(self):
+        p = self.ev.h.peek
+        return {"degree": p(7), "n_cover": p(8), "direct": p(9)}
+
+    def close(self):
+        pass
+
+
+class VecSide:
+    """VecWRSN (the GPU) behind the same interface."""
+
+    def __init__(self, scs, mc, M, **kw):
+        import torch
+        from multi_agent_rl_wrsn_amd import VecWRSN
+        self.torch = torch
+        self.env = VecWRSN(scs, mc, M, **kw)
+
+    def reset(self, mask=None):
+        self.r = self.env.reset(None if mask is None else self.torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8))); self.env.synchronize()
+
+    def step(self, ids, act):
+        self.r = self.env.step(self.torch.tensor(np.asarray(ids)), self.torch.tensor(np.asarray(act, dtype=np.float64))); self.env.synchronize()
+
+    def view(self):
+        r, env = self.r, self.env
+        obs = r["state"]
+        return {"status": r["status"].cpu().numpy(), "agent_id": r["agent_id"].cpu().numpy(), "now": r["now"].cpu().numpy(), "reward": r["reward"].cpu().numpy(),
+                "terminal": r["terminal"].cpu().numpy(), "nodes": env.nodes(), "mcs": env.mcs(), "env_info": env.env_info(),
+                "obs": lambda e: obs[e].double().cpu().numpy()}
+
+    def topology(self):
+        return self.env.topology()
+
+    def close(self):
+        self.env.close()
+
+
+def run_requests(side, scs, mc, M, K, seed, third=1.0, check_topology=False, hatch=False):
+    """`side` (EmuSide / VecSide over `scs`) and one oracle per environment, K decisions per environment with the actions of
+    RandomState(seed) (one draw of [B, 3] per call; third component scaled by `third`: short charging times, chargers return often),
+    every fresh request through RequestCheck.  An environment that is finished or has had its K requests is left alone (-2).  Works for
+    blocking and budgeted handles (a row in flight keeps its action and is ignored by the call).  Returns the RequestCheck and the
+    number of compared requests at which some node was dead (non-terminal deaths)."""
+    from wrsn_oracle import OracleWRSN
+    B = len(scs)
+    ors = [OracleWRSN(s.node_xy, s.target_xy, s.bs_xy, s.node_spec, mc, s.max_time, M) for s in scs]
+    chk = RequestCheck(scs, hatch=hatch)
+    side.reset()
+    last = [o.reset() for o in ors]
+    v = side.view()
+    chk.remember(range(B), v, reset=True)
+    for e, o in enumerate(ors):
+        assert int(v["agent_id"][e]) == (-1 if last[e]["agent_id"] is None else last[e]["agent_id"]) and close(v["now"][e], last[e]["now"], rtol=1e-9), ("reset", e)
+        on = o.nodes()
+        assert np.array_equal(v["nodes"]["level"][e][:o.N], on["level"]) and close(v["nodes"]["energy"][e][:o.N], on["energy"]), ("reset state", e)
+    if check_topology:
+        tp = side.topology()
+        for e, o in enumerate(ors):
+            t = o.topology()
+            assert np.array_equal(tp["degree"][e, :o.N], t["degree"]), ("degree", e)
+            assert np.array_equal(tp["n_cover"][e, :o.N], t["n_cover"]) and np.array_equal(tp["direct"][e, :o.N], t["direct"]), ("cover/direct", e)
+    rng = np.random.RandomState(seed)
+    done = np.zeros(B, dtype=bool); busy = np.zeros(B, dtype=bool); pending = [None] * B
+    deaths_seen = 0; n_fresh = np.zeros(B, dtype=int)
+    for step in range(4000 * K):
+        act = rng.rand(B, 3) * np.array([1.0, 1.0, third])
+        ids = np.full(B, -1, dtype=np.int64)
+        for e in range(B):
+            if done[e]: ids[e] = -2
+            elif not busy[e]:
+                a = last[e]["agent_id"]
+                ids[e] = -1 if a is None else a
+                pending[e] = (a, act[e].copy()); chk.submit(e, a)
+        side.step(ids, act)
+        v = side.view()
+        for e in range(B):
+            if done[e]: continue
+            busy[e] = v["status"][e] == 4
+            if busy[e]:
+                chk.n_flight += 1
+                continue
+            last[e] = ors[e].step(*pending[e])
+            chk.fresh(step, e, last[e], ors[e], v); n_fresh[e] += 1
+            if last[e]["terminal"] or n_fresh[e] >= K: done[e] = True
+            if not last[e]["terminal"]: deaths_seen += int((ors[e].nodes()["status"] == 0).any())
+        if done.all(): break
+    assert done.all(), "a step stayed in flight for 4000 calls"
+    return chk, deaths_seen
+
+
 def check_density_action(z, k, act, nodes, where=""):
     """Fixture with `density_map=True` (the reference ran WRSN.step on G x G policy maps, WRSN.py:293-297, 229-287):
     `act` is what the implementation derived from map k on the node state `nodes` (energy / cs / status of the decision

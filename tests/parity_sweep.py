@@ -4,29 +4,31 @@ tests run; intended for spare GPU time after a change to the exact-second / sche
 import sys, os, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle")); sys.path.insert(0, os.path.join(ROOT, "tests"))
-import numpy as np, torch
+import numpy as np
 from concurrent.futures import ThreadPoolExecutor
-from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, VecWRSN, synth_scenario
+from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, synth_scenario
 from wrsn_oracle import OracleWRSN
-from parity import close
+from parity import RequestCheck, VecSide
 
 
-def run(B=192, K=60, budget=0, seed0=20000, N=200, verbose=True, M=None, deadline_us=None):
-    """returns (requests compared, finished episodes, noise-dependent requests); raises AssertionError on a mismatch"""
+def run(B=192, K=60, budget=0, seed0=20000, N=200, verbose=True, M=None, deadline_us=None, sizes=None, node_spec=None, side=None):
+    """returns (requests compared, finished episodes, noise-dependent requests); raises AssertionError on a mismatch.
+    sizes: list of (n_node, n_target) cycled over the environments (a ragged batch in one handle; None: N nodes and N targets everywhere);
+    node_spec: the node parameters of every network (None: the shipped ones); side: parity.VecSide (the GPU, default) or parity.EmuSide."""
     M = int(os.environ.get("WRSN_M", "3")) if M is None else M
     deadline_us = int(os.environ.get("WRSN_DEADLINE_US", "0")) if deadline_us is None else deadline_us
-    scs = [synth_scenario(seed0 + e, N, N) for e in range(B)]
-    env = VecWRSN(scs, None, M, step_budget=budget, step_deadline_us=deadline_us)
+    sizes = [(N, N)] if sizes is None else list(sizes)
+    scs = [synth_scenario(seed0 + e, sizes[e % len(sizes)][0], sizes[e % len(sizes)][1], node_spec=node_spec) for e in range(B)]
+    env = (VecSide if side is None else side)(scs, DEFAULT_MC_SPEC, M, step_budget=budget, step_deadline_us=deadline_us)
     ors = [OracleWRSN(s.node_xy, s.target_xy, s.bs_xy, s.node_spec, DEFAULT_MC_SPEC, s.max_time, M) for s in scs]
-    r = env.reset(); env.synchronize()
+    chk = RequestCheck(scs)
+    env.reset()
     last = [o.reset() for o in ors]
+    chk.remember(range(B), env.view(), reset=True)
     rng = np.random.RandomState(seed0)
     pool = ThreadPoolExecutor(max_workers=min(64, os.cpu_count() or 8))
-    n_cmp = 0; n_term = 0; n_noise = 0; worst_rew = 0.0; worst_obs = 0.0; t0 = time.time()
-    busy = np.zeros(B, dtype=bool); pending = [None] * B; resets = np.zeros(B, dtype=int); topo_cache = {}
-    # an episode in which an alive node carried a rounding-residue energyCS at some decision: the fitness of THAT instant may have gone into
-    # agents_prev_fitness (WRSN.py:304) and comes back in the reward of a later decision, when the residue itself is gone
-    tainted = np.zeros(B, dtype=bool)
+    n_term = 0; t0 = time.time()
+    busy = np.zeros(B, dtype=bool); pending = [None] * B
     for step in range(K):
         act = rng.rand(B, 3)
         ids = np.full(B, -1, dtype=np.int64)
@@ -36,72 +38,30 @@ def run(B=192, K=60, budget=0, seed0=20000, N=200, verbose=True, M=None, deadlin
                 last[e] = None
         mask = np.array([last[e] is None and not busy[e] for e in range(B)], dtype=np.uint8)
         if mask.any():                                          # reset finished episodes on both sides
-            r = env.reset(torch.from_numpy(mask)); env.synchronize()
+            env.reset(mask)
             for e in np.nonzero(mask)[0]:
-                last[e] = ors[e].reset(); n_term += 1; resets[e] += 1; tainted[e] = False
+                last[e] = ors[e].reset(); n_term += 1
+            chk.remember(np.nonzero(mask)[0], env.view(), reset=True)
         for e in range(B):
             if not busy[e]:
                 ids[e] = -1 if last[e]["agent_id"] is None else last[e]["agent_id"]
-                pending[e] = (last[e]["agent_id"], act[e].copy())
-        r = env.step(torch.tensor(ids), torch.tensor(act)); env.synchronize()
-        st = r["status"].cpu().numpy()
+                pending[e] = (last[e]["agent_id"], act[e].copy()); chk.submit(e, last[e]["agent_id"])
+        env.step(ids, act)
+        v = env.view(); st = v["status"]
         fresh = [e for e in range(B) if st[e] != 4]
         def ostep(e):
             a, x = pending[e]
             return ors[e].step(a, x)
         res = list(pool.map(ostep, fresh))
-        nd = env.nodes(); ag = r["agent_id"].cpu().numpy(); now = r["now"].cpu().numpy(); rew = r["reward"].cpu().numpy(); term = r["terminal"].cpu().numpy()
-        obs = r["state"]
         for e, x in zip(fresh, res):
-            last[e] = x; n_cmp += 1
-            assert int(ag[e]) == (-1 if x["agent_id"] is None else x["agent_id"]), ("agent", step, e, int(ag[e]), x["agent_id"])
-            assert bool(term[e]) == x["terminal"] and close(float(now[e]), x["now"], rtol=1e-9), ("time/terminal", step, e, now[e], x["now"])
-            if x["terminal"]: continue
-            on = ors[e].nodes()
-            assert np.array_equal(nd["status"][e], on["status"]), ("status", step, e)
-            assert close(nd["energy"][e], on["energy"]), ("energy", step, e)
-            gcs = nd["cs"][e]; ocs = on["cs"]; alive_ = nd["status"][e] == 1
-            scale = max(np.abs(gcs).max(), 1e-30)
-            noisy = alive_ & (((np.abs(gcs) < 1e-9 * scale) & (gcs != 0)) | ((np.abs(ocs) < 1e-9 * scale) & (ocs != 0)))
-            tainted[e] |= bool(noisy.any())
-            if x["agent_id"] is not None:
-                d = abs(float(rew[e]) - x["reward"]); worst_rew = max(worst_rew, d / max(1e-9, abs(x["reward"])) if abs(x["reward"]) > 1e-6 else 0.0)
-                # get_reward (WRSN.py:222-227) = (0.8 (fit - prev) + 0.2 excl / avg) / (ctm + mtm): the two terms can nearly cancel, so
-                # the 1e-5 is taken relative to their magnitudes, not to the (possibly tiny) difference
-                om_ = ors[e].mcs(); oi_ = ors[e].env_info(); a_ = x["agent_id"]
-                scale_ = (0.8 * abs(oi_["min_fitness"] - om_["prev_minfit"][a_]) + 0.2 * abs(om_["excl"][a_]) / oi_["avg_nodes_agent"]) / (oi_["charging_time_max"] + oi_["moving_time_max"])
-                if abs(float(rew[e]) - x["reward"]) > 1e-5 * max(abs(x["reward"]), scale_) + 1e-12:
-                    # The reference divides by energyCS in get_network_fitness (WRSN.py:196-209).  Once a node has been idle for
-                    # 10 s its energyCS is the rounding residue of the sliding mean (Node.py:71-77), +-1e-16 instead of 0, and
-                    # (E - thr) / energyCS is +-1e19 with the sign of that residue: a negative one turns the node into a
-                    # bottleneck.  The residue depends on the last bit of every packet cost (SciPy/BLAS distances included), so
-                    # no two implementations -- or BLAS builds -- agree on it.  Such requests are counted, not failed.
-                    if noisy.any() or tainted[e]:
-                        # the escape hatch is pinned: node state (status, energies) matched above, and the GPU's fitness / reward must be
-                        # exactly what the reference's algorithm (tests/fitness_ref.py: WRSN.py:188-227) gives on the GPU's OWN node state
-                        import fitness_ref
-                        if e not in topo_cache:
-                            topo_cache[e] = fitness_ref.Topology(scs[e].node_xy, scs[e].target_xy, scs[e].bs_xy, float(scs[e].node_spec["com_range"]), float(scs[e].node_spec["sen_range"]))
-                        gm = env.mcs(); gi = env.env_info(); a_ = x["agent_id"]
-                        fit = fitness_ref.network_fitness(topo_cache[e], nd["energy"][e][:scs[e].n_node], nd["cs"][e][:scs[e].n_node], nd["status"][e][:scs[e].n_node], float(scs[e].node_spec["threshold"]))
-                        assert close(gi["min_fitness"][e], fit.min(), rtol=1e-9), ("fitness on own state", step, e, gi["min_fitness"][e], fit.min())
-                        want = fitness_ref.reward(fit.min(), gm["prev_minfit"][e][a_], gm["excl"][e][a_], gi["avg_nodes_agent"][e], gi["charging_time_max"][e], gi["moving_time_max"][e])
-                        sc_ = (0.8 * abs(fit.min() - gm["prev_minfit"][e][a_]) + 0.2 * abs(gm["excl"][e][a_]) / gi["avg_nodes_agent"][e]) / (gi["charging_time_max"][e] + gi["moving_time_max"][e])
-                        assert abs(float(rew[e]) - want) <= 1e-5 * max(abs(want), sc_) + 1e-12, ("reward on own state", step, e, float(rew[e]), want)
-                        n_noise += 1
-                        continue
-                    gm = env.mcs(); om = ors[e].mcs(); gi = env.env_info(); oi = ors[e].env_info()
-                    print("REWARD MISMATCH step %d env %d agent %d: gpu %.12g oracle %.12g" % (step, e, int(ag[e]), rew[e], x["reward"]))
-                    print("  gpu   excl %s prev_minfit %s min_fitness %.12g" % (gm["excl"][e], gm["prev_minfit"][e], gi["min_fitness"][e]))
-                    print("  oracle excl %s prev_minfit %s min_fitness %.12g" % (om["excl"], om.get("prev_minfit"), oi["min_fitness"]))
-                    raise AssertionError("reward mismatch (see output)")
-                ref = x["state"]; o = obs[e].double().cpu().numpy()
-                err = np.max(np.abs(o - ref)) / max(1.0, np.abs(ref).max()); worst_obs = max(worst_obs, err)
-                assert err <= 1e-5, ("obs", step, e, err)
+            last[e] = x
+            chk.fresh(step, e, x, ors[e], v)
         busy = st == 4
         if verbose and step % 10 == 9:
-            print("step %d: %d requests compared (%d noise-dependent), %d episodes finished, worst reward rel err %.2e, worst obs err %.2e, %.0f s" % (step + 1, n_cmp, n_noise, n_term, worst_rew, worst_obs, time.time() - t0), flush=True)
+            print("step %d: %d requests compared (%d noise-dependent), %d episodes finished, worst reward rel err %.2e, worst obs err %.2e, %.0f s" % (step + 1, chk.n_cmp, chk.n_noise, n_term, chk.worst_rew, chk.worst_obs, time.time() - t0), flush=True)
+    n_cmp, n_noise = chk.n_cmp, chk.n_noise
     print("parity sweep ok: %d requests, %d finished episodes; %d requests with a reward that depends on the sign of a rounding-noise energyCS (not comparable)" % (n_cmp, n_term, n_noise))
+    print("prev_minfit traced back to the fitness reported with the request: %d actions" % chk.n_prov)
     env.close(); pool.shutdown()
     assert n_noise <= max(2, n_cmp // 200), "more than 0.5 %% of the requests hang on a rounding-residue energyCS: %d of %d" % (n_noise, n_cmp)
     return n_cmp, n_term, n_noise
