@@ -344,6 +344,37 @@ class RawHandle:
         check(self.lib, self.lib.wrsn_peek(self._h, int(what), a.ctypes.data))
         return a
 
+    # -- host views of wrsn_peek: one dict per family, keyed by field name (copies; the caller synchronises first)
+    def nodes(self):
+        return {"energy": self.peek(PEEK_NODE_ENERGY), "cs": self.peek(PEEK_NODE_CS), "rr": self.peek(PEEK_NODE_RR),
+                "status": self.peek(PEEK_NODE_STATUS), "level": self.peek(PEEK_NODE_LEVEL)}
+
+    def topology(self):
+        return {"degree": self.peek(PEEK_NODE_DEGREE), "n_cover": self.peek(PEEK_NODE_NCOVER), "direct": self.peek(PEEK_NODE_DIRECT)}
+
+    def targets_active(self):
+        """Network.targets_active (Network.py:9, 45-55) per environment: int32 [B, T]."""
+        return self.peek(PEEK_TARGETS_ACTIVE)
+
+    def mcs(self):
+        a = self.peek(PEEK_MC)
+        return {k: a[:, :, i].copy() for i, k in enumerate(MC_FIELDS) if not k.startswith("_")}
+
+    def env_info(self):
+        a = self.peek(PEEK_ENV)
+        return {k: a[:, i].copy() for i, k in enumerate(ENV_FIELDS)}
+
+    def rng_state(self):
+        """The MT19937 generators of a stochastic handle: (words uint32 [B, 625] as in random.getstate()[1], draws since reset int64 [B])."""
+        import numpy as np
+        a = self.peek(PEEK_RNG_STATE)
+        return a[:, :625].copy(), a[:, 625].astype(np.int64) | (a[:, 626].astype(np.int64) << 32)
+
+    def pool_info(self):
+        """Per environment: the pool record it runs (-1: its own scenario or a loaded record) and its swaps since wrsn_pool_set."""
+        a = self.peek(PEEK_POOL)
+        return {"record": a[:, 0].copy(), "swaps": a[:, 1].copy()}
+
     # -- environment records (wrsn_save_envs / wrsn_load_envs / wrsn_clone_envs); index arrays are host int32 arrays
     def env_record_bytes(self):
         n = C.c_int64(0)

@@ -323,33 +323,27 @@ class VecWRSN:
 
     def pool_info(self):
         """Per environment: the pool record it runs (-1: its own scenario or a loaded record) and its swaps since `set_pool` (host copies)."""
-        a = self._h.peek(_lib.PEEK_POOL)
-        return {"record": a[:, 0].copy(), "swaps": a[:, 1].copy()}
+        return self._h.pool_info()
 
     def synchronize(self):
         self._h.sync()
 
     # -- read-only views for tests / logging (host copies) --------------------------------------------------
     def nodes(self):
-        p = self._h.peek
-        return {"energy": p(_lib.PEEK_NODE_ENERGY), "cs": p(_lib.PEEK_NODE_CS), "rr": p(_lib.PEEK_NODE_RR),
-                "status": p(_lib.PEEK_NODE_STATUS), "level": p(_lib.PEEK_NODE_LEVEL)}
+        return self._h.nodes()
 
     def topology(self):
-        p = self._h.peek
-        return {"degree": p(_lib.PEEK_NODE_DEGREE), "n_cover": p(_lib.PEEK_NODE_NCOVER), "direct": p(_lib.PEEK_NODE_DIRECT)}
+        return self._h.topology()
 
     def targets_active(self):
         """Network.targets_active (Network.py:9, 45-55) per environment: int32 [B, T]."""
-        return self._h.peek(_lib.PEEK_TARGETS_ACTIVE)
+        return self._h.targets_active()
 
     def mcs(self):
-        a = self._h.peek(_lib.PEEK_MC)
-        return {k: a[:, :, i].copy() for i, k in enumerate(_lib.MC_FIELDS) if not k.startswith("_")}
+        return self._h.mcs()
 
     def env_info(self):
-        a = self._h.peek(_lib.PEEK_ENV)
-        return {k: a[:, i].copy() for i, k in enumerate(_lib.ENV_FIELDS)}
+        return self._h.env_info()
 
     def counters(self):
         return self._h.counters()

@@ -1,4 +1,4 @@
-"""Shared helpers of the entity-observation tests (tests/test_entities.py on the emulator, tests/test_entities_gpu.py on the device).
+"""Shared helpers of the entity-observation tests (tests/test_entities.py, on the emulator and on the device).
 
 The reference for the values is the float64 formula sheet of include/wrsn_hip.h (wrsn_entity_out), evaluated in numpy from wrsn_peek,
 the scenario's positions and the specs.  Tolerance, derived: a value is a float64 expression rounded once to float32, and the device may
@@ -16,40 +16,38 @@ ENV_EXACT = (4, 5, 6, 7)
 
 def peeks(h):
     """What the reference formulas read, for the whole batch of RawHandle h."""
-    from multi_agent_rl_wrsn_amd import _lib
-    return {"energy": h.peek(_lib.PEEK_NODE_ENERGY), "cs": h.peek(_lib.PEEK_NODE_CS), "rr": h.peek(_lib.PEEK_NODE_RR),
-            "status": h.peek(_lib.PEEK_NODE_STATUS), "level": h.peek(_lib.PEEK_NODE_LEVEL), "mc": h.peek(_lib.PEEK_MC),
-            "env": h.peek(_lib.PEEK_ENV)}
+    return {"nodes": h.nodes(), "mcs": h.mcs(), "env": h.env_info()}
 
 
 def reference(pk, e, a, sc, mc, N, M):
     """float64 rows (node [N,8], charger [M,12], environment [8]) of environment e for the asking charger a."""
-    env = pk["env"][e]
-    xmin, xmax, ymin, ymax, mtm, ctm = env[0], env[1], env[2], env[3], env[5], env[6]
-    W, H = xmax - xmin, ymax - ymin
+    env = {k: v[e] for k, v in pk["env"].items()}
+    xmin, ymin, mtm, ctm = env["xmin"], env["ymin"], env["moving_time_max"], env["charging_time_max"]
+    W, H = env["xmax"] - xmin, env["ymax"] - ymin
     a_b2 = mc["alpha"] / mc["beta"] ** 2
     thr, cap = float(sc.node_spec["threshold"]), float(sc.node_spec["capacity"])
     n = sc.n_node
+    nd = {k: v[e, :n] for k, v in pk["nodes"].items()}
     node = np.zeros((N, 8))
     node[:n, 0] = (sc.node_xy[:, 0] - xmin) / W
     node[:n, 1] = (sc.node_xy[:, 1] - ymin) / H
-    alive = pk["status"][e, :n] != 0
-    E, CS, RR = pk["energy"][e, :n], pk["cs"][e, :n], pk["rr"][e, :n]
+    alive = nd["status"] != 0
+    E, CS, RR = nd["energy"], nd["cs"], nd["rr"]
     with np.errstate(divide="ignore", invalid="ignore"):
         ef = (E - thr) / (cap - thr)
         node[:n, 2] = np.where(alive, (CS / a_b2) / ef, 0.0)
     node[:n, 3] = np.where(alive, ef, 0.0)
     node[:n, 4] = np.where(alive, CS / a_b2, 0.0)
     node[:n, 5] = np.where(alive, RR / a_b2, 0.0)
-    node[:n, 6] = np.where(alive, pk["level"][e, :n], 0)
+    node[:n, 6] = np.where(alive, nd["level"], 0)
     node[:n, 7] = alive
-    m = pk["mc"][e]
+    m = {k: v[e] for k, v in pk["mcs"].items()}
     ch = np.zeros((M, 12))
     for o in range(M):
-        lx, ly, energy, status, charging, c0, c1, c2 = m[o, :8]
-        move = 0.0 if o == a else np.sqrt((lx - c0) ** 2 + (ly - m[a, 6]) ** 2) / mc["velocity"] / mtm   # WRSN.py:184, mixed index
-        ch[o] = [(lx - xmin) / W, (ly - ymin) / H, energy / mc["capacity"], float(o == a), float(status != 0), float(charging != 0),
-                 (c0 - xmin) / W, (c1 - ymin) / H, c2 / ctm, move, 0.0, 0.0]
+        lx, ly, c0, c1 = m["loc_x"][o], m["loc_y"][o], m["cur_x"][o], m["cur_y"][o]
+        move = 0.0 if o == a else np.sqrt((lx - c0) ** 2 + (ly - m["cur_y"][a]) ** 2) / mc["velocity"] / mtm   # WRSN.py:184, mixed index
+        ch[o] = [(lx - xmin) / W, (ly - ymin) / H, m["energy"][o] / mc["capacity"], float(o == a), float(m["status"][o] != 0),
+                 float(m["type_charging"][o] != 0), (c0 - xmin) / W, (c1 - ymin) / H, m["cur_t"][o] / ctm, move, 0.0, 0.0]
     t = min(W, H)
     envr = np.array([mc["charging_range"] / W, mc["charging_range"] / H, 0.5 * t / W, 0.5 * t / H, float(a), float(n), 0.0, 0.0])
     return node, ch, envr

@@ -99,7 +99,7 @@ def check_decision(z, k, got, where="", noise=None):
 
 class RequestCheck:
     """One batch stepped side by side with one OracleWRSN per environment: the comparison of every fresh request, on plain
-    numpy values, so that the emulator (EmuSide) and the GPU (VecSide) feed the same code.  Per environment it keeps
+    numpy values, so that the emulator and the GPU (sides.EmuSide / sides.VecSide) feed the same code.  Per environment it keeps
       * `tainted`: an alive node carried a rounding-residue energyCS at some decision of this episode -- the fitness of THAT instant may
         have gone into agents_prev_fitness (WRSN.py:304) and comes back in the reward of a later decision, when the residue is gone;
       * the device's own min_fitness at its last fresh return / reset, and the agent the call in flight gave an action to: WRSN.py:304
@@ -134,7 +134,7 @@ class RequestCheck:
 
     def fresh(self, step, e, x, oracle, view):
         """environment e returned a request (status != 4): `x` is the oracle's return of the same WRSN.step, `view` the device's arrays
-        (see EmuSide.view).  Raises AssertionError on a mismatch; returns False when the reward hangs on a rounding residue (counted)."""
+        (a side's view()).  Raises AssertionError on a mismatch; returns False when the reward hangs on a rounding residue (counted)."""
         n = self.scs[e].n_node
         ag, now, rew, term = view["agent_id"], view["now"], view["reward"], view["terminal"]
         nd, gm, gi = view["nodes"], view["mcs"], view["env_info"]
@@ -202,68 +202,8 @@ class RequestCheck:
         return True
 
 
-class EmuSide:
-    """tests/emu's EmuVec behind the interface RequestCheck's callers drive (reset / step / view / topology)."""
-
-    def __init__(self, scs, mc, M, step_budget=0, step_deadline_us=0, **kw):
-        from emu_env import EmuVec
-        self.ev = EmuVec(scs, mc, M, **kw)
-        if step_budget: self.ev.h.set_step_budget(step_budget)
-        if step_deadline_us: self.ev.h.set_step_deadline(step_deadline_us)
-
-    def reset(self, mask=None):
-        ev = self.ev
-        if mask is None: ev.reset()
-        else:
-            m = np.ascontiguousarray(mask, dtype=np.uint8); ev.h.reset(m.ctypes.data, **ev._ptrs(True))
-
-    def step(self, ids, act):
-        self.ev.step(ids, act)
-
-    def view(self):
-        ev = self.ev
-        return {"status": ev.status.copy(), "agent_id": ev.agent_id.copy(), "now": ev.now.copy(), "reward": ev.reward.copy(), "terminal": ev.terminal.copy(),
-                "nodes": ev.nodes(), "mcs": ev.mcs(), "env_info": ev.env_info(), "obs": lambda e: ev.obs[e].astype(np.float64)}
-
-    def topology(self):
-        p = self.ev.h.peek
-        return {"degree": p(7), "n_cover": p(8), "direct": p(9)}
-
-    def close(self):
-        pass
-
-
-class VecSide:
-    """VecWRSN (the GPU) behind the same interface."""
-
-    def __init__(self, scs, mc, M, **kw):
-        import torch
-        from multi_agent_rl_wrsn_amd import VecWRSN
-        self.torch = torch
-        self.env = VecWRSN(scs, mc, M, **kw)
-
-    def reset(self, mask=None):
-        self.r = self.env.reset(None if mask is None else self.torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8))); self.env.synchronize()
-
-    def step(self, ids, act):
-        self.r = self.env.step(self.torch.tensor(np.asarray(ids)), self.torch.tensor(np.asarray(act, dtype=np.float64))); self.env.synchronize()
-
-    def view(self):
-        r, env = self.r, self.env
-        obs = r["state"]
-        return {"status": r["status"].cpu().numpy(), "agent_id": r["agent_id"].cpu().numpy(), "now": r["now"].cpu().numpy(), "reward": r["reward"].cpu().numpy(),
-                "terminal": r["terminal"].cpu().numpy(), "nodes": env.nodes(), "mcs": env.mcs(), "env_info": env.env_info(),
-                "obs": lambda e: obs[e].double().cpu().numpy()}
-
-    def topology(self):
-        return self.env.topology()
-
-    def close(self):
-        self.env.close()
-
-
 def run_requests(side, scs, mc, M, K, seed, third=1.0, check_topology=False, hatch=False):
-    """`side` (EmuSide / VecSide over `scs`) and one oracle per environment, K decisions per environment with the actions of
+    """`side` (a sides.EmuSide / sides.VecSide over `scs`) and one oracle per environment, K decisions per environment with the actions of
     RandomState(seed) (one draw of [B, 3] per call; third component scaled by `third`: short charging times, chargers return often),
     every fresh request through RequestCheck.  An environment that is finished or has had its K requests is left alone (-2).  Works for
     blocking and budgeted handles (a row in flight keeps its action and is ignored by the call).  Returns the RequestCheck and the
@@ -281,7 +221,7 @@ def run_requests(side, scs, mc, M, K, seed, third=1.0, check_topology=False, hat
         on = o.nodes()
         assert np.array_equal(v["nodes"]["level"][e][:o.N], on["level"]) and close(v["nodes"]["energy"][e][:o.N], on["energy"]), ("reset state", e)
     if check_topology:
-        tp = side.topology()
+        tp = side.handle.topology()
         for e, o in enumerate(ors):
             t = o.topology()
             assert np.array_equal(tp["degree"][e, :o.N], t["degree"]), ("degree", e)
@@ -341,3 +281,43 @@ def check_density_action(z, k, act, nodes, where=""):
     mine = density_ref.objective(np.clip(spot, [lx, ly], [ux, uy]), *args)
     assert mine >= ref_best * (1 - 1e-7) - 1e-12, (tag, "objective", mine, ref_best)
     return mine, ref_best
+
+
+def replay_reference_fixture(Side, name):
+    """The reference run tests/golden/<name>.npz on `Side` (sides.EmuSide / sides.VecSide): the frame and the constants of the network, the
+    reset state, every decision through check_decision, and -- for a density_map=True run -- the action derived from the policy map of
+    each decision."""
+    from sides import load_fixture
+    z, sc, mc = load_fixture(name)
+    side = Side([sc], mc, int(z["num_agent"]), map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]))
+    info = side.handle.env_info()
+    assert close([info["xmin"][0], info["xmax"][0], info["ymin"][0], info["ymax"][0]], z["frame"], rtol=1e-14)
+    assert close([info["moving_time_max"][0], info["charging_time_max"][0], info["avg_nodes_agent"][0], info["nodes_density"][0]], z["consts"], rtol=1e-12)
+    side.reset()
+    noise = []
+    agent, _, reward, _, _ = side.rows()[0]
+    assert agent == int(z["reset_agent"]) and reward == 0.0
+    nd = side.handle.nodes()
+    assert close(nd["energy"][0], z["reset_node_energy"]) and close(nd["cs"][0], z["reset_node_cs"], atol=1e-9)
+    assert np.array_equal(nd["status"][0], z["reset_node_status"]) and np.array_equal(nd["level"][0], z["reset_node_level"])
+    assert np.max(np.abs(side.obs_row(0) - z["reset_obs"])) <= 1e-5 * max(1.0, np.abs(z["reset_obs"]).max())
+    for k in range(len(z["in_action"])):
+        if "in_map" in z.files:                              # density_map=True fixture: the policy map of this decision
+            nd = side.handle.nodes()
+            act = side.density_action([int(z["in_agent"][k])], z["in_map"][k].astype(np.float64)[None])
+            check_density_action(z, k, act[0], {"energy": nd["energy"][0], "cs": nd["cs"][0], "status": nd["status"][0]}, where=name)
+        side.step([int(z["in_agent"][k])], z["in_action"][k][None])   # the reference's own 3-vector: the physics follow the fixture
+        agent, _, reward, _, status = side.rows()[0]
+        if z["is_none"][k]:
+            assert status == 1 and agent == -1
+            break
+        assert status == 0
+        if np.isinf(z["reward"][k]):
+            assert reward == float(z["reward"][k])
+            continue
+        check_decision(z, k, side.decision(), where=name, noise=noise)
+        if z["terminal"][k]:
+            break
+    print("%s on %s: %d of %d decisions replayed, %d rewards hang on a residue" % (name, Side.name, k + 1, len(z["in_action"]), len(noise)))
+    assert len(noise) <= max(1, len(z["in_action"]) // 8), noise     # rewards that hang on the sign of a rounding residue stay rare
+    side.close()

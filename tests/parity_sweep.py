@@ -8,13 +8,14 @@ import numpy as np
 from concurrent.futures import ThreadPoolExecutor
 from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, synth_scenario
 from wrsn_oracle import OracleWRSN
-from parity import RequestCheck, VecSide
+from parity import RequestCheck
+from sides import VecSide
 
 
 def run(B=192, K=60, budget=0, seed0=20000, N=200, verbose=True, M=None, deadline_us=None, sizes=None, node_spec=None, side=None):
     """returns (requests compared, finished episodes, noise-dependent requests); raises AssertionError on a mismatch.
     sizes: list of (n_node, n_target) cycled over the environments (a ragged batch in one handle; None: N nodes and N targets everywhere);
-    node_spec: the node parameters of every network (None: the shipped ones); side: parity.VecSide (the GPU, default) or parity.EmuSide."""
+    node_spec: the node parameters of every network (None: the shipped ones); side: sides.VecSide (the GPU, default) or sides.EmuSide."""
     M = int(os.environ.get("WRSN_M", "3")) if M is None else M
     deadline_us = int(os.environ.get("WRSN_DEADLINE_US", "0")) if deadline_us is None else deadline_us
     sizes = [(N, N)] if sizes is None else list(sizes)

@@ -5,65 +5,17 @@ cache rebuild, reward softmax, widest-path fitness, observation) against the gol
 import numpy as np
 import pytest
 
-from conftest import golden_names, load_golden, oracle_from_golden
-from parity import check_decision, check_density_action, close
+from conftest import golden_names, load_golden
+from parity import check_decision, close, replay_reference_fixture
+from sides import EmuSide
+
 
 FAST = [n for n in golden_names() if "n150" not in n and "n200" not in n]
 
 
-def _emu(scenarios, mc, M, **kw):
-    from emu_env import EmuVec
-    return EmuVec(scenarios, mc, M, **kw)
-
-
-def _got(ev, e=0, with_nodes=True):
-    g = {"agent_id": int(ev.agent_id[e]), "now": float(ev.now[e]), "reward": float(ev.reward[e]), "terminal": bool(ev.terminal[e]),
-         "obs": ev.obs[e].astype(np.float64)}
-    if with_nodes:
-        nd = ev.nodes(); m = ev.mcs()
-        g.update(node_energy=nd["energy"][e], node_cs=nd["cs"][e], node_status=nd["status"][e],
-                 mc_energy=m["energy"][e], mc_loc=np.stack([m["loc_x"][e], m["loc_y"][e]], 1), mc_status=m["status"][e],
-                 mc_charging=m["type_charging"][e], mc_nconn=m["n_conn"][e], excl=m["excl"][e],
-                 prev_minfit=m["prev_minfit"][e], min_fitness=float(ev.env_info()["min_fitness"][e]),
-                 targets_active=ev.targets_active()[e])
-    return g
-
-
 @pytest.mark.parametrize("name", FAST)
 def test_emulated_kernel_matches_reference_fixture(name):
-    z = load_golden(name)
-    from multi_agent_rl_wrsn_amd.scenario import scenario_from_golden
-    sc, mc = scenario_from_golden(z)
-    ev = _emu([sc], mc, int(z["num_agent"]), map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]))
-    info = ev.env_info()
-    assert close([info["xmin"][0], info["xmax"][0], info["ymin"][0], info["ymax"][0]], z["frame"], rtol=1e-14)
-    assert close([info["moving_time_max"][0], info["charging_time_max"][0], info["avg_nodes_agent"][0], info["nodes_density"][0]], z["consts"], rtol=1e-12)
-    ev.reset()
-    noise = []
-    assert int(ev.agent_id[0]) == int(z["reset_agent"]) and float(ev.reward[0]) == 0.0
-    nd = ev.nodes()
-    assert close(nd["energy"][0], z["reset_node_energy"]) and close(nd["cs"][0], z["reset_node_cs"], atol=1e-9)
-    assert np.array_equal(nd["status"][0], z["reset_node_status"]) and np.array_equal(nd["level"][0], z["reset_node_level"])
-    assert np.max(np.abs(ev.obs[0] - z["reset_obs"])) <= 1e-5 * max(1.0, np.abs(z["reset_obs"]).max())
-    gains = []
-    for k in range(len(z["in_action"])):
-        if "in_map" in z.files:                              # density_map=True fixture: the policy map of this decision
-            nd = ev.nodes(); out = np.zeros((1, 3))
-            ids = np.array([int(z["in_agent"][k])], dtype=np.int32); dm = np.ascontiguousarray(z["in_map"][k].astype(np.float64)[None])
-            ev.h.density_action(ids.ctypes.data, dm.ctypes.data, out.ctypes.data)
-            gains.append(check_density_action(z, k, out[0], {"energy": nd["energy"][0], "cs": nd["cs"][0], "status": nd["status"][0]}, where=name))
-        ev.step([int(z["in_agent"][k])], z["in_action"][k][None])   # the reference's own 3-vector: the physics follow the fixture
-        if z["is_none"][k]:
-            assert int(ev.status[0]) == 1 and int(ev.agent_id[0]) == -1
-            break
-        assert int(ev.status[0]) == 0
-        if np.isinf(z["reward"][k]):
-            assert float(ev.reward[0]) == float(z["reward"][k])
-            continue
-        check_decision(z, k, _got(ev), where=name, noise=noise)
-        if z["terminal"][k]:
-            break
-    assert len(noise) <= max(1, len(z["in_action"]) // 8), noise     # rewards that hang on the sign of a rounding residue stay rare
+    replay_reference_fixture(EmuSide, name)
 
 
 def test_emulated_batch_of_different_networks_matches_oracle(hip_lib):
@@ -73,15 +25,15 @@ def test_emulated_batch_of_different_networks_matches_oracle(hip_lib):
     from wrsn_oracle import OracleWRSN
     scs = [synth_scenario(7, 90, 60), synth_scenario(8, 130, 100), synth_scenario(9, 64, 64)]
     M = 3
-    ev = _emu(scs, DEFAULT_MC_SPEC, M)
+    ev = EmuSide(scs, DEFAULT_MC_SPEC, M)
     ors = [OracleWRSN(s.node_xy, s.target_xy, s.bs_xy, s.node_spec, DEFAULT_MC_SPEC, s.max_time, M) for s in scs]
     ev.reset()
     last = [o.reset() for o in ors]
-    topo_deg = ev.h.peek(7)
+    topo = ev.h.topology()
     for e, o in enumerate(ors):
         t = o.topology()
-        assert np.array_equal(topo_deg[e, :o.N], t["degree"])
-        assert np.array_equal(ev.h.peek(8)[e, :o.N], t["n_cover"]) and np.array_equal(ev.h.peek(9)[e, :o.N], t["direct"])
+        assert np.array_equal(topo["degree"][e, :o.N], t["degree"])
+        assert np.array_equal(topo["n_cover"][e, :o.N], t["n_cover"]) and np.array_equal(topo["direct"][e, :o.N], t["direct"])
     rng = np.random.RandomState(5)
     done = [False] * len(scs)
     deaths_seen = 0
@@ -116,7 +68,7 @@ def test_emulated_batch_of_different_networks_matches_oracle(hip_lib):
 def test_emulated_auto_reset_and_untouched_rows(hip_lib):
     from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, synth_scenario
     sc = synth_scenario(21, 70, 50)
-    ev = _emu([sc, sc], DEFAULT_MC_SPEC, 2)
+    ev = EmuSide([sc, sc], DEFAULT_MC_SPEC, 2)
     ev.reset()
     e0 = ev.nodes()["energy"].copy()
     rng = np.random.RandomState(3)
@@ -142,7 +94,7 @@ def test_emulated_step_budget_returns_the_same_requests(name):
     z = load_golden(name)
     from multi_agent_rl_wrsn_amd.scenario import scenario_from_golden
     sc, mc = scenario_from_golden(z)
-    ev = _emu([sc], mc, int(z["num_agent"]), map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]))
+    ev = EmuSide([sc], mc, int(z["num_agent"]), map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]))
     ev.h.set_step_budget(25)
     ev.reset()
     n_susp = 0
@@ -160,7 +112,7 @@ def test_emulated_step_budget_returns_the_same_requests(name):
         assert int(ev.status[0]) == 0
         if np.isinf(z["reward"][k]):
             continue
-        check_decision(z, k, _got(ev), where=name + " (budget)", noise=[])
+        check_decision(z, k, ev.decision(), where=name + " (budget)", noise=[])
         if z["terminal"][k]:
             break
     assert n_susp > 0
@@ -177,7 +129,7 @@ def test_emulated_step_budget_equals_blocking_on_a_200_node_network_with_guarded
     sc = [synth_scenario(500 + e, 200, 200)]
 
     def run(budget):
-        ev = _emu(sc, DEFAULT_MC_SPEC, 3)
+        ev = EmuSide(sc, DEFAULT_MC_SPEC, 3)
         if budget:
             ev.h.set_step_budget(budget)
         ev.reset(with_obs=False)
@@ -214,7 +166,7 @@ def test_emulated_step_deadline_argument_and_same_requests():
     z = load_golden("hanoi1000n50_m3_s1")
     from multi_agent_rl_wrsn_amd.scenario import scenario_from_golden
     sc, mc = scenario_from_golden(z)
-    ev = _emu([sc], mc, int(z["num_agent"]), map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]))
+    ev = EmuSide([sc], mc, int(z["num_agent"]), map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]))
     with pytest.raises(_lib.WrsnError):
         ev.h.set_step_deadline(-1)
     ev.h.set_step_budget(100000)
@@ -231,7 +183,7 @@ def test_emulated_step_deadline_argument_and_same_requests():
         if z["is_none"][k]:
             break
         if not np.isinf(z["reward"][k]):
-            check_decision(z, k, _got(ev), where="deadline", noise=[])
+            check_decision(z, k, ev.decision(), where="deadline", noise=[])
         if z["terminal"][k]:
             break
     assert n_susp > 0
@@ -243,7 +195,7 @@ def test_emulated_rollout_table_matches_host_accumulation():
     from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, synth_scenario
     scs = [synth_scenario(40 + e, 70, 60) for e in range(3)]
     M = 2
-    ev = _emu(scs, DEFAULT_MC_SPEC, M)
+    ev = EmuSide(scs, DEFAULT_MC_SPEC, M)
     ev.reset()
     want = np.zeros((3, M + 3))
     rng = np.random.RandomState(2)
@@ -281,7 +233,7 @@ def test_emulated_density_map_to_action(G):
     import density_ref
     from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, synth_scenario
     sc = synth_scenario(11, 120, 100)
-    ev = _emu([sc] * 5, DEFAULT_MC_SPEC, 2, map_size=G)
+    ev = EmuSide([sc] * 5, DEFAULT_MC_SPEC, 2, map_size=G)
     ev.reset(with_obs=False)
     rng = np.random.RandomState(3)
     for k in range(3):                                       # some dynamics first: energies / consumption rates differ per node
@@ -317,13 +269,13 @@ def test_emulated_step_budget_untouched_and_reset_rows():
     scs = [synth_scenario(60 + e, 80, 70) for e in range(4)]
     act = np.array([[0.3, 0.6, 0.9], [0.7, 0.2, 0.8], [0.5, 0.5, 0.7], [0.2, 0.8, 0.95]])
 
-    ref = _emu(scs, DEFAULT_MC_SPEC, 2)                      # blocking run: what every finished step must return
+    ref = EmuSide(scs, DEFAULT_MC_SPEC, 2)                      # blocking run: what every finished step must return
     ref.reset(with_obs=False)
     ids0 = ref.agent_id.copy()
     ref.step(ids0, act, with_obs=False)
     want = (ref.agent_id.copy(), ref.now.copy(), ref.reward.copy())
 
-    ev = _emu(scs, DEFAULT_MC_SPEC, 2)
+    ev = EmuSide(scs, DEFAULT_MC_SPEC, 2)
     ev.h.set_step_budget(40)
     ev.reset(with_obs=False)
     ev.step(ids0, act, with_obs=False)
@@ -369,7 +321,7 @@ def test_emulated_step_budget_handles_every_environment_once_per_launch(order):
     acts = rng.rand(K, B, 3)
 
     def run(budget):
-        ev = _emu(scs, DEFAULT_MC_SPEC, M)
+        ev = EmuSide(scs, DEFAULT_MC_SPEC, M)
         if budget: ev.h.set_step_budget(budget)
         ev.reset(with_obs=False)
         tab = np.zeros((B, M + 3)); want = np.zeros((B, M + 3)); hist = [[] for _ in range(B)]
@@ -420,7 +372,7 @@ def test_emulated_untouched_and_unmasked_rows_keep_their_request():
     included -- so `r = reset(mask); step(r.agent_id, a)` is safe for the environments that were not reset."""
     from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, synth_scenario
     scs = [synth_scenario(90 + e, 70, 60) for e in range(3)]
-    ev = _emu(scs, DEFAULT_MC_SPEC, 2)
+    ev = EmuSide(scs, DEFAULT_MC_SPEC, 2)
     ev.reset()
     rng = np.random.RandomState(1)
     for _ in range(3):
@@ -447,7 +399,7 @@ def test_emulated_observation_at_other_map_sizes(G):
     from wrsn_oracle import OracleWRSN
     sc = synth_scenario(33, 90, 70)
     M = 3
-    ev = _emu([sc], DEFAULT_MC_SPEC, M, map_size=G)
+    ev = EmuSide([sc], DEFAULT_MC_SPEC, M, map_size=G)
     o = OracleWRSN(sc.node_xy, sc.target_xy, sc.bs_xy, sc.node_spec, DEFAULT_MC_SPEC, sc.max_time, M, map_size=G)
     ev.reset(); r = o.reset()
     assert np.max(np.abs(ev.obs[0] - r["state"])) <= 1e-5 * max(1.0, np.abs(r["state"]).max())
@@ -468,7 +420,7 @@ def test_emulated_launch_order_with_many_environments():
     B, M = 520, 2
     uniq = [synth_scenario(600 + u, 24, 16) for u in range(8)]
     scs = [uniq[e % 8] for e in range(B)]
-    ev = _emu(scs, DEFAULT_MC_SPEC, M, map_size=8)
+    ev = EmuSide(scs, DEFAULT_MC_SPEC, M, map_size=8)
     ev.h.set_step_budget(50)
     ev.reset(with_obs=False)
     rng = np.random.RandomState(12)
@@ -506,7 +458,7 @@ def test_emulated_observation_reuse_is_bit_identical():
     from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, synth_scenario
     scs = [synth_scenario(50 + e, 70, 60) for e in range(3)]
     M, G = 3, 20
-    a = _emu(scs, DEFAULT_MC_SPEC, M, map_size=G); b = _emu(scs, DEFAULT_MC_SPEC, M, map_size=G)
+    a = EmuSide(scs, DEFAULT_MC_SPEC, M, map_size=G); b = EmuSide(scs, DEFAULT_MC_SPEC, M, map_size=G)
     b.h.set_obs_reuse(False)
     a.reset(); b.reset()
     assert np.array_equal(a.obs, b.obs)
@@ -541,7 +493,7 @@ def test_emulated_work_queue_launches_return_the_same_requests():
         return np.random.RandomState(1000 * e + n).rand(3)
 
     def run(deadline_us, calls, pause):
-        ev = _emu(scs, DEFAULT_MC_SPEC, M, map_size=G)
+        ev = EmuSide(scs, DEFAULT_MC_SPEC, M, map_size=G)
         if deadline_us:
             ev.h.set_step_deadline(deadline_us)
         ev.reset()
@@ -577,7 +529,7 @@ def test_emulated_work_queue_launches_return_the_same_requests():
             for a, b in zip(full[e][:n], q[e][:n]):
                 assert a[:3] == b[:3] and a[4] == b[4] and abs(a[3] - b[3]) <= 1e-7 * max(1.0, abs(a[3])), (e, a, b)   # a suspension splits a closed form / re-bases the float32 priorities: ~1e-9
     # a masked reset drops a latched action: the environment answers the reset, then takes the NEXT action it is given
-    ev = _emu(scs, DEFAULT_MC_SPEC, M, map_size=G)
+    ev = EmuSide(scs, DEFAULT_MC_SPEC, M, map_size=G)
     ev.h.set_step_deadline(1)
     ev.reset()
     ev.step(ev.agent_id.copy(), np.full((B, 3), 0.9), auto_reset=True)
@@ -587,7 +539,7 @@ def test_emulated_work_queue_launches_return_the_same_requests():
     mask = np.zeros(B, dtype=np.uint8); mask[e] = 1
     ev.h.reset(mask.ctypes.data, **ev._ptrs(True))
     assert ev.agent_id[e] == 0 and ev.now[e] == 100.0
-    ref = _emu([scs[e]], DEFAULT_MC_SPEC, M, map_size=G); ref.reset(); ref.step([0], np.array([[0.2, 0.3, 0.1]]))
+    ref = EmuSide([scs[e]], DEFAULT_MC_SPEC, M, map_size=G); ref.reset(); ref.step([0], np.array([[0.2, 0.3, 0.1]]))
     ids = np.full(B, -2, dtype=np.int32); ids[e] = 0
     act = np.zeros((B, 3)); act[e] = [0.2, 0.3, 0.1]
     for it in range(3000):

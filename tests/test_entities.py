@@ -1,7 +1,8 @@
-"""Entity observations (wrsn_set_entity_out / wrsn_entities) on the CPU: the unmodified HIP sources in the lockstep wavefront emulator
-of tests/emu.  The rows are held to the float64 formula sheet of the header evaluated from wrsn_peek (one float32 ulp), the formulas
-to the reference's own get_state images of tests/golden (splatted back into four maps), every path that renders to the standalone
-call (bit for bit), and the extent of what a call writes to a byte pattern with guards."""
+"""Entity observations (wrsn_set_entity_out / wrsn_entities), one body each, run here on the emulator (the unmodified HIP sources in
+the lockstep wavefront emulator of tests/emu) and by tests/test_entities_gpu.py on the device.  The rows are held to the float64 formula sheet of the header
+evaluated from wrsn_peek (one float32 ulp), the formulas to the reference's own get_state images of tests/golden (splatted back into
+four maps), every path that renders to the standalone call (bit for bit: the rendered rows, and the whole buffers with their guards),
+and the extent of what a call writes to a byte pattern with guards.  CPU only: the header, the refusals and the splat.  Helpers and tolerances: tests/entity_ref.py."""
 import ctypes as C
 import os
 import re
@@ -9,8 +10,9 @@ import re
 import numpy as np
 import pytest
 
-from conftest import ROOT, load_golden
-from entity_ref import EntBuf, check_extent, check_rows, peeks, reference, splat
+from conftest import ROOT
+from entity_ref import check_extent, check_rows, peeks, reference, splat
+from sides import EmuSide, load_fixture
 
 FIXTURES = ("six_m3_zero_length",                 # 6 nodes: far fewer nodes than threads
             "hanoi1000n50_m3_s1",
@@ -18,77 +20,79 @@ FIXTURES = ("six_m3_zero_length",                 # 6 nodes: far fewer nodes tha
             "hanoi1000n50_m3_cap1500_mcdeath",    # a dead charger
             "redundant_m2_deaths",                # nodes die while the episode goes on
             "synth300_m3_s27")                    # more nodes than a 256-thread block
+# What differs between the sides is size: the emulator draws 8 x 8 images and drives a fixed number of calls; the device draws 16 x 16
+# (100 x 100 where no image is asked for) and drives until every kind of row occurred, at least 9 calls.
+BATCH_G = {"emu": 8, "gpu": 16}
+NO_IMAGE_G = {"emu": 8, "gpu": 100}
+DRIVE = {"blocking": {"emu": (12, 12), "gpu": (40, 9)}, "budget 40": {"emu": (24, 24), "gpu": (60, 9)},
+         "time slices": {"emu": (24, 24), "gpu": (300, 9)}}     # side -> (most calls, least calls)
+# the emulator clones with the image (its per-call switch; VecWRSN renders what its constructor says)
+CLONE_KW = {"emu": dict(with_obs=True), "gpu": {}}
 
 
-def _emu(scenarios, mc, M, **kw):
-    from emu_env import EmuVec
-    return EmuVec(scenarios, mc, M, **kw)
-
-
-def _register(ev):
-    buf = EntBuf(ev.B, ev.N, ev.M)
-    ev.h.set_entity_out(*buf.ptrs())
+def _registered(side):
+    buf = side.entity_buffers()
+    side.set_entity_out(buf)
     return buf
 
 
-def _standalone(ev, agents):
-    """Rows of wrsn_entities for `agents` in buffers of their own."""
-    buf = EntBuf(ev.B, ev.N, ev.M)
-    a = np.ascontiguousarray(agents, dtype=np.int32)
-    ev.h.entities(a.ctypes.data, *buf.ptrs())
-    return buf, buf.snap()
+def _agents(side):
+    return np.array([r[0] for r in side.rows()], dtype=np.int32)
 
 
-def _check_call(ev, buf, rendered, tag):
-    """After a call that rendered exactly the rows `rendered`: extent, untouched rows, and bit-equality with the standalone call."""
+def _check_call(side, buf, rendered, tag):
+    """After a call that rendered exactly the rows `rendered`: extent, untouched rows, and bit-equality with the standalone call -- of
+    the rendered rows and of the whole buffers, guards included."""
     snap = buf.snap()
     check_extent(buf, snap, rendered, tag)
-    agents = np.array([int(ev.agent_id[e]) if e in rendered else -1 for e in range(ev.B)], dtype=np.int32)
-    sbuf, ssnap = _standalone(ev, agents)
+    agents = np.where([e in rendered for e in range(side.B)], _agents(side), -1)
+    sbuf = side.entity_buffers()
+    side.entities(agents, sbuf)
+    ssnap = sbuf.snap()
     check_extent(sbuf, ssnap, rendered, tag + " (standalone)")
     for e in rendered:
         assert np.array_equal(buf.row_bytes(snap, e), sbuf.row_bytes(ssnap, e)), (tag, "row %d differs from wrsn_entities" % e)
+    for k in snap:
+        assert np.array_equal(snap[k], ssnap[k]), (tag, k, "buffers differ from wrsn_entities")
     return snap
 
 
 _REPLAY = {}
 
 
-def _replay(name):
-    """The fixture's scripted actions through an entity-only handle (out->obs NULL).  Per request with agent_id >= 0 (the reset's
-    included): the decision index (-1: reset), the rows the call wrote and the float64 reference rows.  Computed once per fixture."""
-    if name in _REPLAY:
-        return _REPLAY[name]
-    from multi_agent_rl_wrsn_amd.scenario import scenario_from_golden
-    z = load_golden(name)
-    sc, mc = scenario_from_golden(z)
+def _replay(Side, name):
+    """The fixture's scripted actions through an entity-only handle (no image).  Per request with agent_id >= 0 (the reset's included):
+    the decision index (-1: reset), the rows the call wrote and the float64 reference rows.  Computed once per side and fixture."""
+    if (Side.name, name) in _REPLAY:
+        return _REPLAY[Side.name, name]
+    z, sc, mc = load_fixture(name)
     M = int(z["num_agent"])
-    ev = _emu([sc], mc, M, map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]))
-    buf = _register(ev)
+    side = Side([sc], mc, M, map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]), render=False)
+    buf = _registered(side)
     out = []
 
     def record(k):
-        a = int(ev.agent_id[0])
-        snap = _check_call(ev, buf, {0}, "%s decision %d" % (name, k))
+        a, _, _, terminal, _ = side.rows()[0]
+        snap = _check_call(side, buf, {0}, "%s decision %d" % (name, k))
         out.append({"k": k, "agent": a, "got": tuple(x.copy() for x in buf.rows(snap, 0)),
-                    "ref": reference(peeks(ev.h), 0, a, sc, mc, ev.N, M), "terminal": bool(ev.terminal[0])})
+                    "ref": reference(peeks(side.handle), 0, a, sc, mc, side.N, M), "terminal": bool(terminal)})
 
-    ev.reset(with_obs=False)
+    side.reset()
     record(-1)
     for k in range(len(z["in_action"])):
         buf.fill()
-        ev.step([int(z["in_agent"][k])], z["in_action"][k][None], with_obs=False)
-        if z["is_none"][k] or int(ev.agent_id[0]) < 0:
+        side.step([int(z["in_agent"][k])], z["in_action"][k][None])
+        if z["is_none"][k] or side.rows()[0][0] < 0:
             check_extent(buf, buf.snap(), set(), "%s decision %d renders nothing" % (name, k))
             break
         record(k)
-    _REPLAY[name] = (z, sc, out)
-    return _REPLAY[name]
+    side.close()
+    _REPLAY[Side.name, name] = (z, sc, out)
+    return _REPLAY[Side.name, name]
 
 
-@pytest.mark.parametrize("name", FIXTURES)
-def test_values_on_fixtures(name):
-    z, sc, recs = _replay(name)
+def values_on_fixtures(Side, name):
+    z, sc, recs = _replay(Side, name)
     assert len(recs) >= 2
     for r in recs:
         check_rows(r["got"], r["ref"], sc.n_node, "%s decision %d" % (name, r["k"]))
@@ -103,7 +107,7 @@ def test_values_on_fixtures(name):
 def test_features_are_what_get_state_draws(name):
     """The float64 feature values of the formula sheet, splatted with the reference's func and the bandwidths of the environment row,
     are the reference's observation: reset_obs, obs_full[k] and the strided obs_sample[k] at 1e-5 of the map's peak."""
-    z, sc, recs = _replay(name)
+    z, sc, recs = _replay(EmuSide, name)
     G, s = int(z["map_size"]), int(z["obs_stride"])
     full = 0
     for r in recs:
@@ -122,162 +126,208 @@ def test_features_are_what_get_state_draws(name):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-def _batch(map_size=8):
-    """Five small networks, two chargers; the nodes of environment 2 hold little energy: its episodes end within a few steps (terminal rows)."""
+def _batch():
+    """Five small networks for two chargers; the nodes of environment 2 hold little energy: its episodes end within a few steps
+    (terminal rows)."""
     from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, DEFAULT_NODE_SPEC, synth_scenario
     weak = dict(DEFAULT_NODE_SPEC, capacity=1200.0)          # little above the threshold: the first node dies within a few steps
     scs = [synth_scenario(31 + e, 40, 30, node_spec=(weak if e == 2 else None)) for e in range(5)]
-    return scs, DEFAULT_MC_SPEC, _emu(scs, DEFAULT_MC_SPEC, 2, map_size=map_size)
+    return scs, DEFAULT_MC_SPEC
 
 
-def _drive(ev, buf, calls, with_obs, seen, tag):
-    """`calls` step calls with auto-reset; row 1 is left alone (-2) in every other call.  Every call is checked."""
+def _time_sliced_batch(side_name):
+    """(networks, chargers, launch keywords): the emulator slices the small batch after 100 readings of its stand-in clock, the device
+    eight 200-node networks after 50 us."""
+    from multi_agent_rl_wrsn_amd import synth_scenario
+    if side_name == "emu":
+        return _batch()[0], 2, dict(step_budget=100000, step_deadline_us=1)
+    return [synth_scenario(500 + e, 200, 200) for e in range(8)], 3, dict(step_deadline_us=50)
+
+
+def _batch_side(Side, render=False, **kw):
+    scs, mc = _batch()
+    return scs, mc, Side(scs, mc, 2, map_size=(BATCH_G if render else NO_IMAGE_G)[Side.name], render=render, **kw)
+
+
+def _rendered(rows, touched):
+    return {e for e in touched if rows[e][4] != 4 and not rows[e][3] and rows[e][0] >= 0}
+
+
+def _drive(side, buf, need, tag):
+    """Step calls with auto-reset until every kind of row in `need` occurred (DRIVE: most and least calls); row 1 is left alone (-2) in
+    every other call.  Every call is checked."""
+    calls, least = DRIVE[tag][side.name]
     rng = np.random.RandomState(11)
+    seen = set()
     for c in range(calls):
-        ids = ev.agent_id.copy()
-        ids[ev.status == 4] = -1
+        before = side.rows()
+        ids = np.array([-1 if r[4] == 4 else r[0] for r in before], dtype=np.int32)
         skip = c % 2 == 1
         if skip:
             ids[1] = -2
-        before = ev.agent_id.copy()
         buf.fill()
-        ev.step(ids, rng.rand(ev.B, 3), with_obs=with_obs, auto_reset=True)
-        rendered = set()
-        for e in range(ev.B):
-            if skip and e == 1:
-                assert int(ev.agent_id[e]) == int(before[e])
-                seen.add("-2")
-            elif int(ev.status[e]) == 4:
+        side.step(ids, rng.rand(side.B, 3))
+        rows = side.rows()
+        touched = [e for e in range(side.B) if not (skip and e == 1)]
+        if skip:
+            assert rows[1][0] == before[1][0]
+            seen.add("-2")
+        for e in touched:
+            if rows[e][4] == 4:
                 seen.add("status 4")
-            elif ev.terminal[e]:
+            elif rows[e][3]:
                 seen.add("terminal")
-            elif int(ev.agent_id[e]) >= 0:
-                rendered.add(e); seen.add("rendered")
-        _check_call(ev, buf, rendered, "%s call %d" % (tag, c))
+        rendered = _rendered(rows, touched)
+        if rendered:
+            seen.add("rendered")
+        _check_call(side, buf, rendered, "%s call %d" % (tag, c))
+        if need <= seen and c + 1 >= least:
+            break
+    assert need <= seen, (tag, seen)
 
 
-def test_blocking_steps_and_a_masked_reset_write_the_rendered_rows_only(hip_lib):
-    scs, mc, ev = _batch()
-    buf = _register(ev)
-    mask = np.array([1, 0, 1, 1, 0], dtype=np.uint8)
-    ev.h.reset(mask.ctypes.data, **ev._ptrs(True))
-    _check_call(ev, buf, {0, 2, 3}, "masked reset")
+def blocking_steps_and_a_masked_reset(Side):
+    scs, mc, side = _batch_side(Side, render=True, auto_reset=True)
+    buf = _registered(side)
+    side.reset([1, 0, 1, 1, 0])
+    _check_call(side, buf, {0, 2, 3}, "masked reset")
     buf.fill()
-    ev.reset()
-    snap = _check_call(ev, buf, set(range(5)), "reset")
-    pk = peeks(ev.h)
+    side.reset()
+    snap = _check_call(side, buf, set(range(5)), "reset")
+    pk = peeks(side.handle); agents = _agents(side)
     for e in range(5):
-        check_rows(buf.rows(snap, e), reference(pk, e, int(ev.agent_id[e]), scs[e], mc, ev.N, 2), scs[e].n_node, "reset row %d" % e)
-    seen = set()
-    _drive(ev, buf, 12, True, seen, "blocking")
-    assert {"-2", "terminal", "rendered"} <= seen, seen
+        check_rows(buf.rows(snap, e), reference(pk, e, int(agents[e]), scs[e], mc, side.N, 2), scs[e].n_node, "reset row %d" % e)
+    _drive(side, buf, {"-2", "terminal", "rendered"}, "blocking")
+    side.close()
 
 
-def test_step_budget_leaves_rows_in_flight_untouched(hip_lib):
-    scs, mc, ev = _batch()
-    buf = _register(ev)
-    ev.h.set_step_budget(40)
-    ev.reset(with_obs=False)
-    seen = set()
-    _drive(ev, buf, 24, False, seen, "budget 40")
-    assert {"-2", "status 4", "rendered"} <= seen, seen
+def step_budget(Side):
+    scs, mc, side = _batch_side(Side, auto_reset=True, step_budget=40)
+    buf = _registered(side)
+    side.reset()
+    _drive(side, buf, {"-2", "status 4", "rendered"}, "budget 40")
+    side.close()
 
 
-def test_time_sliced_launches_write_the_rendered_rows_only(hip_lib):
-    scs, mc, ev = _batch()
-    buf = _register(ev)
-    ev.h.set_step_budget(100000)
-    ev.h.set_step_deadline(1)                                 # 100 readings of the emulator's stand-in clock
-    ev.reset(with_obs=False)
-    seen = set()
-    _drive(ev, buf, 24, False, seen, "time slices")
-    assert {"-2", "status 4", "rendered"} <= seen, seen
+def time_sliced_launches(Side):
+    scs, M, kw = _time_sliced_batch(Side.name)
+    from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC
+    side = Side(scs, DEFAULT_MC_SPEC, M, map_size=NO_IMAGE_G[Side.name], render=False, auto_reset=True, **kw)
+    buf = _registered(side)
+    side.reset()
+    _drive(side, buf, {"-2", "status 4", "rendered"}, "time slices")
+    side.close()
 
 
-def test_load_clone_and_pool_reset_write_the_replaced_rows_only(hip_lib):
-    from test_scenario_pool import _aligned
-    scs, mc, ev = _batch()
-    buf = _register(ev)
-    ev.reset(with_obs=False)
+def load_clone_and_pool_reset(Side):
+    scs, mc, side = _batch_side(Side)
+    buf = _registered(side)
+    side.reset()
     rng = np.random.RandomState(4)
     for _ in range(3):
-        ev.step(np.where(ev.agent_id >= 0, ev.agent_id, -2).astype(np.int32), rng.rand(5, 3), with_obs=False)   # a finished row is left alone
-    assert (ev.agent_id[[0, 3]] >= 0).all()
-    rec = _aligned((2, ev.h.env_record_bytes()))
-    p = ev._ptrs(False); p.pop("obs")
-    ev.h.save_envs(np.array([0, 3], dtype=np.int32), rec.ctypes.data, **p)
+        a = _agents(side)
+        side.step(np.where(a >= 0, a, -2), rng.rand(5, 3))   # a finished row is left alone
+    assert (_agents(side)[[0, 3]] >= 0).all()
+    rec = side.save_envs([0, 3])
     # load: records of environments 0 and 3 into 1 and 4
     buf.fill()
-    ev.h.load_envs(np.array([1, 4], dtype=np.int32), rec.ctypes.data, **ev._ptrs(False))
-    snap = _check_call(ev, buf, {1, 4}, "load")
-    pk = peeks(ev.h)
+    side.load_envs(rec, [1, 4])
+    snap = _check_call(side, buf, {1, 4}, "load")
+    pk = peeks(side.handle); agents = _agents(side)
     for dst, src in ((1, 0), (4, 3)):
-        check_rows(buf.rows(snap, dst), reference(pk, dst, int(ev.agent_id[dst]), scs[src], mc, ev.N, 2), scs[src].n_node, "loaded row %d" % dst)
-    # clone: 0 -> 2 (with the image this time)
+        check_rows(buf.rows(snap, dst), reference(pk, dst, int(agents[dst]), scs[src], mc, side.N, 2), scs[src].n_node, "loaded row %d" % dst)
+    # clone: 0 -> 2
     buf.fill()
-    ev.h.clone_envs([0], [2], **ev._ptrs(True))
-    _check_call(ev, buf, {2}, "clone")
+    side.clone_envs([0], [2], **CLONE_KW[Side.name])
+    _check_call(side, buf, {2}, "clone")
     # pool reset: rows 1 and 3 by mask, records chosen by the caller
-    ev.h.pool_set(rec.ctypes.data, 2, 5)
-    mask = np.array([0, 1, 0, 1, 0], dtype=np.uint8); index = np.array([9, 1, 9, 0, 9], dtype=np.int32)
+    side.set_pool(rec, 5)
     buf.fill()
-    ev.h.pool_reset(mask.ctypes.data, index.ctypes.data, 0, **ev._ptrs(False))
-    _check_call(ev, buf, {1, 3}, "pool reset")
+    side.pool_reset([0, 1, 0, 1, 0], [9, 1, 9, 0, 9])
+    _check_call(side, buf, {1, 3}, "pool reset")
+    side.close()
 
 
-def test_ragged_batch_values_and_zero_rows():
+def ragged_batch_values_and_zero_rows(Side):
     """six_* (6 nodes) and hanoi1000n50 (82 nodes) in one handle: rows beyond each n_node are written as zeros."""
-    from multi_agent_rl_wrsn_amd.scenario import scenario_from_golden
-    six, _ = scenario_from_golden(load_golden("six_m3_zero_length"))
-    hanoi, mc = scenario_from_golden(load_golden("hanoi1000n50_m3_s1"))
+    _, six, _ = load_fixture("six_m3_zero_length")
+    _, hanoi, mc = load_fixture("hanoi1000n50_m3_s1")
     scs = [six, hanoi]
-    ev = _emu(scs, mc, 3, map_size=8)
-    assert ev.N == 82 and six.n_node == 6
-    buf = _register(ev)
-    ev.reset(with_obs=False)
+    side = Side(scs, mc, 3, map_size=NO_IMAGE_G[Side.name], render=False)
+    assert side.N == 82 and six.n_node == 6
+    buf = _registered(side)
+    side.reset()
     rng = np.random.RandomState(2)
     checked = 0
     for c in range(4):
-        snap = buf.snap(); pk = peeks(ev.h)
+        snap = buf.snap(); pk = peeks(side.handle); agents = _agents(side)
         for e in range(2):
-            if ev.agent_id[e] < 0:
+            if agents[e] < 0:
                 continue
             rows = buf.rows(snap, e)
-            check_rows(rows, reference(pk, e, int(ev.agent_id[e]), scs[e], mc, ev.N, 3), scs[e].n_node, "ragged call %d row %d" % (c, e))
+            check_rows(rows, reference(pk, e, int(agents[e]), scs[e], mc, side.N, 3), scs[e].n_node, "ragged call %d row %d" % (c, e))
             assert not rows[0][scs[e].n_node:].any()
             checked += 1
-        ids = np.where(ev.agent_id >= 0, ev.agent_id, -2).astype(np.int32)
-        ev.step(ids, rng.rand(2, 3), with_obs=False)
+        side.step(np.where(agents >= 0, agents, -2), rng.rand(2, 3))
     assert checked >= 6
+    side.close()
+
+
+def unregistering_and_identical_requests(Side):
+    """No image with entities registered writes the rows; after wrsn_set_entity_out(h, NULL) the same calls write nothing into the
+    buffers that were registered; the requests do not depend on entities being registered."""
+    scs, mc, side = _batch_side(Side, auto_reset=True)
+    _, _, plain = _batch_side(Side, auto_reset=True)
+    buf = _registered(side)
+    rng = np.random.RandomState(8)
+    for c in range(10):
+        act = rng.rand(5, 3)
+        for v in (side, plain):
+            if c == 0:
+                v.reset()
+            else:
+                v.step(_agents(v), act)
+        assert side.rows() == plain.rows(), c
+    snap = buf.snap()
+    assert any(buf.full(snap, e) for e in range(5))
+    side.set_entity_out(None)                                 # off
+    buf.fill()
+    side.reset()
+    side.step(_agents(side), rng.rand(5, 3))
+    side.clone_envs([0], [1])
+    check_extent(buf, buf.snap(), set(), "unregistered")
+    assert (_agents(side) >= 0).any()
+    side.close(); plain.close()
+
+
+# ---- the bodies above on the emulator (tests/test_entities_gpu.py: on the device)
+@pytest.mark.parametrize("name", FIXTURES)
+def test_values_on_fixtures(name):
+    values_on_fixtures(EmuSide, name)
+
+
+def test_blocking_steps_and_a_masked_reset_write_the_rendered_rows_only(hip_lib):
+    blocking_steps_and_a_masked_reset(EmuSide)
+
+
+def test_step_budget_leaves_rows_in_flight_untouched(hip_lib):
+    step_budget(EmuSide)
+
+
+def test_time_sliced_launches_write_the_rendered_rows_only(hip_lib):
+    time_sliced_launches(EmuSide)
+
+
+def test_load_clone_and_pool_reset_write_the_replaced_rows_only(hip_lib):
+    load_clone_and_pool_reset(EmuSide)
+
+
+def test_ragged_batch_values_and_zero_rows():
+    ragged_batch_values_and_zero_rows(EmuSide)
 
 
 def test_entity_only_calls_unregistering_and_identical_requests(hip_lib):
-    """out->obs NULL with entities registered writes the rows; after wrsn_set_entity_out(h, NULL) the same calls write nothing into
-    the buffers that were registered; the requests do not depend on entities being registered."""
-    scs, mc, ev = _batch()
-    _, _, plain = _batch()
-    buf = _register(ev)
-    rng = np.random.RandomState(8)
-    hist = []
-    for c in range(10):
-        act = rng.rand(5, 3)
-        for v in (ev, plain):
-            if c == 0:
-                v.reset(with_obs=False)
-            else:
-                v.step(v.agent_id.copy(), act, with_obs=False, auto_reset=True)
-        for k in ("agent_id", "reward", "now", "terminal", "status"):
-            assert getattr(ev, k).tobytes() == getattr(plain, k).tobytes(), (c, k)
-        hist.append(ev.agent_id.copy())
-    snap = buf.snap()
-    assert any(buf.full(snap, e) for e in range(5))
-    ev.h.set_entity_out()                                     # off
-    buf.fill()
-    ev.reset(with_obs=False)
-    ev.step(ev.agent_id.copy(), rng.rand(5, 3), with_obs=False, auto_reset=True)
-    ev.h.clone_envs([0], [1], **ev._ptrs(False))
-    check_extent(buf, buf.snap(), set(), "unregistered")
-    assert (ev.agent_id >= 0).any()
+    unregistering_and_identical_requests(EmuSide)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -299,8 +349,8 @@ def test_entity_struct_matches_the_header():
 
 def test_bad_entity_structs_are_refused_and_change_nothing(hip_lib):
     from multi_agent_rl_wrsn_amd import _lib
-    scs, mc, ev = _batch()
-    buf = _register(ev)
+    scs, mc, ev = _batch_side(EmuSide)
+    buf = _registered(ev)
     node, mcp, envp = buf.ptrs()
     ids = np.zeros(5, dtype=np.int32)
     for bad in ((node + 4, mcp, envp), (node, mcp + 8, envp), (node, mcp, envp + 2), (0, mcp, envp), (node, 0, envp), (node, mcp, 0)):
@@ -311,5 +361,5 @@ def test_bad_entity_structs_are_refused_and_change_nothing(hip_lib):
             ev.h.entities(ids.ctypes.data, *bad)
         assert ei.value.code == -1
     check_extent(buf, buf.snap(), set(), "refused calls")
-    ev.reset(with_obs=False)                                  # the handle still holds the buffers registered first
+    ev.reset()                                                # the handle still holds the buffers registered first
     check_extent(buf, buf.snap(), set(range(5)), "after refusals")

@@ -1,42 +1,11 @@
 """Environment records (wrsn_save_envs / wrsn_load_envs / wrsn_clone_envs) on the CPU: the unmodified HIP sources in the lockstep
 wavefront emulator of tests/emu.  A restored environment continues exactly as the source would have: against the reference runs of
 tests/golden, against Python's `random` for prob_gp < 1, and against an untouched twin."""
-import os
-import random
-
 import numpy as np
 import pytest
 
-from conftest import load_golden
 from parity import check_decision
-
-PGP_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "prob_gp")
-
-
-def _emu(scenarios, mc, M, **kw):
-    from emu_env import EmuVec
-    return EmuVec(scenarios, mc, M, **kw)
-
-
-def _fixture(name):
-    from multi_agent_rl_wrsn_amd.scenario import MC_SPEC_KEYS, NODE_SPEC_KEYS, Scenario, scenario_from_golden
-    if name.startswith("prob_gp/"):
-        z = np.load(os.path.join(PGP_DIR, name.split("/", 1)[1] + ".npz"))
-        ns = {k: float(v) for k, v in zip(NODE_SPEC_KEYS, z["node_spec"])}
-        mc = {k: float(v) for k, v in zip(MC_SPEC_KEYS, z["mc_spec"])}
-        return z, Scenario(z["node_xy"], z["target_xy"], z["bs_xy"], ns, float(z["max_time"]), int(z["seed64"]), stochastic_packets=True), mc
-    z = load_golden(name)
-    sc, mc = scenario_from_golden(z)
-    return z, sc, mc
-
-
-def _got(ev, e=0):
-    nd = ev.nodes(); m = ev.mcs()
-    return {"agent_id": int(ev.agent_id[e]), "now": float(ev.now[e]), "reward": float(ev.reward[e]), "terminal": bool(ev.terminal[e]),
-            "obs": ev.obs[e].astype(np.float64), "node_energy": nd["energy"][e], "node_cs": nd["cs"][e], "node_status": nd["status"][e],
-            "mc_energy": m["energy"][e], "mc_loc": np.stack([m["loc_x"][e], m["loc_y"][e]], 1), "mc_status": m["status"][e],
-            "mc_charging": m["type_charging"][e], "mc_nconn": m["n_conn"][e], "excl": m["excl"][e], "prev_minfit": m["prev_minfit"][e],
-            "min_fitness": float(ev.env_info()["min_fitness"][e]), "targets_active": ev.targets_active()[e]}
+from sides import EmuSide, load_fixture, python_mt_state
 
 
 def _row(ev, e):
@@ -72,13 +41,6 @@ def _load(ev, envs, rec, with_obs=True):
     ev.h.load_envs(np.asarray(envs, dtype=np.int32), rec.ctypes.data, **ev._ptrs(with_obs))
 
 
-def _python_state(seed, n):
-    r = random.Random(seed)
-    for _ in range(n):
-        r.random()
-    return list(r.getstate()[1])
-
-
 # (fixture, another scenario of the same NP / TP class that the destination handle is built with)
 RESUME = [("hanoi1000n50_m1_s3", "sonla1000n50_m2_s4"),            # M = 1
           ("redundant_m2_deaths", "six_m1_bs_charge_ongrid"),       # M = 2, node deaths
@@ -92,17 +54,17 @@ def test_resume_from_a_record_matches_the_reference(hip_lib, name, other):
     """Replay the fixture to its middle decision, save, load into environment 0 of a handle built with another scenario, and continue:
     every later decision still matches the reference run (and, for prob_gp < 1, the generator matches Python's word for word)."""
     from multi_agent_rl_wrsn_amd import _lib
-    z, sc, mc = _fixture(name)
-    _, sc2, _ = _fixture(other)
+    z, sc, mc = load_fixture(name)
+    _, sc2, _ = load_fixture(other)
     M = int(z["num_agent"]); kw = dict(map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]))
     K = len(z["in_action"]); mid = K // 2
-    src = _emu([sc], mc, M, **kw)
+    src = EmuSide([sc], mc, M, **kw)
     src.reset()
     for k in range(mid):
         src.step([int(z["in_agent"][k])], z["in_action"][k][None])
     rec = _save(src, [0])
     row0, obs0 = _row(src, 0), src.obs[0].copy()
-    dst = _emu([sc2, sc], mc, M, **kw)                        # N, T: the larger of the two scenarios -- same NP and TP as the source's
+    dst = EmuSide([sc2, sc], mc, M, **kw)                        # N, T: the larger of the two scenarios -- same NP and TP as the source's
     assert dst.h.env_record_bytes() == src.h.env_record_bytes()
     dst.reset()
     _load(dst, [0], rec)
@@ -117,27 +79,22 @@ def test_resume_from_a_record_matches_the_reference(hip_lib, name, other):
         if z["is_none"][k]:
             assert int(dst.status[0]) == 1 and int(dst.agent_id[0]) == -1
             break
-        got = _got(dst)
-        for key in ("node_energy", "node_cs", "node_status"):
-            got[key] = got[key][:sc.n_node]
-        got["targets_active"] = got["targets_active"][:sc.n_target]
-        check_decision(z, k, got, where=name, noise=noise)
+        check_decision(z, k, dst.decision(0, sc), where=name, noise=noise)
         if stoch and not z["terminal"][k]:
-            st = dst.h.peek(_lib.PEEK_RNG_STATE)[0]
-            n = int(st[625]) | (int(st[626]) << 32)
-            assert n == int(z["rng_draws"][k]), (name, k)
-            assert [int(v) for v in st[:625]] == _python_state(int(z["seed64"]), n), (name, k)
+            words, n = dst.h.rng_state()
+            assert n[0] == int(z["rng_draws"][k]), (name, k)
+            assert np.array_equal(words[0], python_mt_state(int(z["seed64"]), int(n[0]))), (name, k)
         if z["terminal"][k]:
             break
     assert len(noise) <= max(1, K // 3), noise
 
 
 def test_clone_within_a_handle_follows_the_source_and_leaves_it_alone(hip_lib):
-    z, sc, mc = _fixture("hanoi1000n50_m3_s1")
-    _, sc2, _ = _fixture("sonla1000n50_m2_s4")
+    z, sc, mc = load_fixture("hanoi1000n50_m3_s1")
+    _, sc2, _ = load_fixture("sonla1000n50_m2_s4")
     M = 3
-    ev = _emu([sc, sc2, sc2], mc, M)
-    twin = _emu([sc], mc, M)
+    ev = EmuSide([sc, sc2, sc2], mc, M)
+    twin = EmuSide([sc], mc, M)
     ev.reset(); twin.reset()
     for k in range(4):
         a = int(z["in_agent"][k])
@@ -163,13 +120,13 @@ def test_clone_within_a_handle_follows_the_source_and_leaves_it_alone(hip_lib):
 
 
 def test_reset_and_auto_reset_after_a_load_restore_the_sources_warm_up(hip_lib):
-    z, sc, mc = _fixture("redundant_m2_deaths")
-    _, sc2, _ = _fixture("six_m1_bs_charge_ongrid")
+    z, sc, mc = load_fixture("redundant_m2_deaths")
+    _, sc2, _ = load_fixture("six_m1_bs_charge_ongrid")
     M = 2
-    fresh = _emu([sc], mc, M)
+    fresh = EmuSide([sc], mc, M)
     fresh.reset()
     want = _peeks(fresh, 0, sc); want_row = _row(fresh, 0); want_obs = fresh.obs[0].copy()
-    src = _emu([sc], mc, M)
+    src = EmuSide([sc], mc, M)
     src.reset()
     term_k = int(np.argmax(z["terminal"]))
     for k in range(term_k + 1):
@@ -177,7 +134,7 @@ def test_reset_and_auto_reset_after_a_load_restore_the_sources_warm_up(hip_lib):
     assert src.terminal[0] == 1
     rec = _save(src, [0])
     for auto in (False, True):
-        dst = _emu([sc, sc2], mc, M)                         # environment 1 was built with the six-node network
+        dst = EmuSide([sc, sc2], mc, M)                         # environment 1 was built with the six-node network
         dst.reset()
         _load(dst, [1], rec)
         assert dst.terminal[1] == 1
@@ -202,12 +159,12 @@ def test_refusals_change_nothing(hip_lib):
     from emu_env import emu_lib
     from multi_agent_rl_wrsn_amd import _lib
     lib = emu_lib()
-    _, sc, mc = _fixture("redundant_m2_deaths")             # 30 nodes: NP 64
-    _, big, _ = _fixture("hanoi1000n50_m3_s1")              # 82 nodes: NP 128
-    _, six, _ = _fixture("six_m1_bs_charge_ongrid")
-    _, gsc, _ = _fixture("prob_gp/redundant_m2_p05")
-    _, gsc2, _ = _fixture("prob_gp/redundant_rev_m2_p05")
-    ev = _emu([sc, six, sc], mc, 2)
+    _, sc, mc = load_fixture("redundant_m2_deaths")             # 30 nodes: NP 64
+    _, big, _ = load_fixture("hanoi1000n50_m3_s1")              # 82 nodes: NP 128
+    _, six, _ = load_fixture("six_m1_bs_charge_ongrid")
+    _, gsc, _ = load_fixture("prob_gp/redundant_m2_p05")
+    _, gsc2, _ = load_fixture("prob_gp/redundant_rev_m2_p05")
+    ev = EmuSide([sc, six, sc], mc, 2)
     ev.reset()
     rec = _save(ev, [0, 1])
     before = [_peeks(ev, e) for e in range(3)]; rows = [_row(ev, e) for e in range(3)]
@@ -222,10 +179,10 @@ def test_refusals_change_nothing(hip_lib):
             _same(_peeks(ev, e), before[e])
             assert _row(ev, e) == rows[e]
 
-    bigh = _emu([big], mc, 2)
+    bigh = EmuSide([big], mc, 2)
     brec = _save(bigh, [0])
     refused(lambda: _load(ev, [0], brec), "NP")
-    h3 = _emu([sc], mc, 3); r3 = _save(h3, [0])
+    h3 = EmuSide([sc], mc, 3); r3 = _save(h3, [0])
     refused(lambda: _load(ev, [2], r3), "M")
     bad = rec.copy(); bad[0, 0] ^= 0x55
     refused(lambda: _load(ev, [0, 1], bad), "magic")
@@ -235,7 +192,7 @@ def test_refusals_change_nothing(hip_lib):
     refused(lambda: _load(ev, [2, 2], rec), "twice")
     refused(lambda: ev.h.clone_envs([0, 1], [1, 2], **ev._ptrs(True)), "also a source")
     refused(lambda: ev.h.clone_envs([0], [-1], **ev._ptrs(True)), "out of range")
-    g = _emu([gsc, gsc2], mc, 2); g.reset()
+    g = EmuSide([gsc, gsc2], mc, 2); g.reset()
     grec = _save(g, [0])
     refused(lambda: _load(ev, [0], grec), "has_gen")      # generator record -> a handle without generators that holds a scenario
     before_g = _peeks(g, 1); st_g = g.h.peek(_lib.PEEK_RNG_STATE).copy()
@@ -266,7 +223,7 @@ def test_ragged_record_round_trips(hip_lib):
     from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, synth_scenario
     small, large = synth_scenario(11, 50, 40), synth_scenario(12, 200, 200)
     kw = dict(warm_up_time=5.0)
-    a = _emu([small, large], DEFAULT_MC_SPEC, 2, **kw); b = _emu([large], DEFAULT_MC_SPEC, 2, **kw)
+    a = EmuSide([small, large], DEFAULT_MC_SPEC, 2, **kw); b = EmuSide([large], DEFAULT_MC_SPEC, 2, **kw)
     a.reset(); b.reset()
     rng = np.random.RandomState(1)
     act = rng.rand(2, 3) * np.array([1.0, 1.0, 0.3])
@@ -274,7 +231,7 @@ def test_ragged_record_round_trips(hip_lib):
     rec = _save(a, [0])
     b.h.load_envs([0], rec.ctypes.data, **b._ptrs(True))
     rec2 = _save(b, [0])
-    c = _emu([large, large], DEFAULT_MC_SPEC, 2, **kw); c.reset()
+    c = EmuSide([large, large], DEFAULT_MC_SPEC, 2, **kw); c.reset()
     _load(c, [1], rec2)
     for k in range(3):
         act = rng.rand(3) * np.array([1.0, 1.0, 0.3])
@@ -294,9 +251,9 @@ def test_record_format_version_1_is_pinned(hip_lib):
     import struct
     for name, nbytes, has_gen, nseg in (("hanoi1000n50_m1_warmup10", 116480, 0, 43),                  # 82 nodes, 50 targets: NP 128, TP 64
                                         ("prob_gp/hanoi1000n50_m1_warmup10_p05", 123648, 1, 48)):     # + the generator block
-        z, sc, mc = _fixture(name)
+        z, sc, mc = load_fixture(name)
         assert (sc.n_node, sc.n_target, int(z["num_agent"])) == (82, 50, 1), name
-        ev = _emu([sc], mc, 1, map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]))
+        ev = EmuSide([sc], mc, 1, map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]))
         assert ev.h.env_record_bytes() == nbytes, name
         rec = _save(ev, [0])
         assert rec.shape == (1, nbytes), name

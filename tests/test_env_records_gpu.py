@@ -2,21 +2,16 @@
 reuse, prob_gp < 1, the roll-out bookkeeping, 1000-node networks and through the WRSN facade."""
 import numpy as np
 import pytest
+from sides import need_gpu
 
 pytestmark = pytest.mark.gpu
 
 FIELDS = ("agent_id", "reward", "terminal", "now", "status")
 
 
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch
-
-
 def _assert_rows_equal(ra, rb, ia=None, ib=None, state=True):
     """Request rows ia of ra and ib of rb bit for bit (state: rows with a charger only -- the others are left untouched)."""
-    torch = _torch()
+    torch = need_gpu()
     for k in FIELDS:
         a, b = ra[k], rb[k]
         if ia is not None:
@@ -34,7 +29,7 @@ def _assert_rows_equal(ra, rb, ia=None, ib=None, state=True):
 def test_headline_geometry_resume_is_bit_identical():
     """4096 x 200 nodes x 3 chargers, blocking mode, auto-reset: 40 steps, save every environment, 40 more; the records (through the
     host) loaded into a batch built from other scenarios replay the same 40 steps bit for bit."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN, synth_scenario
     B, U, M, K = 4096, 64, 3, 40
     scs = [synth_scenario(7100 + u, 200, 200) for u in range(U)]
@@ -62,7 +57,7 @@ def test_headline_geometry_resume_is_bit_identical():
 def _drive(env, acts, K, H, rounds=400):
     """Per environment the first K requests of a run driven by acts[j, e % H] for its j-th decision (a status-4 row's action is not
     looked at, so it is not used up)."""
-    torch = _torch()
+    torch = need_gpu()
     B = env.num_env
     j = np.zeros(B, dtype=int); busy = env.status.cpu().numpy() == 4
     hist = [[] for _ in range(B)]
@@ -91,7 +86,7 @@ def _drive(env, acts, K, H, rounds=400):
 def test_clone_under_every_launch_mode(mode):
     """Clone the first half of the batch onto the second half (rows in flight and latched actions included) and continue both halves
     with equal actions: agent, time and terminal identical, rewards to round-off."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN, synth_scenario
     B = 256 if mode == "budget" else 512
     H, M, K = B // 2, 3, 5
@@ -123,7 +118,7 @@ def test_clone_under_every_launch_mode(mode):
 
 
 def test_observation_reuse_after_load_and_clone_equals_a_full_render():
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN, synth_scenario
     B, M = 64, 3
     scs = [synth_scenario(7700 + e, 200, 200) for e in range(B)]
@@ -152,7 +147,7 @@ def test_observation_reuse_after_load_and_clone_equals_a_full_render():
 
 
 def test_prob_gp_batch_generator_follows_clone_and_load():
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import DEFAULT_NODE_SPEC, VecWRSN, synth_scenario
     from multi_agent_rl_wrsn_amd import _lib
     spec = dict(DEFAULT_NODE_SPEC); spec["prob_gp"] = 0.5
@@ -184,7 +179,7 @@ def test_prob_gp_batch_generator_follows_clone_and_load():
 
 
 def test_rollout_collect_appends_nothing_for_restored_rows():
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import TransitionBuffers, VecWRSN, synth_scenario
     B, M = 16, 3
     env = VecWRSN([synth_scenario(8100 + e, 100, 80) for e in range(B)], None, M, auto_reset=True)
@@ -213,7 +208,7 @@ def test_rollout_collect_appends_nothing_for_restored_rows():
 
 
 def test_1000_node_8_charger_round_trip():
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN, synth_scenario
     B, U, M = 256, 8, 8
     uniq = [synth_scenario(8300 + u, 1000, 1000) for u in range(U)]
@@ -236,7 +231,7 @@ def test_1000_node_8_charger_round_trip():
 
 
 def test_facade_lookahead_restores_the_request(tmp_path):
-    _torch()
+    need_gpu()
     import yaml
     from conftest import load_golden
     from multi_agent_rl_wrsn_amd import WRSN

@@ -5,28 +5,10 @@ import numpy as np
 import pytest
 
 from conftest import golden_names, load_golden
-from parity import check_decision, check_density_action, close
+from parity import check_decision, check_density_action, close, replay_reference_fixture
+from sides import VecSide, decision_dict, need_gpu
 
 pytestmark = pytest.mark.gpu
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch
-
-
-def _got(env, r, e=0, with_nodes=True):
-    g = {"agent_id": int(r["agent_id"][e]), "now": float(r["now"][e]), "reward": float(r["reward"][e]),
-         "terminal": bool(r["terminal"][e]), "obs": r["state"][e].double().cpu().numpy()}
-    if with_nodes:
-        nd = env.nodes(); m = env.mcs()
-        g.update(node_energy=nd["energy"][e], node_cs=nd["cs"][e], node_status=nd["status"][e],
-                 mc_energy=m["energy"][e], mc_loc=np.stack([m["loc_x"][e], m["loc_y"][e]], 1), mc_status=m["status"][e],
-                 mc_charging=m["type_charging"][e], mc_nconn=m["n_conn"][e], excl=m["excl"][e],
-                 prev_minfit=m["prev_minfit"][e], min_fitness=float(env.env_info()["min_fitness"][e]),
-                 targets_active=env.targets_active()[e])
-    return g
 
 
 def test_native_library_is_the_one_running():
@@ -39,43 +21,11 @@ def test_native_library_is_the_one_running():
 
 @pytest.mark.parametrize("name", golden_names())
 def test_hip_matches_reference_fixture(name):
-    torch = _torch()
-    from multi_agent_rl_wrsn_amd import VecWRSN
-    from multi_agent_rl_wrsn_amd.scenario import scenario_from_golden
-    z = load_golden(name)
-    sc, mc = scenario_from_golden(z)
-    env = VecWRSN([sc], mc, int(z["num_agent"]), map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]))
-    info = env.env_info()
-    assert close([info["xmin"][0], info["xmax"][0], info["ymin"][0], info["ymax"][0]], z["frame"], rtol=1e-14)
-    r = env.reset(); env.synchronize()
-    noise = []
-    assert int(r["agent_id"][0]) == int(z["reset_agent"]) and float(r["reward"][0]) == 0.0
-    nd = env.nodes()
-    assert close(nd["energy"][0], z["reset_node_energy"]) and np.array_equal(nd["level"][0], z["reset_node_level"])
-    assert np.max(np.abs(r["state"][0].double().cpu().numpy() - z["reset_obs"])) <= 1e-5 * max(1.0, np.abs(z["reset_obs"]).max())
-    for k in range(len(z["in_action"])):
-        if "in_map" in z.files:                              # density_map=True fixture: the policy map of this decision
-            nd = env.nodes()
-            act = env.density_to_action(torch.tensor([int(z["in_agent"][k])]), torch.from_numpy(z["in_map"][k].astype(np.float64)[None])).cpu().numpy()
-            check_density_action(z, k, act[0], {"energy": nd["energy"][0], "cs": nd["cs"][0], "status": nd["status"][0]}, where=name)
-        r = env.step(torch.tensor([int(z["in_agent"][k])]), torch.tensor(z["in_action"][k][None]))   # the reference's own 3-vector
-        env.synchronize()
-        if z["is_none"][k]:
-            assert int(r["status"][0]) == 1 and int(r["agent_id"][0]) == -1
-            break
-        assert int(r["status"][0]) == 0
-        if np.isinf(z["reward"][k]):
-            assert float(r["reward"][0]) == float(z["reward"][k])
-            continue
-        check_decision(z, k, _got(env, r), where=name, noise=noise)
-        if z["terminal"][k]:
-            break
-    assert len(noise) <= max(1, len(z["in_action"]) // 8), noise     # rewards that hang on the sign of a rounding residue stay rare
-    env.close()
+    replay_reference_fixture(VecSide, name)
 
 
 def test_hip_batch_matches_oracle_on_synthetic_200_node_networks():
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, VecWRSN, synth_scenario
     from wrsn_oracle import OracleWRSN
     B, M = 12, 3
@@ -113,7 +63,7 @@ def test_hip_batch_matches_oracle_on_synthetic_200_node_networks():
 
 def test_hip_1000_node_8_charger_network_matches_oracle():
     """BASELINE config 5 shape (multi-slot-per-lane stress): 1000 nodes, 8 chargers, a few decisions."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, VecWRSN, synth_scenario
     from wrsn_oracle import OracleWRSN
     M = 8
@@ -145,7 +95,7 @@ def test_hip_1000_node_8_charger_network_matches_oracle():
 def test_full_size_properties_4096_envs_200_nodes():
     """Size-independent properties at BASELINE.json's configuration: replica invariance, determinism, reset
     idempotence, monotone drain without charging, and spot checks against the oracle."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, VecWRSN, synth_scenario
     from wrsn_oracle import OracleWRSN
     B, U, M = 4096, 64, 3
@@ -205,7 +155,7 @@ def test_full_size_properties_4096_envs_200_nodes():
 def test_full_size_properties_4096_envs_1000_nodes_8_chargers():
     """BASELINE configs[4] at full size (4096 environments x 1000 nodes x 8 chargers, sixteen register slots per lane):
     replica invariance and determinism of a whole batch, spot checks against the oracle, monotone drain without charging."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, VecWRSN, synth_scenario
     from wrsn_oracle import OracleWRSN
     B, U, M, K = 4096, 16, 8, 10
@@ -262,7 +212,7 @@ def test_step_budget_gives_the_same_requests_as_blocking_steps():
     """wrsn_set_step_budget only changes the launch a request is reported in: per environment the sequence of requests
     (agent, simulated time, reward, terminal, observation) of a budgeted run equals the blocking run (float64 values to
     round-off: a suspension may split a closed-form jump in two)."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN, synth_scenario
     B, K = 96, 12
     scs = [synth_scenario(500 + e, 200, 200) for e in range(B)]
@@ -340,7 +290,7 @@ def _compare_histories(h0, h1, B):
 
 
 def test_auto_reset_on_device():
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN, synth_scenario
     scs = [synth_scenario(300 + e, 120, 120) for e in range(64)]
     env = VecWRSN(scs, None, 3, auto_reset=True)
@@ -369,7 +319,7 @@ def test_auto_reset_on_device():
 
 def test_wrsn_facade_dict_protocol(tmp_path):
     """Drop-in facade: same constructor / dict keys / float64 states as rl_env.WRSN.WRSN, values from the fixture."""
-    _torch()
+    need_gpu()
     import yaml
     from multi_agent_rl_wrsn_amd import WRSN
     from multi_agent_rl_wrsn_amd.scenario import MC_SPEC_KEYS, NODE_SPEC_KEYS
@@ -406,7 +356,7 @@ def test_wrsn_facade_dict_protocol(tmp_path):
 def test_density_map_to_action_on_device():
     """f1: WRSN.density_map_to_action (WRSN.py:229-297) through VecWRSN.density_to_action: third component / box exact,
     objective value of the charging spot >= SciPy L-BFGS-B's (the reference's optimiser; its spot is not pinned)."""
-    torch = _torch()
+    torch = need_gpu()
     import density_ref
     from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, VecWRSN, synth_scenario
     B, G = 24, 100
@@ -445,7 +395,7 @@ def test_parity_sweep_whole_episodes_with_resets(budget):
     """tests/parity_sweep.py at a small size: 48 environments x 40 launches side by side with the oracle, whole episodes with
     masked resets, blocking and budgeted; every request compared (rewards that hang on the sign of a rounding-noise
     energyCS of the reference are counted, not compared -- DESIGN.md 2)."""
-    _torch()
+    need_gpu()
     import parity_sweep
     n_cmp, n_term, n_noise = parity_sweep.run(B=48, K=40, budget=budget, seed0=52000)
     assert n_cmp > 600 and n_term > 80 and n_noise < n_cmp // 50
@@ -457,7 +407,7 @@ def test_parity_sweep_wide(case):
     the two-stage pipeline of a step call, with the default work budget and with blocking steps --, time-sliced launches, 1 000 nodes x 8
     chargers (16 node slots per lane, pushed level search, sparse charging-rate list) and 8 chargers on 200 nodes (overlapping
     charging ranges).  Every request of every launch against the oracle, whole episodes with resets."""
-    _torch()
+    need_gpu()
     import parity_sweep
     kw = {"pipeline_budget_512x200": dict(B=512, K=40, budget=1250, seed0=61000),
           "pipeline_blocking_512x200": dict(B=512, K=24, budget=0, seed0=62000),
@@ -486,7 +436,7 @@ def test_wrsn_facade_density_map_path(tmp_path, name):
     against what the fixture pins of it (third component, arg-max box, objective value >= the reference's), then the step is
     taken with the reference's 3-vector (`_action3`, the one unpinned result replaced) so that the next decision starts from the
     reference's state again -- agent, time, reward, node energies and observation of every request are the fixture's."""
-    _torch()
+    need_gpu()
     from multi_agent_rl_wrsn_amd import WRSN
     z = load_golden(name)
     sp, mp = _write_yaml(tmp_path, z)
@@ -509,7 +459,7 @@ def test_wrsn_facade_density_map_path(tmp_path, name):
             assert req is None
             break
         # the request of the device behind the facade, held to the fixture exactly like test_hip_matches_reference_fixture does
-        check_decision(z, k, _got(env.vec, env.vec._result()), where=name + " facade", noise=noise)
+        check_decision(z, k, decision_dict(env.vec._result(), env.vec.state[0].double().cpu().numpy(), env.vec._h), where=name + " facade", noise=noise)
         assert close(env.env.now, z["now"][k], rtol=1e-9), (name, k)
         if z["terminal"][k]:
             assert req["terminal"] and req["agent_id"] is None and req["state"] is None
@@ -529,7 +479,7 @@ def test_wrsn_facade_density_map_path(tmp_path, name):
 def test_untouched_and_unmasked_rows_keep_their_request_on_device():
     """agent_id -2 in step() and a zero mask byte in reset(mask) leave a row's outputs alone (pending request id and
     observation included): `r = env.reset(mask); env.step(r["agent_id"], a)` is safe for the rows that were not reset."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN, synth_scenario
     B = 8
     scs = [synth_scenario(700 + e, 100, 80) for e in range(B)]
@@ -558,7 +508,7 @@ def test_step_budget_never_runs_an_environment_twice_per_launch():
     """Ownership inside a budgeted launch (2 B blocks) on the hardware, where listed and regular blocks of one environment
     really run at the same time: per launch the rollout table counts at most one completed WRSN.step per environment,
     exactly the rows that report a request, and the returns equal the host-side accumulation of those requests."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN, synth_scenario
     B, M = 1024, 3
     uniq = [synth_scenario(8100 + u, 200, 200) for u in range(32)]
@@ -590,7 +540,7 @@ def test_step_budget_never_runs_an_environment_twice_per_launch():
 def test_transition_buffers_equal_the_reference_bookkeeping_on_device():
     """f2: the device-side transition buffers of a batched roll-out (auto-reset, step budget) hold exactly what the reference's
     list bookkeeping (controller/ippo/IPPO.py:137-155, restated in tests/test_ippo.py) collects from B = 1 environments."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import TransitionBuffers, VecWRSN, synth_scenario
     from test_ippo import _policy, reference_bookkeeping
     B, M, K, CAP = 6, 3, 30, 128
@@ -646,7 +596,7 @@ def test_transition_buffers_equal_the_reference_bookkeeping_on_device():
 def test_batched_ippo_rollout_and_update_smoke():
     """configs[2] at a toy size: BatchedIPPO (UNet actor / CNN critic per charger, density-map actions) rolls out a batch of
     environments into the device buffers, selects the batch like the reference and runs the PPO update."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import BatchedIPPO, VecWRSN, synth_scenario
     torch.manual_seed(0); np.random.seed(0)
     B, M = 48, 3
@@ -670,7 +620,7 @@ def test_batched_ippo_rollout_and_update_smoke():
 def test_observation_reuse_is_bit_identical_on_device():
     """wrsn_set_obs_reuse (VecWRSN(reuse_obs=True)): a batch with reuse and one that re-renders every row in full (reuse_obs=False, and the
     caller scribbling over its state tensor) return identical observations over whole episodes with auto-reset and a step budget."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN, synth_scenario
     B, M = 192, 3
     scs = [synth_scenario(6100 + e % 48, 200, 200) for e in range(B)]
@@ -698,7 +648,7 @@ def test_rollout_logp_invariant_and_batchnorm_dependence_on_device():
     stored action evaluated over the SAME batch composition the roll-out forward saw (same chunks, same padding) is the stored one;
     evaluated inside another batch (a minibatch of the update) it is not -- the actors run BatchNorm in training mode, like the
     reference's (IPPO.py:95-113: roll-out on batches of one, update on minibatches)."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import PPOLearner
     from test_ippo import formula_fill
     torch.manual_seed(0)
@@ -723,7 +673,7 @@ def test_ppo_update_on_device_matches_the_same_update_in_float64_on_the_host():
     therefore set near what the current policy gives inside THIS minibatch (ratio ~ 1, both clip branches in play).  Adam's first step is
     lr * g / (|g| + 1e-8): where a gradient element is at noise level its sign -- and with it the whole step -- is not defined by the
     arithmetic, so parameters are compared where |g| is well above that."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import PPOLearner
     from test_ippo import formula_fill
     G, n = 40, 8
@@ -777,7 +727,7 @@ def test_configs2_full_size_4096_env_ippo_rollout_with_oracle_spot_checks():
     buffers, step budget 1250 as in bench_ippo.py).  Spot environments are followed by the CPU oracle fed with the 3-vectors the device
     derived (`density_to_action`): agent, simulated time, reward, terminal flag and node energies of every completed request must
     agree (IPPO.py:137-155, WRSN.py:293-299).  One inference batch shape (chunk 512, padded) so that MIOpen searches once."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import BatchedIPPO, DEFAULT_MC_SPEC, VecWRSN, synth_scenario
     from wrsn_oracle import OracleWRSN
     torch.manual_seed(0); np.random.seed(0)
@@ -834,7 +784,7 @@ def test_configs2_full_size_4096_env_ippo_rollout_with_oracle_spot_checks():
 def test_rollouts_continue_the_episodes_instead_of_restarting_them():
     """`roll_out` keeps the environments (and the pending actions) alive from one roll-out to the next, so that a large batch
     -- which reaches its per-charger quota within a few launches -- still sees later decisions, node deaths and terminal returns."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import BatchedIPPO, VecWRSN, synth_scenario
     torch.manual_seed(0); np.random.seed(0)
     B, M = 256, 3
@@ -859,7 +809,7 @@ def test_pipelined_step_calls_return_what_single_launches_return(monkeypatch, B,
     requests -- agent, time, terminal, reward, observation -- are those of the single launch (WRSN_PIPE=0); only the call a request is
     reported in may differ (another cap for a step in the short half).  Budgeted and blocking, 1 024 environments, whole episodes; and batch
     sizes that are no multiple of the wavefront / of the stage granularity (777, 513: the launch order is padded to a power of two)."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN, synth_scenario
     uniq = [synth_scenario(15000 + u, 200, 200) for u in range(B)]
     g = torch.Generator().manual_seed(9)

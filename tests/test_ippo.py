@@ -8,6 +8,7 @@ import zlib
 
 import numpy as np
 import pytest
+from sides import EmuSide
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden_policy", "policy_nets.npz")
@@ -196,11 +197,10 @@ def test_emulated_transition_buffers_equal_the_reference_bookkeeping():
     """wrsn_rollout_record / wrsn_rollout_collect (csrc/wrsn_rollout.h, emulated) over a batch with auto-reset and a step
     budget == the reference's per-environment list bookkeeping on single environments."""
     import ctypes as C
-    from emu_env import EmuVec
     from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, _lib, synth_scenario
     B, M, G, CAP, K = 3, 2, 12, 64, 28
     scs = [synth_scenario(300 + e, 70, 60) for e in range(B)]
-    ev = EmuVec(scs, DEFAULT_MC_SPEC, M, map_size=G)
+    ev = EmuSide(scs, DEFAULT_MC_SPEC, M, map_size=G)
     ev.h.set_step_budget(60)
     S = 4 * G * G
     arrs = dict(pend_state=np.zeros((B, M, S), np.float32), pend_action=np.zeros((B, M, 3), np.float32), pend_logp=np.zeros((B, M), np.float32),
@@ -227,7 +227,7 @@ def test_emulated_transition_buffers_equal_the_reference_bookkeeping():
     # the same decisions, one environment at a time, with the reference's bookkeeping
     want = [[] for _ in range(M)]
     for e in range(B):
-        one = EmuVec([scs[e]], DEFAULT_MC_SPEC, M, map_size=G)
+        one = EmuSide([scs[e]], DEFAULT_MC_SPEC, M, map_size=G)
         def req():
             return dict(agent_id=int(one.agent_id[0]), state=one.obs[0].reshape(-1).copy(), reward=float(one.reward[0]), terminal=bool(one.terminal[0]),
                         now=float(one.now[0]), policy=lambda n, e=e: _policy(e, n))

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from sides import EmuSide
 
 CANARY = 0xA5C3
 N_CANARY = 4096
@@ -43,25 +44,23 @@ def test_rne_helper_equals_torch():
 
 
 class Bf16Emu:
-    """EmuVec whose observation buffer is exactly B*4*G*G uint16 followed by a canary region."""
+    """An EmuSide whose observation buffer is exactly B*4*G*G uint16 followed by a canary region."""
 
     def __init__(self, scenarios, mc, M, **kw):
-        from emu_env import EmuVec
         from multi_agent_rl_wrsn_amd import _lib
-        self.ev = ev = EmuVec(scenarios, mc, M, **kw)
+        self.ev = ev = EmuSide(scenarios, mc, M, **kw)
         ev.h.set_obs_format(_lib.OBS_BF16)
         n = ev.B * 4 * ev.G * ev.G
         self.raw = np.full(n + N_CANARY, CANARY, dtype=np.uint16)
         self.raw[:n] = 0
-        ev.obs = self.raw[:n].reshape(ev.B, 4, ev.G, ev.G)     # EmuVec._ptrs hands out self.obs.ctypes.data
+        ev.obs = self.raw[:n].reshape(ev.B, 4, ev.G, ev.G)     # EmuSide._ptrs hands out self.obs.ctypes.data
 
     def canary_ok(self):
         return bool((self.raw[self.ev.obs.size:] == CANARY).all())
 
 
 def _pair(scenarios, mc, M, **kw):
-    from emu_env import EmuVec
-    return EmuVec(scenarios, mc, M, **kw), Bf16Emu(scenarios, mc, M, **kw)
+    return EmuSide(scenarios, mc, M, **kw), Bf16Emu(scenarios, mc, M, **kw)
 
 
 def _ref_ok(bits, ref):
@@ -261,10 +260,9 @@ def test_bf16_reuse_is_bit_identical():
 def test_reuse_does_not_survive_a_change_of_format_at_the_same_address():
     """4b. render float32 into a buffer, switch the handle to bf16, render into the SAME address: map 1 equals a render into a fresh
     buffer; the same in the other direction.  (Row 0 has the same address in both formats.)"""
-    from emu_env import EmuVec
     from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, _lib, synth_scenario
     G = 20
-    ev = EmuVec([synth_scenario(50, 70, 60)], DEFAULT_MC_SPEC, 3, map_size=G)    # reuse on
+    ev = EmuSide([synth_scenario(50, 70, 60)], DEFAULT_MC_SPEC, 3, map_size=G)    # reuse on
     ev.reset()
     agents = ev.agent_id.copy()
     buf = np.zeros(4 * G * G, dtype=np.float32)                # one address for both formats
@@ -313,7 +311,6 @@ def _tr_arrays(B, M, S, CAP, obs_dtype):
 def test_bf16_rollout_buffers_hold_the_observation_rows():
     """5. wrsn_rollout_record / wrsn_rollout_collect with bf16 buffers (a canary behind each): every stored state / next_state row is the
     bf16 observation row it was taken from; counts, rewards, now, env equal those of the same run in float32."""
-    from emu_env import EmuVec
     from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, _lib, synth_scenario
     B, M, G, CAP, K = 3, 2, 12, 64, 20
     S = 4 * G * G
@@ -323,7 +320,7 @@ def test_bf16_rollout_buffers_hold_the_observation_rows():
         if fmt == "bf16":
             w = Bf16Emu(scs, DEFAULT_MC_SPEC, M, map_size=G); ev = w.ev
         else:
-            w = None; ev = EmuVec(scs, DEFAULT_MC_SPEC, M, map_size=G)
+            w = None; ev = EmuSide(scs, DEFAULT_MC_SPEC, M, map_size=G)
         ev.h.set_step_budget(60)
         raws, arrs = _tr_arrays(B, M, S, CAP, np.uint16 if fmt == "bf16" else np.float32)
         buf = _lib.WrsnTransitionBuffers(CAP, 3, *[arrs[k].ctypes.data for k in ("pend_state", "pend_action", "pend_logp", "pend_valid", "state",
@@ -399,18 +396,17 @@ def test_bf16_records_render_the_destination_row(hip_lib):
 def test_obs_format_abi_default_and_bad_values():
     """7. the default is float32 (a fresh handle renders what a handle explicitly set to float32 renders, and what the fixture holds);
     formats 2 and -1 are WRSN_ERR_ARG and the handle goes on rendering in its previous format."""
-    from emu_env import EmuVec
     from multi_agent_rl_wrsn_amd import _lib
     from multi_agent_rl_wrsn_amd.scenario import scenario_from_golden
     assert (_lib.OBS_F32, _lib.OBS_BF16) == (0, 1) and "wrsn_set_obs_format" in _lib.EXPORTS
     z = load_golden("six_m3_bs_charge_ongrid")
     sc, mc = scenario_from_golden(z)
     kw = dict(map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]))
-    fresh = EmuVec([sc], mc, int(z["num_agent"]), **kw)
+    fresh = EmuSide([sc], mc, int(z["num_agent"]), **kw)
     fresh.reset()
     assert fresh.obs.dtype == np.float32
     assert np.max(np.abs(fresh.obs[0] - z["reset_obs"])) <= 1e-5 * max(1.0, np.abs(z["reset_obs"]).max())
-    ev = EmuVec([sc], mc, int(z["num_agent"]), **kw)
+    ev = EmuSide([sc], mc, int(z["num_agent"]), **kw)
     ev.h.set_obs_reuse(False)
     ev.h.set_obs_format(_lib.OBS_F32)
     for bad in (2, -1):

@@ -10,17 +10,12 @@ import numpy as np
 import pytest
 
 from conftest import load_golden
+from sides import need_gpu
 
 pytestmark = pytest.mark.gpu
 
 CANARY = -23101                                               # 0xA5C3 as int16
 N_CANARY = 1 << 16
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch
 
 
 def _guarded(torch, shape, device="cuda:0"):
@@ -72,7 +67,7 @@ def _batch(n, seed0=5200, uniq=64):
 def test_bf16_equals_rounded_float32_side_by_side(mode):
     """9 (deterministic modes). B = 1024 synthetic 200-node environments, 3 chargers, random actions, auto-reset, 40 launches: a float32 and
     a bf16 VecWRSN stepped side by side return the same requests, and every bf16 row with a request is the rounded float32 row."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN
     B, M = 1024, 3
     scs = _batch(B)
@@ -106,7 +101,7 @@ def test_bf16_equals_rounded_float32_side_by_side(mode):
 def test_bf16_time_sliced_launches_render_the_rounded_float32_state():
     """9 (time slices). Which launch reports a request is timing-dependent, so the bf16 batch is compared with its OWN float32 render of the
     same state (raw handle switched to float32 and back): the rows of `state` with a request and a fresh bf16 render_state."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN, _lib
     B, M, G = 1024, 3, 100
     env = VecWRSN(_batch(B), None, M, auto_reset=True, reuse_obs=True, step_deadline_us=400, obs_dtype=torch.bfloat16)
@@ -138,7 +133,7 @@ def test_bf16_time_sliced_launches_render_the_rounded_float32_state():
 @pytest.mark.parametrize("name", ["hanoi1000n50_m3_s1", "redundant_m2_map64", "six_m3_bs_charge_ongrid", "hanoi1000n100_m3_s5"])
 def test_bf16_matches_the_reference_fixture_on_device(name):
     """10. reset_obs, obs_full[k] and the strided obs_sample[k] of the reference within 2^-8 |ref| + (1 + 2^-8) 1e-5 max(1, peak)."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN
     from multi_agent_rl_wrsn_amd.scenario import scenario_from_golden
     z = load_golden(name)
@@ -170,7 +165,7 @@ def test_bf16_matches_the_reference_fixture_on_device(name):
 
 def test_bf16_extent_and_untouched_rows_on_device():
     """11 / 3. canary behind exactly B*4*G*G bf16 cells; -2 rows, terminal returns and rows a masked reset leaves out stay byte-identical."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN, synth_scenario
     sc = synth_scenario(21, 70, 50)
     B = 5
@@ -205,7 +200,7 @@ def test_bf16_extent_and_untouched_rows_on_device():
 def test_bf16_reuse_and_format_switch_on_device():
     """11 / 4. bf16 with map-1 reuse equals bf16 without, bit for bit; and a row rendered in one format at an address is not taken for
     map 1 of the other format at the same address (row 0 has the same address in both)."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN, _lib
     B, M, G = 96, 3, 100
     scs = _batch(B, seed0=6100, uniq=48)
@@ -252,7 +247,7 @@ def test_bf16_reuse_and_format_switch_on_device():
 def test_bf16_transition_buffers_on_device():
     """11 / 5. TransitionBuffers of a bf16 environment (canaries behind the three state tensors) against the same run in float32: stored
     state / next_state rows are the rounded float32 rows; counts, rewards, now, env, actions, log-probabilities are equal."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import TransitionBuffers, VecWRSN, _lib, synth_scenario
     from test_ippo import _policy
     B, M, K, CAP = 6, 3, 24, 128
@@ -317,7 +312,7 @@ def test_bf16_transition_buffers_on_device():
 
 def test_bf16_records_on_device():
     """11 / 6. save + load and clone on bf16 batches: every restored row's `state` equals a full render of it, also over the steps after."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN, synth_scenario
     B, M = 64, 3
     scs = [synth_scenario(7700 + e, 200, 200) for e in range(B)]
@@ -363,7 +358,7 @@ def test_batched_ippo_on_bf16_observations(inference_dtype):
     """12. BatchedIPPO over a bf16 environment: the stored states are what the policy saw -- the stored log-probabilities are reproduced
     by rollout_logp on the stored bf16 states (tolerance of the float32 test of that property) -- then one roll_out + one update per
     charger with finite losses."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import BatchedIPPO, VecWRSN, synth_scenario
     torch.manual_seed(0); np.random.seed(0)
     B, M, G = 256, 3, 100

@@ -1,61 +1,19 @@
-"""prob_gp < 1 (Node.py:61: one random.random() per live node and second; packets only when the draw is below prob_gp) on
-the CPU: the unmodified HIP sources in the lockstep wavefront emulator of tests/emu, against the reference runs of
-tests/golden/prob_gp/ (tools/gen_prob_gp_golden.py) and against Python's own `random`."""
-import glob
+"""prob_gp < 1 (Node.py:61: one random.random() per live node and second; packets only when the draw is below prob_gp) :
+one body each, run here on the emulator (the unmodified HIP sources in the lockstep wavefront emulator of tests/emu) and by
+tests/test_prob_gp_gpu.py on the device: against the reference runs of tests/golden/prob_gp/ (tools/gen_prob_gp_golden.py), against Python's own `random` after
+every decision, and against the prob_gp == 1 kernels.  CPU only: launch modes on the emulator, the opt-in rules and the refusals."""
 import os
-import random
 
 import numpy as np
 import pytest
 import yaml
 
 from parity import check_decision
-
-PGP_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "prob_gp")
-PGP_NAMES = sorted(os.path.splitext(os.path.basename(f))[0] for f in glob.glob(os.path.join(PGP_DIR, "*.npz")))
+from sides import EmuSide, PGP_DIR, PGP_NAMES, load_fixture, python_mt_state, scenario_from_prob_gp
 
 
 def _load(name):
-    return np.load(os.path.join(PGP_DIR, name + ".npz"))
-
-
-def _scenario(z, seed=None, stochastic=True, prob_gp=None):
-    from multi_agent_rl_wrsn_amd.scenario import MC_SPEC_KEYS, NODE_SPEC_KEYS, Scenario
-    ns = {k: float(v) for k, v in zip(NODE_SPEC_KEYS, z["node_spec"])}
-    if prob_gp is not None:
-        ns["prob_gp"] = prob_gp
-    mc = {k: float(v) for k, v in zip(MC_SPEC_KEYS, z["mc_spec"])}
-    s = int(z["seed64"]) if seed is None else seed
-    if "seed64" not in z.files and seed is None:
-        s = int(z["seed"])
-    return Scenario(z["node_xy"], z["target_xy"], z["bs_xy"], ns, float(z["max_time"]), s, stochastic_packets=stochastic), mc
-
-
-def _emu(scenarios, mc, M, **kw):
-    from emu_env import EmuVec
-    return EmuVec(scenarios, mc, M, **kw)
-
-
-def _rng_state(ev, e=0):
-    from multi_agent_rl_wrsn_amd import _lib
-    st = ev.h.peek(_lib.PEEK_RNG_STATE)[e]
-    return [int(v) for v in st[:625]], int(st[625]) | (int(st[626]) << 32)
-
-
-def _python_state(seed, n):
-    r = random.Random(seed)
-    for _ in range(n):
-        r.random()
-    return list(r.getstate()[1])
-
-
-def _got(ev, e=0):
-    nd = ev.nodes(); m = ev.mcs()
-    return {"agent_id": int(ev.agent_id[e]), "now": float(ev.now[e]), "reward": float(ev.reward[e]), "terminal": bool(ev.terminal[e]),
-            "obs": ev.obs[e].astype(np.float64), "node_energy": nd["energy"][e], "node_cs": nd["cs"][e], "node_status": nd["status"][e],
-            "mc_energy": m["energy"][e], "mc_loc": np.stack([m["loc_x"][e], m["loc_y"][e]], 1), "mc_status": m["status"][e],
-            "mc_charging": m["type_charging"][e], "mc_nconn": m["n_conn"][e], "excl": m["excl"][e], "prev_minfit": m["prev_minfit"][e],
-            "min_fitness": float(ev.env_info()["min_fitness"][e]), "targets_active": ev.targets_active()[e]}
+    return load_fixture("prob_gp/" + name)[0]
 
 
 def test_fixtures_are_there_and_cover_what_they_should():
@@ -69,47 +27,43 @@ def test_fixtures_are_there_and_cover_what_they_should():
         assert os.path.getsize(os.path.join(PGP_DIR, n + ".npz")) < 1 << 20
 
 
-@pytest.mark.parametrize("seed", [0, 5, -5, -123456789, 2 ** 32, 2 ** 32 + 7, 2 ** 63 - 1, -2 ** 63])
-def test_rng_state_after_the_warm_up_is_pythons(hip_lib, seed):
+SEEDS = [0, 5, -5, -123456789, 2 ** 32, 2 ** 32 + 7, 2 ** 63 - 1, -2 ** 63]
+PGP1_NAMES = ["six_m3_bs_charge_ongrid", "redundant_m2_deaths", "hanoi1000n50_m2_map64", "redundant_m2_maxtime130"]
+
+
+def rng_state_after_the_warm_up_is_pythons(Side, seed):
     """random.seed(seed) followed by one draw per node and second of the warm-up (no node dies in it): word for word."""
     z = _load("six_m1_bs_charge_ongrid_p05")
-    sc, mc = _scenario(z, seed=seed)
-    ev = _emu([sc], mc, 1, map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]))
-    ev.reset()
-    words, n = _rng_state(ev)
-    assert n == int(z["rng_draws_reset"]) == sc.n_node * 100
-    assert words == _python_state(seed, n)
+    sc, mc = scenario_from_prob_gp(z, seed=seed)
+    side = Side([sc], mc, 1, map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]))
+    side.reset()
+    words, n = side.handle.rng_state()
+    assert n[0] == int(z["rng_draws_reset"]) == sc.n_node * 100
+    assert np.array_equal(words[0], python_mt_state(seed, int(n[0])))
     if seed == 5:
-        assert words == _python_state(-5, n)                 # random.seed takes abs(seed)
+        assert np.array_equal(words[0], python_mt_state(-5, int(n[0])))     # random.seed takes abs(seed)
+    side.close()
 
 
-@pytest.mark.parametrize("name", PGP_NAMES)
-def test_emulated_kernel_matches_prob_gp_fixture(hip_lib, name):
-    z = _load(name)
-    sc, mc = _scenario(z)
-    ev = _emu([sc], mc, int(z["num_agent"]), map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]))
-    ev.reset()
-    assert int(ev.agent_id[0]) == int(z["reset_agent"])
-    nd = ev.nodes()
+def kernel_matches_prob_gp_fixture(Side, name):
+    z, sc, mc = load_fixture("prob_gp/" + name)
+    seed = int(z["seed64"])
+    side = Side([sc], mc, int(z["num_agent"]), map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]))
+    side.reset()
+    assert side.rows()[0][0] == int(z["reset_agent"])
+    nd = side.handle.nodes()
     assert np.array_equal(nd["status"][0], z["reset_node_status"])
     assert np.max(np.abs(nd["energy"][0] - z["reset_node_energy"]) / z["reset_node_energy"]) < 1e-9
-    seed = int(z["seed64"]); py = random.Random(seed); taken = 0
-
-    def py_state(n):
-        nonlocal taken
-        for _ in range(n - taken):
-            py.random()
-        taken = n
-        return list(py.getstate()[1])
-    words, n = _rng_state(ev)
-    assert n == int(z["rng_draws_reset"]) and words == py_state(n)
+    words, n = side.handle.rng_state()
+    assert n[0] == int(z["rng_draws_reset"]) and np.array_equal(words[0], python_mt_state(seed, int(n[0])))
     noise = []
     for k in range(len(z["in_action"])):
-        ev.step([int(z["in_agent"][k])], z["in_action"][k][None])
+        side.step([int(z["in_agent"][k])], z["in_action"][k][None])
         if z["is_none"][k]:
-            assert int(ev.status[0]) == 1 and int(ev.agent_id[0]) == -1
+            agent, _, _, _, status = side.rows()[0]
+            assert status == 1 and agent == -1
             break
-        got = _got(ev)
+        got = side.decision()
         # agent and terminal flag exact; the simulated time to the 1e-9 of check_decision (the fast-forwarded charger sub-steps of
         # the prob_gp == 1 path are closed forms too: a few ulps)
         assert got["agent_id"] == int(z["agent_id"][k]) and got["terminal"] == bool(z["terminal"][k]), (name, k)
@@ -117,40 +71,57 @@ def test_emulated_kernel_matches_prob_gp_fixture(hip_lib, name):
         if z["terminal"][k]:
             break                                            # (node state, draws included, is frozen once the network is declared dead)
         assert np.array_equal(got["node_status"], z["node_status"][k]), (name, k)
-        words, n = _rng_state(ev)
-        assert n == int(z["rng_draws"][k]), (name, k, n, int(z["rng_draws"][k]))
-        assert words == py_state(n), (name, k)
+        words, n = side.handle.rng_state()
+        assert n[0] == int(z["rng_draws"][k]), (name, k, int(n[0]), int(z["rng_draws"][k]))
+        assert np.array_equal(words[0], python_mt_state(seed, int(n[0]))), (name, k, "generator words")
     # rewards that hang on the sign of a rounding residue of energyCS are far more common than with prob_gp 1: a node
     # that generated nothing for ten seconds keeps such a residue, and with prob_gp 0.1 most nodes do; each one was held to the
     # reference's algorithm on the product's own node state (parity._reward_depends_on_residue)
     assert len(noise) <= max(1, len(z["in_action"]) // 3), noise
+    side.close()
 
 
-@pytest.mark.parametrize("name", ["six_m3_bs_charge_ongrid", "redundant_m2_deaths", "hanoi1000n50_m2_map64", "redundant_m2_maxtime130"])
-def test_prob_gp_one_on_the_stochastic_kernels_is_bit_identical(hip_lib, name):
+def prob_gp_one_on_the_stochastic_kernels_is_bit_identical(Side, name):
     """An environment with prob_gp == 1 in a handle that runs the stochastic kernels (its neighbour has prob_gp 0.5) returns
     exactly what the plain handle returns, and its generator has taken one draw per live node and second."""
-    from conftest import load_golden
-    z = load_golden(name)
-    sc1, mc = _scenario(z, seed=int(z["seed"]), stochastic=False)
-    sc1s, _ = _scenario(z, seed=int(z["seed"]), stochastic=True)
-    other, _ = _scenario(_load("six_m1_bs_charge_ongrid_p05"))
+    z = load_fixture(name)[0]
+    sc1, mc = scenario_from_prob_gp(z, seed=int(z["seed"]), stochastic=False)
+    sc1s, _ = scenario_from_prob_gp(z, seed=int(z["seed"]), stochastic=True)
+    other = load_fixture("prob_gp/six_m1_bs_charge_ongrid_p05")[1]
     kw = dict(map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]))
     M = int(z["num_agent"])
-    a = _emu([sc1], mc, M, **kw); b = _emu([sc1s, other], mc, M, **kw)
+    a = Side([sc1], mc, M, **kw); b = Side([sc1s, other], mc, M, **kw)
     a.reset(); b.reset()
-    words, n = _rng_state(b, 0)
-    assert n == sc1.n_node * int(z["warm_up"]) and words == _python_state(int(z["seed"]), n)
+    words, n = b.handle.rng_state()
+    assert n[0] == sc1.n_node * int(z["warm_up"]) and np.array_equal(words[0], python_mt_state(int(z["seed"]), int(n[0])))
     for k in range(len(z["in_action"])):
         a.step([int(z["in_agent"][k])], z["in_action"][k][None])
         b.step([int(z["in_agent"][k]), -2], np.stack([z["in_action"][k], z["in_action"][k]]))
-        assert (a.agent_id[0], a.now[0], a.reward[0], a.terminal[0], a.status[0]) == (b.agent_id[0], b.now[0], b.reward[0], b.terminal[0], b.status[0]), (name, k)
-        assert np.array_equal(a.obs[0], b.obs[0])
-        na, nb = a.nodes(), b.nodes()
+        ra = a.rows()[0]
+        assert ra == b.rows()[0], (name, k)
+        assert np.array_equal(a.obs_row(0), b.obs_row(0))
+        na, nb = a.handle.nodes(), b.handle.nodes()
         for key in ("energy", "cs", "status", "level"):
             assert np.array_equal(na[key][0], nb[key][0][:sc1.n_node]), (name, k, key)
-        if a.terminal[0] or a.agent_id[0] < 0:
+        if ra[3] or ra[0] < 0:
             break
+    a.close(); b.close()
+
+
+# ---- the bodies above on the emulator (tests/test_prob_gp_gpu.py: on the device)
+@pytest.mark.parametrize("seed", SEEDS)
+def test_rng_state_after_the_warm_up_is_pythons(hip_lib, seed):
+    rng_state_after_the_warm_up_is_pythons(EmuSide, seed)
+
+
+@pytest.mark.parametrize("name", PGP_NAMES)
+def test_emulated_kernel_matches_prob_gp_fixture(hip_lib, name):
+    kernel_matches_prob_gp_fixture(EmuSide, name)
+
+
+@pytest.mark.parametrize("name", PGP1_NAMES)
+def test_prob_gp_one_on_the_stochastic_kernels_is_bit_identical(hip_lib, name):
+    prob_gp_one_on_the_stochastic_kernels_is_bit_identical(EmuSide, name)
 
 
 def _requests(ev, acts, budget=0, deadline_us=0, rounds=400):
@@ -192,13 +163,13 @@ def test_budgeted_and_time_sliced_launches_return_the_blocking_requests(hip_lib)
     """prob_gp 0.5 with nodes dying: a work budget or a launch deadline only changes the call a request appears in (the reward to
     round-off: a suspension splits the reward accumulation of a grid service in two)."""
     z = _load("redundant_m2_p05"); z2 = _load("redundant_rev_m2_p05")
-    scs = [_scenario(z)[0], _scenario(z2)[0], _scenario(z, seed=-11)[0]]
-    mc = _scenario(z)[1]
+    scs = [scenario_from_prob_gp(z)[0], scenario_from_prob_gp(z2)[0], scenario_from_prob_gp(z, seed=-11)[0]]
+    mc = scenario_from_prob_gp(z)[1]
     K = 14
     acts = np.random.RandomState(5).rand(K, 3, 3) * np.array([1.0, 1.0, 0.6])
-    h0, _ = _requests(_emu(scs, mc, 2), acts)
+    h0, _ = _requests(EmuSide(scs, mc, 2), acts)
     for kw in (dict(budget=300), dict(budget=4000, deadline_us=50), dict(deadline_us=30)):
-        h1, busy = _requests(_emu(scs, mc, 2), acts, rounds=20000, **kw)
+        h1, busy = _requests(EmuSide(scs, mc, 2), acts, rounds=20000, **kw)
         assert busy > 0, kw
         for e in range(len(scs)):
             assert len(h1[e]) == len(h0[e]), (kw, e)
@@ -249,7 +220,7 @@ def test_plain_call_still_refuses_prob_gp_below_one(hip_lib):
     from emu_env import emu_lib
     from multi_agent_rl_wrsn_amd import _lib
     z = _load("six_m1_bs_charge_ongrid_p05")
-    sc, mc = _scenario(z)
+    sc, mc = scenario_from_prob_gp(z)
     lib = emu_lib()
     h = _lib.RawHandle(lib, 1, sc.n_node, sc.n_target, 1, 100, 100.0)
     spec = (_lib.WrsnNodeSpec * 1)(); spec[0] = _lib.make_node_spec(sc.node_spec, sc.max_time)
@@ -268,5 +239,5 @@ def test_plain_call_still_refuses_prob_gp_below_one(hip_lib):
     rc = lib.wrsn_set_scenario_seeded(h._h, 0, 1, nxy.ctypes.data, txy.ctypes.data, bs.ctypes.data, None, None, spec, 1, C.byref(mcs), 0, seed.ctypes.data)
     assert rc == 0
     with pytest.raises(_lib.WrsnError):
-        h.peek(_lib.PEEK_RNG_STATE)
+        h.rng_state()
     h.close()

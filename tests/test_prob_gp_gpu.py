@@ -1,77 +1,28 @@
-"""prob_gp < 1 on a real MI355X: the stochastic kernels against the reference runs of tests/golden/prob_gp/, against Python's own
-`random`, against the prob_gp == 1 kernels, and through the launch machinery (budgets, time slices, the pipelined step call)."""
-import random
-
+"""prob_gp < 1 on a real MI355X: the bodies of tests/test_prob_gp.py on the device (the reference runs of tests/golden/prob_gp/, Python's
+own `random` after every decision, the prob_gp == 1 kernels), and at sizes the emulator cannot reach a mixed batch of 512, auto-reset
+episodes, and the launch machinery (budgets, time slices, the pipelined step call) at 4096 environments."""
 import numpy as np
 import pytest
 
-from parity import check_decision
-from test_prob_gp import PGP_NAMES, _load, _scenario
+import test_prob_gp as body
+from sides import VecSide, load_fixture, need_gpu, python_mt_state, scenario_from_prob_gp
 
 pytestmark = pytest.mark.gpu
 
 
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch
+@pytest.mark.parametrize("seed", body.SEEDS)
+def test_rng_state_after_the_warm_up_is_pythons(seed):
+    body.rng_state_after_the_warm_up_is_pythons(VecSide, seed)
 
 
-def _rng(env):
-    from multi_agent_rl_wrsn_amd import _lib
-    st = env._h.peek(_lib.PEEK_RNG_STATE)
-    return st[:, :625], st[:, 625].astype(np.int64) | (st[:, 626].astype(np.int64) << 32)
-
-
-def _python_state(seed, n):
-    r = random.Random(seed)
-    for _ in range(n):
-        r.random()
-    return np.array(r.getstate()[1], dtype=np.uint32)
-
-
-def _got(env, r, e=0):
-    nd = env.nodes(); m = env.mcs()
-    return {"agent_id": int(r["agent_id"][e]), "now": float(r["now"][e]), "reward": float(r["reward"][e]), "terminal": bool(r["terminal"][e]),
-            "obs": r["state"][e].double().cpu().numpy(), "node_energy": nd["energy"][e], "node_cs": nd["cs"][e], "node_status": nd["status"][e],
-            "mc_energy": m["energy"][e], "mc_loc": np.stack([m["loc_x"][e], m["loc_y"][e]], 1), "mc_status": m["status"][e],
-            "mc_charging": m["type_charging"][e], "mc_nconn": m["n_conn"][e], "excl": m["excl"][e], "prev_minfit": m["prev_minfit"][e],
-            "min_fitness": float(env.env_info()["min_fitness"][e]), "targets_active": env.targets_active()[e]}
-
-
-@pytest.mark.parametrize("name", PGP_NAMES)
+@pytest.mark.parametrize("name", body.PGP_NAMES)
 def test_hip_matches_prob_gp_fixture(name):
-    torch = _torch()
-    from multi_agent_rl_wrsn_amd import VecWRSN
-    z = _load(name)
-    sc, mc = _scenario(z)
-    env = VecWRSN([sc], mc, int(z["num_agent"]), map_size=int(z["map_size"]), warm_up_time=float(z["warm_up"]))
-    r = env.reset(); env.synchronize()
-    assert int(r["agent_id"][0]) == int(z["reset_agent"])
-    words, n = _rng(env)
-    assert n[0] == int(z["rng_draws_reset"]) and np.array_equal(words[0], _python_state(int(z["seed64"]), int(n[0])))
-    noise = []
-    for k in range(len(z["in_action"])):
-        r = env.step(torch.tensor([int(z["in_agent"][k])], dtype=torch.int32), torch.tensor(z["in_action"][k][None]))
-        env.synchronize()
-        if z["is_none"][k]:
-            assert int(r["status"][0]) == 1
-            break
-        got = _got(env, r)
-        assert got["agent_id"] == int(z["agent_id"][k]) and got["terminal"] == bool(z["terminal"][k]), (name, k)
-        check_decision(z, k, got, where=name, noise=noise)
-        if z["terminal"][k]:
-            break
-        assert np.array_equal(got["node_status"], z["node_status"][k]), (name, k)
-        assert int(_rng(env)[1][0]) == int(z["rng_draws"][k]), (name, k)
-    words, n = _rng(env)
-    if not z["terminal"][min(k, len(z["terminal"]) - 1)]:
-        assert np.array_equal(words[0], _python_state(int(z["seed64"]), int(n[0])))
-    # rewards that hang on the sign of a rounding residue of energyCS are far more common than with prob_gp 1: a node
-    # that generated nothing for ten seconds keeps such a residue, and with prob_gp 0.1 most nodes do; each one was held to the
-    # reference's algorithm on the product's own node state (parity._reward_depends_on_residue)
-    assert len(noise) <= max(1, len(z["in_action"]) // 3), noise
-    env.close()
+    body.kernel_matches_prob_gp_fixture(VecSide, name)
+
+
+@pytest.mark.parametrize("name", body.PGP1_NAMES)
+def test_prob_gp_one_on_the_stochastic_kernels_is_bit_identical(name):
+    body.prob_gp_one_on_the_stochastic_kernels_is_bit_identical(VecSide, name)
 
 
 def _mixed_batch(B, N=200):
@@ -90,16 +41,16 @@ def _mixed_batch(B, N=200):
 def test_mixed_batch_of_512_environments():
     """512 synthetic 200-node networks, prob_gp 0 / 0.3 / 0.7 / 1, mixed seeds: the generator after the warm-up (no node dies in it) is
     Python's after N x 100 draws; prob_gp 0 never lowers a node's energy; prob_gp 1 equals the plain handle bit for bit."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN
     B, K, M = 512, 10, 3
     scs = _mixed_batch(B)
     env = VecWRSN(scs, None, M)
     r = env.reset(); env.synchronize()
-    words, n = _rng(env)
+    words, n = env._h.rng_state()
     for e in range(B):
         assert n[e] == 200 * 100, e
-        assert np.array_equal(words[e], _python_state(scs[e].seed, 200 * 100)), e
+        assert np.array_equal(words[e], python_mt_state(scs[e].seed, 200 * 100)), e
     one = [e for e in range(B) if e % 4 == 3]
     from multi_agent_rl_wrsn_amd.scenario import Scenario
     plain = VecWRSN([Scenario(scs[e].node_xy, scs[e].target_xy, scs[e].bs_xy, scs[e].node_spec, scs[e].max_time, scs[e].seed) for e in one], None, M)
@@ -126,12 +77,12 @@ def test_mixed_batch_of_512_environments():
 def test_auto_reset_episodes_replay_bit_for_bit():
     """Every reset restores the generator with the rest of the post-warm-up snapshot (NetworkIO.py:22-24): the episodes of an environment
     driven by the same actions are the same, deaths and packet draws included."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN
-    z = _load("redundant_m2_p05")
-    scs = [_scenario(z, seed=s)[0] for s in (3, 4, 5, 6)] * 16
+    z = load_fixture("prob_gp/redundant_m2_p05")[0]
+    scs = [scenario_from_prob_gp(z, seed=s)[0] for s in (3, 4, 5, 6)] * 16
     B = len(scs)
-    env = VecWRSN(scs, _scenario(z)[1], 2, auto_reset=True)
+    env = VecWRSN(scs, scenario_from_prob_gp(z)[1], 2, auto_reset=True)
     r = env.reset(); env.synchronize()
     acts = torch.tensor(np.random.RandomState(2).rand(400, 3) * np.array([1.0, 1.0, 0.6]))
     step_no = np.zeros(B, dtype=int)                         # decisions into the current episode
@@ -161,7 +112,7 @@ def test_auto_reset_episodes_replay_bit_for_bit():
 def test_launch_modes_return_the_blocking_requests_at_4096():
     """4096 environments, prob_gp 0.5: budgeted launches, time slices and the pipelined step call (the default for a call that renders,
     up to two rounds of the wave slots; here the pipeline runs over the first 1 024) report the requests of blocking launches."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import DEFAULT_NODE_SPEC, VecWRSN, synth_scenario
     spec = dict(DEFAULT_NODE_SPEC); spec["prob_gp"] = 0.5
     uniq = [synth_scenario(23000 + u, 200, 200, node_spec=spec, stochastic_packets=True) for u in range(64)]

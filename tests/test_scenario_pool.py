@@ -5,51 +5,28 @@ import numpy as np
 import pytest
 
 from parity import check_decision, close
-from test_env_records import _fixture, _got, _peeks, _python_state, _row, _same
+from test_env_records import _peeks, _row, _same
+from sides import EmuSide, aligned, load_fixture, python_mt_state
 
 SENT_I, SENT_F = -77, -12345.5                                # sentinels of rows that must stay untouched
 
 
-class PoolEmu:
-    """EmuVec for a stated geometry (n_node / n_target of the handle, not the largest of its scenarios): what one pool needs of the
+def PoolEmu(scenarios, mc, M, N, T, **kw):
+    """An EmuSide for a stated geometry (n_node / n_target of the handle, not the largest of its scenarios): what one pool needs of the
     handles its records come from and go to."""
-
-    def __new__(cls, scenarios, mc, M, N, T, **kw):
-        from emu_env import EmuVec
-
-        class _Sized(EmuVec):
-            def __init__(self, scenarios, mc, M, N, T, map_size=100, warm_up_time=100.0):
-                from emu_env import emu_lib
-                from multi_agent_rl_wrsn_amd import _lib
-                self.B, self.N, self.T, self.M, self.G = len(scenarios), N, T, M, map_size
-                self.h = _lib.RawHandle(emu_lib(), self.B, N, T, M, map_size, warm_up_time, 0, 0, 0)
-                self.h.set_scenarios(scenarios, mc)
-                self.h.set_obs_reuse(True)
-                B, G = self.B, self.G
-                self.agent_id = np.full(B, -1, dtype=np.int32); self.reward = np.zeros(B); self.terminal = np.zeros(B, dtype=np.uint8)
-                self.now = np.zeros(B); self.status = np.zeros(B, dtype=np.int32); self.obs = np.zeros((B, 4, G, G), dtype=np.float32)
-
-        return _Sized(scenarios, mc, M, N, T, **kw)
-
-
-def _aligned(shape):
-    """A zeroed uint8 array whose first byte is 16-byte aligned (device records are)."""
-    n = int(np.prod(shape))
-    buf = np.zeros(n + 16, dtype=np.uint8)
-    off = (-buf.ctypes.data) % 16
-    return buf[off:off + n].reshape(shape)
+    return EmuSide(scenarios, mc, M, n_node=N, n_target=T, **kw)
 
 
 def _record(ev, e=0):
     """The record of environment e with its pending request."""
-    rec = _aligned((1, ev.h.env_record_bytes()))
+    rec = aligned((1, ev.h.env_record_bytes()))
     p = ev._ptrs(False); p.pop("obs")
     ev.h.save_envs(np.asarray([e], dtype=np.int32), rec.ctypes.data, **p)
     return rec
 
 
 def _pool(records):
-    out = _aligned((len(records), records[0].shape[1]))
+    out = aligned((len(records), records[0].shape[1]))
     for i, r in enumerate(records):
         out[i] = r[0]
     return out
@@ -63,20 +40,13 @@ def _pool_reset(ev, mask=None, index=None, ids=None, with_obs=True):
 
 
 def _pool_info(ev):
-    from multi_agent_rl_wrsn_amd import _lib
-    return ev.h.peek(_lib.PEEK_POOL)
+    """[B, 2]: the pool record every environment runs, and its swaps."""
+    info = ev.pool_info()
+    return np.stack([info["record"], info["swaps"]], 1)
 
 
 def _fill_sentinels(ev):
     ev.agent_id[:] = SENT_I; ev.status[:] = SENT_I; ev.reward[:] = SENT_F; ev.now[:] = SENT_F; ev.terminal[:] = 99; ev.obs[:] = SENT_F
-
-
-def _got_cut(ev, e, sc):
-    got = _got(ev, e)
-    for key in ("node_energy", "node_cs", "node_status"):
-        got[key] = got[key][:sc.n_node]
-    got["targets_active"] = got["targets_active"][:sc.n_target]
-    return got
 
 
 POOL_FIXTURES = ("hanoi1000n50_m2_cap9000_detour", "sonla1000n50_m2_s4", "redundant_m2_deaths")
@@ -88,7 +58,7 @@ def test_terminal_rows_restart_in_the_drawn_fixture(hip_lib):
     rows, by the record pool_draw names, and the episode that follows is the drawn fixture's, decision by decision."""
     from multi_agent_rl_wrsn_amd import pool_draw
     N, T, M, P = 82, 56, 2, 3
-    fx = [_fixture(n) for n in POOL_FIXTURES]
+    fx = [load_fixture(n) for n in POOL_FIXTURES]
     assert [len(z["in_action"]) for z, _, _ in fx] == [8, 7, 16]
     assert len({tuple(mc.values()) for _, _, mc in fx}) > 1 and len({sc.n_node for _, sc, _ in fx}) == 3
     recs = []
@@ -142,7 +112,7 @@ def test_terminal_rows_restart_in_the_drawn_fixture(hip_lib):
                 assert _row(ev, e) == before[e]
             else:
                 z, sc, _ = fx[cur[e]]
-                check_decision(z, k[e], _got_cut(ev, e, sc), where="%s (env %d, episode %d)" % (POOL_FIXTURES[cur[e]], e, episodes[e]), noise=noise)
+                check_decision(z, k[e], ev.decision(e, sc), where="%s (env %d, episode %d)" % (POOL_FIXTURES[cur[e]], e, episodes[e]), noise=noise)
                 checked += 1
                 if z["terminal"][k[e]]:
                     pending[e] = True; episodes[e] += 1
@@ -213,8 +183,8 @@ def test_masked_pool_reset_equals_a_load(hip_lib):
 def test_stochastic_pool_record_brings_its_generator(hip_lib):
     from multi_agent_rl_wrsn_amd import _lib
     name = "prob_gp/redundant_m2_p05"
-    z, sc, mc = _fixture(name)
-    _, sc2, _ = _fixture("prob_gp/redundant_rev_m2_p05")
+    z, sc, mc = load_fixture(name)
+    _, sc2, _ = load_fixture("prob_gp/redundant_rev_m2_p05")
     M = int(z["num_agent"])
     src = PoolEmu([sc], mc, M, 30, 56)
     src.reset()
@@ -232,13 +202,12 @@ def test_stochastic_pool_record_brings_its_generator(hip_lib):
     noise = []
     for k in range(len(z["in_action"])):
         ev.step([-2, int(z["in_agent"][k])], np.stack([z["in_action"][k]] * 2))
-        check_decision(z, k, _got_cut(ev, 1, sc), where=name, noise=noise)
+        check_decision(z, k, ev.decision(1, sc), where=name, noise=noise)
         if z["terminal"][k]:
             break
-        st = ev.h.peek(_lib.PEEK_RNG_STATE)[1]
-        n = int(st[625]) | (int(st[626]) << 32)
-        assert n == int(z["rng_draws"][k]), k
-        assert [int(v) for v in st[:625]] == _python_state(int(z["seed64"]), n), k
+        words, n = ev.h.rng_state()
+        assert n[1] == int(z["rng_draws"][k]), k
+        assert np.array_equal(words[1], python_mt_state(int(z["seed64"]), int(n[1]))), k
     assert z["terminal"][k]
     assert len(noise) <= max(1, len(z["in_action"]) // 3), noise
 
@@ -246,10 +215,10 @@ def test_stochastic_pool_record_brings_its_generator(hip_lib):
 def test_pool_refusals_leave_the_handle_working(hip_lib):
     from emu_env import emu_lib
     from multi_agent_rl_wrsn_amd import _lib
-    _, sc, mc = _fixture("redundant_m2_deaths")             # 30 nodes: NP 64
-    _, big, _ = _fixture("hanoi1000n50_m3_s1")              # 82 nodes: NP 128
-    _, six, _ = _fixture("six_m1_bs_charge_ongrid")
-    _, gsc, _ = _fixture("prob_gp/redundant_m2_p05")
+    _, sc, mc = load_fixture("redundant_m2_deaths")             # 30 nodes: NP 64
+    _, big, _ = load_fixture("hanoi1000n50_m3_s1")              # 82 nodes: NP 128
+    _, six, _ = load_fixture("six_m1_bs_charge_ongrid")
+    _, gsc, _ = load_fixture("prob_gp/redundant_m2_p05")
     ev = PoolEmu([sc, six, sc], mc, 2, 30, 56)
     ev.reset()
     pool = _pool([_record(ev, 0), _record(ev, 1)])

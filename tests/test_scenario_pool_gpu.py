@@ -4,16 +4,13 @@ BatchedIPPO over a pooled environment."""
 import numpy as np
 import pytest
 
+from multi_agent_rl_wrsn_amd import _lib
+from sides import decision_dict, need_gpu
+
 pytestmark = pytest.mark.gpu
 
 FIELDS = ("agent_id", "reward", "terminal", "now", "status")
 POOL_FIXTURES = ("hanoi1000n50_m2_cap9000_detour", "sonla1000n50_m2_s4", "redundant_m2_deaths")
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a HIP device"
-    return torch
 
 
 def _rows(env):
@@ -23,19 +20,9 @@ def _rows(env):
     return [(int(aid[e]), float(now[e]), float(rw[e]), int(term[e]), int(st[e])) for e in range(env.num_env)]
 
 
-def _got(env, e, sc):
-    nd = env.nodes(); m = env.mcs(); n = sc.n_node
-    return {"agent_id": int(env.agent_id[e]), "now": float(env.now[e]), "reward": float(env.reward[e]), "terminal": bool(env.terminal[e]),
-            "obs": env.state[e].double().cpu().numpy(), "node_energy": nd["energy"][e][:n], "node_cs": nd["cs"][e][:n],
-            "node_status": nd["status"][e][:n], "mc_energy": m["energy"][e], "mc_loc": np.stack([m["loc_x"][e], m["loc_y"][e]], 1),
-            "mc_status": m["status"][e], "mc_charging": m["type_charging"][e], "mc_nconn": m["n_conn"][e], "excl": m["excl"][e],
-            "prev_minfit": m["prev_minfit"][e], "min_fitness": float(env.env_info()["min_fitness"][e]),
-            "targets_active": env.targets_active()[e][:sc.n_target]}
-
-
 def _same_as_rounded(env16, env32, rows):
     """Request rows bit for bit, bfloat16 observations = the float32 ones rounded to nearest even."""
-    torch = _torch()
+    torch = need_gpu()
     for k in FIELDS:
         assert torch.equal(getattr(env16, k), getattr(env32, k)), k
     if len(rows):
@@ -46,7 +33,7 @@ def _same_as_rounded(env16, env32, rows):
 def test_terminal_rows_restart_in_the_drawn_fixture_f32_and_bf16():
     """tests/test_scenario_pool.py::test_terminal_rows_restart_in_the_drawn_fixture through VecWRSN.step on the device: a float32 batch
     held to the reference fixtures, a bfloat16 batch in lockstep held to the float32 one."""
-    torch = _torch()
+    torch = need_gpu()
     from conftest import load_golden
     from multi_agent_rl_wrsn_amd import VecWRSN, build_scenario_pool, pool_draw
     from multi_agent_rl_wrsn_amd.scenario import scenario_from_golden
@@ -101,7 +88,7 @@ def test_terminal_rows_restart_in_the_drawn_fixture_f32_and_bf16():
                 assert rows[e] == before[e]
             else:
                 z, sc, _ = fx[cur[e]]
-                check_decision(z, k[e], _got(ev, e, sc), where="%s (env %d, episode %d)" % (POOL_FIXTURES[cur[e]], e, episodes[e]), noise=noise)
+                check_decision(z, k[e], decision_dict(ev._result(), ev.state[e].double().cpu().numpy(), ev._h, e, sc), where="%s (env %d, episode %d)" % (POOL_FIXTURES[cur[e]], e, episodes[e]), noise=noise)
                 checked += 1
                 if z["terminal"][k[e]]:
                     pending[e] = True; episodes[e] += 1
@@ -117,7 +104,7 @@ def test_terminal_rows_restart_in_the_drawn_fixture_f32_and_bf16():
 def test_masked_pool_reset_equals_a_load(obs_dtype):
     """VecWRSN.pool_reset(mask, index) against VecWRSN.load_envs of the same records into the same rows of a twin, more than one
     64-row strip of the select kernel and a batch that is no multiple of it; the bfloat16 rows are the float32 rows rounded."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN, build_scenario_pool, synth_scenario
     B, M, P, G = 150, 2, 5, 20
     own = [synth_scenario(31 + e % 7, 60, 40) for e in range(B)]
@@ -155,7 +142,7 @@ def test_masked_pool_reset_equals_a_load(obs_dtype):
     assert bool((a.state[u].float() == torch.tensor(-12345.5).to(a.state.dtype).float()).all())
     for name, pa in a.nodes().items():
         assert np.array_equal(pa, b.nodes()[name]), name
-    assert np.array_equal(a._h.peek(5), b._h.peek(5)) and np.array_equal(a._h.peek(6), b._h.peek(6))
+    assert np.array_equal(a._h.peek(_lib.PEEK_MC), b._h.peek(_lib.PEEK_MC)) and np.array_equal(a._h.peek(_lib.PEEK_ENV), b._h.peek(_lib.PEEK_ENV))
     info = a.pool_info()
     assert np.array_equal(info["record"][sel], index[sel]) and np.array_equal(info["swaps"], mask.astype(np.int32))
     assert np.array_equal(info["record"][unsel], [-1] * len(unsel)) and np.array_equal(b.pool_info()["record"], [-1] * B)
@@ -194,7 +181,7 @@ def _pooled_batch(B, P, seed, own_seed=13000, pool_seed=13100, M=3, **kw):
 def _drive_pooled(env, acts, K, rounds=4000):
     """Per environment its first K requests (status-3 rows included) of a run in which its j-th request that asks for an action gets
     acts[j, e] (a status-4 row's action is not looked at, so it is not used up), and the pool record of each of its swaps."""
-    torch = _torch()
+    torch = need_gpu()
     B = env.num_env
     j = np.zeros(B, dtype=int); busy = env.status.cpu().numpy() == 4
     hist = [[] for _ in range(B)]; recs = [[] for _ in range(B)]
@@ -228,7 +215,7 @@ def test_pooled_auto_reset_under_every_launch_mode(mode, monkeypatch):
     """B = 512 (the smallest batch the pipeline takes) 50-node environments over a pool of 16, random actions, against a blocking pooled
     twin given the same action for the same decision: agent, time, terminal and the sequence of pool records identical, rewards to the
     tolerance the launch-mode tests of test_gpu_parity hold a budgeted or time-sliced run to."""
-    _torch()
+    need_gpu()
     from multi_agent_rl_wrsn_amd import pool_draw
     B, P, K, seed = 512, 16, 48, 7
     kw = {"budget": dict(step_budget=1250), "pipeline": dict(step_budget=1250), "deadline": dict(step_deadline_us=100)}[mode]
@@ -254,7 +241,7 @@ def test_pooled_auto_reset_under_every_launch_mode(mode, monkeypatch):
 
 
 def test_masked_swap_of_a_row_in_flight_drops_the_step():
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN
     B, P = 64, 4
     env, _, pool_scs, _ = _pooled_batch(B, P, 1, step_budget=150)
@@ -294,7 +281,7 @@ def test_masked_swap_of_a_row_in_flight_drops_the_step():
 def test_episode_after_a_swap_is_that_scenarios_episode():
     """Blocking mode: every request of the first episode after an environment's first swap is bit-identical to a fresh handle built
     from the drawn scenario with wrsn_set_scenario + reset and given the same actions."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import VecWRSN, pool_draw
     B, P, K, seed = 32, 8, 48, 5
     env, _, pool_scs, _ = _pooled_batch(B, P, seed, map_size=20)
@@ -346,7 +333,7 @@ def _conn_bound(records):
 def test_denser_pool_record_gets_its_launch_configuration():
     """A pool whose network needs longer connected-node lists than any scenario the handle was built with: wrsn_pool_set fits the launch
     configuration, and the swapped environments step to the requests of a fresh handle of that scenario."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import DEFAULT_NODE_SPEC, VecWRSN, build_scenario_pool, synth_scenario
     B, M = 6, 3
     sparse = [synth_scenario(14000 + e, 100, 60) for e in range(B)]
@@ -378,7 +365,7 @@ def test_rollout_bookkeeping_over_a_pooled_batch():
     """TransitionBuffers over a pooled batch against a host-side shadow of the run: every stored transition belongs to one episode of
     one pool record (a charger's action of the episode before a swap completes nothing), and the rollout table counts every terminal
     return, because a swapped environment keeps its own roll[]."""
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import TransitionBuffers
     B, P, M, K = 16, 4, 3, 60
     env, _, _, _ = _pooled_batch(B, P, 3, map_size=20)
@@ -413,7 +400,7 @@ def test_rollout_bookkeeping_over_a_pooled_batch():
 
 
 def test_batched_ippo_rolls_out_over_a_pooled_batch():
-    torch = _torch()
+    torch = need_gpu()
     from multi_agent_rl_wrsn_amd import BatchedIPPO
     torch.manual_seed(0); np.random.seed(0)
     B, M, G = 64, 3, 16
