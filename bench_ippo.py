@@ -36,13 +36,16 @@ def main():
     ap.add_argument("--infer-chunk", type=int, default=512)
     ap.add_argument("--inference-dtype", default=None, choices=[None, "bf16", "fp16"], help="reduced-precision roll-out inference (update stays float32)")
     ap.add_argument("--obs-dtype", default="float32", choices=["float32", "bfloat16"], help="observation format of the environment and the roll-out buffers")
+    ap.add_argument("--policy", default="image", choices=["image", "entity"], help="image: UNet / CNN critic on the 4 x G x G observation (default); "
+                    "entity: the set policy on entity rows, no image rendered (VecWRSN(render=False, entities=True), BatchedEntityIPPO)")
+    ap.add_argument("--report-updates", action="store_true", help="add peak device memory and the statistics of every update (first minibatch included) to the line")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:       # launcher-free multi-rank entry: before this process touches torch or the GPU
         from multi_agent_rl_wrsn_amd.sharding import launch_ranks
         raise SystemExit(launch_ranks(args.gpus, [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]))
     import numpy as np
     import torch
-    from multi_agent_rl_wrsn_amd import BatchedIPPO, RolloutStats, VecWRSN, init_distributed, synth_scenario
+    from multi_agent_rl_wrsn_amd import BatchedEntityIPPO, BatchedIPPO, RolloutStats, VecWRSN, init_distributed, synth_scenario
     rank, world, local_rank = init_distributed()
     if world != args.gpus and not (args.gpus == 1 and "WORLD_SIZE" in os.environ):      # torchrun without --gpus: WORLD_SIZE rules
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
@@ -55,15 +58,35 @@ def main():
     dev = torch.device("cuda", local_rank)
     torch.cuda.set_device(dev)
     B, N, M = args.envs, args.nodes, 3
-    env = VecWRSN([synth_scenario(rank * B + e, N, N) for e in range(B)], None, M, auto_reset=True, step_budget=args.step_budget, device=str(dev),
-                  reuse_obs=True, obs_dtype=args.obs_dtype)                             # BatchedIPPO only reads the state tensor (index_select / copies)
-    algo = BatchedIPPO(dict(batch_size=args.batch_size, minibatch_size=args.minibatch_size, n_updates_per_iteration=args.updates), env,
-                       capacity=max(2 * args.batch_size, 4096), infer_chunk=args.infer_chunk, inference_dtype=args.inference_dtype,
-                       min_bucket=args.infer_chunk)           # ONE batch shape for every inference pass: MIOpen searches its convolution kernels per shape (seconds each)
+    entity = args.policy == "entity"
+    updates = []                                               # --report-updates: every row train() logs, with the first minibatch's statistics
+    ppo_args = dict(batch_size=args.batch_size, minibatch_size=args.minibatch_size, n_updates_per_iteration=args.updates)
+    if entity:
+        env = VecWRSN([synth_scenario(rank * B + e, N, N) for e in range(B)], None, M, auto_reset=True, step_budget=args.step_budget, device=str(dev),
+                      render=False, entities=True)             # no image at all: 6.6 KB of entity rows per request
+        algo = BatchedEntityIPPO(ppo_args, env, capacity=max(2 * args.batch_size, 4096), infer_chunk=args.infer_chunk, min_bucket=args.infer_chunk)
+    else:
+        env = VecWRSN([synth_scenario(rank * B + e, N, N) for e in range(B)], None, M, auto_reset=True, step_budget=args.step_budget, device=str(dev),
+                      reuse_obs=True, obs_dtype=args.obs_dtype)                             # BatchedIPPO only reads the state tensor (index_select / copies)
+        algo = BatchedIPPO(ppo_args, env,
+                           capacity=max(2 * args.batch_size, 4096), infer_chunk=args.infer_chunk, inference_dtype=args.inference_dtype,
+                           min_bucket=args.infer_chunk)           # ONE batch shape for every inference pass: MIOpen searches its convolution kernels per shape (seconds each)
+    if args.report_updates:                                    # the statistics of the first minibatch of every update: the weights the roll-out ran with
+        first, inner = {}, algo.minibatch_loss
+
+        def minibatch_loss(id, batch, mb):
+            res = inner(id, batch, mb)
+            first.setdefault(id, dict(approx_kl=float(res[4]), clipfrac=float(res[5])))
+            return res
+        algo.minibatch_loss = minibatch_loss
+        algo.log = lambda row: updates.append(dict(row, first_minibatch=first.pop(row["agent"], {})))
     if args.warmup_iters > 0:
         algo.train(args.warmup_iters - 1)
         for k in algo.timers: algo.timers[k] = 0 if isinstance(algo.timers[k], int) else 0.0
+        del updates[:]
     torch.cuda.synchronize(dev)
+    if args.report_updates:
+        torch.cuda.reset_peak_memory_stats(dev)
     c0 = env.counters(); t0 = time.perf_counter()
     rows = algo.train(args.iters - 1)                          # train() runs iterations 0..n inclusive like the reference's loop (IPPO.py:220)
     torch.cuda.synchronize(dev)
@@ -90,6 +113,12 @@ def main():
            "env_steps_per_s_environment_only": steps / max(t["env_s"], 1e-9), "env_steps_per_s_rollout": steps / max(t["env_s"] + t["policy_s"] + t["glue_s"], 1e-9),
            "env_steps_per_s_with_training": steps / wall, "transitions_per_agent": algo.buffers.counts(),
            "last_rows": rows[-M:], "dtype": "f32 policy / f64 physics", "data": "synthetic"}
+    if entity:
+        out["config"]["workload"] = "%d envs x %d nodes x %d MC, set actor + critic per charger on entity rows, 3-vector actions, batch %d / minibatch %d / %d epochs" % (
+            B, N, M, args.batch_size, args.minibatch_size, args.updates)
+        out["config"]["policy"] = "float32, entity rows, no image"
+    if args.report_updates:
+        out["peak_memory_bytes"] = int(torch.cuda.max_memory_allocated(dev)); out["updates"] = updates
     print(json.dumps(out, default=float), flush=True)
     if dist: dist.destroy_process_group()
 

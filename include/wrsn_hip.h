@@ -226,6 +226,11 @@ typedef struct wrsn_transition_buffers {
     int32_t *env;             /* [M, capacity]           environment of the transition */
     int32_t *count;           /* [M] */
 } wrsn_transition_buffers;
+/* ENTITY ROWS.  The same struct serves wrsn_rollout_record_entities / wrsn_rollout_collect_entities (declared after wrsn_entity_out):
+ * a stored state is then one packed float32 row of R = 8 N + 12 M + 8 elements (N = cfg.n_node) -- node [N][8], then mc [M][12], then
+ * env [8], as wrsn_entity_out lays them out -- and
+ *   pend_state [B, M, R]      state, next_state [M, capacity, R]      float32 whatever wrsn_set_obs_format says, 16-byte aligned;
+ * every other member is as above.  Each part is a multiple of 16 bytes, so every row and every part boundary is 16-byte aligned. */
 
 /* The chargers named by agent_id (DEVICE int32 [B], < 0: row skipped) are about to be given `action` (DEVICE float
  * [B, action_elems], the policy's raw output) chosen with log-probability logp (DEVICE float [B]) on observation obs (DEVICE
@@ -282,6 +287,24 @@ int wrsn_set_entity_out(wrsn_t *h, const wrsn_entity_out *ent);
 /* Entity rows for arbitrary agents (DEVICE int32 [B], < 0 = skip) into `ent`, like wrsn_render for the image; the registered buffers
  * are neither needed nor touched.  Asynchronous on the handle's stream. */
 int wrsn_entities(wrsn_t *h, const int32_t *agent_id, const wrsn_entity_out *ent);
+
+/* Roll-out bookkeeping on ENTITY rows: wrsn_rollout_record / wrsn_rollout_collect with the packed entity row (see
+ * wrsn_transition_buffers) in place of the image.  `ent` names the entity buffers the rows are read from; NULL means the buffers
+ * registered with wrsn_set_entity_out.  The semantics are those of the image calls, statement for statement: record skips rows with
+ * agent_id < 0; collect skips rows the last environment launch left untouched or in flight, discards what is pending for terminal and
+ * (auto-)reset rows, appends one transition for a completed WRSN.step whose charger has a pending action; count keeps counting past
+ * `capacity` and the excess is not stored; reward is rounded to float32, now and the environment index are stored.
+ * out->obs may be NULL (entity-only batches: VecWRSN(render=False, entities=True)).
+ * consume != 0: the row's request is consumed, as by wrsn_rollout_collect -- a second collect after the same launch appends nothing.
+ * consume == 0: it is left, so that one launch can feed both kinds of buffers: a caller that keeps image AND entity buffers calls
+ * wrsn_rollout_collect_entities(consume = 0) FIRST and wrsn_rollout_collect SECOND.
+ * WRSN_ERR_ARG, with the handle and every buffer untouched: ent == NULL and nothing registered; node, mc or env NULL or not 16-byte
+ * aligned; pend_state, state or next_state NULL or not 16-byte aligned; agent_id, action or logp NULL (record); out->agent_id, reward,
+ * terminal, now or status NULL (collect).  Both run on the handle's stream, into which a pipelined step has joined: no extra ordering. */
+int wrsn_rollout_record_entities(wrsn_t *h, const wrsn_transition_buffers *buf, const int32_t *agent_id, const float *action,
+                                 const float *logp, const wrsn_entity_out *ent);
+int wrsn_rollout_collect_entities(wrsn_t *h, const wrsn_transition_buffers *buf, const wrsn_step_out *out,
+                                  const wrsn_entity_out *ent, int32_t consume);
 
 /* Copy internal state to HOST memory (parity tests, `net` / `agents` views).  Synchronises. */
 int wrsn_peek(wrsn_t *h, int32_t what, void *dst);

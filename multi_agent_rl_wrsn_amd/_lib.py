@@ -37,7 +37,7 @@ ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max"
 
 # every entry point include/wrsn_hip.h declares
 EXPORTS = ("wrsn_create", "wrsn_destroy", "wrsn_set_stream", "wrsn_set_scenario", "wrsn_set_scenario_seeded", "wrsn_reset", "wrsn_step",
-           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
+           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
            "wrsn_clone_envs", "wrsn_pool_set", "wrsn_pool_reset", "wrsn_synth_network",
            "wrsn_last_error",
            "wrsn_version")
@@ -111,6 +111,10 @@ def bind(lib):
     lib.wrsn_rollout_record.restype = C.c_int
     lib.wrsn_rollout_collect.argtypes = [vp, C.POINTER(WrsnTransitionBuffers), C.POINTER(WrsnStepOut)]
     lib.wrsn_rollout_collect.restype = C.c_int
+    lib.wrsn_rollout_record_entities.argtypes = [vp, C.POINTER(WrsnTransitionBuffers), vp, vp, vp, C.POINTER(WrsnEntityOut)]
+    lib.wrsn_rollout_record_entities.restype = C.c_int
+    lib.wrsn_rollout_collect_entities.argtypes = [vp, C.POINTER(WrsnTransitionBuffers), C.POINTER(WrsnStepOut), C.POINTER(WrsnEntityOut), C.c_int32]
+    lib.wrsn_rollout_collect_entities.restype = C.c_int
     lib.wrsn_set_obs_reuse.argtypes = [vp, C.c_int32]
     lib.wrsn_set_obs_reuse.restype = C.c_int
     lib.wrsn_set_obs_format.argtypes = [vp, C.c_int32]
@@ -286,6 +290,24 @@ class RawHandle:
     def rollout_collect(self, buffers, **out_ptrs):
         o = self._out(**out_ptrs)
         check(self.lib, self.lib.wrsn_rollout_collect(self._h, C.byref(buffers), C.byref(o)))
+
+    @staticmethod
+    def _ent(ent_ptrs):
+        """None (the registered buffers) or a WrsnEntityOut of the (node, mc, env) addresses."""
+        if ent_ptrs is None:
+            return None
+        node, mc, env = ent_ptrs
+        return C.byref(WrsnEntityOut(node or None, mc or None, env or None))
+
+    def rollout_record_entities(self, buffers, agent_ptr, action_ptr, logp_ptr, ent_ptrs=None):
+        """wrsn_rollout_record on packed entity rows; ent_ptrs: (node, mc, env) addresses, None = the registered buffers."""
+        check(self.lib, self.lib.wrsn_rollout_record_entities(self._h, C.byref(buffers), C.c_void_p(agent_ptr), C.c_void_p(action_ptr),
+                                                              C.c_void_p(logp_ptr), self._ent(ent_ptrs)))
+
+    def rollout_collect_entities(self, buffers, ent_ptrs=None, consume=True, **out_ptrs):
+        """wrsn_rollout_collect on packed entity rows (`obs` may be absent); consume=False leaves the requests to a following image collect."""
+        o = self._out(**out_ptrs)
+        check(self.lib, self.lib.wrsn_rollout_collect_entities(self._h, C.byref(buffers), C.byref(o), self._ent(ent_ptrs), 1 if consume else 0))
 
     def set_obs_reuse(self, on):
         check(self.lib, self.lib.wrsn_set_obs_reuse(self._h, 1 if on else 0))

@@ -910,6 +910,44 @@ int wrsn_entities(wrsn_t* h, const int32_t* agent_id, const wrsn_entity_out* ent
     return WRSN_OK;
 }
 
+// Entity transition rows: the buffers of `ent` (NULL: the registered ones) and the three row pointers of the transition buffers, all
+// checked before anything is enqueued or changed.
+static int tr_entity_args(wrsn_t* h, const wrsn_transition_buffers* buf, const wrsn_entity_out* ent, WrsnTrBuffers* t, WrsnEntityOut* e) {
+    if (ent) { const int rc = entity_out(ent, e); if (rc) return rc; }
+    else if (h->ent.node) *e = h->ent;
+    else return fail(WRSN_ERR_ARG, "no entity buffers: pass wrsn_entity_out or register them with wrsn_set_entity_out");
+    const int rc = tr_buffers(buf, t); if (rc) return rc;
+    if (((uintptr_t)t->pend_state | (uintptr_t)t->state | (uintptr_t)t->next_state) % 16)
+        return fail(WRSN_ERR_ARG, "wrsn_transition_buffers: pend_state, state and next_state of entity rows must be 16-byte aligned");
+    return 0;
+}
+
+int wrsn_rollout_record_entities(wrsn_t* h, const wrsn_transition_buffers* buf, const int32_t* agent_id, const float* action, const float* logp,
+                                 const wrsn_entity_out* ent) {
+    if (!h || !agent_id || !action || !logp) return fail(WRSN_ERR_ARG, "null argument");
+    WrsnTrBuffers t; WrsnEntityOut e{};
+    const int rc = tr_entity_args(h, buf, ent, &t, &e); if (rc) return rc;
+    WRSN_ON_DEVICE(h);
+    const int B = h->dev.B;
+    hipLaunchKernelGGL(wrsn_tr_record_entities_kernel, dim3((B + WRSN_ENT_ROWS - 1) / WRSN_ENT_ROWS), dim3(64 * WRSN_ENT_ROWS), 0, h->stream, B, h->dev.M,
+                       h->dev.N, t, agent_id, action, logp, e);
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+int wrsn_rollout_collect_entities(wrsn_t* h, const wrsn_transition_buffers* buf, const wrsn_step_out* out, const wrsn_entity_out* ent, int32_t consume) {
+    if (!h || !out || !out->agent_id || !out->reward || !out->terminal || !out->now || !out->status)   // out->obs may be NULL: entity-only batches
+        return fail(WRSN_ERR_ARG, "wrsn_rollout_collect_entities needs agent_id, reward, terminal, now and status of wrsn_step_out");
+    WrsnTrBuffers t; WrsnEntityOut e{};
+    const int rc = tr_entity_args(h, buf, ent, &t, &e); if (rc) return rc;
+    WRSN_ON_DEVICE(h);
+    const int B = h->dev.B;
+    hipLaunchKernelGGL(wrsn_tr_collect_entities_kernel, dim3((B + WRSN_ENT_ROWS - 1) / WRSN_ENT_ROWS), dim3(64 * WRSN_ENT_ROWS), 0, h->stream, B, h->dev.M,
+                       h->dev.N, t, out->agent_id, out->reward, out->now, h->dev.row_state, e, (int)(consume != 0));
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
 int wrsn_sync(wrsn_t* h) {
     if (!h) return fail(WRSN_ERR_ARG, "null handle");
     WRSN_ON_DEVICE(h);

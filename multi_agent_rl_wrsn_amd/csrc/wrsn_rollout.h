@@ -18,6 +18,9 @@
 //
 // Below them, wrsn_entity_kernel: the ENTITY observation (wrsn_set_entity_out / wrsn_entities), the per-node, per-charger and
 // per-environment terms get_state(agent) is made of (WRSN.py:130-186) as float32 rows instead of the 4 x G x G image.
+//
+// At the end, wrsn_tr_record_entities_kernel / wrsn_tr_collect_entities_kernel: the two bookkeeping kernels again for stored states
+// that are packed entity rows (6.6 KB instead of 160 KB): a wave per row, four rows per block.
 #pragma once
 #include <stdint.h>
 #include "wrsn_state.h"
@@ -178,4 +181,99 @@ __global__ void __launch_bounds__(256) wrsn_entity_kernel(WrsnDev d, const int32
         wrsn_ent_store4(q, (float)(ec->charging_range * invW), (float)(ec->charging_range * invH), (float)(0.5 * tmp * invW), (float)(0.5 * tmp * invH));
         wrsn_ent_store4(q + 4, (float)aid, (float)N, 0.f, 0.f);
     }
+}
+
+// ------------------------------------------------------------------ entity transition rows (wrsn_rollout_record_entities / wrsn_rollout_collect_entities)
+// The bookkeeping of wrsn_tr_record_kernel / wrsn_tr_collect_kernel above, statement for statement, for a stored state that is the entity
+// observation instead of the image: one packed float32 row of R = 8 N + 12 M + 8 elements -- node [N][8], then mc [M][12], then env [8], as
+// wrsn_entity_out lays them out -- in pend_state [B, M, R], state and next_state [M, capacity, R] of the same WrsnTrBuffers.  Every part is
+// a multiple of 16 bytes, so a row is C = 2 N + 3 M + 2 chunks of 16 bytes and every part boundary is a chunk boundary.
+// A row is 6.6 KB at 200 x 3 (32 KB at 1 000 x 8), not 160 KB: ONE 64-LANE WAVE PER ROW, WRSN_ENT_ROWS rows per 256-thread block, no LDS
+// and no __syncthreads.  Consecutive lanes take consecutive chunks through the wrsn_global casts; a pass is up to eight chunks per lane
+// (8 KB per wave) whose loads are all issued -- with clamped indices, not predicates -- before its first store.  The slot claim is one
+// atomicAdd of lane 0, broadcast with wrsn_wave_first (v_readfirstlane); a wave whose row has nothing to do leaves at its first test.
+#define WRSN_ENT_ROWS 4                                       // rows (waves) per block
+#define WRSN_ENT_PASS 8                                       // 16-byte chunks per lane and pass
+
+// where chunk c of a packed row comes from: [0, cn) at `a`, [cn, cm) at `b`, the rest at `c` (cn == cm == the row's chunks: one plain row at `a`)
+struct WrsnEntRowSrc { const WrsnU4* a; const WrsnU4* b; const WrsnU4* c; int cn, cm; };
+
+WDEV WrsnEntRowSrc wrsn_ent_row_gather(const WrsnEntityOut& ent, int e, int N, int M) {
+    WrsnEntRowSrc s;
+    s.a = (const WrsnU4*)(ent.node + (size_t)e * N * WRSN_ENT_NODE_F);
+    s.b = (const WrsnU4*)(ent.mc + (size_t)e * M * WRSN_ENT_MC_F);
+    s.c = (const WrsnU4*)(ent.env + (size_t)e * WRSN_ENT_ENV_F);
+    s.cn = 2 * N; s.cm = 2 * N + 3 * M;
+    return s;
+}
+WDEV WrsnEntRowSrc wrsn_ent_row_plain(const float* row, int C) {
+    WrsnEntRowSrc s; s.a = s.b = s.c = (const WrsnU4*)row; s.cn = s.cm = C; return s;
+}
+
+// the C chunks of one row, by the 64 lanes of a wave.  The three parts are addressed from one base: chunk c lies at a + 16 c, plus the
+// wave-uniform distance of its part from where the row would go on behind `a` -- two selects per chunk, no branch between the loads.
+WDEV void wrsn_ent_row_copy(float* dst, const WrsnEntRowSrc& s, int C, int lane) {
+    const auto d = wrsn_global((WrsnU4*)dst);
+    const uintptr_t a = (uintptr_t)s.a;
+    const int64_t db = (int64_t)((uintptr_t)s.b - a) - 16ll * s.cn, dc = (int64_t)((uintptr_t)s.c - a) - 16ll * s.cm;
+    for (int c0 = 0; c0 < C; c0 += 64 * WRSN_ENT_PASS) {
+        WrsnU4 v[WRSN_ENT_PASS];
+#pragma unroll
+        for (int k = 0; k < WRSN_ENT_PASS; ++k) {
+            const int i = c0 + 64 * k + lane, c = i < C ? i : C - 1;   // clamped: chunks beyond C are not stored
+            const int64_t off = 16ll * c + (c < s.cn ? 0ll : c < s.cm ? db : dc);
+            v[k] = wrsn_ld_u4(wrsn_global((const WrsnU4*)(a + (uintptr_t)off)));
+        }
+#pragma unroll
+        for (int k = 0; k < WRSN_ENT_PASS; ++k) {
+            const int i = c0 + 64 * k + lane;
+            if (i < C) wrsn_st_u4(d + i, v[k]);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(64 * WRSN_ENT_ROWS) wrsn_tr_record_entities_kernel(int B, int M, int N, WrsnTrBuffers t, const int32_t* __restrict__ agent_id,
+                                                                                      const float* __restrict__ action, const float* __restrict__ logp,
+                                                                                      WrsnEntityOut ent) {
+    const int lane = (int)threadIdx.x & 63;
+    const int e = (int)blockIdx.x * WRSN_ENT_ROWS + ((int)threadIdx.x >> 6);
+    if (e >= B) return;
+    const int a = wrsn_wave_first(agent_id[e]);
+    if (a < 0 || a >= M) return;
+    const int C = 2 * N + 3 * M + 2, A = t.action_elems;
+    const size_t slot = (size_t)e * M + a;
+    wrsn_ent_row_copy(t.pend_state + slot * C * 4, wrsn_ent_row_gather(ent, e, N, M), C, lane);
+#pragma clang loop vectorize(disable) interleave(disable)
+    for (int i = lane; i < A; i += 64) t.pend_action[slot * A + i] = action[(size_t)e * A + i];
+    if (lane == 0) { t.pend_logp[slot] = logp[e]; t.pend_valid[slot] = 1; }
+}
+
+__global__ void __launch_bounds__(64 * WRSN_ENT_ROWS) wrsn_tr_collect_entities_kernel(int B, int M, int N, WrsnTrBuffers t, const int32_t* __restrict__ agent_id,
+                                                                                       const double* __restrict__ reward, const double* __restrict__ now,
+                                                                                       int32_t* row_state, WrsnEntityOut ent, int consume) {
+    const int lane = (int)threadIdx.x & 63;
+    const int e = (int)blockIdx.x * WRSN_ENT_ROWS + ((int)threadIdx.x >> 6);
+    if (e >= B) return;
+    const int st = wrsn_wave_first(row_state[e]);             // the row_state rules of wrsn_tr_collect_kernel; every lane has read before lane 0 writes
+    if (st == 0 || st == 3) return;
+    if (consume && lane == 0) row_state[e] = 0;               // consume == 0: left for the image collect that follows
+    if (st == 2 || st == 4) {                                 // episode over or restarted: pending actions are discarded
+        if (lane < M) t.pend_valid[(size_t)e * M + lane] = 0;
+        return;
+    }
+    const int a = wrsn_wave_first(agent_id[e]);
+    if (a < 0 || a >= M) return;
+    const size_t pslot = (size_t)e * M + a;
+    if (!wrsn_wave_first((int)t.pend_valid[pslot])) return;   // this charger has not acted yet in this episode (IPPO.py:146-147)
+    int slot = 0;
+    if (lane == 0) slot = atomicAdd(&t.count[a], 1);
+    slot = wrsn_wave_first(slot);
+    if (slot >= t.capacity) return;                           // buffer full: counted, not stored
+    const int C = 2 * N + 3 * M + 2, A = t.action_elems;
+    const size_t q = (size_t)a * t.capacity + slot;
+    wrsn_ent_row_copy(t.state + q * C * 4, wrsn_ent_row_plain(t.pend_state + pslot * C * 4, C), C, lane);
+    wrsn_ent_row_copy(t.next_state + q * C * 4, wrsn_ent_row_gather(ent, e, N, M), C, lane);
+#pragma clang loop vectorize(disable) interleave(disable)
+    for (int i = lane; i < A; i += 64) t.action[q * A + i] = t.pend_action[pslot * A + i];
+    if (lane == 0) { t.reward[q] = (float)reward[e]; t.logp[q] = t.pend_logp[pslot]; t.now[q] = now[e]; t.env[q] = e; }
 }

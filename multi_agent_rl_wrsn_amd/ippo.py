@@ -232,13 +232,7 @@ class PPOLearner:
         for k in ("gamma", "clip", "batch_size", "minibatch_size", "n_updates_per_iteration", "save_freq", "gae", "clip_vloss", "ent_coef",
                   "vf_coef", "gae_lambda", "norm_adv", "max_grad_norm"):
             setattr(self, k, a[k])
-        UNet, CNNCritic = build_networks(self.map_size)
-        # channels-last weights and activations: the same float32 arithmetic, 3.6 x the NCHW convolution throughput of MIOpen on
-        # MI355X (tools/diag_policy.py: 71 vs 20 TFLOP/s for the UNet forward); state_dict keys and shapes are unaffected
-        self._cl = self.device.type == "cuda"
-        mf = dict(memory_format=torch.channels_last) if self._cl else {}
-        self.actors = [UNet().to(self.device).to(**mf) for _ in range(self.num_agent)]
-        self.critics = [CNNCritic().to(self.device).to(**mf) for _ in range(self.num_agent)]
+        self.actors, self.critics = self._build_networks()
         # optional reduced-precision INFERENCE (roll-out actions and values only; the update stays float32): "bf16" doubles the
         # forward throughput again but the roll-out log-probabilities then differ from the float32 ones the update recomputes
         self.inference_dtype = {None: None, "bf16": torch.bfloat16, "fp16": torch.float16}[inference_dtype]
@@ -259,6 +253,21 @@ class PPOLearner:
                            for i in range(self.num_agent)]
         self.infer_chunk = int(infer_chunk)
         self.min_bucket = max(1, int(min_bucket))
+
+    # -- what a subclass with other networks replaces: construction, `_forward`, and the axes a decision's action spans
+    _logp_dims = (1, 2)                                        # log-prob / entropy are summed over these axes of the action (G x G map)
+
+    def _build_networks(self):
+        """(actors, critics): one network of each kind per charger, on `self.device`."""
+        torch = self.torch
+        UNet, CNNCritic = build_networks(self.map_size)
+        # channels-last weights and activations: the same float32 arithmetic, 3.6 x the NCHW convolution throughput of MIOpen on
+        # MI355X (tools/diag_policy.py: 71 vs 20 TFLOP/s for the UNet forward); state_dict keys and shapes are unaffected
+        self._cl = self.device.type == "cuda"
+        mf = dict(memory_format=torch.channels_last) if self._cl else {}
+        actors = [UNet().to(self.device).to(**mf) for _ in range(self.num_agent)]
+        critics = [CNNCritic().to(self.device).to(**mf) for _ in range(self.num_agent)]
+        return actors, critics
 
     # -- policy ------------------------------------------------------------------------------------------------------
     def _bucket(self, r):
@@ -289,7 +298,7 @@ class PPOLearner:
                 mean, log_std = mean[:r].float(), log_std[:r].float()
                 dist = torch.distributions.Normal(mean, log_std.exp())
                 act = dist.sample()
-                outs.append(act); lps.append(dist.log_prob(act).sum((1, 2)))
+                outs.append(act); lps.append(dist.log_prob(act).sum(self._logp_dims))
         return torch.cat(outs), torch.cat(lps)
 
     def rollout_logp(self, agent_id, states, actions):
@@ -308,7 +317,7 @@ class PPOLearner:
                     s = s.index_select(0, torch.arange(nb, device=s.device) % r)
                 mean, log_std = self._forward(self.actors[agent_id], s, inference=True)
                 dist = torch.distributions.Normal(mean[:r].float(), log_std[:r].float().exp())
-                lps.append(dist.log_prob(a.float()).sum((1, 2)))
+                lps.append(dist.log_prob(a.float()).sum(self._logp_dims))
         return torch.cat(lps)
 
     def _forward(self, net, x, inference=False):
@@ -328,7 +337,7 @@ class PPOLearner:
         torch = self.torch
         mean, log_std = self._forward(self.actors[agent_id], batch_states)
         dist = torch.distributions.Normal(mean, log_std.exp())
-        return dist.log_prob(batch_actions).sum((1, 2)), dist.entropy().sum((1, 2))
+        return dist.log_prob(batch_actions).sum(self._logp_dims), dist.entropy().sum(self._logp_dims)
 
     def get_value(self, agent_id, state):                     # IPPO.py:115-117
         return self._forward(self.critics[agent_id], state).sum(1)
@@ -511,6 +520,10 @@ class BatchedIPPO(PPOLearner):
         self._req = r
         return r
 
+    def _stored_actions(self, actions):
+        """Stored action rows [n, action_elems] in the shape `evaluate` takes."""
+        return actions.view(-1, self.env.map_size, self.env.map_size)
+
     def roll_out(self, max_launches=100000, fresh_episodes=False):
         """IPPO.py:119-210 over the batch: launches until every charger has `batch_size` transitions, then the reference's
         per-charger batch selection.  Environments restart by auto-reset, so one roll-out spans many episodes.
@@ -523,7 +536,7 @@ class BatchedIPPO(PPOLearner):
         runs every episode to its terminal (IPPO.py:130-190).  `fresh_episodes=True` restores the restart-per-roll-out behaviour."""
         torch, env = self.torch, self.env
         if not env.auto_reset:
-            raise ValueError("BatchedIPPO needs VecWRSN(auto_reset=True)")
+            raise ValueError("%s needs VecWRSN(auto_reset=True)" % type(self).__name__)
         if fresh_episodes or self._req is None:
             self.buffers.clear()
             self._req = env.reset()
@@ -548,7 +561,7 @@ class BatchedIPPO(PPOLearner):
             # the reference runs cal_rt_adv per episode over the transitions of that episode (IPPO.py:171); with terminals all
             # False neither returns nor advantages couple two transitions, so one call over the selected batch gives the same values
             returns, adv, values = self.cal_rt_adv(a, states, rew, nxt, torch.zeros_like(rew))
-            out.append(dict(states=states, actions=self.buffers.action[a].index_select(0, idx).view(-1, env.map_size, env.map_size),
+            out.append(dict(states=states, actions=self._stored_actions(self.buffers.action[a].index_select(0, idx)),
                             log_probs=self.buffers.logp[a].index_select(0, idx), rewards=rew, next_states=nxt, advantages=adv, returns=returns,
                             values=values))
             self.loggers[a]["rewards"].append(float(rew.mean()))
@@ -579,3 +592,257 @@ class BatchedIPPO(PPOLearner):
                     self.save_checkpoint(id, os.path.join(save_folder, str(lg["i_so_far"]), str(id)))
             self.timers["train_s"] += self._sync_time() - t0
         return rows
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# training from the entity observation: packed rows, a permutation-invariant actor / critic, the trainer on top
+# ------------------------------------------------------------------------------------------------------------------
+def entity_row_elems(n_node, num_agent):
+    """Floats of one packed entity row: node [N][8], then mc [M][12], then env [8] (include/wrsn_hip.h, wrsn_transition_buffers)."""
+    return _lib.ENT_NODE_F * int(n_node) + _lib.ENT_MC_F * int(num_agent) + _lib.ENT_ENV_F
+
+
+class EntityTransitionBuffers:
+    """`TransitionBuffers` for the entity observation (`wrsn_rollout_record_entities` / `wrsn_rollout_collect_entities`): a stored
+    state is one packed float32 row of R = 8 N + 12 M + 8 elements, `pend_state` [B, M, R], `state` / `next_state` [M, capacity, R].
+
+    env          : VecWRSN(entities=True); needs no image (`render=False`) -- the rows are read from the buffers it registered
+    capacity     : transitions kept per charger (further ones are counted in `count` and dropped)
+    action_elems : size of the policy's raw output per decision (3: the action vector itself)"""
+
+    def __init__(self, env, capacity, action_elems=3):
+        torch = env.torch
+        if not getattr(env, "entities", False):
+            raise ValueError("EntityTransitionBuffers needs a VecWRSN with the entity observation (entities=True)")
+        self.env = env
+        B, M, C, A = env.num_env, env.num_agent, int(capacity), int(action_elems)
+        R = entity_row_elems(env.n_node, M)
+        self.capacity, self.action_elems, self.row_elems = C, A, R
+        dev = env.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.pend_state = torch.zeros((B, M, R), **f32)
+        self.pend_action = torch.zeros((B, M, A), **f32)
+        self.pend_logp = torch.zeros((B, M), **f32)
+        self.pend_valid = torch.zeros((B, M), dtype=torch.uint8, device=dev)
+        self.state = torch.zeros((M, C, R), **f32)
+        self.action = torch.zeros((M, C, A), **f32)
+        self.next_state = torch.zeros((M, C, R), **f32)
+        self.reward = torch.zeros((M, C), **f32)
+        self.logp = torch.zeros((M, C), **f32)
+        self.now = torch.zeros((M, C), dtype=torch.float64, device=dev)
+        self.env_index = torch.zeros((M, C), dtype=torch.int32, device=dev)
+        self.count = torch.zeros((M,), dtype=torch.int32, device=dev)
+        self._c = _lib.WrsnTransitionBuffers(C, A, *[t.data_ptr() for t in (
+            self.pend_state, self.pend_action, self.pend_logp, self.pend_valid, self.state, self.action, self.next_state,
+            self.reward, self.logp, self.now, self.env_index, self.count)])
+
+    @staticmethod
+    def split(rows, num_agent):
+        """Views (nodes [n,N,8], chargers [n,M,12], env_feat [n,8]) of packed rows [n,R] for M = num_agent chargers."""
+        M = int(num_agent)
+        nf, mf, ef = _lib.ENT_NODE_F, _lib.ENT_MC_F, _lib.ENT_ENV_F
+        n, R = rows.shape[0], rows.shape[-1]
+        N = (R - mf * M - ef) // nf
+        if N < 0 or entity_row_elems(N, M) != R:
+            raise ValueError("rows of %d floats are no packed entity rows of %d chargers" % (R, M))
+        return (rows[..., :nf * N].reshape(n, N, nf), rows[..., nf * N:nf * N + mf * M].reshape(n, M, mf), rows[..., nf * N + mf * M:])
+
+    @staticmethod
+    def pack(nodes, chargers, env_feat):
+        """Packed rows [n,R] of entity tensors (nodes [n,N,8], chargers [n,M,12], env_feat [n,8]): what the device kernels store."""
+        torch = _torch()
+        return torch.cat([nodes.flatten(1), chargers.flatten(1), env_feat.flatten(1)], 1)
+
+    def clear(self, keep_pending=False):
+        self.count.zero_()
+        if not keep_pending:
+            self.pend_valid.zero_()
+
+    def record(self, agent_ids, actions, logp):
+        """The chargers `agent_ids` [B] (< 0: none) are about to receive `actions` [B, action_elems], chosen on the entity rows the
+        environment holds now (IPPO.py:141-142)."""
+        env, t = self.env, self.env.torch
+        env._bind_stream()
+        a = agent_ids.to(device=env.device, dtype=t.int32).contiguous()
+        x = actions.to(device=env.device, dtype=t.float32).reshape(env.num_env, self.action_elems).contiguous()
+        lp = logp.to(device=env.device, dtype=t.float32).reshape(env.num_env).contiguous()
+        self._keep = (a, x, lp)                               # alive until the kernel has run
+        env._h.rollout_record_entities(self._c, a.data_ptr(), x.data_ptr(), lp.data_ptr())
+
+    def collect(self, consume=True):
+        """Append the transitions the request just returned by `env.step` completes (IPPO.py:144-155).  consume=False leaves the
+        requests to the `TransitionBuffers.collect` of the same launch that follows."""
+        env = self.env
+        env._bind_stream()
+        env._h.rollout_collect_entities(self._c, None, consume, **env._out_ptrs())
+
+    def counts(self):
+        """Transitions appended per charger so far (host list; synchronises)."""
+        return [int(v) for v in self.count.cpu()]
+
+    def stored(self):
+        return [min(c, self.capacity) for c in self.counts()]
+
+
+def build_entity_networks(n_agent_rows):
+    """Returns (EntityActor, EntityCritic) classes over packed entity rows [n, R] of `n_agent_rows` chargers (the node count follows
+    from R).  A set policy: a per-node MLP pooled by masked mean and masked max over the live nodes, a per-charger MLP pooled by
+    masked mean plus the asking charger's own embedding, and a head over the pools and the environment row.  No BatchNorm and no other
+    operation across rows: a row's output does not depend on the batch it is evaluated in, so the log-probabilities of the roll-out and of
+    the update agree.  Dead and padded node rows have no influence whatever they hold: their inputs are replaced by zeros and their
+    embeddings masked out of both pools; a row without a live node pools to zeros."""
+    torch = _torch()
+    nn = torch.nn
+    F = torch.nn.functional
+    M = int(n_agent_rows)
+    n_alive, c_alive, c_self = _lib.ENT_NODE["alive"], _lib.ENT_MC["alive"], _lib.ENT_MC["is_self"]
+    e_agent, e_nnode = _lib.ENT_ENV["agent"], _lib.ENT_ENV["n_node"]
+
+    def lin(layer, x):
+        """`layer` on x [n, r, K] as n separate [r, K] x [K, O] products (a batched matrix product over the rows of the batch): one
+        flattened [n r, K] GEMM is tiled over all rows, and which tile -- hence which summation order -- a row falls into depends on the
+        batch around it; here the arithmetic done for a row is the same whatever the batch holds."""
+        return torch.bmm(x, layer.weight.t().unsqueeze(0).expand(x.shape[0], -1, -1)) + layer.bias
+
+    class _Trunk(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.node1 = _ortho(nn.Linear(_lib.ENT_NODE_F, 64)); self.node2 = _ortho(nn.Linear(64, 64))
+            self.mc1 = _ortho(nn.Linear(_lib.ENT_MC_F, 32)); self.mc2 = _ortho(nn.Linear(32, 32))
+            self.head1 = _ortho(nn.Linear(64 + 64 + 32 + 32 + _lib.ENT_ENV_F, 128)); self.head2 = _ortho(nn.Linear(128, 128))
+
+        def forward(self, rows):
+            nodes, mcs, env = EntityTransitionBuffers.split(rows, M)
+            alive = nodes[..., n_alive] == 1                                             # [n, N]
+            x = torch.where(alive.unsqueeze(-1), nodes, torch.zeros_like(nodes))       # a select, not a product: NaN / inf in a dead row vanish too
+            h = F.relu(lin(self.node2, F.relu(lin(self.node1, x))))
+            w = alive.unsqueeze(-1).to(h.dtype)
+            cnt = w.sum(1)                                                               # [n, 1] live nodes of the row
+            mean = (h * w).sum(1) / cnt.clamp(min=1.0)
+            mx = h.masked_fill(~alive.unsqueeze(-1), float("-inf")).max(1).values
+            mx = torch.where(cnt > 0, mx, torch.zeros_like(mx))                           # no live node: zeros
+            g = F.relu(lin(self.mc2, F.relu(lin(self.mc1, mcs))))
+            cw = (mcs[..., c_alive] == 1).unsqueeze(-1).to(g.dtype)
+            cmean = (g * cw).sum(1) / cw.sum(1).clamp(min=1.0)
+            own = (g * (mcs[..., c_self] == 1).unsqueeze(-1).to(g.dtype)).sum(1)          # the asking charger's embedding
+            scale = torch.ones(_lib.ENT_ENV_F, dtype=env.dtype, device=env.device)       # charger index and node count as fractions
+            scale[e_agent] = 1.0 / M; scale[e_nnode] = 1.0 / max(1, nodes.shape[1])
+            x = torch.cat([mean, mx, cmean, own, env * scale], 1).unsqueeze(1)
+            return F.relu(lin(self.head2, F.relu(lin(self.head1, x))))               # [n, 1, 128]: the heads go on row by row
+
+    class EntityActor(nn.Module):
+        """Packed rows [n, R] -> (mean [n, 3], log_std [n, 3]) of a diagonal Gaussian over the action vector; log_std in [-4, 1]."""
+
+        def __init__(self):
+            super().__init__()
+            self.trunk = _Trunk()
+            self.mean = _ortho(nn.Linear(128, 3), std=0.01)
+            self.log_std = _ortho(nn.Linear(128, 3), std=0.01)
+
+        def forward(self, rows):
+            z = self.trunk(rows)
+            return lin(self.mean, z).squeeze(1), lin(self.log_std, z).squeeze(1).clamp(-4.0, 1.0)
+
+    class EntityCritic(nn.Module):
+        """Packed rows [n, R] -> value [n, 1]."""
+
+        def __init__(self):
+            super().__init__()
+            self.trunk = _Trunk()
+            self.value = _ortho(nn.Linear(128, 1), std=0.01)
+
+        def forward(self, rows):
+            return lin(self.value, self.trunk(rows)).squeeze(1)
+
+    return EntityActor, EntityCritic
+
+
+class EntityPPOLearner(PPOLearner):
+    """`PPOLearner` with the set networks of `build_entity_networks` over packed entity rows and 3-vector actions.  `evaluate`,
+    `get_value`, `cal_rt_adv`, `minibatch_loss`, `update`, the data-parallel gradient exchange and the checkpoints are inherited.
+    Unlike the image learner's, the log-probabilities `get_action` stores are the ones `evaluate` recomputes at unchanged weights
+    (float32 rounding apart): the first minibatch of an update has ratio 1."""
+
+    _logp_dims = (1,)                                          # the action is a 3-vector
+
+    def __init__(self, args, num_agent, device, model_path=None, infer_chunk=1024, process_group=None, min_bucket=16):
+        super().__init__(args, num_agent, 0, device, model_path, infer_chunk, process_group, None, min_bucket)
+
+    def _build_networks(self):
+        self._cl = False
+        Actor, Critic = build_entity_networks(self.num_agent)
+        return ([Actor().to(self.device) for _ in range(self.num_agent)], [Critic().to(self.device) for _ in range(self.num_agent)])
+
+    def _forward(self, net, x, inference=False):
+        return net(x)
+
+    def get_action(self, agent_id, states):
+        """Packed rows [n, R] -> (action [n, 3], log-prob [n]).  Chunks of `infer_chunk` rows, a short chunk padded to its bucket by
+        repeating its own rows (a small set of GEMM shapes; the padding cannot change a row's output)."""
+        torch = self.torch
+        outs, lps = [], []
+        with torch.no_grad():
+            for s in states.split(self.infer_chunk):
+                r = s.shape[0]
+                nb = self._bucket(r)
+                if r < nb:
+                    s = s.index_select(0, torch.arange(nb, device=s.device) % r)
+                mean, log_std = self._forward(self.actors[agent_id], s, inference=True)
+                dist = torch.distributions.Normal(mean[:r], log_std[:r].exp())
+                act = dist.sample()
+                outs.append(act); lps.append(dist.log_prob(act).sum(self._logp_dims))
+        return torch.cat(outs), torch.cat(lps)
+
+
+class BatchedEntityIPPO(EntityPPOLearner):
+    """The roll-out of `BatchedIPPO` on entity rows: `VecWRSN(entities=True)` (no image needed: `render=False`), the set policy's
+    3-vector is the action `env.step` takes, and the transitions live in `EntityTransitionBuffers`."""
+
+    def __init__(self, args, env, device=None, model_path=None, capacity=None, infer_chunk=1024, process_group=None, log=None, min_bucket=16):
+        if not getattr(env, "entities", False):
+            raise ValueError("BatchedEntityIPPO needs a VecWRSN with the entity observation (entities=True)")
+        super().__init__(args, env.num_agent, device if device is not None else env.device, model_path, infer_chunk, process_group, min_bucket)
+        self.env = env
+        self.buffers = EntityTransitionBuffers(env, capacity or 2 * self.batch_size, 3)
+        self.timers = {"env_s": 0.0, "policy_s": 0.0, "glue_s": 0.0, "train_s": 0.0, "launches": 0, "requests": 0}
+        self.log = log
+        self._req = None
+
+    _sync_time = BatchedIPPO._sync_time
+    roll_out = BatchedIPPO.roll_out
+    train = BatchedIPPO.train
+
+    def _stored_actions(self, actions):
+        return actions
+
+    def step_batch(self):
+        """One launch of the batched roll-out: act for every environment that carries a request, step, collect."""
+        torch, env = self.torch, self.env
+        r = self._req
+        ids = r["agent_id"].clone()                           # the request's ids, detached from the tensor the step writes
+        t0 = self._sync_time()
+        act3 = torch.zeros((env.num_env, 3), dtype=torch.float32, device=env.device)
+        logp = torch.zeros((env.num_env,), dtype=torch.float32, device=env.device)
+        for a in range(self.num_agent):
+            rows = torch.nonzero(ids == a).flatten()
+            if rows.numel() == 0:
+                continue
+            x = EntityTransitionBuffers.pack(r["nodes"].index_select(0, rows), r["chargers"].index_select(0, rows), r["env_feat"].index_select(0, rows))
+            act, lp = self.get_action(a, x)
+            act3.index_copy_(0, rows, act.float()); logp.index_copy_(0, rows, lp.float())
+        t1 = self._sync_time()
+        self.buffers.record(ids, act3, logp)
+        t2 = self._sync_time()
+        r = env.step(ids, act3.double())
+        t3 = self._sync_time()
+        bad = torch.nonzero(r["status"] < 0).flatten()
+        if bad.numel():
+            raise RuntimeError("environment rows %s report status %s" % (bad.tolist(), r["status"][bad].tolist()))
+        self.buffers.collect()
+        t4 = self._sync_time()
+        tm = self.timers
+        tm["policy_s"] += t1 - t0; tm["glue_s"] += (t2 - t1) + (t4 - t3); tm["env_s"] += t3 - t2; tm["launches"] += 1
+        tm["requests"] += int((ids >= 0).sum())
+        self.last_ids, self.last_action3 = ids, act3          # what this launch handed to the environments (tests / logging)
+        self._req = r
+        return r
