@@ -38,8 +38,12 @@ def main():
     ap.add_argument("--obs-dtype", default="float32", choices=["float32", "bfloat16"], help="observation format of the environment and the roll-out buffers")
     ap.add_argument("--policy", default="image", choices=["image", "entity"], help="image: UNet / CNN critic on the 4 x G x G observation (default); "
                     "entity: the set policy on entity rows, no image rendered (VecWRSN(render=False, entities=True), BatchedEntityIPPO)")
+    ap.add_argument("--fused-policy", action="store_true", help="with --policy entity: the device samples the actions itself (wrsn_entity_act, "
+                    "BatchedEntityIPPO(fused_policy=True)) instead of one PyTorch forward pass per charger")
     ap.add_argument("--report-updates", action="store_true", help="add peak device memory and the statistics of every update (first minibatch included) to the line")
     args = ap.parse_args()
+    if args.fused_policy and args.policy != "entity":
+        raise SystemExit("--fused-policy needs --policy entity")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:       # launcher-free multi-rank entry: before this process touches torch or the GPU
         from multi_agent_rl_wrsn_amd.sharding import launch_ranks
         raise SystemExit(launch_ranks(args.gpus, [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]))
@@ -64,7 +68,8 @@ def main():
     if entity:
         env = VecWRSN([synth_scenario(rank * B + e, N, N) for e in range(B)], None, M, auto_reset=True, step_budget=args.step_budget, device=str(dev),
                       render=False, entities=True)             # no image at all: 6.6 KB of entity rows per request
-        algo = BatchedEntityIPPO(ppo_args, env, capacity=max(2 * args.batch_size, 4096), infer_chunk=args.infer_chunk, min_bucket=args.infer_chunk)
+        algo = BatchedEntityIPPO(ppo_args, env, capacity=max(2 * args.batch_size, 4096), infer_chunk=args.infer_chunk, min_bucket=args.infer_chunk,
+                                 **({"fused_policy": True} if args.fused_policy else {}))
     else:
         env = VecWRSN([synth_scenario(rank * B + e, N, N) for e in range(B)], None, M, auto_reset=True, step_budget=args.step_budget, device=str(dev),
                       reuse_obs=True, obs_dtype=args.obs_dtype)                             # BatchedIPPO only reads the state tensor (index_select / copies)
@@ -116,7 +121,7 @@ def main():
     if entity:
         out["config"]["workload"] = "%d envs x %d nodes x %d MC, set actor + critic per charger on entity rows, 3-vector actions, batch %d / minibatch %d / %d epochs" % (
             B, N, M, args.batch_size, args.minibatch_size, args.updates)
-        out["config"]["policy"] = "float32, entity rows, no image"
+        out["config"]["policy"] = "float32, entity rows, no image" + (", actions sampled on the device (wrsn_entity_act)" if args.fused_policy else "")
     if args.report_updates:
         out["peak_memory_bytes"] = int(torch.cuda.max_memory_allocated(dev)); out["updates"] = updates
     print(json.dumps(out, default=float), flush=True)

@@ -306,6 +306,50 @@ int wrsn_rollout_record_entities(wrsn_t *h, const wrsn_transition_buffers *buf, 
 int wrsn_rollout_collect_entities(wrsn_t *h, const wrsn_transition_buffers *buf, const wrsn_step_out *out,
                                   const wrsn_entity_out *ent, int32_t consume);
 
+/* ACTING FROM ENTITY ROWS.  The actor of build_entity_networks (ippo.py: a set policy over the entity rows, a diagonal Gaussian over
+ * the 3-vector action) evaluated and sampled on the device, between the call that wrote the entity rows and
+ * wrsn_rollout_record_entities.  `actors` holds one packed float32 block per charger, [n_mc, wrsn_entity_actor_floats()].
+ * BLOCK LAYOUT.  Every Linear is stored TRANSPOSED, [in, out] row-major, directly followed by its bias [out], in this order
+ * (offsets in floats):
+ *     node1    8 ->  64  at     0, bias at   512      node2   64 ->  64  at   576, bias at  4672
+ *     mc1     12 ->  32  at  4736, bias at  5120      mc2     32 ->  32  at  5152, bias at  6176
+ *     head1  200 -> 128  at  6208, bias at 31808      head2  128 -> 128  at 31936, bias at 48320
+ *     mean   128 ->   3  at 48448, bias at 48832      log_std 128 ->  3  at 48835, bias at 49219
+ * 49 222 floats, then zeros up to a multiple of 4: wrsn_entity_actor_floats() == 49 224.  The WRSN_ENTPOL_FEAT inputs of head1 are, in
+ * this order: the mean of the node embeddings over the alive nodes [64], their maximum [64], the mean of the charger embeddings over
+ * the alive chargers [32], the asking charger's own embedding [32], the environment row [8] with slot 4 (the asking charger) scaled by
+ * 1 / n_mc and slot 5 (n_node) by 1 / (the handle's node count).  (Stored [in, out], a matrix-core operand W[out = 32 t + (l & 31)]
+ * [k = 2 kk + (l >> 5)] of lane l is two runs of 32 consecutive floats.)
+ * SEMANTICS.  Row e with a = agent_id[e] in [0, n_mc) is evaluated exactly as EntityActor.forward evaluates it, with block a: a node's
+ * eight inputs are replaced by zeros unless its slot 7 (alive) equals 1 -- a select: NaN or inf in a dead or padded node row vanish --;
+ * mean and maximum of ReLU(node2(ReLU(node1(x)))) are taken over the alive nodes, the mean divided by max(count, 1), the maximum zero
+ * when no node is alive; the charger mean is taken over the chargers whose slot 4 (alive) equals 1, divided by max(count, 1); the own
+ * embedding is the sum over the chargers whose slot 3 (is_self) equals 1 -- from the rows themselves, not from agent_id --;
+ * (mean, log_std) = the two 3-vectors on ReLU(head2(ReLU(head1(features)))), log_std clamped to [-4, 1].  Then, all in float32,
+ *     action[d] = fmaf(exp(log_std[d]), eps[d], mean[d])          logp = sum_d (-eps[d]^2 / 2 - log_std[d]) - 1.5 log(2 pi)
+ * with eps == NULL standing for eps = 0 (the mode).  action_f64 holds the same values widened, as wrsn_step takes them.  Rows with
+ * agent_id outside [0, n_mc) are skipped: every byte of every output is kept.
+ * A row's outputs depend on its own entity rows, its charger's block and its eps only: not on any other row of the batch, not on its
+ * position in it, and not on the run -- two calls on equal inputs give equal bytes.  The call needs no scenario: it reads nothing but
+ * `ent`, `actors`, `agent_id` and `eps`.
+ * WRSN_ERR_ARG, with the handle and every buffer untouched: h, actors, agent_id, out, out->action or out->logp NULL; ent == NULL and
+ * nothing registered; node, mc or env NULL or not 16-byte aligned; actors not 16-byte aligned.
+ * Asynchronous on the handle's stream, into which a pipelined step has joined.  The first call allocates a scratch of
+ * n_env * (WRSN_ENTPOL_FEAT + n_mc) words in the handle; wrsn_destroy frees it. */
+#define WRSN_ENTPOL_FEAT 200            /* 64 mean + 64 max + 32 charger mean + 32 own + 8 env */
+int32_t wrsn_entity_actor_floats(void); /* floats of one block, a multiple of 4; host only, no handle */
+
+typedef struct wrsn_entity_act_out {    /* DEVICE, caller-owned; written only for the rows that are not skipped */
+    float  *action;      /* [B,3] the sample: what wrsn_rollout_record_entities stores */
+    double *action_f64;  /* [B,3] the same values widened: what wrsn_step takes; may be NULL */
+    float  *logp;        /* [B]   */
+    float  *mean;        /* [B,3] may be NULL */
+    float  *log_std;     /* [B,3] after the clamp to [-4, 1]; may be NULL */
+} wrsn_entity_act_out;
+
+int wrsn_entity_act(wrsn_t *h, const float *actors, const int32_t *agent_id, const float *eps, const wrsn_entity_out *ent,
+                    const wrsn_entity_act_out *out);
+
 /* Copy internal state to HOST memory (parity tests, `net` / `agents` views).  Synchronises. */
 int wrsn_peek(wrsn_t *h, int32_t what, void *dst);
 

@@ -30,6 +30,7 @@ ENT_ENV_FIELDS = ("h_x", "h_y", "h_self_x", "h_self_y", "agent", "n_node", "_r0"
 ENT_NODE = {k: i for i, k in enumerate(ENT_NODE_FIELDS)}      # ENT_NODE["weight"] == 2: the slot of a field, no magic numbers at the caller
 ENT_MC = {k: i for i, k in enumerate(ENT_MC_FIELDS) if not k.startswith("_")}
 ENT_ENV = {k: i for i, k in enumerate(ENT_ENV_FIELDS) if not k.startswith("_")}
+ENTPOL_FEAT = 200            # wrsn_entity_act: inputs of the actor's head (64 mean + 64 max + 32 charger mean + 32 own + 8 env)
 MC_FIELDS = ("loc_x", "loc_y", "energy", "status", "type_charging", "cur_x", "cur_y", "cur_t", "n_conn",
              "excl", "prev_minfit", "act0", "act1", "act2", "_r0", "_r1")
 ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max", "charging_time_max",
@@ -37,7 +38,7 @@ ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max"
 
 # every entry point include/wrsn_hip.h declares
 EXPORTS = ("wrsn_create", "wrsn_destroy", "wrsn_set_stream", "wrsn_set_scenario", "wrsn_set_scenario_seeded", "wrsn_reset", "wrsn_step",
-           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
+           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_entity_actor_floats", "wrsn_entity_act", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
            "wrsn_clone_envs", "wrsn_pool_set", "wrsn_pool_reset", "wrsn_synth_network",
            "wrsn_last_error",
            "wrsn_version")
@@ -66,6 +67,10 @@ class WrsnStepOut(C.Structure):
 
 class WrsnEntityOut(C.Structure):
     _fields_ = [("node", C.c_void_p), ("mc", C.c_void_p), ("env", C.c_void_p)]
+
+
+class WrsnEntityActOut(C.Structure):
+    _fields_ = [("action", C.c_void_p), ("action_f64", C.c_void_p), ("logp", C.c_void_p), ("mean", C.c_void_p), ("log_std", C.c_void_p)]
 
 
 class WrsnTransitionBuffers(C.Structure):
@@ -115,6 +120,10 @@ def bind(lib):
     lib.wrsn_rollout_record_entities.restype = C.c_int
     lib.wrsn_rollout_collect_entities.argtypes = [vp, C.POINTER(WrsnTransitionBuffers), C.POINTER(WrsnStepOut), C.POINTER(WrsnEntityOut), C.c_int32]
     lib.wrsn_rollout_collect_entities.restype = C.c_int
+    lib.wrsn_entity_actor_floats.argtypes = []
+    lib.wrsn_entity_actor_floats.restype = C.c_int32
+    lib.wrsn_entity_act.argtypes = [vp, vp, vp, vp, C.POINTER(WrsnEntityOut), C.POINTER(WrsnEntityActOut)]
+    lib.wrsn_entity_act.restype = C.c_int
     lib.wrsn_set_obs_reuse.argtypes = [vp, C.c_int32]
     lib.wrsn_set_obs_reuse.restype = C.c_int
     lib.wrsn_set_obs_format.argtypes = [vp, C.c_int32]
@@ -308,6 +317,13 @@ class RawHandle:
         """wrsn_rollout_collect on packed entity rows (`obs` may be absent); consume=False leaves the requests to a following image collect."""
         o = self._out(**out_ptrs)
         check(self.lib, self.lib.wrsn_rollout_collect_entities(self._h, C.byref(buffers), C.byref(o), self._ent(ent_ptrs), 1 if consume else 0))
+
+    def entity_act(self, actors_ptr, agent_ptr, eps_ptr=0, ent_ptrs=None, action=0, action_f64=0, logp=0, mean=0, log_std=0):
+        """wrsn_entity_act: sample the packed actors at actors_ptr ([M, wrsn_entity_actor_floats()] float32) on the entity rows of
+        ent_ptrs ((node, mc, env) addresses, None = the registered buffers) for the chargers at agent_ptr; eps_ptr 0 = the mode."""
+        o = WrsnEntityActOut(action or None, action_f64 or None, logp or None, mean or None, log_std or None)
+        check(self.lib, self.lib.wrsn_entity_act(self._h, C.c_void_p(actors_ptr or None), C.c_void_p(agent_ptr or None), C.c_void_p(eps_ptr or None),
+                                                 self._ent(ent_ptrs), C.byref(o)))
 
     def set_obs_reuse(self, on):
         check(self.lib, self.lib.wrsn_set_obs_reuse(self._h, 1 if on else 0))

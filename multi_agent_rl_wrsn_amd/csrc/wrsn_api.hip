@@ -108,6 +108,8 @@ struct wrsn_handle {
     int32_t* d_pool_cur = nullptr; int32_t* d_pool_swaps = nullptr;
     int32_t* d_pairs = nullptr; int32_t* d_pair_n = nullptr;
     WrsnEntityOut ent{};            // wrsn_set_entity_out: the caller's entity-observation buffers (node == nullptr: off, the default)
+    // wrsn_entity_act (allocated by its first call): the head's inputs [B, WRSN_ENTPOL_FEAT], the row lists [M, B] and counters [8] per charger
+    float* ep_feat = nullptr; int32_t* ep_list = nullptr; int32_t* ep_cnt = nullptr;
 };
 
 namespace {
@@ -944,6 +946,35 @@ int wrsn_rollout_collect_entities(wrsn_t* h, const wrsn_transition_buffers* buf,
     const int B = h->dev.B;
     hipLaunchKernelGGL(wrsn_tr_collect_entities_kernel, dim3((B + WRSN_ENT_ROWS - 1) / WRSN_ENT_ROWS), dim3(64 * WRSN_ENT_ROWS), 0, h->stream, B, h->dev.M,
                        h->dev.N, t, out->agent_id, out->reward, out->now, h->dev.row_state, e, (int)(consume != 0));
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+int32_t wrsn_entity_actor_floats(void) { return WRSN_EP_FLOATS; }
+
+int wrsn_entity_act(wrsn_t* h, const float* actors, const int32_t* agent_id, const float* eps, const wrsn_entity_out* ent,
+                    const wrsn_entity_act_out* out) {
+    if (!h || !actors || !agent_id || !out || !out->action || !out->logp)
+        return fail(WRSN_ERR_ARG, "wrsn_entity_act needs actors, agent_id, out->action and out->logp");
+    WrsnEntityOut e{};
+    if (ent) { const int rc = entity_out(ent, &e); if (rc) return rc; }
+    else if (h->ent.node) e = h->ent;
+    else return fail(WRSN_ERR_ARG, "no entity buffers: pass wrsn_entity_out or register them with wrsn_set_entity_out");
+    if ((uintptr_t)actors % 16) return fail(WRSN_ERR_ARG, "wrsn_entity_act: actors must be 16-byte aligned");
+    WRSN_ON_DEVICE(h);
+    const int B = h->dev.B, M = h->dev.M;
+    if (!h->ep_cnt) {
+        int rc = dalloc(h, &h->ep_feat, (size_t)B * WRSN_ENTPOL_FEAT);
+        if (!rc) rc = dalloc(h, &h->ep_list, (size_t)B * M);
+        if (!rc) rc = dalloc(h, &h->ep_cnt, (size_t)WRSN_MAX_MC);
+        if (rc) return rc;
+    }
+    WrsnEntActOut o; o.action = out->action; o.action_f64 = out->action_f64; o.logp = out->logp; o.mean = out->mean; o.log_std = out->log_std;
+    HIPCHK(hipMemsetAsync(h->ep_cnt, 0, WRSN_MAX_MC * sizeof(int32_t), h->stream));
+    hipLaunchKernelGGL(wrsn_entpol_group_kernel, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, M, agent_id, h->ep_list, h->ep_cnt);
+    hipLaunchKernelGGL(wrsn_entpol_trunk_kernel, dim3(B), dim3(256), WRSN_EP_T_LDS, h->stream, B, M, h->dev.N, actors, agent_id, e, h->ep_feat);
+    hipLaunchKernelGGL(wrsn_entpol_head_kernel, dim3((B + WRSN_EP_HEAD_ROWS - 1) / WRSN_EP_HEAD_ROWS + M), dim3(256), WRSN_EP_H_LDS, h->stream, B, M,
+                       actors, (const float*)h->ep_feat, (const int32_t*)h->ep_list, (const int32_t*)h->ep_cnt, eps, o);
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }

@@ -277,3 +277,295 @@ __global__ void __launch_bounds__(64 * WRSN_ENT_ROWS) wrsn_tr_collect_entities_k
     for (int i = lane; i < A; i += 64) t.action[q * A + i] = t.pend_action[pslot * A + i];
     if (lane == 0) { t.reward[q] = (float)reward[e]; t.logp[q] = t.pend_logp[pslot]; t.now[q] = now[e]; t.env[q] = e; }
 }
+
+// ------------------------------------------------------------------ entity policy: acting from entity rows (wrsn_entity_act)
+// The actor of build_entity_networks (ippo.py) evaluated on the device, one packed float32 block per charger (layout: include/wrsn_hip.h;
+// every Linear stored [in, out], its bias behind it).  Three launches on the handle's stream:
+//   wrsn_entpol_group_kernel   row lists per charger: one ballot per charger and wave, one atomicAdd per wave into M counters
+//   wrsn_entpol_trunk_kernel   one 256-thread block per row: node MLP on the matrix cores, the pools, the charger MLP -> feat[e][200]
+//   wrsn_entpol_head_kernel    one block per (charger, tile of <= 32 of its rows): head1, head2 on the matrix cores, the six 128-long
+//                              dot products, the clamp, the sample and the log-probability
+// All matrix products are v_mfma_f32_32x32x2_f32 in the TRANSPOSED orientation: D[unit i][column j] = sum_k W[k][i] X[k][j], units in D's
+// rows, nodes (trunk) or batch rows (head) in D's columns.  The A operand of k-pair kk is W[2 kk + (l >> 5)][32 t + (l & 31)]: two runs of
+// 32 consecutive floats of the [in, out] block.  An accumulator register r of a finished layer holds, for column l & 31, unit
+// u(r) = (r & 3) + 8 (r >> 2) in lanes 0..31 and unit u(r) + 4 in lanes 32..63: that IS a B operand for the k-pair (u, u + 4), so the node
+// MLP's second layer takes the first layer's 32 registers as they are, in a fixed permutation of k, with no trip through LDS.
+// What a row's outputs depend on: its own entity rows, its charger's block, its eps.  Every sum has a fixed order that nothing outside
+// the row enters: a column's MFMA chain is k-ordered whatever the column; a wave folds the 32 columns of a tile by a fixed butterfly and
+// adds its tiles in tile order; the four waves are added in wave order; the six final dot products are four chains over k mod 4 each.
+// The order of the row lists may differ from run to run; the column a row lands in changes no bit of it.
+// Registers: the pools are folded tile by tile, so a lane carries two sums and two maxima, not 64 values: 91 VGPRs + 32 AGPRs, no scratch,
+// four waves per SIMD (profiles/entity_act_kernel_resource_usage.csv).
+#define WRSN_ENTPOL_FEAT 200
+#define WRSN_EP_NODE1 0
+#define WRSN_EP_NODE1_B 512
+#define WRSN_EP_NODE2 576
+#define WRSN_EP_NODE2_B 4672
+#define WRSN_EP_MC1 4736
+#define WRSN_EP_MC1_B 5120
+#define WRSN_EP_MC2 5152
+#define WRSN_EP_MC2_B 6176
+#define WRSN_EP_HEAD1 6208
+#define WRSN_EP_HEAD1_B 31808
+#define WRSN_EP_HEAD2 31936
+#define WRSN_EP_HEAD2_B 48320
+#define WRSN_EP_MEAN 48448
+#define WRSN_EP_MEAN_B 48832
+#define WRSN_EP_LSTD 48835
+#define WRSN_EP_LSTD_B 49219
+#define WRSN_EP_FLOATS 49224                                  // 49 222 rounded up to a multiple of 4
+// LDS of the trunk block, in floats: node1 / node2 with their biases (the first WRSN_EP_MC1 floats of the block), the pools of the four
+// waves, their live-node counts, the two charger layers
+#define WRSN_EP_T_SUM WRSN_EP_MC1
+#define WRSN_EP_T_MAX (WRSN_EP_T_SUM + 256)
+#define WRSN_EP_T_CNT (WRSN_EP_T_MAX + 256)
+#define WRSN_EP_T_G1 (WRSN_EP_T_CNT + 4)
+#define WRSN_EP_T_G2 (WRSN_EP_T_G1 + 256)
+#define WRSN_EP_T_LDS ((WRSN_EP_T_G2 + 256) * 4)              // bytes
+// LDS of the head block, in floats: the feature tile [32][201] (later the second layer's output [128][32]), the first layer's output
+// [128][32] (later the six dot products [6][32])
+#define WRSN_EP_H_LD 201
+#define WRSN_EP_H_Z (32 * WRSN_EP_H_LD)
+#define WRSN_EP_H_LDS ((WRSN_EP_H_Z + 128 * 32) * 4)          // bytes
+#define WRSN_EP_HEAD_ROWS 32                                  // rows (columns of the product) per head block
+
+struct WrsnEntActOut { float* action; double* action_f64; float* logp; float* mean; float* log_std; };   // mirrors wrsn_entity_act_out
+
+WDEV int wrsn_ep_unit(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }   // row of D that register r holds in lane half h
+
+// v[r] of the 32 lanes of a half wave folded into the lanes with (l & 15) == r (of each half): sum or max over the 32 columns in a fixed
+// butterfly -- four halving steps (8 + 4 + 2 + 1 exchanges) and one plain exchange, not 80
+template <bool MAX>
+WDEV float wrsn_ep_fold16(float (&v)[16], int lane) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const int m = 8 >> s;                                 // lane distance and half the number of values left
+        const bool up = (lane & m) != 0;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            if (r < m) {
+                const float a = v[r], b = v[r + m];
+                const float got = __shfl_xor(up ? a : b, m);
+                const float keep = up ? b : a;
+                v[r] = MAX ? fmaxf(keep, got) : keep + got;
+            }
+        }
+    }
+    const float o = __shfl_xor(v[0], 16);
+    return MAX ? fmaxf(v[0], o) : v[0] + o;
+}
+
+__global__ void __launch_bounds__(64) wrsn_entpol_group_kernel(int B, int M, const int32_t* __restrict__ agent_id, int32_t* __restrict__ list,
+                                                               int32_t* cnt) {
+    const int lane = (int)threadIdx.x, e = (int)blockIdx.x * 64 + lane;
+    const int a = e < B ? agent_id[e] : -1;
+    for (int c = 0; c < M; ++c) {
+        const unsigned long long m = __ballot(a == c);
+        if (m == 0ull) continue;                              // wave-uniform
+        int base = 0;
+        if (lane == 0) base = atomicAdd(&cnt[c], __popcll(m));
+        base = wrsn_wave_first(base);
+        if (a == c) list[(size_t)c * B + base + __popcll(m & ((1ull << lane) - 1ull))] = e;
+    }
+}
+
+__global__ void __launch_bounds__(256) wrsn_entpol_trunk_kernel(int B, int M, int N, const float* __restrict__ actors,
+                                                                const int32_t* __restrict__ agent_id, WrsnEntityOut ent, float* __restrict__ feat) {
+    extern __shared__ double smem[];
+    float* sW = (float*)smem;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
+    const int e = (int)blockIdx.x;
+    if (e >= B) return;
+    const int aid = wrsn_wave_first(agent_id[e]);
+    if (aid < 0 || aid >= M) return;
+    const float* blk = actors + (size_t)aid * WRSN_EP_FLOATS;
+    {   // node1, node2 and their biases: 1 184 chunks of 16 bytes
+        const auto src = wrsn_global((const WrsnU4*)blk);
+        WrsnU4* dst = (WrsnU4*)sW;
+        for (int i = tid; i < WRSN_EP_MC1 / 4; i += 256) dst[i] = wrsn_ld_u4(src + i);
+    }
+    __syncthreads();
+    float psum[2] = {0.f, 0.f}, pmax[2] = {0.f, 0.f}, cnt = 0.f;   // lane (r, h) of a wave: units 32 t2 + u(r) + 4 h, r = lane & 15
+    const float* nrow = ent.node + (size_t)e * N * WRSN_ENT_NODE_F;
+    const int ntile = (N + 31) >> 5;
+    for (int tile = wave; tile < ((ntile + 3) & ~3); tile += 4) {   // every wave the same number of rounds: the folds below are exchanges
+        const bool on = tile < ntile;                          // wave-uniform; a round without a tile folds zeros
+        const int n = tile * 32 + col, srcn = n < N ? n : N - 1;   // clamped: a column beyond N is computed on zeros and pooled nowhere
+        const auto p = wrsn_global((const WrsnU4*)(nrow + (size_t)srcn * WRSN_ENT_NODE_F));
+        const WrsnU4 c0 = wrsn_ld_u4(p), c1 = wrsn_ld_u4(p + 1);
+        const bool alive = n < N && __int_as_float((int)c1.w) == 1.f;
+        float x[4];                                           // features 2 kk + h of the column, zeros unless the node is alive (a select)
+        x[0] = __int_as_float((int)(h ? c0.y : c0.x)); x[1] = __int_as_float((int)(h ? c0.w : c0.z));
+        x[2] = __int_as_float((int)(h ? c1.y : c1.x)); x[3] = __int_as_float((int)(h ? c1.w : c1.z));
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) x[kk] = alive ? x[kk] : 0.f;
+        wrsn_v16f h1[2];
+        if (on) {
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                wrsn_v16f acc;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] = sW[WRSN_EP_NODE1_B + 32 * t + wrsn_ep_unit(r, h)];
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk)
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sW[WRSN_EP_NODE1 + (2 * kk + h) * 64 + 32 * t + col], x[kk], acc, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) h1[t][r] = fmaxf(acc[r], 0.f);
+            }
+        }
+#pragma unroll
+        for (int t2 = 0; t2 < 2; ++t2) {
+            float v[16], w[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) v[r] = 0.f;
+            if (on) {
+                wrsn_v16f acc;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] = sW[WRSN_EP_NODE2_B + 32 * t2 + wrsn_ep_unit(r, h)];
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)              // register r of h1[t]: the k-pair (u, u + 4), u = 32 t + (r & 3) + 8 (r >> 2)
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sW[WRSN_EP_NODE2 + (32 * t + wrsn_ep_unit(r, h)) * 64 + 32 * t2 + col], h1[t][r], acc, 0, 0, 0);
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) v[r] = alive ? fmaxf(acc[r], 0.f) : 0.f;
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) w[r] = v[r];
+            psum[t2] += wrsn_ep_fold16<false>(v, lane);        // the tile's 32 columns, then the wave's tiles in tile order
+            pmax[t2] = fmaxf(pmax[t2], wrsn_ep_fold16<true>(w, lane));
+        }
+        cnt += (on && alive) ? 1.f : 0.f;
+    }
+    // ---- the four waves: through LDS, added in wave order below
+    cnt += __shfl_xor(cnt, 1); cnt += __shfl_xor(cnt, 2); cnt += __shfl_xor(cnt, 4); cnt += __shfl_xor(cnt, 8); cnt += __shfl_xor(cnt, 16);
+    if ((lane & 16) == 0) {
+#pragma unroll
+        for (int t2 = 0; t2 < 2; ++t2) {
+            const int unit = 32 * t2 + wrsn_ep_unit(lane & 15, h);
+            sW[WRSN_EP_T_SUM + 64 * wave + unit] = psum[t2]; sW[WRSN_EP_T_MAX + 64 * wave + unit] = pmax[t2];
+        }
+        if (lane == 0) sW[WRSN_EP_T_CNT + wave] = cnt;
+    }
+    // ---- the charger MLP on the VALU: thread (c, o) = unit o of charger c
+    const float* mrow = ent.mc + (size_t)e * M * WRSN_ENT_MC_F;
+    const int c = tid >> 5, o = tid & 31;
+    if (c < M) {
+        float s = blk[WRSN_EP_MC1_B + o];
+#pragma unroll
+        for (int k = 0; k < WRSN_ENT_MC_F; ++k) s = fmaf(mrow[c * WRSN_ENT_MC_F + k], blk[WRSN_EP_MC1 + k * 32 + o], s);
+        sW[WRSN_EP_T_G1 + tid] = fmaxf(s, 0.f);
+    }
+    __syncthreads();
+    if (c < M) {
+        float s = blk[WRSN_EP_MC2_B + o];
+#pragma unroll 8
+        for (int k = 0; k < 32; ++k) s = fmaf(sW[WRSN_EP_T_G1 + 32 * c + k], blk[WRSN_EP_MC2 + k * 32 + o], s);
+        sW[WRSN_EP_T_G2 + tid] = fmaxf(s, 0.f);
+    }
+    __syncthreads();
+    float* frow = feat + (size_t)e * WRSN_ENTPOL_FEAT;
+    if (tid < 64) {
+        const float n_alive = ((sW[WRSN_EP_T_CNT] + sW[WRSN_EP_T_CNT + 1]) + sW[WRSN_EP_T_CNT + 2]) + sW[WRSN_EP_T_CNT + 3];
+        const float sum = ((sW[WRSN_EP_T_SUM + tid] + sW[WRSN_EP_T_SUM + 64 + tid]) + sW[WRSN_EP_T_SUM + 128 + tid]) + sW[WRSN_EP_T_SUM + 192 + tid];
+        const float mx = fmaxf(fmaxf(sW[WRSN_EP_T_MAX + tid], sW[WRSN_EP_T_MAX + 64 + tid]), fmaxf(sW[WRSN_EP_T_MAX + 128 + tid], sW[WRSN_EP_T_MAX + 192 + tid]));
+        frow[tid] = sum / fmaxf(n_alive, 1.f);
+        frow[64 + tid] = mx;                                  // ReLU outputs pooled from 0: zeros when no node is alive
+    } else if (tid < 96) {
+        const int u = tid - 64;
+        float sa = 0.f, so = 0.f, na = 0.f;
+        for (int k = 0; k < M; ++k) {
+            const float g = sW[WRSN_EP_T_G2 + 32 * k + u];
+            const bool al = mrow[k * WRSN_ENT_MC_F + 4] == 1.f, self = mrow[k * WRSN_ENT_MC_F + 3] == 1.f;   // ENT_MC["alive"], ENT_MC["is_self"]
+            sa += al ? g : 0.f; na += al ? 1.f : 0.f; so += self ? g : 0.f;
+        }
+        frow[128 + u] = sa / fmaxf(na, 1.f);
+        frow[160 + u] = so;
+    } else if (tid < 104) {
+        const int k = tid - 96;
+        const float v = ent.env[(size_t)e * WRSN_ENT_ENV_F + k];
+        frow[192 + k] = k == 4 ? v * (1.f / (float)M) : k == 5 ? v * (1.f / (float)(N > 1 ? N : 1)) : v;   // ENT_ENV["agent"] / M, ENT_ENV["n_node"] / N
+    }
+}
+
+__global__ void __launch_bounds__(256) wrsn_entpol_head_kernel(int B, int M, const float* __restrict__ actors, const float* __restrict__ feat,
+                                                               const int32_t* __restrict__ list, const int32_t* __restrict__ cnt,
+                                                               const float* __restrict__ eps, WrsnEntActOut out) {
+    extern __shared__ double smem[];
+    float* sF = (float*)smem;
+    float* sZ = sF + WRSN_EP_H_Z;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
+    // which (charger, tile) this block is: the tiles of charger 0, then of charger 1, ...
+    int b = (int)blockIdx.x, a = -1, rows = 0, first = 0;
+    for (int c = 0; c < M; ++c) {
+        int k = cnt[c]; k = k < 0 ? 0 : (k > B ? B : k);
+        const int nt = (k + WRSN_EP_HEAD_ROWS - 1) / WRSN_EP_HEAD_ROWS;
+        if (a < 0) {
+            if (b < nt) { a = c; first = WRSN_EP_HEAD_ROWS * b; rows = k - first < WRSN_EP_HEAD_ROWS ? k - first : WRSN_EP_HEAD_ROWS; }
+            else b -= nt;
+        }
+    }
+    if (a < 0) return;                                        // block-uniform: more blocks than tiles
+    const int32_t* mine = list + (size_t)a * B + first;
+    const float* blk = actors + (size_t)a * WRSN_EP_FLOATS;
+    for (int i = tid; i < WRSN_EP_HEAD_ROWS * WRSN_ENTPOL_FEAT; i += 256) {   // a column beyond `rows` repeats the last row: computed, not stored
+        const int j = i / WRSN_ENTPOL_FEAT, k = i - j * WRSN_ENTPOL_FEAT;
+        const int row = mine[j < rows ? j : rows - 1];
+        sF[j * WRSN_EP_H_LD + k] = feat[(size_t)row * WRSN_ENTPOL_FEAT + k];
+    }
+    __syncthreads();
+    {   // head1: wave w holds units 32 w .. 32 w + 31 of all 32 columns
+        wrsn_v16f acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = blk[WRSN_EP_HEAD1_B + 32 * wave + wrsn_ep_unit(r, h)];
+        const float* wa = blk + WRSN_EP_HEAD1 + h * 128 + 32 * wave + col;
+        const float* xb = sF + col * WRSN_EP_H_LD + h;
+#pragma unroll 10
+        for (int kk = 0; kk < WRSN_ENTPOL_FEAT / 2; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[kk * 256], xb[2 * kk], acc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sZ[(32 * wave + wrsn_ep_unit(r, h)) * 32 + col] = fmaxf(acc[r], 0.f);
+    }
+    __syncthreads();
+    {   // head2
+        wrsn_v16f acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = blk[WRSN_EP_HEAD2_B + 32 * wave + wrsn_ep_unit(r, h)];
+        const float* wa = blk + WRSN_EP_HEAD2 + h * 128 + 32 * wave + col;
+        const float* xb = sZ + h * 32 + col;
+#pragma unroll 8
+        for (int kk = 0; kk < 64; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[kk * 256], xb[kk * 64], acc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sF[(32 * wave + wrsn_ep_unit(r, h)) * 32 + col] = fmaxf(acc[r], 0.f);   // the feature tile is dead
+    }
+    __syncthreads();
+    if (tid < 192) {                                          // six dot products per column: thread (d, j); four k-ordered chains over k mod 4, the
+        const int j = tid & 31, d = tid >> 5;                 // bias in the first, added as (0 + 1) + (2 + 3): a quarter of the chain length
+        const float* w = blk + (d < 3 ? WRSN_EP_MEAN + d : WRSN_EP_LSTD + d - 3);
+        float s0 = d < 3 ? blk[WRSN_EP_MEAN_B + d] : blk[WRSN_EP_LSTD_B + d - 3], s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll 4
+        for (int k = 0; k < 128; k += 4) {
+            s0 = fmaf(sF[k * 32 + j], w[3 * k], s0); s1 = fmaf(sF[(k + 1) * 32 + j], w[3 * k + 3], s1);
+            s2 = fmaf(sF[(k + 2) * 32 + j], w[3 * k + 6], s2); s3 = fmaf(sF[(k + 3) * 32 + j], w[3 * k + 9], s3);
+        }
+        sZ[d * 32 + j] = (s0 + s1) + (s2 + s3);               // head1's output is dead
+    }
+    __syncthreads();
+    if (tid < rows) {
+        const int e = mine[tid];
+        float lp = 0.f;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const float mu = sZ[d * 32 + tid];
+            const float ls = fminf(fmaxf(sZ[(3 + d) * 32 + tid], -4.f), 1.f);
+            const float ep = eps ? eps[(size_t)e * 3 + d] : 0.f;
+            const float x = fmaf(expf(ls), ep, mu);
+            lp += -0.5f * ep * ep - ls;
+            out.action[(size_t)e * 3 + d] = x;
+            if (out.action_f64) out.action_f64[(size_t)e * 3 + d] = (double)x;
+            if (out.mean) out.mean[(size_t)e * 3 + d] = mu;
+            if (out.log_std) out.log_std[(size_t)e * 3 + d] = ls;
+        }
+        out.logp[e] = lp - 2.7568156f;                        // 1.5 log(2 pi)
+    }
+}

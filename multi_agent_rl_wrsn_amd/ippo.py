@@ -757,6 +757,19 @@ def build_entity_networks(n_agent_rows):
     return EntityActor, EntityCritic
 
 
+def pack_entity_actor(actor):
+    """The `EntityActor` as the float32 block `wrsn_entity_act` reads (layout: include/wrsn_hip.h): node1, node2, mc1, mc2, head1, head2,
+    mean, log_std, every Linear transposed to [in, out] and followed by its bias, zeros up to a multiple of 4 floats.  A new tensor [P] on
+    the actor's device; it does not follow later changes of the parameters."""
+    torch = _torch()
+    t = actor.trunk
+    parts = []
+    for layer in (t.node1, t.node2, t.mc1, t.mc2, t.head1, t.head2, actor.mean, actor.log_std):
+        parts += [layer.weight.detach().t().reshape(-1), layer.bias.detach().reshape(-1)]
+    flat = torch.cat([p.to(torch.float32) for p in parts])
+    return torch.cat([flat, flat.new_zeros((-flat.numel()) % 4)])
+
+
 class EntityPPOLearner(PPOLearner):
     """`PPOLearner` with the set networks of `build_entity_networks` over packed entity rows and 3-vector actions.  `evaluate`,
     `get_value`, `cal_rt_adv`, `minibatch_loss`, `update`, the data-parallel gradient exchange and the checkpoints are inherited.
@@ -775,6 +788,11 @@ class EntityPPOLearner(PPOLearner):
 
     def _forward(self, net, x, inference=False):
         return net(x)
+
+    def packed_actors(self):
+        """The actors as `wrsn_entity_act` takes them: a new float32 tensor [M, P] on the device, built from the parameters as they are
+        now.  Nothing here keeps it: whoever does must rebuild it after every `update` and every checkpoint load."""
+        return self.torch.stack([pack_entity_actor(a) for a in self.actors]).contiguous()
 
     def get_action(self, agent_id, states):
         """Packed rows [n, R] -> (action [n, 3], log-prob [n]).  Chunks of `infer_chunk` rows, a short chunk padded to its bucket by
@@ -796,9 +814,14 @@ class EntityPPOLearner(PPOLearner):
 
 class BatchedEntityIPPO(EntityPPOLearner):
     """The roll-out of `BatchedIPPO` on entity rows: `VecWRSN(entities=True)` (no image needed: `render=False`), the set policy's
-    3-vector is the action `env.step` takes, and the transitions live in `EntityTransitionBuffers`."""
+    3-vector is the action `env.step` takes, and the transitions live in `EntityTransitionBuffers`.
 
-    def __init__(self, args, env, device=None, model_path=None, capacity=None, infer_chunk=1024, process_group=None, log=None, min_bucket=16):
+    fused_policy : True = the device chooses the actions itself (`VecWRSN.entity_act`, `wrsn_entity_act`): one call on the entity rows the
+                   environment holds, with the actors packed at the start of the roll-out (`packed_actors`) and standard-normal draws
+                   of `torch.randn`; no row gathering and no per-charger forward pass.  False (the default): `get_action` per charger."""
+
+    def __init__(self, args, env, device=None, model_path=None, capacity=None, infer_chunk=1024, process_group=None, log=None, min_bucket=16,
+                 fused_policy=False):
         if not getattr(env, "entities", False):
             raise ValueError("BatchedEntityIPPO needs a VecWRSN with the entity observation (entities=True)")
         super().__init__(args, env.num_agent, device if device is not None else env.device, model_path, infer_chunk, process_group, min_bucket)
@@ -807,16 +830,55 @@ class BatchedEntityIPPO(EntityPPOLearner):
         self.timers = {"env_s": 0.0, "policy_s": 0.0, "glue_s": 0.0, "train_s": 0.0, "launches": 0, "requests": 0}
         self.log = log
         self._req = None
+        self.fused_policy = bool(fused_policy)
+        self._packed = None                                   # packed_actors() of the weights as they are now, or None: rebuilt before use
 
     _sync_time = BatchedIPPO._sync_time
-    roll_out = BatchedIPPO.roll_out
     train = BatchedIPPO.train
+
+    def roll_out(self, max_launches=100000, fresh_episodes=False):
+        if self.fused_policy:
+            self._packed = self.packed_actors()
+        return BatchedIPPO.roll_out(self, max_launches, fresh_episodes)
+
+    def update(self, id, batch, shuffle=np.random.shuffle):
+        self._packed = None                                   # the weights change: never carried across an update
+        return super().update(id, batch, shuffle)
 
     def _stored_actions(self, actions):
         return actions
 
+    def _step_batch_fused(self):
+        """`step_batch` with the policy on the device: draw eps, `entity_act`, record, step, collect."""
+        torch, env = self.torch, self.env
+        r = self._req
+        ids = r["agent_id"].clone()
+        t0 = self._sync_time()
+        if self._packed is None:
+            self._packed = self.packed_actors()
+        eps = torch.randn((env.num_env, 3), dtype=torch.float32, device=env.device)
+        act3, act64, logp = env.entity_act(ids, self._packed, eps)
+        t1 = self._sync_time()
+        self.buffers.record(ids, act3, logp)
+        t2 = self._sync_time()
+        r = env.step(ids, act64)
+        t3 = self._sync_time()
+        bad = torch.nonzero(r["status"] < 0).flatten()
+        if bad.numel():
+            raise RuntimeError("environment rows %s report status %s" % (bad.tolist(), r["status"][bad].tolist()))
+        self.buffers.collect()
+        t4 = self._sync_time()
+        tm = self.timers
+        tm["policy_s"] += t1 - t0; tm["glue_s"] += (t2 - t1) + (t4 - t3); tm["env_s"] += t3 - t2; tm["launches"] += 1
+        tm["requests"] += int((ids >= 0).sum())
+        self.last_ids, self.last_action3 = ids, act3
+        self._req = r
+        return r
+
     def step_batch(self):
         """One launch of the batched roll-out: act for every environment that carries a request, step, collect."""
+        if self.fused_policy:
+            return self._step_batch_fused()
         torch, env = self.torch, self.env
         r = self._req
         ids = r["agent_id"].clone()                           # the request's ids, detached from the tensor the step writes

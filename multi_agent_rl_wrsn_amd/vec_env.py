@@ -217,6 +217,39 @@ class VecWRSN:
         self._h.entities(a.data_ptr(), out["nodes"].data_ptr(), out["chargers"].data_ptr(), out["env_feat"].data_ptr())
         return out
 
+    def entity_act(self, agent_ids, packed, eps=None):
+        """`wrsn_entity_act` on the entity rows this object holds (`entities=True`): the chargers `agent_ids` [B] (< 0: row skipped) act with
+        the packed actors `packed` [M, P] (`EntityPPOLearner.packed_actors`) and the standard-normal draws `eps` [B, 3] (None: the mode).
+        Returns (action float32 [B,3], action_f64 float64 [B,3] -- what `step` takes --, logp float32 [B]): tensors this object owns and
+        writes again at the next call; skipped rows keep what they held."""
+        t = self.torch
+        if not self.entities:
+            raise ValueError("entity_act needs a VecWRSN with the entity observation (entities=True)")
+        self._bind_stream()
+        a = agent_ids
+        if not (a.dtype == t.int32 and a.device == self.device and a.is_contiguous() and a.numel() == self.num_env):
+            a = a.to(device=self.device, dtype=t.int32).reshape(-1).contiguous()
+        P = self._h.lib.wrsn_entity_actor_floats()
+        w = packed
+        if not (w.dtype == t.float32 and w.device == self.device and w.is_contiguous()):
+            w = w.to(device=self.device, dtype=t.float32).contiguous()
+        if tuple(w.shape) != (self.num_agent, P):
+            raise ValueError("packed actors must be [%d, %d], not %s" % (self.num_agent, P, list(w.shape)))
+        e = None
+        if eps is not None:
+            e = eps.to(device=self.device, dtype=t.float32).contiguous()
+            if e.numel() != 3 * self.num_env:
+                raise ValueError("eps must be [%d, 3]" % self.num_env)
+        if getattr(self, "_act", None) is None:
+            B = self.num_env
+            self._act = (t.zeros((B, 3), dtype=t.float32, device=self.device), t.zeros((B, 3), dtype=t.float64, device=self.device),
+                         t.zeros((B,), dtype=t.float32, device=self.device))
+        self._keep_act = (a, w, e)                            # alive until the launch has run
+        act, act64, logp = self._act
+        self._h.entity_act(w.data_ptr(), a.data_ptr(), e.data_ptr() if e is not None else 0, None,
+                           action=act.data_ptr(), action_f64=act64.data_ptr(), logp=logp.data_ptr())
+        return act, act64, logp
+
     def set_step_budget(self, work_units):
         self.step_budget = int(work_units)
         self._h.set_step_budget(self.step_budget)

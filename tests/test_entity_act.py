@@ -1,0 +1,437 @@
+"""Acting from entity rows (wrsn_entity_act, csrc/wrsn_rollout.h) on the emulated library.
+
+The bodies take the side (tests/sides.py): this module runs them on EmuSide, tests/test_entity_act_gpu.py on VecSide.  Memory handling,
+synthetic rows, the actors and the reference (the module in float64 on the CPU; the bound 4 * err32 + 1e-6 with err32 the module's own
+float32 error over the rows of the test) are in tests/entity_act_ref.py."""
+import numpy as np
+import pytest
+from sides import EmuSide
+
+import entity_act_ref as R
+
+B1, M1 = 96, 3
+NODES = {70: (300, 60), 33: (411, 17), 257: (421, 129)}      # node count -> (seed, targets) of the network the handle is created with
+
+
+def case1_ids():
+    """Charger 0 has 40 rows (a second head tile with a ragged end), charger 1 exactly 32, charger 2 24; no row is skipped."""
+    ids = np.array([0] * 40 + [1] * 32 + [2] * 24, np.int32)
+    np.random.default_rng(1).shuffle(ids)
+    return ids
+
+
+def make_side(Side, N, B, M, **kw):
+    from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, synth_scenario
+    seed, T = NODES[N]
+    return Side([synth_scenario(seed, N, T)] * B, DEFAULT_MC_SPEC, M, map_size=12, render=False, warm_up_time=1.0, **kw)
+
+
+_CASE1 = {}
+
+
+def case1(N):
+    """(ids, eps, node, mc, env, Ref) of case 1 at N nodes: computed once, shared by every test and both sides, never modified."""
+    if N not in _CASE1:
+        ids = case1_ids()
+        node, mc, env = R.synth_rows(5 + N, B1, N, M1, ids)
+        eps = np.random.default_rng(2).standard_normal((B1, 3)).astype(np.float32)
+        _CASE1[N] = (ids, eps, node, mc, env, R.Ref(R.make_actors(M1), R.pack_rows(node, mc, env), ids, eps))
+    return _CASE1[N]
+
+
+def case1_call(side, N=70):
+    ids, eps, node, mc, env, ref = case1(N)
+    return R.Call(side, M1, node, mc, env, ids, eps), ref
+
+
+# ------------------------------------------------------------------------------------------------------------ 1. synthetic rows
+def synthetic_rows_match(Side, N):
+    """B = 96, M = 3, every row compared.  N = 70: three node tiles, the last with 6 nodes; 33: one full tile plus one node; 257: nine
+    tiles, more than two a wave.  log_std leaves [-4, 1] on both sides on some rows."""
+    side = make_side(Side, N, B1, M1)
+    call, ref = case1_call(side, N)
+    assert ref.rows_in == list(range(B1))
+    raw = np.concatenate([R.make_actors(M1)[a].log_std.weight.detach().numpy().ravel() for a in range(M1)])
+    assert np.abs(raw).max() > 0.05                           # not the stock 0.01 head
+    ls = ref.f64["log_std"]
+    assert (ls == -4.0).any() and (ls == 1.0).any() and ((ls > -4.0) & (ls < 1.0)).any()
+    assert 0.3 < np.abs(ref.f64["mean"]).max() < 30.0
+    got = call.run()
+    ref.check(got, "%s N=%d" % (side.name, N))
+    assert call.out.guards_intact(call.out.snap())
+    side.close()
+
+
+@pytest.mark.parametrize("N", [70, 33, 257])
+def test_emulated_entity_act_synthetic_rows(N):
+    synthetic_rows_match(EmuSide, N)
+
+
+# ------------------------------------------------------------------------------------------------------------ 2. masks
+def masks_are_selects(Side):
+    """M = 8 in one handle, N = 33.  Row 0: its dead nodes hold NaN and inf; row 1: no alive node (and NaN everywhere else in its node
+    rows); row 2: no alive charger; row 3: is_self sits on another charger than agent_id (the kernel takes `own` from the rows, the
+    weights from agent_id)."""
+    B, M, N = 16, 8, 33
+    side = make_side(Side, N, B, M)
+    ids = (np.arange(B) % M).astype(np.int32)
+    node, mc, env = R.synth_rows(77, B, N, M, ids)
+    dead = node[0, :, 7] == 0
+    assert dead.any() and (~dead).any()
+    node[0, dead, :7] = np.where(np.arange(7) % 2 == 0, np.nan, np.inf).astype(np.float32)
+    node[1, :, 7] = 0.0; node[1, :, :7] = np.nan
+    mc[2, :, 4] = 0.0
+    mc[3, :, 3] = 0.0; mc[3, (int(ids[3]) + 2) % M, 3] = 1.0
+    eps = np.random.default_rng(3).standard_normal((B, 3)).astype(np.float32)
+    ref = R.Ref(R.make_actors(M), R.pack_rows(node, mc, env), ids, eps)
+    assert all(np.isfinite(ref.f64[k]).all() for k in ref.f64)
+    call = R.Call(side, M, node, mc, env, ids, eps)
+    got = call.run()
+    assert all(np.isfinite(got[k]).all() for k in got)
+    ref.check(got, "%s masks" % side.name)
+    side.close()
+
+
+def test_emulated_entity_act_masks():
+    masks_are_selects(EmuSide)
+
+
+# ------------------------------------------------------------------------------------------------------------ 3. independence
+def rows_are_independent(Side):
+    """A row's five outputs are bit-identical in the batch of case 1, in a batch where every other row's charger and content changed,
+    and at another row index; two identical calls give identical bytes."""
+    side = make_side(Side, 70, B1, M1)
+    ids, eps, node, mc, env, _ = case1(70)
+    call, _ = case1_call(side)
+    call.run()
+    first = call.out.snap()
+    call.out.fill(); call.run()
+    second = call.out.snap()
+    assert all(np.array_equal(first[k], second[k]) for k in first)
+    base = call.out.arrays(first)
+    e, e2 = 5, 77
+    # every other row: another charger, other content, other draws
+    ids_b = ((ids + 1) % M1).astype(np.int32); ids_b[e] = ids[e]
+    node_b, mc_b, env_b = R.synth_rows(991, B1, 70, M1, ids_b)
+    eps_b = np.random.default_rng(8).standard_normal((B1, 3)).astype(np.float32)
+    for dst, src in ((node_b, node), (mc_b, mc), (env_b, env), (eps_b, eps)):
+        dst[e] = src[e]
+    got_b = R.Call(side, M1, node_b, mc_b, env_b, ids_b, eps_b).run()
+    # the same row at index e2 of that batch
+    ids_c = ids_b.copy(); ids_c[e2] = ids[e]; ids_c[e] = (ids[e] + 1) % M1
+    for dst, src in ((node_b, node), (mc_b, mc), (env_b, env), (eps_b, eps)):
+        dst[e2] = src[e]; dst[e] = src[e2]
+    got_c = R.Call(side, M1, node_b, mc_b, env_b, ids_c, eps_b).run()
+    bits = lambda x: np.atleast_1d(x).copy().view(np.uint8)
+    for k in R.OUTS:
+        assert np.array_equal(bits(base[k][e]), bits(got_b[k][e])), ("other batch", k)
+        assert np.array_equal(bits(base[k][e]), bits(got_c[k][e2])), ("other index", k)
+    assert not np.array_equal(base["action"][e2], got_b["action"][e2])
+    side.close()
+
+
+def test_emulated_entity_act_independence():
+    rows_are_independent(EmuSide)
+
+
+# ------------------------------------------------------------------------------------------------------------ 4. extent
+def extent_is_respected(Side):
+    """Guard bytes around every output; skipped rows (-1, -2) keep the fill pattern in all five outputs; action_f64 == action exactly;
+    eps = NULL gives action == mean and logp == -sum log_std - 1.5 log 2 pi within the bound."""
+    side = make_side(Side, 70, B1, M1)
+    ids, eps, node, mc, env, _ = case1(70)
+    ids = ids.copy(); skipped = [0, 17, 40, 63, 95]
+    ids[skipped] = [-1, -2, -1, -2, -1]
+    call = R.Call(side, M1, node, mc, env, ids, None)
+    got = call.run()
+    snap = call.out.snap()
+    assert call.out.guards_intact(snap)
+    asked = [e for e in range(B1) if ids[e] >= 0]
+    for e in range(B1):
+        assert call.out.row_untouched(snap, e) == (e in skipped), e
+    for k in R.OUTS:                                           # no 4-byte slot of a written row keeps the pattern
+        assert not (np.ascontiguousarray(got[k][asked]).view(np.uint32) == R.PATTERN * 0x01010101).any(), k
+    assert np.array_equal(got["action_f64"][asked], got["action"][asked].astype(np.float64))
+    assert np.array_equal(got["action"][asked], got["mean"][asked])
+    ref = R.Ref(R.make_actors(M1), R.pack_rows(node, mc, env), ids, None)
+    ref.check(got, "%s eps=NULL" % side.name)
+    want = -ref.f64["log_std"].sum(1) - R.LOG_2PI_15
+    assert np.abs(got["logp"][asked] - want[asked]).max() <= 4 * ref.err32["logp"] + 1e-6
+    # mean and log_std may be left out
+    call.out.fill()
+    got2 = call.run(mean=0, log_std=0, action_f64=0)
+    snap2 = call.out.snap()
+    assert all((snap2[k] == R.PATTERN).all() for k in ("mean", "log_std", "action_f64"))
+    assert np.array_equal(got2["action"][asked], got["action"][asked]) and np.array_equal(got2["logp"][asked], got["logp"][asked])
+    side.close()
+
+
+def test_emulated_entity_act_extent():
+    extent_is_respected(EmuSide)
+
+
+# ------------------------------------------------------------------------------------------------------------ 5. arguments
+def bad_arguments_leave_everything_untouched(Side):
+    """Every WRSN_ERR_ARG case leaves the outputs as they were; the valid call that follows each still gives case 1's bytes."""
+    import ctypes as C
+    from multi_agent_rl_wrsn_amd import _lib
+    side = make_side(Side, 70, B1, M1)
+    call, ref = case1_call(side)
+    call.run()
+    want = call.out.snap()
+    ref.check(call.out.arrays(want), "%s arguments" % side.name)
+    ent = call.ent.ptrs()
+    bad = [dict(actors_ptr=0), dict(agent_ptr=0), dict(action=0), dict(logp=0), dict(actors_ptr=R.addr(call.actors) + 4),
+           dict(ent_ptrs=None)]                                  # nothing is registered on this handle
+    for k in range(3):
+        bad.append(dict(ent_ptrs=tuple(0 if j == k else p for j, p in enumerate(ent))))
+        bad.append(dict(ent_ptrs=tuple(p + 4 if j == k else p for j, p in enumerate(ent))))
+
+    def out_null():
+        h = side.handle
+        e = _lib.WrsnEntityOut(*ent)
+        _lib.check(h.lib, h.lib.wrsn_entity_act(h._h, C.c_void_p(R.addr(call.actors)), C.c_void_p(R.addr(call.ids)), C.c_void_p(R.addr(call.eps)),
+                                                C.byref(e), None))
+
+    for case in bad + [out_null]:
+        call.out.fill()
+        before = call.out.snap()
+        with pytest.raises(_lib.WrsnError) as ei:
+            out_null() if case is out_null else call.run(ent=case.get("ent_ptrs", "own"), **{k: v for k, v in case.items() if k != "ent_ptrs"})
+        R.sync(side)
+        assert ei.value.code == -1, case
+        after = call.out.snap()
+        assert all(np.array_equal(before[k], after[k]) for k in before), case
+        call.run()
+        again = call.out.snap()
+        assert all(np.array_equal(want[k], again[k]) for k in want), case
+    side.close()
+
+
+def test_emulated_entity_act_bad_arguments():
+    bad_arguments_leave_everything_untouched(EmuSide)
+
+
+# ------------------------------------------------------------------------------------------------------------ 6. layout
+def hand_built_block(actor):
+    """The block as include/wrsn_hip.h describes it, in numpy: every Linear transposed to [in, out] and followed by its bias, in the
+    order node1, node2, mc1, mc2, head1, head2, mean, log_std; zeros up to a multiple of 4."""
+    sd = {k: v.detach().numpy() for k, v in actor.state_dict().items()}
+    off = {"trunk.node1": (0, 512, 8, 64), "trunk.node2": (576, 4672, 64, 64), "trunk.mc1": (4736, 5120, 12, 32), "trunk.mc2": (5152, 6176, 32, 32),
+           "trunk.head1": (6208, 31808, 200, 128), "trunk.head2": (31936, 48320, 128, 128), "mean": (48448, 48832, 128, 3),
+           "log_std": (48835, 49219, 128, 3)}
+    blk = np.zeros(49224, np.float32)
+    for name, (w0, b0, k_in, k_out) in off.items():
+        w, b = sd[name + ".weight"], sd[name + ".bias"]
+        assert w.shape == (k_out, k_in)
+        for k in range(k_in):
+            blk[w0 + k * k_out:w0 + (k + 1) * k_out] = w[:, k]
+        assert b0 == w0 + k_in * k_out
+        blk[b0:b0 + k_out] = b
+    return blk
+
+
+def layout_matches_the_header(lib):
+    from multi_agent_rl_wrsn_amd import _lib, pack_entity_actor
+    actor = R.make_actors(M1)[1]
+    mine = pack_entity_actor(actor)
+    assert mine.dtype.is_floating_point and mine.element_size() == 4
+    assert int(lib.wrsn_entity_actor_floats()) == mine.numel() == 49224 and mine.numel() % 4 == 0
+    assert np.array_equal(mine.numpy(), hand_built_block(actor))
+    assert (mine.numpy()[49222:] == 0).all() and _lib.ENTPOL_FEAT == 200
+
+
+def test_emulated_entity_actor_layout():
+    from emu_env import emu_lib
+    layout_matches_the_header(emu_lib())
+
+
+# ------------------------------------------------------------------------------------------------------------ 7. against the simulator
+def registered_rows(side):
+    """Host (node, mc, env) of the entity buffers registered on the side's handle."""
+    if side.device is None:
+        s = side.ent.snap()
+        return tuple(np.stack([side.ent.rows(s, e)[k] for e in range(side.B)]) for k in range(3))
+    side.env.synchronize()
+    e = side.env
+    return e.nodes_feat.cpu().numpy(), e.chargers_feat.cpu().numpy(), e.env_feat.cpu().numpy()
+
+
+def acts_on_the_simulators_rows(Side):
+    """Three 70-node networks with entities registered: reset, entity_act on the registered buffers (ent = NULL) with the returned
+    agent_id, step with action_f64, and record_entities / collect_entities store exactly `action` and `logp`."""
+    from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, synth_scenario
+    from test_entity_rollout import TrBuf, row_elems
+    B, M = 3, 3
+    side = Side([synth_scenario(300 + e, 70, 60) for e in range(B)], DEFAULT_MC_SPEC, M, map_size=12, render=False, entities=True, auto_reset=True)
+    buf = TrBuf(side, 32, row_elems(side.N, M))
+    actors = R.to_side(side, R.packed(M))
+    out = R.OutBuf(side, B)
+    g = np.random.default_rng(4)
+    recorded = [set() for _ in range(M)]
+    side.reset()
+    for it in range(12):
+        ids = side._host()["agent_id"].astype(np.int32)
+        assert (ids >= 0).all()
+        eps = g.standard_normal((B, 3)).astype(np.float32)
+        keep = [R.to_side(side, ids), R.to_side(side, eps)]
+        side.handle.entity_act(R.addr(actors), R.addr(keep[0]), R.addr(keep[1]), None, **out.ptrs())
+        R.sync(side)
+        got = out.arrays()
+        if it == 0:
+            node, mc, env = registered_rows(side)
+            assert (env[:, 4] == ids).all()
+            R.Ref(R.make_actors(M), R.pack_rows(node, mc, env), ids, eps).check(got, "%s simulator" % side.name)
+        side.handle.rollout_record_entities(buf.c(), R.addr(keep[0]), out.ptr("action"), out.ptr("logp"))
+        R.sync(side)
+        a_ = buf.arrays()
+        for e in range(B):
+            assert np.array_equal(a_["pend_action"][e, ids[e]], got["action"][e]) and a_["pend_logp"][e, ids[e]] == got["logp"][e]
+            recorded[ids[e]].add(got["action"][e].tobytes() + got["logp"][e].tobytes())
+        side.step(ids, got["action_f64"])
+        assert (side._host()["status"] >= 0).all()
+        if side.device is None:
+            side.handle.rollout_collect_entities(buf.c(), None, True, **side._ptrs(False))
+        else:
+            side.handle.rollout_collect_entities(buf.c(), None, True, **side.env._out_ptrs())
+        R.sync(side)
+    snap = buf.snap(); a_ = buf.arrays(snap)
+    assert buf.guards_intact(snap) and int(a_["count"].sum()) > 0
+    for a in range(M):
+        for q in range(min(int(a_["count"][a]), buf.capacity)):
+            assert a_["action"][a, q].tobytes() + a_["logp"][a, q].tobytes() in recorded[a], (a, q)
+    side.close()
+
+
+def test_emulated_entity_act_on_simulator_rows():
+    acts_on_the_simulators_rows(EmuSide)
+
+
+# ------------------------------------------------------------------------------------------------------------ 8. trainer, CPU part
+def test_packed_actors_follow_the_update():
+    """packed_actors() is built from the parameters as they are: it equals pack_entity_actor per charger, and changes after update."""
+    import torch
+    from multi_agent_rl_wrsn_amd import EntityPPOLearner, pack_entity_actor
+    from test_entity_policy import _batch
+    torch.set_num_threads(2)
+    torch.manual_seed(0)
+    lr = EntityPPOLearner(dict(batch_size=48, minibatch_size=8, n_updates_per_iteration=2, lr=1e-3), 2, "cpu")
+    p0 = lr.packed_actors()
+    assert p0.shape == (2, 49224) and p0.dtype == torch.float32
+    assert torch.equal(p0[1], pack_entity_actor(lr.actors[1])) and torch.equal(p0, lr.packed_actors())
+    lr.update(0, _batch(21, 48), shuffle=np.random.RandomState(3).shuffle)
+    p1 = lr.packed_actors()
+    assert not torch.equal(p1[0], p0[0]) and torch.equal(p1[1], p0[1])       # charger 0 was updated, charger 1 was not
+    assert torch.equal(p1[0], pack_entity_actor(lr.actors[0]))
+
+
+class EmuVec:
+    """What BatchedEntityIPPO and EntityTransitionBuffers use of a VecWRSN, on an EmuSide with entities: CPU tensors that share the
+    memory the emulated library writes."""
+
+    def __init__(self, side):
+        import torch
+        self.torch, self.device, self.side = torch, torch.device("cpu"), side
+        self.num_env, self.num_agent, self.n_node, self.map_size = side.B, side.M, side.N, side.G
+        self.entities, self.auto_reset, self.state, self._h = True, side.auto_reset, None, side.handle
+        self._t = {k: torch.from_numpy(getattr(side, k)) for k in ("agent_id", "reward", "terminal", "now", "status")}
+        raw = side.ent.raw
+        shp = side.ent.shapes
+        self._e = {k: torch.from_numpy(raw[k][R.GUARD:-R.GUARD].view(np.float32).reshape(shp[k])) for k in shp}
+        self.nodes_feat, self.chargers_feat, self.env_feat = self._e["node"], self._e["mc"], self._e["env"]
+        self._act = None
+
+    def _bind_stream(self):
+        pass
+
+    def _out_ptrs(self):
+        return self.side._ptrs(False)
+
+    def _result(self):
+        r = dict(self._t); r.update(state=None, nodes=self.nodes_feat, chargers=self.chargers_feat, env_feat=self.env_feat)
+        return r
+
+    def reset(self):
+        self.side.reset(); return self._result()
+
+    def step(self, ids, actions):
+        self.side.step(ids.numpy(), actions.numpy()); return self._result()
+
+    def entity_act(self, ids, packed, eps=None):
+        from multi_agent_rl_wrsn_amd import VecWRSN
+        return VecWRSN.entity_act(self, ids, packed, eps)
+
+
+def _parent_step_batch(self):
+    """BatchedEntityIPPO.step_batch as it stood before the fused option, statement for statement (the timers left out)."""
+    from multi_agent_rl_wrsn_amd import EntityTransitionBuffers
+    torch, env = self.torch, self.env
+    r = self._req
+    ids = r["agent_id"].clone()
+    act3 = torch.zeros((env.num_env, 3), dtype=torch.float32, device=env.device)
+    logp = torch.zeros((env.num_env,), dtype=torch.float32, device=env.device)
+    for a in range(self.num_agent):
+        rows = torch.nonzero(ids == a).flatten()
+        if rows.numel() == 0:
+            continue
+        x = EntityTransitionBuffers.pack(r["nodes"].index_select(0, rows), r["chargers"].index_select(0, rows), r["env_feat"].index_select(0, rows))
+        act, lp = self.get_action(a, x)
+        act3.index_copy_(0, rows, act.float()); logp.index_copy_(0, rows, lp.float())
+    self.buffers.record(ids, act3, logp)
+    r = env.step(ids, act3.double())
+    self.buffers.collect()
+    self.last_ids, self.last_action3 = ids, act3
+    self._req = r
+    return r
+
+
+def _emu_rollout(fused, parent=False, launches=6):
+    import torch
+    from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, BatchedEntityIPPO, synth_scenario
+    torch.set_num_threads(2)
+    side = EmuSide([synth_scenario(300 + e, 70, 60) for e in range(3)], DEFAULT_MC_SPEC, 2, map_size=12, render=False, entities=True, auto_reset=True)
+    env = EmuVec(side)
+    torch.manual_seed(11)
+    algo = BatchedEntityIPPO(dict(batch_size=8, minibatch_size=4, n_updates_per_iteration=1), env, device="cpu", **({"fused_policy": True} if fused else {}))
+    algo.buffers.clear(); algo._req = env.reset()
+    torch.manual_seed(12)
+    acts = []
+    for _ in range(launches):
+        _parent_step_batch(algo) if parent else algo.step_batch()
+        acts.append(algo.last_action3.clone())
+    out = {k: getattr(algo.buffers, k).clone() for k in ("state", "action", "next_state", "reward", "logp", "now", "count", "pend_action", "pend_logp")}
+    out["acts"] = torch.stack(acts)
+    return algo, env, side, out
+
+
+def test_emulated_unfused_roll_out_is_untouched():
+    """fused_policy=False (the default) stores, over a seeded roll-out on the emulator, bit for bit what the step_batch of before the
+    option stores."""
+    import torch
+    _, _, s1, a = _emu_rollout(False)
+    _, _, s2, b = _emu_rollout(False, parent=True)
+    assert int(a["count"].sum()) > 0
+    for k in a:
+        assert torch.equal(a[k], b[k]), k
+    s1.close(); s2.close()
+
+
+def test_emulated_fused_roll_out_stores_what_evaluate_recomputes():
+    """fused_policy=True through the same adapter: the stored log-probabilities are the ones evaluate recomputes (|log-ratio| <= 1e-4,
+    the CPU bound of tests/test_entity_policy.py), and the packed actors are dropped by update."""
+    import torch
+    algo, env, side, out = _emu_rollout(True, launches=8)
+    assert algo._packed is not None and int(out["count"].sum()) > 0
+    for a in range(2):
+        n = min(int(out["count"][a]), algo.buffers.capacity)
+        if n == 0:
+            continue
+        with torch.no_grad():
+            new, _ = algo.evaluate(a, algo.buffers.state[a, :n], algo.buffers.action[a, :n])
+        d = float((new - algo.buffers.logp[a, :n]).abs().max())
+        print("charger %d: %d transitions, max |evaluate - stored logp| %.3g" % (a, n, d))
+        assert d <= 1e-4, (a, d)
+    from test_entity_policy import _batch
+    algo.update(0, _batch(21, 8), shuffle=np.random.RandomState(3).shuffle)
+    assert algo._packed is None
+    side.close()
