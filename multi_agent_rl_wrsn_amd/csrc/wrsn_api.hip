@@ -857,12 +857,14 @@ static int tr_buffers(const wrsn_transition_buffers* b, WrsnTrBuffers* t) {
     return 0;
 }
 
+static int obs_elem_bytes(const wrsn_t* h) { return h->obs_fmt == WRSN_OBS_BF16 ? 2 : 4; }   // of the rows the image copy kernels move
+
 int wrsn_rollout_record(wrsn_t* h, const wrsn_transition_buffers* buf, const int32_t* agent_id, const float* action, const float* logp,
                         const float* obs) {
     if (!h || !agent_id || !action || !logp || !obs) return fail(WRSN_ERR_ARG, "null argument");
     WrsnTrBuffers t; int rc = tr_buffers(buf, &t); if (rc) return rc;
     WRSN_ON_DEVICE(h);
-    hipLaunchKernelGGL(wrsn_tr_record_kernel, dim3(h->dev.B), dim3(256), 0, h->stream, h->dev.B, h->dev.M, h->dev.G, t, agent_id, action, logp, obs, h->obs_fmt == WRSN_OBS_BF16 ? 2 : 4);
+    hipLaunchKernelGGL(wrsn_tr_record_kernel, dim3(h->dev.B), dim3(256), 0, h->stream, h->dev.B, h->dev.M, h->dev.G, t, agent_id, action, logp, obs, obs_elem_bytes(h));
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }
@@ -873,7 +875,7 @@ int wrsn_rollout_collect(wrsn_t* h, const wrsn_transition_buffers* buf, const wr
     WrsnTrBuffers t; int rc = tr_buffers(buf, &t); if (rc) return rc;
     WRSN_ON_DEVICE(h);
     hipLaunchKernelGGL(wrsn_tr_collect_kernel, dim3(h->dev.B), dim3(256), 16, h->stream, h->dev.B, h->dev.M, h->dev.G, t, out->agent_id,
-                       out->reward, out->now, h->dev.row_state, out->obs, h->obs_fmt == WRSN_OBS_BF16 ? 2 : 4);
+                       out->reward, out->now, h->dev.row_state, out->obs, obs_elem_bytes(h));
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }
@@ -912,17 +914,25 @@ int wrsn_entities(wrsn_t* h, const int32_t* agent_id, const wrsn_entity_out* ent
     return WRSN_OK;
 }
 
+// The entity buffers a call reads: those of `ent`, checked, or with ent == NULL the registered ones.
+static int entity_in(const wrsn_t* h, const wrsn_entity_out* ent, WrsnEntityOut* e) {
+    if (ent) return entity_out(ent, e);
+    if (!h->ent.node) return fail(WRSN_ERR_ARG, "no entity buffers: pass wrsn_entity_out or register them with wrsn_set_entity_out");
+    *e = h->ent;
+    return 0;
+}
+
 // Entity transition rows: the buffers of `ent` (NULL: the registered ones) and the three row pointers of the transition buffers, all
 // checked before anything is enqueued or changed.
 static int tr_entity_args(wrsn_t* h, const wrsn_transition_buffers* buf, const wrsn_entity_out* ent, WrsnTrBuffers* t, WrsnEntityOut* e) {
-    if (ent) { const int rc = entity_out(ent, e); if (rc) return rc; }
-    else if (h->ent.node) *e = h->ent;
-    else return fail(WRSN_ERR_ARG, "no entity buffers: pass wrsn_entity_out or register them with wrsn_set_entity_out");
-    const int rc = tr_buffers(buf, t); if (rc) return rc;
+    int rc = entity_in(h, ent, e); if (rc) return rc;
+    rc = tr_buffers(buf, t); if (rc) return rc;
     if (((uintptr_t)t->pend_state | (uintptr_t)t->state | (uintptr_t)t->next_state) % 16)
         return fail(WRSN_ERR_ARG, "wrsn_transition_buffers: pend_state, state and next_state of entity rows must be 16-byte aligned");
     return 0;
 }
+
+static dim3 entity_row_grid(int B) { return dim3((B + WRSN_ENT_ROWS - 1) / WRSN_ENT_ROWS); }   // of blocks of 64 * WRSN_ENT_ROWS: a wave per row
 
 int wrsn_rollout_record_entities(wrsn_t* h, const wrsn_transition_buffers* buf, const int32_t* agent_id, const float* action, const float* logp,
                                  const wrsn_entity_out* ent) {
@@ -931,7 +941,7 @@ int wrsn_rollout_record_entities(wrsn_t* h, const wrsn_transition_buffers* buf, 
     const int rc = tr_entity_args(h, buf, ent, &t, &e); if (rc) return rc;
     WRSN_ON_DEVICE(h);
     const int B = h->dev.B;
-    hipLaunchKernelGGL(wrsn_tr_record_entities_kernel, dim3((B + WRSN_ENT_ROWS - 1) / WRSN_ENT_ROWS), dim3(64 * WRSN_ENT_ROWS), 0, h->stream, B, h->dev.M,
+    hipLaunchKernelGGL(wrsn_tr_record_entities_kernel, entity_row_grid(B), dim3(64 * WRSN_ENT_ROWS), 0, h->stream, B, h->dev.M,
                        h->dev.N, t, agent_id, action, logp, e);
     HIPCHK(hipGetLastError());
     return WRSN_OK;
@@ -944,7 +954,7 @@ int wrsn_rollout_collect_entities(wrsn_t* h, const wrsn_transition_buffers* buf,
     const int rc = tr_entity_args(h, buf, ent, &t, &e); if (rc) return rc;
     WRSN_ON_DEVICE(h);
     const int B = h->dev.B;
-    hipLaunchKernelGGL(wrsn_tr_collect_entities_kernel, dim3((B + WRSN_ENT_ROWS - 1) / WRSN_ENT_ROWS), dim3(64 * WRSN_ENT_ROWS), 0, h->stream, B, h->dev.M,
+    hipLaunchKernelGGL(wrsn_tr_collect_entities_kernel, entity_row_grid(B), dim3(64 * WRSN_ENT_ROWS), 0, h->stream, B, h->dev.M,
                        h->dev.N, t, out->agent_id, out->reward, out->now, h->dev.row_state, e, (int)(consume != 0));
     HIPCHK(hipGetLastError());
     return WRSN_OK;
@@ -957,9 +967,7 @@ int wrsn_entity_act(wrsn_t* h, const float* actors, const int32_t* agent_id, con
     if (!h || !actors || !agent_id || !out || !out->action || !out->logp)
         return fail(WRSN_ERR_ARG, "wrsn_entity_act needs actors, agent_id, out->action and out->logp");
     WrsnEntityOut e{};
-    if (ent) { const int rc = entity_out(ent, &e); if (rc) return rc; }
-    else if (h->ent.node) e = h->ent;
-    else return fail(WRSN_ERR_ARG, "no entity buffers: pass wrsn_entity_out or register them with wrsn_set_entity_out");
+    { const int rc = entity_in(h, ent, &e); if (rc) return rc; }
     if ((uintptr_t)actors % 16) return fail(WRSN_ERR_ARG, "wrsn_entity_act: actors must be 16-byte aligned");
     WRSN_ON_DEVICE(h);
     const int B = h->dev.B, M = h->dev.M;

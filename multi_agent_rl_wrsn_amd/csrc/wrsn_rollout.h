@@ -297,23 +297,27 @@ __global__ void __launch_bounds__(64 * WRSN_ENT_ROWS) wrsn_tr_collect_entities_k
 // Registers: the pools are folded tile by tile, so a lane carries two sums and two maxima, not 64 values: 91 VGPRs + 32 AGPRs, no scratch,
 // four waves per SIMD (profiles/entity_act_kernel_resource_usage.csv).
 #define WRSN_ENTPOL_FEAT 200
-#define WRSN_EP_NODE1 0
-#define WRSN_EP_NODE1_B 512
-#define WRSN_EP_NODE2 576
-#define WRSN_EP_NODE2_B 4672
-#define WRSN_EP_MC1 4736
-#define WRSN_EP_MC1_B 5120
-#define WRSN_EP_MC2 5152
-#define WRSN_EP_MC2_B 6176
-#define WRSN_EP_HEAD1 6208
-#define WRSN_EP_HEAD1_B 31808
-#define WRSN_EP_HEAD2 31936
-#define WRSN_EP_HEAD2_B 48320
-#define WRSN_EP_MEAN 48448
-#define WRSN_EP_MEAN_B 48832
-#define WRSN_EP_LSTD 48835
-#define WRSN_EP_LSTD_B 49219
-#define WRSN_EP_FLOATS 49224                                  // 49 222 rounded up to a multiple of 4
+// The packed block (include/wrsn_hip.h): per layer the weights [in][out], then the bias [out], layer after layer
+#define WRSN_EP_NODE1 0                                                            // node1    8 ->  64
+#define WRSN_EP_NODE1_B (WRSN_EP_NODE1 + WRSN_ENT_NODE_F * 64)
+#define WRSN_EP_NODE2 (WRSN_EP_NODE1_B + 64)                                       // node2   64 ->  64
+#define WRSN_EP_NODE2_B (WRSN_EP_NODE2 + 64 * 64)
+#define WRSN_EP_MC1 (WRSN_EP_NODE2_B + 64)                                         // mc1     12 ->  32
+#define WRSN_EP_MC1_B (WRSN_EP_MC1 + WRSN_ENT_MC_F * 32)
+#define WRSN_EP_MC2 (WRSN_EP_MC1_B + 32)                                           // mc2     32 ->  32
+#define WRSN_EP_MC2_B (WRSN_EP_MC2 + 32 * 32)
+#define WRSN_EP_HEAD1 (WRSN_EP_MC2_B + 32)                                         // head1  200 -> 128
+#define WRSN_EP_HEAD1_B (WRSN_EP_HEAD1 + WRSN_ENTPOL_FEAT * 128)
+#define WRSN_EP_HEAD2 (WRSN_EP_HEAD1_B + 128)                                      // head2  128 -> 128
+#define WRSN_EP_HEAD2_B (WRSN_EP_HEAD2 + 128 * 128)
+#define WRSN_EP_MEAN (WRSN_EP_HEAD2_B + 128)                                       // mean   128 ->   3
+#define WRSN_EP_MEAN_B (WRSN_EP_MEAN + 128 * 3)
+#define WRSN_EP_LSTD (WRSN_EP_MEAN_B + 3)                                          // log_std 128 -> 3
+#define WRSN_EP_LSTD_B (WRSN_EP_LSTD + 128 * 3)
+#define WRSN_EP_FLOATS ((WRSN_EP_LSTD_B + 3 + 3) / 4 * 4)                          // rounded up to a multiple of 4
+static_assert(WRSN_ENTPOL_FEAT == 64 + 64 + 32 + 32 + WRSN_ENT_ENV_F, "head1 reads both node pools, both charger pools and the env row");
+static_assert(WRSN_EP_HEAD1 == 6208 && WRSN_EP_MEAN == 48448 && WRSN_EP_FLOATS == 49224, "the layout documented in include/wrsn_hip.h");
+static_assert(WRSN_EP_MC1 % 4 == 0, "the trunk stages the first WRSN_EP_MC1 floats in LDS by 16-byte loads");
 // LDS of the trunk block, in floats: node1 / node2 with their biases (the first WRSN_EP_MC1 floats of the block), the pools of the four
 // waves, their live-node counts, the two charger layers
 #define WRSN_EP_T_SUM WRSN_EP_MC1

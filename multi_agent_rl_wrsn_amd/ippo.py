@@ -129,31 +129,26 @@ def build_networks(map_size=100):
 # ------------------------------------------------------------------------------------------------------------------
 # device-side transition buffers
 # ------------------------------------------------------------------------------------------------------------------
-class TransitionBuffers:
-    """Per-charger transition lists of a batched roll-out, filled by the HIP kernels of csrc/wrsn_rollout.h.
+class _TransitionBuffers:
+    """What the two kinds of transition buffers share: the twelve tensors of `wrsn_transition_buffers`, the ctypes struct over them and
+    the calls that do not depend on what a stored state row is.  A subclass states the shape and dtype of a state row and which
+    `_lib.RawHandle` calls `record` and `collect` go to."""
 
-    env          : VecWRSN (rendering on); `pend_state`, `state` and `next_state` take the dtype of its `state` (float32 or bfloat16:
-                   the copy kernels move rows in the environment's observation format)
-    capacity     : transitions kept per charger (further ones are counted in `count` and dropped)
-    action_elems : size of the policy's raw output per decision: 3, or map_size**2 for density-map policies"""
-
-    def __init__(self, env, capacity, action_elems):
+    def __init__(self, env, capacity, action_elems, row_shape, row_dtype):
         torch = env.torch
-        if env.state is None:
-            raise ValueError("TransitionBuffers needs a rendering VecWRSN (render=True)")
         self.env = env
-        B, M, G, C, A = env.num_env, env.num_agent, env.map_size, int(capacity), int(action_elems)
+        B, M, C, A = env.num_env, env.num_agent, int(capacity), int(action_elems)
         self.capacity, self.action_elems = C, A
         dev = env.device
         f32 = dict(dtype=torch.float32, device=dev)
-        obs = dict(dtype=env.state.dtype, device=dev)
-        self.pend_state = torch.zeros((B, M, 4, G, G), **obs)
+        row = dict(dtype=row_dtype, device=dev)
+        self.pend_state = torch.zeros((B, M) + row_shape, **row)
         self.pend_action = torch.zeros((B, M, A), **f32)
         self.pend_logp = torch.zeros((B, M), **f32)
         self.pend_valid = torch.zeros((B, M), dtype=torch.uint8, device=dev)
-        self.state = torch.zeros((M, C, 4, G, G), **obs)
+        self.state = torch.zeros((M, C) + row_shape, **row)
         self.action = torch.zeros((M, C, A), **f32)
-        self.next_state = torch.zeros((M, C, 4, G, G), **obs)
+        self.next_state = torch.zeros((M, C) + row_shape, **row)
         self.reward = torch.zeros((M, C), **f32)
         self.logp = torch.zeros((M, C), **f32)
         self.now = torch.zeros((M, C), dtype=torch.float64, device=dev)
@@ -168,22 +163,20 @@ class TransitionBuffers:
         if not keep_pending:
             self.pend_valid.zero_()
 
-    def record(self, agent_ids, actions, logp, states=None):
-        """The chargers `agent_ids` [B] (< 0: none) are about to receive `actions` [B, action_elems] (IPPO.py:141-142)."""
+    def _record(self, call, agent_ids, actions, logp, *rows):
+        """`call(self._c, agent_ids, actions, logp, *rows)` on the addresses of the arguments in the types the kernels read."""
         env, t = self.env, self.env.torch
         env._bind_stream()
         a = agent_ids.to(device=env.device, dtype=t.int32).contiguous()
         x = actions.to(device=env.device, dtype=t.float32).reshape(env.num_env, self.action_elems).contiguous()
         lp = logp.to(device=env.device, dtype=t.float32).reshape(env.num_env).contiguous()
-        st = (env.state if states is None else states.to(device=env.device, dtype=env.state.dtype)).contiguous()
-        self._keep = (a, x, lp, st)                           # alive until the kernel has run
-        env._h.rollout_record(self._c, a.data_ptr(), x.data_ptr(), lp.data_ptr(), st.data_ptr())
+        self._keep = (a, x, lp) + rows                        # alive until the kernel has run
+        call(self._c, *[v.data_ptr() for v in self._keep])
 
-    def collect(self):
-        """Append the transitions the request just returned by `env.step` completes (IPPO.py:144-155)."""
+    def _collect(self, call, *args):
         env = self.env
         env._bind_stream()
-        env._h.rollout_collect(self._c, **env._out_ptrs())
+        call(self._c, *args, **env._out_ptrs())
 
     def counts(self):
         """Transitions appended per charger so far (host list; synchronises)."""
@@ -191,6 +184,30 @@ class TransitionBuffers:
 
     def stored(self):
         return [min(c, self.capacity) for c in self.counts()]
+
+
+class TransitionBuffers(_TransitionBuffers):
+    """Per-charger transition lists of a batched roll-out, filled by the HIP kernels of csrc/wrsn_rollout.h.
+
+    env          : VecWRSN (rendering on); `pend_state`, `state` and `next_state` take the dtype of its `state` (float32 or bfloat16:
+                   the copy kernels move rows in the environment's observation format)
+    capacity     : transitions kept per charger (further ones are counted in `count` and dropped)
+    action_elems : size of the policy's raw output per decision: 3, or map_size**2 for density-map policies"""
+
+    def __init__(self, env, capacity, action_elems):
+        if env.state is None:
+            raise ValueError("TransitionBuffers needs a rendering VecWRSN (render=True)")
+        super().__init__(env, capacity, action_elems, (4, env.map_size, env.map_size), env.state.dtype)
+
+    def record(self, agent_ids, actions, logp, states=None):
+        """The chargers `agent_ids` [B] (< 0: none) are about to receive `actions` [B, action_elems] (IPPO.py:141-142)."""
+        env = self.env
+        st = (env.state if states is None else states.to(device=env.device, dtype=env.state.dtype)).contiguous()
+        self._record(env._h.rollout_record, agent_ids, actions, logp, st)
+
+    def collect(self):
+        """Append the transitions the request just returned by `env.step` completes (IPPO.py:144-155)."""
+        self._collect(self.env._h.rollout_collect)
 
 
 def select_batch(rewards, batch_size, rng=np.random):
@@ -280,6 +297,20 @@ class PPOLearner:
             b <<= 1
         return min(b, self.infer_chunk)
 
+    _pad_on_cpu = False                                        # short chunks are padded to their bucket on the device only
+
+    def _actor_chunks(self, agent_id, states):
+        """The actor over `states` in the batch composition of the roll-out: chunks of `infer_chunk` rows, a short chunk filled up to its
+        bucket by repeating its own rows, whose outputs are dropped.  Yields (mean, log_std) in float32 per chunk."""
+        torch = self.torch
+        for s in states.split(self.infer_chunk):
+            r = s.shape[0]
+            nb = self._bucket(r) if self._pad_on_cpu or self.device.type == "cuda" else r
+            if r < nb:
+                s = s.index_select(0, torch.arange(nb, device=s.device) % r)
+            mean, log_std = self._forward(self.actors[agent_id], s, inference=True)
+            yield mean[:r].float(), log_std[:r].float()
+
     def get_action(self, agent_id, states):
         """IPPO.py:95-105 for a batch: states [n,4,G,G] -> (action maps [n,G,G], summed log-prob [n]).
 
@@ -289,13 +320,7 @@ class PPOLearner:
         torch = self.torch
         outs, lps = [], []
         with torch.no_grad():
-            for s in states.split(self.infer_chunk):
-                r = s.shape[0]
-                nb = self._bucket(r) if self.device.type == "cuda" else r
-                if r < nb:                                    # a short chunk is filled up by repeating its own rows, whose outputs are dropped
-                    s = s.index_select(0, torch.arange(nb, device=s.device) % r)
-                mean, log_std = self._forward(self.actors[agent_id], s, inference=True)
-                mean, log_std = mean[:r].float(), log_std[:r].float()
+            for mean, log_std in self._actor_chunks(agent_id, states):
                 dist = torch.distributions.Normal(mean, log_std.exp())
                 act = dist.sample()
                 outs.append(act); lps.append(dist.log_prob(act).sum(self._logp_dims))
@@ -310,14 +335,8 @@ class PPOLearner:
         torch = self.torch
         lps = []
         with torch.no_grad():
-            for s, a in zip(states.split(self.infer_chunk), actions.split(self.infer_chunk)):
-                r = s.shape[0]
-                nb = self._bucket(r) if self.device.type == "cuda" else r
-                if r < nb:
-                    s = s.index_select(0, torch.arange(nb, device=s.device) % r)
-                mean, log_std = self._forward(self.actors[agent_id], s, inference=True)
-                dist = torch.distributions.Normal(mean[:r].float(), log_std[:r].float().exp())
-                lps.append(dist.log_prob(a.float()).sum(self._logp_dims))
+            for (mean, log_std), a in zip(self._actor_chunks(agent_id, states), actions.split(self.infer_chunk)):
+                lps.append(torch.distributions.Normal(mean, log_std.exp()).log_prob(a.float()).sum(self._logp_dims))
         return torch.cat(lps)
 
     def _forward(self, net, x, inference=False):
@@ -470,19 +489,17 @@ class PPOLearner:
         return stats
 
 
-class BatchedIPPO(PPOLearner):
-    """`IPPO(args, env, device, model_path=None)` of the reference (IPPO.py:17-69) over a `VecWRSN` with density-map actions
-    (`density_map=True` environments of runner/IPPO.py:19-21): the actor's G x G output is the action and is turned into the
-    3-vector on the device (`VecWRSN.density_to_action`)."""
+class RolloutDriver:
+    """The batched roll-out and the training loop on top of a learner (`PPOLearner` or a subclass, which follows this class in the bases of a
+    trainer): timers, `step_batch`, `roll_out`, `train`.  A trainer says how its policy chooses (`_choose`), what it hands to `env.step` if
+    that is not what it stores (`_action3`), whether a launch checks the status rows (`_check_status`) and the shape `evaluate` takes
+    the stored actions in (`_stored_actions`)."""
 
-    def __init__(self, args, env, device=None, model_path=None, capacity=None, infer_chunk=1024, process_group=None, log=None, inference_dtype=None,
-                 min_bucket=16):
-        super().__init__(args, env.num_agent, env.map_size, device if device is not None else env.device, model_path, infer_chunk, process_group,
-                         inference_dtype, min_bucket)
-        self.env = env
-        self.buffers = TransitionBuffers(env, capacity or 2 * self.batch_size, env.map_size * env.map_size)
+    _check_status = False                                      # raise when a row comes back from the step with status < 0
+
+    def _attach(self, env, buffers, log):
+        self.env, self.buffers, self.log = env, buffers, log
         self.timers = {"env_s": 0.0, "policy_s": 0.0, "glue_s": 0.0, "train_s": 0.0, "launches": 0, "requests": 0}
-        self.log = log
         self._req = None
 
     # -- roll-out ----------------------------------------------------------------------------------------------------
@@ -490,27 +507,50 @@ class BatchedIPPO(PPOLearner):
         self.torch.cuda.synchronize(self.device) if self.device.type == "cuda" else None
         return time.perf_counter()
 
-    def step_batch(self):
-        """One launch of the batched roll-out: act for every environment that carries a request, step, collect."""
+    def _choose_per_charger(self, ids, width, gather):
+        """One `get_action` per charger over the rows that ask for it, `gather(rows)` being its input for those rows: (actions
+        [B, width], log-probabilities [B]), zeros where nobody asks."""
         torch, env = self.torch, self.env
-        r = self._req
-        ids = r["agent_id"]
-        G = env.map_size
-        t0 = self._sync_time()
-        maps = torch.zeros((env.num_env, G * G), dtype=torch.float32, device=env.device)
+        out = torch.zeros((env.num_env, width), dtype=torch.float32, device=env.device)
         logp = torch.zeros((env.num_env,), dtype=torch.float32, device=env.device)
         for a in range(self.num_agent):
             rows = torch.nonzero(ids == a).flatten()
             if rows.numel() == 0:
                 continue
-            act, lp = self.get_action(a, r["state"].index_select(0, rows))
-            maps.index_copy_(0, rows, act.reshape(rows.numel(), G * G).float()); logp.index_copy_(0, rows, lp.float())
+            act, lp = self.get_action(a, gather(rows))
+            out.index_copy_(0, rows, act.reshape(rows.numel(), width).float()); logp.index_copy_(0, rows, lp.float())
+        return out, logp
+
+    def _choose(self, r, ids):
+        """(what the buffers store [B, action_elems], log-probabilities [B], the float64 [B, 3] `env.step` takes or None: `_action3`
+        widened) for the request `r`, whose charger ids are `ids`."""
+        raise NotImplementedError
+
+    def _action3(self, ids, stored):
+        """The 3-vector of a launch, from what the policy chose and the buffers store."""
+        return stored
+
+    def _stored_actions(self, actions):
+        """Stored action rows [n, action_elems] in the shape `evaluate` takes."""
+        return actions
+
+    def step_batch(self):
+        """One launch of the batched roll-out: act for every environment that carries a request, step, collect."""
+        torch, env = self.torch, self.env
+        r = self._req
+        ids = r["agent_id"].clone()                           # the request's ids, detached from the tensor the step writes
+        t0 = self._sync_time()
+        stored, logp, handed = self._choose(r, ids)
         t1 = self._sync_time()
-        self.buffers.record(ids, maps, logp)
-        act3 = env.density_to_action(ids, maps.view(env.num_env, G, G).double())
+        self.buffers.record(ids, stored, logp)
+        act3 = self._action3(ids, stored)
         t2 = self._sync_time()
-        r = env.step(ids.clone(), act3)
+        r = env.step(ids, act3.double() if handed is None else handed)
         t3 = self._sync_time()
+        if self._check_status:
+            bad = torch.nonzero(r["status"] < 0).flatten()
+            if bad.numel():
+                raise RuntimeError("environment rows %s report status %s" % (bad.tolist(), r["status"][bad].tolist()))
         self.buffers.collect()
         t4 = self._sync_time()
         tm = self.timers
@@ -519,10 +559,6 @@ class BatchedIPPO(PPOLearner):
         self.last_ids, self.last_action3 = ids, act3          # what this launch handed to the environments (tests / logging)
         self._req = r
         return r
-
-    def _stored_actions(self, actions):
-        """Stored action rows [n, action_elems] in the shape `evaluate` takes."""
-        return actions.view(-1, self.env.map_size, self.env.map_size)
 
     def roll_out(self, max_launches=100000, fresh_episodes=False):
         """IPPO.py:119-210 over the batch: launches until every charger has `batch_size` transitions, then the reference's
@@ -594,6 +630,29 @@ class BatchedIPPO(PPOLearner):
         return rows
 
 
+class BatchedIPPO(RolloutDriver, PPOLearner):
+    """`IPPO(args, env, device, model_path=None)` of the reference (IPPO.py:17-69) over a `VecWRSN` with density-map actions
+    (`density_map=True` environments of runner/IPPO.py:19-21): the actor's G x G output is the action and is turned into the
+    3-vector on the device (`VecWRSN.density_to_action`)."""
+
+    def __init__(self, args, env, device=None, model_path=None, capacity=None, infer_chunk=1024, process_group=None, log=None, inference_dtype=None,
+                 min_bucket=16):
+        super().__init__(args, env.num_agent, env.map_size, device if device is not None else env.device, model_path, infer_chunk, process_group,
+                         inference_dtype, min_bucket)
+        self._attach(env, TransitionBuffers(env, capacity or 2 * self.batch_size, env.map_size * env.map_size), log)
+
+    def _choose(self, r, ids):
+        G = self.env.map_size
+        return self._choose_per_charger(ids, G * G, lambda rows: r["state"].index_select(0, rows)) + (None,)
+
+    def _action3(self, ids, maps):                            # float64: `step_batch` hands it to `env.step` as it is
+        G = self.env.map_size
+        return self.env.density_to_action(ids, maps.view(self.env.num_env, G, G).double())
+
+    def _stored_actions(self, actions):
+        return actions.view(-1, self.env.map_size, self.env.map_size)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # training from the entity observation: packed rows, a permutation-invariant actor / critic, the trainer on top
 # ------------------------------------------------------------------------------------------------------------------
@@ -602,7 +661,7 @@ def entity_row_elems(n_node, num_agent):
     return _lib.ENT_NODE_F * int(n_node) + _lib.ENT_MC_F * int(num_agent) + _lib.ENT_ENV_F
 
 
-class EntityTransitionBuffers:
+class EntityTransitionBuffers(_TransitionBuffers):
     """`TransitionBuffers` for the entity observation (`wrsn_rollout_record_entities` / `wrsn_rollout_collect_entities`): a stored
     state is one packed float32 row of R = 8 N + 12 M + 8 elements, `pend_state` [B, M, R], `state` / `next_state` [M, capacity, R].
 
@@ -611,30 +670,10 @@ class EntityTransitionBuffers:
     action_elems : size of the policy's raw output per decision (3: the action vector itself)"""
 
     def __init__(self, env, capacity, action_elems=3):
-        torch = env.torch
         if not getattr(env, "entities", False):
             raise ValueError("EntityTransitionBuffers needs a VecWRSN with the entity observation (entities=True)")
-        self.env = env
-        B, M, C, A = env.num_env, env.num_agent, int(capacity), int(action_elems)
-        R = entity_row_elems(env.n_node, M)
-        self.capacity, self.action_elems, self.row_elems = C, A, R
-        dev = env.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.pend_state = torch.zeros((B, M, R), **f32)
-        self.pend_action = torch.zeros((B, M, A), **f32)
-        self.pend_logp = torch.zeros((B, M), **f32)
-        self.pend_valid = torch.zeros((B, M), dtype=torch.uint8, device=dev)
-        self.state = torch.zeros((M, C, R), **f32)
-        self.action = torch.zeros((M, C, A), **f32)
-        self.next_state = torch.zeros((M, C, R), **f32)
-        self.reward = torch.zeros((M, C), **f32)
-        self.logp = torch.zeros((M, C), **f32)
-        self.now = torch.zeros((M, C), dtype=torch.float64, device=dev)
-        self.env_index = torch.zeros((M, C), dtype=torch.int32, device=dev)
-        self.count = torch.zeros((M,), dtype=torch.int32, device=dev)
-        self._c = _lib.WrsnTransitionBuffers(C, A, *[t.data_ptr() for t in (
-            self.pend_state, self.pend_action, self.pend_logp, self.pend_valid, self.state, self.action, self.next_state,
-            self.reward, self.logp, self.now, self.env_index, self.count)])
+        self.row_elems = entity_row_elems(env.n_node, env.num_agent)
+        super().__init__(env, capacity, action_elems, (self.row_elems,), env.torch.float32)
 
     @staticmethod
     def split(rows, num_agent):
@@ -653,35 +692,15 @@ class EntityTransitionBuffers:
         torch = _torch()
         return torch.cat([nodes.flatten(1), chargers.flatten(1), env_feat.flatten(1)], 1)
 
-    def clear(self, keep_pending=False):
-        self.count.zero_()
-        if not keep_pending:
-            self.pend_valid.zero_()
-
     def record(self, agent_ids, actions, logp):
         """The chargers `agent_ids` [B] (< 0: none) are about to receive `actions` [B, action_elems], chosen on the entity rows the
         environment holds now (IPPO.py:141-142)."""
-        env, t = self.env, self.env.torch
-        env._bind_stream()
-        a = agent_ids.to(device=env.device, dtype=t.int32).contiguous()
-        x = actions.to(device=env.device, dtype=t.float32).reshape(env.num_env, self.action_elems).contiguous()
-        lp = logp.to(device=env.device, dtype=t.float32).reshape(env.num_env).contiguous()
-        self._keep = (a, x, lp)                               # alive until the kernel has run
-        env._h.rollout_record_entities(self._c, a.data_ptr(), x.data_ptr(), lp.data_ptr())
+        self._record(self.env._h.rollout_record_entities, agent_ids, actions, logp)
 
     def collect(self, consume=True):
         """Append the transitions the request just returned by `env.step` completes (IPPO.py:144-155).  consume=False leaves the
         requests to the `TransitionBuffers.collect` of the same launch that follows."""
-        env = self.env
-        env._bind_stream()
-        env._h.rollout_collect_entities(self._c, None, consume, **env._out_ptrs())
-
-    def counts(self):
-        """Transitions appended per charger so far (host list; synchronises)."""
-        return [int(v) for v in self.count.cpu()]
-
-    def stored(self):
-        return [min(c, self.capacity) for c in self.counts()]
+        self._collect(self.env._h.rollout_collect_entities, None, consume)
 
 
 def build_entity_networks(n_agent_rows):
@@ -776,7 +795,8 @@ class EntityPPOLearner(PPOLearner):
     Unlike the image learner's, the log-probabilities `get_action` stores are the ones `evaluate` recomputes at unchanged weights
     (float32 rounding apart): the first minibatch of an update has ratio 1."""
 
-    _logp_dims = (1,)                                          # the action is a 3-vector
+    _logp_dims = (1,)                                          # the action is a 3-vector: `get_action` gives (action [n, 3], log-prob [n])
+    _pad_on_cpu = True                                         # a small set of GEMM shapes everywhere; the padding cannot change a row's output
 
     def __init__(self, args, num_agent, device, model_path=None, infer_chunk=1024, process_group=None, min_bucket=16):
         super().__init__(args, num_agent, 0, device, model_path, infer_chunk, process_group, None, min_bucket)
@@ -794,25 +814,8 @@ class EntityPPOLearner(PPOLearner):
         now.  Nothing here keeps it: whoever does must rebuild it after every `update` and every checkpoint load."""
         return self.torch.stack([pack_entity_actor(a) for a in self.actors]).contiguous()
 
-    def get_action(self, agent_id, states):
-        """Packed rows [n, R] -> (action [n, 3], log-prob [n]).  Chunks of `infer_chunk` rows, a short chunk padded to its bucket by
-        repeating its own rows (a small set of GEMM shapes; the padding cannot change a row's output)."""
-        torch = self.torch
-        outs, lps = [], []
-        with torch.no_grad():
-            for s in states.split(self.infer_chunk):
-                r = s.shape[0]
-                nb = self._bucket(r)
-                if r < nb:
-                    s = s.index_select(0, torch.arange(nb, device=s.device) % r)
-                mean, log_std = self._forward(self.actors[agent_id], s, inference=True)
-                dist = torch.distributions.Normal(mean[:r], log_std[:r].exp())
-                act = dist.sample()
-                outs.append(act); lps.append(dist.log_prob(act).sum(self._logp_dims))
-        return torch.cat(outs), torch.cat(lps)
 
-
-class BatchedEntityIPPO(EntityPPOLearner):
+class BatchedEntityIPPO(RolloutDriver, EntityPPOLearner):
     """The roll-out of `BatchedIPPO` on entity rows: `VecWRSN(entities=True)` (no image needed: `render=False`), the set policy's
     3-vector is the action `env.step` takes, and the transitions live in `EntityTransitionBuffers`.
 
@@ -820,91 +823,33 @@ class BatchedEntityIPPO(EntityPPOLearner):
                    environment holds, with the actors packed at the start of the roll-out (`packed_actors`) and standard-normal draws
                    of `torch.randn`; no row gathering and no per-charger forward pass.  False (the default): `get_action` per charger."""
 
+    _check_status = True
+
     def __init__(self, args, env, device=None, model_path=None, capacity=None, infer_chunk=1024, process_group=None, log=None, min_bucket=16,
                  fused_policy=False):
         if not getattr(env, "entities", False):
             raise ValueError("BatchedEntityIPPO needs a VecWRSN with the entity observation (entities=True)")
         super().__init__(args, env.num_agent, device if device is not None else env.device, model_path, infer_chunk, process_group, min_bucket)
-        self.env = env
-        self.buffers = EntityTransitionBuffers(env, capacity or 2 * self.batch_size, 3)
-        self.timers = {"env_s": 0.0, "policy_s": 0.0, "glue_s": 0.0, "train_s": 0.0, "launches": 0, "requests": 0}
-        self.log = log
-        self._req = None
+        self._attach(env, EntityTransitionBuffers(env, capacity or 2 * self.batch_size, 3), log)
         self.fused_policy = bool(fused_policy)
         self._packed = None                                   # packed_actors() of the weights as they are now, or None: rebuilt before use
-
-    _sync_time = BatchedIPPO._sync_time
-    train = BatchedIPPO.train
 
     def roll_out(self, max_launches=100000, fresh_episodes=False):
         if self.fused_policy:
             self._packed = self.packed_actors()
-        return BatchedIPPO.roll_out(self, max_launches, fresh_episodes)
+        return super().roll_out(max_launches, fresh_episodes)
 
     def update(self, id, batch, shuffle=np.random.shuffle):
         self._packed = None                                   # the weights change: never carried across an update
         return super().update(id, batch, shuffle)
 
-    def _stored_actions(self, actions):
-        return actions
-
-    def _step_batch_fused(self):
-        """`step_batch` with the policy on the device: draw eps, `entity_act`, record, step, collect."""
-        torch, env = self.torch, self.env
-        r = self._req
-        ids = r["agent_id"].clone()
-        t0 = self._sync_time()
+    def _choose(self, r, ids):
+        if not self.fused_policy:
+            return self._choose_per_charger(ids, 3, lambda rows: EntityTransitionBuffers.pack(
+                r["nodes"].index_select(0, rows), r["chargers"].index_select(0, rows), r["env_feat"].index_select(0, rows))) + (None,)
+        torch, env = self.torch, self.env                     # the policy on the device: draw eps, `entity_act`
         if self._packed is None:
             self._packed = self.packed_actors()
         eps = torch.randn((env.num_env, 3), dtype=torch.float32, device=env.device)
         act3, act64, logp = env.entity_act(ids, self._packed, eps)
-        t1 = self._sync_time()
-        self.buffers.record(ids, act3, logp)
-        t2 = self._sync_time()
-        r = env.step(ids, act64)
-        t3 = self._sync_time()
-        bad = torch.nonzero(r["status"] < 0).flatten()
-        if bad.numel():
-            raise RuntimeError("environment rows %s report status %s" % (bad.tolist(), r["status"][bad].tolist()))
-        self.buffers.collect()
-        t4 = self._sync_time()
-        tm = self.timers
-        tm["policy_s"] += t1 - t0; tm["glue_s"] += (t2 - t1) + (t4 - t3); tm["env_s"] += t3 - t2; tm["launches"] += 1
-        tm["requests"] += int((ids >= 0).sum())
-        self.last_ids, self.last_action3 = ids, act3
-        self._req = r
-        return r
-
-    def step_batch(self):
-        """One launch of the batched roll-out: act for every environment that carries a request, step, collect."""
-        if self.fused_policy:
-            return self._step_batch_fused()
-        torch, env = self.torch, self.env
-        r = self._req
-        ids = r["agent_id"].clone()                           # the request's ids, detached from the tensor the step writes
-        t0 = self._sync_time()
-        act3 = torch.zeros((env.num_env, 3), dtype=torch.float32, device=env.device)
-        logp = torch.zeros((env.num_env,), dtype=torch.float32, device=env.device)
-        for a in range(self.num_agent):
-            rows = torch.nonzero(ids == a).flatten()
-            if rows.numel() == 0:
-                continue
-            x = EntityTransitionBuffers.pack(r["nodes"].index_select(0, rows), r["chargers"].index_select(0, rows), r["env_feat"].index_select(0, rows))
-            act, lp = self.get_action(a, x)
-            act3.index_copy_(0, rows, act.float()); logp.index_copy_(0, rows, lp.float())
-        t1 = self._sync_time()
-        self.buffers.record(ids, act3, logp)
-        t2 = self._sync_time()
-        r = env.step(ids, act3.double())
-        t3 = self._sync_time()
-        bad = torch.nonzero(r["status"] < 0).flatten()
-        if bad.numel():
-            raise RuntimeError("environment rows %s report status %s" % (bad.tolist(), r["status"][bad].tolist()))
-        self.buffers.collect()
-        t4 = self._sync_time()
-        tm = self.timers
-        tm["policy_s"] += t1 - t0; tm["glue_s"] += (t2 - t1) + (t4 - t3); tm["env_s"] += t3 - t2; tm["launches"] += 1
-        tm["requests"] += int((ids >= 0).sum())
-        self.last_ids, self.last_action3 = ids, act3          # what this launch handed to the environments (tests / logging)
-        self._req = r
-        return r
+        return act3, logp, act64

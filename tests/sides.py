@@ -10,7 +10,8 @@ of that module runs it on EmuSide and the test of the `_gpu` module (marked gpu)
     def test_x(...): body.x_matches(VecSide, ...)              # tests/test_x_gpu.py
 
 What a side offers: reset / step / view / decision / rows / density_action / render_state / save_envs / load_envs / clone_envs /
-set_pool / pool_reset / pool_info / entity_buffers / set_entity_out / entities / handle / close."""
+set_pool / pool_reset / pool_info / entity_buffers / set_entity_out / entities / handle / close.  EmuVec puts the part of VecWRSN's
+interface that the trainers of ippo.py use on top of an EmuSide."""
 import glob
 import os
 import random
@@ -227,6 +228,49 @@ class EmuSide(_Side):
 
     def close(self):
         self.h.close()
+
+
+class EmuVec:
+    """What the batched trainers and the transition buffers use of a VecWRSN, on an EmuSide that renders (float32), has entities, or
+    both: CPU tensors that share the memory the emulated library writes."""
+
+    def __init__(self, side):
+        import torch
+        from entity_ref import GUARD
+        self.torch, self.device, self.side = torch, torch.device("cpu"), side
+        self.num_env, self.num_agent, self.n_node, self.map_size = side.B, side.M, side.N, side.G
+        self.entities, self.auto_reset, self._h = side.ent is not None, side.auto_reset, side.handle
+        self.state = torch.from_numpy(side.obs) if side.render else None
+        self._t = {k: torch.from_numpy(getattr(side, k)) for k in FIELDS}
+        self.nodes_feat = self.chargers_feat = self.env_feat = None
+        if self.entities:
+            raw, shp = side.ent.raw, side.ent.shapes
+            self.nodes_feat, self.chargers_feat, self.env_feat = (
+                torch.from_numpy(raw[k][GUARD:-GUARD].view(np.float32).reshape(shp[k])) for k in ("node", "mc", "env"))
+        self._act = None
+
+    def _bind_stream(self):
+        pass
+
+    def _out_ptrs(self):
+        return self.side._ptrs()
+
+    def _result(self):
+        r = dict(self._t); r.update(state=self.state, nodes=self.nodes_feat, chargers=self.chargers_feat, env_feat=self.env_feat)
+        return r
+
+    def reset(self):
+        self.side.reset(); return self._result()
+
+    def step(self, ids, actions):
+        self.side.step(ids.numpy(), actions.numpy()); return self._result()
+
+    def density_to_action(self, ids, dmaps):
+        return self.torch.from_numpy(self.side.density_action(ids.numpy(), dmaps.numpy()))
+
+    def entity_act(self, ids, packed, eps=None):
+        from multi_agent_rl_wrsn_amd import VecWRSN
+        return VecWRSN.entity_act(self, ids, packed, eps)
 
 
 class VecSide(_Side):

@@ -5,7 +5,7 @@ synthetic rows, the actors and the reference (the module in float64 on the CPU; 
 float32 error over the rows of the test) are in tests/entity_act_ref.py."""
 import numpy as np
 import pytest
-from sides import EmuSide
+from sides import EmuSide, EmuVec
 
 import entity_act_ref as R
 
@@ -323,43 +323,6 @@ def test_packed_actors_follow_the_update():
     p1 = lr.packed_actors()
     assert not torch.equal(p1[0], p0[0]) and torch.equal(p1[1], p0[1])       # charger 0 was updated, charger 1 was not
     assert torch.equal(p1[0], pack_entity_actor(lr.actors[0]))
-
-
-class EmuVec:
-    """What BatchedEntityIPPO and EntityTransitionBuffers use of a VecWRSN, on an EmuSide with entities: CPU tensors that share the
-    memory the emulated library writes."""
-
-    def __init__(self, side):
-        import torch
-        self.torch, self.device, self.side = torch, torch.device("cpu"), side
-        self.num_env, self.num_agent, self.n_node, self.map_size = side.B, side.M, side.N, side.G
-        self.entities, self.auto_reset, self.state, self._h = True, side.auto_reset, None, side.handle
-        self._t = {k: torch.from_numpy(getattr(side, k)) for k in ("agent_id", "reward", "terminal", "now", "status")}
-        raw = side.ent.raw
-        shp = side.ent.shapes
-        self._e = {k: torch.from_numpy(raw[k][R.GUARD:-R.GUARD].view(np.float32).reshape(shp[k])) for k in shp}
-        self.nodes_feat, self.chargers_feat, self.env_feat = self._e["node"], self._e["mc"], self._e["env"]
-        self._act = None
-
-    def _bind_stream(self):
-        pass
-
-    def _out_ptrs(self):
-        return self.side._ptrs(False)
-
-    def _result(self):
-        r = dict(self._t); r.update(state=None, nodes=self.nodes_feat, chargers=self.chargers_feat, env_feat=self.env_feat)
-        return r
-
-    def reset(self):
-        self.side.reset(); return self._result()
-
-    def step(self, ids, actions):
-        self.side.step(ids.numpy(), actions.numpy()); return self._result()
-
-    def entity_act(self, ids, packed, eps=None):
-        from multi_agent_rl_wrsn_amd import VecWRSN
-        return VecWRSN.entity_act(self, ids, packed, eps)
 
 
 def _parent_step_batch(self):
