@@ -40,10 +40,14 @@ def main():
                     "entity: the set policy on entity rows, no image rendered (VecWRSN(render=False, entities=True), BatchedEntityIPPO)")
     ap.add_argument("--fused-policy", action="store_true", help="with --policy entity: the device samples the actions itself (wrsn_entity_act, "
                     "BatchedEntityIPPO(fused_policy=True)) instead of one PyTorch forward pass per charger")
+    ap.add_argument("--fused-update", action="store_true", help="with --policy entity: the PPO update runs on the device (wrsn_entity_ppo_grad, "
+                    "wrsn_entity_adam, BatchedEntityIPPO(fused_update=True)) instead of PyTorch autograd and torch.optim.Adam")
     ap.add_argument("--report-updates", action="store_true", help="add peak device memory and the statistics of every update (first minibatch included) to the line")
     args = ap.parse_args()
     if args.fused_policy and args.policy != "entity":
         raise SystemExit("--fused-policy needs --policy entity")
+    if args.fused_update and args.policy != "entity":
+        raise SystemExit("--fused-update needs --policy entity")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:       # launcher-free multi-rank entry: before this process touches torch or the GPU
         from multi_agent_rl_wrsn_amd.sharding import launch_ranks
         raise SystemExit(launch_ranks(args.gpus, [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]))
@@ -69,7 +73,7 @@ def main():
         env = VecWRSN([synth_scenario(rank * B + e, N, N) for e in range(B)], None, M, auto_reset=True, step_budget=args.step_budget, device=str(dev),
                       render=False, entities=True)             # no image at all: 6.6 KB of entity rows per request
         algo = BatchedEntityIPPO(ppo_args, env, capacity=max(2 * args.batch_size, 4096), infer_chunk=args.infer_chunk, min_bucket=args.infer_chunk,
-                                 **({"fused_policy": True} if args.fused_policy else {}))
+                                 **({"fused_policy": True} if args.fused_policy else {}), **({"fused_update": True} if args.fused_update else {}))
     else:
         env = VecWRSN([synth_scenario(rank * B + e, N, N) for e in range(B)], None, M, auto_reset=True, step_budget=args.step_budget, device=str(dev),
                       reuse_obs=True, obs_dtype=args.obs_dtype)                             # BatchedIPPO only reads the state tensor (index_select / copies)
@@ -85,6 +89,9 @@ def main():
             return res
         algo.minibatch_loss = minibatch_loss
         algo.log = lambda row: updates.append(dict(row, first_minibatch=first.pop(row["agent"], {})))
+        if args.fused_update:                                  # no minibatch_loss is called: the device table's first row
+            algo.log = lambda row: updates.append(dict(row, first_minibatch=dict(approx_kl=algo.first_minibatch_stats[row["agent"]][4],
+                                                                                 clipfrac=algo.first_minibatch_stats[row["agent"]][5])))
     if args.warmup_iters > 0:
         algo.train(args.warmup_iters - 1)
         for k in algo.timers: algo.timers[k] = 0 if isinstance(algo.timers[k], int) else 0.0
@@ -121,7 +128,8 @@ def main():
     if entity:
         out["config"]["workload"] = "%d envs x %d nodes x %d MC, set actor + critic per charger on entity rows, 3-vector actions, batch %d / minibatch %d / %d epochs" % (
             B, N, M, args.batch_size, args.minibatch_size, args.updates)
-        out["config"]["policy"] = "float32, entity rows, no image" + (", actions sampled on the device (wrsn_entity_act)" if args.fused_policy else "")
+        out["config"]["policy"] = "float32, entity rows, no image" + (", actions sampled on the device (wrsn_entity_act)" if args.fused_policy else "") + (
+            ", update on the device (wrsn_entity_ppo_grad, wrsn_entity_adam)" if args.fused_update else "")
     if args.report_updates:
         out["peak_memory_bytes"] = int(torch.cuda.max_memory_allocated(dev)); out["updates"] = updates
     print(json.dumps(out, default=float), flush=True)

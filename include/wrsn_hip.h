@@ -350,6 +350,68 @@ typedef struct wrsn_entity_act_out {    /* DEVICE, caller-owned; written only fo
 int wrsn_entity_act(wrsn_t *h, const float *actors, const int32_t *agent_id, const float *eps, const wrsn_entity_out *ent,
                     const wrsn_entity_act_out *out);
 
+/* THE PPO UPDATE OF THE ENTITY POLICY.  One minibatch step of PPOLearner.update (ippo.py) for the set networks of build_entity_networks:
+ * forward, PPO loss, backward, gradient clipping and Adam as a handful of launches on the handle's stream, nothing read back on the host.
+ * None of the three calls needs a scenario: the handle supplies the stream and a scratch area that grows on demand and is freed by
+ * wrsn_destroy.  All asynchronous.
+ *
+ * The CRITIC block: the trunk (node1, node2, mc1, mc2, head1, head2, every Linear [in, out] followed by its bias) at the offsets of the
+ * actor block, through head2's bias: 48 448 floats; then value (128 -> 1) [in, out] at 48 448 and its bias at 48 576: 48 577 floats,
+ * zeros up to wrsn_entity_critic_floats() == 48 580.
+ *
+ * ROWS: packed entity rows as the transition buffers store them, R = 8 n_node + 12 n_mc + 8 floats each (node [N][8], mc [M][12], env [8]).
+ * Minibatch row i is row index[i] of `rows` (index == NULL: rows 0 .. n - 1; repeats are allowed).  1 <= n_mc <= 8, n_node >= 1, n >= 1.
+ *
+ * wrsn_entity_eval: EntityActor.forward and EntityCritic.forward on the rows: float32 mean [n,3], log_std [n,3] (after the clamp to
+ * [-4, 1]) and value [n].  actor or critic may be NULL; then that net's outputs must be NULL too.  Masks and selects are those of
+ * wrsn_entity_act; a row's outputs depend on that row and the block only; for one row content and one block, mean and log_std are
+ * bit-equal to what wrsn_entity_act writes.
+ *
+ * wrsn_entity_ppo_grad: the loss of PPOLearner.minibatch_loss on the n rows and its gradient.  With sigma = exp(log_std), z = (a - mu) / sigma:
+ *   newlogp = sum_d(-z^2/2 - log_std_d) - 1.5 log 2 pi, H = sum_d(log_std_d + 1/2 + 1/2 log 2 pi), l = newlogp - logp_old, r = e^l,
+ *   approx_kl = mean((r - 1) - l), clipfrac = mean(|r - 1| > clip), A^ = (A - mean A) / (std A + 1e-8) (unbiased std over the n rows) with
+ *   norm_adv, else A; pg = mean(max(-A^ r, -A^ clamp(r, 1 - clip, 1 + clip))); v_loss = 1/2 mean(max((v - R)^2, (V + clamp(v - V, -clip,
+ *   clip) - R)^2)) with clip_vloss, else 1/2 mean((v - R)^2); loss = pg - ent_coef mean(H) + vf_coef v_loss.
+ * batch arrays are float32 and indexed by the same `index` as the rows.  grad_actor [wrsn_entity_actor_floats()] and grad_critic
+ * [wrsn_entity_critic_floats()] receive d loss / d block in the block's own layout: overwritten, not accumulated, padding zero.
+ * stats: float32 [8] on the device: loss, pg, v_loss, entropy, approx_kl, clipfrac, 0, 0.  Derivatives at the kinks are autograd's: ReLU
+ * passes where its output is > 0, a clamp on the closed interval, of two terms under a max the larger (equal terms: their mean), the masked
+ * maximum goes to the lowest-index alive node that attains it, nothing flows into the advantages or through the alive / is_self selects.
+ * Two calls on equal inputs give equal bytes: every sum has a fixed order, no float atomics.
+ *
+ * wrsn_entity_adam: clip_grad_norm_ (max_norm) then torch.optim.Adam (no weight decay, no amsgrad) in place on one block of n_floats:
+ *   g *= min(1, max_norm / (||g|| + 1e-6)); m = beta1 m + (1 - beta1) g; v = beta2 v + (1 - beta2) g^2;
+ *   p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps).   `grad` itself is left as it is.  norm_out: a device float
+ * that receives ||g||, or NULL.
+ *
+ * WRSN_ERR_ARG, with every buffer untouched: a required pointer NULL (eval: h, rows, rows->rows, one of actor / critic, an output of a net
+ * that is given -- at least one; an output of a net that is not given must be NULL); a block, rows->rows or a gradient buffer (adam:
+ * param, grad, m, v) not 16-byte aligned; n < 1, or n < 2 with norm_adv; n_mc outside [1, 8]; n_node < 1; n_floats < 1; step < 1. */
+int32_t wrsn_entity_critic_floats(void); /* floats of one critic block, a multiple of 4; host only, no handle */
+
+typedef struct wrsn_entity_rows {       /* DEVICE pointers */
+    const float *rows;                  /* [*, R] float32, 16-byte aligned */
+    const int32_t *index;               /* [n] or NULL */
+    int32_t n, n_node, n_mc;
+} wrsn_entity_rows;
+
+typedef struct wrsn_ppo_batch {         /* DEVICE, float32, indexed like the rows */
+    const float *action;                /* [*, 3] */
+    const float *logp_old, *advantage, *ret, *value_old;
+} wrsn_ppo_batch;
+
+typedef struct wrsn_ppo_hyper {
+    float clip, ent_coef, vf_coef;
+    int32_t norm_adv, clip_vloss;
+} wrsn_ppo_hyper;
+
+int wrsn_entity_eval(wrsn_t *h, const float *actor, const float *critic, const wrsn_entity_rows *rows, float *mean, float *log_std,
+                     float *value);
+int wrsn_entity_ppo_grad(wrsn_t *h, const float *actor, const float *critic, const wrsn_entity_rows *rows, const wrsn_ppo_batch *batch,
+                         const wrsn_ppo_hyper *hyper, float *grad_actor, float *grad_critic, float *stats);
+int wrsn_entity_adam(wrsn_t *h, float *param, const float *grad, float *m, float *v, int32_t n_floats, int32_t step, float lr, float beta1,
+                     float beta2, float eps, float max_norm, float *norm_out);
+
 /* Copy internal state to HOST memory (parity tests, `net` / `agents` views).  Synchronises. */
 int wrsn_peek(wrsn_t *h, int32_t what, void *dst);
 

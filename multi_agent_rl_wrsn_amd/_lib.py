@@ -30,6 +30,7 @@ ENT_ENV_FIELDS = ("h_x", "h_y", "h_self_x", "h_self_y", "agent", "n_node", "_r0"
 ENT_NODE = {k: i for i, k in enumerate(ENT_NODE_FIELDS)}      # ENT_NODE["weight"] == 2: the slot of a field, no magic numbers at the caller
 ENT_MC = {k: i for i, k in enumerate(ENT_MC_FIELDS) if not k.startswith("_")}
 ENT_ENV = {k: i for i, k in enumerate(ENT_ENV_FIELDS) if not k.startswith("_")}
+ENTITY_ACTOR_FLOATS, ENTITY_CRITIC_FLOATS = 49224, 48580   # wrsn_entity_actor_floats(), wrsn_entity_critic_floats() (include/wrsn_hip.h)
 ENTPOL_FEAT = 200            # wrsn_entity_act: inputs of the actor's head (64 mean + 64 max + 32 charger mean + 32 own + 8 env)
 MC_FIELDS = ("loc_x", "loc_y", "energy", "status", "type_charging", "cur_x", "cur_y", "cur_t", "n_conn",
              "excl", "prev_minfit", "act0", "act1", "act2", "_r0", "_r1")
@@ -38,7 +39,7 @@ ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max"
 
 # every entry point include/wrsn_hip.h declares
 EXPORTS = ("wrsn_create", "wrsn_destroy", "wrsn_set_stream", "wrsn_set_scenario", "wrsn_set_scenario_seeded", "wrsn_reset", "wrsn_step",
-           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_entity_actor_floats", "wrsn_entity_act", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
+           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_entity_actor_floats", "wrsn_entity_act", "wrsn_entity_critic_floats", "wrsn_entity_eval", "wrsn_entity_ppo_grad", "wrsn_entity_adam", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
            "wrsn_clone_envs", "wrsn_pool_set", "wrsn_pool_reset", "wrsn_synth_network",
            "wrsn_last_error",
            "wrsn_version")
@@ -71,6 +72,18 @@ class WrsnEntityOut(C.Structure):
 
 class WrsnEntityActOut(C.Structure):
     _fields_ = [("action", C.c_void_p), ("action_f64", C.c_void_p), ("logp", C.c_void_p), ("mean", C.c_void_p), ("log_std", C.c_void_p)]
+
+
+class WrsnEntityRows(C.Structure):
+    _fields_ = [("rows", C.c_void_p), ("index", C.c_void_p), ("n", C.c_int32), ("n_node", C.c_int32), ("n_mc", C.c_int32)]
+
+
+class WrsnPpoBatch(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("action", "logp_old", "advantage", "ret", "value_old")]
+
+
+class WrsnPpoHyper(C.Structure):
+    _fields_ = [("clip", C.c_float), ("ent_coef", C.c_float), ("vf_coef", C.c_float), ("norm_adv", C.c_int32), ("clip_vloss", C.c_int32)]
 
 
 class WrsnTransitionBuffers(C.Structure):
@@ -124,6 +137,14 @@ def bind(lib):
     lib.wrsn_entity_actor_floats.restype = C.c_int32
     lib.wrsn_entity_act.argtypes = [vp, vp, vp, vp, C.POINTER(WrsnEntityOut), C.POINTER(WrsnEntityActOut)]
     lib.wrsn_entity_act.restype = C.c_int
+    lib.wrsn_entity_critic_floats.argtypes = []
+    lib.wrsn_entity_critic_floats.restype = C.c_int32
+    lib.wrsn_entity_eval.argtypes = [vp, vp, vp, C.POINTER(WrsnEntityRows), vp, vp, vp]
+    lib.wrsn_entity_eval.restype = C.c_int
+    lib.wrsn_entity_ppo_grad.argtypes = [vp, vp, vp, C.POINTER(WrsnEntityRows), C.POINTER(WrsnPpoBatch), C.POINTER(WrsnPpoHyper), vp, vp, vp]
+    lib.wrsn_entity_ppo_grad.restype = C.c_int
+    lib.wrsn_entity_adam.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, vp]
+    lib.wrsn_entity_adam.restype = C.c_int
     lib.wrsn_set_obs_reuse.argtypes = [vp, C.c_int32]
     lib.wrsn_set_obs_reuse.restype = C.c_int
     lib.wrsn_set_obs_format.argtypes = [vp, C.c_int32]
@@ -324,6 +345,33 @@ class RawHandle:
         o = WrsnEntityActOut(action or None, action_f64 or None, logp or None, mean or None, log_std or None)
         check(self.lib, self.lib.wrsn_entity_act(self._h, C.c_void_p(actors_ptr or None), C.c_void_p(agent_ptr or None), C.c_void_p(eps_ptr or None),
                                                  self._ent(ent_ptrs), C.byref(o)))
+
+    @staticmethod
+    def _rows(rows_ptr, index_ptr, n, n_node, n_mc):
+        return C.byref(WrsnEntityRows(rows_ptr or None, index_ptr or None, int(n), int(n_node), int(n_mc)))
+
+    def entity_eval(self, actor_ptr, critic_ptr, rows_ptr, index_ptr, n, n_node, n_mc, mean=0, log_std=0, value=0):
+        """wrsn_entity_eval: the actor block at actor_ptr and / or the critic block at critic_ptr (0: not asked) on the n packed entity
+        rows index_ptr (int32 [n]; 0: rows 0 .. n - 1) picks from rows_ptr; mean [n,3], log_std [n,3], value [n] are float32 addresses."""
+        check(self.lib, self.lib.wrsn_entity_eval(self._h, C.c_void_p(actor_ptr or None), C.c_void_p(critic_ptr or None),
+                                                  self._rows(rows_ptr, index_ptr, n, n_node, n_mc), C.c_void_p(mean or None),
+                                                  C.c_void_p(log_std or None), C.c_void_p(value or None)))
+
+    def entity_ppo_grad(self, actor_ptr, critic_ptr, rows_ptr, index_ptr, n, n_node, n_mc, action, logp_old, advantage, ret, value_old,
+                        clip, ent_coef, vf_coef, norm_adv, clip_vloss, grad_actor, grad_critic, stats):
+        """wrsn_entity_ppo_grad: loss of PPOLearner.minibatch_loss on the n rows, d loss / d block into grad_actor / grad_critic (block
+        layout, overwritten) and the statistics (float32 [8]: loss, pg, v_loss, entropy, approx_kl, clipfrac, 0, 0) into stats."""
+        b = WrsnPpoBatch(action or None, logp_old or None, advantage or None, ret or None, value_old or None)
+        hp = WrsnPpoHyper(float(clip), float(ent_coef), float(vf_coef), 1 if norm_adv else 0, 1 if clip_vloss else 0)
+        check(self.lib, self.lib.wrsn_entity_ppo_grad(self._h, C.c_void_p(actor_ptr or None), C.c_void_p(critic_ptr or None),
+                                                      self._rows(rows_ptr, index_ptr, n, n_node, n_mc), C.byref(b), C.byref(hp),
+                                                      C.c_void_p(grad_actor or None), C.c_void_p(grad_critic or None), C.c_void_p(stats or None)))
+
+    def entity_adam(self, param, grad, m, v, n_floats, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, max_norm=0.5, norm_out=0):
+        """wrsn_entity_adam: clip_grad_norm_(max_norm) then one torch.optim.Adam step, in place on the block of n_floats at `param`."""
+        check(self.lib, self.lib.wrsn_entity_adam(self._h, C.c_void_p(param or None), C.c_void_p(grad or None), C.c_void_p(m or None),
+                                                  C.c_void_p(v or None), int(n_floats), int(step), float(lr), float(beta1), float(beta2), float(eps),
+                                                  float(max_norm), C.c_void_p(norm_out or None)))
 
     def set_obs_reuse(self, on):
         check(self.lib, self.lib.wrsn_set_obs_reuse(self._h, 1 if on else 0))

@@ -15,6 +15,7 @@
 #include "wrsn_sim.h"
 #include "wrsn_rollout.h"
 #include "wrsn_state.h"
+#include "wrsn_entity_train.h"
 
 namespace {
 
@@ -110,6 +111,9 @@ struct wrsn_handle {
     WrsnEntityOut ent{};            // wrsn_set_entity_out: the caller's entity-observation buffers (node == nullptr: off, the default)
     // wrsn_entity_act (allocated by its first call): the head's inputs [B, WRSN_ENTPOL_FEAT], the row lists [M, B] and counters [8] per charger
     float* ep_feat = nullptr; int32_t* ep_list = nullptr; int32_t* ep_cnt = nullptr;
+    // wrsn_entity_eval / wrsn_entity_ppo_grad / wrsn_entity_adam: the scratch area (grown on demand, the old one kept until wrsn_destroy: launches
+    // in flight may still use it) and the gradient norm of the Adam call
+    float* et_scratch = nullptr; size_t et_cap = 0; float* et_norm = nullptr;
 };
 
 namespace {
@@ -983,6 +987,106 @@ int wrsn_entity_act(wrsn_t* h, const float* actors, const int32_t* agent_id, con
     hipLaunchKernelGGL(wrsn_entpol_trunk_kernel, dim3(B), dim3(256), WRSN_EP_T_LDS, h->stream, B, M, h->dev.N, actors, agent_id, e, h->ep_feat);
     hipLaunchKernelGGL(wrsn_entpol_head_kernel, dim3((B + WRSN_EP_HEAD_ROWS - 1) / WRSN_EP_HEAD_ROWS + M), dim3(256), WRSN_EP_H_LDS, h->stream, B, M,
                        actors, (const float*)h->ep_feat, (const int32_t*)h->ep_list, (const int32_t*)h->ep_cnt, eps, o);
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+// ------------------------------------------------------------------ the PPO update of the entity policy (wrsn_entity_train.h)
+int32_t wrsn_entity_critic_floats(void) { return WRSN_EC_FLOATS; }
+
+namespace {
+const char* entity_rows_bad(const wrsn_entity_rows* r) {
+    if (!r || !r->rows) return "rows and rows->rows are required";
+    if ((uintptr_t)r->rows % 16) return "rows->rows must be 16-byte aligned";
+    if (r->n < 1) return "n must be >= 1";
+    if (r->n_mc < 1 || r->n_mc > WRSN_MAX_MC) return "n_mc must be in [1, 8]";
+    if (r->n_node < 1) return "n_node must be >= 1";
+    return nullptr;
+}
+int entity_scratch(wrsn_handle* h, int n, bool grad, WrsnEtScratch* s) {
+    const size_t need = wrsn_et_scratch_floats((size_t)n, grad);
+    if (need > h->et_cap) {
+        const int rc = dalloc(h, &h->et_scratch, need);
+        if (rc) return rc;
+        h->et_cap = need;
+    }
+    float* p = h->et_scratch;
+    const size_t q = 2 * (size_t)n;
+    s->feat = p; p += q * WRSN_ENTPOL_FEAT; s->arg = p; p += q * 64; s->cnt = p; p += q * 4; s->z1 = p; p += q * 128; s->z2 = p; p += q * 128;
+    s->raw = p; p += 8 * (size_t)n;
+    s->dz1 = s->dz2 = s->dfeat = s->part = s->dout = nullptr;
+    if (grad) {
+        s->dz1 = p; p += q * 128; s->dz2 = p; p += q * 128; s->dfeat = p; p += q * WRSN_ENTPOL_FEAT; s->part = p; p += q * WRSN_ET_TRUNK_FLOATS;
+        s->dout = p; p += 8 * (size_t)n;
+    }
+    return 0;
+}
+void entity_forward(wrsn_handle* h, const WrsnEtRows& rw, const float* actor, const float* critic, const WrsnEtScratch& s, const WrsnEtEvalOut& o) {
+    hipLaunchKernelGGL(wrsn_et_trunk_fwd_kernel, dim3(2 * rw.n), dim3(256), WRSN_ET_T_LDS, h->stream, rw, actor, critic, s);
+    hipLaunchKernelGGL(wrsn_et_head_fwd_kernel, dim3(2 * ((rw.n + WRSN_EP_HEAD_ROWS - 1) / WRSN_EP_HEAD_ROWS)), dim3(256), WRSN_EP_H_LDS, h->stream,
+                       rw.n, actor, critic, s, o);
+}
+}  // namespace
+
+int wrsn_entity_eval(wrsn_t* h, const float* actor, const float* critic, const wrsn_entity_rows* rows, float* mean, float* log_std, float* value) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    if (const char* bad = entity_rows_bad(rows)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_eval: ") + bad);
+    if (!actor && !critic) return fail(WRSN_ERR_ARG, "wrsn_entity_eval needs an actor or a critic");
+    if ((actor && !mean && !log_std) || (critic && !value)) return fail(WRSN_ERR_ARG, "wrsn_entity_eval: a net that is given needs an output");
+    if ((!actor && (mean || log_std)) || (!critic && value)) return fail(WRSN_ERR_ARG, "wrsn_entity_eval: outputs of a net that is not given must be NULL");
+    if ((uintptr_t)actor % 16 || (uintptr_t)critic % 16) return fail(WRSN_ERR_ARG, "wrsn_entity_eval: blocks must be 16-byte aligned");
+    WRSN_ON_DEVICE(h);
+    WrsnEtScratch s;
+    { const int rc = entity_scratch(h, rows->n, false, &s); if (rc) return rc; }
+    WrsnEtRows rw; rw.rows = rows->rows; rw.index = rows->index; rw.n = rows->n; rw.N = rows->n_node; rw.M = rows->n_mc;
+    WrsnEtEvalOut o; o.mean = mean; o.log_std = log_std; o.value = value;
+    entity_forward(h, rw, actor, critic, s, o);
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+int wrsn_entity_ppo_grad(wrsn_t* h, const float* actor, const float* critic, const wrsn_entity_rows* rows, const wrsn_ppo_batch* batch,
+                         const wrsn_ppo_hyper* hyper, float* grad_actor, float* grad_critic, float* stats) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    if (const char* bad = entity_rows_bad(rows)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_ppo_grad: ") + bad);
+    if (!actor || !critic || !batch || !hyper || !grad_actor || !grad_critic || !stats || !batch->action || !batch->logp_old || !batch->advantage ||
+        !batch->ret || !batch->value_old)
+        return fail(WRSN_ERR_ARG, "wrsn_entity_ppo_grad needs actor, critic, every batch array, hyper, grad_actor, grad_critic and stats");
+    if ((uintptr_t)actor % 16 || (uintptr_t)critic % 16 || (uintptr_t)grad_actor % 16 || (uintptr_t)grad_critic % 16)
+        return fail(WRSN_ERR_ARG, "wrsn_entity_ppo_grad: blocks and gradient buffers must be 16-byte aligned");
+    if (hyper->norm_adv && rows->n < 2) return fail(WRSN_ERR_ARG, "wrsn_entity_ppo_grad: norm_adv needs n >= 2");
+    WRSN_ON_DEVICE(h);
+    WrsnEtScratch s;
+    { const int rc = entity_scratch(h, rows->n, true, &s); if (rc) return rc; }
+    WrsnEtRows rw; rw.rows = rows->rows; rw.index = rows->index; rw.n = rows->n; rw.N = rows->n_node; rw.M = rows->n_mc;
+    WrsnEtBatch b; b.action = batch->action; b.logp_old = batch->logp_old; b.advantage = batch->advantage; b.ret = batch->ret; b.value_old = batch->value_old;
+    WrsnEtHyper hp; hp.clip = hyper->clip; hp.ent_coef = hyper->ent_coef; hp.vf_coef = hyper->vf_coef; hp.norm_adv = hyper->norm_adv != 0;
+    hp.clip_vloss = hyper->clip_vloss != 0;
+    WrsnEtEvalOut o; o.mean = nullptr; o.log_std = nullptr; o.value = nullptr;
+    const int n = rw.n;
+    entity_forward(h, rw, actor, critic, s, o);
+    hipLaunchKernelGGL(wrsn_et_loss_kernel, dim3(1), dim3(256), 256 * sizeof(double), h->stream, n, rw.index, b, hp, s, stats);
+    hipLaunchKernelGGL(wrsn_et_head_bwd_kernel, dim3(2 * n), dim3(256), 256 * sizeof(float), h->stream, n, actor, critic, s);
+    hipLaunchKernelGGL(wrsn_et_trunk_bwd_kernel, dim3(2 * n), dim3(256), WRSN_ET_B_LDS, h->stream, rw, actor, critic, s);
+    hipLaunchKernelGGL(wrsn_et_reduce_kernel, dim3(2 * ((WRSN_EP_FLOATS + 255) / 256)), dim3(256), 0, h->stream, n, s, grad_actor, grad_critic);
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+int wrsn_entity_adam(wrsn_t* h, float* param, const float* grad, float* m, float* v, int32_t n_floats, int32_t step, float lr, float beta1,
+                     float beta2, float eps, float max_norm, float* norm_out) {
+    if (!h || !param || !grad || !m || !v) return fail(WRSN_ERR_ARG, "wrsn_entity_adam needs param, grad, m and v");
+    if ((uintptr_t)param % 16 || (uintptr_t)grad % 16 || (uintptr_t)m % 16 || (uintptr_t)v % 16)
+        return fail(WRSN_ERR_ARG, "wrsn_entity_adam: param, grad, m and v must be 16-byte aligned");
+    if (n_floats < 1) return fail(WRSN_ERR_ARG, "wrsn_entity_adam: n_floats must be >= 1");
+    if (step < 1) return fail(WRSN_ERR_ARG, "wrsn_entity_adam: step must be >= 1");
+    WRSN_ON_DEVICE(h);
+    if (!h->et_norm) { const int rc = dalloc(h, &h->et_norm, (size_t)4); if (rc) return rc; }
+    const double bc1 = 1.0 - std::pow((double)beta1, (double)step), bc2 = 1.0 - std::pow((double)beta2, (double)step);
+    hipLaunchKernelGGL(wrsn_et_norm_kernel, dim3(1), dim3(256), 256 * sizeof(double), h->stream, grad, (int)n_floats, h->et_norm, norm_out);
+    hipLaunchKernelGGL(wrsn_et_adam_kernel, dim3((n_floats + 255) / 256), dim3(256), 0, h->stream, param, grad, m, v, (int)n_floats,
+                       (const float*)h->et_norm, (float)((double)lr / bc1), (float)(1.0 / std::sqrt(bc2)), beta1, beta2, (float)(1.0 - (double)beta1),
+                       (float)(1.0 - (double)beta2), eps, max_norm);
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }

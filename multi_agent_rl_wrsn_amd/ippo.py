@@ -789,6 +789,43 @@ def pack_entity_actor(actor):
     return torch.cat([flat, flat.new_zeros((-flat.numel()) % 4)])
 
 
+def _entity_layers(net):
+    t = net.trunk
+    return (t.node1, t.node2, t.mc1, t.mc2, t.head1, t.head2) + ((net.value,) if hasattr(net, "value") else (net.mean, net.log_std))
+
+
+def pack_entity_critic(critic):
+    """The `EntityCritic` as the float32 block `wrsn_entity_eval` / `wrsn_entity_ppo_grad` read (layout: include/wrsn_hip.h): the trunk at
+    the offsets of the actor block, then `value`, every Linear transposed to [in, out] and followed by its bias, zeros up to a multiple of
+    4 floats.  A new tensor; it does not follow later changes of the parameters."""
+    torch = _torch()
+    parts = []
+    for layer in _entity_layers(critic):
+        parts += [layer.weight.detach().t().reshape(-1), layer.bias.detach().reshape(-1)]
+    flat = torch.cat([p.to(torch.float32) for p in parts])
+    return torch.cat([flat, flat.new_zeros((-flat.numel()) % 4)])
+
+
+def _unpack_entity(block, net):
+    torch = _torch()
+    o = 0
+    with torch.no_grad():
+        for layer in _entity_layers(net):
+            w, b = layer.weight, layer.bias
+            w.copy_(block[o:o + w.numel()].view(w.shape[1], w.shape[0]).t()); o += w.numel()
+            b.copy_(block[o:o + b.numel()]); o += b.numel()
+
+
+def unpack_entity_actor(block, actor):
+    """`pack_entity_actor` backwards: `copy_` of the block's floats into the parameters of `actor` (unpack(pack(x)) is x bit for bit)."""
+    _unpack_entity(block, actor)
+
+
+def unpack_entity_critic(block, critic):
+    """`pack_entity_critic` backwards: `copy_` of the block's floats into the parameters of `critic`."""
+    _unpack_entity(block, critic)
+
+
 class EntityPPOLearner(PPOLearner):
     """`PPOLearner` with the set networks of `build_entity_networks` over packed entity rows and 3-vector actions.  `evaluate`,
     `get_value`, `cal_rt_adv`, `minibatch_loss`, `update`, the data-parallel gradient exchange and the checkpoints are inherited.
@@ -821,18 +858,32 @@ class BatchedEntityIPPO(RolloutDriver, EntityPPOLearner):
 
     fused_policy : True = the device chooses the actions itself (`VecWRSN.entity_act`, `wrsn_entity_act`): one call on the entity rows the
                    environment holds, with the actors packed at the start of the roll-out (`packed_actors`) and standard-normal draws
-                   of `torch.randn`; no row gathering and no per-charger forward pass.  False (the default): `get_action` per charger."""
+                   of `torch.randn`; no row gathering and no per-charger forward pass.  False (the default): `get_action` per charger.
+    fused_update : True = `update` runs on the device (`wrsn_entity_ppo_grad`, `wrsn_entity_adam`): per minibatch one gradient call into
+                   one flat tensor, (data-parallel: one all-reduce of it,) one Adam call each for actor and critic, nothing read back
+                   until the update is over; `_values` (hence `cal_rt_adv`) goes through `wrsn_entity_eval`.  The modules stay the source
+                   of truth between updates (they are packed at the start of `update` and written back at its end, so checkpoints load
+                   and save as ever), but the Adam moments and step counts live in this object in block layout and the torch optimisers
+                   are never stepped.  The mode is fixed at construction.  False (the default): the PyTorch update, no new launch."""
 
     _check_status = True
 
     def __init__(self, args, env, device=None, model_path=None, capacity=None, infer_chunk=1024, process_group=None, log=None, min_bucket=16,
-                 fused_policy=False):
+                 fused_policy=False, fused_update=False):
         if not getattr(env, "entities", False):
             raise ValueError("BatchedEntityIPPO needs a VecWRSN with the entity observation (entities=True)")
         super().__init__(args, env.num_agent, device if device is not None else env.device, model_path, infer_chunk, process_group, min_bucket)
         self._attach(env, EntityTransitionBuffers(env, capacity or 2 * self.batch_size, 3), log)
         self.fused_policy = bool(fused_policy)
         self._packed = None                                   # packed_actors() of the weights as they are now, or None: rebuilt before use
+        self.fused_update = bool(fused_update)
+        self.first_minibatch_stats = [None] * self.num_agent  # fused_update: (loss, pg, v_loss, entropy, approx_kl, clipfrac) of an update's first minibatch
+        if self.fused_update:
+            torch = self.torch
+            self._pa, self._pc = _lib.ENTITY_ACTOR_FLOATS, _lib.ENTITY_CRITIC_FLOATS
+            z = lambda n: torch.zeros(n, dtype=torch.float32, device=env.device)
+            self._grad = z(self._pa + self._pc)               # ONE tensor: what the data-parallel exchange reduces
+            self._adam = [dict(m_a=z(self._pa), v_a=z(self._pa), m_c=z(self._pc), v_c=z(self._pc), step=0) for _ in range(self.num_agent)]
 
     def roll_out(self, max_launches=100000, fresh_episodes=False):
         if self.fused_policy:
@@ -841,7 +892,50 @@ class BatchedEntityIPPO(RolloutDriver, EntityPPOLearner):
 
     def update(self, id, batch, shuffle=np.random.shuffle):
         self._packed = None                                   # the weights change: never carried across an update
+        if self.fused_update:
+            return self._update_fused(id, batch, shuffle)
         return super().update(id, batch, shuffle)
+
+    def _values(self, agent_id, states):
+        if not self.fused_update:
+            return super()._values(agent_id, states)
+        torch = self.torch
+        blk = pack_entity_critic(self.critics[agent_id]).to(self.env.device)
+        return self.env.entity_eval(states.to(torch.float32).contiguous(), critic=blk)[2]
+
+    def _update_fused(self, id, batch, shuffle):
+        """`PPOLearner.update` on the device: the same epochs, the same shuffles and minibatches, the same return value."""
+        torch, env = self.torch, self.env
+        dev = env.device
+        f32 = lambda x: x.to(device=dev, dtype=torch.float32).contiguous()
+        blk_a, blk_c = f32(pack_entity_actor(self.actors[id])), f32(pack_entity_critic(self.critics[id]))
+        rows = f32(batch["states"])
+        b = {"actions": f32(batch["actions"]).reshape(-1, 3), "log_probs": f32(batch["log_probs"]), "advantages": f32(batch["advantages"]),
+             "returns": f32(batch["returns"]), "values": f32(batch["values"])}
+        hyper = dict(clip=self.clip, ent_coef=self.ent_coef, vf_coef=self.vf_coef, norm_adv=self.norm_adv, clip_vloss=self.clip_vloss)
+        per_epoch = (self.batch_size + self.minibatch_size - 1) // self.minibatch_size
+        table = torch.zeros((self.n_updates_per_iteration * per_epoch, 8), dtype=torch.float32, device=dev)
+        st, ga, gc, lr = self._adam[id], self._grad[:self._pa], self._grad[self._pa:], self.args["lr"]
+        b_inds = np.arange(self.batch_size)
+        k, keep = 0, []
+        for _ in range(self.n_updates_per_iteration):
+            shuffle(b_inds)
+            idx = torch.from_numpy(b_inds.astype(np.int32)).to(dev)      # uploaded once per epoch
+            keep.append(idx)                                          # the launches are asynchronous: alive until the table is read
+            for start in range(0, self.batch_size, self.minibatch_size):
+                env.entity_ppo_grad(blk_a, blk_c, rows, idx[start:start + self.minibatch_size], b, hyper, self._grad, table[k])
+                if self.world > 1:
+                    torch.distributed.all_reduce(self._grad, group=self.group)
+                    self._grad /= self.world
+                st["step"] += 1
+                env.entity_adam(blk_a, ga, st["m_a"], st["v_a"], st["step"], lr, self.max_grad_norm)
+                env.entity_adam(blk_c, gc, st["m_c"], st["v_c"], st["step"], lr, self.max_grad_norm)
+                k += 1
+        unpack_entity_actor(blk_a, self.actors[id]); unpack_entity_critic(blk_c, self.critics[id])
+        t = table.cpu().numpy().astype(np.float64)                   # the one read of the update
+        self.loggers[id]["losses"].extend(float(x) for x in t[:, 0])
+        self.first_minibatch_stats[id] = tuple(float(x) for x in t[0, :6])
+        return (float(t[-1, 1]), float(t[-1, 2]), float(t[-1, 3]), float(t[-1, 4]), float(np.mean(t[:, 5])))
 
     def _choose(self, r, ids):
         if not self.fused_policy:

@@ -358,6 +358,51 @@ class VecWRSN:
         """Per environment: the pool record it runs (-1: its own scenario or a loaded record) and its swaps since `set_pool` (host copies)."""
         return self._h.pool_info()
 
+    # -- the PPO update of the entity policy (wrsn_entity_eval / wrsn_entity_ppo_grad / wrsn_entity_adam): thin wrappers that bind the stream
+    def _entity_rows(self, rows, index):
+        t = self.torch
+        if not (rows.dtype == t.float32 and rows.is_contiguous() and rows.dim() == 2):
+            raise ValueError("rows must be a contiguous float32 tensor [*, R]")
+        M = self.num_agent
+        N = (rows.shape[1] - 12 * M - 8) // 8
+        if N < 1 or 8 * N + 12 * M + 8 != rows.shape[1]:
+            raise ValueError("rows of %d floats are no packed entity rows of %d chargers" % (rows.shape[1], M))
+        if index is not None and not (index.dtype == t.int32 and index.is_contiguous()):
+            raise ValueError("index must be a contiguous int32 tensor")
+        n = rows.shape[0] if index is None else index.numel()
+        return rows.data_ptr(), (0 if index is None else index.data_ptr()), n, N, M
+
+    def entity_eval(self, rows, actor=None, critic=None, index=None):
+        """`wrsn_entity_eval`: the packed actor and / or critic block on packed entity rows [*, R] (row index[i] for minibatch row i;
+        None: all rows in order).  Returns (mean [n,3], log_std [n,3], value [n]) as new float32 tensors, None for a net that is not given."""
+        t = self.torch
+        self._bind_stream()
+        rp, ip, n, N, M = self._entity_rows(rows, index)
+        new = lambda *sh: t.empty(sh, dtype=t.float32, device=rows.device)
+        mean, log_std = (new(n, 3), new(n, 3)) if actor is not None else (None, None)
+        value = new(n) if critic is not None else None
+        ptr = lambda x: 0 if x is None else x.data_ptr()
+        self._h.entity_eval(ptr(actor), ptr(critic), rp, ip, n, N, M, ptr(mean), ptr(log_std), ptr(value))
+        return mean, log_std, value
+
+    def entity_ppo_grad(self, actor, critic, rows, index, batch, hyper, grad, stats):
+        """`wrsn_entity_ppo_grad`: loss and gradient of one minibatch.  batch: float32 tensors `actions` [*,3], `log_probs`, `advantages`,
+        `returns`, `values`, indexed like the rows; hyper: clip, ent_coef, vf_coef, norm_adv, clip_vloss; grad: ONE contiguous float32
+        tensor [P_actor + P_critic] (overwritten), stats: float32 [8] (loss, pg, v_loss, entropy, approx_kl, clipfrac, 0, 0)."""
+        self._bind_stream()
+        rp, ip, n, N, M = self._entity_rows(rows, index)
+        Pa = self._h.lib.wrsn_entity_actor_floats()
+        self._h.entity_ppo_grad(actor.data_ptr(), critic.data_ptr(), rp, ip, n, N, M, batch["actions"].data_ptr(), batch["log_probs"].data_ptr(),
+                                batch["advantages"].data_ptr(), batch["returns"].data_ptr(), batch["values"].data_ptr(), hyper["clip"],
+                                hyper["ent_coef"], hyper["vf_coef"], hyper["norm_adv"], hyper["clip_vloss"], grad.data_ptr(),
+                                grad.data_ptr() + 4 * Pa, stats.data_ptr())
+
+    def entity_adam(self, param, grad, m, v, step, lr, max_norm, beta1=0.9, beta2=0.999, eps=1e-8, norm_out=None):
+        """`wrsn_entity_adam`: clip_grad_norm_(max_norm) and one Adam step in place on the block `param` with moments m, v."""
+        self._bind_stream()
+        self._h.entity_adam(param.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), param.numel(), step, lr, beta1, beta2, eps, max_norm,
+                            0 if norm_out is None else norm_out.data_ptr())
+
     def synchronize(self):
         self._h.sync()
 
