@@ -42,8 +42,12 @@ def main():
                     "BatchedEntityIPPO(fused_policy=True)) instead of one PyTorch forward pass per charger")
     ap.add_argument("--fused-update", action="store_true", help="with --policy entity: the PPO update runs on the device (wrsn_entity_ppo_grad, "
                     "wrsn_entity_adam, BatchedEntityIPPO(fused_update=True)) instead of PyTorch autograd and torch.optim.Adam")
+    ap.add_argument("--joint-update", action="store_true", help="implies --fused-update: every charger's update goes through the same launches behind "
+                    "one call (wrsn_entity_ppo_update, BatchedEntityIPPO(joint_update=True))")
     ap.add_argument("--report-updates", action="store_true", help="add peak device memory and the statistics of every update (first minibatch included) to the line")
     args = ap.parse_args()
+    if args.joint_update:
+        args.fused_update = True
     if args.fused_policy and args.policy != "entity":
         raise SystemExit("--fused-policy needs --policy entity")
     if args.fused_update and args.policy != "entity":
@@ -73,7 +77,8 @@ def main():
         env = VecWRSN([synth_scenario(rank * B + e, N, N) for e in range(B)], None, M, auto_reset=True, step_budget=args.step_budget, device=str(dev),
                       render=False, entities=True)             # no image at all: 6.6 KB of entity rows per request
         algo = BatchedEntityIPPO(ppo_args, env, capacity=max(2 * args.batch_size, 4096), infer_chunk=args.infer_chunk, min_bucket=args.infer_chunk,
-                                 **({"fused_policy": True} if args.fused_policy else {}), **({"fused_update": True} if args.fused_update else {}))
+                                 **({"fused_policy": True} if args.fused_policy else {}), **({"fused_update": True} if args.fused_update else {}),
+                                 **({"joint_update": True} if args.joint_update else {}))
     else:
         env = VecWRSN([synth_scenario(rank * B + e, N, N) for e in range(B)], None, M, auto_reset=True, step_budget=args.step_budget, device=str(dev),
                       reuse_obs=True, obs_dtype=args.obs_dtype)                             # BatchedIPPO only reads the state tensor (index_select / copies)
@@ -129,7 +134,8 @@ def main():
         out["config"]["workload"] = "%d envs x %d nodes x %d MC, set actor + critic per charger on entity rows, 3-vector actions, batch %d / minibatch %d / %d epochs" % (
             B, N, M, args.batch_size, args.minibatch_size, args.updates)
         out["config"]["policy"] = "float32, entity rows, no image" + (", actions sampled on the device (wrsn_entity_act)" if args.fused_policy else "") + (
-            ", update on the device (wrsn_entity_ppo_grad, wrsn_entity_adam)" if args.fused_update else "")
+            ", update on the device (wrsn_entity_ppo_grad, wrsn_entity_adam)" if args.fused_update else "") + (
+            ", every charger in one call (wrsn_entity_ppo_update)" if args.joint_update else "")
     if args.report_updates:
         out["peak_memory_bytes"] = int(torch.cuda.max_memory_allocated(dev)); out["updates"] = updates
     print(json.dumps(out, default=float), flush=True)

@@ -412,6 +412,58 @@ int wrsn_entity_ppo_grad(wrsn_t *h, const float *actor, const float *critic, con
 int wrsn_entity_adam(wrsn_t *h, float *param, const float *grad, float *m, float *v, int32_t n_floats, int32_t step, float lr, float beta1,
                      float beta2, float eps, float max_norm, float *norm_out);
 
+/* THE UPDATE OF SEVERAL INDEPENDENT LEARNERS AT ONCE.  The chargers of IPPO share nothing: own nets, own Adam state, own batch.  A GROUP is
+ * one (actor, critic) pair with its optimiser state and its data; the three calls below do for G groups (1 <= G <= 8) what the
+ * single-group calls above do for one, in the SAME number of launches however large G is (the group is a dimension of every kernel's
+ * grid), and run the whole of PPOLearner.update behind one call.  All asynchronous on the handle's stream; none needs a scenario.
+ *
+ * wrsn_entity_ppo_grad_multi: wrsn_entity_ppo_grad for every group, six launches.  n, n_node, n_mc are common to the groups.  index: DEVICE
+ * int32 [G][n], group g's minibatch row i is row index[g * n + i] of ITS rows and batch arrays; NULL: rows 0 .. n - 1 for every group.
+ * stats: DEVICE float32 [G][8].  The groups' adam_step and moments are not read (they may be NULL).
+ *
+ * wrsn_entity_adam_multi: wrsn_entity_adam on the 2 G blocks of the groups, two launches: group g's actor (grad_actor, m_actor, v_actor)
+ * and critic (grad_critic, m_critic, v_critic) are stepped at step adam_step + 1, each block clipped by ITS OWN norm (actor and critic
+ * separately, as PPOLearner.update clips them).  The bias corrections are formed in double on the host and rounded once, exactly as
+ * wrsn_entity_adam forms them.  rows and batch are not read.  The caller advances its step counts.
+ *
+ * wrsn_entity_ppo_update: `epochs` x ceil(batch_size / minibatch) steps; a step is wrsn_entity_ppo_grad_multi then wrsn_entity_adam_multi.
+ * index: DEVICE int32 [G][epochs][batch_size] -- the caller's shuffles; minibatch s of epoch e of group g is entries s * minibatch ..
+ * min((s + 1) * minibatch, batch_size) - 1 of index[g][e] (the last one of an epoch may be short).  Step k (counted over epochs and
+ * minibatches, from 0) steps group g at adam_step + 1 + k and writes row stats[g][k] of the DEVICE float32 table stats
+ * [G][epochs * ceil(batch_size / minibatch)][8].  The host loop only enqueues: nothing is read back, nothing synchronises.  The caller
+ * advances its step counts by the number of steps.
+ *
+ * CONTRACT.  After a multi call, group g's blocks, moments, gradient buffers and statistics hold THE BYTES the single-group calls give
+ * on the same inputs in the same order.  They do not depend on G, on the other groups' data or on g's position among the groups.  Two
+ * calls on equal inputs give equal bytes (no float atomics, every sum in a fixed order).
+ *
+ * WRSN_ERR_ARG, with every buffer untouched: every case of the single-group calls, for any group (a required pointer NULL -- of a group:
+ * what the call reads or writes; a block, moment, gradient buffer or rows not 16-byte aligned; n < 1; n_mc outside [1, 8]; n_node < 1;
+ * adam_step < 0); n_groups outside [1, 8]; two groups naming the same block, moment or gradient buffer; minibatch, epochs or batch_size
+ * < 1; norm_adv when any minibatch, the short last one included, has fewer than 2 rows.
+ *
+ * OUT OF SCOPE: capture of the update as a HIP graph (the launches are simply enqueued); a device-side shuffle or generator (the caller
+ * draws the permutations); groups with different n, n_node or n_mc. */
+typedef struct wrsn_entity_group {      /* a HOST struct of DEVICE pointers; blocks, moments and gradient buffers 16-byte aligned */
+    float *actor, *critic;              /* blocks [wrsn_entity_actor_floats()], [wrsn_entity_critic_floats()]: updated in place by Adam */
+    float *m_actor, *v_actor, *m_critic, *v_critic;   /* Adam moments, block layout */
+    float *grad_actor, *grad_critic;    /* caller-owned gradient buffers, block layout: overwritten by the gradient, read by Adam */
+    const float *rows;                  /* [*, R] packed entity rows, 16-byte aligned */
+    wrsn_ppo_batch batch;               /* indexed like the rows */
+    int32_t adam_step;                  /* Adam steps taken before the call */
+} wrsn_entity_group;
+
+typedef struct wrsn_adam_hyper {
+    float lr, beta1, beta2, eps, max_norm;
+} wrsn_adam_hyper;
+
+int wrsn_entity_ppo_grad_multi(wrsn_t *h, const wrsn_entity_group *groups, int32_t n_groups, int32_t n, int32_t n_node, int32_t n_mc,
+                               const int32_t *index, const wrsn_ppo_hyper *hyper, float *stats);
+int wrsn_entity_adam_multi(wrsn_t *h, const wrsn_entity_group *groups, int32_t n_groups, const wrsn_adam_hyper *adam);
+int wrsn_entity_ppo_update(wrsn_t *h, const wrsn_entity_group *groups, int32_t n_groups, int32_t n_node, int32_t n_mc, const int32_t *index,
+                           int32_t batch_size, int32_t minibatch, int32_t epochs, const wrsn_ppo_hyper *hyper, const wrsn_adam_hyper *adam,
+                           float *stats);
+
 /* Copy internal state to HOST memory (parity tests, `net` / `agents` views).  Synchronises. */
 int wrsn_peek(wrsn_t *h, int32_t what, void *dst);
 

@@ -39,7 +39,7 @@ ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max"
 
 # every entry point include/wrsn_hip.h declares
 EXPORTS = ("wrsn_create", "wrsn_destroy", "wrsn_set_stream", "wrsn_set_scenario", "wrsn_set_scenario_seeded", "wrsn_reset", "wrsn_step",
-           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_entity_actor_floats", "wrsn_entity_act", "wrsn_entity_critic_floats", "wrsn_entity_eval", "wrsn_entity_ppo_grad", "wrsn_entity_adam", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
+           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_entity_actor_floats", "wrsn_entity_act", "wrsn_entity_critic_floats", "wrsn_entity_eval", "wrsn_entity_ppo_grad", "wrsn_entity_adam", "wrsn_entity_ppo_grad_multi", "wrsn_entity_adam_multi", "wrsn_entity_ppo_update", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
            "wrsn_clone_envs", "wrsn_pool_set", "wrsn_pool_reset", "wrsn_synth_network",
            "wrsn_last_error",
            "wrsn_version")
@@ -84,6 +84,16 @@ class WrsnPpoBatch(C.Structure):
 
 class WrsnPpoHyper(C.Structure):
     _fields_ = [("clip", C.c_float), ("ent_coef", C.c_float), ("vf_coef", C.c_float), ("norm_adv", C.c_int32), ("clip_vloss", C.c_int32)]
+
+
+class WrsnEntityGroup(C.Structure):
+    """wrsn_entity_group: one (actor, critic) pair with its Adam state, gradient buffers, rows and batch (device addresses)."""
+    _fields_ = [(k, C.c_void_p) for k in ("actor", "critic", "m_actor", "v_actor", "m_critic", "v_critic", "grad_actor", "grad_critic", "rows")] + \
+               [("batch", WrsnPpoBatch), ("adam_step", C.c_int32)]
+
+
+class WrsnAdamHyper(C.Structure):
+    _fields_ = [(k, C.c_float) for k in ("lr", "beta1", "beta2", "eps", "max_norm")]
 
 
 class WrsnTransitionBuffers(C.Structure):
@@ -145,6 +155,13 @@ def bind(lib):
     lib.wrsn_entity_ppo_grad.restype = C.c_int
     lib.wrsn_entity_adam.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, vp]
     lib.wrsn_entity_adam.restype = C.c_int
+    lib.wrsn_entity_ppo_grad_multi.argtypes = [vp, C.POINTER(WrsnEntityGroup), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.POINTER(WrsnPpoHyper), vp]
+    lib.wrsn_entity_ppo_grad_multi.restype = C.c_int
+    lib.wrsn_entity_adam_multi.argtypes = [vp, C.POINTER(WrsnEntityGroup), C.c_int32, C.POINTER(WrsnAdamHyper)]
+    lib.wrsn_entity_adam_multi.restype = C.c_int
+    lib.wrsn_entity_ppo_update.argtypes = [vp, C.POINTER(WrsnEntityGroup), C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32,
+                                           C.POINTER(WrsnPpoHyper), C.POINTER(WrsnAdamHyper), vp]
+    lib.wrsn_entity_ppo_update.restype = C.c_int
     lib.wrsn_set_obs_reuse.argtypes = [vp, C.c_int32]
     lib.wrsn_set_obs_reuse.restype = C.c_int
     lib.wrsn_set_obs_format.argtypes = [vp, C.c_int32]
@@ -372,6 +389,50 @@ class RawHandle:
         check(self.lib, self.lib.wrsn_entity_adam(self._h, C.c_void_p(param or None), C.c_void_p(grad or None), C.c_void_p(m or None),
                                                   C.c_void_p(v or None), int(n_floats), int(step), float(lr), float(beta1), float(beta2), float(eps),
                                                   float(max_norm), C.c_void_p(norm_out or None)))
+
+    @staticmethod
+    def _groups(groups):
+        """A ctypes array of wrsn_entity_group from dicts of device addresses: actor, critic, m_actor, v_actor, m_critic, v_critic,
+        grad_actor, grad_critic, rows, action, logp_old, advantage, ret, value_old (absent or 0: NULL) and adam_step (default 0).  None: NULL."""
+        if groups is None:
+            return None
+        arr = (WrsnEntityGroup * max(1, len(groups)))()
+        for q, g in zip(arr, groups):
+            for k in ("actor", "critic", "m_actor", "v_actor", "m_critic", "v_critic", "grad_actor", "grad_critic", "rows"):
+                setattr(q, k, g.get(k) or None)
+            q.batch = WrsnPpoBatch(*(g.get(k) or None for k in ("action", "logp_old", "advantage", "ret", "value_old")))
+            q.adam_step = int(g.get("adam_step", 0))
+        return arr
+
+    @staticmethod
+    def _hyper(hyper):
+        return None if hyper is None else C.byref(WrsnPpoHyper(float(hyper["clip"]), float(hyper["ent_coef"]), float(hyper["vf_coef"]),
+                                                               1 if hyper["norm_adv"] else 0, 1 if hyper["clip_vloss"] else 0))
+
+    @staticmethod
+    def _adam(adam):
+        return None if adam is None else C.byref(WrsnAdamHyper(float(adam["lr"]), float(adam.get("beta1", 0.9)), float(adam.get("beta2", 0.999)),
+                                                               float(adam.get("eps", 1e-8)), float(adam["max_norm"])))
+
+    def entity_ppo_grad_multi(self, groups, n, n_node, n_mc, index, hyper, stats, n_groups=None):
+        """wrsn_entity_ppo_grad_multi: wrsn_entity_ppo_grad for every group (dicts, see `_groups`) in six launches; index: int32 [G][n] or 0,
+        hyper: dict clip, ent_coef, vf_coef, norm_adv, clip_vloss; stats: float32 [G][8].  n_groups: what the call is told (default len)."""
+        check(self.lib, self.lib.wrsn_entity_ppo_grad_multi(self._h, self._groups(groups), len(groups) if n_groups is None else int(n_groups), int(n),
+                                                            int(n_node), int(n_mc), C.c_void_p(index or None), self._hyper(hyper),
+                                                            C.c_void_p(stats or None)))
+
+    def entity_adam_multi(self, groups, adam, n_groups=None):
+        """wrsn_entity_adam_multi: clip_grad_norm_ and Adam on the 2 G blocks of the groups in two launches, group g at adam_step + 1.
+        adam: dict lr, max_norm and optionally beta1, beta2, eps."""
+        check(self.lib, self.lib.wrsn_entity_adam_multi(self._h, self._groups(groups), len(groups) if n_groups is None else int(n_groups),
+                                                        self._adam(adam)))
+
+    def entity_ppo_update(self, groups, n_node, n_mc, index, batch_size, minibatch, epochs, hyper, adam, stats, n_groups=None):
+        """wrsn_entity_ppo_update: the whole of PPOLearner.update for the groups; index: int32 [G][epochs][batch_size], stats: float32
+        [G][epochs * ceil(batch_size / minibatch)][8].  Only enqueues."""
+        check(self.lib, self.lib.wrsn_entity_ppo_update(self._h, self._groups(groups), len(groups) if n_groups is None else int(n_groups), int(n_node),
+                                                        int(n_mc), C.c_void_p(index or None), int(batch_size), int(minibatch), int(epochs),
+                                                        self._hyper(hyper), self._adam(adam), C.c_void_p(stats or None)))
 
     def set_obs_reuse(self, on):
         check(self.lib, self.lib.wrsn_set_obs_reuse(self._h, 1 if on else 0))

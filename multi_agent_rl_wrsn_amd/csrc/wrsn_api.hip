@@ -1003,8 +1003,10 @@ const char* entity_rows_bad(const wrsn_entity_rows* r) {
     if (r->n_node < 1) return "n_node must be >= 1";
     return nullptr;
 }
-int entity_scratch(wrsn_handle* h, int n, bool grad, WrsnEtScratch* s) {
-    const size_t need = wrsn_et_scratch_floats((size_t)n, grad);
+// group 0's slice of the scratch area for G groups of n rows; group g's lies g * s->chunk floats behind it
+int entity_scratch(wrsn_handle* h, int n, bool grad, int G, WrsnEtScratch* s) {
+    s->chunk = wrsn_et_scratch_floats((size_t)n, grad);
+    const size_t need = (size_t)G * s->chunk;
     if (need > h->et_cap) {
         const int rc = dalloc(h, &h->et_scratch, need);
         if (rc) return rc;
@@ -1021,10 +1023,91 @@ int entity_scratch(wrsn_handle* h, int n, bool grad, WrsnEtScratch* s) {
     }
     return 0;
 }
-void entity_forward(wrsn_handle* h, const WrsnEtRows& rw, const float* actor, const float* critic, const WrsnEtScratch& s, const WrsnEtEvalOut& o) {
-    hipLaunchKernelGGL(wrsn_et_trunk_fwd_kernel, dim3(2 * rw.n), dim3(256), WRSN_ET_T_LDS, h->stream, rw, actor, critic, s);
-    hipLaunchKernelGGL(wrsn_et_head_fwd_kernel, dim3(2 * ((rw.n + WRSN_EP_HEAD_ROWS - 1) / WRSN_EP_HEAD_ROWS)), dim3(256), WRSN_EP_H_LDS, h->stream,
-                       rw.n, actor, critic, s, o);
+void entity_forward(wrsn_handle* h, const WrsnEtGroups& gs, int G, const WrsnEtDims& dm, const WrsnEtScratch& s, const WrsnEtEvalOut& o) {
+    hipLaunchKernelGGL(wrsn_et_trunk_fwd_kernel, dim3(2 * G * dm.n), dim3(256), WRSN_ET_T_LDS, h->stream, gs, dm, s);
+    hipLaunchKernelGGL(wrsn_et_head_fwd_kernel, dim3(2 * G * ((dm.n + WRSN_EP_HEAD_ROWS - 1) / WRSN_EP_HEAD_ROWS)), dim3(256), WRSN_EP_H_LDS, h->stream,
+                       gs, dm.n, s, o);
+}
+// one gradient step of G groups: six launches however large G is.  Arguments are checked by the callers.
+int entity_grad_launch(wrsn_handle* h, const WrsnEtGroups& gs, int G, const WrsnEtDims& dm, const WrsnEtHyper& hp) {
+    WrsnEtScratch s;
+    { const int rc = entity_scratch(h, dm.n, true, G, &s); if (rc) return rc; }
+    WrsnEtEvalOut o; o.mean = nullptr; o.log_std = nullptr; o.value = nullptr;
+    const int n = dm.n;
+    entity_forward(h, gs, G, dm, s, o);
+    hipLaunchKernelGGL(wrsn_et_loss_kernel, dim3(G), dim3(256), 256 * sizeof(double), h->stream, gs, n, hp, s);
+    hipLaunchKernelGGL(wrsn_et_head_bwd_kernel, dim3(2 * G * n), dim3(256), 256 * sizeof(float), h->stream, gs, n, s);
+    hipLaunchKernelGGL(wrsn_et_trunk_bwd_kernel, dim3(2 * G * n), dim3(256), WRSN_ET_B_LDS, h->stream, gs, dm, s);
+    hipLaunchKernelGGL(wrsn_et_reduce_kernel, dim3(2 * G * ((WRSN_EP_FLOATS + 255) / 256)), dim3(256), 0, h->stream, gs, n, s);
+    return 0;
+}
+// entry k of an Adam table: the block, and the bias corrections of `step` formed in double and rounded once
+void entity_adam_block(WrsnEtAdamBlocks* bs, int k, float* p, const float* g, float* m, float* v, float* norm_out, int nf, int step, float lr, float beta1,
+                       float beta2) {
+    const double bc1 = 1.0 - std::pow((double)beta1, (double)step), bc2 = 1.0 - std::pow((double)beta2, (double)step);
+    WrsnEtAdamBlock& b = bs->b[k];
+    b.p = p; b.g = g; b.m = m; b.v = v; b.norm_out = norm_out; b.nf = nf;
+    b.step_size = (float)((double)lr / bc1); b.inv_sqrt_bc2 = (float)(1.0 / std::sqrt(bc2));
+}
+// one Adam step on the nb blocks of the table: two launches.  max_nf: the floats of the largest block
+int entity_adam_launch(wrsn_handle* h, const WrsnEtAdamBlocks& bs, int nb, int max_nf, float beta1, float beta2, float eps, float max_norm) {
+    if (!h->et_norm) { const int rc = dalloc(h, &h->et_norm, (size_t)(2 * WRSN_MAX_MC)); if (rc) return rc; }
+    const int per = (max_nf + 255) / 256;
+    hipLaunchKernelGGL(wrsn_et_norm_kernel, dim3(nb), dim3(256), 256 * sizeof(double), h->stream, bs, h->et_norm);
+    hipLaunchKernelGGL(wrsn_et_adam_kernel, dim3(nb * per), dim3(256), 0, h->stream, bs, per, (const float*)h->et_norm, beta1, beta2,
+                       (float)(1.0 - (double)beta1), (float)(1.0 - (double)beta2), eps, max_norm);
+    return 0;
+}
+WrsnEtHyper entity_hyper(const wrsn_ppo_hyper* hyper) {
+    WrsnEtHyper hp; hp.clip = hyper->clip; hp.ent_coef = hyper->ent_coef; hp.vf_coef = hyper->vf_coef; hp.norm_adv = hyper->norm_adv != 0;
+    hp.clip_vloss = hyper->clip_vloss != 0;
+    return hp;
+}
+// what is wrong with the G groups of a multi call, or nullptr.  batch: the gradient's inputs are needed; moments: Adam's
+const char* entity_groups_bad(const wrsn_entity_group* groups, int G, bool batch, bool moments) {
+    if (G < 1 || G > WRSN_MAX_MC) return "n_groups must be in [1, 8]";
+    if (!groups) return "groups is required";
+    const void* named[WRSN_MAX_MC][8];
+    const int nn = moments ? 8 : 4;
+    for (int g = 0; g < G; ++g) {
+        const wrsn_entity_group& q = groups[g];
+        if (!q.actor || !q.critic || !q.grad_actor || !q.grad_critic) return "every group needs actor, critic, grad_actor and grad_critic";
+        if ((uintptr_t)q.actor % 16 || (uintptr_t)q.critic % 16 || (uintptr_t)q.grad_actor % 16 || (uintptr_t)q.grad_critic % 16)
+            return "blocks and gradient buffers must be 16-byte aligned";
+        if (batch) {
+            if (!q.rows || !q.batch.action || !q.batch.logp_old || !q.batch.advantage || !q.batch.ret || !q.batch.value_old)
+                return "every group needs rows and every batch array";
+            if ((uintptr_t)q.rows % 16) return "rows must be 16-byte aligned";
+        }
+        if (moments) {
+            if (!q.m_actor || !q.v_actor || !q.m_critic || !q.v_critic) return "every group needs m_actor, v_actor, m_critic and v_critic";
+            if ((uintptr_t)q.m_actor % 16 || (uintptr_t)q.v_actor % 16 || (uintptr_t)q.m_critic % 16 || (uintptr_t)q.v_critic % 16)
+                return "moments must be 16-byte aligned";
+            if (q.adam_step < 0) return "adam_step must be >= 0";
+        }
+        const void* mine[8] = {q.actor, q.critic, q.grad_actor, q.grad_critic, q.m_actor, q.v_actor, q.m_critic, q.v_critic};
+        for (int k = 0; k < nn; ++k) {
+            for (int g2 = 0; g2 < g; ++g2)
+                for (int k2 = 0; k2 < nn; ++k2)
+                    if (named[g2][k2] == mine[k]) return "two groups name the same block, moment or gradient buffer";
+            named[g][k] = mine[k];
+        }
+    }
+    return nullptr;
+}
+const char* entity_dims_bad(int n, int n_node, int n_mc) {
+    if (n < 1) return "n must be >= 1";
+    if (n_mc < 1 || n_mc > WRSN_MAX_MC) return "n_mc must be in [1, 8]";
+    if (n_node < 1) return "n_node must be >= 1";
+    return nullptr;
+}
+void entity_adam_table(const wrsn_entity_group* groups, int G, int step_offset, const wrsn_adam_hyper* a, WrsnEtAdamBlocks* bs) {
+    for (int g = 0; g < G; ++g) {
+        const wrsn_entity_group& q = groups[g];
+        const int step = q.adam_step + 1 + step_offset;
+        entity_adam_block(bs, 2 * g, q.actor, q.grad_actor, q.m_actor, q.v_actor, nullptr, WRSN_EP_FLOATS, step, a->lr, a->beta1, a->beta2);
+        entity_adam_block(bs, 2 * g + 1, q.critic, q.grad_critic, q.m_critic, q.v_critic, nullptr, WRSN_EC_FLOATS, step, a->lr, a->beta1, a->beta2);
+    }
 }
 }  // namespace
 
@@ -1037,10 +1120,12 @@ int wrsn_entity_eval(wrsn_t* h, const float* actor, const float* critic, const w
     if ((uintptr_t)actor % 16 || (uintptr_t)critic % 16) return fail(WRSN_ERR_ARG, "wrsn_entity_eval: blocks must be 16-byte aligned");
     WRSN_ON_DEVICE(h);
     WrsnEtScratch s;
-    { const int rc = entity_scratch(h, rows->n, false, &s); if (rc) return rc; }
-    WrsnEtRows rw; rw.rows = rows->rows; rw.index = rows->index; rw.n = rows->n; rw.N = rows->n_node; rw.M = rows->n_mc;
+    { const int rc = entity_scratch(h, rows->n, false, 1, &s); if (rc) return rc; }
+    WrsnEtGroups gs{};
+    gs.g[0].actor = actor; gs.g[0].critic = critic; gs.g[0].rows = rows->rows; gs.g[0].index = rows->index;
+    WrsnEtDims dm; dm.n = rows->n; dm.N = rows->n_node; dm.M = rows->n_mc;
     WrsnEtEvalOut o; o.mean = mean; o.log_std = log_std; o.value = value;
-    entity_forward(h, rw, actor, critic, s, o);
+    entity_forward(h, gs, 1, dm, s, o);
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }
@@ -1056,19 +1141,12 @@ int wrsn_entity_ppo_grad(wrsn_t* h, const float* actor, const float* critic, con
         return fail(WRSN_ERR_ARG, "wrsn_entity_ppo_grad: blocks and gradient buffers must be 16-byte aligned");
     if (hyper->norm_adv && rows->n < 2) return fail(WRSN_ERR_ARG, "wrsn_entity_ppo_grad: norm_adv needs n >= 2");
     WRSN_ON_DEVICE(h);
-    WrsnEtScratch s;
-    { const int rc = entity_scratch(h, rows->n, true, &s); if (rc) return rc; }
-    WrsnEtRows rw; rw.rows = rows->rows; rw.index = rows->index; rw.n = rows->n; rw.N = rows->n_node; rw.M = rows->n_mc;
-    WrsnEtBatch b; b.action = batch->action; b.logp_old = batch->logp_old; b.advantage = batch->advantage; b.ret = batch->ret; b.value_old = batch->value_old;
-    WrsnEtHyper hp; hp.clip = hyper->clip; hp.ent_coef = hyper->ent_coef; hp.vf_coef = hyper->vf_coef; hp.norm_adv = hyper->norm_adv != 0;
-    hp.clip_vloss = hyper->clip_vloss != 0;
-    WrsnEtEvalOut o; o.mean = nullptr; o.log_std = nullptr; o.value = nullptr;
-    const int n = rw.n;
-    entity_forward(h, rw, actor, critic, s, o);
-    hipLaunchKernelGGL(wrsn_et_loss_kernel, dim3(1), dim3(256), 256 * sizeof(double), h->stream, n, rw.index, b, hp, s, stats);
-    hipLaunchKernelGGL(wrsn_et_head_bwd_kernel, dim3(2 * n), dim3(256), 256 * sizeof(float), h->stream, n, actor, critic, s);
-    hipLaunchKernelGGL(wrsn_et_trunk_bwd_kernel, dim3(2 * n), dim3(256), WRSN_ET_B_LDS, h->stream, rw, actor, critic, s);
-    hipLaunchKernelGGL(wrsn_et_reduce_kernel, dim3(2 * ((WRSN_EP_FLOATS + 255) / 256)), dim3(256), 0, h->stream, n, s, grad_actor, grad_critic);
+    WrsnEtGroups gs{};
+    WrsnEtGroup& G = gs.g[0];
+    G.actor = actor; G.critic = critic; G.grad_actor = grad_actor; G.grad_critic = grad_critic; G.rows = rows->rows; G.index = rows->index; G.stats = stats;
+    G.b.action = batch->action; G.b.logp_old = batch->logp_old; G.b.advantage = batch->advantage; G.b.ret = batch->ret; G.b.value_old = batch->value_old;
+    WrsnEtDims dm; dm.n = rows->n; dm.N = rows->n_node; dm.M = rows->n_mc;
+    if (const int rc = entity_grad_launch(h, gs, 1, dm, entity_hyper(hyper))) return rc;
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }
@@ -1081,12 +1159,87 @@ int wrsn_entity_adam(wrsn_t* h, float* param, const float* grad, float* m, float
     if (n_floats < 1) return fail(WRSN_ERR_ARG, "wrsn_entity_adam: n_floats must be >= 1");
     if (step < 1) return fail(WRSN_ERR_ARG, "wrsn_entity_adam: step must be >= 1");
     WRSN_ON_DEVICE(h);
-    if (!h->et_norm) { const int rc = dalloc(h, &h->et_norm, (size_t)4); if (rc) return rc; }
-    const double bc1 = 1.0 - std::pow((double)beta1, (double)step), bc2 = 1.0 - std::pow((double)beta2, (double)step);
-    hipLaunchKernelGGL(wrsn_et_norm_kernel, dim3(1), dim3(256), 256 * sizeof(double), h->stream, grad, (int)n_floats, h->et_norm, norm_out);
-    hipLaunchKernelGGL(wrsn_et_adam_kernel, dim3((n_floats + 255) / 256), dim3(256), 0, h->stream, param, grad, m, v, (int)n_floats,
-                       (const float*)h->et_norm, (float)((double)lr / bc1), (float)(1.0 / std::sqrt(bc2)), beta1, beta2, (float)(1.0 - (double)beta1),
-                       (float)(1.0 - (double)beta2), eps, max_norm);
+    WrsnEtAdamBlocks bs{};
+    entity_adam_block(&bs, 0, param, grad, m, v, norm_out, (int)n_floats, (int)step, lr, beta1, beta2);
+    if (const int rc = entity_adam_launch(h, bs, 1, (int)n_floats, beta1, beta2, eps, max_norm)) return rc;
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+namespace {
+// the device table of the groups for one step: minibatch rows index + g * index_stride (NULL: rows 0 .. n - 1), statistics stats + g * stats_stride
+void entity_group_table(const wrsn_entity_group* groups, int G, const int32_t* index, size_t index_stride, float* stats, size_t stats_stride,
+                        WrsnEtGroups* gs) {
+    for (int g = 0; g < G; ++g) {
+        const wrsn_entity_group& q = groups[g];
+        WrsnEtGroup& d = gs->g[g];
+        d.actor = q.actor; d.critic = q.critic; d.grad_actor = q.grad_actor; d.grad_critic = q.grad_critic; d.rows = q.rows;
+        d.index = index ? index + (size_t)g * index_stride : nullptr;
+        d.b.action = q.batch.action; d.b.logp_old = q.batch.logp_old; d.b.advantage = q.batch.advantage; d.b.ret = q.batch.ret;
+        d.b.value_old = q.batch.value_old;
+        d.stats = stats + (size_t)g * stats_stride;
+    }
+}
+}  // namespace
+
+int wrsn_entity_ppo_grad_multi(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, int32_t n, int32_t n_node, int32_t n_mc,
+                               const int32_t* index, const wrsn_ppo_hyper* hyper, float* stats) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    if (const char* bad = entity_groups_bad(groups, n_groups, true, false)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_ppo_grad_multi: ") + bad);
+    if (const char* bad = entity_dims_bad(n, n_node, n_mc)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_ppo_grad_multi: ") + bad);
+    if (!hyper || !stats) return fail(WRSN_ERR_ARG, "wrsn_entity_ppo_grad_multi needs hyper and stats");
+    if (hyper->norm_adv && n < 2) return fail(WRSN_ERR_ARG, "wrsn_entity_ppo_grad_multi: norm_adv needs n >= 2");
+    WRSN_ON_DEVICE(h);
+    WrsnEtGroups gs{};
+    entity_group_table(groups, n_groups, index, (size_t)n, stats, 8, &gs);
+    WrsnEtDims dm; dm.n = n; dm.N = n_node; dm.M = n_mc;
+    if (const int rc = entity_grad_launch(h, gs, n_groups, dm, entity_hyper(hyper))) return rc;
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+int wrsn_entity_adam_multi(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, const wrsn_adam_hyper* adam) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    if (const char* bad = entity_groups_bad(groups, n_groups, false, true)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_adam_multi: ") + bad);
+    if (!adam) return fail(WRSN_ERR_ARG, "wrsn_entity_adam_multi needs the Adam hyper-parameters");
+    WRSN_ON_DEVICE(h);
+    WrsnEtAdamBlocks bs{};
+    entity_adam_table(groups, n_groups, 0, adam, &bs);
+    if (const int rc = entity_adam_launch(h, bs, 2 * n_groups, WRSN_EP_FLOATS, adam->beta1, adam->beta2, adam->eps, adam->max_norm)) return rc;
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+int wrsn_entity_ppo_update(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, int32_t n_node, int32_t n_mc, const int32_t* index,
+                           int32_t batch_size, int32_t minibatch, int32_t epochs, const wrsn_ppo_hyper* hyper, const wrsn_adam_hyper* adam,
+                           float* stats) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    if (const char* bad = entity_groups_bad(groups, n_groups, true, true)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_ppo_update: ") + bad);
+    if (batch_size < 1 || minibatch < 1 || epochs < 1) return fail(WRSN_ERR_ARG, "wrsn_entity_ppo_update: batch_size, minibatch and epochs must be >= 1");
+    if (const char* bad = entity_dims_bad(batch_size, n_node, n_mc)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_ppo_update: ") + bad);
+    if (!index || !hyper || !adam || !stats) return fail(WRSN_ERR_ARG, "wrsn_entity_ppo_update needs index, hyper, adam and stats");
+    const int per_epoch = (int)(((int64_t)batch_size + minibatch - 1) / minibatch);
+    const int64_t steps64 = (int64_t)per_epoch * epochs;
+    if (steps64 > INT32_MAX) return fail(WRSN_ERR_ARG, "wrsn_entity_ppo_update: too many steps");
+    const int steps = (int)steps64, n_full = minibatch < batch_size ? minibatch : batch_size, n_last = batch_size - (per_epoch - 1) * minibatch;
+    if (hyper->norm_adv && (n_full < 2 || n_last < 2)) return fail(WRSN_ERR_ARG, "wrsn_entity_ppo_update: norm_adv needs every minibatch to hold >= 2 rows");
+    WRSN_ON_DEVICE(h);
+    {   // the scratch area of the largest step, so that no step of the loop allocates
+        WrsnEtScratch s;
+        const int rc = entity_scratch(h, n_full, true, n_groups, &s); if (rc) return rc;
+    }
+    const WrsnEtHyper hp = entity_hyper(hyper);
+    int k = 0;
+    for (int e = 0; e < epochs; ++e)
+        for (int start = 0; start < batch_size; start += minibatch, ++k) {   // only enqueues: nothing is read back, nothing synchronises
+            WrsnEtGroups gs{};
+            entity_group_table(groups, n_groups, index + (size_t)e * batch_size + start, (size_t)epochs * batch_size, stats + (size_t)k * 8, (size_t)steps * 8, &gs);
+            WrsnEtDims dm; dm.n = batch_size - start < minibatch ? batch_size - start : minibatch; dm.N = n_node; dm.M = n_mc;
+            if (const int rc = entity_grad_launch(h, gs, n_groups, dm, hp)) return rc;
+            WrsnEtAdamBlocks bs{};
+            entity_adam_table(groups, n_groups, k, adam, &bs);
+            if (const int rc = entity_adam_launch(h, bs, 2 * n_groups, WRSN_EP_FLOATS, adam->beta1, adam->beta2, adam->eps, adam->max_norm)) return rc;
+        }
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }

@@ -1,15 +1,16 @@
 // wrsn_entity_train.h -- the PPO update of the entity policy on the device (gfx950): wrsn_entity_eval, wrsn_entity_ppo_grad,
-// wrsn_entity_adam of include/wrsn_hip.h.
+// wrsn_entity_adam and their multi-group forms wrsn_entity_ppo_grad_multi, wrsn_entity_adam_multi, wrsn_entity_ppo_update of
+// include/wrsn_hip.h.  Every kernel serves G groups (WrsnEtGroups below) in one launch; the single-group calls are G = 1.
 //
 // One minibatch step of PPOLearner.update for the set networks of build_entity_networks (ippo.py) on packed entity rows
 // (R = 8 N + 12 M + 8 floats, as the transition buffers store them), an actor block (wrsn_entity_act's layout) and a critic block (the same
-// trunk offsets, `value` 128 -> 1 behind head2's bias).  Both nets go through every kernel together: block index = net * (blocks per net).
+// trunk offsets, `value` 128 -> 1 behind head2's bias).  Every group's two nets go through every kernel together: block index = (group * 2 + net) * (blocks per net) + ...
 //   wrsn_et_trunk_fwd_kernel   one 256-thread block per (row, net): the trunk of wrsn_entpol_trunk_kernel restated on a packed row --
 //                              the same MFMA chains, folds, tile and wave order, so the 200 features are its features bit for bit --
 //                              plus the live count and, per pooled unit, the lowest-index node that attains the maximum
 //   wrsn_et_head_fwd_kernel    tiles of <= 32 rows: head1, head2 on the matrix cores as wrsn_entpol_head_kernel, the six (actor) or one
 //                              (critic) last dot products in four chains; keeps head1's and head2's outputs and the raw outputs
-//   wrsn_et_loss_kernel        one block: the loss of PPOLearner.minibatch_loss, its statistics, d loss / d (mean, log_std, value) per row
+//   wrsn_et_loss_kernel        one block per group: the loss of PPOLearner.minibatch_loss, its statistics, d loss / d (mean, log_std, value) per row
 //   wrsn_et_head_bwd_kernel    one block per (row, net): back through the last layers, head2 and head1 on the VALU (a row is a
 //                              128-vector: 42 k multiply-adds) -> d / d features
 //   wrsn_et_trunk_bwd_kernel   one block per (row, net): per 32-node tile h1, h2 recomputed exactly as the forward does, delta2 from the two
@@ -17,7 +18,7 @@
 //                              cores, the charger MLP on the VALU; per-row partial gradients of the trunk to scratch
 //   wrsn_et_reduce_kernel      one thread per float of a gradient block: trunk partials summed over the rows in index order; the weight
 //                              gradients of head1, head2 and the last layers as sums over the rows of (input x delta) in index order
-//   wrsn_et_norm_kernel / wrsn_et_adam_kernel   clip_grad_norm_ and torch.optim.Adam on one block
+//   wrsn_et_norm_kernel / wrsn_et_adam_kernel   clip_grad_norm_ and torch.optim.Adam on up to 16 blocks (WrsnEtAdamBlocks), each clipped by its own norm
 // Orientation of the matrix products: that of wrsn_rollout.h, D[i][j] = sum_k A[k][i] B[k][j] with v_mfma_f32_32x32x2_f32, units in D's rows and
 // nodes in D's columns.  delta2 in accumulator layout is a B operand as it stands (k-pair (u, u + 4)), so delta1 needs no exchange; its A
 // operand is W2 read along its rows.  dW2 and dW1 contract over the NODES, which the accumulators hold in lanes: h1, delta2 (then delta1, x) of a
@@ -43,10 +44,23 @@ static_assert(WRSN_EC_VALUE == 48448 && WRSN_EC_VALUE_B == 48576 && WRSN_EC_FLOA
 #define WRSN_ET_B_LDS (4 * 4096 * 4)                          // bytes: two [32 nodes][64 units] tiles per wave
 #define WRSN_ET_TILE(n_, u_) ((n_) * 64 + ((u_) ^ (n_)))      // [node < 32][unit < 64], bank-swizzled
 
-struct WrsnEtRows { const float* rows; const int32_t* index; int n, N, M; };   // mirrors wrsn_entity_rows
+struct WrsnEtDims { int n, N, M; };                           // rows of the minibatch, nodes and chargers of a row: common to the groups of a call
 struct WrsnEtBatch { const float* action; const float* logp_old; const float* advantage; const float* ret; const float* value_old; };
 struct WrsnEtHyper { float clip, ent_coef, vf_coef; int norm_adv, clip_vloss; };
-// scratch of one call, [2 nets][n rows] each unless stated
+// A GROUP: one (actor, critic) pair with its rows, batch and outputs (wrsn_entity_group of include/wrsn_hip.h; the single-group calls are
+// one group).  The groups of a call reach every kernel as ONE by-value argument: the block index carries the group,
+// (group * 2 + net) * (blocks per net) + ..., and a block picks its entry by that wave-uniform index -- scalar loads from the kernel-argument
+// segment, no vector register, no scratch (profiles/entity_update_joint_kernel_resource_usage.csv).  Group g's slice of the scratch area
+// lies g * `chunk` floats behind group 0's.
+struct WrsnEtGroup {
+    const float* actor; const float* critic; float* grad_actor; float* grad_critic;
+    const float* rows; const int32_t* index; WrsnEtBatch b; float* stats;
+};
+struct WrsnEtGroups { WrsnEtGroup g[WRSN_MAX_MC]; };
+// the blocks of an Adam call: at most an actor and a critic per group
+struct WrsnEtAdamBlock { float* p; const float* g; float* m; float* v; float* norm_out; int nf; float step_size, inv_sqrt_bc2; };
+struct WrsnEtAdamBlocks { WrsnEtAdamBlock b[2 * WRSN_MAX_MC]; };
+// scratch of one group, [2 nets][n rows] each unless stated
 struct WrsnEtScratch {
     float* feat;    // [.][200] head inputs
     float* arg;     // [.][64]  node index (as a float) the max pool of the unit took, -1: none (maximum 0)
@@ -59,7 +73,14 @@ struct WrsnEtScratch {
     float* part;    // [.][WRSN_ET_TRUNK_FLOATS] a row's gradient of the trunk's first four layers
     float* raw;     // [n][8] mean 3, log_std before the clamp 3, value, 0
     float* dout;    // [n][8] d loss / d of those
+    size_t chunk;   // floats from a group's slice to the next group's
 };
+// group g's slice
+WDEV WrsnEtScratch wrsn_et_slice(WrsnEtScratch s, int g) {
+    const size_t o = (size_t)g * s.chunk;
+    s.feat += o; s.arg += o; s.cnt += o; s.z1 += o; s.z2 += o; s.dz1 += o; s.dz2 += o; s.dfeat += o; s.part += o; s.raw += o; s.dout += o;
+    return s;
+}
 
 static inline size_t wrsn_et_scratch_floats(size_t n, bool grad) {   // host
     return 2 * n * (WRSN_ENTPOL_FEAT + 64 + 4 + 128 + 128) + 8 * n + (grad ? 2 * n * (128 + 128 + WRSN_ENTPOL_FEAT + WRSN_ET_TRUNK_FLOATS) + 8 * n : 0);
@@ -104,27 +125,30 @@ WDEV bool wrsn_et_tile_fwd(const float* W, const float* nrow, int N, int tile, i
     return alive;
 }
 
-// which (net, row) a block of the per-row kernels is, and where its packed row lies
-struct WrsnEtWho { int net, i; const float* blk; const float* row; };
-WDEV WrsnEtWho wrsn_et_who(const WrsnEtRows& rw, const float* actor, const float* critic) {
+// which (group, net, row) a block of the per-row kernels is, and where its packed row lies
+struct WrsnEtWho { int grp, net, i; const float* blk; const float* row; };
+WDEV WrsnEtWho wrsn_et_who(const WrsnEtGroups& gs, const WrsnEtDims& dm) {
     WrsnEtWho w;
-    w.net = (int)blockIdx.x / rw.n; w.i = (int)blockIdx.x - w.net * rw.n;
-    w.blk = w.net ? critic : actor;
-    const int src = rw.index ? wrsn_wave_first(rw.index[w.i]) : w.i;
-    w.row = rw.rows + (size_t)src * (size_t)(WRSN_ENT_NODE_F * rw.N + WRSN_ENT_MC_F * rw.M + WRSN_ENT_ENV_F);
+    const int q = (int)blockIdx.x / dm.n;                     // group * 2 + net
+    w.i = (int)blockIdx.x - q * dm.n; w.grp = q >> 1; w.net = q & 1;
+    const WrsnEtGroup& G = gs.g[w.grp];
+    w.blk = w.net ? G.critic : G.actor;
+    const int32_t* index = G.index;
+    const int src = index ? wrsn_wave_first(index[w.i]) : w.i;
+    w.row = G.rows + (size_t)src * (size_t)(WRSN_ENT_NODE_F * dm.N + WRSN_ENT_MC_F * dm.M + WRSN_ENT_ENV_F);
     return w;
 }
 
-__global__ void __launch_bounds__(256) wrsn_et_trunk_fwd_kernel(WrsnEtRows rw, const float* __restrict__ actor, const float* __restrict__ critic,
-                                                                WrsnEtScratch s) {
+__global__ void __launch_bounds__(256) wrsn_et_trunk_fwd_kernel(WrsnEtGroups gs, WrsnEtDims dm, WrsnEtScratch s0) {
     extern __shared__ double smem[];
     float* sW = (float*)smem;
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
-    const WrsnEtWho who = wrsn_et_who(rw, actor, critic);
+    const WrsnEtWho who = wrsn_et_who(gs, dm);
     const float* blk = who.blk;
     if (!blk) return;                                         // block-uniform: this net is not asked for
-    const int N = rw.N, M = rw.M;
-    const size_t base = (size_t)who.net * rw.n + who.i;
+    const WrsnEtScratch s = wrsn_et_slice(s0, who.grp);
+    const int N = dm.N, M = dm.M;
+    const size_t base = (size_t)who.net * dm.n + who.i;
     {
         const auto src = wrsn_global((const WrsnU4*)blk);
         WrsnU4* dst = (WrsnU4*)sW;
@@ -235,16 +259,16 @@ __global__ void __launch_bounds__(256) wrsn_et_trunk_fwd_kernel(WrsnEtRows rw, c
 
 struct WrsnEtEvalOut { float* mean; float* log_std; float* value; };   // any may be null
 
-__global__ void __launch_bounds__(256) wrsn_et_head_fwd_kernel(int n, const float* __restrict__ actor, const float* __restrict__ critic, WrsnEtScratch s,
-                                                               WrsnEtEvalOut out) {
+__global__ void __launch_bounds__(256) wrsn_et_head_fwd_kernel(WrsnEtGroups gs, int n, WrsnEtScratch s0, WrsnEtEvalOut out) {
     extern __shared__ double smem[];
     float* sF = (float*)smem;
     float* sZ = sF + WRSN_EP_H_Z;
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
     const int nt = (n + WRSN_EP_HEAD_ROWS - 1) / WRSN_EP_HEAD_ROWS;
-    const int net = (int)blockIdx.x / nt, first = ((int)blockIdx.x - net * nt) * WRSN_EP_HEAD_ROWS;
-    const float* blk = net ? critic : actor;
+    const int q = (int)blockIdx.x / nt, grp = q >> 1, net = q & 1, first = ((int)blockIdx.x - q * nt) * WRSN_EP_HEAD_ROWS;
+    const float* blk = net ? gs.g[grp].critic : gs.g[grp].actor;
     if (!blk) return;
+    const WrsnEtScratch s = wrsn_et_slice(s0, grp);
     const int rows = n - first < WRSN_EP_HEAD_ROWS ? n - first : WRSN_EP_HEAD_ROWS;
     const size_t base = (size_t)net * n + first;
     for (int i = tid; i < WRSN_EP_HEAD_ROWS * WRSN_ENTPOL_FEAT; i += 256) {   // a column beyond `rows` repeats the last row: computed, not stored
@@ -332,10 +356,13 @@ WDEV double wrsn_et_block_sum(double v, double* s, int tid) {
 }
 
 // PPOLearner.minibatch_loss, statement for statement, and its derivative with respect to the raw outputs.  Thread t takes rows t, t + 256, ...
-__global__ void __launch_bounds__(256) wrsn_et_loss_kernel(int n, const int32_t* __restrict__ index, WrsnEtBatch b, WrsnEtHyper hp, WrsnEtScratch s,
-                                                           float* __restrict__ stats) {
+__global__ void __launch_bounds__(256) wrsn_et_loss_kernel(WrsnEtGroups gs, int n, WrsnEtHyper hp, WrsnEtScratch s0) {
     extern __shared__ double smem[];
-    const int tid = (int)threadIdx.x;
+    const int tid = (int)threadIdx.x, grp = (int)blockIdx.x;  // one block per group
+    const int32_t* index = gs.g[grp].index;
+    const WrsnEtBatch b = gs.g[grp].b;
+    float* stats = gs.g[grp].stats;
+    const WrsnEtScratch s = wrsn_et_slice(s0, grp);
     double mean = 0.0, sd = 1.0;
     if (hp.norm_adv) {
         double a = 0.0;
@@ -402,12 +429,13 @@ __global__ void __launch_bounds__(256) wrsn_et_loss_kernel(int n, const int32_t*
 
 // one block per (row, net): d / d (head2 pre-activation), d / d (head1 pre-activation), d / d features.  Thread k owns unit k and reads
 // row k of the [in, out] weights.
-__global__ void __launch_bounds__(256) wrsn_et_head_bwd_kernel(int n, const float* __restrict__ actor, const float* __restrict__ critic, WrsnEtScratch s) {
+__global__ void __launch_bounds__(256) wrsn_et_head_bwd_kernel(WrsnEtGroups gs, int n, WrsnEtScratch s0) {
     extern __shared__ double smem[];
     float* sD = (float*)smem;
     const int tid = (int)threadIdx.x;
-    const int net = (int)blockIdx.x / n, i = (int)blockIdx.x - net * n;
-    const float* blk = net ? critic : actor;
+    const int q = (int)blockIdx.x / n, grp = q >> 1, net = q & 1, i = (int)blockIdx.x - q * n;
+    const float* blk = net ? gs.g[grp].critic : gs.g[grp].actor;
+    const WrsnEtScratch s = wrsn_et_slice(s0, grp);
     const size_t base = (size_t)net * n + i;
     const float* dout = s.dout + (size_t)i * 8;
     if (tid < 128) {
@@ -446,15 +474,15 @@ __global__ void __launch_bounds__(256) wrsn_et_head_bwd_kernel(int n, const floa
     }
 }
 
-__global__ void __launch_bounds__(256) wrsn_et_trunk_bwd_kernel(WrsnEtRows rw, const float* __restrict__ actor, const float* __restrict__ critic,
-                                                                WrsnEtScratch s) {
+__global__ void __launch_bounds__(256) wrsn_et_trunk_bwd_kernel(WrsnEtGroups gs, WrsnEtDims dm, WrsnEtScratch s0) {
     extern __shared__ double smem[];
     float* sT = (float*)smem;
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
-    const WrsnEtWho who = wrsn_et_who(rw, actor, critic);
+    const WrsnEtWho who = wrsn_et_who(gs, dm);
     const float* blk = who.blk;
-    const int N = rw.N, M = rw.M;
-    const size_t base = (size_t)who.net * rw.n + who.i;
+    const WrsnEtScratch s = wrsn_et_slice(s0, who.grp);
+    const int N = dm.N, M = dm.M;
+    const size_t base = (size_t)who.net * dm.n + who.i;
     float* sA = sT + wave * 4096;                             // h1 of the wave's tile [node][unit], later delta1
     float* sB = sA + 2048;                                    // delta2 [node][unit], later x [node][8]
     const float* df = s.dfeat + base * WRSN_ENTPOL_FEAT;
@@ -618,10 +646,11 @@ __global__ void __launch_bounds__(256) wrsn_et_trunk_bwd_kernel(WrsnEtRows rw, c
 }
 
 // one thread per float of a gradient block; rows in index order
-__global__ void __launch_bounds__(256) wrsn_et_reduce_kernel(int n, WrsnEtScratch s, float* __restrict__ grad_actor, float* __restrict__ grad_critic) {
+__global__ void __launch_bounds__(256) wrsn_et_reduce_kernel(WrsnEtGroups gs, int n, WrsnEtScratch s0) {
     const int nb = (WRSN_EP_FLOATS + 255) / 256;
-    const int net = (int)blockIdx.x / nb, p = ((int)blockIdx.x - net * nb) * 256 + (int)threadIdx.x;
+    const int q = (int)blockIdx.x / nb, grp = q >> 1, net = q & 1, p = ((int)blockIdx.x - q * nb) * 256 + (int)threadIdx.x;
     if (p >= (net ? WRSN_EC_FLOATS : WRSN_EP_FLOATS)) return;
+    const WrsnEtScratch s = wrsn_et_slice(s0, grp);
     const size_t b0 = (size_t)net * n;
     float a = 0.f;
     if (p < WRSN_EP_HEAD1) {
@@ -652,26 +681,30 @@ __global__ void __launch_bounds__(256) wrsn_et_reduce_kernel(int n, WrsnEtScratc
             for (int i = 0; i < n; ++i) a += s.dout[(size_t)i * 8 + 3 + p - WRSN_EP_LSTD_B];
         }
     }
-    (net ? grad_critic : grad_actor)[p] = a;                  // the padding: zero
+    (net ? gs.g[grp].grad_critic : gs.g[grp].grad_actor)[p] = a;   // the padding: zero
 }
 
-// ||g|| of one block, summed by one workgroup in a fixed order
-__global__ void __launch_bounds__(256) wrsn_et_norm_kernel(const float* __restrict__ g, int nf, float* __restrict__ norm, float* __restrict__ norm_out) {
+// ||g|| of a block, summed by one workgroup in a fixed order: workgroup k takes block k of the table
+__global__ void __launch_bounds__(256) wrsn_et_norm_kernel(WrsnEtAdamBlocks bs, float* __restrict__ norm) {
     extern __shared__ double smem[];
-    const int tid = (int)threadIdx.x;
+    const int tid = (int)threadIdx.x, k = (int)blockIdx.x;
+    const float* g = bs.b[k].g;
+    const int nf = bs.b[k].nf;
+    float* norm_out = bs.b[k].norm_out;
     double a = 0.0;
     for (int i = tid; i < nf; i += 256) a += (double)g[i] * (double)g[i];
     const double t = wrsn_et_block_sum(a, smem, tid);
-    if (tid == 0) { const float r = (float)sqrt(t); *norm = r; if (norm_out) *norm_out = r; }
+    if (tid == 0) { const float r = (float)sqrt(t); norm[k] = r; if (norm_out) *norm_out = r; }
 }
 
-// clip_grad_norm_ then torch.optim.Adam (no weight decay, no amsgrad) on one block, in place
-__global__ void __launch_bounds__(256) wrsn_et_adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, int nf,
-                                                           const float* __restrict__ norm, float step_size, float inv_sqrt_bc2, float beta1, float beta2,
+// clip_grad_norm_ then torch.optim.Adam (no weight decay, no amsgrad) on every block of the table, in place: `per` workgroups per block
+__global__ void __launch_bounds__(256) wrsn_et_adam_kernel(WrsnEtAdamBlocks bs, int per, const float* __restrict__ norm, float beta1, float beta2,
                                                            float omb1, float omb2, float eps, float max_norm) {   // omb: 1 - beta, rounded once
-    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
-    if (i >= nf) return;
-    const float scale = fminf(1.f, max_norm / (*norm + 1e-6f));
+    const int k = (int)blockIdx.x / per, i = ((int)blockIdx.x - k * per) * 256 + (int)threadIdx.x;
+    if (i >= bs.b[k].nf) return;
+    float* p = bs.b[k].p; const float* g = bs.b[k].g; float* m = bs.b[k].m; float* v = bs.b[k].v;
+    const float step_size = bs.b[k].step_size, inv_sqrt_bc2 = bs.b[k].inv_sqrt_bc2;
+    const float scale = fminf(1.f, max_norm / (norm[k] + 1e-6f));
     const float gi = g[i] * scale;
     const float mi = beta1 * m[i] + omb1 * gi;
     const float vi = beta2 * v[i] + omb2 * gi * gi;

@@ -611,10 +611,11 @@ class RolloutDriver:
             batches = self.roll_out()
             i_so_far += 1
             t0 = self._sync_time()
+            joint = self.update_all(batches) if getattr(self, "joint_update", False) else None   # every charger's update at once
             for id in range(self.num_agent):
                 lg = self.loggers[id]
                 lg["t_so_far"] += self.batch_size; lg["i_so_far"] += 1
-                st = self.update(id, batches[id])
+                st = joint[id] if joint is not None else self.update(id, batches[id])
                 y_pred, y_true = batches[id]["values"].cpu().numpy(), batches[id]["returns"].cpu().numpy()
                 var_y = np.var(y_true)
                 ev = float("nan") if var_y == 0 else 1 - np.var(y_true - y_pred) / var_y
@@ -864,12 +865,16 @@ class BatchedEntityIPPO(RolloutDriver, EntityPPOLearner):
                    until the update is over; `_values` (hence `cal_rt_adv`) goes through `wrsn_entity_eval`.  The modules stay the source
                    of truth between updates (they are packed at the start of `update` and written back at its end, so checkpoints load
                    and save as ever), but the Adam moments and step counts live in this object in block layout and the torch optimisers
-                   are never stepped.  The mode is fixed at construction.  False (the default): the PyTorch update, no new launch."""
+                   are never stepped.  The mode is fixed at construction.  False (the default): the PyTorch update, no new launch.
+    joint_update : True (needs fused_update) = `train` updates every charger at once through `update_all`: the chargers are independent
+                   learners, so their minibatch steps go through the same launches (`wrsn_entity_ppo_update`; data-parallel: per step
+                   `wrsn_entity_ppo_grad_multi`, one all-reduce, `wrsn_entity_adam_multi`).  Bit for bit what `update` per charger gives
+                   under the same shuffles.  False (the default): nothing new is launched."""
 
     _check_status = True
 
     def __init__(self, args, env, device=None, model_path=None, capacity=None, infer_chunk=1024, process_group=None, log=None, min_bucket=16,
-                 fused_policy=False, fused_update=False):
+                 fused_policy=False, fused_update=False, joint_update=False):
         if not getattr(env, "entities", False):
             raise ValueError("BatchedEntityIPPO needs a VecWRSN with the entity observation (entities=True)")
         super().__init__(args, env.num_agent, device if device is not None else env.device, model_path, infer_chunk, process_group, min_bucket)
@@ -877,12 +882,17 @@ class BatchedEntityIPPO(RolloutDriver, EntityPPOLearner):
         self.fused_policy = bool(fused_policy)
         self._packed = None                                   # packed_actors() of the weights as they are now, or None: rebuilt before use
         self.fused_update = bool(fused_update)
+        self.joint_update = bool(joint_update)
+        if self.joint_update and not self.fused_update:
+            raise ValueError("joint_update=True needs fused_update=True")
+        self._joint_per_step = False                          # tests: the per-step path of `update_all` (the data-parallel one) at world == 1
         self.first_minibatch_stats = [None] * self.num_agent  # fused_update: (loss, pg, v_loss, entropy, approx_kl, clipfrac) of an update's first minibatch
         if self.fused_update:
             torch = self.torch
             self._pa, self._pc = _lib.ENTITY_ACTOR_FLOATS, _lib.ENTITY_CRITIC_FLOATS
             z = lambda n: torch.zeros(n, dtype=torch.float32, device=env.device)
             self._grad = z(self._pa + self._pc)               # ONE tensor: what the data-parallel exchange reduces
+            self._grad_all = None                             # joint_update: the same for every charger, [M, P_actor + P_critic], at first use
             self._adam = [dict(m_a=z(self._pa), v_a=z(self._pa), m_c=z(self._pc), v_c=z(self._pc), step=0) for _ in range(self.num_agent)]
 
     def roll_out(self, max_launches=100000, fresh_episodes=False):
@@ -936,6 +946,70 @@ class BatchedEntityIPPO(RolloutDriver, EntityPPOLearner):
         self.loggers[id]["losses"].extend(float(x) for x in t[:, 0])
         self.first_minibatch_stats[id] = tuple(float(x) for x in t[0, :6])
         return (float(t[-1, 1]), float(t[-1, 2]), float(t[-1, 3]), float(t[-1, 4]), float(np.mean(t[:, 5])))
+
+    def update_all(self, batches, shuffle=np.random.shuffle):
+        """`update(id, batches[id])` for every charger at once (joint_update): the list of the tuples `update` returns.  The shuffles are
+        drawn in the order the per-charger loop draws them (charger 0's epochs, then charger 1's, ...), so under one seed the two paths
+        give the same bytes.  One process: one index upload and one `entity_ppo_update` call.  Data-parallel (or `_joint_per_step`):
+        per minibatch step one `entity_ppo_grad_multi` into one flat [M (P_actor + P_critic)] tensor, one all-reduce of it, one
+        `entity_adam_multi`."""
+        if not self.joint_update:
+            raise ValueError("update_all needs joint_update=True")
+        self._packed = None
+        torch, env = self.torch, self.env
+        dev, M = env.device, self.num_agent
+        f32 = lambda x: x.to(device=dev, dtype=torch.float32).contiguous()
+        epochs, bs, mb = self.n_updates_per_iteration, self.batch_size, self.minibatch_size
+        per_epoch = (bs + mb - 1) // mb
+        steps = epochs * per_epoch
+        if self._grad_all is None:
+            self._grad_all = torch.zeros((M, self._pa + self._pc), dtype=torch.float32, device=dev)   # ONE tensor: what the exchange reduces
+        groups = []
+        for id in range(M):
+            batch, st = batches[id], self._adam[id]
+            b = {"actions": f32(batch["actions"]).reshape(-1, 3), "log_probs": f32(batch["log_probs"]), "advantages": f32(batch["advantages"]),
+                 "returns": f32(batch["returns"]), "values": f32(batch["values"])}
+            groups.append(dict(actor=f32(pack_entity_actor(self.actors[id])), critic=f32(pack_entity_critic(self.critics[id])), grad=self._grad_all[id],
+                               rows=f32(batch["states"]), batch=b, m_a=st["m_a"], v_a=st["v_a"], m_c=st["m_c"], v_c=st["v_c"], step=st["step"]))
+        idx_np = np.empty((M, epochs, bs), dtype=np.int32)
+        for id in range(M):
+            b_inds = np.arange(bs)
+            for e in range(epochs):
+                shuffle(b_inds)
+                idx_np[id, e] = b_inds
+        idx = torch.from_numpy(idx_np).to(dev)                       # the one upload of the update
+        hyper = dict(clip=self.clip, ent_coef=self.ent_coef, vf_coef=self.vf_coef, norm_adv=self.norm_adv, clip_vloss=self.clip_vloss)
+        lr = self.args["lr"]
+        if self.world == 1 and not self._joint_per_step:
+            table = torch.zeros((M, steps, 8), dtype=torch.float32, device=dev)
+            env.entity_ppo_update(groups, idx, mb, hyper, table, lr, self.max_grad_norm)
+            for st in self._adam:
+                st["step"] += steps
+        else:
+            by_step = torch.zeros((steps, M, 8), dtype=torch.float32, device=dev)
+            k, keep = 0, []
+            for e in range(epochs):
+                for start in range(0, bs, mb):
+                    mbi = idx[:, e, start:start + mb].contiguous()
+                    keep.append(mbi)                                  # the launches are asynchronous: alive until the table is read
+                    env.entity_ppo_grad_multi(groups, mbi, hyper, by_step[k])
+                    if self.world > 1:
+                        torch.distributed.all_reduce(self._grad_all, group=self.group)
+                        self._grad_all /= self.world
+                    env.entity_adam_multi(groups, lr, self.max_grad_norm)
+                    for g, st in zip(groups, self._adam):
+                        st["step"] += 1; g["step"] = st["step"]
+                    k += 1
+            table = by_step.permute(1, 0, 2)
+        for id, g in enumerate(groups):
+            unpack_entity_actor(g["actor"], self.actors[id]); unpack_entity_critic(g["critic"], self.critics[id])
+        t = table.cpu().numpy().astype(np.float64)                   # the one read of the update
+        out = []
+        for id in range(M):
+            self.loggers[id]["losses"].extend(float(x) for x in t[id, :, 0])
+            self.first_minibatch_stats[id] = tuple(float(x) for x in t[id, 0, :6])
+            out.append((float(t[id, -1, 1]), float(t[id, -1, 2]), float(t[id, -1, 3]), float(t[id, -1, 4]), float(np.mean(t[id, :, 5]))))
+        return out
 
     def _choose(self, r, ids):
         if not self.fused_policy:

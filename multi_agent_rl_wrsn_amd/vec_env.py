@@ -403,6 +403,62 @@ class VecWRSN:
         self._h.entity_adam(param.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), param.numel(), step, lr, beta1, beta2, eps, max_norm,
                             0 if norm_out is None else norm_out.data_ptr())
 
+    # -- the same for several independent learners at once (wrsn_entity_ppo_grad_multi / wrsn_entity_adam_multi / wrsn_entity_ppo_update)
+    def _entity_groups(self, groups, need_batch):
+        """Raw groups (dicts of addresses) from groups of tensors: `actor`, `critic`, `grad` (ONE contiguous float32 tensor [P_actor +
+        P_critic]), `m_a`, `v_a`, `m_c`, `v_c`, `step`, and with need_batch `rows` [*, R] and `batch` (the tensors `entity_ppo_grad` takes).
+        Returns (raw groups, N, M)."""
+        Pa = self._h.lib.wrsn_entity_actor_floats()
+        raw, N = [], 0
+        for g in groups:
+            q = dict(actor=g["actor"].data_ptr(), critic=g["critic"].data_ptr(), grad_actor=g["grad"].data_ptr(), grad_critic=g["grad"].data_ptr() + 4 * Pa,
+                     adam_step=int(g.get("step", 0)))
+            for k, name in (("m_a", "m_actor"), ("v_a", "v_actor"), ("m_c", "m_critic"), ("v_c", "v_critic")):
+                if g.get(k) is not None:
+                    q[name] = g[k].data_ptr()
+            if need_batch:
+                rp, _, _, n_node, _ = self._entity_rows(g["rows"], None)
+                if N and n_node != N:
+                    raise ValueError("the groups' rows must hold the same number of nodes")
+                N = n_node
+                b = g["batch"]
+                q.update(rows=rp, action=b["actions"].data_ptr(), logp_old=b["log_probs"].data_ptr(), advantage=b["advantages"].data_ptr(),
+                         ret=b["returns"].data_ptr(), value_old=b["values"].data_ptr())
+            raw.append(q)
+        return raw, N, self.num_agent
+
+    def _entity_index(self, index, shape):
+        t = self.torch
+        if not (index.dtype == t.int32 and index.is_contiguous() and tuple(index.shape) == tuple(shape)):
+            raise ValueError("index must be a contiguous int32 tensor %s" % (tuple(shape),))
+        return index.data_ptr()
+
+    def entity_ppo_grad_multi(self, groups, index, hyper, stats):
+        """`wrsn_entity_ppo_grad_multi`: loss and gradient of one minibatch for every group (see `_entity_groups`) in six launches.  index:
+        int32 [G, n] (row index[g, i] of group g's rows) or None: all rows of every group; stats: float32 [G, 8]."""
+        self._bind_stream()
+        raw, N, M = self._entity_groups(groups, True)
+        n = groups[0]["rows"].shape[0] if index is None else index.shape[1]
+        ip = 0 if index is None else self._entity_index(index, (len(groups), n))
+        self._h.entity_ppo_grad_multi(raw, n, N, M, ip, hyper, stats.data_ptr())
+
+    def entity_adam_multi(self, groups, lr, max_norm, beta1=0.9, beta2=0.999, eps=1e-8):
+        """`wrsn_entity_adam_multi`: clip_grad_norm_(max_norm) and one Adam step on both blocks of every group, group g at `step` + 1."""
+        self._bind_stream()
+        raw, _, _ = self._entity_groups(groups, False)
+        self._h.entity_adam_multi(raw, dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, max_norm=max_norm))
+
+    def entity_ppo_update(self, groups, index, minibatch, hyper, stats, lr, max_norm, beta1=0.9, beta2=0.999, eps=1e-8):
+        """`wrsn_entity_ppo_update`: every epoch and minibatch of `PPOLearner.update` for every group behind one call.  index: int32
+        [G, epochs, batch_size], the shuffles; stats: float32 [G, epochs * ceil(batch_size / minibatch), 8].  Only enqueues; the caller
+        advances its step counts by stats.shape[1]."""
+        self._bind_stream()
+        raw, N, M = self._entity_groups(groups, True)
+        ip = self._entity_index(index, (len(groups),) + tuple(index.shape[1:3]))
+        epochs, batch_size = int(index.shape[1]), int(index.shape[2])
+        self._h.entity_ppo_update(raw, N, M, ip, batch_size, minibatch, epochs, hyper,
+                                  dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, max_norm=max_norm), stats.data_ptr())
+
     def synchronize(self):
         self._h.sync()
 
