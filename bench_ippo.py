@@ -44,9 +44,11 @@ def main():
                     "wrsn_entity_adam, BatchedEntityIPPO(fused_update=True)) instead of PyTorch autograd and torch.optim.Adam")
     ap.add_argument("--joint-update", action="store_true", help="implies --fused-update: every charger's update goes through the same launches behind "
                     "one call (wrsn_entity_ppo_update, BatchedEntityIPPO(joint_update=True))")
+    ap.add_argument("--fused-prepare", action="store_true", help="implies --fused-update: values, GAE and the gathers of every charger's batch in one device "
+                    "call (wrsn_entity_prepare, BatchedEntityIPPO(fused_prepare=True)) instead of index_select and cal_rt_adv per charger")
     ap.add_argument("--report-updates", action="store_true", help="add peak device memory and the statistics of every update (first minibatch included) to the line")
     args = ap.parse_args()
-    if args.joint_update:
+    if args.joint_update or args.fused_prepare:
         args.fused_update = True
     if args.fused_policy and args.policy != "entity":
         raise SystemExit("--fused-policy needs --policy entity")
@@ -78,7 +80,7 @@ def main():
                       render=False, entities=True)             # no image at all: 6.6 KB of entity rows per request
         algo = BatchedEntityIPPO(ppo_args, env, capacity=max(2 * args.batch_size, 4096), infer_chunk=args.infer_chunk, min_bucket=args.infer_chunk,
                                  **({"fused_policy": True} if args.fused_policy else {}), **({"fused_update": True} if args.fused_update else {}),
-                                 **({"joint_update": True} if args.joint_update else {}))
+                                 **({"joint_update": True} if args.joint_update else {}), **({"fused_prepare": True} if args.fused_prepare else {}))
     else:
         env = VecWRSN([synth_scenario(rank * B + e, N, N) for e in range(B)], None, M, auto_reset=True, step_budget=args.step_budget, device=str(dev),
                       reuse_obs=True, obs_dtype=args.obs_dtype)                             # BatchedIPPO only reads the state tensor (index_select / copies)
@@ -124,7 +126,7 @@ def main():
            "config": {"workload": "%d envs x %d nodes x %d MC, UNet actor + CNN critic per charger, density-map actions, batch %d / minibatch %d / %d epochs" %
                       (B, N, M, args.batch_size, args.minibatch_size, args.updates), "step_budget": args.step_budget, "obs_dtype": args.obs_dtype,
                       "policy": "float32, channels-last%s" % ("" if not args.inference_dtype else ", %s roll-out inference" % args.inference_dtype)},
-           "per_iteration_s": {"environment": t["env_s"] / it, "policy_inference": t["policy_s"] / it, "rollout_glue": t["glue_s"] / it, "ppo_update": t["train_s"] / it,
+           "per_iteration_s": {"environment": t["env_s"] / it, "policy_inference": t["policy_s"] / it, "rollout_glue": t["glue_s"] / it, "batch_preparation": t["prepare_s"] / it, "ppo_update": t["train_s"] / it,
                                "wall": wall / it},
            "launches_per_iteration": t["launches"] / it, "requests_served": t["requests"], "env_steps": steps,
            "env_steps_per_s_environment_only": steps / max(t["env_s"], 1e-9), "env_steps_per_s_rollout": steps / max(t["env_s"] + t["policy_s"] + t["glue_s"], 1e-9),
@@ -135,7 +137,8 @@ def main():
             B, N, M, args.batch_size, args.minibatch_size, args.updates)
         out["config"]["policy"] = "float32, entity rows, no image" + (", actions sampled on the device (wrsn_entity_act)" if args.fused_policy else "") + (
             ", update on the device (wrsn_entity_ppo_grad, wrsn_entity_adam)" if args.fused_update else "") + (
-            ", every charger in one call (wrsn_entity_ppo_update)" if args.joint_update else "")
+            ", every charger in one call (wrsn_entity_ppo_update)" if args.joint_update else "") + (
+            ", batch prepared on the device (wrsn_entity_prepare)" if args.fused_prepare else "")
     if args.report_updates:
         out["peak_memory_bytes"] = int(torch.cuda.max_memory_allocated(dev)); out["updates"] = updates
     print(json.dumps(out, default=float), flush=True)

@@ -464,6 +464,47 @@ int wrsn_entity_ppo_update(wrsn_t *h, const wrsn_entity_group *groups, int32_t n
                            int32_t batch_size, int32_t minibatch, int32_t epochs, const wrsn_ppo_hyper *hyper, const wrsn_adam_hyper *adam,
                            float *stats);
 
+/* THE PPO BATCH OF SEVERAL LEARNERS, PREPARED ON THE DEVICE: the critic's values of the selected transitions, PPOLearner.cal_rt_adv
+ * (gae=True) over them and the gathers of the batch tensors, for G groups (1 <= G <= 8) in three launches however large G and n are.
+ * Asynchronous on the handle's stream, needs no scenario, reads nothing back.
+ *
+ * For group g and position i let s = index[g * n + i] (index: DEVICE int32 [G][n], repeats allowed; NULL: s = i).
+ *   value[i]      the critic's value of state[s]: THE BYTES wrsn_entity_eval writes for that row and block.  The value of next_state[s]
+ *                 ("next_value") lives in the handle's scratch area only.
+ *   advantage, ret  the reference's recurrence in float32 -- every operation rounded to float32, none contracted into an FMA:
+ *                     g = (float)gamma;  c = (float)((double)gamma * (double)gae_lambda);                  formed on the host
+ *                     last = 0;  for t = n - 1 .. 0:   tm = terminal ? terminal[s_t] : 0
+ *                         delta = (reward[s_t] + (g * next_value[t]) * tm) - value[t];
+ *                         last  = delta + ((c * tm) * last);
+ *                         advantage[t] = last;   ret[t] = advantage[t] + value[t];
+ *                 `terminal` is the reference's FACTOR on the bootstrap term (IPPO.py:71-93), not a done flag.  Non-finite values go
+ *                 through the recurrence as they are (0 * inf is NaN): there is no shortcut on tm == 0.
+ *   out_state[i] = state[s], out_next_state[i] = next_state[s], out_action[i] = action[s], out_logp[i] = logp[s],
+ *   out_reward[i] = reward[s]: plain copies; each output may be NULL (nothing is written for it).
+ *
+ * CONTRACT.  A group's outputs depend on that group's inputs only: not on G, on the other groups' data or on the group's position.  Two
+ * calls on equal inputs give equal bytes.  Nothing outside the stated extents is written.
+ *
+ * WRSN_ERR_ARG, with every buffer untouched (checked before the first launch): h or groups NULL; n_groups outside [1, 8]; n < 1;
+ * n_node < 1; n_mc outside [1, 8]; critic, state, next_state, reward, value, advantage or ret of a group NULL; an output given whose
+ * source is NULL (out_action without action, out_logp without logp); critic, state, next_state, out_state or out_next_state not 16-byte
+ * aligned; two groups naming the same output buffer; gamma or gae_lambda not finite.
+ *
+ * OUT OF SCOPE: the batch selection (the caller's: it uploads the index); groups with different n, n_node or n_mc; the gae=False branch. */
+typedef struct wrsn_prepare_group {      /* a HOST struct of DEVICE pointers */
+    const float *critic;                 /* critic block [wrsn_entity_critic_floats()], 16-byte aligned */
+    const float *state, *next_state;     /* [*, R] packed entity rows, 16-byte aligned (a charger's slice of the transition buffers) */
+    const float *reward;                 /* [*] */
+    const float *terminal;               /* [*] the reference's factor on the bootstrap term, or NULL = all 0 */
+    const float *action, *logp;          /* [*, 3], [*]; each may be NULL, then its output must be NULL */
+    float *value, *advantage, *ret;      /* [n] required outputs, in selection order */
+    float *out_state, *out_next_state;   /* [n, R] gathered rows, 16-byte aligned; each may be NULL */
+    float *out_action, *out_logp, *out_reward;   /* [n, 3], [n], [n]; each may be NULL */
+} wrsn_prepare_group;
+
+int wrsn_entity_prepare(wrsn_t *h, const wrsn_prepare_group *groups, int32_t n_groups, int32_t n, int32_t n_node, int32_t n_mc,
+                        const int32_t *index /* DEVICE [G][n] or NULL = rows 0..n-1 */, float gamma, float gae_lambda);
+
 /* Copy internal state to HOST memory (parity tests, `net` / `agents` views).  Synchronises. */
 int wrsn_peek(wrsn_t *h, int32_t what, void *dst);
 

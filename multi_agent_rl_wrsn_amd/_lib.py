@@ -39,7 +39,7 @@ ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max"
 
 # every entry point include/wrsn_hip.h declares
 EXPORTS = ("wrsn_create", "wrsn_destroy", "wrsn_set_stream", "wrsn_set_scenario", "wrsn_set_scenario_seeded", "wrsn_reset", "wrsn_step",
-           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_entity_actor_floats", "wrsn_entity_act", "wrsn_entity_critic_floats", "wrsn_entity_eval", "wrsn_entity_ppo_grad", "wrsn_entity_adam", "wrsn_entity_ppo_grad_multi", "wrsn_entity_adam_multi", "wrsn_entity_ppo_update", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
+           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_entity_actor_floats", "wrsn_entity_act", "wrsn_entity_critic_floats", "wrsn_entity_eval", "wrsn_entity_ppo_grad", "wrsn_entity_adam", "wrsn_entity_ppo_grad_multi", "wrsn_entity_adam_multi", "wrsn_entity_ppo_update", "wrsn_entity_prepare", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
            "wrsn_clone_envs", "wrsn_pool_set", "wrsn_pool_reset", "wrsn_synth_network",
            "wrsn_last_error",
            "wrsn_version")
@@ -90,6 +90,12 @@ class WrsnEntityGroup(C.Structure):
     """wrsn_entity_group: one (actor, critic) pair with its Adam state, gradient buffers, rows and batch (device addresses)."""
     _fields_ = [(k, C.c_void_p) for k in ("actor", "critic", "m_actor", "v_actor", "m_critic", "v_critic", "grad_actor", "grad_critic", "rows")] + \
                [("batch", WrsnPpoBatch), ("adam_step", C.c_int32)]
+
+
+class WrsnPrepareGroup(C.Structure):
+    """wrsn_prepare_group: one learner's critic block, transition arrays and batch outputs (device addresses)."""
+    _fields_ = [(k, C.c_void_p) for k in ("critic", "state", "next_state", "reward", "terminal", "action", "logp", "value", "advantage", "ret",
+                                          "out_state", "out_next_state", "out_action", "out_logp", "out_reward")]
 
 
 class WrsnAdamHyper(C.Structure):
@@ -162,6 +168,8 @@ def bind(lib):
     lib.wrsn_entity_ppo_update.argtypes = [vp, C.POINTER(WrsnEntityGroup), C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32,
                                            C.POINTER(WrsnPpoHyper), C.POINTER(WrsnAdamHyper), vp]
     lib.wrsn_entity_ppo_update.restype = C.c_int
+    lib.wrsn_entity_prepare.argtypes = [vp, C.POINTER(WrsnPrepareGroup), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_float, C.c_float]
+    lib.wrsn_entity_prepare.restype = C.c_int
     lib.wrsn_set_obs_reuse.argtypes = [vp, C.c_int32]
     lib.wrsn_set_obs_reuse.restype = C.c_int
     lib.wrsn_set_obs_format.argtypes = [vp, C.c_int32]
@@ -433,6 +441,18 @@ class RawHandle:
         check(self.lib, self.lib.wrsn_entity_ppo_update(self._h, self._groups(groups), len(groups) if n_groups is None else int(n_groups), int(n_node),
                                                         int(n_mc), C.c_void_p(index or None), int(batch_size), int(minibatch), int(epochs),
                                                         self._hyper(hyper), self._adam(adam), C.c_void_p(stats or None)))
+
+    def entity_prepare(self, groups, n, n_node, n_mc, index, gamma, gae_lambda, n_groups=None):
+        """wrsn_entity_prepare: values, GAE and gathers of every group's batch in three launches.  groups: dicts of device addresses under
+        the field names of wrsn_prepare_group (absent or 0: NULL), None: NULL; index: int32 [G][n] or 0.  n_groups: what the call is told."""
+        arr = None
+        if groups is not None:
+            arr = (WrsnPrepareGroup * max(1, len(groups)))()
+            for q, g in zip(arr, groups):
+                for k, _ in WrsnPrepareGroup._fields_:
+                    setattr(q, k, g.get(k) or None)
+        check(self.lib, self.lib.wrsn_entity_prepare(self._h, arr, (0 if groups is None else len(groups)) if n_groups is None else int(n_groups), int(n),
+                                                     int(n_node), int(n_mc), C.c_void_p(index or None), float(gamma), float(gae_lambda)))
 
     def set_obs_reuse(self, on):
         check(self.lib, self.lib.wrsn_set_obs_reuse(self._h, 1 if on else 0))

@@ -1244,6 +1244,66 @@ int wrsn_entity_ppo_update(wrsn_t* h, const wrsn_entity_group* groups, int32_t n
     return WRSN_OK;
 }
 
+namespace {
+// what is wrong with the G groups of wrsn_entity_prepare, or nullptr
+const char* prepare_groups_bad(const wrsn_prepare_group* groups, int G) {
+    if (G < 1 || G > WRSN_MAX_MC) return "n_groups must be in [1, 8]";
+    if (!groups) return "groups is required";
+    const void* named[WRSN_MAX_MC * 8];
+    int nn = 0;
+    for (int g = 0; g < G; ++g) {
+        const wrsn_prepare_group& q = groups[g];
+        if (!q.critic || !q.state || !q.next_state || !q.reward || !q.value || !q.advantage || !q.ret)
+            return "every group needs critic, state, next_state, reward, value, advantage and ret";
+        if ((q.out_action && !q.action) || (q.out_logp && !q.logp)) return "an output is given whose source is NULL";
+        if ((uintptr_t)q.critic % 16 || (uintptr_t)q.state % 16 || (uintptr_t)q.next_state % 16 || (uintptr_t)q.out_state % 16 ||
+            (uintptr_t)q.out_next_state % 16)
+            return "the critic block, state, next_state, out_state and out_next_state must be 16-byte aligned";
+        const void* mine[8] = {q.value, q.advantage, q.ret, q.out_state, q.out_next_state, q.out_action, q.out_logp, q.out_reward};
+        for (int k = 0; k < 8; ++k) {
+            if (!mine[k]) continue;
+            for (int k2 = 0; k2 < nn; ++k2)
+                if (named[k2] == mine[k]) return "two groups name the same output buffer";
+            named[nn++] = mine[k];
+        }
+    }
+    return nullptr;
+}
+}  // namespace
+
+int wrsn_entity_prepare(wrsn_t* h, const wrsn_prepare_group* groups, int32_t n_groups, int32_t n, int32_t n_node, int32_t n_mc, const int32_t* index,
+                        float gamma, float gae_lambda) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    if (const char* bad = prepare_groups_bad(groups, n_groups)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_prepare: ") + bad);
+    if (const char* bad = entity_dims_bad(n, n_node, n_mc)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_prepare: ") + bad);
+    if (!std::isfinite(gamma) || !std::isfinite(gae_lambda)) return fail(WRSN_ERR_ARG, "wrsn_entity_prepare: gamma and gae_lambda must be finite");
+    WRSN_ON_DEVICE(h);
+    const int G = n_groups;
+    WrsnEtScratch s;
+    { const int rc = entity_scratch(h, n, false, 2 * G, &s); if (rc) return rc; }
+    WrsnEtGroups gs{};                                        // two row sets per group: its critic on `state` and on `next_state`
+    WrsnEtPrepGroups ps{};
+    for (int g = 0; g < G; ++g) {
+        const wrsn_prepare_group& q = groups[g];
+        for (int k = 0; k < 2; ++k) {
+            WrsnEtGroup& d = gs.g[2 * g + k];
+            d.critic = q.critic; d.rows = k ? q.next_state : q.state; d.index = index ? index + (size_t)g * n : nullptr;
+        }
+        WrsnEtPrepGroup& p = ps.g[g];
+        p.state = q.state; p.next_state = q.next_state; p.reward = q.reward; p.terminal = q.terminal; p.action = q.action; p.logp = q.logp;
+        p.value = q.value; p.advantage = q.advantage; p.ret = q.ret; p.out_state = q.out_state; p.out_next_state = q.out_next_state;
+        p.out_action = q.out_action; p.out_logp = q.out_logp; p.out_reward = q.out_reward;
+    }
+    WrsnEtDims dm; dm.n = n; dm.N = n_node; dm.M = n_mc;
+    WrsnEtEvalOut o; o.mean = nullptr; o.log_std = nullptr; o.value = nullptr;
+    entity_forward(h, gs, 2 * G, dm, s, o);
+    const int row_u4 = (WRSN_ENT_NODE_F * n_node + WRSN_ENT_MC_F * n_mc + WRSN_ENT_ENV_F) / 4;   // R is a multiple of 4 floats
+    hipLaunchKernelGGL(wrsn_et_prepare_kernel, dim3((unsigned)G * ((unsigned)n + 1u)), dim3(256), WRSN_ET_PREP_LDS, h->stream, ps, (int)n, row_u4, index,
+                       gamma, (float)((double)gamma * (double)gae_lambda), s);
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
 int wrsn_sync(wrsn_t* h) {
     if (!h) return fail(WRSN_ERR_ARG, "null handle");
     WRSN_ON_DEVICE(h);

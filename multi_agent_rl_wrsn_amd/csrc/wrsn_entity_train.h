@@ -1,6 +1,7 @@
 // wrsn_entity_train.h -- the PPO update of the entity policy on the device (gfx950): wrsn_entity_eval, wrsn_entity_ppo_grad,
 // wrsn_entity_adam and their multi-group forms wrsn_entity_ppo_grad_multi, wrsn_entity_adam_multi, wrsn_entity_ppo_update of
-// include/wrsn_hip.h.  Every kernel serves G groups (WrsnEtGroups below) in one launch; the single-group calls are G = 1.
+// include/wrsn_hip.h.  Every kernel serves G groups (WrsnEtGroups below) in one launch; the single-group calls are G = 1.  At the end of
+// the file: wrsn_entity_prepare, the batch preparation (values, GAE, gathers) on the same forward kernels.
 //
 // One minibatch step of PPOLearner.update for the set networks of build_entity_networks (ippo.py) on packed entity rows
 // (R = 8 N + 12 M + 8 floats, as the transition buffers store them), an actor block (wrsn_entity_act's layout) and a critic block (the same
@@ -56,7 +57,9 @@ struct WrsnEtGroup {
     const float* actor; const float* critic; float* grad_actor; float* grad_critic;
     const float* rows; const int32_t* index; WrsnEtBatch b; float* stats;
 };
-struct WrsnEtGroups { WrsnEtGroup g[WRSN_MAX_MC]; };
+// 2 * WRSN_MAX_MC entries: the update calls fill at most WRSN_MAX_MC; wrsn_entity_prepare fills two per group (below)
+#define WRSN_ET_MAX_GROUPS (2 * WRSN_MAX_MC)
+struct WrsnEtGroups { WrsnEtGroup g[WRSN_ET_MAX_GROUPS]; };
 // the blocks of an Adam call: at most an actor and a critic per group
 struct WrsnEtAdamBlock { float* p; const float* g; float* m; float* v; float* norm_out; int nf; float step_size, inv_sqrt_bc2; };
 struct WrsnEtAdamBlocks { WrsnEtAdamBlock b[2 * WRSN_MAX_MC]; };
@@ -710,4 +713,102 @@ __global__ void __launch_bounds__(256) wrsn_et_adam_kernel(WrsnEtAdamBlocks bs, 
     const float vi = beta2 * v[i] + omb2 * gi * gi;
     m[i] = mi; v[i] = vi;
     p[i] = p[i] - step_size * (mi / (sqrtf(vi) * inv_sqrt_bc2 + eps));
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// wrsn_entity_prepare: the PPO batch of G groups -- values, PPOLearner.cal_rt_adv (gae=True), gathers -- in three launches.
+//   the two forward kernels above, unchanged, on 2 G ROW SETS: entry 2 g of the group table is (no actor, group g's critic, its `state`
+//       rows), entry 2 g + 1 the same critic on its `next_state` rows, both under group g's index.  An entry without an actor costs a
+//       block that returns at once; the value of row i of an entry is raw[8 i + 6] of the entry's scratch slice -- the float
+//       wrsn_entity_eval writes for that row and block, from the same instructions
+//   wrsn_et_prepare_kernel   1 + n blocks per group, the group in blockIdx.x alone.  Block 0 of a group: delta_t and c tm_t of a chunk of
+//       WRSN_ET_PREP_CHUNK positions formed by the 256 threads into LDS (the small gathers ride along), then ONE lane runs the
+//       dependent chain over the chunk from its end, eight positions' operands loaded ahead of their use; chunks go from the last to the
+//       first and the lane carries `last` across them, so n is unbounded and the order is the reference's.  Block 1 + i of a group:
+//       out_state[i] and out_next_state[i] as 16-byte copies.
+// The recurrence is the reference's float32 statement sequence: every product and sum below is rounded on its own (contraction off).
+#define WRSN_ET_PREP_CHUNK 256
+#define WRSN_ET_PREP_LDS (3 * WRSN_ET_PREP_CHUNK * 4)         // bytes: delta / advantage, c tm, value
+struct WrsnEtPrepGroup {
+    const float* state; const float* next_state; const float* reward; const float* terminal; const float* action; const float* logp;
+    float* value; float* advantage; float* ret; float* out_state; float* out_next_state; float* out_action; float* out_logp; float* out_reward;
+};
+struct WrsnEtPrepGroups { WrsnEtPrepGroup g[WRSN_MAX_MC]; };
+
+// delta = (r + (g nv) tm) - v, and last' = delta + (ctm last): four, then two roundings
+WDEV float wrsn_et_gae_delta(float r, float g, float nv, float tm, float v) {
+#pragma clang fp contract(off)
+    const float a = g * nv;
+    const float b = a * tm;
+    const float c = r + b;
+    return c - v;
+}
+WDEV float wrsn_et_gae_step(float delta, float ctm, float last) {
+#pragma clang fp contract(off)
+    const float a = ctm * last;
+    return delta + a;
+}
+WDEV float wrsn_et_mul(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+WDEV float wrsn_et_add(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
+__global__ void __launch_bounds__(256) wrsn_et_prepare_kernel(WrsnEtPrepGroups ps, int n, int row_u4, const int32_t* __restrict__ index, float g, float c,
+                                                              WrsnEtScratch s0) {
+    extern __shared__ double smem[];
+    const int tid = (int)threadIdx.x;
+    const int grp = (int)blockIdx.x / (n + 1), j = (int)blockIdx.x - grp * (n + 1);
+    const WrsnEtPrepGroup& P = ps.g[grp];
+    const int32_t* idx = index ? index + (size_t)grp * n : nullptr;
+    if (j > 0) {                                              // ---- the rows of position i, 16 bytes per thread and pass
+        const int i = j - 1;
+        const size_t src = (size_t)(idx ? idx[i] : i) * row_u4, dst = (size_t)i * row_u4;
+        const WrsnU4* a = (const WrsnU4*)P.state; const WrsnU4* b = (const WrsnU4*)P.next_state;
+        WrsnU4* oa = (WrsnU4*)P.out_state; WrsnU4* ob = (WrsnU4*)P.out_next_state;
+        for (int k = tid; k < row_u4; k += 256) {
+            if (oa) wrsn_st_u4(wrsn_global(oa + dst + k), wrsn_ld_u4(wrsn_global(a + src + k)));
+            if (ob) wrsn_st_u4(wrsn_global(ob + dst + k), wrsn_ld_u4(wrsn_global(b + src + k)));
+        }
+        return;
+    }
+    float* sD = (float*)smem; float* sC = sD + WRSN_ET_PREP_CHUNK; float* sV = sC + WRSN_ET_PREP_CHUNK;
+    const float* raw_v = wrsn_et_slice(s0, 2 * grp).raw;      // [n][8]: slot 6 is the critic's value of the row
+    const float* raw_nv = wrsn_et_slice(s0, 2 * grp + 1).raw;
+    float last = 0.f;                                         // thread 0's, carried from chunk to chunk
+    for (int hi = n; hi > 0; hi -= WRSN_ET_PREP_CHUNK) {      // block-uniform
+        const int lo = hi > WRSN_ET_PREP_CHUNK ? hi - WRSN_ET_PREP_CHUNK : 0, m = hi - lo;
+        for (int k = tid; k < m; k += 256) {
+            const size_t t = (size_t)(lo + k), s = (size_t)(idx ? idx[t] : (int)t);
+            const float r = P.reward[s], tm = P.terminal ? P.terminal[s] : 0.f;
+            const float v = raw_v[t * 8 + 6], nv = raw_nv[t * 8 + 6];
+            sD[k] = wrsn_et_gae_delta(r, g, nv, tm, v); sC[k] = wrsn_et_mul(c, tm); sV[k] = v;
+            P.value[t] = v;
+            if (P.out_reward) P.out_reward[t] = r;
+            if (P.out_logp) P.out_logp[t] = P.logp[s];
+            if (P.out_action) { P.out_action[t * 3] = P.action[s * 3]; P.out_action[t * 3 + 1] = P.action[s * 3 + 1]; P.out_action[t * 3 + 2] = P.action[s * 3 + 2]; }
+        }
+        __syncthreads();
+        if (tid == 0) {                                       // the dependent chain: t = hi - 1 .. lo
+            int k = m;
+            for (; k >= 8; k -= 8) {
+                float d[8], cf[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) { d[u] = sD[k - 1 - u]; cf[u] = sC[k - 1 - u]; }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) { last = wrsn_et_gae_step(d[u], cf[u], last); sD[k - 1 - u] = last; }
+            }
+            for (; k > 0; --k) { last = wrsn_et_gae_step(sD[k - 1], sC[k - 1], last); sD[k - 1] = last; }
+        }
+        __syncthreads();
+        for (int k = tid; k < m; k += 256) {
+            const size_t t = (size_t)(lo + k);
+            const float a = sD[k];
+            P.advantage[t] = a; P.ret[t] = wrsn_et_add(a, sV[k]);
+        }
+        __syncthreads();                                      // the next chunk overwrites the LDS arrays
+    }
 }

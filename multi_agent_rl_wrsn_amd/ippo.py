@@ -499,7 +499,7 @@ class RolloutDriver:
 
     def _attach(self, env, buffers, log):
         self.env, self.buffers, self.log = env, buffers, log
-        self.timers = {"env_s": 0.0, "policy_s": 0.0, "glue_s": 0.0, "train_s": 0.0, "launches": 0, "requests": 0}
+        self.timers = {"env_s": 0.0, "policy_s": 0.0, "glue_s": 0.0, "prepare_s": 0.0, "train_s": 0.0, "launches": 0, "requests": 0}
         self._req = None
 
     # -- roll-out ----------------------------------------------------------------------------------------------------
@@ -582,10 +582,18 @@ class RolloutDriver:
             self.step_batch()
             if min(self.buffers.counts()) >= self.batch_size:
                 break
+        t0 = self._sync_time()                                 # `prepare_s`: everything from here on -- selection, gathers, values, GAE
         short = [a for a, n in enumerate(self.buffers.stored()) if n < self.batch_size]
         if short:
             raise RuntimeError("roll_out stopped after %d launches with %s transitions per charger, fewer than batch_size %d (buffer capacity %d): "
                                "raise max_launches / capacity or lower batch_size" % (max_launches, self.buffers.stored(), self.batch_size, self.buffers.capacity))
+        out = self._prepare_batches()
+        self.timers["prepare_s"] += self._sync_time() - t0
+        return out
+
+    def _prepare_batches(self):
+        """The tail of `roll_out`: per charger the reference's batch selection, the gathers and `cal_rt_adv`; the list of batch dicts."""
+        torch, env = self.torch, self.env
         out = []
         for a in range(self.num_agent):
             n = self.buffers.stored()[a]
@@ -869,12 +877,18 @@ class BatchedEntityIPPO(RolloutDriver, EntityPPOLearner):
     joint_update : True (needs fused_update) = `train` updates every charger at once through `update_all`: the chargers are independent
                    learners, so their minibatch steps go through the same launches (`wrsn_entity_ppo_update`; data-parallel: per step
                    `wrsn_entity_ppo_grad_multi`, one all-reduce, `wrsn_entity_adam_multi`).  Bit for bit what `update` per charger gives
-                   under the same shuffles.  False (the default): nothing new is launched."""
+                   under the same shuffles.  False (the default): nothing new is launched.
+    fused_prepare: True (needs fused_update: the values must be the HIP critic's for the two paths to agree) = the tail of `roll_out` runs on
+                   the device (`wrsn_entity_prepare`): one host read of the stored rewards, the reference's selection per charger on the
+                   host (the `np.random` stream of the default path), one index upload, the critics packed once, and ONE call that
+                   writes every charger's values, advantages, returns and gathered rows into [M, batch_size, ...] tensors; the batch
+                   dicts hold per-charger views of them, bit for bit what the default path returns.  False (the default): the
+                   per-charger `index_select`s and `cal_rt_adv`, no new launch."""
 
     _check_status = True
 
     def __init__(self, args, env, device=None, model_path=None, capacity=None, infer_chunk=1024, process_group=None, log=None, min_bucket=16,
-                 fused_policy=False, fused_update=False, joint_update=False):
+                 fused_policy=False, fused_update=False, joint_update=False, fused_prepare=False):
         if not getattr(env, "entities", False):
             raise ValueError("BatchedEntityIPPO needs a VecWRSN with the entity observation (entities=True)")
         super().__init__(args, env.num_agent, device if device is not None else env.device, model_path, infer_chunk, process_group, min_bucket)
@@ -885,6 +899,9 @@ class BatchedEntityIPPO(RolloutDriver, EntityPPOLearner):
         self.joint_update = bool(joint_update)
         if self.joint_update and not self.fused_update:
             raise ValueError("joint_update=True needs fused_update=True")
+        self.fused_prepare = bool(fused_prepare)
+        if self.fused_prepare and not self.fused_update:
+            raise ValueError("fused_prepare=True needs fused_update=True")
         self._joint_per_step = False                          # tests: the per-step path of `update_all` (the data-parallel one) at world == 1
         self.first_minibatch_stats = [None] * self.num_agent  # fused_update: (loss, pg, v_loss, entropy, approx_kl, clipfrac) of an update's first minibatch
         if self.fused_update:
@@ -899,6 +916,38 @@ class BatchedEntityIPPO(RolloutDriver, EntityPPOLearner):
         if self.fused_policy:
             self._packed = self.packed_actors()
         return super().roll_out(max_launches, fresh_episodes)
+
+    def _prepare_batches(self):
+        if not self.fused_prepare:
+            return super()._prepare_batches()
+        torch, env, buf = self.torch, self.env, self.buffers
+        dev, M, bs = env.device, self.num_agent, self.batch_size
+        if not self.gae:                                      # the reference's plain branch raises (`cal_rt_adv`): the same, before any launch
+            raise IndexError("index %d is out of bounds for dimension 0 with size %d" % (bs, bs))
+        stored = buf.stored()
+        host = buf.reward[:, :max(stored)].cpu().numpy()      # the one host read
+        idx_np = np.empty((M, bs), dtype=np.int32)
+        for a in range(M):                                    # in charger order: the `np.random` stream of the default path
+            idx_np[a] = select_batch(host[a, :stored[a]], bs)
+        idx = torch.from_numpy(idx_np).to(dev)                # the one upload
+        critics = torch.stack([pack_entity_critic(c) for c in self.critics]).to(device=dev, dtype=torch.float32).contiguous()
+        new = lambda *sh: torch.empty((M, bs) + sh, dtype=torch.float32, device=dev)
+        R = buf.row_elems
+        o = dict(value=new(), advantage=new(), ret=new(), out_state=new(R), out_next_state=new(R), out_action=new(3), out_logp=new(),
+                 out_reward=torch.empty((M, (-bs) % 64 + bs), dtype=torch.float32, device=dev)[:, :bs])    # every charger's rewards start on a 256-byte boundary, as a tensor of their own would
+        groups = []
+        for a in range(M):
+            g = dict(critic=critics[a], state=buf.state[a], next_state=buf.next_state[a], reward=buf.reward[a], action=buf.action[a], logp=buf.logp[a])
+            g.update({k: v[a] for k, v in o.items()})
+            groups.append(g)
+        env.entity_prepare(groups, idx, self.gamma, self.gae_lambda)       # stored terminal flags are all 0: terminal = NULL
+        out = [dict(states=o["out_state"][a], actions=self._stored_actions(o["out_action"][a]), log_probs=o["out_logp"][a], rewards=o["out_reward"][a],
+                    next_states=o["out_next_state"][a], advantages=o["advantage"][a], returns=o["ret"][a], values=o["value"][a]) for a in range(M)]
+        # the logged mean is torch's float32 reduction of the gathered rewards -- the default path's `float(rew.mean())` on the same floats
+        means = torch.stack([b["rewards"].mean() for b in out]).cpu()
+        for a in range(M):
+            self.loggers[a]["rewards"].append(float(means[a]))
+        return out
 
     def update(self, id, batch, shuffle=np.random.shuffle):
         self._packed = None                                   # the weights change: never carried across an update

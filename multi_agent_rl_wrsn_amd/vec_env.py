@@ -459,6 +459,33 @@ class VecWRSN:
         self._h.entity_ppo_update(raw, N, M, ip, batch_size, minibatch, epochs, hyper,
                                   dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, max_norm=max_norm), stats.data_ptr())
 
+    def entity_prepare(self, groups, index, gamma, gae_lambda):
+        """`wrsn_entity_prepare`: the PPO batch of every group -- the critic's values, `PPOLearner.cal_rt_adv` (gae=True) and the gathers --
+        in three launches.  groups: dicts of contiguous float32 tensors under the field names of `wrsn_prepare_group`: `critic`, `state` and
+        `next_state` [*, R], `reward` [*], `value`, `advantage`, `ret` [n]; optional (absent or None: NULL) `terminal` [*], `action` [*, 3],
+        `logp` [*], `out_state`, `out_next_state` [n, R], `out_action` [n, 3], `out_logp`, `out_reward` [n].  index: int32 [G, n] (position i
+        of group g takes row index[g, i] of ITS arrays) or None: rows 0 .. n - 1 (n = the length of `value`).  Only enqueues."""
+        t = self.torch
+        self._bind_stream()
+        n = int(groups[0]["value"].numel()) if index is None else int(index.shape[1])
+        ip = 0 if index is None else self._entity_index(index, (len(groups), n))
+        raw, N = [], 0
+        for g in groups:
+            for k in ("state", "next_state"):
+                _, _, _, n_node, _ = self._entity_rows(g[k], None)
+                if N and n_node != N:
+                    raise ValueError("the groups' rows must hold the same number of nodes")
+                N = n_node
+            q = {}
+            for k, v in g.items():
+                if v is None:
+                    continue
+                if not (v.dtype == t.float32 and v.is_contiguous()):
+                    raise ValueError("%s must be a contiguous float32 tensor" % k)
+                q[k] = v.data_ptr()
+            raw.append(q)
+        self._h.entity_prepare(raw, n, N, self.num_agent, ip, gamma, gae_lambda)
+
     def synchronize(self):
         self._h.sync()
 
