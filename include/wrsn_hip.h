@@ -350,6 +350,71 @@ typedef struct wrsn_entity_act_out {    /* DEVICE, caller-owned; written only fo
 int wrsn_entity_act(wrsn_t *h, const float *actors, const int32_t *agent_id, const float *eps, const wrsn_entity_out *ent,
                     const wrsn_entity_act_out *out);
 
+/* A HEURISTIC BASELINE ON THE ENTITY ROWS: "go to the most critical node nobody else is serving".  Deterministic, no parameters but
+ * charge_scale; the answer to "better than what?" for a learned entity policy.  For row e with a = agent_id[e] in [0, n_mc), everything
+ * in float32, every operation rounded on its own (no contraction into an FMA):
+ *   self     the lowest-index charger row whose slot 3 (is_self) equals 1; row a when there is none;
+ *   alive    a node whose slot 7 equals 1 -- a select: NaN or inf in a dead or padded node row vanish;
+ *   claimed  a node (u, v) for which some charger o != self with slot 4 (alive) == 1 has
+ *                dx = (u - mc[o][6]) / env[0],  dy = (v - mc[o][7]) / env[1],  dx * dx + dy * dy <= 1
+ *            (the node lies inside the charging disc around that charger's destination; a NaN compares false: not claimed);
+ *   pick     among the alive, unclaimed nodes the one with the largest score, the lowest index among equal scores; the score is slot 2
+ *            (w_n, the weight of map 1), with anything that is not > -inf (a NaN, -inf) counted as -inf: a NaN never beats a number.
+ *            When every alive node is claimed, the same rule over all alive nodes;
+ *   action   (u_n, v_n, c) with t = charge_scale * (1 - node[n][3]), c = t > 0 ? (t < 1 ? t : 1) : 0 (selects: a NaN gives 0);
+ *            (mc[self][0], mc[self][1], 0) when no node is alive.
+ * Node slots 0, 1 and charger slots 0, 1, 6, 7 are positions in the frame wrsn_step maps an action's first two components back from
+ * (WRSN.py:95-98), so (u_n, v_n) is the action that sends the charger to node n.  action_f64 holds the same values widened, as
+ * wrsn_step takes them.  Rows with agent_id outside [0, n_mc) are skipped: every output byte is kept.  A row's output depends on its
+ * own entity rows only; two calls on equal inputs give equal bytes.  `ent` NULL: the registered buffers.  Needs no scenario.
+ * WRSN_ERR_ARG, with every buffer untouched: h, agent_id or action NULL; ent == NULL and nothing registered; node, mc or env NULL or
+ * not 16-byte aligned.  Asynchronous on the handle's stream. */
+int wrsn_entity_heuristic_act(wrsn_t *h, const int32_t *agent_id, const wrsn_entity_out *ent, float charge_scale, float *action,
+                              double *action_f64);
+
+/* EPISODE LEDGER: whole episodes, per environment, on the device.  wrsn_rollout_table sums over whatever ran; this keeps one entry per
+ * finished episode -- lifetime (env.now of the closing return), return and decisions per charger, why it ended, the pool record it ran
+ * in -- and tells the caller which rows to restart.  All arrays are caller-owned DEVICE memory; the library keeps no episode state.
+ * Call it after every call that wrote `out` (wrsn_step, wrsn_reset, wrsn_pool_reset).  Per row, keyed on what the last environment
+ * launch did with it (the row states wrsn_rollout_collect goes by):
+ *   untouched / already consumed   nothing is accumulated, next_agent_id[e] keeps its bytes;
+ *   step in flight (status 4)      next_agent_id[e] = -1;
+ *   reset, auto-reset, pool swap   an episode starts: the running sums of the row are zeroed; next_agent_id[e] = out->agent_id[e];
+ *   fresh request                  with a = out->agent_id[e] in [0, n_mc): run_return[e, a] += out->reward[e] (float64, one add) and
+ *                                  run_decisions[e, a] += 1.  Then the episode CLOSES with ended = 3 when out->status[e] == 1, else with
+ *                                  ended = 2 when time_limit > 0 and out->now[e] >= time_limit; otherwise next_agent_id[e] = a;
+ *   terminal return                the episode closes with ended = 1.
+ * Closing, with k = finished[e]: k < episodes stores lifetime[k, e] = out->now[e], ep_return[k, e, :], decisions[k, e, :], ended[k, e]
+ * and record[k, e]; otherwise dropped[e] += 1.  Then finished[e] = k + 1, the running sums are zeroed, next_agent_id[e] = -2 (the next
+ * wrsn_step leaves the row alone) and restart[e] = 1 -- unless quota > 0 and k + 1 >= quota: the row is PARKED, restart[e] = 0.
+ * restart[e] is written for every row at every call (0 unless this call closed an episode of a row it did not park): it is the mask
+ * for wrsn_reset / wrsn_pool_reset.  A parked row (quota > 0 and finished[e] >= quota at entry) accumulates nothing and gets
+ * next_agent_id[e] = -2 at every call, whatever the launch did with it.  An episode that outlives max_time never reports terminal
+ * (Network.py:79) and would return at the same instant forever: time_limit closes it.
+ * consume != 0: rows with a fresh request, a reset or a terminal return are marked consumed afterwards (a second call after the same
+ * launch finds nothing, and so does wrsn_rollout_collect*); consume == 0: they are left, so a training roll-out runs the ledger FIRST
+ * and wrsn_rollout_collect_entities SECOND.
+ * One thread per environment, no atomics, nothing written outside the stated extents; two calls on equal inputs give equal bytes.
+ * Needs no scenario.  next_agent_id and restart may each be NULL; record may be NULL.
+ * WRSN_ERR_ARG, with every buffer untouched: h, log or out NULL; run_return, run_decisions, finished, dropped, lifetime, ep_return,
+ * decisions or ended NULL; out->agent_id, reward, now or status NULL; episodes < 1; quota < 0 or quota > episodes;
+ * next_agent_id == out->agent_id.  Asynchronous on the handle's stream. */
+typedef struct wrsn_episode_log {      /* DEVICE, caller-owned */
+    int32_t episodes;                  /* E >= 1: finished episodes stored per environment */
+    int32_t quota;                     /* 0: never park; 1..E: an environment is parked once it has finished `quota` episodes */
+    double  *run_return;               /* [B, M] sum of rewards per charger in the running episode */
+    int32_t *run_decisions;            /* [B, M] requests that asked charger m in the running episode */
+    int32_t *finished;                 /* [B]    episodes closed since the caller zeroed the log */
+    int32_t *dropped;                  /* [B]    of those, the ones with index >= E: counted, not stored */
+    double  *lifetime;                 /* [E, B] env.now of the closing return; episode k of environment e at [k, e] */
+    double  *ep_return;                /* [E, B, M] */
+    int32_t *decisions;                /* [E, B, M] */
+    int32_t *ended;                    /* [E, B] 1 terminal return, 2 time limit, 3 fell off the end (status 1) */
+    int32_t *record;                   /* [E, B] pool record the episode ran in (WRSN_PEEK_POOL[., 0]); may be NULL */
+} wrsn_episode_log;
+int wrsn_episodes_collect(wrsn_t *h, const wrsn_episode_log *log, const wrsn_step_out *out, double time_limit,
+                          int32_t *next_agent_id, uint8_t *restart, int32_t consume);
+
 /* THE PPO UPDATE OF THE ENTITY POLICY.  One minibatch step of PPOLearner.update (ippo.py) for the set networks of build_entity_networks:
  * forward, PPO loss, backward, gradient clipping and Adam as a handful of launches on the handle's stream, nothing read back on the host.
  * None of the three calls needs a scenario: the handle supplies the stream and a scratch area that grows on demand and is freed by

@@ -39,7 +39,7 @@ ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max"
 
 # every entry point include/wrsn_hip.h declares
 EXPORTS = ("wrsn_create", "wrsn_destroy", "wrsn_set_stream", "wrsn_set_scenario", "wrsn_set_scenario_seeded", "wrsn_reset", "wrsn_step",
-           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_entity_actor_floats", "wrsn_entity_act", "wrsn_entity_critic_floats", "wrsn_entity_eval", "wrsn_entity_ppo_grad", "wrsn_entity_adam", "wrsn_entity_ppo_grad_multi", "wrsn_entity_adam_multi", "wrsn_entity_ppo_update", "wrsn_entity_prepare", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
+           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_entity_actor_floats", "wrsn_entity_act", "wrsn_entity_heuristic_act", "wrsn_episodes_collect", "wrsn_entity_critic_floats", "wrsn_entity_eval", "wrsn_entity_ppo_grad", "wrsn_entity_adam", "wrsn_entity_ppo_grad_multi", "wrsn_entity_adam_multi", "wrsn_entity_ppo_update", "wrsn_entity_prepare", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
            "wrsn_clone_envs", "wrsn_pool_set", "wrsn_pool_reset", "wrsn_synth_network",
            "wrsn_last_error",
            "wrsn_version")
@@ -72,6 +72,15 @@ class WrsnEntityOut(C.Structure):
 
 class WrsnEntityActOut(C.Structure):
     _fields_ = [("action", C.c_void_p), ("action_f64", C.c_void_p), ("logp", C.c_void_p), ("mean", C.c_void_p), ("log_std", C.c_void_p)]
+
+
+EPISODE_LOG_ARRAYS = ("run_return", "run_decisions", "finished", "dropped", "lifetime", "ep_return", "decisions", "ended", "record")
+ENDED_TERMINAL, ENDED_TIME_LIMIT, ENDED_FELL_OFF = 1, 2, 3     # wrsn_episode_log.ended
+
+
+class WrsnEpisodeLog(C.Structure):
+    """wrsn_episode_log: the episode ledger of wrsn_episodes_collect (device addresses)."""
+    _fields_ = [("episodes", C.c_int32), ("quota", C.c_int32)] + [(k, C.c_void_p) for k in EPISODE_LOG_ARRAYS]
 
 
 class WrsnEntityRows(C.Structure):
@@ -153,6 +162,10 @@ def bind(lib):
     lib.wrsn_entity_actor_floats.restype = C.c_int32
     lib.wrsn_entity_act.argtypes = [vp, vp, vp, vp, C.POINTER(WrsnEntityOut), C.POINTER(WrsnEntityActOut)]
     lib.wrsn_entity_act.restype = C.c_int
+    lib.wrsn_entity_heuristic_act.argtypes = [vp, vp, C.POINTER(WrsnEntityOut), C.c_float, vp, vp]
+    lib.wrsn_entity_heuristic_act.restype = C.c_int
+    lib.wrsn_episodes_collect.argtypes = [vp, C.POINTER(WrsnEpisodeLog), C.POINTER(WrsnStepOut), C.c_double, vp, vp, C.c_int32]
+    lib.wrsn_episodes_collect.restype = C.c_int
     lib.wrsn_entity_critic_floats.argtypes = []
     lib.wrsn_entity_critic_floats.restype = C.c_int32
     lib.wrsn_entity_eval.argtypes = [vp, vp, vp, C.POINTER(WrsnEntityRows), vp, vp, vp]
@@ -370,6 +383,18 @@ class RawHandle:
         o = WrsnEntityActOut(action or None, action_f64 or None, logp or None, mean or None, log_std or None)
         check(self.lib, self.lib.wrsn_entity_act(self._h, C.c_void_p(actors_ptr or None), C.c_void_p(agent_ptr or None), C.c_void_p(eps_ptr or None),
                                                  self._ent(ent_ptrs), C.byref(o)))
+
+    def entity_heuristic_act(self, agent_ptr, ent_ptrs=None, charge_scale=1.0, action=0, action_f64=0):
+        """wrsn_entity_heuristic_act: the most critical unclaimed node of every row whose charger at agent_ptr is in [0, M), from the
+        entity rows of ent_ptrs ((node, mc, env) addresses, None = the registered buffers), into action [B,3] float32 / action_f64."""
+        check(self.lib, self.lib.wrsn_entity_heuristic_act(self._h, C.c_void_p(agent_ptr or None), self._ent(ent_ptrs), float(charge_scale),
+                                                           C.c_void_p(action or None), C.c_void_p(action_f64 or None)))
+
+    def episodes_collect(self, log, time_limit=0.0, next_agent_ptr=0, restart_ptr=0, consume=True, **out_ptrs):
+        """wrsn_episodes_collect: `log` is a WrsnEpisodeLog (None: NULL); out_ptrs the request rows the last environment call wrote."""
+        o = self._out(**out_ptrs)
+        check(self.lib, self.lib.wrsn_episodes_collect(self._h, None if log is None else C.byref(log), C.byref(o), float(time_limit),
+                                                       C.c_void_p(next_agent_ptr or None), C.c_void_p(restart_ptr or None), 1 if consume else 0))
 
     @staticmethod
     def _rows(rows_ptr, index_ptr, n, n_node, n_mc):

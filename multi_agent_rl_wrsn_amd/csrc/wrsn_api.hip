@@ -991,6 +991,41 @@ int wrsn_entity_act(wrsn_t* h, const float* actors, const int32_t* agent_id, con
     return WRSN_OK;
 }
 
+int wrsn_entity_heuristic_act(wrsn_t* h, const int32_t* agent_id, const wrsn_entity_out* ent, float charge_scale, float* action, double* action_f64) {
+    if (!h || !agent_id || !action) return fail(WRSN_ERR_ARG, "wrsn_entity_heuristic_act needs agent_id and action");
+    WrsnEntityOut e{};
+    { const int rc = entity_in(h, ent, &e); if (rc) return rc; }
+    WRSN_ON_DEVICE(h);
+    const int B = h->dev.B;
+    hipLaunchKernelGGL(wrsn_entity_heuristic_kernel, entity_row_grid(B), dim3(64 * WRSN_ENT_ROWS), 0, h->stream, B, h->dev.M, h->dev.N, agent_id, e,
+                       charge_scale, action, action_f64);
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+int wrsn_episodes_collect(wrsn_t* h, const wrsn_episode_log* log, const wrsn_step_out* out, double time_limit, int32_t* next_agent_id,
+                          uint8_t* restart, int32_t consume) {
+    if (!h || !log || !out) return fail(WRSN_ERR_ARG, "null argument");
+    if (!log->run_return || !log->run_decisions || !log->finished || !log->dropped || !log->lifetime || !log->ep_return || !log->decisions || !log->ended)
+        return fail(WRSN_ERR_ARG, "wrsn_episode_log: every array but record is required");
+    if (!out->agent_id || !out->reward || !out->now || !out->status)
+        return fail(WRSN_ERR_ARG, "wrsn_episodes_collect needs agent_id, reward, now and status of wrsn_step_out");
+    if (log->episodes < 1) return fail(WRSN_ERR_ARG, "wrsn_episode_log: episodes must be at least 1");
+    if (log->quota < 0 || log->quota > log->episodes) return fail(WRSN_ERR_ARG, "wrsn_episode_log: quota must lie in [0, episodes]");
+    if (next_agent_id == out->agent_id) return fail(WRSN_ERR_ARG, "wrsn_episodes_collect: next_agent_id must not be out->agent_id");
+    WrsnEpisodeLog L;
+    L.episodes = log->episodes; L.quota = log->quota; L.run_return = log->run_return; L.run_decisions = log->run_decisions;
+    L.finished = log->finished; L.dropped = log->dropped; L.lifetime = log->lifetime; L.ep_return = log->ep_return;
+    L.decisions = log->decisions; L.ended = log->ended; L.record = log->record;
+    WRSN_ON_DEVICE(h);
+    const int B = h->dev.B;
+    hipLaunchKernelGGL(wrsn_episodes_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, B, h->dev.M, L, (const int32_t*)out->agent_id,
+                       (const double*)out->reward, (const double*)out->now, (const int32_t*)out->status, h->dev.row_state,
+                       (const int32_t*)h->d_pool_cur, time_limit, next_agent_id, restart, (int)(consume != 0));
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
 // ------------------------------------------------------------------ the PPO update of the entity policy (wrsn_entity_train.h)
 int32_t wrsn_entity_critic_floats(void) { return WRSN_EC_FLOATS; }
 

@@ -573,3 +573,135 @@ __global__ void __launch_bounds__(256) wrsn_entpol_head_kernel(int B, int M, con
         out.logp[e] = lp - 2.7568156f;                        // 1.5 log(2 pi)
     }
 }
+
+// ------------------------------------------------------------------ heuristic baseline on the entity rows (wrsn_entity_heuristic_act)
+// "The most critical node nobody else is serving" (include/wrsn_hip.h has the rule, statement for statement): a wave per row,
+// WRSN_ENT_ROWS rows per block like the entity bookkeeping kernels, no LDS and no __syncthreads.  The chargers (at most eight) are read
+// by every lane with wave-uniform addresses; lane l takes nodes l, l + 64, ... as two 16-byte loads each, with clamped indices, and
+// keeps two candidates -- the best alive node, the best alive node that is not claimed -- as (score, index) pairs under `>`, so the
+// lowest index of a lane wins a tie.  Both candidates are then reduced by every wave, whether or not the fallback is needed (no
+// wave-divergent reduction): the maximum of the score, then the minimum of the index among the lanes that hold the maximum.  Maximum
+// and minimum are exact, so the order of the reduction does not enter the result; it is a __shfl_xor butterfly, not the DPP chain of
+// wrsn_sim.h, because the emulator of tests/emu models DPP rows for one-wave blocks only and this block holds four waves.
+// float32 throughout, contraction off where a product feeds a sum.
+#define WRSN_EH_NONE 0x7fffffff                               // index of "no candidate"
+
+WDEV bool wrsn_eh_claims(float u, float v, float cx, float cy, float hx, float hy) {
+#pragma clang fp contract(off)
+    const float dx = (u - cx) / hx, dy = (v - cy) / hy;
+    const float a = dx * dx, b = dy * dy;
+    return a + b <= 1.f;                                      // a NaN compares false
+}
+WDEV float wrsn_eh_charge(float charge_scale, float level) {
+#pragma clang fp contract(off)
+    const float r = 1.f - level;
+    const float t = charge_scale * r;
+    return t > 0.f ? (t < 1.f ? t : 1.f) : 0.f;               // selects: a NaN gives 0
+}
+// (score, index) of the wave's best candidate in every lane: lanes without a candidate hold (-inf, WRSN_EH_NONE)
+WDEV int wrsn_eh_wave_best(float s, int i) {
+    float m = s;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const float o = __shfl_xor(m, d); m = o > m ? o : m; }
+    int k = (s == m) ? i : WRSN_EH_NONE;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_xor(k, d); k = o < k ? o : k; }
+    return k;
+}
+
+__global__ void __launch_bounds__(64 * WRSN_ENT_ROWS) wrsn_entity_heuristic_kernel(int B, int M, int N, const int32_t* __restrict__ agent_id, WrsnEntityOut ent,
+                                                                                    float charge_scale, float* __restrict__ action,
+                                                                                    double* __restrict__ action_f64) {
+    const int lane = (int)threadIdx.x & 63;
+    const int e = (int)blockIdx.x * WRSN_ENT_ROWS + ((int)threadIdx.x >> 6);
+    if (e >= B) return;
+    const int a = wrsn_wave_first(agent_id[e]);
+    if (a < 0 || a >= M) return;
+    const float* mc = ent.mc + (size_t)e * M * WRSN_ENT_MC_F;
+    const float hx = ent.env[(size_t)e * WRSN_ENT_ENV_F], hy = ent.env[(size_t)e * WRSN_ENT_ENV_F + 1];
+    int self = a;
+    for (int o = M - 1; o >= 0; --o) if (mc[o * WRSN_ENT_MC_F + 3] == 1.f) self = o;
+    float cx[WRSN_MAX_MC], cy[WRSN_MAX_MC]; bool on[WRSN_MAX_MC];
+#pragma unroll
+    for (int o = 0; o < WRSN_MAX_MC; ++o) {
+        const int c = o < M ? o : M - 1;                      // clamped: chargers beyond M are switched off
+        on[o] = o < M && o != self && mc[c * WRSN_ENT_MC_F + 4] == 1.f;
+        cx[o] = mc[c * WRSN_ENT_MC_F + 6]; cy[o] = mc[c * WRSN_ENT_MC_F + 7];
+    }
+    const auto node = wrsn_global((const WrsnU4*)(ent.node + (size_t)e * N * WRSN_ENT_NODE_F));
+    const float ninf = -__builtin_inff();
+    float sA = ninf, sU = ninf; int iA = WRSN_EH_NONE, iU = WRSN_EH_NONE;
+    for (int n0 = 0; n0 < N; n0 += 64) {
+        const int n = n0 + lane, c = n < N ? n : N - 1;       // clamped: nodes beyond N are no candidates
+        const WrsnU4 p = wrsn_ld_u4(node + 2 * c), q = wrsn_ld_u4(node + 2 * c + 1);
+        const float u = __int_as_float((int)p.x), v = __int_as_float((int)p.y), w = __int_as_float((int)p.z);
+        const bool alive = n < N && __int_as_float((int)q.w) == 1.f;
+        bool claimed = false;
+#pragma unroll
+        for (int o = 0; o < WRSN_MAX_MC; ++o) claimed = claimed || (on[o] && wrsn_eh_claims(u, v, cx[o], cy[o], hx, hy));
+        const float s = w > ninf ? w : ninf;                  // a NaN never beats a number
+        if (alive && (iA == WRSN_EH_NONE || s > sA)) { sA = s; iA = n; }
+        if (alive && !claimed && (iU == WRSN_EH_NONE || s > sU)) { sU = s; iU = n; }
+    }
+    const int bU = wrsn_eh_wave_best(sU, iU), bA = wrsn_eh_wave_best(sA, iA);
+    const int n = bU != WRSN_EH_NONE ? bU : bA;
+    if (lane != 0) return;
+    float x, y, t;
+    if (n != WRSN_EH_NONE) {
+        const float* r = ent.node + ((size_t)e * N + n) * WRSN_ENT_NODE_F;
+        x = r[0]; y = r[1]; t = wrsn_eh_charge(charge_scale, r[3]);
+    } else { x = mc[self * WRSN_ENT_MC_F]; y = mc[self * WRSN_ENT_MC_F + 1]; t = 0.f; }
+    float* o = action + (size_t)e * 3;
+    o[0] = x; o[1] = y; o[2] = t;
+    if (action_f64) { double* d = action_f64 + (size_t)e * 3; d[0] = (double)x; d[1] = (double)y; d[2] = (double)t; }
+}
+
+// ------------------------------------------------------------------ episode ledger (wrsn_episodes_collect)
+// One entry per finished episode and environment, and the restart mask of the evaluation loop.  One thread per environment, 256 per
+// block: a row's state lives in its own slots of the caller's arrays, so there is no atomic, no reduction and no order to fix.  The
+// rules (include/wrsn_hip.h) are keyed on WrsnDev.row_state exactly as wrsn_tr_collect_entities_kernel's are.
+struct WrsnEpisodeLog {                                       // mirrors wrsn_episode_log of include/wrsn_hip.h (device pointers)
+    int32_t episodes, quota;
+    double* run_return; int32_t* run_decisions; int32_t* finished; int32_t* dropped;
+    double* lifetime; double* ep_return; int32_t* decisions; int32_t* ended; int32_t* record;
+};
+
+__global__ void __launch_bounds__(256) wrsn_episodes_kernel(int B, int M, WrsnEpisodeLog L, const int32_t* __restrict__ agent_id,
+                                                            const double* __restrict__ reward, const double* __restrict__ now,
+                                                            const int32_t* __restrict__ status, int32_t* __restrict__ row_state,
+                                                            const int32_t* __restrict__ pool_cur, double time_limit,
+                                                            int32_t* __restrict__ next_agent_id, uint8_t* __restrict__ restart, int consume) {
+    const int e = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (e >= B) return;
+    const int st = row_state[e];
+    const int k = L.finished[e];
+    double* run = L.run_return + (size_t)e * M; int32_t* dec = L.run_decisions + (size_t)e * M;
+    int next = 0, close = 0; bool has_next = false; uint8_t again = 0;
+    if (L.quota > 0 && k >= L.quota) { next = -2; has_next = true; }          // parked: whatever the launch did with the row
+    else if (st == 3) { next = -1; has_next = true; }                         // step in flight
+    else if (st == 2) {                                                       // reset / auto-reset / pool swap: an episode starts
+        for (int m = 0; m < M; ++m) { run[m] = 0.0; dec[m] = 0; }
+        next = agent_id[e]; has_next = true;
+    } else if (st == 1) {                                                     // fresh request
+        const int a = agent_id[e];
+        if (a >= 0 && a < M) { run[a] += reward[e]; dec[a] += 1; }
+        if (status[e] == 1) close = 3;
+        else if (time_limit > 0.0 && now[e] >= time_limit) close = 2;
+        else { next = a; has_next = true; }
+    } else if (st == 4) close = 1;                                            // terminal return
+    if (close) {
+        if (k < L.episodes) {
+            const size_t q = (size_t)k * B + e;
+            L.lifetime[q] = now[e]; L.ended[q] = close;
+            for (int m = 0; m < M; ++m) { L.ep_return[q * M + m] = run[m]; L.decisions[q * M + m] = dec[m]; }
+            if (L.record) L.record[q] = pool_cur[e];
+        } else L.dropped[e] += 1;
+        L.finished[e] = k + 1;
+        for (int m = 0; m < M; ++m) { run[m] = 0.0; dec[m] = 0; }
+        next = -2; has_next = true;
+        again = (L.quota > 0 && k + 1 >= L.quota) ? 0 : 1;                    // parked from now on: not restarted
+    }
+    if (next_agent_id && has_next) next_agent_id[e] = next;
+    if (restart) restart[e] = again;
+    if (consume && (st == 1 || st == 2 || st == 4)) row_state[e] = 0;
+}

@@ -23,6 +23,7 @@ runs the actor on batches of one, in training mode); logging goes to CSV (tensor
 import math
 import os
 import time
+import warnings
 
 import numpy as np
 
@@ -496,6 +497,7 @@ class RolloutDriver:
     the stored actions in (`_stored_actions`)."""
 
     _check_status = False                                      # raise when a row comes back from the step with status < 0
+    _ledger = None                                             # an EpisodeLog the roll-out books its requests into (log_episodes), or None
 
     def _attach(self, env, buffers, log):
         self.env, self.buffers, self.log = env, buffers, log
@@ -551,6 +553,8 @@ class RolloutDriver:
             bad = torch.nonzero(r["status"] < 0).flatten()
             if bad.numel():
                 raise RuntimeError("environment rows %s report status %s" % (bad.tolist(), r["status"][bad].tolist()))
+        if self._ledger is not None:                          # the ledger first and without consuming: the requests are the buffers' too
+            env.episodes_collect(self._ledger, 0.0, consume=False)
         self.buffers.collect()
         t4 = self._sync_time()
         tm = self.timers
@@ -576,6 +580,8 @@ class RolloutDriver:
         if fresh_episodes or self._req is None:
             self.buffers.clear()
             self._req = env.reset()
+            if self._ledger is not None:                      # every row starts an episode: what ran before is not booked
+                env.episodes_collect(self._ledger, 0.0, consume=False)
         else:
             self.buffers.clear(keep_pending=True)
         for _ in range(max_launches):
@@ -590,6 +596,24 @@ class RolloutDriver:
         out = self._prepare_batches()
         self.timers["prepare_s"] += self._sync_time() - t0
         return out
+
+    def _episode_stats(self):
+        """The reference's `_log_summary` fields (IPPO.py:316-317) over the episodes the ledger closed since it was last emptied:
+        `avg_ep_lifetime` (mean env.now of the closing returns), `avg_ep_lens` (mean requests per charger and episode; the reference's
+        `cnt` leaves out each charger's first) and `episodes` (how many closed; NaN averages when none did).  One host read; the log is
+        emptied, the sums of the episodes in progress stay."""
+        log = self._ledger
+        fin = log.finished.cpu().numpy()
+        stored = np.arange(log.episodes)[:, None] < np.minimum(fin, log.episodes)[None, :]      # [E, B]: slots that hold an episode
+        life, dec, closed = log.lifetime.cpu().numpy()[stored], log.decisions.cpu().numpy()[stored], int(fin.sum())
+        dropped = int(log.dropped.sum())
+        if dropped:                                           # the averages cover the stored episodes only: say so instead of hiding it
+            warnings.warn("%d of %d episodes closed since the last read did not fit the %d slots per environment: avg_ep_lifetime and "
+                          "avg_ep_lens leave them out (raise episode_slots)" % (dropped, closed, log.episodes))
+        log.clear(keep_running=True)                          # after the reads: on a CPU device `fin` is a view of the log
+        nan = float("nan")
+        return dict(avg_ep_lifetime=float(life.mean()) if life.size else nan, avg_ep_lens=float(dec.mean()) if dec.size else nan,
+                    episodes=closed)
 
     def _prepare_batches(self):
         """The tail of `roll_out`: per charger the reference's batch selection, the gathers and `cal_rt_adv`; the list of batch dicts."""
@@ -612,12 +636,15 @@ class RolloutDriver:
         return out
 
     def train(self, trained_iterations, save_folder=None):
-        """IPPO.py:212-311: roll out, update every charger, log, checkpoint every `save_freq` iterations."""
+        """IPPO.py:212-311: roll out, update every charger, log, checkpoint every `save_freq` iterations.  With `log_episodes` the
+        episode fields of an iteration cover everything the ledger closed since it was last read: a `roll_out()` called directly in
+        front of `train()` is counted into the first iteration's rows."""
         torch = self.torch
         start = time.time(); i_so_far = 0; rows = []
         while i_so_far <= trained_iterations:
             batches = self.roll_out()
             i_so_far += 1
+            episodes = self._episode_stats() if self._ledger is not None else {}
             t0 = self._sync_time()
             joint = self.update_all(batches) if getattr(self, "joint_update", False) else None   # every charger's update at once
             for id in range(self.num_agent):
@@ -630,6 +657,7 @@ class RolloutDriver:
                 row = dict(iteration=lg["i_so_far"], timesteps=lg["t_so_far"], agent=id, policy_loss=st[0], value_loss=st[1], entropy=st[2],
                            approx_kl=st[3], clipfrac=st[4], explained_variance=float(ev), mean_reward=lg["rewards"][-1],
                            sps=i_so_far / (time.time() - start))
+                row.update(episodes)
                 rows.append(row)
                 if self.log:
                     self.log(row)
@@ -883,16 +911,27 @@ class BatchedEntityIPPO(RolloutDriver, EntityPPOLearner):
                    host (the `np.random` stream of the default path), one index upload, the critics packed once, and ONE call that
                    writes every charger's values, advantages, returns and gathered rows into [M, batch_size, ...] tensors; the batch
                    dicts hold per-charger views of them, bit for bit what the default path returns.  False (the default): the
-                   per-charger `index_select`s and `cal_rt_adv`, no new launch."""
+                   per-charger `index_select`s and `cal_rt_adv`, no new launch.
+    log_episodes : True = every launch of the roll-out also runs the episode ledger (`wrsn_episodes_collect`, never parking, no time limit,
+                   not consuming) in front of the buffers' collect, and every row `train` logs gains `avg_ep_lifetime`, `avg_ep_lens`
+                   and `episodes` over the episodes that closed in that iteration (at most `episode_slots` per environment are kept;
+                   more are counted in `episodes` only).  Batches, weights and optimiser state are unchanged, bit for bit.  False (the
+                   default): nothing new is launched and the rows have the keys they always had.
+
+    `evaluate_episodes(eval_env, ...)` measures the policy over whole episodes on ANOTHER batch of environments (`evaluate.evaluate_policy`;
+    `evaluate` itself is the reference's `evaluate(agent, states, actions)` of the learner)."""
 
     _check_status = True
 
     def __init__(self, args, env, device=None, model_path=None, capacity=None, infer_chunk=1024, process_group=None, log=None, min_bucket=16,
-                 fused_policy=False, fused_update=False, joint_update=False, fused_prepare=False):
+                 fused_policy=False, fused_update=False, joint_update=False, fused_prepare=False, log_episodes=False, episode_slots=64):
         if not getattr(env, "entities", False):
             raise ValueError("BatchedEntityIPPO needs a VecWRSN with the entity observation (entities=True)")
         super().__init__(args, env.num_agent, device if device is not None else env.device, model_path, infer_chunk, process_group, min_bucket)
         self._attach(env, EntityTransitionBuffers(env, capacity or 2 * self.batch_size, 3), log)
+        self.log_episodes = bool(log_episodes)
+        if self.log_episodes:
+            self._ledger = env.new_episode_log(episode_slots, quota=0)
         self.fused_policy = bool(fused_policy)
         self._packed = None                                   # packed_actors() of the weights as they are now, or None: rebuilt before use
         self.fused_update = bool(fused_update)
@@ -911,6 +950,15 @@ class BatchedEntityIPPO(RolloutDriver, EntityPPOLearner):
             self._grad = z(self._pa + self._pc)               # ONE tensor: what the data-parallel exchange reduces
             self._grad_all = None                             # joint_update: the same for every charger, [M, P_actor + P_critic], at first use
             self._adam = [dict(m_a=z(self._pa), v_a=z(self._pa), m_c=z(self._pc), v_c=z(self._pc), step=0) for _ in range(self.num_agent)]
+
+    def evaluate_episodes(self, eval_env, episodes=1, deterministic=True, generator=None, **kw):
+        """`evaluate_policy` of the actors as they are now -- their mode, or with deterministic=False a sample per decision -- on
+        `eval_env`, a `VecWRSN(entities=True, auto_reset=False)` with this trainer's number of chargers; `kw` goes to `evaluate_policy`.
+        ValueError when `eval_env` is the trainer's own batch: its environments live across roll-outs and must not be disturbed."""
+        from .evaluate import EntityPolicy, evaluate_policy
+        if eval_env is self.env:
+            raise ValueError("evaluate on a batch of its own: the trainer's environments live across roll-outs")
+        return evaluate_policy(eval_env, EntityPolicy(self.packed_actors(), deterministic, generator), episodes, **kw)
 
     def roll_out(self, max_launches=100000, fresh_episodes=False):
         if self.fused_policy:

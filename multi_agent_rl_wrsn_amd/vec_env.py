@@ -30,6 +30,31 @@ def obs_torch_dtype(obs_dtype):
     raise ValueError("obs_dtype must be 'float32' or 'bfloat16' (or torch.float32 / torch.bfloat16), got %r" % (obs_dtype,))
 
 
+class EpisodeLog:
+    """The episode ledger of `wrsn_episodes_collect` for B environments x M chargers: the tensors under the field names of
+    `wrsn_episode_log` (`run_return`, `run_decisions`, `finished`, `dropped`, `lifetime`, `ep_return`, `decisions`, `ended`, `record`),
+    `episodes` stored per environment and the parking `quota`.  `clear()` zeroes everything (asynchronously); `clear(keep_running=True)`
+    keeps the sums of the episodes in progress, for a log that is read and emptied while its environments go on."""
+
+    def __init__(self, torch, device, B, M, episodes, quota=0):
+        E, quota = int(episodes), int(quota)
+        if E < 1 or not 0 <= quota <= E:
+            raise ValueError("episodes must be >= 1 and quota in [0, episodes], got %d and %d" % (E, quota))
+        self.episodes, self.quota = E, quota
+        f64, i32 = torch.float64, torch.int32
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
+        self.run_return, self.run_decisions = z((B, M), f64), z((B, M), i32)
+        self.finished, self.dropped = z((B,), i32), z((B,), i32)
+        self.lifetime, self.ep_return, self.decisions = z((E, B), f64), z((E, B, M), f64), z((E, B, M), i32)
+        self.ended, self.record = z((E, B), i32), z((E, B), i32)
+        self.raw = _lib.WrsnEpisodeLog(E, quota, *(getattr(self, k).data_ptr() for k in _lib.EPISODE_LOG_ARRAYS))
+
+    def clear(self, keep_running=False):
+        for k in _lib.EPISODE_LOG_ARRAYS:
+            if not (keep_running and k in ("run_return", "run_decisions")):
+                getattr(self, k).zero_()
+
+
 class VecWRSN:
     """Batched WRSN environment on one MI355X.
 
@@ -249,6 +274,45 @@ class VecWRSN:
         self._h.entity_act(w.data_ptr(), a.data_ptr(), e.data_ptr() if e is not None else 0, None,
                            action=act.data_ptr(), action_f64=act64.data_ptr(), logp=logp.data_ptr())
         return act, act64, logp
+
+    def entity_heuristic_act(self, agent_ids, charge_scale=1.0):
+        """`wrsn_entity_heuristic_act` on the entity rows this object holds (`entities=True`): for the chargers `agent_ids` [B] (outside
+        [0, M): row skipped) the most critical node no other charger is heading for.  Returns (action float32 [B,3], action_f64 float64
+        [B,3] -- what `step` takes): tensors this object owns and writes again at the next call; skipped rows keep what they held."""
+        t = self.torch
+        if not self.entities:
+            raise ValueError("entity_heuristic_act needs a VecWRSN with the entity observation (entities=True)")
+        self._bind_stream()
+        a = agent_ids
+        if not (a.dtype == t.int32 and a.device == self.device and a.is_contiguous() and a.numel() == self.num_env):
+            a = a.to(device=self.device, dtype=t.int32).reshape(-1).contiguous()
+        if getattr(self, "_heur", None) is None:
+            B = self.num_env
+            self._heur = (t.zeros((B, 3), dtype=t.float32, device=self.device), t.zeros((B, 3), dtype=t.float64, device=self.device))
+        self._keep_heur = a                                   # alive until the launch has run
+        act, act64 = self._heur
+        self._h.entity_heuristic_act(a.data_ptr(), None, charge_scale, action=act.data_ptr(), action_f64=act64.data_ptr())
+        return act, act64
+
+    def new_episode_log(self, episodes, quota=0):
+        """An `EpisodeLog` for this batch: `episodes` finished episodes stored per environment; quota 0 = never park, else an environment
+        is parked (left alone, not restarted) once it has finished `quota` episodes."""
+        return EpisodeLog(self.torch, self.device, self.num_env, self.num_agent, episodes, quota)
+
+    def episodes_collect(self, log, time_limit=0.0, consume=True):
+        """`wrsn_episodes_collect` after a `reset`, `step` or `pool_reset` of this object: books the requests of that call into `log` and
+        returns (next_agent_id int32 [B], restart uint8 [B]) -- the ids for the next `step` (-2: leave the row alone, -1: step in flight)
+        and the mask of the rows whose episode this call closed, for `reset(mask=...)` / `pool_reset(mask=...)`.  Tensors this object owns.
+        time_limit > 0 closes an episode whose request comes at env.now >= time_limit; consume=False leaves the requests to a
+        following `TransitionBuffers.collect`."""
+        t = self.torch
+        self._bind_stream()
+        if getattr(self, "_ledger_out", None) is None:
+            self._ledger_out = (t.full((self.num_env,), -2, dtype=t.int32, device=self.device), t.zeros(self.num_env, dtype=t.uint8, device=self.device))
+        nxt, restart = self._ledger_out
+        p = self._out_ptrs(); p.pop("obs", None)
+        self._h.episodes_collect(log.raw, time_limit, nxt.data_ptr(), restart.data_ptr(), consume, **p)
+        return nxt, restart
 
     def set_step_budget(self, work_units):
         self.step_budget = int(work_units)

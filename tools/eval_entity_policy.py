@@ -1,0 +1,177 @@
+"""Whole-episode evaluation of the entity policy against its baselines, and the cost of the episode ledger.
+
+Default mode: `evaluate_policy` on a HELD-OUT set -- `--eval-envs` (256) synthetic 200-node networks whose seeds the trainer never sees --
+for: uniform actions, the heuristic (`HeuristicPolicy`, as the kernel's rule stands and with `--min-charge`), the untrained actors (mode
+and sampled) and the actors after `--iters` (200) iterations of BatchedEntityIPPO with the fused options of bench_ippo.py (mode and
+sampled).  A policy that uses up `--max-launches` is recorded with its partial log and the number of environments standing still (a
+deterministic policy that repeats an action of zero duration gets the same request again at the same instant).  Writes
+profiles/entity_eval.json.
+
+--bench: the evaluation loop per launch at `--envs` (4096) x 200 nodes x 3 chargers with the heuristic policy, in two forms: with
+wrsn_episodes_collect, and with the same bookkeeping in elementwise torch on calls that existed before it (`step`, `reset(mask)`).
+Alternating windows of `--launches` launches (synchronised wall time of a window / launches), medians of the window medians.  Writes
+profiles/episodes_bench.json.  `--only fused|torch` runs one form (for a kernel trace).
+python tools/eval_entity_policy.py [--iters 200] [--episodes 1] [--bench] [--windows 3] [--only fused]"""
+import argparse, json, os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def torch_loop(env, policy, episodes, time_limit, park=True):
+    """The bookkeeping of the ledger in elementwise torch: a generator that performs one launch per next().  park=False: `episodes`
+    slots are stored, later episodes only counted, nothing is parked (the ledger's quota 0)."""
+    t = env.torch
+    B, M, E = env.num_env, env.num_agent, episodes
+    z = lambda shape, dt: t.zeros(shape, dtype=dt, device=env.device)
+    run_ret, run_dec, finished = z((B, M), t.float64), z((B, M), t.int32), z((B,), t.int64)
+    life, ep_ret, dec, ended = z((E, B), t.float64), z((E, B, M), t.float64), z((E, B, M), t.int32), z((E, B), t.int32)
+    ar = t.arange(B, device=env.device)
+    ids = env.reset()["agent_id"].clone()
+    while True:
+        r = env.step(ids, policy(env, ids))
+        agent, status, now, reward, terminal = r["agent_id"], r["status"], r["now"], r["reward"], r["terminal"]
+        stepped = ids != -2
+        flying = stepped & (status == 4)
+        term = stepped & ~flying & (terminal != 0)
+        fresh = stepped & ~flying & (terminal == 0)
+        hot = (t.nn.functional.one_hot(agent.clamp(0, M - 1).long(), M) * (fresh & (agent >= 0) & (agent < M))[:, None])
+        run_ret += hot * reward[:, None]; run_dec += hot.int()
+        code = t.where(term, 1, t.where(fresh & (status == 1), 3, t.where(fresh & (now >= time_limit), 2, 0)))
+        closing = (code > 0) & (finished < E)
+        k = finished.clamp(max=E - 1)
+        life[k, ar] = t.where(closing, now, life[k, ar]); ended[k, ar] = t.where(closing, code.int(), ended[k, ar])
+        ep_ret[k, ar] = t.where(closing[:, None], run_ret, ep_ret[k, ar]); dec[k, ar] = t.where(closing[:, None], run_dec, dec[k, ar])
+        finished += (code > 0)
+        keep = (code == 0)[:, None]
+        run_ret *= keep; run_dec *= keep
+        restart = (code > 0) & ((finished < E) if park else (finished >= 0))
+        ids = t.where(code > 0, -2, t.where(flying, -1, t.where(fresh, agent, ids))).int()
+        r = env.reset(mask=restart.to(t.uint8))
+        ids = t.where(restart, r["agent_id"], ids).int().contiguous()
+        yield finished
+
+
+def ledger_loop(env, policy, episodes, time_limit, park=True):
+    log = env.new_episode_log(episodes, quota=episodes if park else 0)
+    env.reset()
+    ids, restart = env.episodes_collect(log, time_limit)
+    while True:
+        env.step(ids, policy(env, ids))
+        ids, restart = env.episodes_collect(log, time_limit)
+        env.reset(mask=restart)
+        ids, restart = env.episodes_collect(log, time_limit)
+        yield log.finished
+
+
+def bench(args):
+    import numpy as np
+    import torch
+    from multi_agent_rl_wrsn_amd import HeuristicPolicy, VecWRSN, synth_scenario
+    N, M = 200, 3
+    scs = [synth_scenario(e, N, N) for e in range(args.envs)]
+    tl = min(s.max_time for s in scs)
+    forms = [(k, f) for k, f in (("fused", ledger_loop), ("torch", torch_loop)) if args.only in (None, k)]
+    envs = {k: VecWRSN(scs, None, M, render=False, entities=True, step_budget=1250) for k, _ in forms}
+    pol = HeuristicPolicy(min_charge=args.min_charge)
+    loops = {k: f(envs[k], pol, 8, tl, park=False) for k, f in forms}   # nothing parks: every launch steps every environment
+    dev = envs[forms[0][0]].device
+    out = {"workload": "evaluation loop, %d envs x %d nodes x %d chargers, heuristic policy (min_charge %g), step budget 1250" % (args.envs, N, M, args.min_charge),
+           "device": torch.cuda.get_device_name(dev), "launches_per_window": args.launches, "windows": {k: [] for k, _ in forms}}
+    for k, _ in forms:
+        for _ in range(10):
+            next(loops[k])
+    for _ in range(args.windows):
+        for k, _ in forms:
+            torch.cuda.synchronize(dev); t0 = time.perf_counter()
+            for _ in range(args.launches):
+                next(loops[k])
+            torch.cuda.synchronize(dev)
+            out["windows"][k].append((time.perf_counter() - t0) * 1e3 / args.launches)
+    for k, _ in forms:
+        w = out["windows"][k]
+        out[k + "_ms_per_launch"] = float(np.median(w)); out[k + "_spread_ms"] = float(max(w) - min(w))
+    if args.only is None:
+        out["torch_over_fused"] = out["torch_ms_per_launch"] / out["fused_ms_per_launch"]
+    return out
+
+
+def compare(args):
+    import numpy as np
+    import torch
+    from multi_agent_rl_wrsn_amd import (BatchedEntityIPPO, EntityPolicy, HeuristicPolicy, UniformPolicy, VecWRSN, evaluate_policy, synth_scenario)
+    from multi_agent_rl_wrsn_amd.evaluate import LaunchCapReached
+    N, M = 200, 3
+    torch.manual_seed(0); np.random.seed(0)
+    train_env = VecWRSN([synth_scenario(e, N, N) for e in range(args.envs)], None, M, render=False, entities=True, auto_reset=True, step_budget=1250)
+    eval_env = VecWRSN([synth_scenario(1_000_000 + e, N, N) for e in range(args.eval_envs)], None, M, render=False, entities=True, step_budget=1250)
+    algo = BatchedEntityIPPO(dict(batch_size=512, minibatch_size=64, n_updates_per_iteration=5), train_env, capacity=4096, fused_policy=True,
+                             fused_update=True, joint_update=True, fused_prepare=True, log_episodes=True)
+    gen = lambda: torch.Generator(device=eval_env.device).manual_seed(7)
+    out = {"eval_set": "%d synthetic %d-node networks, seeds 1000000.., %d chargers, %d episode(s) each, time limit %g s" %
+                       (args.eval_envs, N, M, args.episodes, min(s.max_time for s in eval_env.scenarios)),
+           "device": torch.cuda.get_device_name(eval_env.device), "max_launches": args.max_launches, "policies": {}}
+
+    def run(name, policy):
+        t0 = time.perf_counter()
+        try:
+            res, capped = evaluate_policy(eval_env, policy, episodes=args.episodes, max_launches=args.max_launches), False
+        except LaunchCapReached as ex:
+            res, capped = ex.result, True
+        row = dict(res["summary"], launches=int(res["launches"]), launch_cap_reached=capped, seconds=time.perf_counter() - t0)
+        if capped:
+            row.update(environments_finished=int((res["finished"] >= args.episodes).sum()), environments_standing_still=int(res["standing"].sum()))
+        out["policies"][name] = row
+        print(name, json.dumps(row), flush=True)
+
+    run("uniform", UniformPolicy(gen()))
+    run("heuristic", HeuristicPolicy())
+    run("heuristic_min_charge", HeuristicPolicy(min_charge=args.min_charge))
+    run("untrained_mode", EntityPolicy(algo.packed_actors(), True))
+    run("untrained_sampled", EntityPolicy(algo.packed_actors(), False, gen()))
+    t0 = time.perf_counter()
+    # The trainer raises when a row comes back with a negative status (an environment whose step reported an error: seen after a handful
+    # of iterations at these shapes).  Here such rows are counted, not fatal: they are a few of thousands and ask nobody for an action.
+    algo._check_status = False
+    errors = torch.zeros((), dtype=torch.int64, device=train_env.device)
+    step = train_env.step
+
+    def counting_step(ids, act):
+        r = step(ids, act)
+        errors.add_((r["status"] < 0).sum())
+        return r
+
+    train_env.step = counting_step
+    rows = algo.train(args.iters - 1) if args.iters > 0 else []
+    train_env.step = step
+    out["training"] = {"iterations": len(rows) // M, "error_status_rows_summed_over_launches": int(errors), "launches": algo.timers["launches"],
+                       "seconds": time.perf_counter() - t0,
+                       "last_rows": [{k: r[k] for k in ("iteration", "agent", "mean_reward", "avg_ep_lifetime", "avg_ep_lens", "episodes")} for r in rows[-M:]]}
+    run("trained_mode", EntityPolicy(algo.packed_actors(), True))
+    run("trained_sampled", EntityPolicy(algo.packed_actors(), False, gen()))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--episodes", type=int, default=1)
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--eval-envs", type=int, default=256)
+    ap.add_argument("--max-launches", type=int, default=4000)
+    ap.add_argument("--min-charge", type=float, default=0.02)
+    ap.add_argument("--bench", action="store_true")
+    ap.add_argument("--windows", type=int, default=3)
+    ap.add_argument("--launches", type=int, default=50)
+    ap.add_argument("--only", default=None, choices=[None, "fused", "torch"])
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    out = bench(args) if args.bench else compare(args)
+    path = args.out or os.path.join(ROOT, "profiles", "episodes_bench.json" if args.bench else "entity_eval.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as w:
+        json.dump(out, w, indent=1)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
