@@ -36,8 +36,9 @@ def main():
     ap.add_argument("--infer-chunk", type=int, default=512)
     ap.add_argument("--inference-dtype", default=None, choices=[None, "bf16", "fp16"], help="reduced-precision roll-out inference (update stays float32)")
     ap.add_argument("--obs-dtype", default="float32", choices=["float32", "bfloat16"], help="observation format of the environment and the roll-out buffers")
-    ap.add_argument("--policy", default="image", choices=["image", "entity"], help="image: UNet / CNN critic on the 4 x G x G observation (default); "
-                    "entity: the set policy on entity rows, no image rendered (VecWRSN(render=False, entities=True), BatchedEntityIPPO)")
+    ap.add_argument("--policy", default="image", choices=["image", "entity", "pointer"], help="image: UNet / CNN critic on the 4 x G x G observation (default); "
+                    "entity: the set policy on entity rows, no image rendered (VecWRSN(render=False, entities=True), BatchedEntityIPPO); "
+                    "pointer: the node-pointer policy on the same rows (BatchedEntityPointerIPPO; --fused-policy: wrsn_entity_pointer_act)")
     ap.add_argument("--fused-policy", action="store_true", help="with --policy entity: the device samples the actions itself (wrsn_entity_act, "
                     "BatchedEntityIPPO(fused_policy=True)) instead of one PyTorch forward pass per charger")
     ap.add_argument("--fused-update", action="store_true", help="with --policy entity: the PPO update runs on the device (wrsn_entity_ppo_grad, "
@@ -46,12 +47,14 @@ def main():
                     "one call (wrsn_entity_ppo_update, BatchedEntityIPPO(joint_update=True))")
     ap.add_argument("--fused-prepare", action="store_true", help="implies --fused-update: values, GAE and the gathers of every charger's batch in one device "
                     "call (wrsn_entity_prepare, BatchedEntityIPPO(fused_prepare=True)) instead of index_select and cal_rt_adv per charger")
+    ap.add_argument("--min-charge", type=float, default=0.02, help="with --policy pointer: the least third component of an action "
+                    "(BatchedEntityPointerIPPO(min_charge=...))")
     ap.add_argument("--report-updates", action="store_true", help="add peak device memory and the statistics of every update (first minibatch included) to the line")
     args = ap.parse_args()
     if args.joint_update or args.fused_prepare:
         args.fused_update = True
-    if args.fused_policy and args.policy != "entity":
-        raise SystemExit("--fused-policy needs --policy entity")
+    if args.fused_policy and args.policy not in ("entity", "pointer"):
+        raise SystemExit("--fused-policy needs --policy entity or --policy pointer")
     if args.fused_update and args.policy != "entity":
         raise SystemExit("--fused-update needs --policy entity")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:       # launcher-free multi-rank entry: before this process touches torch or the GPU
@@ -59,7 +62,7 @@ def main():
         raise SystemExit(launch_ranks(args.gpus, [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]))
     import numpy as np
     import torch
-    from multi_agent_rl_wrsn_amd import BatchedEntityIPPO, BatchedIPPO, RolloutStats, VecWRSN, init_distributed, synth_scenario
+    from multi_agent_rl_wrsn_amd import BatchedEntityIPPO, BatchedEntityPointerIPPO, BatchedIPPO, RolloutStats, VecWRSN, init_distributed, synth_scenario
     rank, world, local_rank = init_distributed()
     if world != args.gpus and not (args.gpus == 1 and "WORLD_SIZE" in os.environ):      # torchrun without --gpus: WORLD_SIZE rules
         raise SystemExit("--gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
@@ -72,10 +75,15 @@ def main():
     dev = torch.device("cuda", local_rank)
     torch.cuda.set_device(dev)
     B, N, M = args.envs, args.nodes, 3
-    entity = args.policy == "entity"
+    entity, pointer = args.policy == "entity", args.policy == "pointer"
     updates = []                                               # --report-updates: every row train() logs, with the first minibatch's statistics
     ppo_args = dict(batch_size=args.batch_size, minibatch_size=args.minibatch_size, n_updates_per_iteration=args.updates)
-    if entity:
+    if pointer:
+        env = VecWRSN([synth_scenario(rank * B + e, N, N) for e in range(B)], None, M, auto_reset=True, step_budget=args.step_budget, device=str(dev),
+                      render=False, entities=True)
+        algo = BatchedEntityPointerIPPO(ppo_args, env, capacity=max(2 * args.batch_size, 4096), infer_chunk=args.infer_chunk, min_bucket=args.infer_chunk,
+                                        fused_policy=args.fused_policy, min_charge=args.min_charge)
+    elif entity:
         env = VecWRSN([synth_scenario(rank * B + e, N, N) for e in range(B)], None, M, auto_reset=True, step_budget=args.step_budget, device=str(dev),
                       render=False, entities=True)             # no image at all: 6.6 KB of entity rows per request
         algo = BatchedEntityIPPO(ppo_args, env, capacity=max(2 * args.batch_size, 4096), infer_chunk=args.infer_chunk, min_bucket=args.infer_chunk,
@@ -139,6 +147,10 @@ def main():
             ", update on the device (wrsn_entity_ppo_grad, wrsn_entity_adam)" if args.fused_update else "") + (
             ", every charger in one call (wrsn_entity_ppo_update)" if args.joint_update else "") + (
             ", batch prepared on the device (wrsn_entity_prepare)" if args.fused_prepare else "")
+    if pointer:
+        out["config"]["workload"] = "%d envs x %d nodes x %d MC, node-pointer actor + set critic per charger on entity rows, (node, x) actions, batch %d / minibatch %d / %d epochs" % (
+            B, N, M, args.batch_size, args.minibatch_size, args.updates)
+        out["config"]["policy"] = "float32, entity rows, no image" + (", actions sampled on the device (wrsn_entity_pointer_act)" if args.fused_policy else "")
     if args.report_updates:
         out["peak_memory_bytes"] = int(torch.cuda.max_memory_allocated(dev)); out["updates"] = updates
     print(json.dumps(out, default=float), flush=True)

@@ -350,6 +350,60 @@ typedef struct wrsn_entity_act_out {    /* DEVICE, caller-owned; written only fo
 int wrsn_entity_act(wrsn_t *h, const float *actors, const int32_t *agent_id, const float *eps, const wrsn_entity_out *ent,
                     const wrsn_entity_act_out *out);
 
+/* ACTING FROM ENTITY ROWS WITH A NODE POINTER.  The actor of build_entity_pointer_networks (ippo.py) evaluated and sampled on the
+ * device: the trunk of the set policy above, a categorical choice of ONE alive node, and a charge head on the chosen node's own
+ * features.  The destination is the chosen node's position, so the actor names a node instead of regressing a position from pools,
+ * and the third component is a sigmoid raised to at least min_charge, so with min_charge > 0 every decision spends simulated time.
+ * `actors` holds one packed float32 block per charger, [n_mc, wrsn_entity_pointer_floats()].
+ * BLOCK LAYOUT.  The trunk -- node1, node2, mc1, mc2, head1, head2 -- at the offsets of the block of wrsn_entity_act, 48 448 floats;
+ * then, every Linear again TRANSPOSED, [in, out] row-major, directly followed by its bias (offsets in floats):
+ *     query  128 ->  64  at 48448, bias at 56640      charge 136 ->   2  at 56704, bias at 56976
+ * charge's 136 input rows are z [128] first, then the chosen node's eight features; its outputs are (mean, log_std).  56 978 floats,
+ * then zeros up to a multiple of 4: wrsn_entity_pointer_floats() == 56 980.
+ * SEMANTICS.  Row e with a = agent_id[e] in [0, n_mc) is evaluated exactly as EntityPointerActor evaluates it, with block a, all in
+ * float32.  z = ReLU(head2(ReLU(head1(features)))) as for wrsn_entity_act; q = query(z); h_i = ReLU(node2(ReLU(node1(x_i)))) with x_i
+ * the eight inputs of node i (they are used only for alive nodes);
+ *     l_i = 0.125 <h_i, q>   for the nodes whose slot 7 (alive) equals 1, -inf for every other -- a select: NaN or inf in a dead or
+ *                            padded node row never enter (an alive node whose l_i is not > -inf -- a NaN from weights that are
+ *                            not finite -- counts as not alive);
+ *     node_logp[i] = l_i - log sum_{j alive} exp(l_j)            (-inf where l_i is)
+ *     node = the alive i with the largest l_i + gumbel[e][i], the lowest index among equal scores; a score that is not > -inf
+ *            (a NaN) counts as -inf; gumbel == NULL stands for zeros (the mode)
+ *     (mean, log_std) = charge([z, x_node]), log_std clamped to [-4, 1];  x = fmaf(exp(log_std), eps[e], mean), eps == NULL: eps = 0
+ *     c = min_charge + (1 - min_charge) * (1 / (1 + expf(-x)))
+ *     action = (node[node][0], node[node][1], c)        stored = ((float)node, x)
+ *     logp = node_logp[node] + (-eps^2 / 2 - log_std - 0.5 log(2 pi))
+ * A row with no alive node: node = -1, stored[0] = -1, the node term of logp is 0, x_node is zeros, node_logp is -inf everywhere, and
+ * the destination is the asking charger's own position (mc[self][0], mc[self][1]), self being the lowest-index charger row whose slot 3
+ * (is_self) equals 1 and row a when there is none: the rule of wrsn_entity_heuristic_act.  No output is a NaN for it.
+ * `stored` is what wrsn_rollout_record_entities stores for this policy (action_elems = 2): from it and the stored row, the update
+ * recomputes logp.  action_f64 holds `action` widened, as wrsn_step takes it.  Rows with agent_id outside [0, n_mc) are skipped:
+ * every byte of every output is kept.
+ * A row's outputs depend on its own entity rows, its charger's block, its gumbel row and its eps only: not on any other row of the
+ * batch, not on its position in it, and not on the run -- two calls on equal inputs give equal bytes (no float atomics; every sum and
+ * every maximum in a fixed order; the bits of l_i do not depend on where node i sits in the row's tiles).  `ent` NULL: the registered
+ * buffers.  The call needs no scenario: it reads nothing but `ent`, `actors`, `agent_id`, `gumbel` and `eps`.
+ * WRSN_ERR_ARG, with the handle and every buffer untouched: h, actors, agent_id, out, out->node, out->stored, out->action or out->logp
+ * NULL; ent == NULL and nothing registered; node, mc or env NULL or not 16-byte aligned; actors not 16-byte aligned; min_charge not
+ * finite or outside [0, 1).
+ * Asynchronous on the handle's stream, into which a pipelined step has joined.  The scratch -- that of wrsn_entity_act, shared with
+ * it, plus n_env * 192 floats for z and q -- lives in the handle, is allocated by the first call and freed by wrsn_destroy. */
+int32_t wrsn_entity_pointer_floats(void);            /* 56 980: floats of one block, a multiple of 4; host only, no handle */
+
+typedef struct wrsn_entity_pointer_out {             /* DEVICE, caller-owned; written only for rows that are not skipped */
+    int32_t *node;        /* [B]   chosen node, -1: no alive node */
+    float   *stored;      /* [B,2] ((float)node, x): what wrsn_rollout_record_entities stores (action_elems = 2) */
+    float   *action;      /* [B,3] (u_k, v_k, c) */
+    double  *action_f64;  /* [B,3] the same widened; may be NULL */
+    float   *logp;        /* [B] */
+    float   *node_logp;   /* [B,N] log-softmax over the alive nodes, -inf elsewhere; may be NULL */
+    float   *charge_mean, *charge_log_std;   /* [B] each, after the clamp; each may be NULL */
+} wrsn_entity_pointer_out;
+
+int wrsn_entity_pointer_act(wrsn_t *h, const float *actors /* [n_mc, floats] */, const int32_t *agent_id,
+                            const float *gumbel /* [B,N] or NULL */, const float *eps /* [B] or NULL */,
+                            float min_charge, const wrsn_entity_out *ent, const wrsn_entity_pointer_out *out);
+
 /* A HEURISTIC BASELINE ON THE ENTITY ROWS: "go to the most critical node nobody else is serving".  Deterministic, no parameters but
  * charge_scale; the answer to "better than what?" for a learned entity policy.  For row e with a = agent_id[e] in [0, n_mc), everything
  * in float32, every operation rounded on its own (no contraction into an FMA):

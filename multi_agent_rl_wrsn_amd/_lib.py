@@ -31,6 +31,7 @@ ENT_NODE = {k: i for i, k in enumerate(ENT_NODE_FIELDS)}      # ENT_NODE["weight
 ENT_MC = {k: i for i, k in enumerate(ENT_MC_FIELDS) if not k.startswith("_")}
 ENT_ENV = {k: i for i, k in enumerate(ENT_ENV_FIELDS) if not k.startswith("_")}
 ENTITY_ACTOR_FLOATS, ENTITY_CRITIC_FLOATS = 49224, 48580   # wrsn_entity_actor_floats(), wrsn_entity_critic_floats() (include/wrsn_hip.h)
+ENTITY_POINTER_FLOATS = 56980   # wrsn_entity_pointer_floats(): the block of the node-pointer actor (include/wrsn_hip.h)
 ENTPOL_FEAT = 200            # wrsn_entity_act: inputs of the actor's head (64 mean + 64 max + 32 charger mean + 32 own + 8 env)
 MC_FIELDS = ("loc_x", "loc_y", "energy", "status", "type_charging", "cur_x", "cur_y", "cur_t", "n_conn",
              "excl", "prev_minfit", "act0", "act1", "act2", "_r0", "_r1")
@@ -39,7 +40,7 @@ ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max"
 
 # every entry point include/wrsn_hip.h declares
 EXPORTS = ("wrsn_create", "wrsn_destroy", "wrsn_set_stream", "wrsn_set_scenario", "wrsn_set_scenario_seeded", "wrsn_reset", "wrsn_step",
-           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_entity_actor_floats", "wrsn_entity_act", "wrsn_entity_heuristic_act", "wrsn_episodes_collect", "wrsn_entity_critic_floats", "wrsn_entity_eval", "wrsn_entity_ppo_grad", "wrsn_entity_adam", "wrsn_entity_ppo_grad_multi", "wrsn_entity_adam_multi", "wrsn_entity_ppo_update", "wrsn_entity_prepare", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
+           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_entity_actor_floats", "wrsn_entity_act", "wrsn_entity_pointer_floats", "wrsn_entity_pointer_act", "wrsn_entity_heuristic_act", "wrsn_episodes_collect", "wrsn_entity_critic_floats", "wrsn_entity_eval", "wrsn_entity_ppo_grad", "wrsn_entity_adam", "wrsn_entity_ppo_grad_multi", "wrsn_entity_adam_multi", "wrsn_entity_ppo_update", "wrsn_entity_prepare", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
            "wrsn_clone_envs", "wrsn_pool_set", "wrsn_pool_reset", "wrsn_synth_network",
            "wrsn_last_error",
            "wrsn_version")
@@ -72,6 +73,10 @@ class WrsnEntityOut(C.Structure):
 
 class WrsnEntityActOut(C.Structure):
     _fields_ = [("action", C.c_void_p), ("action_f64", C.c_void_p), ("logp", C.c_void_p), ("mean", C.c_void_p), ("log_std", C.c_void_p)]
+
+
+class WrsnEntityPointerOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("node", "stored", "action", "action_f64", "logp", "node_logp", "charge_mean", "charge_log_std")]
 
 
 EPISODE_LOG_ARRAYS = ("run_return", "run_decisions", "finished", "dropped", "lifetime", "ep_return", "decisions", "ended", "record")
@@ -162,6 +167,10 @@ def bind(lib):
     lib.wrsn_entity_actor_floats.restype = C.c_int32
     lib.wrsn_entity_act.argtypes = [vp, vp, vp, vp, C.POINTER(WrsnEntityOut), C.POINTER(WrsnEntityActOut)]
     lib.wrsn_entity_act.restype = C.c_int
+    lib.wrsn_entity_pointer_floats.argtypes = []
+    lib.wrsn_entity_pointer_floats.restype = C.c_int32
+    lib.wrsn_entity_pointer_act.argtypes = [vp, vp, vp, vp, vp, C.c_float, C.POINTER(WrsnEntityOut), C.POINTER(WrsnEntityPointerOut)]
+    lib.wrsn_entity_pointer_act.restype = C.c_int
     lib.wrsn_entity_heuristic_act.argtypes = [vp, vp, C.POINTER(WrsnEntityOut), C.c_float, vp, vp]
     lib.wrsn_entity_heuristic_act.restype = C.c_int
     lib.wrsn_episodes_collect.argtypes = [vp, C.POINTER(WrsnEpisodeLog), C.POINTER(WrsnStepOut), C.c_double, vp, vp, C.c_int32]
@@ -383,6 +392,17 @@ class RawHandle:
         o = WrsnEntityActOut(action or None, action_f64 or None, logp or None, mean or None, log_std or None)
         check(self.lib, self.lib.wrsn_entity_act(self._h, C.c_void_p(actors_ptr or None), C.c_void_p(agent_ptr or None), C.c_void_p(eps_ptr or None),
                                                  self._ent(ent_ptrs), C.byref(o)))
+
+    def entity_pointer_act(self, actors_ptr, agent_ptr, gumbel_ptr=0, eps_ptr=0, min_charge=0.0, ent_ptrs=None, node=0, stored=0, action=0,
+                           action_f64=0, logp=0, node_logp=0, charge_mean=0, charge_log_std=0):
+        """wrsn_entity_pointer_act: the packed node-pointer actors at actors_ptr ([M, wrsn_entity_pointer_floats()] float32) on the entity
+        rows of ent_ptrs ((node, mc, env) addresses, None = the registered buffers) for the chargers at agent_ptr; gumbel_ptr [B,N] and
+        eps_ptr [B]: 0 = the mode of that part."""
+        o = WrsnEntityPointerOut(node or None, stored or None, action or None, action_f64 or None, logp or None, node_logp or None,
+                                 charge_mean or None, charge_log_std or None)
+        check(self.lib, self.lib.wrsn_entity_pointer_act(self._h, C.c_void_p(actors_ptr or None), C.c_void_p(agent_ptr or None),
+                                                         C.c_void_p(gumbel_ptr or None), C.c_void_p(eps_ptr or None), float(min_charge),
+                                                         self._ent(ent_ptrs), C.byref(o)))
 
     def entity_heuristic_act(self, agent_ptr, ent_ptrs=None, charge_scale=1.0, action=0, action_f64=0):
         """wrsn_entity_heuristic_act: the most critical unclaimed node of every row whose charger at agent_ptr is in [0, M), from the

@@ -111,6 +111,8 @@ struct wrsn_handle {
     WrsnEntityOut ent{};            // wrsn_set_entity_out: the caller's entity-observation buffers (node == nullptr: off, the default)
     // wrsn_entity_act (allocated by its first call): the head's inputs [B, WRSN_ENTPOL_FEAT], the row lists [M, B] and counters [8] per charger
     float* ep_feat = nullptr; int32_t* ep_list = nullptr; int32_t* ep_cnt = nullptr;
+    // wrsn_entity_pointer_act (allocated by its first call): z [B, 128] and q [B, 64] between its head and score kernels; it shares the above
+    float* pp_z = nullptr; float* pp_q = nullptr;
     // wrsn_entity_eval / wrsn_entity_ppo_grad / wrsn_entity_adam: the scratch area (grown on demand, the old one kept until wrsn_destroy: launches
     // in flight may still use it) and the gradient norm of the Adam call
     float* et_scratch = nullptr; size_t et_cap = 0; float* et_norm = nullptr;
@@ -984,9 +986,47 @@ int wrsn_entity_act(wrsn_t* h, const float* actors, const int32_t* agent_id, con
     WrsnEntActOut o; o.action = out->action; o.action_f64 = out->action_f64; o.logp = out->logp; o.mean = out->mean; o.log_std = out->log_std;
     HIPCHK(hipMemsetAsync(h->ep_cnt, 0, WRSN_MAX_MC * sizeof(int32_t), h->stream));
     hipLaunchKernelGGL(wrsn_entpol_group_kernel, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, M, agent_id, h->ep_list, h->ep_cnt);
-    hipLaunchKernelGGL(wrsn_entpol_trunk_kernel, dim3(B), dim3(256), WRSN_EP_T_LDS, h->stream, B, M, h->dev.N, actors, agent_id, e, h->ep_feat);
+    hipLaunchKernelGGL(wrsn_entpol_trunk_kernel, dim3(B), dim3(256), WRSN_EP_T_LDS, h->stream, B, M, h->dev.N, actors, agent_id, e, h->ep_feat,
+                       (int)WRSN_EP_FLOATS);
     hipLaunchKernelGGL(wrsn_entpol_head_kernel, dim3((B + WRSN_EP_HEAD_ROWS - 1) / WRSN_EP_HEAD_ROWS + M), dim3(256), WRSN_EP_H_LDS, h->stream, B, M,
                        actors, (const float*)h->ep_feat, (const int32_t*)h->ep_list, (const int32_t*)h->ep_cnt, eps, o);
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+int32_t wrsn_entity_pointer_floats(void) { return WRSN_PP_FLOATS; }
+
+int wrsn_entity_pointer_act(wrsn_t* h, const float* actors, const int32_t* agent_id, const float* gumbel, const float* eps, float min_charge,
+                            const wrsn_entity_out* ent, const wrsn_entity_pointer_out* out) {
+    if (!h || !actors || !agent_id || !out || !out->node || !out->stored || !out->action || !out->logp)
+        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_act needs actors, agent_id, out->node, out->stored, out->action and out->logp");
+    if (!(min_charge >= 0.f && min_charge < 1.f)) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_act: min_charge must lie in [0, 1)");   // a NaN fails both
+    WrsnEntityOut e{};
+    { const int rc = entity_in(h, ent, &e); if (rc) return rc; }
+    if ((uintptr_t)actors % 16) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_act: actors must be 16-byte aligned");
+    WRSN_ON_DEVICE(h);
+    const int B = h->dev.B, M = h->dev.M, N = h->dev.N;
+    if (!h->ep_cnt) {                                         // the scratch of wrsn_entity_act: the two calls share it, in stream order
+        int rc = dalloc(h, &h->ep_feat, (size_t)B * WRSN_ENTPOL_FEAT);
+        if (!rc) rc = dalloc(h, &h->ep_list, (size_t)B * M);
+        if (!rc) rc = dalloc(h, &h->ep_cnt, (size_t)WRSN_MAX_MC);
+        if (rc) return rc;
+    }
+    if (!h->pp_z) {
+        int rc = dalloc(h, &h->pp_z, (size_t)B * 128);
+        if (!rc) rc = dalloc(h, &h->pp_q, (size_t)B * 64);
+        if (rc) return rc;
+    }
+    WrsnEntPtrOut o; o.node = out->node; o.stored = out->stored; o.action = out->action; o.action_f64 = out->action_f64; o.logp = out->logp;
+    o.node_logp = out->node_logp; o.charge_mean = out->charge_mean; o.charge_log_std = out->charge_log_std;
+    HIPCHK(hipMemsetAsync(h->ep_cnt, 0, WRSN_MAX_MC * sizeof(int32_t), h->stream));
+    hipLaunchKernelGGL(wrsn_entpol_group_kernel, dim3((B + 63) / 64), dim3(64), 0, h->stream, B, M, agent_id, h->ep_list, h->ep_cnt);
+    hipLaunchKernelGGL(wrsn_entpol_trunk_kernel, dim3(B), dim3(256), WRSN_EP_T_LDS, h->stream, B, M, N, actors, agent_id, e, h->ep_feat,
+                       (int)WRSN_PP_FLOATS);
+    hipLaunchKernelGGL(wrsn_entptr_head_kernel, dim3((B + WRSN_EP_HEAD_ROWS - 1) / WRSN_EP_HEAD_ROWS + M), dim3(256), WRSN_EP_H_LDS, h->stream, B, M,
+                       actors, (const float*)h->ep_feat, (const int32_t*)h->ep_list, (const int32_t*)h->ep_cnt, h->pp_z, h->pp_q);
+    hipLaunchKernelGGL(wrsn_entptr_score_kernel, dim3(B), dim3(256), WRSN_PP_SCORE_LDS(N), h->stream, B, M, N, actors, agent_id, e,
+                       (const float*)h->pp_z, (const float*)h->pp_q, gumbel, eps, min_charge, o);
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }

@@ -374,7 +374,8 @@ __global__ void __launch_bounds__(64) wrsn_entpol_group_kernel(int B, int M, con
 }
 
 __global__ void __launch_bounds__(256) wrsn_entpol_trunk_kernel(int B, int M, int N, const float* __restrict__ actors,
-                                                                const int32_t* __restrict__ agent_id, WrsnEntityOut ent, float* __restrict__ feat) {
+                                                                const int32_t* __restrict__ agent_id, WrsnEntityOut ent, float* __restrict__ feat,
+                                                                int stride) {   // floats from one charger's block to the next: the trunk leads every actor block
     extern __shared__ double smem[];
     float* sW = (float*)smem;
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
@@ -382,7 +383,7 @@ __global__ void __launch_bounds__(256) wrsn_entpol_trunk_kernel(int B, int M, in
     if (e >= B) return;
     const int aid = wrsn_wave_first(agent_id[e]);
     if (aid < 0 || aid >= M) return;
-    const float* blk = actors + (size_t)aid * WRSN_EP_FLOATS;
+    const float* blk = actors + (size_t)aid * stride;
     {   // node1, node2 and their biases: 1 184 chunks of 16 bytes
         const auto src = wrsn_global((const WrsnU4*)blk);
         WrsnU4* dst = (WrsnU4*)sW;
@@ -493,15 +494,16 @@ __global__ void __launch_bounds__(256) wrsn_entpol_trunk_kernel(int B, int M, in
     }
 }
 
-__global__ void __launch_bounds__(256) wrsn_entpol_head_kernel(int B, int M, const float* __restrict__ actors, const float* __restrict__ feat,
-                                                               const int32_t* __restrict__ list, const int32_t* __restrict__ cnt,
-                                                               const float* __restrict__ eps, WrsnEntActOut out) {
-    extern __shared__ double smem[];
-    float* sF = (float*)smem;
-    float* sZ = sF + WRSN_EP_H_Z;
+// The front of a head block, shared by wrsn_entpol_head_kernel and wrsn_entptr_head_kernel: which (charger, tile of <= 32 of its rows) the
+// block is -- the tiles of charger 0, then of charger 1, ... --, then head1 and head2 of the block at `actors + a * stride` on that tile.
+// false (block-uniform): more blocks than tiles.  On return sF holds ReLU(head2(ReLU(head1(features)))) as [128 units][32 columns];
+// a column beyond `rows` repeats the last row.  Ends in a __syncthreads.
+WDEV bool wrsn_ep_head_front(int B, int M, int stride, const float* __restrict__ actors, const float* __restrict__ feat,
+                             const int32_t* __restrict__ list, const int32_t* __restrict__ cnt, float* sF, float* sZ, int& rows,
+                             const int32_t*& mine, const float*& blk) {
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
-    // which (charger, tile) this block is: the tiles of charger 0, then of charger 1, ...
-    int b = (int)blockIdx.x, a = -1, rows = 0, first = 0;
+    int b = (int)blockIdx.x, a = -1, first = 0;
+    rows = 0;
     for (int c = 0; c < M; ++c) {
         int k = cnt[c]; k = k < 0 ? 0 : (k > B ? B : k);
         const int nt = (k + WRSN_EP_HEAD_ROWS - 1) / WRSN_EP_HEAD_ROWS;
@@ -510,9 +512,9 @@ __global__ void __launch_bounds__(256) wrsn_entpol_head_kernel(int B, int M, con
             else b -= nt;
         }
     }
-    if (a < 0) return;                                        // block-uniform: more blocks than tiles
-    const int32_t* mine = list + (size_t)a * B + first;
-    const float* blk = actors + (size_t)a * WRSN_EP_FLOATS;
+    if (a < 0) return false;
+    mine = list + (size_t)a * B + first;
+    blk = actors + (size_t)a * stride;
     for (int i = tid; i < WRSN_EP_HEAD_ROWS * WRSN_ENTPOL_FEAT; i += 256) {   // a column beyond `rows` repeats the last row: computed, not stored
         const int j = i / WRSN_ENTPOL_FEAT, k = i - j * WRSN_ENTPOL_FEAT;
         const int row = mine[j < rows ? j : rows - 1];
@@ -543,6 +545,18 @@ __global__ void __launch_bounds__(256) wrsn_entpol_head_kernel(int B, int M, con
         for (int r = 0; r < 16; ++r) sF[(32 * wave + wrsn_ep_unit(r, h)) * 32 + col] = fmaxf(acc[r], 0.f);   // the feature tile is dead
     }
     __syncthreads();
+    return true;
+}
+
+__global__ void __launch_bounds__(256) wrsn_entpol_head_kernel(int B, int M, const float* __restrict__ actors, const float* __restrict__ feat,
+                                                               const int32_t* __restrict__ list, const int32_t* __restrict__ cnt,
+                                                               const float* __restrict__ eps, WrsnEntActOut out) {
+    extern __shared__ double smem[];
+    float* sF = (float*)smem;
+    float* sZ = sF + WRSN_EP_H_Z;
+    const int tid = (int)threadIdx.x;
+    int rows; const int32_t* mine; const float* blk;
+    if (!wrsn_ep_head_front(B, M, WRSN_EP_FLOATS, actors, feat, list, cnt, sF, sZ, rows, mine, blk)) return;   // block-uniform
     if (tid < 192) {                                          // six dot products per column: thread (d, j); four k-ordered chains over k mod 4, the
         const int j = tid & 31, d = tid >> 5;                 // bias in the first, added as (0 + 1) + (2 + 3): a quarter of the chain length
         const float* w = blk + (d < 3 ? WRSN_EP_MEAN + d : WRSN_EP_LSTD + d - 3);
@@ -654,6 +668,234 @@ __global__ void __launch_bounds__(64 * WRSN_ENT_ROWS) wrsn_entity_heuristic_kern
     float* o = action + (size_t)e * 3;
     o[0] = x; o[1] = y; o[2] = t;
     if (action_f64) { double* d = action_f64 + (size_t)e * 3; d[0] = (double)x; d[1] = (double)y; d[2] = (double)t; }
+}
+
+// ------------------------------------------------------------------ node-pointer entity policy: acting (wrsn_entity_pointer_act)
+// The actor of build_entity_pointer_networks (ippo.py): the trunk of the set policy, a categorical choice of ONE alive node by a score per
+// node, and a charge head on the chosen node's features.  The query needs z, z needs the pools over all nodes: the nodes are visited
+// twice.  Four launches on the handle's stream:
+//   wrsn_entpol_group_kernel   as for wrsn_entity_act
+//   wrsn_entpol_trunk_kernel   as for wrsn_entity_act, with the pointer block's stride -> feat[e][200]
+//   wrsn_entptr_head_kernel    head1, head2 (wrsn_ep_head_front), then query 128 -> 64 on the matrix cores by waves 0 and 1 -> z[e][128], q[e][64]
+//   wrsn_entptr_score_kernel   one 256-thread block per row: h_i recomputed tile by tile exactly as the trunk kernel does and never stored;
+//                              l_i = 0.125 <h_i, q> into LDS; then maximum, arg-max of l_i + g_i, log-sum-exp, the charge head, the outputs
+// The bits of l_i do not depend on the tile, wave or column of node i: a column's MFMA chains are k-ordered whatever the column, the dot
+// product with q is ONE fmaf chain over the lane's 32 units in (t2, r) order, and the two half-lanes of a column are added as
+// (units of half 0) + (units of half 1) in both.  Every reduction over the nodes is either exact (maximum; minimum index among the holders
+// of the maximum, as wrsn_entity_heuristic_kernel) or a sum in a fixed order: thread t adds nodes t, t + 256, ... in order, a __shfl_xor
+// butterfly adds the lanes (both partners add the same two numbers), the four waves are added in wave order.  No DPP row operation: the
+// emulator of tests/emu models those for one-wave blocks only.
+#define WRSN_PP_QUERY WRSN_EP_MEAN                                                 // query  128 ->  64: where the Gaussian heads of the set actor sit
+#define WRSN_PP_QUERY_B (WRSN_PP_QUERY + 128 * 64)
+#define WRSN_PP_CHARGE_IN (128 + WRSN_ENT_NODE_F)
+#define WRSN_PP_CHARGE (WRSN_PP_QUERY_B + 64)                                      // charge 136 ->   2: rows z [128], then the chosen node's features [8]
+#define WRSN_PP_CHARGE_B (WRSN_PP_CHARGE + WRSN_PP_CHARGE_IN * 2)
+#define WRSN_PP_FLOATS ((WRSN_PP_CHARGE_B + 2 + 3) / 4 * 4)                        // rounded up to a multiple of 4
+static_assert(WRSN_PP_QUERY == 48448 && WRSN_PP_QUERY_B == 56640 && WRSN_PP_CHARGE == 56704 && WRSN_PP_CHARGE_B == 56976 && WRSN_PP_FLOATS == 56980,
+              "the layout documented in include/wrsn_hip.h");
+static_assert(WRSN_PP_CHARGE_IN % 4 == 0, "the charge head runs four chains over k mod 4");
+// LDS of the score block, in floats: node1 / node2 with their biases, q [64], z [128], the reduction slots [16], l [N rounded up to whole tiles]
+#define WRSN_PP_S_Q WRSN_EP_MC1
+#define WRSN_PP_S_Z (WRSN_PP_S_Q + 64)
+#define WRSN_PP_S_RED (WRSN_PP_S_Z + 128)
+#define WRSN_PP_S_L (WRSN_PP_S_RED + 16)
+#define WRSN_PP_SCORE_LDS(N) ((size_t)(WRSN_PP_S_L + (((N) + 31) & ~31)) * 4)     // bytes
+
+struct WrsnEntPtrOut { int32_t* node; float* stored; float* action; double* action_f64; float* logp; float* node_logp; float* charge_mean; float* charge_log_std; };   // mirrors wrsn_entity_pointer_out
+
+__global__ void __launch_bounds__(256) wrsn_entptr_head_kernel(int B, int M, const float* __restrict__ actors, const float* __restrict__ feat,
+                                                               const int32_t* __restrict__ list, const int32_t* __restrict__ cnt,
+                                                               float* __restrict__ zbuf, float* __restrict__ qbuf) {
+    extern __shared__ double smem[];
+    float* sF = (float*)smem;
+    float* sZ = sF + WRSN_EP_H_Z;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
+    int rows; const int32_t* mine; const float* blk;
+    if (!wrsn_ep_head_front(B, M, WRSN_PP_FLOATS, actors, feat, list, cnt, sF, sZ, rows, mine, blk)) return;   // block-uniform
+    for (int i = tid; i < rows * 128; i += 256) {             // z = sF [128 units][32 columns], row by row
+        const int j = i >> 7, u = i & 127;
+        zbuf[(size_t)mine[j] * 128 + u] = sF[u * 32 + j];
+    }
+    if (wave < 2) {                                           // query: wave w holds units 32 w .. 32 w + 31 of all 32 columns (wave-uniform)
+        wrsn_v16f acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = blk[WRSN_PP_QUERY_B + 32 * wave + wrsn_ep_unit(r, h)];
+        const float* wa = blk + WRSN_PP_QUERY + h * 64 + 32 * wave + col;
+        const float* xb = sF + h * 32 + col;
+#pragma unroll 8
+        for (int kk = 0; kk < 64; ++kk) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[kk * 128], xb[kk * 64], acc, 0, 0, 0);
+        if (col < rows) {
+            float* q = qbuf + (size_t)mine[col] * 64 + 32 * wave;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) q[wrsn_ep_unit(r, h)] = acc[r];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) wrsn_entptr_score_kernel(int B, int M, int N, const float* __restrict__ actors,
+                                                                const int32_t* __restrict__ agent_id, WrsnEntityOut ent,
+                                                                const float* __restrict__ zbuf, const float* __restrict__ qbuf,
+                                                                const float* __restrict__ gumbel, const float* __restrict__ eps,
+                                                                float min_charge, WrsnEntPtrOut out) {
+    extern __shared__ double smem[];
+    float* sW = (float*)smem;
+    float* sQ = sW + WRSN_PP_S_Q;
+    float* sZ = sW + WRSN_PP_S_Z;
+    float* sR = sW + WRSN_PP_S_RED;
+    int* sK = (int*)sR;                                       // the index slots of the reductions
+    float* sL = sW + WRSN_PP_S_L;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
+    const int e = (int)blockIdx.x;
+    if (e >= B) return;
+    const int aid = wrsn_wave_first(agent_id[e]);
+    if (aid < 0 || aid >= M) return;
+    const float* blk = actors + (size_t)aid * WRSN_PP_FLOATS;
+    {   // node1, node2 and their biases, as the trunk kernel stages them
+        const auto src = wrsn_global((const WrsnU4*)blk);
+        WrsnU4* dst = (WrsnU4*)sW;
+        for (int i = tid; i < WRSN_EP_MC1 / 4; i += 256) dst[i] = wrsn_ld_u4(src + i);
+    }
+    if (tid < 64) sQ[tid] = qbuf[(size_t)e * 64 + tid];
+    else if (tid < 192) sZ[tid - 64] = zbuf[(size_t)e * 128 + tid - 64];
+    __syncthreads();
+    const float ninf = -__builtin_inff();
+    const float* nrow = ent.node + (size_t)e * N * WRSN_ENT_NODE_F;
+    const int ntile = (N + 31) >> 5;
+    for (int tile = wave; tile < ((ntile + 3) & ~3); tile += 4) {   // every wave the same number of rounds: the exchange below is one
+        const bool on = tile < ntile;                          // wave-uniform
+        const int n = tile * 32 + col, srcn = n < N ? n : N - 1;   // clamped: a column beyond N is computed on zeros and stored nowhere
+        const auto p = wrsn_global((const WrsnU4*)(nrow + (size_t)srcn * WRSN_ENT_NODE_F));
+        const WrsnU4 c0 = wrsn_ld_u4(p), c1 = wrsn_ld_u4(p + 1);
+        const bool alive = n < N && __int_as_float((int)c1.w) == 1.f;
+        float x[4];                                           // features 2 kk + h of the column, zeros unless the node is alive (a select)
+        x[0] = __int_as_float((int)(h ? c0.y : c0.x)); x[1] = __int_as_float((int)(h ? c0.w : c0.z));
+        x[2] = __int_as_float((int)(h ? c1.y : c1.x)); x[3] = __int_as_float((int)(h ? c1.w : c1.z));
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) x[kk] = alive ? x[kk] : 0.f;
+        float part = 0.f;                                     // <h_i, q> over this lane's 32 units: 32 t2 + u(r) + 4 h
+        if (on) {
+            wrsn_v16f h1[2];
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                wrsn_v16f acc;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] = sW[WRSN_EP_NODE1_B + 32 * t + wrsn_ep_unit(r, h)];
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk)
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sW[WRSN_EP_NODE1 + (2 * kk + h) * 64 + 32 * t + col], x[kk], acc, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) h1[t][r] = fmaxf(acc[r], 0.f);
+            }
+#pragma unroll
+            for (int t2 = 0; t2 < 2; ++t2) {
+                wrsn_v16f acc;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[r] = sW[WRSN_EP_NODE2_B + 32 * t2 + wrsn_ep_unit(r, h)];
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)              // register r of h1[t]: the k-pair (u, u + 4), u = 32 t + (r & 3) + 8 (r >> 2)
+                        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sW[WRSN_EP_NODE2 + (32 * t + wrsn_ep_unit(r, h)) * 64 + 32 * t2 + col], h1[t][r], acc, 0, 0, 0);
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) part = fmaf(fmaxf(acc[r], 0.f), sQ[32 * t2 + wrsn_ep_unit(r, h)], part);
+            }
+        }
+        const float other = __shfl_xor(part, 32);             // the column's other half: both halves form (half 0) + (half 1)
+        const float l = 0.125f * ((h ? other : part) + (h ? part : other));
+        if (on && h == 0 && n < N) sL[n] = (alive && l > ninf) ? l : ninf;   // a select: whatever a dead or padded node row holds never enters; -inf IS "not alive" below
+    }
+    __syncthreads();
+    // ---- over the alive nodes: the maximum of l and the maximum of l + g -- thread t takes nodes t, t + 256, ...
+    const float* grow = gumbel ? gumbel + (size_t)e * N : nullptr;
+    float mx = ninf, bs = ninf;
+    for (int n = tid; n < N; n += 256) {
+        const float l = sL[n];
+        if (!(l > ninf)) continue;                            // -inf marks a node that is not alive: the flag is not read again
+        mx = l > mx ? l : mx;
+        const float sc = grow ? l + grow[n] : l;
+        const float s = sc > ninf ? sc : ninf;                // a NaN never beats a number
+        bs = s > bs ? s : bs;
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const float o = __shfl_xor(mx, d); mx = o > mx ? o : mx;
+        const float b = __shfl_xor(bs, d); bs = b > bs ? b : bs;
+    }
+    if (lane == 0) { sR[wave] = mx; sR[4 + wave] = bs; }
+    __syncthreads();
+    const float m_all = fmaxf(fmaxf(sR[0], sR[1]), fmaxf(sR[2], sR[3]));
+    const float b_all = fmaxf(fmaxf(sR[4], sR[5]), fmaxf(sR[6], sR[7]));
+    // ---- the lowest index among the holders of the best score; the sum of exp(l - max) in a fixed order
+    float sum = 0.f; int k = WRSN_EH_NONE;
+    for (int n = tid; n < N; n += 256) {
+        const float l = sL[n];
+        if (!(l > ninf)) continue;
+        sum += expf(l - m_all);
+        const float sc = grow ? l + grow[n] : l;
+        const float s = sc > ninf ? sc : ninf;
+        if (k == WRSN_EH_NONE && s == b_all) k = n;           // increasing n: the lane's lowest
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        sum += __shfl_xor(sum, d);
+        const int o = __shfl_xor(k, d); k = o < k ? o : k;
+    }
+    if (lane == 0) { sR[8 + wave] = sum; sK[12 + wave] = k; }
+    __syncthreads();
+    const float s_all = ((sR[8] + sR[9]) + sR[10]) + sR[11];
+    int node = sK[12];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) node = sK[12 + w] < node ? sK[12 + w] : node;
+    const bool any = node != WRSN_EH_NONE;                    // block-uniform: some node is alive
+    const float lse = m_all + logf(s_all);                    // used only when `any`
+    if (out.node_logp) {
+        float* o = out.node_logp + (size_t)e * N;
+        for (int n = tid; n < N; n += 256) o[n] = sL[n] > ninf ? sL[n] - lse : ninf;
+    }
+    // ---- the charge head on [z, x_k]: thread d = 0 (mean), 1 (log_std); four k-ordered chains over k mod 4, added as (0 + 1) + (2 + 3)
+    if (tid < 2) {
+        const float* w = blk + WRSN_PP_CHARGE + tid;
+        const float* z = sZ;
+        const float* xk = nrow + (size_t)(any ? node : 0) * WRSN_ENT_NODE_F;
+        float s0 = blk[WRSN_PP_CHARGE_B + tid], s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll 4
+        for (int i = 0; i < 128; i += 4) {
+            s0 = fmaf(z[i], w[2 * i], s0); s1 = fmaf(z[i + 1], w[2 * i + 2], s1);
+            s2 = fmaf(z[i + 2], w[2 * i + 4], s2); s3 = fmaf(z[i + 3], w[2 * i + 6], s3);
+        }
+#pragma unroll
+        for (int i = 0; i < WRSN_ENT_NODE_F; i += 4) {        // the chosen node's own features; zeros when no node is alive (a select)
+            const float* wn = w + 2 * (128 + i);
+            s0 = fmaf(any ? xk[i] : 0.f, wn[0], s0); s1 = fmaf(any ? xk[i + 1] : 0.f, wn[2], s1);
+            s2 = fmaf(any ? xk[i + 2] : 0.f, wn[4], s2); s3 = fmaf(any ? xk[i + 3] : 0.f, wn[6], s3);
+        }
+        sR[tid] = (s0 + s1) + (s2 + s3);                      // the maxima of sR[0..7] were read before the last barrier
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    const float mu = sR[0], ls = fminf(fmaxf(sR[1], -4.f), 1.f);
+    const float ep = eps ? eps[e] : 0.f;
+    const float x = fmaf(expf(ls), ep, mu);
+    const float c = min_charge + (1.f - min_charge) * (1.f / (1.f + expf(-x)));
+    float u, v;
+    if (any) { u = nrow[(size_t)node * WRSN_ENT_NODE_F]; v = nrow[(size_t)node * WRSN_ENT_NODE_F + 1]; }
+    else {                                                    // the asking charger's own position: the heuristic's rule
+        const float* mc = ent.mc + (size_t)e * M * WRSN_ENT_MC_F;
+        int self = aid;
+        for (int o = M - 1; o >= 0; --o) if (mc[o * WRSN_ENT_MC_F + 3] == 1.f) self = o;
+        u = mc[self * WRSN_ENT_MC_F]; v = mc[self * WRSN_ENT_MC_F + 1];
+    }
+    const int kout = any ? node : -1;
+    const float lp = (any ? sL[node] - lse : 0.f) + (-0.5f * ep * ep - ls - 0.9189385f);   // 0.5 log(2 pi)
+    out.node[e] = kout;
+    out.stored[(size_t)e * 2] = (float)kout; out.stored[(size_t)e * 2 + 1] = x;
+    float* a = out.action + (size_t)e * 3;
+    a[0] = u; a[1] = v; a[2] = c;
+    if (out.action_f64) { double* d = out.action_f64 + (size_t)e * 3; d[0] = (double)u; d[1] = (double)v; d[2] = (double)c; }
+    out.logp[e] = lp;
+    if (out.charge_mean) out.charge_mean[e] = mu;
+    if (out.charge_log_std) out.charge_log_std[e] = ls;
 }
 
 // ------------------------------------------------------------------ episode ledger (wrsn_episodes_collect)

@@ -5,7 +5,8 @@ and would otherwise return at the same instant forever), parks an environment on
 launch and the restart mask; the host reads one flag every `poll` launches.
 
 Policies are callables `policy(env, ids) -> float64 [B, 3]` (rows with ids outside [0, M) are ignored by `env.step`):
-`EntityPolicy` (the learned set policy through `wrsn_entity_act`, its mode or a sample), `HeuristicPolicy` (the deterministic baseline of
+`EntityPolicy` (the learned set policy through `wrsn_entity_act`, its mode or a sample), `PointerPolicy` (the learned node-pointer
+policy through `wrsn_entity_pointer_act`, likewise), `HeuristicPolicy` (the deterministic baseline of
 `wrsn_entity_heuristic_act`) and `UniformPolicy` (`torch.rand`)."""
 import numpy as np
 
@@ -28,6 +29,25 @@ class EntityPolicy:
             t = env.torch
             eps = t.randn((env.num_env, 3), dtype=t.float32, device=env.device, generator=self.generator)
         return env.entity_act(ids, self.packed, eps)[1]
+
+
+class PointerPolicy:
+    """The node-pointer actors `packed_actors` ([M, P], `EntityPointerPPOLearner.packed_actors()`) through `VecWRSN.entity_pointer_act`:
+    the most probable node and the mode of the charge variable (`deterministic=True`), or a sample with Gumbel noise -log(-log(u)), u
+    from `torch.rand`, and `torch.randn` draws of `generator`.  The third component of every action is at least `min_charge`: with
+    min_charge > 0 every decision spends simulated time, so the policy cannot stand still."""
+
+    def __init__(self, packed_actors, deterministic=True, generator=None, min_charge=0.02):
+        self.packed, self.deterministic, self.generator, self.min_charge = packed_actors, bool(deterministic), generator, float(min_charge)
+
+    def __call__(self, env, ids):
+        g = eps = None
+        if not self.deterministic:
+            t = env.torch
+            u = t.rand((env.num_env, env.n_node), dtype=t.float32, device=env.device, generator=self.generator)
+            g = -t.log(-t.log(u))
+            eps = t.randn((env.num_env,), dtype=t.float32, device=env.device, generator=self.generator)
+        return env.entity_pointer_act(ids, self.packed, g, eps, self.min_charge)[1]
 
 
 class HeuristicPolicy:

@@ -740,13 +740,8 @@ class EntityTransitionBuffers(_TransitionBuffers):
         self._collect(self.env._h.rollout_collect_entities, None, consume)
 
 
-def build_entity_networks(n_agent_rows):
-    """Returns (EntityActor, EntityCritic) classes over packed entity rows [n, R] of `n_agent_rows` chargers (the node count follows
-    from R).  A set policy: a per-node MLP pooled by masked mean and masked max over the live nodes, a per-charger MLP pooled by
-    masked mean plus the asking charger's own embedding, and a head over the pools and the environment row.  No BatchNorm and no other
-    operation across rows: a row's output does not depend on the batch it is evaluated in, so the log-probabilities of the roll-out and of
-    the update agree.  Dead and padded node rows have no influence whatever they hold: their inputs are replaced by zeros and their
-    embeddings masked out of both pools; a row without a live node pools to zeros."""
+def _entity_parts(n_agent_rows):
+    """(torch, lin, _Trunk): what the entity networks of `n_agent_rows` chargers share -- the row-wise Linear and the trunk class."""
     torch = _torch()
     nn = torch.nn
     F = torch.nn.functional
@@ -768,10 +763,18 @@ def build_entity_networks(n_agent_rows):
             self.head1 = _ortho(nn.Linear(64 + 64 + 32 + 32 + _lib.ENT_ENV_F, 128)); self.head2 = _ortho(nn.Linear(128, 128))
 
         def forward(self, rows):
+            return self.embed(rows)[0]
+
+        def embed(self, rows):
+            """(z [n, 1, 128], the node embeddings h [n, N, 64], alive [n, N], and the views nodes, mcs, env of `rows`)."""
             nodes, mcs, env = EntityTransitionBuffers.split(rows, M)
             alive = nodes[..., n_alive] == 1                                             # [n, N]
             x = torch.where(alive.unsqueeze(-1), nodes, torch.zeros_like(nodes))       # a select, not a product: NaN / inf in a dead row vanish too
             h = F.relu(lin(self.node2, F.relu(lin(self.node1, x))))
+            z = self._head(h, alive, nodes, mcs, env)
+            return z, h, alive, nodes, mcs, env
+
+        def _head(self, h, alive, nodes, mcs, env):
             w = alive.unsqueeze(-1).to(h.dtype)
             cnt = w.sum(1)                                                               # [n, 1] live nodes of the row
             mean = (h * w).sum(1) / cnt.clamp(min=1.0)
@@ -785,6 +788,19 @@ def build_entity_networks(n_agent_rows):
             scale[e_agent] = 1.0 / M; scale[e_nnode] = 1.0 / max(1, nodes.shape[1])
             x = torch.cat([mean, mx, cmean, own, env * scale], 1).unsqueeze(1)
             return F.relu(lin(self.head2, F.relu(lin(self.head1, x))))               # [n, 1, 128]: the heads go on row by row
+
+    return torch, lin, _Trunk
+
+
+def build_entity_networks(n_agent_rows):
+    """Returns (EntityActor, EntityCritic) classes over packed entity rows [n, R] of `n_agent_rows` chargers (the node count follows
+    from R).  A set policy: a per-node MLP pooled by masked mean and masked max over the live nodes, a per-charger MLP pooled by
+    masked mean plus the asking charger's own embedding, and a head over the pools and the environment row.  No BatchNorm and no other
+    operation across rows: a row's output does not depend on the batch it is evaluated in, so the log-probabilities of the roll-out and of
+    the update agree.  Dead and padded node rows have no influence whatever they hold: their inputs are replaced by zeros and their
+    embeddings masked out of both pools; a row without a live node pools to zeros."""
+    torch, lin, _Trunk = _entity_parts(n_agent_rows)
+    nn = torch.nn
 
     class EntityActor(nn.Module):
         """Packed rows [n, R] -> (mean [n, 3], log_std [n, 3]) of a diagonal Gaussian over the action vector; log_std in [-4, 1]."""
@@ -811,6 +827,137 @@ def build_entity_networks(n_agent_rows):
             return lin(self.value, self.trunk(rows)).squeeze(1)
 
     return EntityActor, EntityCritic
+
+
+LOG_SQRT_2PI = 0.5 * math.log(2.0 * math.pi)
+
+
+def build_entity_pointer_networks(n_agent_rows):
+    """Returns (EntityPointerActor, EntityCritic) classes over packed entity rows [n, R] of `n_agent_rows` chargers; the critic is the
+    class `build_entity_networks` returns.  The actor names a node: on the set policy's trunk (z [n, 128] and the per-node embeddings
+    h [n, N, 64]) a query q = query(z) scores every alive node, l_i = 0.125 <h_i, q>, the decision is one alive node k drawn from
+    softmax(l) and a charge variable x ~ N(mu, exp(log_std)) with (mu, log_std) = charge([z, the chosen node's eight features]); the
+    action is (u_k, v_k, min_charge + (1 - min_charge) sigmoid(x)).  A row with no alive node has k = -1, no node term in
+    log-probability and entropy, zeros for the node's features and the asking charger's own position as destination.  Like the set
+    policy, nothing couples the rows of a batch (`lin` / `bmm`), and dead or padded node rows have no influence whatever they hold."""
+    torch, lin, _Trunk = _entity_parts(n_agent_rows)
+    nn = torch.nn
+    M = int(n_agent_rows)
+    c_self, e_agent = _lib.ENT_MC["is_self"], _lib.ENT_ENV["agent"]
+    _, EntityCritic = build_entity_networks(n_agent_rows)
+
+    class EntityPointerActor(nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.trunk = _Trunk()
+            self.query = _ortho(nn.Linear(128, 64), std=0.01)
+            self.charge = _ortho(nn.Linear(128 + _lib.ENT_NODE_F, 2), std=0.01)
+
+        def scores(self, rows):
+            """(z [n, 1, 128], logits l [n, N] with -inf for nodes that are not alive, node_logp [n, N] likewise, alive [n, N], the views
+            nodes, mcs, env of `rows`).  Every -inf is put in by a select on finite numbers: no NaN, forward or backward."""
+            z, h, alive, nodes, mcs, env = self.trunk.embed(rows)
+            q = lin(self.query, z)                                                       # [n, 1, 64]
+            raw = 0.125 * torch.bmm(h, q.transpose(1, 2)).squeeze(2)                     # [n, N], finite everywhere: h of a dead node comes from zeros
+            ninf = torch.full_like(raw, float("-inf"))
+            any_alive = alive.any(1, keepdim=True)
+            m = torch.where(any_alive, torch.where(alive, raw, ninf).max(1, keepdim=True).values.detach(), torch.zeros_like(raw[:, :1]))
+            ex = torch.where(alive, (torch.where(alive, raw, m) - m).exp(), torch.zeros_like(raw))
+            s = ex.sum(1, keepdim=True)
+            lse = m + torch.where(any_alive, s, torch.ones_like(s)).log()
+            return z, torch.where(alive, raw, ninf), torch.where(alive, raw - lse, ninf), alive, nodes, mcs, env
+
+        @staticmethod
+        def choose(logits, alive, gumbel=None):
+            """k [n] = the alive node with the largest l + g (g None: l alone, the mode), the lowest index among equal scores; -1 when no
+            node is alive."""
+            N = logits.shape[1]
+            sc = logits if gumbel is None else logits + gumbel.to(logits.dtype)
+            sc = torch.where(alive & (sc > float("-inf")), sc, torch.full_like(sc, float("-inf")))      # a NaN never beats a number
+            best = sc.max(1, keepdim=True).values
+            idx = torch.arange(N, device=logits.device).expand_as(sc)
+            k = torch.where(alive & (sc == best), idx, torch.full_like(idx, N)).min(1).values
+            return torch.where(k < N, k, torch.full_like(k, -1))
+
+        def charge_head(self, z, nodes, k):
+            """(mu [n], log_std [n] in [-4, 1], x_k [n, 8]) of the charge variable for the chosen nodes k [n] (-1: zeros for x_k)."""
+            has = (k >= 0).unsqueeze(1)
+            xk = nodes.gather(1, k.clamp(min=0).view(-1, 1, 1).expand(-1, 1, nodes.shape[2])).squeeze(1)
+            xk = torch.where(has, xk, torch.zeros_like(xk))
+            out = lin(self.charge, torch.cat([z, xk.unsqueeze(1)], 2)).squeeze(1)
+            return out[:, 0], out[:, 1].clamp(-4.0, 1.0), xk
+
+        @staticmethod
+        def destination(nodes, mcs, env, k):
+            """(u, v) [n, 2] of the decision: the chosen node's position; for k = -1 the asking charger's own -- the lowest-index charger
+            row with is_self == 1, else the row the environment row names."""
+            n = nodes.shape[0]
+            is_self = mcs[..., c_self] == 1
+            idx = torch.arange(M, device=nodes.device).expand(n, M)
+            first = torch.where(is_self, idx, torch.full_like(idx, M)).min(1).values
+            agent = torch.nan_to_num(env[:, e_agent]).long().clamp(0, M - 1)
+            me = torch.where(first < M, first, agent)
+            own = mcs.gather(1, me.view(-1, 1, 1).expand(-1, 1, mcs.shape[2])).squeeze(1)[:, :2]
+            at = nodes.gather(1, k.clamp(min=0).view(-1, 1, 1).expand(-1, 1, nodes.shape[2])).squeeze(1)[:, :2]
+            return torch.where((k >= 0).unsqueeze(1), at, own)
+
+        def act(self, rows, gumbel=None, eps=None, min_charge=0.0):
+            """Draw a decision per row: dict of node [n], x [n], logp [n], action [n, 3], node_logp [n, N], mean [n], log_std [n]."""
+            z, l, nlp, alive, nodes, mcs, env = self.scores(rows)
+            k = self.choose(l, alive, gumbel)
+            mu, ls, _ = self.charge_head(z, nodes, k)
+            ep = torch.zeros_like(mu) if eps is None else eps.to(mu.dtype)
+            x = mu + ls.exp() * ep
+            c = min_charge + (1.0 - min_charge) * torch.sigmoid(x)
+            lp = self._node_term(nlp, k) + (-0.5 * ep * ep - ls - LOG_SQRT_2PI)
+            return dict(node=k, x=x, logp=lp, action=torch.cat([self.destination(nodes, mcs, env, k), c.unsqueeze(1)], 1), node_logp=nlp,
+                        mean=mu, log_std=ls)
+
+        @staticmethod
+        def _node_term(nlp, k):
+            picked = torch.where(nlp > float("-inf"), nlp, torch.zeros_like(nlp)).gather(1, k.clamp(min=0).unsqueeze(1)).squeeze(1)
+            return torch.where(k >= 0, picked, torch.zeros_like(picked))
+
+        def forward(self, rows, node, x):
+            """(log-probability [n], entropy [n]) of the decisions (node [n] integer, -1: none; x [n]) on `rows`."""
+            z, l, nlp, alive, nodes, mcs, env = self.scores(rows)
+            k = node.long()
+            mu, ls, _ = self.charge_head(z, nodes, k)
+            ep = (x.to(mu.dtype) - mu) / ls.exp()
+            lp = self._node_term(nlp, k) + (-0.5 * ep * ep - ls - LOG_SQRT_2PI)
+            safe = torch.where(alive, nlp, torch.zeros_like(nlp))
+            ent = -(torch.where(alive, safe.exp(), torch.zeros_like(safe)) * safe).sum(1) + ls + 0.5 + LOG_SQRT_2PI
+            return lp, ent
+
+    return EntityPointerActor, EntityCritic
+
+
+def _pointer_layers(actor):
+    t = actor.trunk
+    return (t.node1, t.node2, t.mc1, t.mc2, t.head1, t.head2, actor.query, actor.charge)
+
+
+def pack_entity_pointer_actor(actor):
+    """The `EntityPointerActor` as the float32 block `wrsn_entity_pointer_act` reads (layout: include/wrsn_hip.h): the trunk at the offsets
+    of the set actor's block, then query and charge, every Linear transposed to [in, out] and followed by its bias, zeros up to a
+    multiple of 4 floats (56 980).  A new tensor [P] on the actor's device; it does not follow later changes of the parameters."""
+    torch = _torch()
+    parts = []
+    for layer in _pointer_layers(actor):
+        parts += [layer.weight.detach().t().reshape(-1), layer.bias.detach().reshape(-1)]
+    flat = torch.cat([p.to(torch.float32) for p in parts])
+    return torch.cat([flat, flat.new_zeros((-flat.numel()) % 4)])
+
+
+def unpack_entity_pointer_actor(block, actor):
+    """`pack_entity_pointer_actor` backwards: `copy_` of the block's floats into the parameters of `actor` (unpack(pack(x)) is x bit for bit)."""
+    torch = _torch()
+    o = 0
+    with torch.no_grad():
+        for layer in _pointer_layers(actor):
+            w, b = layer.weight, layer.bias
+            w.copy_(block[o:o + w.numel()].view(w.shape[1], w.shape[0]).t()); o += w.numel()
+            b.copy_(block[o:o + b.numel()]); o += b.numel()
 
 
 def pack_entity_actor(actor):
@@ -1118,3 +1265,119 @@ class BatchedEntityIPPO(RolloutDriver, EntityPPOLearner):
         eps = torch.randn((env.num_env, 3), dtype=torch.float32, device=env.device)
         act3, act64, logp = env.entity_act(ids, self._packed, eps)
         return act3, logp, act64
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the node-pointer entity policy: a learner and a trainer next to the Gaussian set policy's
+# ------------------------------------------------------------------------------------------------------------------
+class EntityPointerPPOLearner(EntityPPOLearner):
+    """`EntityPPOLearner` with the actors of `build_entity_pointer_networks`.  A decision is stored as two floats, (node, x): the chosen
+    node's index (-1: no node was alive) and the raw charge variable; `evaluate` recomputes its log-probability from them and the stored
+    row.  `minibatch_loss`, `update`, the data-parallel gradient exchange and the checkpoints are inherited."""
+
+    def _build_networks(self):
+        self._cl = False
+        Actor, Critic = build_entity_pointer_networks(self.num_agent)
+        return ([Actor().to(self.device) for _ in range(self.num_agent)], [Critic().to(self.device) for _ in range(self.num_agent)])
+
+    def get_action(self, agent_id, states):
+        """Packed rows [n, R] -> (stored [n, 2] = (node, x), log-probability [n]): Gumbel noise -log(-log(u)) per node and a
+        standard-normal draw per row, u from `torch.rand`."""
+        torch = self.torch
+        outs, lps = [], []
+        with torch.no_grad():
+            for s in states.split(self.infer_chunk):
+                n, N = s.shape[0], EntityTransitionBuffers.split(s, self.num_agent)[0].shape[1]
+                g = -torch.log(-torch.log(torch.rand((n, N), dtype=torch.float32, device=s.device)))
+                d = self.actors[agent_id].act(s, g, torch.randn((n,), dtype=torch.float32, device=s.device))
+                outs.append(torch.stack([d["node"].to(d["x"].dtype), d["x"]], 1)); lps.append(d["logp"])
+        return torch.cat(outs), torch.cat(lps)
+
+    def evaluate(self, agent_id, batch_states, batch_actions):
+        """(log-probability [n], entropy [n]) of the stored decisions `batch_actions` [n, 2] = (node, x) on `batch_states`."""
+        return self.actors[agent_id](batch_states, batch_actions[:, 0], batch_actions[:, 1])
+
+    def packed_actors(self):
+        """The actors as `wrsn_entity_pointer_act` takes them: a new float32 tensor [M, P] on the device, built from the parameters as
+        they are now."""
+        return self.torch.stack([pack_entity_pointer_actor(a) for a in self.actors]).contiguous()
+
+
+class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
+    """The roll-out of `BatchedEntityIPPO` with the node-pointer policy: `VecWRSN(entities=True)`, transitions in
+    `EntityTransitionBuffers(action_elems=2)` -- (node, x) per decision --, the PyTorch update of `PPOLearner`.
+
+    min_charge   : the third component of every action is min_charge + (1 - min_charge) sigmoid(x): with min_charge > 0 (default 0.02)
+                   every decision spends at least min_charge * charging_time_max seconds of simulated time, so a request cannot come back
+                   at the same instant forever.
+    fused_policy : True = the device chooses (`VecWRSN.entity_pointer_act`, `wrsn_entity_pointer_act`): one call on the entity rows the
+                   environment holds, with the actors packed at the start of the roll-out and noise derived from `torch.rand` /
+                   `torch.randn`.  False (the default): `get_action` per charger.
+    log_episodes : as `BatchedEntityIPPO`.
+
+    The update of this actor is PyTorch's: there is no fused update, joint update or fused prepare for it yet, and asking for one raises."""
+
+    _check_status = True
+
+    def __init__(self, args, env, device=None, model_path=None, capacity=None, infer_chunk=1024, process_group=None, log=None, min_bucket=16,
+                 min_charge=0.02, fused_policy=False, log_episodes=False, episode_slots=64, fused_update=False, joint_update=False,
+                 fused_prepare=False):
+        for k, v in (("fused_update", fused_update), ("joint_update", joint_update), ("fused_prepare", fused_prepare)):
+            if v:
+                raise ValueError("BatchedEntityPointerIPPO has no %s: the fused update, joint update and prepare exist for the Gaussian set "
+                                 "policy (BatchedEntityIPPO) only" % k)
+        if not getattr(env, "entities", False):
+            raise ValueError("BatchedEntityPointerIPPO needs a VecWRSN with the entity observation (entities=True)")
+        if not 0.0 <= float(min_charge) < 1.0:
+            raise ValueError("min_charge must lie in [0, 1)")
+        super().__init__(args, env.num_agent, device if device is not None else env.device, model_path, infer_chunk, process_group, min_bucket)
+        self._attach(env, EntityTransitionBuffers(env, capacity or 2 * self.batch_size, 2), log)
+        self.min_charge = float(min_charge)
+        self.log_episodes = bool(log_episodes)
+        if self.log_episodes:
+            self._ledger = env.new_episode_log(episode_slots, quota=0)
+        self.fused_policy = bool(fused_policy)
+        self._packed = None                                   # packed_actors() of the weights as they are now, or None: rebuilt before use
+
+    def evaluate_episodes(self, eval_env, episodes=1, deterministic=True, generator=None, **kw):
+        """`evaluate_policy` of the actors as they are now (`evaluate.PointerPolicy`) on `eval_env`, another batch than the trainer's."""
+        from .evaluate import PointerPolicy, evaluate_policy
+        if eval_env is self.env:
+            raise ValueError("evaluate on a batch of its own: the trainer's environments live across roll-outs")
+        return evaluate_policy(eval_env, PointerPolicy(self.packed_actors(), deterministic, generator, self.min_charge), episodes, **kw)
+
+    def roll_out(self, max_launches=100000, fresh_episodes=False):
+        if self.fused_policy:
+            self._packed = self.packed_actors()
+        return super().roll_out(max_launches, fresh_episodes)
+
+    def update(self, id, batch, shuffle=np.random.shuffle):
+        self._packed = None                                   # the weights change: never carried across an update
+        return super().update(id, batch, shuffle)
+
+    def _choose(self, r, ids):
+        torch, env = self.torch, self.env
+        if not self.fused_policy:
+            return self._choose_per_charger(ids, 2, lambda rows: EntityTransitionBuffers.pack(
+                r["nodes"].index_select(0, rows), r["chargers"].index_select(0, rows), r["env_feat"].index_select(0, rows))) + (None,)
+        if self._packed is None:
+            self._packed = self.packed_actors()
+        g = -torch.log(-torch.log(torch.rand((env.num_env, env.n_node), dtype=torch.float32, device=env.device)))
+        eps = torch.randn((env.num_env,), dtype=torch.float32, device=env.device)
+        stored, act64, logp, _ = env.entity_pointer_act(ids, self._packed, g, eps, self.min_charge)
+        self._handed = act64
+        return stored, logp, act64
+
+    def _action3(self, ids, stored):
+        """The 3-vector of a launch: the device's own when it chose (fused_policy), else `stored_action3`."""
+        return self._handed if self.fused_policy else self.stored_action3(stored)
+
+    def stored_action3(self, stored):
+        """(u, v) of the stored node from the request's node rows -- the asking charger's own position for node -1 --, and the squashed x:
+        what `wrsn_entity_pointer_act` writes as `action` for the same decision (the tests hold the two together)."""
+        torch, r = self.torch, self._req
+        Actor = type(self.actors[0])
+        k = stored[:, 0].long()
+        uv = Actor.destination(r["nodes"], r["chargers"], r["env_feat"], k)
+        c = self.min_charge + (1.0 - self.min_charge) * torch.sigmoid(stored[:, 1])
+        return torch.cat([uv, c.unsqueeze(1)], 1)

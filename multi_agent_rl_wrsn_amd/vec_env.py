@@ -275,6 +275,46 @@ class VecWRSN:
                            action=act.data_ptr(), action_f64=act64.data_ptr(), logp=logp.data_ptr())
         return act, act64, logp
 
+    def entity_pointer_act(self, agent_ids, packed, gumbel=None, eps=None, min_charge=0.0):
+        """`wrsn_entity_pointer_act` on the entity rows this object holds (`entities=True`): the chargers `agent_ids` [B] (< 0: row skipped)
+        act with the packed node-pointer actors `packed` [M, P] (`EntityPointerPPOLearner.packed_actors`), the Gumbel draws `gumbel` [B, N]
+        (None: the most probable node) and the standard-normal draws `eps` [B] (None: the mode of the charge variable); the third
+        component of every action is at least `min_charge`.  Returns (stored float32 [B,2] -- (node, x), what the buffers keep --,
+        action_f64 float64 [B,3] -- what `step` takes --, logp float32 [B], node int32 [B], -1: no alive node): tensors this object owns
+        and writes again at the next call; skipped rows keep what they held."""
+        t = self.torch
+        if not self.entities:
+            raise ValueError("entity_pointer_act needs a VecWRSN with the entity observation (entities=True)")
+        self._bind_stream()
+        a = agent_ids
+        if not (a.dtype == t.int32 and a.device == self.device and a.is_contiguous() and a.numel() == self.num_env):
+            a = a.to(device=self.device, dtype=t.int32).reshape(-1).contiguous()
+        P = self._h.lib.wrsn_entity_pointer_floats()
+        w = packed
+        if not (w.dtype == t.float32 and w.device == self.device and w.is_contiguous()):
+            w = w.to(device=self.device, dtype=t.float32).contiguous()
+        if tuple(w.shape) != (self.num_agent, P):
+            raise ValueError("packed pointer actors must be [%d, %d], not %s" % (self.num_agent, P, list(w.shape)))
+        g = e = None
+        if gumbel is not None:
+            g = gumbel.to(device=self.device, dtype=t.float32).contiguous()
+            if g.numel() != self.n_node * self.num_env:
+                raise ValueError("gumbel must be [%d, %d]" % (self.num_env, self.n_node))
+        if eps is not None:
+            e = eps.to(device=self.device, dtype=t.float32).contiguous()
+            if e.numel() != self.num_env:
+                raise ValueError("eps must be [%d]" % self.num_env)
+        if getattr(self, "_ptr_act", None) is None:
+            B = self.num_env
+            z = lambda shape, dt: t.zeros(shape, dtype=dt, device=self.device)
+            self._ptr_act = (z((B, 2), t.float32), z((B, 3), t.float32), z((B, 3), t.float64), z((B,), t.float32), z((B,), t.int32))
+        self._keep_ptr_act = (a, w, g, e)                     # alive until the launch has run
+        stored, act, act64, logp, node = self._ptr_act
+        self._h.entity_pointer_act(w.data_ptr(), a.data_ptr(), g.data_ptr() if g is not None else 0, e.data_ptr() if e is not None else 0,
+                                   min_charge, None, node=node.data_ptr(), stored=stored.data_ptr(), action=act.data_ptr(),
+                                   action_f64=act64.data_ptr(), logp=logp.data_ptr())
+        return stored, act64, logp, node
+
     def entity_heuristic_act(self, agent_ids, charge_scale=1.0):
         """`wrsn_entity_heuristic_act` on the entity rows this object holds (`entities=True`): for the chargers `agent_ids` [B] (outside
         [0, M): row skipped) the most critical node no other charger is heading for.  Returns (action float32 [B,3], action_f64 float64

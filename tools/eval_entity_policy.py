@@ -3,7 +3,9 @@
 Default mode: `evaluate_policy` on a HELD-OUT set -- `--eval-envs` (256) synthetic 200-node networks whose seeds the trainer never sees --
 for: uniform actions, the heuristic (`HeuristicPolicy`, as the kernel's rule stands and with `--min-charge`), the untrained actors (mode
 and sampled) and the actors after `--iters` (200) iterations of BatchedEntityIPPO with the fused options of bench_ippo.py (mode and
-sampled).  A policy that uses up `--max-launches` is recorded with its partial log and the number of environments standing still (a
+sampled).  `--policy pointer` does the same for the node-pointer policy: uniform and heuristic as above, then the untrained pointer
+actors (mode and sampled) and the actors after `--iters` iterations of BatchedEntityPointerIPPO (fused acting, the PyTorch update; mode
+and sampled), every pointer row with `--min-charge`; it writes profiles/entity_pointer_eval.json.  A policy that uses up `--max-launches` is recorded with its partial log and the number of environments standing still (a
 deterministic policy that repeats an action of zero duration gets the same request again at the same instant).  Writes
 profiles/entity_eval.json.
 
@@ -95,21 +97,41 @@ def bench(args):
     return out
 
 
-def compare(args):
-    import numpy as np
-    import torch
-    from multi_agent_rl_wrsn_amd import (BatchedEntityIPPO, EntityPolicy, HeuristicPolicy, UniformPolicy, VecWRSN, evaluate_policy, synth_scenario)
-    from multi_agent_rl_wrsn_amd.evaluate import LaunchCapReached
-    N, M = 200, 3
-    torch.manual_seed(0); np.random.seed(0)
+def device_envs(args, N=200, M=3):
+    """(training batch, held-out evaluation batch) on the device."""
+    from multi_agent_rl_wrsn_amd import VecWRSN, synth_scenario
     train_env = VecWRSN([synth_scenario(e, N, N) for e in range(args.envs)], None, M, render=False, entities=True, auto_reset=True, step_budget=1250)
     eval_env = VecWRSN([synth_scenario(1_000_000 + e, N, N) for e in range(args.eval_envs)], None, M, render=False, entities=True, step_budget=1250)
-    algo = BatchedEntityIPPO(dict(batch_size=512, minibatch_size=64, n_updates_per_iteration=5), train_env, capacity=4096, fused_policy=True,
-                             fused_update=True, joint_update=True, fused_prepare=True, log_episodes=True)
+    return train_env, eval_env
+
+
+def compare(args, make_envs=device_envs):
+    """The policy comparison; `make_envs(args)` gives the two batches (the tests pass emulated ones)."""
+    import numpy as np
+    import torch
+    from multi_agent_rl_wrsn_amd import (BatchedEntityIPPO, BatchedEntityPointerIPPO, EntityPolicy, HeuristicPolicy, PointerPolicy, UniformPolicy,
+                                         evaluate_policy)
+    from multi_agent_rl_wrsn_amd.evaluate import LaunchCapReached
+    torch.manual_seed(0); np.random.seed(0)
+    train_env, eval_env = make_envs(args)
+    N, M = train_env.n_node, train_env.num_agent
+    pointer = args.policy == "pointer"
+    ppo = dict(batch_size=args.batch_size, minibatch_size=args.minibatch_size, n_updates_per_iteration=5)
+    if pointer:
+        algo = BatchedEntityPointerIPPO(ppo, train_env, capacity=max(4096, 2 * args.batch_size), fused_policy=True, log_episodes=True,
+                                        min_charge=args.min_charge)
+        Policy = lambda det, g=None: PointerPolicy(algo.packed_actors(), det, g, args.min_charge)
+    else:
+        algo = BatchedEntityIPPO(ppo, train_env, capacity=max(4096, 2 * args.batch_size), fused_policy=True,
+                                 fused_update=True, joint_update=True, fused_prepare=True, log_episodes=True)
+        Policy = lambda det, g=None: EntityPolicy(algo.packed_actors(), det, g)
     gen = lambda: torch.Generator(device=eval_env.device).manual_seed(7)
     out = {"eval_set": "%d synthetic %d-node networks, seeds 1000000.., %d chargers, %d episode(s) each, time limit %g s" %
                        (args.eval_envs, N, M, args.episodes, min(s.max_time for s in eval_env.scenarios)),
-           "device": torch.cuda.get_device_name(eval_env.device), "max_launches": args.max_launches, "policies": {}}
+           "device": torch.cuda.get_device_name(eval_env.device) if eval_env.device.type == "cuda" else str(eval_env.device),
+           "max_launches": args.max_launches, "policy": args.policy, "policies": {}}
+    if pointer:
+        out["min_charge"] = args.min_charge
 
     def run(name, policy):
         t0 = time.perf_counter()
@@ -126,8 +148,8 @@ def compare(args):
     run("uniform", UniformPolicy(gen()))
     run("heuristic", HeuristicPolicy())
     run("heuristic_min_charge", HeuristicPolicy(min_charge=args.min_charge))
-    run("untrained_mode", EntityPolicy(algo.packed_actors(), True))
-    run("untrained_sampled", EntityPolicy(algo.packed_actors(), False, gen()))
+    run("untrained_mode", Policy(True))
+    run("untrained_sampled", Policy(False, gen()))
     t0 = time.perf_counter()
     # The trainer raises when a row comes back with a negative status (an environment whose step reported an error: seen after a handful
     # of iterations at these shapes).  Here such rows are counted, not fatal: they are a few of thousands and ask nobody for an action.
@@ -146,13 +168,17 @@ def compare(args):
     out["training"] = {"iterations": len(rows) // M, "error_status_rows_summed_over_launches": int(errors), "launches": algo.timers["launches"],
                        "seconds": time.perf_counter() - t0,
                        "last_rows": [{k: r[k] for k in ("iteration", "agent", "mean_reward", "avg_ep_lifetime", "avg_ep_lens", "episodes")} for r in rows[-M:]]}
-    run("trained_mode", EntityPolicy(algo.packed_actors(), True))
-    run("trained_sampled", EntityPolicy(algo.packed_actors(), False, gen()))
+    run("trained_mode", Policy(True))
+    run("trained_sampled", Policy(False, gen()))
     return out
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--policy", default="gaussian", choices=["gaussian", "pointer"], help="gaussian: the set policy (BatchedEntityIPPO, the default); "
+                    "pointer: the node-pointer policy (BatchedEntityPointerIPPO, PointerPolicy)")
+    ap.add_argument("--batch-size", type=int, default=512)
+    ap.add_argument("--minibatch-size", type=int, default=64)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--episodes", type=int, default=1)
     ap.add_argument("--envs", type=int, default=4096)
@@ -164,9 +190,10 @@ def main():
     ap.add_argument("--launches", type=int, default=50)
     ap.add_argument("--only", default=None, choices=[None, "fused", "torch"])
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     out = bench(args) if args.bench else compare(args)
-    path = args.out or os.path.join(ROOT, "profiles", "episodes_bench.json" if args.bench else "entity_eval.json")
+    path = args.out or os.path.join(ROOT, "profiles", "episodes_bench.json" if args.bench else
+                                    "entity_pointer_eval.json" if args.policy == "pointer" else "entity_eval.json")
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as w:
         json.dump(out, w, indent=1)
