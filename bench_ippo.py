@@ -47,6 +47,8 @@ def main():
                     "one call (wrsn_entity_ppo_update, BatchedEntityIPPO(joint_update=True))")
     ap.add_argument("--fused-prepare", action="store_true", help="implies --fused-update: values, GAE and the gathers of every charger's batch in one device "
                     "call (wrsn_entity_prepare, BatchedEntityIPPO(fused_prepare=True)) instead of index_select and cal_rt_adv per charger")
+    ap.add_argument("--device-update", action="store_true", help="with --policy pointer: the PPO update runs on the device (wrsn_entity_pointer_ppo_grad, "
+                    "wrsn_entity_adam, BatchedEntityPointerIPPO(device_update=True)) instead of PyTorch autograd and torch.optim.Adam")
     ap.add_argument("--min-charge", type=float, default=0.02, help="with --policy pointer: the least third component of an action "
                     "(BatchedEntityPointerIPPO(min_charge=...))")
     ap.add_argument("--report-updates", action="store_true", help="add peak device memory and the statistics of every update (first minibatch included) to the line")
@@ -57,6 +59,8 @@ def main():
         raise SystemExit("--fused-policy needs --policy entity or --policy pointer")
     if args.fused_update and args.policy != "entity":
         raise SystemExit("--fused-update needs --policy entity")
+    if args.device_update and args.policy != "pointer":
+        raise SystemExit("--device-update needs --policy pointer")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:       # launcher-free multi-rank entry: before this process touches torch or the GPU
         from multi_agent_rl_wrsn_amd.sharding import launch_ranks
         raise SystemExit(launch_ranks(args.gpus, [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]))
@@ -82,7 +86,8 @@ def main():
         env = VecWRSN([synth_scenario(rank * B + e, N, N) for e in range(B)], None, M, auto_reset=True, step_budget=args.step_budget, device=str(dev),
                       render=False, entities=True)
         algo = BatchedEntityPointerIPPO(ppo_args, env, capacity=max(2 * args.batch_size, 4096), infer_chunk=args.infer_chunk, min_bucket=args.infer_chunk,
-                                        fused_policy=args.fused_policy, min_charge=args.min_charge)
+                                        fused_policy=args.fused_policy, min_charge=args.min_charge,
+                                        **({"device_update": True} if args.device_update else {}))
     elif entity:
         env = VecWRSN([synth_scenario(rank * B + e, N, N) for e in range(B)], None, M, auto_reset=True, step_budget=args.step_budget, device=str(dev),
                       render=False, entities=True)             # no image at all: 6.6 KB of entity rows per request
@@ -104,7 +109,7 @@ def main():
             return res
         algo.minibatch_loss = minibatch_loss
         algo.log = lambda row: updates.append(dict(row, first_minibatch=first.pop(row["agent"], {})))
-        if args.fused_update:                                  # no minibatch_loss is called: the device table's first row
+        if args.fused_update or args.device_update:            # no minibatch_loss is called: the device table's first row
             algo.log = lambda row: updates.append(dict(row, first_minibatch=dict(approx_kl=algo.first_minibatch_stats[row["agent"]][4],
                                                                                  clipfrac=algo.first_minibatch_stats[row["agent"]][5])))
     if args.warmup_iters > 0:
@@ -150,7 +155,8 @@ def main():
     if pointer:
         out["config"]["workload"] = "%d envs x %d nodes x %d MC, node-pointer actor + set critic per charger on entity rows, (node, x) actions, batch %d / minibatch %d / %d epochs" % (
             B, N, M, args.batch_size, args.minibatch_size, args.updates)
-        out["config"]["policy"] = "float32, entity rows, no image" + (", actions sampled on the device (wrsn_entity_pointer_act)" if args.fused_policy else "")
+        out["config"]["policy"] = "float32, entity rows, no image" + (", actions sampled on the device (wrsn_entity_pointer_act)" if args.fused_policy else "") + (
+            ", update on the device (wrsn_entity_pointer_ppo_grad, wrsn_entity_adam)" if args.device_update else "")
     if args.report_updates:
         out["peak_memory_bytes"] = int(torch.cuda.max_memory_allocated(dev)); out["updates"] = updates
     print(json.dumps(out, default=float), flush=True)

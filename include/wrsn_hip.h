@@ -531,6 +531,36 @@ int wrsn_entity_ppo_grad(wrsn_t *h, const float *actor, const float *critic, con
 int wrsn_entity_adam(wrsn_t *h, float *param, const float *grad, float *m, float *v, int32_t n_floats, int32_t step, float lr, float beta1,
                      float beta2, float eps, float max_norm, float *norm_out);
 
+/* ---- the same for the node-pointer policy, one learner per call: EntityPointerActor.forward, EntityCritic.forward and
+ * PPOLearner.minibatch_loss of ippo.py, statement for statement, in float32.  `actor` is a pointer block (wrsn_entity_pointer_floats()
+ * floats, wrsn_entity_pointer_act's layout), `critic` the block of wrsn_entity_critic_floats() floats, `rows` as above; `stored` [*, 2]
+ * holds the decisions as EntityTransitionBuffers(action_elems=2) keeps them, ((float) node, x), indexed like the rows.  Both calls are
+ * asynchronous on the handle's stream, need no scenario and use the handle's growing scratch.  For one row with stored (kf, x):
+ *   k  = (int) kf when kf is finite and 0 <= k < n_node, else -1 -- a select made before anything is indexed;  kv = k >= 0 and node k is alive
+ *   z, q, h_i, l_i, lse, node_logp as under wrsn_entity_pointer_act (-inf for nodes that are not alive);  p_i = exp(l_i - lse)
+ *   (mu, s_raw) = charge([z, x_k]), s = clamp(s_raw, -4, 1);  x_k = the eight floats of node row k as they stand (alive or not), zeros for k = -1
+ *   t = (x - mu) / exp(s);  logp = (kv ? node_logp[k] : 0) - t^2 / 2 - s - 1/2 log 2 pi
+ *   H_cat = -sum_alive p_i (l_i - lse) (0 with no alive node);  entropy = H_cat + s + 1/2 + 1/2 log 2 pi
+ * wrsn_entity_pointer_eval writes logp [n], entropy [n], node_logp [n, n_node], charge_mean [n], charge_log_std [n] (after the clamp) and
+ * value [n]; any output may be NULL, `actor` or `critic` may be NULL (not both), and the outputs of an absent net must be NULL.  For one row
+ * content and one block node_logp, charge_mean and charge_log_std are THE BYTES wrsn_entity_pointer_act writes when stored[0] is that call's
+ * node; logp differs from its logp by rounding only (act forms it from its own eps).
+ * wrsn_entity_pointer_ppo_grad: loss, statistics, advantage normalisation, value terms and kinks exactly as under wrsn_entity_ppo_grad with
+ * this logp and entropy; grad_actor (wrsn_entity_pointer_floats() floats) and grad_critic (wrsn_entity_critic_floats()) are overwritten in
+ * block layout, the padding with zeros; stats as there.  Nothing flows into x_k, the advantages or the selects.
+ * Two calls on equal inputs give equal bytes; a row's forward outputs depend on that row, its stored pair and the block only.
+ * WRSN_ERR_ARG with every buffer untouched: the cases of wrsn_entity_eval / wrsn_entity_ppo_grad carried over, `stored` NULL with an actor, and
+ * more nodes than the score block's LDS holds (about 11 000). */
+typedef struct wrsn_pointer_batch {      /* DEVICE, float32, indexed like the rows */
+    const float *stored;                 /* [*, 2] ((float)node, x), as EntityTransitionBuffers(action_elems=2) keeps it */
+    const float *logp_old, *advantage, *ret, *value_old;
+} wrsn_pointer_batch;
+
+int wrsn_entity_pointer_eval(wrsn_t *h, const float *actor, const float *critic, const wrsn_entity_rows *rows, const float *stored, float *logp,
+                             float *entropy, float *node_logp, float *charge_mean, float *charge_log_std, float *value);
+int wrsn_entity_pointer_ppo_grad(wrsn_t *h, const float *actor, const float *critic, const wrsn_entity_rows *rows, const wrsn_pointer_batch *batch,
+                                 const wrsn_ppo_hyper *hyper, float *grad_actor, float *grad_critic, float *stats);
+
 /* THE UPDATE OF SEVERAL INDEPENDENT LEARNERS AT ONCE.  The chargers of IPPO share nothing: own nets, own Adam state, own batch.  A GROUP is
  * one (actor, critic) pair with its optimiser state and its data; the three calls below do for G groups (1 <= G <= 8) what the
  * single-group calls above do for one, in the SAME number of launches however large G is (the group is a dimension of every kernel's

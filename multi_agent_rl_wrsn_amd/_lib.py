@@ -40,7 +40,7 @@ ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max"
 
 # every entry point include/wrsn_hip.h declares
 EXPORTS = ("wrsn_create", "wrsn_destroy", "wrsn_set_stream", "wrsn_set_scenario", "wrsn_set_scenario_seeded", "wrsn_reset", "wrsn_step",
-           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_entity_actor_floats", "wrsn_entity_act", "wrsn_entity_pointer_floats", "wrsn_entity_pointer_act", "wrsn_entity_heuristic_act", "wrsn_episodes_collect", "wrsn_entity_critic_floats", "wrsn_entity_eval", "wrsn_entity_ppo_grad", "wrsn_entity_adam", "wrsn_entity_ppo_grad_multi", "wrsn_entity_adam_multi", "wrsn_entity_ppo_update", "wrsn_entity_prepare", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
+           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_entity_actor_floats", "wrsn_entity_act", "wrsn_entity_pointer_floats", "wrsn_entity_pointer_eval", "wrsn_entity_pointer_ppo_grad", "wrsn_entity_pointer_act", "wrsn_entity_heuristic_act", "wrsn_episodes_collect", "wrsn_entity_critic_floats", "wrsn_entity_eval", "wrsn_entity_ppo_grad", "wrsn_entity_adam", "wrsn_entity_ppo_grad_multi", "wrsn_entity_adam_multi", "wrsn_entity_ppo_update", "wrsn_entity_prepare", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
            "wrsn_clone_envs", "wrsn_pool_set", "wrsn_pool_reset", "wrsn_synth_network",
            "wrsn_last_error",
            "wrsn_version")
@@ -94,6 +94,11 @@ class WrsnEntityRows(C.Structure):
 
 class WrsnPpoBatch(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("action", "logp_old", "advantage", "ret", "value_old")]
+
+
+class WrsnPointerBatch(C.Structure):
+    """wrsn_pointer_batch: the batch of wrsn_entity_pointer_ppo_grad; `stored` is [*, 2] = ((float) node, x)."""
+    _fields_ = [(k, C.c_void_p) for k in ("stored", "logp_old", "advantage", "ret", "value_old")]
 
 
 class WrsnPpoHyper(C.Structure):
@@ -181,6 +186,10 @@ def bind(lib):
     lib.wrsn_entity_eval.restype = C.c_int
     lib.wrsn_entity_ppo_grad.argtypes = [vp, vp, vp, C.POINTER(WrsnEntityRows), C.POINTER(WrsnPpoBatch), C.POINTER(WrsnPpoHyper), vp, vp, vp]
     lib.wrsn_entity_ppo_grad.restype = C.c_int
+    lib.wrsn_entity_pointer_eval.argtypes = [vp, vp, vp, C.POINTER(WrsnEntityRows), vp, vp, vp, vp, vp, vp, vp]
+    lib.wrsn_entity_pointer_eval.restype = C.c_int
+    lib.wrsn_entity_pointer_ppo_grad.argtypes = [vp, vp, vp, C.POINTER(WrsnEntityRows), C.POINTER(WrsnPointerBatch), C.POINTER(WrsnPpoHyper), vp, vp, vp]
+    lib.wrsn_entity_pointer_ppo_grad.restype = C.c_int
     lib.wrsn_entity_adam.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, vp]
     lib.wrsn_entity_adam.restype = C.c_int
     lib.wrsn_entity_ppo_grad_multi.argtypes = [vp, C.POINTER(WrsnEntityGroup), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.POINTER(WrsnPpoHyper), vp]
@@ -436,6 +445,24 @@ class RawHandle:
         check(self.lib, self.lib.wrsn_entity_ppo_grad(self._h, C.c_void_p(actor_ptr or None), C.c_void_p(critic_ptr or None),
                                                       self._rows(rows_ptr, index_ptr, n, n_node, n_mc), C.byref(b), C.byref(hp),
                                                       C.c_void_p(grad_actor or None), C.c_void_p(grad_critic or None), C.c_void_p(stats or None)))
+
+    def entity_pointer_eval(self, actor_ptr, critic_ptr, rows_ptr, index_ptr, n, n_node, n_mc, stored=0, logp=0, entropy=0, node_logp=0,
+                            charge_mean=0, charge_log_std=0, value=0):
+        """wrsn_entity_pointer_eval: the pointer block at actor_ptr and / or the critic block at critic_ptr (0: not asked) on the n packed
+        entity rows and the stored decisions ([*, 2] = (node, x), indexed like the rows); the outputs are float32 addresses, 0: not wanted."""
+        p = lambda x: C.c_void_p(x or None)
+        check(self.lib, self.lib.wrsn_entity_pointer_eval(self._h, p(actor_ptr), p(critic_ptr), self._rows(rows_ptr, index_ptr, n, n_node, n_mc),
+                                                          p(stored), p(logp), p(entropy), p(node_logp), p(charge_mean), p(charge_log_std), p(value)))
+
+    def entity_pointer_ppo_grad(self, actor_ptr, critic_ptr, rows_ptr, index_ptr, n, n_node, n_mc, stored, logp_old, advantage, ret, value_old,
+                                clip, ent_coef, vf_coef, norm_adv, clip_vloss, grad_actor, grad_critic, stats):
+        """wrsn_entity_pointer_ppo_grad: `entity_ppo_grad` for the node-pointer actor (grad_actor: wrsn_entity_pointer_floats() floats)."""
+        b = WrsnPointerBatch(stored or None, logp_old or None, advantage or None, ret or None, value_old or None)
+        hp = WrsnPpoHyper(float(clip), float(ent_coef), float(vf_coef), 1 if norm_adv else 0, 1 if clip_vloss else 0)
+        check(self.lib, self.lib.wrsn_entity_pointer_ppo_grad(self._h, C.c_void_p(actor_ptr or None), C.c_void_p(critic_ptr or None),
+                                                              self._rows(rows_ptr, index_ptr, n, n_node, n_mc), C.byref(b), C.byref(hp),
+                                                              C.c_void_p(grad_actor or None), C.c_void_p(grad_critic or None),
+                                                              C.c_void_p(stats or None)))
 
     def entity_adam(self, param, grad, m, v, n_floats, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, max_norm=0.5, norm_out=0):
         """wrsn_entity_adam: clip_grad_norm_(max_norm) then one torch.optim.Adam step, in place on the block of n_floats at `param`."""

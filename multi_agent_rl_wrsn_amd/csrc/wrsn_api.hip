@@ -16,6 +16,7 @@
 #include "wrsn_rollout.h"
 #include "wrsn_state.h"
 #include "wrsn_entity_train.h"
+#include "wrsn_entity_pointer_train.h"
 
 namespace {
 
@@ -1237,6 +1238,90 @@ int wrsn_entity_adam(wrsn_t* h, float* param, const float* grad, float* m, float
     WrsnEtAdamBlocks bs{};
     entity_adam_block(&bs, 0, param, grad, m, v, norm_out, (int)n_floats, (int)step, lr, beta1, beta2);
     if (const int rc = entity_adam_launch(h, bs, 1, (int)n_floats, beta1, beta2, eps, max_norm)) return rc;
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+// ------------------------------------------------------------------ the PPO gradient of the node-pointer policy (wrsn_entity_pointer_train.h)
+namespace {
+// the set policy's scratch for one group of n rows, and behind it what the pointer kernels keep
+int pointer_scratch(wrsn_handle* h, int n, int N, bool grad, WrsnEtScratch* s, WrsnEtpScratch* ps) {
+    const size_t et = wrsn_et_scratch_floats((size_t)n, grad), need = et + wrsn_etp_scratch_floats((size_t)n, N, grad);
+    if (need > h->et_cap) {
+        const int rc = dalloc(h, &h->et_scratch, need);
+        if (rc) return rc;
+        h->et_cap = need;
+    }
+    { const int rc = entity_scratch(h, n, grad, 1, s); if (rc) return rc; }
+    float* p = h->et_scratch + et;
+    ps->ld = (N + 31) & ~31;
+    ps->q = p; p += (size_t)n * 64; ps->lp = p; p += (size_t)n * ps->ld; ps->prow = p; p += (size_t)n * 8;
+    ps->dq = ps->dch = ps->part2 = nullptr;
+    if (grad) { ps->dq = p; p += (size_t)n * 64; ps->dch = p; p += (size_t)n * 4; ps->part2 = p; p += (size_t)n * WRSN_EP_MC1; }
+    return 0;
+}
+// trunk and heads of both nets, then -- with an actor -- the query and the scores of the stored decisions
+void pointer_forward(wrsn_handle* h, const WrsnEtGroups& gs, const WrsnEtDims& dm, const WrsnEtScratch& s, const WrsnEtpScratch& ps, const float* stored,
+                     float* value, const WrsnEtpEvalOut& o) {
+    WrsnEtEvalOut eo; eo.mean = nullptr; eo.log_std = nullptr; eo.value = value;
+    entity_forward(h, gs, 1, dm, s, eo);
+    if (!gs.g[0].actor) return;
+    hipLaunchKernelGGL(wrsn_etp_query_kernel, dim3((dm.n + WRSN_EP_HEAD_ROWS - 1) / WRSN_EP_HEAD_ROWS), dim3(256), 128 * 32 * sizeof(float), h->stream, gs, dm.n, s, ps);
+    hipLaunchKernelGGL(wrsn_etp_score_fwd_kernel, dim3(dm.n), dim3(256), WRSN_PP_SCORE_LDS(dm.N), h->stream, gs, dm, s, ps, stored, o);
+}
+}  // namespace
+
+int wrsn_entity_pointer_eval(wrsn_t* h, const float* actor, const float* critic, const wrsn_entity_rows* rows, const float* stored, float* logp,
+                             float* entropy, float* node_logp, float* charge_mean, float* charge_log_std, float* value) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    if (const char* bad = entity_rows_bad(rows)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_eval: ") + bad);
+    if (!actor && !critic) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_eval needs an actor or a critic");
+    if (actor && !stored) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_eval: an actor needs stored");
+    if ((actor && !logp && !entropy && !node_logp && !charge_mean && !charge_log_std) || (critic && !value))
+        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_eval: a net that is given needs an output");
+    if ((!actor && (logp || entropy || node_logp || charge_mean || charge_log_std)) || (!critic && value))
+        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_eval: outputs of a net that is not given must be NULL");
+    if ((uintptr_t)actor % 16 || (uintptr_t)critic % 16) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_eval: blocks must be 16-byte aligned");
+    if (WRSN_PP_SCORE_LDS(rows->n_node) > 65536) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_eval: too many nodes for the score block's LDS");
+    WRSN_ON_DEVICE(h);
+    WrsnEtScratch s; WrsnEtpScratch ps;
+    { const int rc = pointer_scratch(h, rows->n, rows->n_node, false, &s, &ps); if (rc) return rc; }
+    WrsnEtGroups gs{};
+    gs.g[0].actor = actor; gs.g[0].critic = critic; gs.g[0].rows = rows->rows; gs.g[0].index = rows->index;
+    WrsnEtDims dm; dm.n = rows->n; dm.N = rows->n_node; dm.M = rows->n_mc;
+    WrsnEtpEvalOut o; o.logp = logp; o.entropy = entropy; o.node_logp = node_logp; o.charge_mean = charge_mean; o.charge_log_std = charge_log_std;
+    pointer_forward(h, gs, dm, s, ps, stored, value, o);
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+int wrsn_entity_pointer_ppo_grad(wrsn_t* h, const float* actor, const float* critic, const wrsn_entity_rows* rows, const wrsn_pointer_batch* batch,
+                                 const wrsn_ppo_hyper* hyper, float* grad_actor, float* grad_critic, float* stats) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    if (const char* bad = entity_rows_bad(rows)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_ppo_grad: ") + bad);
+    if (!actor || !critic || !batch || !hyper || !grad_actor || !grad_critic || !stats || !batch->stored || !batch->logp_old || !batch->advantage ||
+        !batch->ret || !batch->value_old)
+        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_grad needs actor, critic, every batch array, hyper, grad_actor, grad_critic and stats");
+    if ((uintptr_t)actor % 16 || (uintptr_t)critic % 16 || (uintptr_t)grad_actor % 16 || (uintptr_t)grad_critic % 16)
+        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_grad: blocks and gradient buffers must be 16-byte aligned");
+    if (hyper->norm_adv && rows->n < 2) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_grad: norm_adv needs n >= 2");
+    if (WRSN_ETP_BWD_LDS(rows->n_node) > 65536) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_grad: too many nodes for the score block's LDS");
+    WRSN_ON_DEVICE(h);
+    WrsnEtDims dm; dm.n = rows->n; dm.N = rows->n_node; dm.M = rows->n_mc;
+    WrsnEtScratch s; WrsnEtpScratch ps;
+    { const int rc = pointer_scratch(h, dm.n, dm.N, true, &s, &ps); if (rc) return rc; }
+    WrsnEtGroups gs{};
+    WrsnEtGroup& G = gs.g[0];
+    G.actor = actor; G.critic = critic; G.grad_actor = grad_actor; G.grad_critic = grad_critic; G.rows = rows->rows; G.index = rows->index; G.stats = stats;
+    G.b.action = batch->stored; G.b.logp_old = batch->logp_old; G.b.advantage = batch->advantage; G.b.ret = batch->ret; G.b.value_old = batch->value_old;
+    const int n = dm.n;
+    pointer_forward(h, gs, dm, s, ps, batch->stored, nullptr, WrsnEtpEvalOut{});
+    hipLaunchKernelGGL(wrsn_etp_loss_kernel, dim3(1), dim3(256), 256 * sizeof(double), h->stream, gs, n, entity_hyper(hyper), s, ps);
+    hipLaunchKernelGGL(wrsn_etp_score_bwd_kernel, dim3(n), dim3(256), WRSN_ETP_BWD_LDS(dm.N), h->stream, gs, dm, s, ps);
+    hipLaunchKernelGGL(wrsn_etp_head_bwd_kernel, dim3(2 * n), dim3(256), 256 * sizeof(float), h->stream, gs, n, s);
+    hipLaunchKernelGGL(wrsn_et_trunk_bwd_kernel, dim3(2 * n), dim3(256), WRSN_ET_B_LDS, h->stream, gs, dm, s);
+    hipLaunchKernelGGL(wrsn_etp_trunk_bwd_kernel, dim3(n), dim3(256), WRSN_ET_B_LDS, h->stream, gs, dm, s, ps);
+    hipLaunchKernelGGL(wrsn_etp_reduce_kernel, dim3(2 * ((WRSN_PP_FLOATS + 255) / 256)), dim3(256), 0, h->stream, gs, dm, s, ps);
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }

@@ -85,6 +85,17 @@ WDEV WrsnEtScratch wrsn_et_slice(WrsnEtScratch s, int g) {
     return s;
 }
 
+// what the node-pointer update (wrsn_entity_pointer_train.h) keeps per row next to the above; null in every call of the set policy
+struct WrsnEtpScratch {
+    float* q;       // [n][64]  query(z)
+    float* lp;      // [n][ld]  log-probability of every node (-inf: not alive), then d loss / d l in place
+    float* prow;    // [n][8]   logp, H, H_cat, mu, s_raw, the validated node (-1: none) as a float, [it is alive], t = (x - mu) / exp(s)
+    float* dq;      // [n][64]  d loss / d q
+    float* dch;     // [n][2]   d loss / d (mu, s_raw)
+    float* part2;   // [n][WRSN_EP_MC1] the row's gradient of node1 / node2 through the scores
+    int ld;         // floats per row of lp: N rounded up to whole tiles
+};
+
 static inline size_t wrsn_et_scratch_floats(size_t n, bool grad) {   // host
     return 2 * n * (WRSN_ENTPOL_FEAT + 64 + 4 + 128 + 128) + 8 * n + (grad ? 2 * n * (128 + 128 + WRSN_ENTPOL_FEAT + WRSN_ET_TRUNK_FLOATS) + 8 * n : 0);
 }
@@ -359,7 +370,10 @@ WDEV double wrsn_et_block_sum(double v, double* s, int tid) {
 }
 
 // PPOLearner.minibatch_loss, statement for statement, and its derivative with respect to the raw outputs.  Thread t takes rows t, t + 256, ...
-__global__ void __launch_bounds__(256) wrsn_et_loss_kernel(WrsnEtGroups gs, int n, WrsnEtHyper hp, WrsnEtScratch s0) {
+// PTR: the node-pointer actor -- log-probability and entropy of a row are the two floats the score kernel left in prow, and what goes back is
+// d loss / d logp and d loss / d H (dout[0], dout[1]).
+template <bool PTR>
+WDEV void wrsn_et_loss_body(const WrsnEtGroups& gs, int n, const WrsnEtHyper& hp, const WrsnEtScratch& s0, const float* prow) {
     extern __shared__ double smem[];
     const int tid = (int)threadIdx.x, grp = (int)blockIdx.x;  // one block per group
     const int32_t* index = gs.g[grp].index;
@@ -383,6 +397,8 @@ __global__ void __launch_bounds__(256) wrsn_et_loss_kernel(WrsnEtGroups gs, int 
         float* dout = s.dout + (size_t)i * 8;
         float z[3], sg[3], newlogp = 0.f, H = 0.f;
         bool pass[3];
+        if constexpr (PTR) { newlogp = prow[(size_t)i * 8]; H = prow[(size_t)i * 8 + 1]; }
+        else {
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
             const float lr = raw[3 + d], ls = fminf(fmaxf(lr, -4.f), 1.f);
@@ -393,6 +409,7 @@ __global__ void __launch_bounds__(256) wrsn_et_loss_kernel(WrsnEtGroups gs, int 
             H += ls + 1.4189385f;                             // 1/2 + 1/2 log(2 pi)
         }
         newlogp -= 2.7568156f;                                // 1.5 log(2 pi)
+        }
         const float lratio = newlogp - b.logp_old[q], ratio = expf(lratio);
         a_kl += (double)expm1f(lratio) - (double)lratio;     // (r - 1) - l without the cancellation in r - 1
         a_cf += fabsf(ratio - 1.f) > hp.clip ? 1.0 : 0.0;
@@ -403,10 +420,13 @@ __global__ void __launch_bounds__(256) wrsn_et_loss_kernel(WrsnEtGroups gs, int 
         const float d1 = -A, d2 = inside ? -A : 0.f;         // of two terms under a max the larger counts; equal terms share
         const float dr = t1 > t2 ? d1 : t2 > t1 ? d2 : 0.5f * d1 + 0.5f * d2;
         const float glp = dr * ratio * inv_n;
+        if constexpr (PTR) { dout[0] = glp; dout[1] = -hp.ent_coef * inv_n; dout[2] = 0.f; dout[3] = 0.f; dout[4] = 0.f; dout[5] = 0.f; }
+        else {
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
             dout[d] = glp * z[d] / sg[d];
             dout[3 + d] = pass[d] ? glp * (z[d] * z[d] - 1.f) - hp.ent_coef * inv_n : 0.f;
+        }
         }
         a_h += (double)H;
         const float v = raw[6], R = b.ret[q], u = v - R;
@@ -429,10 +449,15 @@ __global__ void __launch_bounds__(256) wrsn_et_loss_kernel(WrsnEtGroups gs, int 
         stats[1] = (float)pg; stats[2] = (float)vl; stats[3] = (float)en; stats[4] = (float)kl; stats[5] = (float)cf; stats[6] = 0.f; stats[7] = 0.f;
     }
 }
+__global__ void __launch_bounds__(256) wrsn_et_loss_kernel(WrsnEtGroups gs, int n, WrsnEtHyper hp, WrsnEtScratch s0) {
+    wrsn_et_loss_body<false>(gs, n, hp, s0, nullptr);
+}
 
 // one block per (row, net): d / d (head2 pre-activation), d / d (head1 pre-activation), d / d features.  Thread k owns unit k and reads
 // row k of the [in, out] weights.
-__global__ void __launch_bounds__(256) wrsn_et_head_bwd_kernel(WrsnEtGroups gs, int n, WrsnEtScratch s0) {
+// PTR: the actor's d / d (head2 pre-activation) is given (the score backward wrote it to dz2); the critic's rows are as ever.
+template <bool PTR>
+WDEV void wrsn_et_head_bwd_body(const WrsnEtGroups& gs, int n, const WrsnEtScratch& s0) {
     extern __shared__ double smem[];
     float* sD = (float*)smem;
     const int tid = (int)threadIdx.x;
@@ -444,6 +469,7 @@ __global__ void __launch_bounds__(256) wrsn_et_head_bwd_kernel(WrsnEtGroups gs, 
     if (tid < 128) {
         float g;
         if (net) g = dout[6] * blk[WRSN_EC_VALUE + tid];
+        else if constexpr (PTR) g = s.dz2[base * 128 + tid];
         else {
             g = 0.f;
 #pragma unroll
@@ -475,6 +501,9 @@ __global__ void __launch_bounds__(256) wrsn_et_head_bwd_kernel(WrsnEtGroups gs, 
         }
         s.dfeat[base * WRSN_ENTPOL_FEAT + tid] = (a0 + a1) + (a2 + a3);
     }
+}
+__global__ void __launch_bounds__(256) wrsn_et_head_bwd_kernel(WrsnEtGroups gs, int n, WrsnEtScratch s0) {
+    wrsn_et_head_bwd_body<false>(gs, n, s0);
 }
 
 __global__ void __launch_bounds__(256) wrsn_et_trunk_bwd_kernel(WrsnEtGroups gs, WrsnEtDims dm, WrsnEtScratch s0) {
@@ -649,15 +678,24 @@ __global__ void __launch_bounds__(256) wrsn_et_trunk_bwd_kernel(WrsnEtGroups gs,
 }
 
 // one thread per float of a gradient block; rows in index order
-__global__ void __launch_bounds__(256) wrsn_et_reduce_kernel(WrsnEtGroups gs, int n, WrsnEtScratch s0) {
-    const int nb = (WRSN_EP_FLOATS + 255) / 256;
+// PTR: the actor's block is the node-pointer actor's -- WRSN_PP_FLOATS floats, query and charge behind head2 -- and node1 / node2 add the second partial.
+template <bool PTR>
+WDEV void wrsn_et_reduce_body(const WrsnEtGroups& gs, int n, const WrsnEtScratch& s0, const WrsnEtpScratch& ps, int dmN, int dmM) {
+    const int nb = ((PTR ? WRSN_PP_FLOATS : WRSN_EP_FLOATS) + 255) / 256;
     const int q = (int)blockIdx.x / nb, grp = q >> 1, net = q & 1, p = ((int)blockIdx.x - q * nb) * 256 + (int)threadIdx.x;
-    if (p >= (net ? WRSN_EC_FLOATS : WRSN_EP_FLOATS)) return;
+    if (p >= (net ? WRSN_EC_FLOATS : PTR ? WRSN_PP_FLOATS : WRSN_EP_FLOATS)) return;
     const WrsnEtScratch s = wrsn_et_slice(s0, grp);
     const size_t b0 = (size_t)net * n;
     float a = 0.f;
     if (p < WRSN_EP_HEAD1) {
         for (int i = 0; i < n; ++i) a += s.part[(b0 + i) * WRSN_ET_TRUNK_FLOATS + p];
+        if constexpr (PTR) {
+            if (!net && p < WRSN_EP_MC1) {
+                float b = 0.f;
+                for (int i = 0; i < n; ++i) b += ps.part2[(size_t)i * WRSN_EP_MC1 + p];
+                a += b;
+            }
+        }
     } else if (p < WRSN_EP_HEAD1_B) {
         const int k = (p - WRSN_EP_HEAD1) >> 7, j = (p - WRSN_EP_HEAD1) & 127;
         for (int i = 0; i < n; ++i) a = fmaf(s.feat[(b0 + i) * WRSN_ENTPOL_FEAT + k], s.dz1[(b0 + i) * 128 + j], a);
@@ -671,6 +709,28 @@ __global__ void __launch_bounds__(256) wrsn_et_reduce_kernel(WrsnEtGroups gs, in
     } else if (net) {
         if (p < WRSN_EC_VALUE_B) { for (int i = 0; i < n; ++i) a = fmaf(s.z2[(b0 + i) * 128 + p - WRSN_EC_VALUE], s.dout[(size_t)i * 8 + 6], a); }
         else if (p == WRSN_EC_VALUE_B) { for (int i = 0; i < n; ++i) a += s.dout[(size_t)i * 8 + 6]; }
+    } else if constexpr (PTR) {
+        if (p < WRSN_PP_QUERY_B) {                            // query: z x dq
+            const int k = (p - WRSN_PP_QUERY) >> 6, j = (p - WRSN_PP_QUERY) & 63;
+            for (int i = 0; i < n; ++i) a = fmaf(s.z2[(b0 + i) * 128 + k], ps.dq[(size_t)i * 64 + j], a);
+        } else if (p < WRSN_PP_CHARGE) {
+            for (int i = 0; i < n; ++i) a += ps.dq[(size_t)i * 64 + p - WRSN_PP_QUERY_B];
+        } else if (p < WRSN_PP_CHARGE + 256) {                // charge, rows z: z x (dmu, ds_raw)
+            const int k = (p - WRSN_PP_CHARGE) >> 1, d = (p - WRSN_PP_CHARGE) & 1;
+            for (int i = 0; i < n; ++i) a = fmaf(s.z2[(b0 + i) * 128 + k], ps.dch[(size_t)i * 2 + d], a);
+        } else if (p < WRSN_PP_CHARGE_B) {                    // charge, rows x_k: the stored node's features as they stand, zeros for node -1
+            const int f = (p - WRSN_PP_CHARGE - 256) >> 1, d = (p - WRSN_PP_CHARGE) & 1;
+            const int32_t* index = gs.g[grp].index;
+            const size_t R = (size_t)(WRSN_ENT_NODE_F * dmN + WRSN_ENT_MC_F * dmM + WRSN_ENT_ENV_F);
+            for (int i = 0; i < n; ++i) {
+                const int k = (int)ps.prow[(size_t)i * 8 + 5];
+                const int kk = k < 0 ? 0 : k;
+                const float x = gs.g[grp].rows[(size_t)(index ? index[i] : i) * R + (size_t)kk * WRSN_ENT_NODE_F + f];
+                a = fmaf(k < 0 ? 0.f : x, ps.dch[(size_t)i * 2 + d], a);
+            }
+        } else if (p < WRSN_PP_CHARGE_B + 2) {
+            for (int i = 0; i < n; ++i) a += ps.dch[(size_t)i * 2 + p - WRSN_PP_CHARGE_B];
+        }
     } else {
         if (p < WRSN_EP_MEAN_B) {
             const int k = (p - WRSN_EP_MEAN) / 3, d = (p - WRSN_EP_MEAN) - 3 * k;
@@ -685,6 +745,9 @@ __global__ void __launch_bounds__(256) wrsn_et_reduce_kernel(WrsnEtGroups gs, in
         }
     }
     (net ? gs.g[grp].grad_critic : gs.g[grp].grad_actor)[p] = a;   // the padding: zero
+}
+__global__ void __launch_bounds__(256) wrsn_et_reduce_kernel(WrsnEtGroups gs, int n, WrsnEtScratch s0) {
+    wrsn_et_reduce_body<false>(gs, n, s0, WrsnEtpScratch{}, 0, 0);
 }
 
 // ||g|| of a block, summed by one workgroup in a fixed order: workgroup k takes block k of the table

@@ -1315,13 +1315,23 @@ class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
                    `torch.randn`.  False (the default): `get_action` per charger.
     log_episodes : as `BatchedEntityIPPO`.
 
-    The update of this actor is PyTorch's: there is no fused update, joint update or fused prepare for it yet, and asking for one raises."""
+    device_update: True = `update` runs on the device for ONE learner per call (`wrsn_entity_pointer_ppo_grad`, `wrsn_entity_adam`): the
+                   actor and critic are packed at its start (`pack_entity_pointer_actor`, `pack_entity_critic`), the epochs, shuffles and
+                   minibatches are `PPOLearner.update`'s with one int32 index upload per epoch, and per minibatch there is one gradient call
+                   into one flat tensor [P_pointer + P_critic], (data-parallel: one all-reduce of it,) and one Adam call each for actor and
+                   critic; the statistics go to a device table read once at the end, when the blocks are unpacked into the modules.  The
+                   Adam moments and step counts live in this object in block layout and the torch optimisers are never stepped; `_values`
+                   goes through `wrsn_entity_eval`.  The same return value as the default; `first_minibatch_stats` is filled.  The mode is
+                   fixed at construction.  False (the default): the PyTorch update, nothing new is launched.
+
+    `fused_update`, `joint_update` and `fused_prepare` are the set policy's (BatchedEntityIPPO): there is no joint update or fused prepare for
+    this actor yet, and asking for one of the three raises."""
 
     _check_status = True
 
     def __init__(self, args, env, device=None, model_path=None, capacity=None, infer_chunk=1024, process_group=None, log=None, min_bucket=16,
                  min_charge=0.02, fused_policy=False, log_episodes=False, episode_slots=64, fused_update=False, joint_update=False,
-                 fused_prepare=False):
+                 fused_prepare=False, device_update=False):
         for k, v in (("fused_update", fused_update), ("joint_update", joint_update), ("fused_prepare", fused_prepare)):
             if v:
                 raise ValueError("BatchedEntityPointerIPPO has no %s: the fused update, joint update and prepare exist for the Gaussian set "
@@ -1338,6 +1348,14 @@ class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
             self._ledger = env.new_episode_log(episode_slots, quota=0)
         self.fused_policy = bool(fused_policy)
         self._packed = None                                   # packed_actors() of the weights as they are now, or None: rebuilt before use
+        self.device_update = bool(device_update)
+        self.first_minibatch_stats = [None] * self.num_agent  # device_update: (loss, pg, v_loss, entropy, approx_kl, clipfrac) of an update's first minibatch
+        if self.device_update:
+            torch = self.torch
+            self._pa, self._pc = _lib.ENTITY_POINTER_FLOATS, _lib.ENTITY_CRITIC_FLOATS
+            z = lambda n: torch.zeros(n, dtype=torch.float32, device=env.device)
+            self._grad = z(self._pa + self._pc)               # ONE tensor: what the data-parallel exchange reduces
+            self._adam = [dict(m_a=z(self._pa), v_a=z(self._pa), m_c=z(self._pc), v_c=z(self._pc), step=0) for _ in range(self.num_agent)]
 
     def evaluate_episodes(self, eval_env, episodes=1, deterministic=True, generator=None, **kw):
         """`evaluate_policy` of the actors as they are now (`evaluate.PointerPolicy`) on `eval_env`, another batch than the trainer's."""
@@ -1353,7 +1371,50 @@ class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
 
     def update(self, id, batch, shuffle=np.random.shuffle):
         self._packed = None                                   # the weights change: never carried across an update
+        if self.device_update:
+            return self._update_device(id, batch, shuffle)
         return super().update(id, batch, shuffle)
+
+    def _values(self, agent_id, states):
+        if not self.device_update:
+            return super()._values(agent_id, states)
+        torch = self.torch
+        blk = pack_entity_critic(self.critics[agent_id]).to(self.env.device)
+        return self.env.entity_eval(states.to(torch.float32).contiguous(), critic=blk)[2]
+
+    def _update_device(self, id, batch, shuffle):
+        """`PPOLearner.update` on the device, as `BatchedEntityIPPO._update_fused`: the same epochs, shuffles, minibatches and return value."""
+        torch, env = self.torch, self.env
+        dev = env.device
+        f32 = lambda x: x.to(device=dev, dtype=torch.float32).contiguous()
+        blk_a, blk_c = f32(pack_entity_pointer_actor(self.actors[id])), f32(pack_entity_critic(self.critics[id]))
+        rows = f32(batch["states"])
+        b = {"actions": f32(batch["actions"]).reshape(-1, 2), "log_probs": f32(batch["log_probs"]), "advantages": f32(batch["advantages"]),
+             "returns": f32(batch["returns"]), "values": f32(batch["values"])}
+        hyper = dict(clip=self.clip, ent_coef=self.ent_coef, vf_coef=self.vf_coef, norm_adv=self.norm_adv, clip_vloss=self.clip_vloss)
+        per_epoch = (self.batch_size + self.minibatch_size - 1) // self.minibatch_size
+        table = torch.zeros((self.n_updates_per_iteration * per_epoch, 8), dtype=torch.float32, device=dev)
+        st, ga, gc, lr = self._adam[id], self._grad[:self._pa], self._grad[self._pa:], self.args["lr"]
+        b_inds = np.arange(self.batch_size)
+        k, keep = 0, []
+        for _ in range(self.n_updates_per_iteration):
+            shuffle(b_inds)
+            idx = torch.from_numpy(b_inds.astype(np.int32)).to(dev)      # uploaded once per epoch
+            keep.append(idx)                                          # the launches are asynchronous: alive until the table is read
+            for start in range(0, self.batch_size, self.minibatch_size):
+                env.entity_pointer_ppo_grad(blk_a, blk_c, rows, idx[start:start + self.minibatch_size], b, hyper, self._grad, table[k])
+                if self.world > 1:
+                    torch.distributed.all_reduce(self._grad, group=self.group)
+                    self._grad /= self.world
+                st["step"] += 1
+                env.entity_adam(blk_a, ga, st["m_a"], st["v_a"], st["step"], lr, self.max_grad_norm)
+                env.entity_adam(blk_c, gc, st["m_c"], st["v_c"], st["step"], lr, self.max_grad_norm)
+                k += 1
+        unpack_entity_pointer_actor(blk_a, self.actors[id]); unpack_entity_critic(blk_c, self.critics[id])
+        t = table.cpu().numpy().astype(np.float64)                   # the one read of the update
+        self.loggers[id]["losses"].extend(float(x) for x in t[:, 0])
+        self.first_minibatch_stats[id] = tuple(float(x) for x in t[0, :6])
+        return (float(t[-1, 1]), float(t[-1, 2]), float(t[-1, 3]), float(t[-1, 4]), float(np.mean(t[:, 5])))
 
     def _choose(self, r, ids):
         torch, env = self.torch, self.env

@@ -501,6 +501,40 @@ class VecWRSN:
                                 hyper["ent_coef"], hyper["vf_coef"], hyper["norm_adv"], hyper["clip_vloss"], grad.data_ptr(),
                                 grad.data_ptr() + 4 * Pa, stats.data_ptr())
 
+    def entity_pointer_eval(self, rows, stored=None, actor=None, critic=None, index=None, node_logp=False):
+        """`wrsn_entity_pointer_eval`: the packed node-pointer actor and / or critic block on packed entity rows [*, R] and the stored
+        decisions `stored` [*, 2] = (node, x), indexed like the rows (row index[i] for minibatch row i; None: all rows in order).  Returns
+        a dict of new float32 tensors: logp [n], entropy [n], mean [n], log_std [n] (and node_logp [n, N] when asked) with an actor,
+        value [n] with a critic."""
+        t = self.torch
+        self._bind_stream()
+        rp, ip, n, N, M = self._entity_rows(rows, index)
+        new = lambda *sh: t.empty(sh, dtype=t.float32, device=rows.device)
+        o = {}
+        if actor is not None:
+            if stored is None or not (stored.dtype == t.float32 and stored.is_contiguous()):
+                raise ValueError("stored must be a contiguous float32 tensor [*, 2]")
+            o.update(logp=new(n), entropy=new(n), mean=new(n), log_std=new(n))
+            if node_logp:
+                o["node_logp"] = new(n, N)
+        if critic is not None:
+            o["value"] = new(n)
+        ptr = lambda x: 0 if x is None else x.data_ptr()
+        self._h.entity_pointer_eval(ptr(actor), ptr(critic), rp, ip, n, N, M, ptr(stored) if actor is not None else 0, ptr(o.get("logp")),
+                                    ptr(o.get("entropy")), ptr(o.get("node_logp")), ptr(o.get("mean")), ptr(o.get("log_std")), ptr(o.get("value")))
+        return o
+
+    def entity_pointer_ppo_grad(self, actor, critic, rows, index, batch, hyper, grad, stats):
+        """`wrsn_entity_pointer_ppo_grad`: `entity_ppo_grad` for the node-pointer actor; batch["actions"] is the stored decisions [*, 2] and
+        grad ONE contiguous float32 tensor [wrsn_entity_pointer_floats() + wrsn_entity_critic_floats()] (overwritten)."""
+        self._bind_stream()
+        rp, ip, n, N, M = self._entity_rows(rows, index)
+        Pa = self._h.lib.wrsn_entity_pointer_floats()
+        self._h.entity_pointer_ppo_grad(actor.data_ptr(), critic.data_ptr(), rp, ip, n, N, M, batch["actions"].data_ptr(),
+                                        batch["log_probs"].data_ptr(), batch["advantages"].data_ptr(), batch["returns"].data_ptr(),
+                                        batch["values"].data_ptr(), hyper["clip"], hyper["ent_coef"], hyper["vf_coef"], hyper["norm_adv"],
+                                        hyper["clip_vloss"], grad.data_ptr(), grad.data_ptr() + 4 * Pa, stats.data_ptr())
+
     def entity_adam(self, param, grad, m, v, step, lr, max_norm, beta1=0.9, beta2=0.999, eps=1e-8, norm_out=None):
         """`wrsn_entity_adam`: clip_grad_norm_(max_norm) and one Adam step in place on the block `param` with moments m, v."""
         self._bind_stream()
