@@ -93,7 +93,9 @@ enum wrsn_peek_what {
     WRSN_PEEK_NODE_STATUS = 3,   /* int32  [B,N]   Node.status                                    */
     WRSN_PEEK_NODE_LEVEL = 4,    /* int32  [B,N]   Node.level                                     */
     WRSN_PEEK_MC = 5,            /* double [B,M,16] loc_x, loc_y, energy, status, charging, cur_x, cur_y,
-                                                    cur_t, n_conn, excl, prev_minfit, act0, act1, act2, 0, 0 */
+                                                    cur_t, n_conn, excl, prev_minfit, act0, act1, act2, error, 0
+                                                    (error: the ENVIRONMENT's error code behind a row of status
+                                                    WRSN_ERR_CAPACITY, 0 = none, the same in every charger's row) */
     WRSN_PEEK_ENV = 6,           /* double [B,16]  xmin,xmax,ymin,ymax,density,moving_time_max,charging_time_max,
                                                     avg_nodes_agent,now,alive,ticks,exact_ticks,events,min_fitness,
                                                     n_edges,n_cover                                 */

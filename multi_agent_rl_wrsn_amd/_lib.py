@@ -18,6 +18,7 @@ ERR_NAMES = {0: "WRSN_OK", -1: "WRSN_ERR_ARG", -2: "WRSN_ERR_HIP", -3: "WRSN_ERR
 PEEK_NODE_ENERGY, PEEK_NODE_CS, PEEK_NODE_RR, PEEK_NODE_STATUS, PEEK_NODE_LEVEL = 0, 1, 2, 3, 4
 PEEK_MC, PEEK_ENV, PEEK_NODE_DEGREE, PEEK_NODE_NCOVER, PEEK_NODE_DIRECT = 5, 6, 7, 8, 9
 PEEK_TARGETS_ACTIVE = 11
+REC_CONN_BOUND_OFFSET = 44   # byte offset of WrsnRecHeader.conn_bound (int32) in an environment record (csrc/wrsn_state.h)
 PEEK_POOL = 13               # int32 [B, 2]: the pool record the environment runs (-1: none), its swaps since wrsn_pool_set
 STATUS_POOL_INDEX = -5       # per-row status of wrsn_pool_reset: pool_index outside the pool, row left as it was
 PEEK_RNG_STATE = 12          # uint32 [B, 627]: MT19937 words, index (random.getstate()[1]), draws since reset (low, high word)
@@ -34,7 +35,7 @@ ENTITY_ACTOR_FLOATS, ENTITY_CRITIC_FLOATS = 49224, 48580   # wrsn_entity_actor_f
 ENTITY_POINTER_FLOATS = 56980   # wrsn_entity_pointer_floats(): the block of the node-pointer actor (include/wrsn_hip.h)
 ENTPOL_FEAT = 200            # wrsn_entity_act: inputs of the actor's head (64 mean + 64 max + 32 charger mean + 32 own + 8 env)
 MC_FIELDS = ("loc_x", "loc_y", "energy", "status", "type_charging", "cur_x", "cur_y", "cur_t", "n_conn",
-             "excl", "prev_minfit", "act0", "act1", "act2", "_r0", "_r1")
+             "excl", "prev_minfit", "act0", "act1", "act2", "error", "_r1")
 ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max", "charging_time_max",
               "avg_nodes_agent", "now", "alive", "n_ticks", "n_exact", "n_events", "min_fitness", "n_edges", "n_cover")
 

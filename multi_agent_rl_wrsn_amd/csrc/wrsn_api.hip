@@ -1518,7 +1518,7 @@ int wrsn_peek(wrsn_t* h, int32_t what, void* dst) {
                 const WrsnAgent& a = dy[e].ag[m]; double* q = o + (e * d.M + m) * 16;
                 q[0] = a.loc[0]; q[1] = a.loc[1]; q[2] = a.energy; q[3] = a.status; q[4] = a.type_charging;
                 q[5] = a.cur[0]; q[6] = a.cur[1]; q[7] = a.cur[2]; q[8] = a.n_conn; q[9] = a.excl; q[10] = a.prev_minfit;
-                q[11] = a.action[0]; q[12] = a.action[1]; q[13] = a.action[2]; q[14] = 0; q[15] = 0;
+                q[11] = a.action[0]; q[12] = a.action[1]; q[13] = a.action[2]; q[14] = dy[e].error; q[15] = 0;
             }
         return 0; }
     case WRSN_PEEK_ENV: {

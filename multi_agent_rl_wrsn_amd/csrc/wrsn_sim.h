@@ -188,7 +188,13 @@ WDEV int wv_scan_incl(int v, int lane) {
     return v;
 }
 
+// Charger arithmetic (positions, distances, charging rates, clocks) is held to the reference operation by operation: Node.energyRR is
+// compared to the ulp (tests/test_action_streams.py), and a fused multiply-add in `loc + u * span` or `dx * dx + dy * dy` moves a
+// position by an ulp, which arrives in alpha / (d + beta)^2 as several ulps of the rate.  The functions below keep the compiler from
+// contracting; the per-node loops of the grid keep their FMAs.
+#define WRSN_EXACT_FP _Pragma("clang fp contract(off)")
 WDEV double dist2(double ax, double ay, double bx, double by) {
+    WRSN_EXACT_FP
     double dx = ax - bx, dy = ay - by;
     return sqrt(dx * dx + dy * dy);
 }
@@ -346,7 +352,14 @@ struct Sim : SimStochRegs<STOCH> {
     // Node.energyRR (Node.py:31, 137-146) as a SPARSE list of the nodes whose charging rate is not zero: at most a few nodes are inside the
     // charging range of a charger at a time (r02 kept a float64 per node in LDS: 8 KB at 1 024 nodes, the difference between three and four
     // environments per CU there)
-    WDEV int RRCAP() const { return M * CC + 32; }
+    // Capacity (wrsn_rr_cap): one entry per node up to 512 nodes -- the list cannot fill.  Above, M * CC + 32 entries in LDS and the rest
+    // SPILLS to the node's word of the live energyRR row in HBM (kRRSpill): rounding residues of overlapping chargers and the rates
+    // of nodes that died while connected stay for the rest of an episode (Node.py:135, 142), so no fixed number bounds them.  While
+    // SRRN()[1] > 0 nodes are spilled, a non-zero word of the row IS a spilled entry and every other word of it is zero; store() writes the
+    // row back dense, load() splits it again.
+    static constexpr bool kRRSpill = NPL > 8;
+    WDEV int RRCAP() const { return wrsn_rr_cap(NP, M, CC); }
+    WDEV double WRSN_GLOBAL_AS* RRROW() const { return wrsn_global(dp->live.RR + (size_t)env * NP); }
     WDEV double* SRRV() const { return SURACC() + M * CC; }                             // [RRCAP] rates
     WDEV double* SREQD() const { return SRRV() + RRCAP(); }                             // [0] time limit, [1] now, [2] seq (as int64), [3] spare
     WDEV Scalar* SS() const { return (Scalar*)(SREQD() + 4); }
@@ -355,8 +368,8 @@ struct Sim : SimStochRegs<STOCH> {
     WDEV int32_t* SCTR() const { return SCA() + (M + 1); }
     WDEV int32_t* SCP() const { return SCTR() + (M + 1); }
     WDEV int32_t* SURN() const { return SCP() + (M + 1); }
-    WDEV int32_t* SRRN() const { return SURN() + 1; }                                   // entries of the charging-rate list
-    WDEV int16_t* SCONN() const { return (int16_t*)(SRRN() + 1); }
+    WDEV int32_t* SRRN() const { return SURN() + 1; }                                   // [0] entries of the charging-rate list, [1] spilled nodes
+    WDEV int16_t* SCONN() const { return (int16_t*)(SRRN() + 2); }
     WDEV int16_t* SURIDX() const { return SCONN() + M * CC; }
     WDEV int16_t* SURAGENT() const { return SURIDX() + M * CC; }
     WDEV int16_t* SRRI() const { return SURAGENT() + M * CC; }                          // [RRCAP] nodes of the charging-rate list
@@ -371,14 +384,36 @@ struct Sim : SimStochRegs<STOCH> {
                 return;
             }
         }
+        if constexpr (kRRSpill) {
+            if (SRRN()[1] > 0) {                              // a spilled node: its word of the row
+                const double h = RRROW()[i];
+                if (h != 0.0) { const double v = h + delta; RRROW()[i] = v; if (v == 0.0) SRRN()[1] -= 1; return; }
+            }
+        }
         if (delta == 0.0) return;
-        if (n >= RRCAP()) { err = -11; return; }
+        if (n >= RRCAP()) {
+            if constexpr (kRRSpill) {
+                if (SRRN()[1] == 0) for (int q = 0; q < N; ++q) RRROW()[q] = 0.0;     // the first spilled node: the row is what load() read
+                RRROW()[i] = delta; SRRN()[1] += 1;
+            } else err = -11;                                // cannot happen: the list of these kernels holds every node
+            return;
+        }
         SRRI()[n] = (int16_t)i; SRRV()[n] = delta; SRRN()[0] = n + 1;
     }
     // scale * energyRR of the lane's nodes
     WDEV void rr_slots(double (&out)[NPL], double scale) const {
 #pragma unroll
         for (int j = 0; j < NPL; ++j) out[j] = 0.0;
+        if constexpr (kRRSpill) {
+            if (SRRN()[1] > 0) {                              // spilled nodes (never in the list as well); rare: one slot at a time
+#pragma unroll 1
+                for (int jj = 0; jj < NPL; ++jj) {
+                    const int i = jj * 64 + lane; const double v = i < N ? RRROW()[i] * scale : 0.0;
+#pragma unroll
+                    for (int j = 0; j < NPL; ++j) out[j] = (j == jj) ? v : out[j];
+                }
+            }
+        }
         const int n = SRRN()[0];
         for (int k = 0; k < n; ++k) {
             const int i = SRRI()[k]; const double v = SRRV()[k] * scale;
@@ -713,8 +748,22 @@ struct Sim : SimStochRegs<STOCH> {
                 if (nz && pos < RRCAP()) { SRRI()[pos] = (int16_t)i; SRRV()[pos] = rr[j]; }
                 base += __popcll(mk);
             }
-            if (base > RRCAP()) { err = -11; base = RRCAP(); }
-            if (lane == 0) SRRN()[0] = base;
+            int spilled = 0;
+            if constexpr (kRRSpill) {
+                if (base > RRCAP()) {                         // the live row takes the spilled nodes, zero elsewhere (`a` may be the snapshot)
+                    spilled = base - RRCAP(); base = RRCAP();
+                    int seen = 0;                             // rare: the row is read again, one slot at a time
+#pragma unroll 1
+                    for (int j = 0; j < NPL; ++j) {
+                        const int i = j * 64 + lane; const double v = i < N ? gRR[i] : 0.0;
+                        const unsigned long long mk = __ballot(v != 0.0);
+                        const int pos = seen + __popcll(mk & ((1ull << lane) - 1ull));
+                        if (i < N) RRROW()[i] = (v != 0.0 && pos >= RRCAP()) ? v : 0.0;
+                        seen += __popcll(mk);
+                    }
+                }
+            }
+            if (lane == 0) { SRRN()[0] = base; SRRN()[1] = spilled; }
         }
         if (lane == 0) { SREQ()[0] = 0; SREQ()[1] = 0; SREQ()[2] = n_conn0; SS()->n_events = n_ev0; SURN()[0] = 0; }
         __syncthreads();
@@ -1307,6 +1356,7 @@ struct Sim : SimStochRegs<STOCH> {
     // alpha / (dist(node, charger) + beta)^2 (Node.py:137, WRSN.py:122) of connected node k of charger m at the charger's
     // CURRENT location (a stale "charging" charger may be on the move); node positions were cached by conn_build
     WDEV double conn_rate_of(int m, int k, int i) const {
+        WRSN_EXACT_FP
         (void)i;
         const double* xy = SCONNXY() + 2 * (m * CC + k);
         double dd = dist2(xy[0], xy[1], SAG()[m].loc[0], SAG()[m].loc[1]) + EC()->beta;
@@ -1817,16 +1867,19 @@ struct Sim : SimStochRegs<STOCH> {
     }
 
     WDEV void ff_apply(int ti, double t, bool all) {
+        WRSN_EXACT_FP
         const int a = STH()[ti].agent;
         int n = STH()[ti].ff_n; double ft = STH()[ti].ff_t;
         if (STH()[ti].ff == 1) {
             const double ux = STH()[ti].mvec[0] / STH()[ti].total_time * 1.0, uy = STH()[ti].mvec[1] / STH()[ti].total_time * 1.0;
             const double de = EC()->pm * 1.0 * EC()->velocity;
-            // closed form of m identical unit sub-steps: positions / energy differ from the step-by-step sums by a few
-            // ulps (1e-13 relative), the time is accumulated exactly like successive `now + 1.0`
+            // m identical unit sub-steps, added one by one as MobileCharger.py:77-78 adds them: the position a charger arrives with goes
+            // into every charging rate of the stay (Node.py:137), where the few ulps of a closed form `m * u` show as tens of ulps of
+            // Node.energyRR.  A move is a few hundred sub-steps at the most; the time is accumulated like successive `now + 1.0`
             const int m = all ? n : due_units(ft, t, n);
-            const double dm = (double)m;
-            SAG()[a].loc[0] = SAG()[a].loc[0] + dm * ux; SAG()[a].loc[1] = SAG()[a].loc[1] + dm * uy; SAG()[a].energy = SAG()[a].energy - dm * de;
+            double lx = SAG()[a].loc[0], ly = SAG()[a].loc[1], en = SAG()[a].energy;
+            for (int q = 0; q < m; ++q) { lx = lx + ux; ly = ly + uy; en -= de; }
+            SAG()[a].loc[0] = lx; SAG()[a].loc[1] = ly; SAG()[a].energy = en;
             ft = add_ones(ft, m); n -= m;
         } else if (STH()[ti].ff == 2) {
             const double cr = SAG()[a].charging_rate;
@@ -1856,6 +1909,7 @@ struct Sim : SimStochRegs<STOCH> {
     }
 
     WDEV void mc_move_loop(int ti) {                         // MobileCharger.py:85-94 from the top of `while True`
+        WRSN_EXACT_FP
         int a = STH()[ti].agent;
         if (STH()[ti].moving_time <= 0.0) { th_sched(ti, PC_MOVE_DONE, WRSN_NORMAL, now); return; }
         if (SAG()[a].status == 0) { th_sched(ti, PC_MOVE_DEADWAIT, WRSN_NORMAL, now + STH()[ti].moving_time); return; }
@@ -1899,6 +1953,7 @@ struct Sim : SimStochRegs<STOCH> {
     }
 
     WDEV void mc_charge_loop(int ti) {                       // MobileCharger.py:59-69 from the top of `while True`
+        WRSN_EXACT_FP
         int a = STH()[ti].agent;
         if (STH()[ti].tmp == 0.0) { th_sched(ti, PC_CHG_DONE, WRSN_NORMAL, now); return; }
         if (SAG()[a].status == 0) { SAG()[a].cur[2] = 0.0; th_sched(ti, PC_CHG_DEADWAIT, WRSN_NORMAL, now + STH()[ti].tmp); return; }
@@ -1937,6 +1992,7 @@ struct Sim : SimStochRegs<STOCH> {
     }
 
     WDEV void p_init_tail(int ti, double tmp) {              // MobileCharger.py:110, 116-121 / 128-130
+        WRSN_EXACT_FP
         const int a = STH()[ti].agent;
         const double dx = STH()[ti].phy[0], dy = STH()[ti].phy[1], ct = STH()[ti].phy[2];
         double used = dist2(dx, dy, SAG()[a].loc[0], SAG()[a].loc[1]) * EC()->pm;
@@ -1957,6 +2013,7 @@ struct Sim : SimStochRegs<STOCH> {
 
     // returns a wave request (REQ_PRECHECK / REQ_CONN) or 0
     WDEV int thread_fire(int ti) {
+        WRSN_EXACT_FP
         const int a = STH()[ti].agent;
         if (STH()[ti].ff != 0) ff_apply(ti, now, true);        // the resume event: every virtual sub-step precedes it
         WRSN_PROF_EV(STH()[ti].pc, 1)
@@ -2353,7 +2410,7 @@ __global__ void __launch_bounds__(64, WRSN_WAVES_PER_SIMD(NPL)) wrsn_warmup_kern
     for (int w = lane; w <= s.M; w += 64) { s.SCTR()[w] = 0; s.SCP()[w] = 0; s.SCA()[w] = 0; s.SCT()[w] = 0; s.SCS()[w] = 0; }
     __syncthreads();
     if (lane == 0) {
-        s.SREQ()[0] = 0; s.SREQ()[1] = 0; s.SREQ()[2] = 0; s.SURN()[0] = 0; s.SRRN()[0] = 0;
+        s.SREQ()[0] = 0; s.SREQ()[1] = 0; s.SREQ()[2] = 0; s.SURN()[0] = 0; s.SRRN()[0] = 0; s.SRRN()[1] = 0;
         s.warmup_init_chargers();
     }
     s.warmup_first_items();
@@ -2399,7 +2456,7 @@ __device__ __forceinline__ void wrsn_warmup_stoch_env(const WrsnDev* __restrict_
     for (int w = lane; w <= s.M; w += 64) { s.SCTR()[w] = 0; s.SCP()[w] = 0; s.SCA()[w] = 0; s.SCT()[w] = 0; s.SCS()[w] = 0; }
     __syncthreads();
     if (lane == 0) {
-        s.SREQ()[0] = 0; s.SREQ()[1] = 0; s.SREQ()[2] = 0; s.SURN()[0] = 0; s.SRRN()[0] = 0;
+        s.SREQ()[0] = 0; s.SREQ()[1] = 0; s.SREQ()[2] = 0; s.SURN()[0] = 0; s.SRRN()[0] = 0; s.SRRN()[1] = 0;
         s.warmup_init_chargers();
     }
     s.warmup_first_items();
@@ -2503,9 +2560,12 @@ __device__ __forceinline__ void wrsn_step_env(const WrsnDev* __restrict__ dp, in
                 double act[3];
                 for (int k = 0; k < 3; ++k) { double v = act_src[k]; act[k] = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v); }   // np.clip (WRSN.py:299)
                 s.SAG()[aid].action[0] = act[0]; s.SAG()[aid].action[1] = act[1]; s.SAG()[aid].action[2] = act[2];
-                double p0 = act[0] * (ec->frame[1] - ec->frame[0]) + ec->frame[0];  // translate (WRSN.py:95-98)
-                double p1 = act[1] * (ec->frame[3] - ec->frame[2]) + ec->frame[2];
-                double p2 = ec->charging_time_max * act[2];
+                double p0, p1, p2;
+                {   WRSN_EXACT_FP
+                    p0 = act[0] * (ec->frame[1] - ec->frame[0]) + ec->frame[0];  // translate (WRSN.py:95-98)
+                    p1 = act[1] * (ec->frame[3] - ec->frame[2]) + ec->frame[2];
+                    p2 = ec->charging_time_max * act[2];
+                }
                 int ti = s.new_thread(aid, p0, p1, p2);
                 if (ti < 0) s.err = -8; else s.SAG()[aid].cur_thread = ti;
                 s.SAG()[aid].prev_minfit = s.last_minfit;      // WRSN.py:304 (node state is unchanged since the last return)

@@ -61,9 +61,9 @@ struct WrsnEnvDyn {
     int32_t fit_dirty, map1_valid;           // node state changed (a grid service ran) since last_minfit was evaluated / since map 1 of the
     uint64_t map1_ptr;                       // observation was rendered into the row at this address (wrsn_set_obs_reuse; written by the observation kernel)
     int32_t n_connected, error, log_pending, susp;   // susp: WRSN.step in flight (work budget of a launch used up)
-    // error (0 = none; the row reports status WRSN_ERR_CAPACITY and the code stays readable through wrsn_peek): -6 event loop guard, -7 no
+    // error (0 = none; the row reports status WRSN_ERR_CAPACITY and the code is slot 14 of every charger's WRSN_PEEK_MC row): -6 event loop guard, -7 no
     // event and no grid item, -8 no free process record, -9 connection list longer than its bound, -10 service loop ran out, -11 charging-rate
-    // list full (more than M * CC + 32 nodes with a non-zero energyRR)
+    // list full (cannot happen: the list holds every node or spills, wrsn_rr_cap)
     // work-queue launches (wrsn_set_step_deadline): the action of a WRSN.step call that no wave has taken up yet (wrsn_latch_kernel); the
     // environment may wait for its turn over several launches, during which the caller's row says "in flight" and is ignored
     int32_t lat_valid, lat_agent; double lat_action[3];
@@ -145,10 +145,16 @@ struct WrsnStepOutDev {
 // environments of 1 024 nodes x 8 chargers then fit the 160 KB of a CU instead of two)
 #define WRSN_CHG_MAX(NP_) ((NP_) > 512 ? 6 : ((NP_) > 256 ? 8 : 4))
 // LDS of one environment wave; must match the carve-up of Sim (wrsn_sim.h)
+// entries of the sparse charging-rate list (Node.energyRR) in LDS: every node up to 512 nodes; above, the nodes the chargers can hold at
+// once and 32 more, beyond which entries spill to the energyRR row in HBM (wrsn_sim.h, kRRSpill)
+#if defined(__HIPCC__) || defined(__CUDACC__)
+__host__ __device__
+#endif
+static inline int wrsn_rr_cap(int NP, int M, int CC) { return NP <= 512 ? NP : M * CC + 32; }
 static inline int wrsn_lds_bytes(int NP, int M, int CC) {
     int b = 0;
     b += 2 * NP * 8 + 2 * NP * 4;                     // 2 scratch arrays, level/alive words, cached receivers
-    b += (M * CC + 32) * (8 + 2) + 4;                 // the charging rates (Node.energyRR) as a sparse list: rates, nodes, count
+    b += wrsn_rr_cap(NP, M, CC) * (8 + 2) + 2 * 4;    // the charging rates as a sparse list: rates, nodes, count, spilled nodes
     b += M * (int)sizeof(WrsnAgent) + 2 * M * (int)sizeof(WrsnThread);
     b += (M + 1) * (8 + 8);                           // condition times / seqs
     b += 4 * M * CC * 8;                              // connected-node positions (x, y), reward-entry rates and accumulators

@@ -797,6 +797,9 @@ void wo_peek_nodes(const wo_t *w, double *E, double *CS, double *RR, int32_t *st
     }
 }
 
+/* TEST-ONLY setter: Node.energyRR of every node, for tests that start both sides from a constructed charging-rate state */
+void wo_set_node_rr(wo_t *w, const double *RR) { for (int i = 0; i < w->N; i++) w->RR[i] = RR[i]; }
+
 /* per MC: loc x, loc y, energy, status, type_charging, cur0, cur1, cur2, n_conn, excl, prev_minfit, action0..2 -> 14 doubles */
 void wo_peek_mcs(const wo_t *w, double *out) {
     for (int m = 0; m < w->M; m++) {

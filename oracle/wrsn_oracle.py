@@ -49,6 +49,7 @@ def lib():
         L.wo_step.argtypes = [C.c_void_p, C.c_int, dp, C.POINTER(WoOut)]
         L.wo_get_state.argtypes = [C.c_void_p, C.c_int, dp]
         L.wo_peek_nodes.argtypes = [C.c_void_p, dp, dp, dp, ip, ip]
+        L.wo_set_node_rr.argtypes = [C.c_void_p, dp]
         L.wo_peek_mcs.argtypes = [C.c_void_p, dp]
         L.wo_peek_env.argtypes = [C.c_void_p, dp]
         L.wo_peek_topology.argtypes = [C.c_void_p, ip, ip, ip]
@@ -143,6 +144,11 @@ class OracleWRSN:
         st = np.empty(self.N, dtype=np.int32); lv = np.empty(self.N, dtype=np.int32)
         lib().wo_peek_nodes(self._h, _dp(E), _dp(CS), _dp(RR), _ip(st), _ip(lv))
         return {"energy": E, "cs": CS, "rr": RR, "status": st, "level": lv}
+
+    def set_node_rr(self, rr):
+        """TEST-ONLY: replace Node.energyRR of every node (a constructed charging-rate state, tests/test_action_streams.py)."""
+        a = np.ascontiguousarray(rr, dtype=np.float64).reshape(self.N)
+        lib().wo_set_node_rr(self._h, _dp(a))
 
     def mcs(self):
         a = np.empty((self.M, 14))
