@@ -44,9 +44,11 @@ def main():
     ap.add_argument("--fused-update", action="store_true", help="with --policy entity: the PPO update runs on the device (wrsn_entity_ppo_grad, "
                     "wrsn_entity_adam, BatchedEntityIPPO(fused_update=True)) instead of PyTorch autograd and torch.optim.Adam")
     ap.add_argument("--joint-update", action="store_true", help="implies --fused-update: every charger's update goes through the same launches behind "
-                    "one call (wrsn_entity_ppo_update, BatchedEntityIPPO(joint_update=True))")
+                    "one call (wrsn_entity_ppo_update, BatchedEntityIPPO(joint_update=True)); with --policy pointer it implies --device-update "
+                    "(wrsn_entity_pointer_ppo_update, BatchedEntityPointerIPPO(joint_update=True))")
     ap.add_argument("--fused-prepare", action="store_true", help="implies --fused-update: values, GAE and the gathers of every charger's batch in one device "
-                    "call (wrsn_entity_prepare, BatchedEntityIPPO(fused_prepare=True)) instead of index_select and cal_rt_adv per charger")
+                    "call (wrsn_entity_prepare, BatchedEntityIPPO(fused_prepare=True)) instead of index_select and cal_rt_adv per charger; with --policy pointer "
+                    "it implies --device-update (BatchedEntityPointerIPPO(fused_prepare=True))")
     ap.add_argument("--device-update", action="store_true", help="with --policy pointer: the PPO update runs on the device (wrsn_entity_pointer_ppo_grad, "
                     "wrsn_entity_adam, BatchedEntityPointerIPPO(device_update=True)) instead of PyTorch autograd and torch.optim.Adam")
     ap.add_argument("--min-charge", type=float, default=0.02, help="with --policy pointer: the least third component of an action "
@@ -54,7 +56,10 @@ def main():
     ap.add_argument("--report-updates", action="store_true", help="add peak device memory and the statistics of every update (first minibatch included) to the line")
     args = ap.parse_args()
     if args.joint_update or args.fused_prepare:
-        args.fused_update = True
+        if args.policy == "pointer":
+            args.device_update = True
+        else:
+            args.fused_update = True
     if args.fused_policy and args.policy not in ("entity", "pointer"):
         raise SystemExit("--fused-policy needs --policy entity or --policy pointer")
     if args.fused_update and args.policy != "entity":
@@ -87,7 +92,8 @@ def main():
                       render=False, entities=True)
         algo = BatchedEntityPointerIPPO(ppo_args, env, capacity=max(2 * args.batch_size, 4096), infer_chunk=args.infer_chunk, min_bucket=args.infer_chunk,
                                         fused_policy=args.fused_policy, min_charge=args.min_charge,
-                                        **({"device_update": True} if args.device_update else {}))
+                                        **({"device_update": True} if args.device_update else {}), **({"joint_update": True} if args.joint_update else {}),
+                                        **({"fused_prepare": True} if args.fused_prepare else {}))
     elif entity:
         env = VecWRSN([synth_scenario(rank * B + e, N, N) for e in range(B)], None, M, auto_reset=True, step_budget=args.step_budget, device=str(dev),
                       render=False, entities=True)             # no image at all: 6.6 KB of entity rows per request
@@ -156,7 +162,9 @@ def main():
         out["config"]["workload"] = "%d envs x %d nodes x %d MC, node-pointer actor + set critic per charger on entity rows, (node, x) actions, batch %d / minibatch %d / %d epochs" % (
             B, N, M, args.batch_size, args.minibatch_size, args.updates)
         out["config"]["policy"] = "float32, entity rows, no image" + (", actions sampled on the device (wrsn_entity_pointer_act)" if args.fused_policy else "") + (
-            ", update on the device (wrsn_entity_pointer_ppo_grad, wrsn_entity_adam)" if args.device_update else "")
+            ", update on the device (wrsn_entity_pointer_ppo_grad, wrsn_entity_adam)" if args.device_update else "") + (
+            ", every charger in one call (wrsn_entity_pointer_ppo_update)" if args.joint_update else "") + (
+            ", batch prepared on the device (wrsn_entity_prepare)" if args.fused_prepare else "")
     if args.report_updates:
         out["peak_memory_bytes"] = int(torch.cuda.max_memory_allocated(dev)); out["updates"] = updates
     print(json.dumps(out, default=float), flush=True)

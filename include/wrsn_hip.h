@@ -615,6 +615,34 @@ int wrsn_entity_ppo_update(wrsn_t *h, const wrsn_entity_group *groups, int32_t n
                            int32_t batch_size, int32_t minibatch, int32_t epochs, const wrsn_ppo_hyper *hyper, const wrsn_adam_hyper *adam,
                            float *stats);
 
+/* ---- the same three calls for the node-pointer policy.  They reuse wrsn_entity_group as it stands; for these calls
+ *   - actor, m_actor, v_actor and grad_actor hold wrsn_entity_pointer_floats() floats (56 980), critic and its buffers as above;
+ *   - batch.action is the [*, 2] stored pair ((float)node, x) of wrsn_pointer_batch, indexed like the rows.
+ * The single-group calls they stand for are wrsn_entity_pointer_ppo_grad, and wrsn_entity_adam once on the actor block (56 980 floats)
+ * and once on the critic block.  Everything stated above holds with these in place of wrsn_entity_ppo_grad / wrsn_entity_adam:
+ *
+ * wrsn_entity_pointer_ppo_grad_multi: wrsn_entity_pointer_ppo_grad for every group, ten launches however large G is.  index: DEVICE int32
+ * [G][n] or NULL (rows 0 .. n - 1 for every group); stats: DEVICE float32 [G][8].  adam_step and the moments are not read.
+ * wrsn_entity_pointer_adam_multi: wrsn_entity_adam on the 2 G blocks, two launches, group g at adam_step + 1, each block clipped by its
+ * own norm.  rows and batch are not read.  The caller advances its step counts.
+ * wrsn_entity_pointer_ppo_update: `epochs` x ceil(batch_size / minibatch) steps of the two; index: DEVICE int32 [G][epochs][batch_size]
+ * (required), stats: DEVICE float32 [G][steps][8]; step k steps group g at adam_step + 1 + k.  The host loop only enqueues on the
+ * handle's stream: nothing is read back, nothing synchronises, and the scratch of the largest step is taken before the loop.
+ *
+ * CONTRACT.  After a multi call, group g's blocks, moments, gradient buffers and statistics row hold THE BYTES the single-group calls
+ * give on the same inputs in the same order, whatever G is (1 <= G <= 8), whatever the other groups hold and wherever g stands among
+ * them.  Two calls on equal inputs give equal bytes.
+ *
+ * WRSN_ERR_ARG, with every buffer untouched and everything checked before the first launch: every case listed for the three calls above;
+ * norm_adv when any minibatch, the short last one included, has fewer than 2 rows; more nodes than the score block's LDS holds.
+ * OUT OF SCOPE, as above: HIP-graph capture, a device-side shuffle, groups of different shape. */
+int wrsn_entity_pointer_ppo_grad_multi(wrsn_t *h, const wrsn_entity_group *groups, int32_t n_groups, int32_t n, int32_t n_node, int32_t n_mc,
+                                       const int32_t *index, const wrsn_ppo_hyper *hyper, float *stats);
+int wrsn_entity_pointer_adam_multi(wrsn_t *h, const wrsn_entity_group *groups, int32_t n_groups, const wrsn_adam_hyper *adam);
+int wrsn_entity_pointer_ppo_update(wrsn_t *h, const wrsn_entity_group *groups, int32_t n_groups, int32_t n_node, int32_t n_mc,
+                                   const int32_t *index, int32_t batch_size, int32_t minibatch, int32_t epochs, const wrsn_ppo_hyper *hyper,
+                                   const wrsn_adam_hyper *adam, float *stats);
+
 /* THE PPO BATCH OF SEVERAL LEARNERS, PREPARED ON THE DEVICE: the critic's values of the selected transitions, PPOLearner.cal_rt_adv
  * (gae=True) over them and the gathers of the batch tensors, for G groups (1 <= G <= 8) in three launches however large G and n are.
  * Asynchronous on the handle's stream, needs no scenario, reads nothing back.

@@ -41,7 +41,8 @@ ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max"
 
 # every entry point include/wrsn_hip.h declares
 EXPORTS = ("wrsn_create", "wrsn_destroy", "wrsn_set_stream", "wrsn_set_scenario", "wrsn_set_scenario_seeded", "wrsn_reset", "wrsn_step",
-           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_entity_actor_floats", "wrsn_entity_act", "wrsn_entity_pointer_floats", "wrsn_entity_pointer_eval", "wrsn_entity_pointer_ppo_grad", "wrsn_entity_pointer_act", "wrsn_entity_heuristic_act", "wrsn_episodes_collect", "wrsn_entity_critic_floats", "wrsn_entity_eval", "wrsn_entity_ppo_grad", "wrsn_entity_adam", "wrsn_entity_ppo_grad_multi", "wrsn_entity_adam_multi", "wrsn_entity_ppo_update", "wrsn_entity_prepare", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
+           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_entity_actor_floats", "wrsn_entity_act", "wrsn_entity_pointer_floats", "wrsn_entity_pointer_eval", "wrsn_entity_pointer_ppo_grad", "wrsn_entity_pointer_act", "wrsn_entity_heuristic_act", "wrsn_episodes_collect", "wrsn_entity_critic_floats", "wrsn_entity_eval", "wrsn_entity_ppo_grad", "wrsn_entity_adam", "wrsn_entity_ppo_grad_multi", "wrsn_entity_adam_multi", "wrsn_entity_ppo_update", "wrsn_entity_pointer_ppo_grad_multi", "wrsn_entity_pointer_adam_multi",
+           "wrsn_entity_pointer_ppo_update", "wrsn_entity_prepare", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
            "wrsn_clone_envs", "wrsn_pool_set", "wrsn_pool_reset", "wrsn_synth_network",
            "wrsn_last_error",
            "wrsn_version")
@@ -200,6 +201,12 @@ def bind(lib):
     lib.wrsn_entity_ppo_update.argtypes = [vp, C.POINTER(WrsnEntityGroup), C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32,
                                            C.POINTER(WrsnPpoHyper), C.POINTER(WrsnAdamHyper), vp]
     lib.wrsn_entity_ppo_update.restype = C.c_int
+    lib.wrsn_entity_pointer_ppo_grad_multi.argtypes = lib.wrsn_entity_ppo_grad_multi.argtypes
+    lib.wrsn_entity_pointer_ppo_grad_multi.restype = C.c_int
+    lib.wrsn_entity_pointer_adam_multi.argtypes = lib.wrsn_entity_adam_multi.argtypes
+    lib.wrsn_entity_pointer_adam_multi.restype = C.c_int
+    lib.wrsn_entity_pointer_ppo_update.argtypes = lib.wrsn_entity_ppo_update.argtypes
+    lib.wrsn_entity_pointer_ppo_update.restype = C.c_int
     lib.wrsn_entity_prepare.argtypes = [vp, C.POINTER(WrsnPrepareGroup), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_float, C.c_float]
     lib.wrsn_entity_prepare.restype = C.c_int
     lib.wrsn_set_obs_reuse.argtypes = [vp, C.c_int32]
@@ -514,6 +521,25 @@ class RawHandle:
         check(self.lib, self.lib.wrsn_entity_ppo_update(self._h, self._groups(groups), len(groups) if n_groups is None else int(n_groups), int(n_node),
                                                         int(n_mc), C.c_void_p(index or None), int(batch_size), int(minibatch), int(epochs),
                                                         self._hyper(hyper), self._adam(adam), C.c_void_p(stats or None)))
+
+    def entity_pointer_ppo_grad_multi(self, groups, n, n_node, n_mc, index, hyper, stats, n_groups=None):
+        """wrsn_entity_pointer_ppo_grad_multi: `entity_ppo_grad_multi` for node-pointer actors in ten launches.  The groups' actor, m_actor,
+        v_actor and grad_actor hold wrsn_entity_pointer_floats() floats, `action` is the [*, 2] stored pair."""
+        check(self.lib, self.lib.wrsn_entity_pointer_ppo_grad_multi(self._h, self._groups(groups), len(groups) if n_groups is None else int(n_groups),
+                                                                    int(n), int(n_node), int(n_mc), C.c_void_p(index or None), self._hyper(hyper),
+                                                                    C.c_void_p(stats or None)))
+
+    def entity_pointer_adam_multi(self, groups, adam, n_groups=None):
+        """wrsn_entity_pointer_adam_multi: `entity_adam_multi` on pointer blocks (the actor's block: wrsn_entity_pointer_floats() floats)."""
+        check(self.lib, self.lib.wrsn_entity_pointer_adam_multi(self._h, self._groups(groups), len(groups) if n_groups is None else int(n_groups),
+                                                                self._adam(adam)))
+
+    def entity_pointer_ppo_update(self, groups, n_node, n_mc, index, batch_size, minibatch, epochs, hyper, adam, stats, n_groups=None):
+        """wrsn_entity_pointer_ppo_update: `entity_ppo_update` for node-pointer actors; index: int32 [G][epochs][batch_size], stats: float32
+        [G][epochs * ceil(batch_size / minibatch)][8].  Only enqueues."""
+        check(self.lib, self.lib.wrsn_entity_pointer_ppo_update(self._h, self._groups(groups), len(groups) if n_groups is None else int(n_groups),
+                                                                int(n_node), int(n_mc), C.c_void_p(index or None), int(batch_size), int(minibatch),
+                                                                int(epochs), self._hyper(hyper), self._adam(adam), C.c_void_p(stats or None)))
 
     def entity_prepare(self, groups, n, n_node, n_mc, index, gamma, gae_lambda, n_groups=None):
         """wrsn_entity_prepare: values, GAE and gathers of every group's batch in three launches.  groups: dicts of device addresses under

@@ -1177,11 +1177,12 @@ const char* entity_dims_bad(int n, int n_node, int n_mc) {
     if (n_node < 1) return "n_node must be >= 1";
     return nullptr;
 }
-void entity_adam_table(const wrsn_entity_group* groups, int G, int step_offset, const wrsn_adam_hyper* a, WrsnEtAdamBlocks* bs) {
+void entity_adam_table(const wrsn_entity_group* groups, int G, int step_offset, const wrsn_adam_hyper* a, WrsnEtAdamBlocks* bs,
+                       int actor_floats = WRSN_EP_FLOATS) {
     for (int g = 0; g < G; ++g) {
         const wrsn_entity_group& q = groups[g];
         const int step = q.adam_step + 1 + step_offset;
-        entity_adam_block(bs, 2 * g, q.actor, q.grad_actor, q.m_actor, q.v_actor, nullptr, WRSN_EP_FLOATS, step, a->lr, a->beta1, a->beta2);
+        entity_adam_block(bs, 2 * g, q.actor, q.grad_actor, q.m_actor, q.v_actor, nullptr, actor_floats, step, a->lr, a->beta1, a->beta2);
         entity_adam_block(bs, 2 * g + 1, q.critic, q.grad_critic, q.m_critic, q.v_critic, nullptr, WRSN_EC_FLOATS, step, a->lr, a->beta1, a->beta2);
     }
 }
@@ -1244,15 +1245,18 @@ int wrsn_entity_adam(wrsn_t* h, float* param, const float* grad, float* m, float
 
 // ------------------------------------------------------------------ the PPO gradient of the node-pointer policy (wrsn_entity_pointer_train.h)
 namespace {
-// the set policy's scratch for one group of n rows, and behind it what the pointer kernels keep
-int pointer_scratch(wrsn_handle* h, int n, int N, bool grad, WrsnEtScratch* s, WrsnEtpScratch* ps) {
-    const size_t et = wrsn_et_scratch_floats((size_t)n, grad), need = et + wrsn_etp_scratch_floats((size_t)n, N, grad);
+// the set policy's scratch for G groups of n rows, and behind it what the pointer kernels keep: G slices, group 0's first (with G = 1 it
+// sits right behind the one set-policy slice), group g's ps->chunk floats behind it
+int pointer_scratch(wrsn_handle* h, int n, int N, bool grad, int G, WrsnEtScratch* s, WrsnEtpScratch* ps) {
+    const size_t et = (size_t)G * wrsn_et_scratch_floats((size_t)n, grad);
+    ps->chunk = wrsn_etp_scratch_floats((size_t)n, N, grad);
+    const size_t need = et + (size_t)G * ps->chunk;
     if (need > h->et_cap) {
         const int rc = dalloc(h, &h->et_scratch, need);
         if (rc) return rc;
         h->et_cap = need;
     }
-    { const int rc = entity_scratch(h, n, grad, 1, s); if (rc) return rc; }
+    { const int rc = entity_scratch(h, n, grad, G, s); if (rc) return rc; }
     float* p = h->et_scratch + et;
     ps->ld = (N + 31) & ~31;
     ps->q = p; p += (size_t)n * 64; ps->lp = p; p += (size_t)n * ps->ld; ps->prow = p; p += (size_t)n * 8;
@@ -1261,13 +1265,30 @@ int pointer_scratch(wrsn_handle* h, int n, int N, bool grad, WrsnEtScratch* s, W
     return 0;
 }
 // trunk and heads of both nets, then -- with an actor -- the query and the scores of the stored decisions
-void pointer_forward(wrsn_handle* h, const WrsnEtGroups& gs, const WrsnEtDims& dm, const WrsnEtScratch& s, const WrsnEtpScratch& ps, const float* stored,
-                     float* value, const WrsnEtpEvalOut& o) {
+// stored: wrsn_entity_pointer_eval's decisions (G = 1); NULL: every group's b.action.  A call without an actor is the eval of a critic alone.
+void pointer_forward(wrsn_handle* h, const WrsnEtGroups& gs, int G, const WrsnEtDims& dm, const WrsnEtScratch& s, const WrsnEtpScratch& ps,
+                     const float* stored, float* value, const WrsnEtpEvalOut& o) {
     WrsnEtEvalOut eo; eo.mean = nullptr; eo.log_std = nullptr; eo.value = value;
-    entity_forward(h, gs, 1, dm, s, eo);
+    entity_forward(h, gs, G, dm, s, eo);
     if (!gs.g[0].actor) return;
-    hipLaunchKernelGGL(wrsn_etp_query_kernel, dim3((dm.n + WRSN_EP_HEAD_ROWS - 1) / WRSN_EP_HEAD_ROWS), dim3(256), 128 * 32 * sizeof(float), h->stream, gs, dm.n, s, ps);
-    hipLaunchKernelGGL(wrsn_etp_score_fwd_kernel, dim3(dm.n), dim3(256), WRSN_PP_SCORE_LDS(dm.N), h->stream, gs, dm, s, ps, stored, o);
+    hipLaunchKernelGGL(wrsn_etp_query_kernel, dim3(G * ((dm.n + WRSN_EP_HEAD_ROWS - 1) / WRSN_EP_HEAD_ROWS)), dim3(256), 128 * 32 * sizeof(float), h->stream,
+                       gs, dm.n, s, ps);
+    hipLaunchKernelGGL(wrsn_etp_score_fwd_kernel, dim3(G * dm.n), dim3(256), WRSN_PP_SCORE_LDS(dm.N), h->stream, gs, dm, s, ps, stored, o);
+}
+// one gradient step of G groups: ten launches however large G is.  The pointer-only per-row kernels run G * n blocks (the actor's rows),
+// the shared ones 2 * G * n.  Arguments are checked by the callers.
+int pointer_grad_launch(wrsn_handle* h, const WrsnEtGroups& gs, int G, const WrsnEtDims& dm, const WrsnEtHyper& hp) {
+    WrsnEtScratch s; WrsnEtpScratch ps;
+    { const int rc = pointer_scratch(h, dm.n, dm.N, true, G, &s, &ps); if (rc) return rc; }
+    const int n = dm.n;
+    pointer_forward(h, gs, G, dm, s, ps, nullptr, nullptr, WrsnEtpEvalOut{});
+    hipLaunchKernelGGL(wrsn_etp_loss_kernel, dim3(G), dim3(256), 256 * sizeof(double), h->stream, gs, n, hp, s, ps);
+    hipLaunchKernelGGL(wrsn_etp_score_bwd_kernel, dim3(G * n), dim3(256), WRSN_ETP_BWD_LDS(dm.N), h->stream, gs, dm, s, ps);
+    hipLaunchKernelGGL(wrsn_etp_head_bwd_kernel, dim3(2 * G * n), dim3(256), 256 * sizeof(float), h->stream, gs, n, s);
+    hipLaunchKernelGGL(wrsn_et_trunk_bwd_kernel, dim3(2 * G * n), dim3(256), WRSN_ET_B_LDS, h->stream, gs, dm, s);
+    hipLaunchKernelGGL(wrsn_etp_trunk_bwd_kernel, dim3(G * n), dim3(256), WRSN_ET_B_LDS, h->stream, gs, dm, s, ps);
+    hipLaunchKernelGGL(wrsn_etp_reduce_kernel, dim3(2 * G * ((WRSN_PP_FLOATS + 255) / 256)), dim3(256), 0, h->stream, gs, dm, s, ps);
+    return 0;
 }
 }  // namespace
 
@@ -1285,12 +1306,12 @@ int wrsn_entity_pointer_eval(wrsn_t* h, const float* actor, const float* critic,
     if (WRSN_PP_SCORE_LDS(rows->n_node) > 65536) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_eval: too many nodes for the score block's LDS");
     WRSN_ON_DEVICE(h);
     WrsnEtScratch s; WrsnEtpScratch ps;
-    { const int rc = pointer_scratch(h, rows->n, rows->n_node, false, &s, &ps); if (rc) return rc; }
+    { const int rc = pointer_scratch(h, rows->n, rows->n_node, false, 1, &s, &ps); if (rc) return rc; }
     WrsnEtGroups gs{};
     gs.g[0].actor = actor; gs.g[0].critic = critic; gs.g[0].rows = rows->rows; gs.g[0].index = rows->index;
     WrsnEtDims dm; dm.n = rows->n; dm.N = rows->n_node; dm.M = rows->n_mc;
     WrsnEtpEvalOut o; o.logp = logp; o.entropy = entropy; o.node_logp = node_logp; o.charge_mean = charge_mean; o.charge_log_std = charge_log_std;
-    pointer_forward(h, gs, dm, s, ps, stored, value, o);
+    pointer_forward(h, gs, 1, dm, s, ps, stored, value, o);
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }
@@ -1308,20 +1329,11 @@ int wrsn_entity_pointer_ppo_grad(wrsn_t* h, const float* actor, const float* cri
     if (WRSN_ETP_BWD_LDS(rows->n_node) > 65536) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_grad: too many nodes for the score block's LDS");
     WRSN_ON_DEVICE(h);
     WrsnEtDims dm; dm.n = rows->n; dm.N = rows->n_node; dm.M = rows->n_mc;
-    WrsnEtScratch s; WrsnEtpScratch ps;
-    { const int rc = pointer_scratch(h, dm.n, dm.N, true, &s, &ps); if (rc) return rc; }
     WrsnEtGroups gs{};
     WrsnEtGroup& G = gs.g[0];
     G.actor = actor; G.critic = critic; G.grad_actor = grad_actor; G.grad_critic = grad_critic; G.rows = rows->rows; G.index = rows->index; G.stats = stats;
     G.b.action = batch->stored; G.b.logp_old = batch->logp_old; G.b.advantage = batch->advantage; G.b.ret = batch->ret; G.b.value_old = batch->value_old;
-    const int n = dm.n;
-    pointer_forward(h, gs, dm, s, ps, batch->stored, nullptr, WrsnEtpEvalOut{});
-    hipLaunchKernelGGL(wrsn_etp_loss_kernel, dim3(1), dim3(256), 256 * sizeof(double), h->stream, gs, n, entity_hyper(hyper), s, ps);
-    hipLaunchKernelGGL(wrsn_etp_score_bwd_kernel, dim3(n), dim3(256), WRSN_ETP_BWD_LDS(dm.N), h->stream, gs, dm, s, ps);
-    hipLaunchKernelGGL(wrsn_etp_head_bwd_kernel, dim3(2 * n), dim3(256), 256 * sizeof(float), h->stream, gs, n, s);
-    hipLaunchKernelGGL(wrsn_et_trunk_bwd_kernel, dim3(2 * n), dim3(256), WRSN_ET_B_LDS, h->stream, gs, dm, s);
-    hipLaunchKernelGGL(wrsn_etp_trunk_bwd_kernel, dim3(n), dim3(256), WRSN_ET_B_LDS, h->stream, gs, dm, s, ps);
-    hipLaunchKernelGGL(wrsn_etp_reduce_kernel, dim3(2 * ((WRSN_PP_FLOATS + 255) / 256)), dim3(256), 0, h->stream, gs, dm, s, ps);
+    if (const int rc = pointer_grad_launch(h, gs, 1, dm, entity_hyper(hyper))) return rc;
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }
@@ -1399,6 +1411,74 @@ int wrsn_entity_ppo_update(wrsn_t* h, const wrsn_entity_group* groups, int32_t n
             WrsnEtAdamBlocks bs{};
             entity_adam_table(groups, n_groups, k, adam, &bs);
             if (const int rc = entity_adam_launch(h, bs, 2 * n_groups, WRSN_EP_FLOATS, adam->beta1, adam->beta2, adam->eps, adam->max_norm)) return rc;
+        }
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+// ------------------------------------------------------------------ the node-pointer policy's multi-group calls: as the three above, on
+// pointer blocks (WRSN_PP_FLOATS floats) and stored pairs, through pointer_grad_launch
+int wrsn_entity_pointer_ppo_grad_multi(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, int32_t n, int32_t n_node, int32_t n_mc,
+                                       const int32_t* index, const wrsn_ppo_hyper* hyper, float* stats) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    if (const char* bad = entity_groups_bad(groups, n_groups, true, false)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_ppo_grad_multi: ") + bad);
+    if (const char* bad = entity_dims_bad(n, n_node, n_mc)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_ppo_grad_multi: ") + bad);
+    if (!hyper || !stats) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_grad_multi needs hyper and stats");
+    if (hyper->norm_adv && n < 2) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_grad_multi: norm_adv needs n >= 2");
+    if (WRSN_ETP_BWD_LDS(n_node) > 65536) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_grad_multi: too many nodes for the score block's LDS");
+    WRSN_ON_DEVICE(h);
+    WrsnEtGroups gs{};
+    entity_group_table(groups, n_groups, index, (size_t)n, stats, 8, &gs);
+    WrsnEtDims dm; dm.n = n; dm.N = n_node; dm.M = n_mc;
+    if (const int rc = pointer_grad_launch(h, gs, n_groups, dm, entity_hyper(hyper))) return rc;
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+int wrsn_entity_pointer_adam_multi(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, const wrsn_adam_hyper* adam) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    if (const char* bad = entity_groups_bad(groups, n_groups, false, true)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_adam_multi: ") + bad);
+    if (!adam) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_adam_multi needs the Adam hyper-parameters");
+    WRSN_ON_DEVICE(h);
+    WrsnEtAdamBlocks bs{};
+    entity_adam_table(groups, n_groups, 0, adam, &bs, WRSN_PP_FLOATS);
+    if (const int rc = entity_adam_launch(h, bs, 2 * n_groups, WRSN_PP_FLOATS, adam->beta1, adam->beta2, adam->eps, adam->max_norm)) return rc;
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+int wrsn_entity_pointer_ppo_update(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, int32_t n_node, int32_t n_mc, const int32_t* index,
+                                   int32_t batch_size, int32_t minibatch, int32_t epochs, const wrsn_ppo_hyper* hyper, const wrsn_adam_hyper* adam,
+                                   float* stats) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    if (const char* bad = entity_groups_bad(groups, n_groups, true, true)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_ppo_update: ") + bad);
+    if (batch_size < 1 || minibatch < 1 || epochs < 1)
+        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_update: batch_size, minibatch and epochs must be >= 1");
+    if (const char* bad = entity_dims_bad(batch_size, n_node, n_mc)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_ppo_update: ") + bad);
+    if (!index || !hyper || !adam || !stats) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_update needs index, hyper, adam and stats");
+    const int per_epoch = (int)(((int64_t)batch_size + minibatch - 1) / minibatch);
+    const int64_t steps64 = (int64_t)per_epoch * epochs;
+    if (steps64 > INT32_MAX) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_update: too many steps");
+    const int steps = (int)steps64, n_full = minibatch < batch_size ? minibatch : batch_size, n_last = batch_size - (per_epoch - 1) * minibatch;
+    if (hyper->norm_adv && (n_full < 2 || n_last < 2))
+        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_update: norm_adv needs every minibatch to hold >= 2 rows");
+    if (WRSN_ETP_BWD_LDS(n_node) > 65536) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_update: too many nodes for the score block's LDS");
+    WRSN_ON_DEVICE(h);
+    {   // the scratch area of the largest step, so that no step of the loop allocates
+        WrsnEtScratch s; WrsnEtpScratch ps;
+        const int rc = pointer_scratch(h, n_full, n_node, true, n_groups, &s, &ps); if (rc) return rc;
+    }
+    const WrsnEtHyper hp = entity_hyper(hyper);
+    int k = 0;
+    for (int e = 0; e < epochs; ++e)
+        for (int start = 0; start < batch_size; start += minibatch, ++k) {   // only enqueues: nothing is read back, nothing synchronises
+            WrsnEtGroups gs{};
+            entity_group_table(groups, n_groups, index + (size_t)e * batch_size + start, (size_t)epochs * batch_size, stats + (size_t)k * 8, (size_t)steps * 8, &gs);
+            WrsnEtDims dm; dm.n = batch_size - start < minibatch ? batch_size - start : minibatch; dm.N = n_node; dm.M = n_mc;
+            if (const int rc = pointer_grad_launch(h, gs, n_groups, dm, hp)) return rc;
+            WrsnEtAdamBlocks bs{};
+            entity_adam_table(groups, n_groups, k, adam, &bs, WRSN_PP_FLOATS);
+            if (const int rc = entity_adam_launch(h, bs, 2 * n_groups, WRSN_PP_FLOATS, adam->beta1, adam->beta2, adam->eps, adam->max_norm)) return rc;
         }
     HIPCHK(hipGetLastError());
     return WRSN_OK;

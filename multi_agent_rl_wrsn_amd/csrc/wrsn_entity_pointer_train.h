@@ -1,5 +1,7 @@
-// wrsn_entity_pointer_train.h -- the PPO gradient of the node-pointer policy on the device (gfx950): wrsn_entity_pointer_eval and
-// wrsn_entity_pointer_ppo_grad of include/wrsn_hip.h, for ONE learner per call (group 0 of the group table).
+// wrsn_entity_pointer_train.h -- the PPO gradient of the node-pointer policy on the device (gfx950): wrsn_entity_pointer_eval,
+// wrsn_entity_pointer_ppo_grad and the multi-group forms wrsn_entity_pointer_ppo_grad_multi, wrsn_entity_pointer_adam_multi and
+// wrsn_entity_pointer_ppo_update of include/wrsn_hip.h.  Every kernel serves G groups (WrsnEtGroups) in one launch, the group folded into
+// blockIdx.x; the single-group calls are G = 1.  Group g's slice of the pointer scratch lies g * WrsnEtpScratch::chunk floats behind group 0's.
 //
 // EntityPointerActor.forward, EntityCritic.forward and PPOLearner.minibatch_loss (ippo.py) on packed entity rows, a pointer block
 // (wrsn_entity_pointer_act's layout: the set actor's trunk, then query and charge) and a critic block.  The trunk and the two head layers
@@ -35,12 +37,38 @@ static inline size_t wrsn_etp_scratch_floats(size_t n, int N, bool grad) {   // 
     return n * (64 + ld + 8) + (grad ? n * (64 + 4 + WRSN_EP_MC1) : 0);
 }
 
-__global__ void __launch_bounds__(256) wrsn_etp_query_kernel(WrsnEtGroups gs, int n, WrsnEtScratch s, WrsnEtpScratch ps) {
+// group g's slice of the pointer scratch
+WDEV WrsnEtpScratch wrsn_etp_slice(WrsnEtpScratch ps, int g) {
+    const size_t o = (size_t)g * ps.chunk;
+    ps.q += o; ps.lp += o; ps.prow += o; ps.dq += o; ps.dch += o; ps.part2 += o;
+    return ps;
+}
+
+// which (group, row) a block of the per-row pointer kernels is: these serve the actor alone, so their grid is G * n -- block index =
+// group * n + row -- and not wrsn_et_who's 2 * G * n with a critic half that returns at once.  The group's entry of the table is read
+// by that wave-uniform index (scalar loads).  src: the row's place in the group's rows and batch arrays.
+struct WrsnEtpWho { int grp, i; size_t src; const float* blk; const float* row; const float* stored; };
+WDEV WrsnEtpWho wrsn_etp_who(const WrsnEtGroups& gs, const WrsnEtDims& dm) {
+    WrsnEtpWho w;
+    w.grp = (int)blockIdx.x / dm.n; w.i = (int)blockIdx.x - w.grp * dm.n;
+    const WrsnEtGroup& G = gs.g[w.grp];
+    w.blk = G.actor; w.stored = G.b.action;
+    const int32_t* index = G.index;
+    w.src = (size_t)(index ? wrsn_wave_first(index[w.i]) : w.i);
+    w.row = G.rows + w.src * (size_t)(WRSN_ENT_NODE_F * dm.N + WRSN_ENT_MC_F * dm.M + WRSN_ENT_ENV_F);
+    return w;
+}
+
+__global__ void __launch_bounds__(256) wrsn_etp_query_kernel(WrsnEtGroups gs, int n, WrsnEtScratch s0, WrsnEtpScratch ps0) {
     extern __shared__ double smem[];
     float* sF = (float*)smem;                                 // z [128 units][32 columns]
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
-    const float* blk = gs.g[0].actor;
-    const int first = (int)blockIdx.x * WRSN_EP_HEAD_ROWS;
+    const int nt = (n + WRSN_EP_HEAD_ROWS - 1) / WRSN_EP_HEAD_ROWS;
+    const int grp = (int)blockIdx.x / nt;                     // block index = group * (tiles per group) + tile
+    const float* blk = gs.g[grp].actor;
+    const WrsnEtScratch s = wrsn_et_slice(s0, grp);
+    const WrsnEtpScratch ps = wrsn_etp_slice(ps0, grp);
+    const int first = ((int)blockIdx.x - grp * nt) * WRSN_EP_HEAD_ROWS;
     const int rows = n - first < WRSN_EP_HEAD_ROWS ? n - first : WRSN_EP_HEAD_ROWS;
     for (int i = tid; i < WRSN_EP_HEAD_ROWS * 128; i += 256) {   // a column beyond `rows` repeats the last row: computed, not stored
         const int j = i >> 7, u = i & 127;
@@ -70,8 +98,9 @@ WDEV int wrsn_etp_node(float kf, int N) {
     return (k >= 0 && k < N) ? k : -1;
 }
 
-__global__ void __launch_bounds__(256) wrsn_etp_score_fwd_kernel(WrsnEtGroups gs, WrsnEtDims dm, WrsnEtScratch s, WrsnEtpScratch ps,
-                                                                 const float* __restrict__ stored, WrsnEtpEvalOut out) {
+// stored0: the decisions of wrsn_entity_pointer_eval (one group); null in the gradient path, where they are the group's b.action
+__global__ void __launch_bounds__(256) wrsn_etp_score_fwd_kernel(WrsnEtGroups gs, WrsnEtDims dm, WrsnEtScratch s0, WrsnEtpScratch ps0,
+                                                                 const float* __restrict__ stored0, WrsnEtpEvalOut out) {
     extern __shared__ double smem[];
     float* sW = (float*)smem;
     float* sQ = sW + WRSN_PP_S_Q;
@@ -79,10 +108,13 @@ __global__ void __launch_bounds__(256) wrsn_etp_score_fwd_kernel(WrsnEtGroups gs
     float* sR = sW + WRSN_PP_S_RED;
     float* sL = sW + WRSN_PP_S_L;
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
-    const WrsnEtWho who = wrsn_et_who(gs, dm);                // blocks 0 .. n - 1: the actor's rows
+    const WrsnEtpWho who = wrsn_etp_who(gs, dm);
     const float* blk = who.blk;
+    const WrsnEtScratch s = wrsn_et_slice(s0, who.grp);
+    const WrsnEtpScratch ps = wrsn_etp_slice(ps0, who.grp);
     const int N = dm.N, i = who.i;
-    const size_t src = (size_t)(who.row - gs.g[0].rows) / (size_t)(WRSN_ENT_NODE_F * N + WRSN_ENT_MC_F * dm.M + WRSN_ENT_ENV_F);
+    const size_t src = who.src;
+    const float* stored = stored0 ? stored0 : who.stored;
     {   // node1, node2 and their biases, as the trunk kernel stages them
         const auto g = wrsn_global((const WrsnU4*)blk);
         WrsnU4* dst = (WrsnU4*)sW;
@@ -186,18 +218,20 @@ __global__ void __launch_bounds__(256) wrsn_etp_score_fwd_kernel(WrsnEtGroups gs
 }
 
 __global__ void __launch_bounds__(256) wrsn_etp_loss_kernel(WrsnEtGroups gs, int n, WrsnEtHyper hp, WrsnEtScratch s0, WrsnEtpScratch ps) {
-    wrsn_et_loss_body<true>(gs, n, hp, s0, ps.prow);
+    wrsn_et_loss_body<true>(gs, n, hp, s0, ps.prow + (size_t)blockIdx.x * ps.chunk);   // one block per group
 }
 
-__global__ void __launch_bounds__(256) wrsn_etp_score_bwd_kernel(WrsnEtGroups gs, WrsnEtDims dm, WrsnEtScratch s, WrsnEtpScratch ps) {
+__global__ void __launch_bounds__(256) wrsn_etp_score_bwd_kernel(WrsnEtGroups gs, WrsnEtDims dm, WrsnEtScratch s0, WrsnEtpScratch ps0) {
     extern __shared__ double smem[];
     float* sW = (float*)smem;
     float* sP = sW + WRSN_ETP_S_PART;                          // [4 waves][64 units], then dq [64]
     float* sDq = sP + 256;
     float* sDL = sW + WRSN_ETP_B_DL;
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
-    const WrsnEtWho who = wrsn_et_who(gs, dm);                // blocks 0 .. n - 1: the actor's rows
+    const WrsnEtpWho who = wrsn_etp_who(gs, dm);
     const float* blk = who.blk;
+    const WrsnEtScratch s = wrsn_et_slice(s0, who.grp);
+    const WrsnEtpScratch ps = wrsn_etp_slice(ps0, who.grp);
     const int N = dm.N, i = who.i;
     {
         const auto g = wrsn_global((const WrsnU4*)blk);
@@ -274,16 +308,17 @@ __global__ void __launch_bounds__(256) wrsn_etp_head_bwd_kernel(WrsnEtGroups gs,
     wrsn_et_head_bwd_body<true>(gs, n, s0);
 }
 
-// The second pass of the trunk backward, for the actor's rows (blocks 0 .. n - 1).  The trunk's gradient is linear in delta2, so the term the
+// The second pass of the trunk backward, for the actor's rows (block index = group * n + row).  The trunk's gradient is linear in delta2, so the term the
 // scores add, delta2 = relu' 0.125 dl_i q_u, goes through wrsn_et_trunk_bwd_kernel's tiles on its own: that kernel holds 256 VGPRs and 250
 // AGPRs and one more addend in it spills.  node1 / node2 and their biases only -- the scores do not see the chargers -- into ps.part2; the
 // reduce adds the two partials.  The tile loop and the wave sum are that kernel's, statement for statement.
-__global__ void __launch_bounds__(256) wrsn_etp_trunk_bwd_kernel(WrsnEtGroups gs, WrsnEtDims dm, WrsnEtScratch s0, WrsnEtpScratch ps) {
+__global__ void __launch_bounds__(256) wrsn_etp_trunk_bwd_kernel(WrsnEtGroups gs, WrsnEtDims dm, WrsnEtScratch s0, WrsnEtpScratch ps0) {
     extern __shared__ double smem[];
     float* sT = (float*)smem;
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, h = lane >> 5;
-    const WrsnEtWho who = wrsn_et_who(gs, dm);
+    const WrsnEtpWho who = wrsn_etp_who(gs, dm);
     const float* blk = who.blk;
+    const WrsnEtpScratch ps = wrsn_etp_slice(ps0, who.grp);
     const int N = dm.N;
     float* sA = sT + wave * 4096;                             // h1 of the wave's tile [node][unit], later delta1
     float* sB = sA + 2048;                                    // delta2 [node][unit], later x [node][8]
@@ -392,5 +427,6 @@ __global__ void __launch_bounds__(256) wrsn_etp_trunk_bwd_kernel(WrsnEtGroups gs
 }
 
 __global__ void __launch_bounds__(256) wrsn_etp_reduce_kernel(WrsnEtGroups gs, WrsnEtDims dm, WrsnEtScratch s0, WrsnEtpScratch ps) {
-    wrsn_et_reduce_body<true>(gs, dm.n, s0, ps, dm.N, dm.M);
+    const int grp = ((int)blockIdx.x / ((WRSN_PP_FLOATS + 255) / 256)) >> 1;   // the body's own split: (group * 2 + net) * (blocks per net) + ...
+    wrsn_et_reduce_body<true>(gs, dm.n, s0, wrsn_etp_slice(ps, grp), dm.N, dm.M);
 }

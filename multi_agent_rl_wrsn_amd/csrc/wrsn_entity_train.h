@@ -94,6 +94,7 @@ struct WrsnEtpScratch {
     float* dch;     // [n][2]   d loss / d (mu, s_raw)
     float* part2;   // [n][WRSN_EP_MC1] the row's gradient of node1 / node2 through the scores
     int ld;         // floats per row of lp: N rounded up to whole tiles
+    size_t chunk;   // floats from a group's slice to the next group's (as WrsnEtScratch::chunk)
 };
 
 static inline size_t wrsn_et_scratch_floats(size_t n, bool grad) {   // host

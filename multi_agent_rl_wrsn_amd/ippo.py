@@ -1036,6 +1036,106 @@ class EntityPPOLearner(PPOLearner):
         return self.torch.stack([pack_entity_actor(a) for a in self.actors]).contiguous()
 
 
+def _fused_prepare_batches(self, width):
+    """The fused tail of `roll_out` for both entity trainers (fused_prepare): see `BatchedEntityIPPO`.  width: floats of a stored action.
+    3 (the set policy): `wrsn_entity_prepare` gathers the actions itself.  2 (the node-pointer policy): its `out_action` stays NULL and
+    the [M, batch_size, 2] stored pairs are gathered from `buffers.action` with the uploaded index by one torch gather on the device."""
+    torch, env, buf = self.torch, self.env, self.buffers
+    dev, M, bs = env.device, self.num_agent, self.batch_size
+    if not self.gae:                                      # the reference's plain branch raises (`cal_rt_adv`): the same, before any launch
+        raise IndexError("index %d is out of bounds for dimension 0 with size %d" % (bs, bs))
+    stored = buf.stored()
+    host = buf.reward[:, :max(stored)].cpu().numpy()      # the one host read
+    idx_np = np.empty((M, bs), dtype=np.int32)
+    for a in range(M):                                    # in charger order: the `np.random` stream of the default path
+        idx_np[a] = select_batch(host[a, :stored[a]], bs)
+    idx = torch.from_numpy(idx_np).to(dev)                # the one upload
+    critics = torch.stack([pack_entity_critic(c) for c in self.critics]).to(device=dev, dtype=torch.float32).contiguous()
+    new = lambda *sh: torch.empty((M, bs) + sh, dtype=torch.float32, device=dev)
+    R = buf.row_elems
+    o = dict(value=new(), advantage=new(), ret=new(), out_state=new(R), out_next_state=new(R))
+    if width == 3:
+        o["out_action"] = new(3)
+    o.update(out_logp=new(),
+             out_reward=torch.empty((M, (-bs) % 64 + bs), dtype=torch.float32, device=dev)[:, :bs])    # every charger's rewards start on a 256-byte boundary, as a tensor of their own would
+    groups = []
+    for a in range(M):
+        g = dict(critic=critics[a], state=buf.state[a], next_state=buf.next_state[a], reward=buf.reward[a], logp=buf.logp[a])
+        if width == 3:
+            g["action"] = buf.action[a]
+        g.update({k: v[a] for k, v in o.items()})
+        groups.append(g)
+    env.entity_prepare(groups, idx, self.gamma, self.gae_lambda)       # stored terminal flags are all 0: terminal = NULL
+    acts = o["out_action"] if width == 3 else buf.action.gather(1, idx.long().unsqueeze(2).expand(M, bs, width))
+    out = [dict(states=o["out_state"][a], actions=self._stored_actions(acts[a]), log_probs=o["out_logp"][a], rewards=o["out_reward"][a],
+                next_states=o["out_next_state"][a], advantages=o["advantage"][a], returns=o["ret"][a], values=o["value"][a]) for a in range(M)]
+    # the logged mean is torch's float32 reduction of the gathered rewards -- the default path's `float(rew.mean())` on the same floats
+    means = torch.stack([b["rewards"].mean() for b in out]).cpu()
+    for a in range(M):
+        self.loggers[a]["rewards"].append(float(means[a]))
+    return out
+
+
+def _joint_update_all(self, batches, shuffle, width, pack_actor, unpack_actor, ppo_update, grad_multi, adam_multi):
+    """`update_all` of both entity trainers (joint_update): see `BatchedEntityIPPO.update_all`.  width: floats of a stored action;
+    pack_actor / unpack_actor: the actor's block layout; ppo_update, grad_multi, adam_multi: the three environment calls."""
+    self._packed = None
+    torch, env = self.torch, self.env
+    dev, M = env.device, self.num_agent
+    f32 = lambda x: x.to(device=dev, dtype=torch.float32).contiguous()
+    epochs, bs, mb = self.n_updates_per_iteration, self.batch_size, self.minibatch_size
+    per_epoch = (bs + mb - 1) // mb
+    steps = epochs * per_epoch
+    if self._grad_all is None:
+        self._grad_all = torch.zeros((M, self._pa + self._pc), dtype=torch.float32, device=dev)   # ONE tensor: what the exchange reduces
+    groups = []
+    for id in range(M):
+        batch, st = batches[id], self._adam[id]
+        b = {"actions": f32(batch["actions"]).reshape(-1, width), "log_probs": f32(batch["log_probs"]), "advantages": f32(batch["advantages"]),
+             "returns": f32(batch["returns"]), "values": f32(batch["values"])}
+        groups.append(dict(actor=f32(pack_actor(self.actors[id])), critic=f32(pack_entity_critic(self.critics[id])), grad=self._grad_all[id],
+                           rows=f32(batch["states"]), batch=b, m_a=st["m_a"], v_a=st["v_a"], m_c=st["m_c"], v_c=st["v_c"], step=st["step"]))
+    idx_np = np.empty((M, epochs, bs), dtype=np.int32)
+    for id in range(M):
+        b_inds = np.arange(bs)
+        for e in range(epochs):
+            shuffle(b_inds)
+            idx_np[id, e] = b_inds
+    idx = torch.from_numpy(idx_np).to(dev)                       # the one upload of the update
+    hyper = dict(clip=self.clip, ent_coef=self.ent_coef, vf_coef=self.vf_coef, norm_adv=self.norm_adv, clip_vloss=self.clip_vloss)
+    lr = self.args["lr"]
+    if self.world == 1 and not self._joint_per_step:
+        table = torch.zeros((M, steps, 8), dtype=torch.float32, device=dev)
+        ppo_update(groups, idx, mb, hyper, table, lr, self.max_grad_norm)
+        for st in self._adam:
+            st["step"] += steps
+    else:
+        by_step = torch.zeros((steps, M, 8), dtype=torch.float32, device=dev)
+        k, keep = 0, []
+        for e in range(epochs):
+            for start in range(0, bs, mb):
+                mbi = idx[:, e, start:start + mb].contiguous()
+                keep.append(mbi)                                  # the launches are asynchronous: alive until the table is read
+                grad_multi(groups, mbi, hyper, by_step[k])
+                if self.world > 1:
+                    torch.distributed.all_reduce(self._grad_all, group=self.group)
+                    self._grad_all /= self.world
+                adam_multi(groups, lr, self.max_grad_norm)
+                for g, st in zip(groups, self._adam):
+                    st["step"] += 1; g["step"] = st["step"]
+                k += 1
+        table = by_step.permute(1, 0, 2)
+    for id, g in enumerate(groups):
+        unpack_actor(g["actor"], self.actors[id]); unpack_entity_critic(g["critic"], self.critics[id])
+    t = table.cpu().numpy().astype(np.float64)                   # the one read of the update
+    out = []
+    for id in range(M):
+        self.loggers[id]["losses"].extend(float(x) for x in t[id, :, 0])
+        self.first_minibatch_stats[id] = tuple(float(x) for x in t[id, 0, :6])
+        out.append((float(t[id, -1, 1]), float(t[id, -1, 2]), float(t[id, -1, 3]), float(t[id, -1, 4]), float(np.mean(t[id, :, 5]))))
+    return out
+
+
 class BatchedEntityIPPO(RolloutDriver, EntityPPOLearner):
     """The roll-out of `BatchedIPPO` on entity rows: `VecWRSN(entities=True)` (no image needed: `render=False`), the set policy's
     3-vector is the action `env.step` takes, and the transitions live in `EntityTransitionBuffers`.
@@ -1115,34 +1215,7 @@ class BatchedEntityIPPO(RolloutDriver, EntityPPOLearner):
     def _prepare_batches(self):
         if not self.fused_prepare:
             return super()._prepare_batches()
-        torch, env, buf = self.torch, self.env, self.buffers
-        dev, M, bs = env.device, self.num_agent, self.batch_size
-        if not self.gae:                                      # the reference's plain branch raises (`cal_rt_adv`): the same, before any launch
-            raise IndexError("index %d is out of bounds for dimension 0 with size %d" % (bs, bs))
-        stored = buf.stored()
-        host = buf.reward[:, :max(stored)].cpu().numpy()      # the one host read
-        idx_np = np.empty((M, bs), dtype=np.int32)
-        for a in range(M):                                    # in charger order: the `np.random` stream of the default path
-            idx_np[a] = select_batch(host[a, :stored[a]], bs)
-        idx = torch.from_numpy(idx_np).to(dev)                # the one upload
-        critics = torch.stack([pack_entity_critic(c) for c in self.critics]).to(device=dev, dtype=torch.float32).contiguous()
-        new = lambda *sh: torch.empty((M, bs) + sh, dtype=torch.float32, device=dev)
-        R = buf.row_elems
-        o = dict(value=new(), advantage=new(), ret=new(), out_state=new(R), out_next_state=new(R), out_action=new(3), out_logp=new(),
-                 out_reward=torch.empty((M, (-bs) % 64 + bs), dtype=torch.float32, device=dev)[:, :bs])    # every charger's rewards start on a 256-byte boundary, as a tensor of their own would
-        groups = []
-        for a in range(M):
-            g = dict(critic=critics[a], state=buf.state[a], next_state=buf.next_state[a], reward=buf.reward[a], action=buf.action[a], logp=buf.logp[a])
-            g.update({k: v[a] for k, v in o.items()})
-            groups.append(g)
-        env.entity_prepare(groups, idx, self.gamma, self.gae_lambda)       # stored terminal flags are all 0: terminal = NULL
-        out = [dict(states=o["out_state"][a], actions=self._stored_actions(o["out_action"][a]), log_probs=o["out_logp"][a], rewards=o["out_reward"][a],
-                    next_states=o["out_next_state"][a], advantages=o["advantage"][a], returns=o["ret"][a], values=o["value"][a]) for a in range(M)]
-        # the logged mean is torch's float32 reduction of the gathered rewards -- the default path's `float(rew.mean())` on the same floats
-        means = torch.stack([b["rewards"].mean() for b in out]).cpu()
-        for a in range(M):
-            self.loggers[a]["rewards"].append(float(means[a]))
-        return out
+        return _fused_prepare_batches(self, 3)
 
     def update(self, id, batch, shuffle=np.random.shuffle):
         self._packed = None                                   # the weights change: never carried across an update
@@ -1199,61 +1272,9 @@ class BatchedEntityIPPO(RolloutDriver, EntityPPOLearner):
         `entity_adam_multi`."""
         if not self.joint_update:
             raise ValueError("update_all needs joint_update=True")
-        self._packed = None
-        torch, env = self.torch, self.env
-        dev, M = env.device, self.num_agent
-        f32 = lambda x: x.to(device=dev, dtype=torch.float32).contiguous()
-        epochs, bs, mb = self.n_updates_per_iteration, self.batch_size, self.minibatch_size
-        per_epoch = (bs + mb - 1) // mb
-        steps = epochs * per_epoch
-        if self._grad_all is None:
-            self._grad_all = torch.zeros((M, self._pa + self._pc), dtype=torch.float32, device=dev)   # ONE tensor: what the exchange reduces
-        groups = []
-        for id in range(M):
-            batch, st = batches[id], self._adam[id]
-            b = {"actions": f32(batch["actions"]).reshape(-1, 3), "log_probs": f32(batch["log_probs"]), "advantages": f32(batch["advantages"]),
-                 "returns": f32(batch["returns"]), "values": f32(batch["values"])}
-            groups.append(dict(actor=f32(pack_entity_actor(self.actors[id])), critic=f32(pack_entity_critic(self.critics[id])), grad=self._grad_all[id],
-                               rows=f32(batch["states"]), batch=b, m_a=st["m_a"], v_a=st["v_a"], m_c=st["m_c"], v_c=st["v_c"], step=st["step"]))
-        idx_np = np.empty((M, epochs, bs), dtype=np.int32)
-        for id in range(M):
-            b_inds = np.arange(bs)
-            for e in range(epochs):
-                shuffle(b_inds)
-                idx_np[id, e] = b_inds
-        idx = torch.from_numpy(idx_np).to(dev)                       # the one upload of the update
-        hyper = dict(clip=self.clip, ent_coef=self.ent_coef, vf_coef=self.vf_coef, norm_adv=self.norm_adv, clip_vloss=self.clip_vloss)
-        lr = self.args["lr"]
-        if self.world == 1 and not self._joint_per_step:
-            table = torch.zeros((M, steps, 8), dtype=torch.float32, device=dev)
-            env.entity_ppo_update(groups, idx, mb, hyper, table, lr, self.max_grad_norm)
-            for st in self._adam:
-                st["step"] += steps
-        else:
-            by_step = torch.zeros((steps, M, 8), dtype=torch.float32, device=dev)
-            k, keep = 0, []
-            for e in range(epochs):
-                for start in range(0, bs, mb):
-                    mbi = idx[:, e, start:start + mb].contiguous()
-                    keep.append(mbi)                                  # the launches are asynchronous: alive until the table is read
-                    env.entity_ppo_grad_multi(groups, mbi, hyper, by_step[k])
-                    if self.world > 1:
-                        torch.distributed.all_reduce(self._grad_all, group=self.group)
-                        self._grad_all /= self.world
-                    env.entity_adam_multi(groups, lr, self.max_grad_norm)
-                    for g, st in zip(groups, self._adam):
-                        st["step"] += 1; g["step"] = st["step"]
-                    k += 1
-            table = by_step.permute(1, 0, 2)
-        for id, g in enumerate(groups):
-            unpack_entity_actor(g["actor"], self.actors[id]); unpack_entity_critic(g["critic"], self.critics[id])
-        t = table.cpu().numpy().astype(np.float64)                   # the one read of the update
-        out = []
-        for id in range(M):
-            self.loggers[id]["losses"].extend(float(x) for x in t[id, :, 0])
-            self.first_minibatch_stats[id] = tuple(float(x) for x in t[id, 0, :6])
-            out.append((float(t[id, -1, 1]), float(t[id, -1, 2]), float(t[id, -1, 3]), float(t[id, -1, 4]), float(np.mean(t[id, :, 5]))))
-        return out
+        env = self.env
+        return _joint_update_all(self, batches, shuffle, 3, pack_entity_actor, unpack_entity_actor, env.entity_ppo_update,
+                                 env.entity_ppo_grad_multi, env.entity_adam_multi)
 
     def _choose(self, r, ids):
         if not self.fused_policy:
@@ -1324,18 +1345,29 @@ class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
                    goes through `wrsn_entity_eval`.  The same return value as the default; `first_minibatch_stats` is filled.  The mode is
                    fixed at construction.  False (the default): the PyTorch update, nothing new is launched.
 
-    `fused_update`, `joint_update` and `fused_prepare` are the set policy's (BatchedEntityIPPO): there is no joint update or fused prepare for
-    this actor yet, and asking for one of the three raises."""
+    joint_update : True (needs device_update) = `train` updates every charger at once through `update_all`, as `BatchedEntityIPPO` does:
+                   one index upload and one `wrsn_entity_pointer_ppo_update` (data-parallel: per step
+                   `wrsn_entity_pointer_ppo_grad_multi`, one all-reduce, `wrsn_entity_pointer_adam_multi`) -- ten gradient and two Adam
+                   launches per minibatch step however many chargers there are.  Bit for bit what `update` per charger gives under
+                   the same shuffles.  False (the default): nothing new is launched.
+    fused_prepare: True (needs device_update) = the tail of `roll_out` runs on the device as `BatchedEntityIPPO`'s does
+                   (`wrsn_entity_prepare` with `out_action` NULL); the [M, batch_size, 2] stored pairs are gathered from the buffers with
+                   the uploaded index by one torch gather.  The batch dicts are bit for bit the default path's.  False (the default):
+                   the per-charger `index_select`s and `cal_rt_adv`.
+
+    `fused_update` is the set policy's option (BatchedEntityIPPO) and always raises here: this actor's is `device_update`."""
 
     _check_status = True
 
     def __init__(self, args, env, device=None, model_path=None, capacity=None, infer_chunk=1024, process_group=None, log=None, min_bucket=16,
                  min_charge=0.02, fused_policy=False, log_episodes=False, episode_slots=64, fused_update=False, joint_update=False,
                  fused_prepare=False, device_update=False):
-        for k, v in (("fused_update", fused_update), ("joint_update", joint_update), ("fused_prepare", fused_prepare)):
-            if v:
-                raise ValueError("BatchedEntityPointerIPPO has no %s: the fused update, joint update and prepare exist for the Gaussian set "
-                                 "policy (BatchedEntityIPPO) only" % k)
+        if fused_update:
+            raise ValueError("BatchedEntityPointerIPPO has no fused_update: that is the Gaussian set policy's option (BatchedEntityIPPO); "
+                             "this actor's is device_update")
+        for k, v in (("joint_update", joint_update), ("fused_prepare", fused_prepare)):
+            if v and not device_update:
+                raise ValueError("%s=True needs device_update=True" % k)
         if not getattr(env, "entities", False):
             raise ValueError("BatchedEntityPointerIPPO needs a VecWRSN with the entity observation (entities=True)")
         if not 0.0 <= float(min_charge) < 1.0:
@@ -1349,12 +1381,16 @@ class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
         self.fused_policy = bool(fused_policy)
         self._packed = None                                   # packed_actors() of the weights as they are now, or None: rebuilt before use
         self.device_update = bool(device_update)
+        self.joint_update = bool(joint_update)
+        self.fused_prepare = bool(fused_prepare)
+        self._joint_per_step = False                          # tests: the per-step path of `update_all` (the data-parallel one) at world == 1
         self.first_minibatch_stats = [None] * self.num_agent  # device_update: (loss, pg, v_loss, entropy, approx_kl, clipfrac) of an update's first minibatch
         if self.device_update:
             torch = self.torch
             self._pa, self._pc = _lib.ENTITY_POINTER_FLOATS, _lib.ENTITY_CRITIC_FLOATS
             z = lambda n: torch.zeros(n, dtype=torch.float32, device=env.device)
             self._grad = z(self._pa + self._pc)               # ONE tensor: what the data-parallel exchange reduces
+            self._grad_all = None                             # joint_update: the same for every charger, [M, P_pointer + P_critic], at first use
             self._adam = [dict(m_a=z(self._pa), v_a=z(self._pa), m_c=z(self._pc), v_c=z(self._pc), step=0) for _ in range(self.num_agent)]
 
     def evaluate_episodes(self, eval_env, episodes=1, deterministic=True, generator=None, **kw):
@@ -1381,6 +1417,22 @@ class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
         torch = self.torch
         blk = pack_entity_critic(self.critics[agent_id]).to(self.env.device)
         return self.env.entity_eval(states.to(torch.float32).contiguous(), critic=blk)[2]
+
+    def _prepare_batches(self):
+        if not self.fused_prepare:
+            return super()._prepare_batches()
+        return _fused_prepare_batches(self, 2)
+
+    def update_all(self, batches, shuffle=np.random.shuffle):
+        """`update(id, batches[id])` for every charger at once (joint_update), the counterpart of `BatchedEntityIPPO.update_all`: the list
+        of the tuples `update` returns, the shuffles drawn in the per-charger order.  One process: one index upload and one
+        `entity_pointer_ppo_update`.  Data-parallel (or `_joint_per_step`): per minibatch step one `entity_pointer_ppo_grad_multi` into one
+        flat [M (P_pointer + P_critic)] tensor, one all-reduce of it, one `entity_pointer_adam_multi`."""
+        if not self.joint_update:
+            raise ValueError("update_all needs joint_update=True")
+        env = self.env
+        return _joint_update_all(self, batches, shuffle, 2, pack_entity_pointer_actor, unpack_entity_pointer_actor, env.entity_pointer_ppo_update,
+                                 env.entity_pointer_ppo_grad_multi, env.entity_pointer_adam_multi)
 
     def _update_device(self, id, batch, shuffle):
         """`PPOLearner.update` on the device, as `BatchedEntityIPPO._update_fused`: the same epochs, shuffles, minibatches and return value."""

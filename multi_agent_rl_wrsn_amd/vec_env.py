@@ -542,11 +542,12 @@ class VecWRSN:
                             0 if norm_out is None else norm_out.data_ptr())
 
     # -- the same for several independent learners at once (wrsn_entity_ppo_grad_multi / wrsn_entity_adam_multi / wrsn_entity_ppo_update)
-    def _entity_groups(self, groups, need_batch):
+    def _entity_groups(self, groups, need_batch, pointer=False):
         """Raw groups (dicts of addresses) from groups of tensors: `actor`, `critic`, `grad` (ONE contiguous float32 tensor [P_actor +
         P_critic]), `m_a`, `v_a`, `m_c`, `v_c`, `step`, and with need_batch `rows` [*, R] and `batch` (the tensors `entity_ppo_grad` takes).
+        pointer: the actors are node-pointer blocks (P_actor = wrsn_entity_pointer_floats()) and `actions` the [*, 2] stored pairs.
         Returns (raw groups, N, M)."""
-        Pa = self._h.lib.wrsn_entity_actor_floats()
+        Pa = self._h.lib.wrsn_entity_pointer_floats() if pointer else self._h.lib.wrsn_entity_actor_floats()
         raw, N = [], 0
         for g in groups:
             q = dict(actor=g["actor"].data_ptr(), critic=g["critic"].data_ptr(), grad_actor=g["grad"].data_ptr(), grad_critic=g["grad"].data_ptr() + 4 * Pa,
@@ -596,6 +597,32 @@ class VecWRSN:
         epochs, batch_size = int(index.shape[1]), int(index.shape[2])
         self._h.entity_ppo_update(raw, N, M, ip, batch_size, minibatch, epochs, hyper,
                                   dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, max_norm=max_norm), stats.data_ptr())
+
+    # -- and for node-pointer actors (wrsn_entity_pointer_ppo_grad_multi / wrsn_entity_pointer_adam_multi / wrsn_entity_pointer_ppo_update)
+    def entity_pointer_ppo_grad_multi(self, groups, index, hyper, stats):
+        """`wrsn_entity_pointer_ppo_grad_multi`: `entity_ppo_grad_multi` for node-pointer actors, ten launches.  The groups' `actor` holds
+        wrsn_entity_pointer_floats() floats, `grad` is [P_pointer + P_critic] and the batch's `actions` the [*, 2] stored pairs."""
+        self._bind_stream()
+        raw, N, M = self._entity_groups(groups, True, pointer=True)
+        n = groups[0]["rows"].shape[0] if index is None else index.shape[1]
+        ip = 0 if index is None else self._entity_index(index, (len(groups), n))
+        self._h.entity_pointer_ppo_grad_multi(raw, n, N, M, ip, hyper, stats.data_ptr())
+
+    def entity_pointer_adam_multi(self, groups, lr, max_norm, beta1=0.9, beta2=0.999, eps=1e-8):
+        """`wrsn_entity_pointer_adam_multi`: `entity_adam_multi` on pointer blocks, group g at `step` + 1."""
+        self._bind_stream()
+        raw, _, _ = self._entity_groups(groups, False, pointer=True)
+        self._h.entity_pointer_adam_multi(raw, dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, max_norm=max_norm))
+
+    def entity_pointer_ppo_update(self, groups, index, minibatch, hyper, stats, lr, max_norm, beta1=0.9, beta2=0.999, eps=1e-8):
+        """`wrsn_entity_pointer_ppo_update`: `entity_ppo_update` for node-pointer actors.  index: int32 [G, epochs, batch_size]; stats:
+        float32 [G, epochs * ceil(batch_size / minibatch), 8].  Only enqueues; the caller advances its step counts by stats.shape[1]."""
+        self._bind_stream()
+        raw, N, M = self._entity_groups(groups, True, pointer=True)
+        ip = self._entity_index(index, (len(groups),) + tuple(index.shape[1:3]))
+        epochs, batch_size = int(index.shape[1]), int(index.shape[2])
+        self._h.entity_pointer_ppo_update(raw, N, M, ip, batch_size, minibatch, epochs, hyper,
+                                          dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, max_norm=max_norm), stats.data_ptr())
 
     def entity_prepare(self, groups, index, gamma, gae_lambda):
         """`wrsn_entity_prepare`: the PPO batch of every group -- the critic's values, `PPOLearner.cal_rt_adv` (gae=True) and the gathers --
