@@ -53,6 +53,8 @@ def main():
                     "wrsn_entity_adam, BatchedEntityPointerIPPO(device_update=True)) instead of PyTorch autograd and torch.optim.Adam")
     ap.add_argument("--min-charge", type=float, default=0.02, help="with --policy pointer: the least third component of an action "
                     "(BatchedEntityPointerIPPO(min_charge=...))")
+    ap.add_argument("--mask-claimed", action="store_true", help="with --policy pointer: the actors choose among the nodes no other charger serves "
+                    "(wrsn_set_entity_pointer_mask, BatchedEntityPointerIPPO(mask_claimed=True))")
     ap.add_argument("--report-updates", action="store_true", help="add peak device memory and the statistics of every update (first minibatch included) to the line")
     args = ap.parse_args()
     if args.joint_update or args.fused_prepare:
@@ -66,6 +68,8 @@ def main():
         raise SystemExit("--fused-update needs --policy entity")
     if args.device_update and args.policy != "pointer":
         raise SystemExit("--device-update needs --policy pointer")
+    if args.mask_claimed and args.policy != "pointer":
+        raise SystemExit("--mask-claimed needs --policy pointer")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:       # launcher-free multi-rank entry: before this process touches torch or the GPU
         from multi_agent_rl_wrsn_amd.sharding import launch_ranks
         raise SystemExit(launch_ranks(args.gpus, [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]))
@@ -93,7 +97,7 @@ def main():
         algo = BatchedEntityPointerIPPO(ppo_args, env, capacity=max(2 * args.batch_size, 4096), infer_chunk=args.infer_chunk, min_bucket=args.infer_chunk,
                                         fused_policy=args.fused_policy, min_charge=args.min_charge,
                                         **({"device_update": True} if args.device_update else {}), **({"joint_update": True} if args.joint_update else {}),
-                                        **({"fused_prepare": True} if args.fused_prepare else {}))
+                                        **({"fused_prepare": True} if args.fused_prepare else {}), **({"mask_claimed": True} if args.mask_claimed else {}))
     elif entity:
         env = VecWRSN([synth_scenario(rank * B + e, N, N) for e in range(B)], None, M, auto_reset=True, step_budget=args.step_budget, device=str(dev),
                       render=False, entities=True)             # no image at all: 6.6 KB of entity rows per request
@@ -164,7 +168,8 @@ def main():
         out["config"]["policy"] = "float32, entity rows, no image" + (", actions sampled on the device (wrsn_entity_pointer_act)" if args.fused_policy else "") + (
             ", update on the device (wrsn_entity_pointer_ppo_grad, wrsn_entity_adam)" if args.device_update else "") + (
             ", every charger in one call (wrsn_entity_pointer_ppo_update)" if args.joint_update else "") + (
-            ", batch prepared on the device (wrsn_entity_prepare)" if args.fused_prepare else "")
+            ", batch prepared on the device (wrsn_entity_prepare)" if args.fused_prepare else "") + (
+            ", candidate mask on (wrsn_set_entity_pointer_mask)" if args.mask_claimed else "")
     if args.report_updates:
         out["peak_memory_bytes"] = int(torch.cuda.max_memory_allocated(dev)); out["updates"] = updates
     print(json.dumps(out, default=float), flush=True)

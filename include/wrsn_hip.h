@@ -406,6 +406,32 @@ int wrsn_entity_pointer_act(wrsn_t *h, const float *actors /* [n_mc, floats] */,
                             const float *gumbel /* [B,N] or NULL */, const float *eps /* [B] or NULL */,
                             float min_charge, const wrsn_entity_out *ent, const wrsn_entity_pointer_out *out);
 
+/* THE CANDIDATE MASK OF THE NODE POINTER: "not a node another charger serves", the rule of wrsn_entity_heuristic_act below as an
+ * opt-in mask on the pointer's choice.  Handle state, WRSN_POINTER_MASK_NONE by default; not part of an environment record.  Allowed
+ * between any two calls: it is read when a call enqueues its launches, so the launches enqueued so far keep theirs (as
+ * wrsn_set_obs_format).  Read by wrsn_entity_pointer_act, wrsn_entity_pointer_eval, wrsn_entity_pointer_ppo_grad,
+ * wrsn_entity_pointer_ppo_grad_multi and wrsn_entity_pointer_ppo_update (once, before its loop).  With WRSN_POINTER_MASK_NONE every
+ * call gives the bytes it gave before the mask existed.
+ * WRSN_POINTER_MASK_CLAIMED.  A pure function of the row's content (node, mc, env -- acting rows and stored packed rows alike), in
+ * float32, every operation rounded on its own (no contraction into an FMA):
+ *     claimer o    : charger row o with mc[o][4] (alive) == 1 and mc[o][3] (is_self) != 1.  No agent_id enters, so the update forms it
+ *                    from the stored row alone.  The heuristic excludes `self` (the lowest-index is_self row, else row agent_id)
+ *                    instead: the two differ only on rows with no or with several is_self flags -- with none every alive charger
+ *                    claims here, with several none of the flagged ones does.
+ *     claimed(i)   : for some claimer o,  dx = (node[i][0] - mc[o][6]) / env[0],  dy = (node[i][1] - mc[o][7]) / env[1],
+ *                    dx * dx + dy * dy <= 1.  A NaN compares false: it claims nothing.
+ *     candidate(i) : alive(i) && !claimed(i) when the row holds at least one such node; else alive(i) -- the heuristic's fallback, so a
+ *                    row never loses its last choice.  alive(i) is "l_i > -inf" of the semantics above.
+ * "alive" is replaced by "candidate" in exactly two places: the select that writes l_i or -inf -- hence node_logp, the log-sum-exp,
+ * the arg-max and the categorical entropy --, and the update's kv = k >= 0 && candidate(k): a stored node that is no candidate
+ * contributes no node term to logp, exactly as a stored dead node.  Nothing else moves: the pools behind z run over all alive nodes
+ * (a claimed node is still part of the state), x_k is the stored node's eight floats as they stand, a row with no alive node is
+ * treated as without the mask, and wrsn_entity_pointer_eval keeps writing the bytes wrsn_entity_pointer_act writes under the same mode.
+ * WRSN_ERR_ARG, handle unchanged: h NULL or any other mode. */
+#define WRSN_POINTER_MASK_NONE    0
+#define WRSN_POINTER_MASK_CLAIMED 1
+int wrsn_set_entity_pointer_mask(wrsn_t *h, int32_t mode);
+
 /* A HEURISTIC BASELINE ON THE ENTITY ROWS: "go to the most critical node nobody else is serving".  Deterministic, no parameters but
  * charge_scale; the answer to "better than what?" for a learned entity policy.  For row e with a = agent_id[e] in [0, n_mc), everything
  * in float32, every operation rounded on its own (no contraction into an FMA):

@@ -32,6 +32,7 @@ ENT_NODE = {k: i for i, k in enumerate(ENT_NODE_FIELDS)}      # ENT_NODE["weight
 ENT_MC = {k: i for i, k in enumerate(ENT_MC_FIELDS) if not k.startswith("_")}
 ENT_ENV = {k: i for i, k in enumerate(ENT_ENV_FIELDS) if not k.startswith("_")}
 ENTITY_ACTOR_FLOATS, ENTITY_CRITIC_FLOATS = 49224, 48580   # wrsn_entity_actor_floats(), wrsn_entity_critic_floats() (include/wrsn_hip.h)
+POINTER_MASK_NONE, POINTER_MASK_CLAIMED = 0, 1   # wrsn_set_entity_pointer_mask: every alive node / not the nodes another charger serves
 ENTITY_POINTER_FLOATS = 56980   # wrsn_entity_pointer_floats(): the block of the node-pointer actor (include/wrsn_hip.h)
 ENTPOL_FEAT = 200            # wrsn_entity_act: inputs of the actor's head (64 mean + 64 max + 32 charger mean + 32 own + 8 env)
 MC_FIELDS = ("loc_x", "loc_y", "energy", "status", "type_charging", "cur_x", "cur_y", "cur_t", "n_conn",
@@ -42,7 +43,7 @@ ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max"
 # every entry point include/wrsn_hip.h declares
 EXPORTS = ("wrsn_create", "wrsn_destroy", "wrsn_set_stream", "wrsn_set_scenario", "wrsn_set_scenario_seeded", "wrsn_reset", "wrsn_step",
            "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_entity_actor_floats", "wrsn_entity_act", "wrsn_entity_pointer_floats", "wrsn_entity_pointer_eval", "wrsn_entity_pointer_ppo_grad", "wrsn_entity_pointer_act", "wrsn_entity_heuristic_act", "wrsn_episodes_collect", "wrsn_entity_critic_floats", "wrsn_entity_eval", "wrsn_entity_ppo_grad", "wrsn_entity_adam", "wrsn_entity_ppo_grad_multi", "wrsn_entity_adam_multi", "wrsn_entity_ppo_update", "wrsn_entity_pointer_ppo_grad_multi", "wrsn_entity_pointer_adam_multi",
-           "wrsn_entity_pointer_ppo_update", "wrsn_entity_prepare", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
+           "wrsn_entity_pointer_ppo_update", "wrsn_set_entity_pointer_mask", "wrsn_entity_prepare", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
            "wrsn_clone_envs", "wrsn_pool_set", "wrsn_pool_reset", "wrsn_synth_network",
            "wrsn_last_error",
            "wrsn_version")
@@ -211,6 +212,8 @@ def bind(lib):
     lib.wrsn_entity_prepare.restype = C.c_int
     lib.wrsn_set_obs_reuse.argtypes = [vp, C.c_int32]
     lib.wrsn_set_obs_reuse.restype = C.c_int
+    lib.wrsn_set_entity_pointer_mask.argtypes = [vp, C.c_int32]
+    lib.wrsn_set_entity_pointer_mask.restype = C.c_int
     lib.wrsn_set_obs_format.argtypes = [vp, C.c_int32]
     lib.wrsn_set_obs_format.restype = C.c_int
     lib.wrsn_set_timing.argtypes = [vp, C.c_int32]
@@ -559,6 +562,11 @@ class RawHandle:
     def set_obs_format(self, fmt):
         """OBS_F32 / OBS_BF16 for every observation written or copied by the calls that follow (anything else: WrsnError)."""
         check(self.lib, self.lib.wrsn_set_obs_format(self._h, int(fmt)))
+
+    def set_entity_pointer_mask(self, mode):
+        """POINTER_MASK_NONE / POINTER_MASK_CLAIMED for the node-pointer calls that follow: acting, eval, gradient and update (anything
+        else: WrsnError, mode unchanged)."""
+        check(self.lib, self.lib.wrsn_set_entity_pointer_mask(self._h, int(mode)))
 
     def set_timing(self, on):
         check(self.lib, self.lib.wrsn_set_timing(self._h, 1 if on else 0))

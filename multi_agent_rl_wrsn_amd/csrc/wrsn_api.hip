@@ -109,6 +109,7 @@ struct wrsn_handle {
     const uint8_t* pool = nullptr; int pool_n = 0; uint64_t pool_seed = 0; int64_t pool_rec_bytes = 0;
     int32_t* d_pool_cur = nullptr; int32_t* d_pool_swaps = nullptr;
     int32_t* d_pairs = nullptr; int32_t* d_pair_n = nullptr;
+    int ptr_mask = WRSN_POINTER_MASK_NONE;   // wrsn_set_entity_pointer_mask: the candidate mask of the node-pointer calls, read when they enqueue
     WrsnEntityOut ent{};            // wrsn_set_entity_out: the caller's entity-observation buffers (node == nullptr: off, the default)
     // wrsn_entity_act (allocated by its first call): the head's inputs [B, WRSN_ENTPOL_FEAT], the row lists [M, B] and counters [8] per charger
     float* ep_feat = nullptr; int32_t* ep_list = nullptr; int32_t* ep_cnt = nullptr;
@@ -1027,8 +1028,15 @@ int wrsn_entity_pointer_act(wrsn_t* h, const float* actors, const int32_t* agent
     hipLaunchKernelGGL(wrsn_entptr_head_kernel, dim3((B + WRSN_EP_HEAD_ROWS - 1) / WRSN_EP_HEAD_ROWS + M), dim3(256), WRSN_EP_H_LDS, h->stream, B, M,
                        actors, (const float*)h->ep_feat, (const int32_t*)h->ep_list, (const int32_t*)h->ep_cnt, h->pp_z, h->pp_q);
     hipLaunchKernelGGL(wrsn_entptr_score_kernel, dim3(B), dim3(256), WRSN_PP_SCORE_LDS(N), h->stream, B, M, N, actors, agent_id, e,
-                       (const float*)h->pp_z, (const float*)h->pp_q, gumbel, eps, min_charge, o);
+                       (const float*)h->pp_z, (const float*)h->pp_q, gumbel, eps, min_charge, o, h->ptr_mask);
     HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+int wrsn_set_entity_pointer_mask(wrsn_t* h, int32_t mode) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    if (mode != WRSN_POINTER_MASK_NONE && mode != WRSN_POINTER_MASK_CLAIMED) return fail(WRSN_ERR_ARG, "unknown node-pointer mask");
+    h->ptr_mask = mode;                                        // read at launch time: the launches enqueued so far keep theirs
     return WRSN_OK;
 }
 
@@ -1267,21 +1275,21 @@ int pointer_scratch(wrsn_handle* h, int n, int N, bool grad, int G, WrsnEtScratc
 // trunk and heads of both nets, then -- with an actor -- the query and the scores of the stored decisions
 // stored: wrsn_entity_pointer_eval's decisions (G = 1); NULL: every group's b.action.  A call without an actor is the eval of a critic alone.
 void pointer_forward(wrsn_handle* h, const WrsnEtGroups& gs, int G, const WrsnEtDims& dm, const WrsnEtScratch& s, const WrsnEtpScratch& ps,
-                     const float* stored, float* value, const WrsnEtpEvalOut& o) {
+                     const float* stored, float* value, const WrsnEtpEvalOut& o, int mask) {
     WrsnEtEvalOut eo; eo.mean = nullptr; eo.log_std = nullptr; eo.value = value;
     entity_forward(h, gs, G, dm, s, eo);
     if (!gs.g[0].actor) return;
     hipLaunchKernelGGL(wrsn_etp_query_kernel, dim3(G * ((dm.n + WRSN_EP_HEAD_ROWS - 1) / WRSN_EP_HEAD_ROWS)), dim3(256), 128 * 32 * sizeof(float), h->stream,
                        gs, dm.n, s, ps);
-    hipLaunchKernelGGL(wrsn_etp_score_fwd_kernel, dim3(G * dm.n), dim3(256), WRSN_PP_SCORE_LDS(dm.N), h->stream, gs, dm, s, ps, stored, o);
+    hipLaunchKernelGGL(wrsn_etp_score_fwd_kernel, dim3(G * dm.n), dim3(256), WRSN_PP_SCORE_LDS(dm.N), h->stream, gs, dm, s, ps, stored, o, mask);
 }
 // one gradient step of G groups: ten launches however large G is.  The pointer-only per-row kernels run G * n blocks (the actor's rows),
 // the shared ones 2 * G * n.  Arguments are checked by the callers.
-int pointer_grad_launch(wrsn_handle* h, const WrsnEtGroups& gs, int G, const WrsnEtDims& dm, const WrsnEtHyper& hp) {
+int pointer_grad_launch(wrsn_handle* h, const WrsnEtGroups& gs, int G, const WrsnEtDims& dm, const WrsnEtHyper& hp, int mask) {
     WrsnEtScratch s; WrsnEtpScratch ps;
     { const int rc = pointer_scratch(h, dm.n, dm.N, true, G, &s, &ps); if (rc) return rc; }
     const int n = dm.n;
-    pointer_forward(h, gs, G, dm, s, ps, nullptr, nullptr, WrsnEtpEvalOut{});
+    pointer_forward(h, gs, G, dm, s, ps, nullptr, nullptr, WrsnEtpEvalOut{}, mask);
     hipLaunchKernelGGL(wrsn_etp_loss_kernel, dim3(G), dim3(256), 256 * sizeof(double), h->stream, gs, n, hp, s, ps);
     hipLaunchKernelGGL(wrsn_etp_score_bwd_kernel, dim3(G * n), dim3(256), WRSN_ETP_BWD_LDS(dm.N), h->stream, gs, dm, s, ps);
     hipLaunchKernelGGL(wrsn_etp_head_bwd_kernel, dim3(2 * G * n), dim3(256), 256 * sizeof(float), h->stream, gs, n, s);
@@ -1311,7 +1319,7 @@ int wrsn_entity_pointer_eval(wrsn_t* h, const float* actor, const float* critic,
     gs.g[0].actor = actor; gs.g[0].critic = critic; gs.g[0].rows = rows->rows; gs.g[0].index = rows->index;
     WrsnEtDims dm; dm.n = rows->n; dm.N = rows->n_node; dm.M = rows->n_mc;
     WrsnEtpEvalOut o; o.logp = logp; o.entropy = entropy; o.node_logp = node_logp; o.charge_mean = charge_mean; o.charge_log_std = charge_log_std;
-    pointer_forward(h, gs, 1, dm, s, ps, stored, value, o);
+    pointer_forward(h, gs, 1, dm, s, ps, stored, value, o, h->ptr_mask);
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }
@@ -1333,7 +1341,7 @@ int wrsn_entity_pointer_ppo_grad(wrsn_t* h, const float* actor, const float* cri
     WrsnEtGroup& G = gs.g[0];
     G.actor = actor; G.critic = critic; G.grad_actor = grad_actor; G.grad_critic = grad_critic; G.rows = rows->rows; G.index = rows->index; G.stats = stats;
     G.b.action = batch->stored; G.b.logp_old = batch->logp_old; G.b.advantage = batch->advantage; G.b.ret = batch->ret; G.b.value_old = batch->value_old;
-    if (const int rc = pointer_grad_launch(h, gs, 1, dm, entity_hyper(hyper))) return rc;
+    if (const int rc = pointer_grad_launch(h, gs, 1, dm, entity_hyper(hyper), h->ptr_mask)) return rc;
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }
@@ -1430,7 +1438,7 @@ int wrsn_entity_pointer_ppo_grad_multi(wrsn_t* h, const wrsn_entity_group* group
     WrsnEtGroups gs{};
     entity_group_table(groups, n_groups, index, (size_t)n, stats, 8, &gs);
     WrsnEtDims dm; dm.n = n; dm.N = n_node; dm.M = n_mc;
-    if (const int rc = pointer_grad_launch(h, gs, n_groups, dm, entity_hyper(hyper))) return rc;
+    if (const int rc = pointer_grad_launch(h, gs, n_groups, dm, entity_hyper(hyper), h->ptr_mask)) return rc;
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }
@@ -1469,13 +1477,14 @@ int wrsn_entity_pointer_ppo_update(wrsn_t* h, const wrsn_entity_group* groups, i
         const int rc = pointer_scratch(h, n_full, n_node, true, n_groups, &s, &ps); if (rc) return rc;
     }
     const WrsnEtHyper hp = entity_hyper(hyper);
+    const int mask = h->ptr_mask;                             // read once: every step of the loop under the same mask
     int k = 0;
     for (int e = 0; e < epochs; ++e)
         for (int start = 0; start < batch_size; start += minibatch, ++k) {   // only enqueues: nothing is read back, nothing synchronises
             WrsnEtGroups gs{};
             entity_group_table(groups, n_groups, index + (size_t)e * batch_size + start, (size_t)epochs * batch_size, stats + (size_t)k * 8, (size_t)steps * 8, &gs);
             WrsnEtDims dm; dm.n = batch_size - start < minibatch ? batch_size - start : minibatch; dm.N = n_node; dm.M = n_mc;
-            if (const int rc = pointer_grad_launch(h, gs, n_groups, dm, hp)) return rc;
+            if (const int rc = pointer_grad_launch(h, gs, n_groups, dm, hp, mask)) return rc;
             WrsnEtAdamBlocks bs{};
             entity_adam_table(groups, n_groups, k, adam, &bs, WRSN_PP_FLOATS);
             if (const int rc = entity_adam_launch(h, bs, 2 * n_groups, WRSN_PP_FLOATS, adam->beta1, adam->beta2, adam->eps, adam->max_norm)) return rc;

@@ -12,7 +12,10 @@
 //   wrsn_etp_query_kernel      tiles of <= 32 rows: q = query(z) on the matrix cores, wrsn_entptr_head_kernel's chain -> q [n][64]
 //   wrsn_etp_score_fwd_kernel  one 256-thread block per row: wrsn_entptr_score_kernel on a packed row with the STORED node in place of the
 //                              arg-max -- l_i through wrsn_et_tile_fwd, maximum, exp-sum and the charge head in that kernel's orders, so
-//                              node_logp, the charge mean and log_std are its bits --, then the categorical entropy, logp and H
+//                              node_logp, the charge mean and log_std are its bits --, then the categorical entropy, logp and H; with
+//                              the candidate mask (wrsn_set_entity_pointer_mask) that kernel's pass wrsn_pp_mask_claimed on the packed
+//                              row, behind which -inf IS "no candidate": kv, the stored log p and dl carry the mask to the two
+//                              backward kernels, which read no alive flag for the scores and stay as they are
 //   wrsn_etp_loss_kernel       wrsn_et_loss_body<true>: the loss on scalar (logp, H) -> a = d loss / d logp, e = d loss / d H, d / d value
 //   wrsn_etp_score_bwd_kernel  one block per row: dl in place of node_logp, dq = 0.125 sum_i dl_i h_i with h_i recomputed tile by tile
 //                              (tile order, then wave order), (dmu, ds_raw), and dz = W_charge[0:128] (dmu, ds_raw) + W_query dq
@@ -100,7 +103,7 @@ WDEV int wrsn_etp_node(float kf, int N) {
 
 // stored0: the decisions of wrsn_entity_pointer_eval (one group); null in the gradient path, where they are the group's b.action
 __global__ void __launch_bounds__(256) wrsn_etp_score_fwd_kernel(WrsnEtGroups gs, WrsnEtDims dm, WrsnEtScratch s0, WrsnEtpScratch ps0,
-                                                                 const float* __restrict__ stored0, WrsnEtpEvalOut out) {
+                                                                 const float* __restrict__ stored0, WrsnEtpEvalOut out, int mask) {
     extern __shared__ double smem[];
     float* sW = (float*)smem;
     float* sQ = sW + WRSN_PP_S_Q;
@@ -144,6 +147,9 @@ __global__ void __launch_bounds__(256) wrsn_etp_score_fwd_kernel(WrsnEtGroups gs
         if (on && h == 0 && n < N) sL[n] = (alive && l > ninf) ? l : ninf;   // -inf IS "not alive" below
     }
     __syncthreads();
+    if (mask)                                                 // block-uniform: wrsn_entptr_score_kernel's pass on the packed row [node | mc | env]
+        wrsn_pp_mask_claimed(sL, (int*)sR + 12, nrow, nrow + (size_t)N * WRSN_ENT_NODE_F,
+                             nrow + (size_t)N * WRSN_ENT_NODE_F + (size_t)dm.M * WRSN_ENT_MC_F, N, dm.M);
     // ---- over the alive nodes: the maximum, then the sum of exp(l - max) -- thread t takes nodes t, t + 256, ...; lanes by a butterfly, waves in order
     float mx = ninf;
     for (int n = tid; n < N; n += 256) {
@@ -205,7 +211,7 @@ __global__ void __launch_bounds__(256) wrsn_etp_score_fwd_kernel(WrsnEtGroups gs
     if (tid != 0) return;
     const float hcat = any ? -(((sR[4] + sR[5]) + sR[6]) + sR[7]) : 0.f;
     const float mu = sR[0], sraw = sR[1], ls = fminf(fmaxf(sraw, -4.f), 1.f);
-    const bool kv = k >= 0 && sL[kk] > ninf;                  // the stored node is alive
+    const bool kv = k >= 0 && sL[kk] > ninf;                  // the stored node is alive -- under the mask: a candidate, sL says both
     const float t = (stored[src * 2 + 1] - mu) / expf(ls);
     const float lp = (kv ? sL[kk] - lse : 0.f) + (-0.5f * t * t - ls - 0.9189385f);   // 0.5 log(2 pi)
     const float H = ((hcat + ls) + 0.5f) + 0.9189385f;

@@ -701,6 +701,49 @@ static_assert(WRSN_PP_CHARGE_IN % 4 == 0, "the charge head runs four chains over
 #define WRSN_PP_S_L (WRSN_PP_S_RED + 16)
 #define WRSN_PP_SCORE_LDS(N) ((size_t)(WRSN_PP_S_L + (((N) + 31) & ~31)) * 4)     // bytes
 
+// The candidate mask (wrsn_set_entity_pointer_mask, WRSN_POINTER_MASK_CLAIMED; include/wrsn_hip.h has the rule, statement for statement):
+// one pass of the 256-thread score block over sL, between the barrier behind the tile loop that fills it and the first reduction.  The
+// chargers (at most eight) and the disc's half-axes are read with block-uniform addresses, as wrsn_entity_heuristic_kernel reads them; a
+// claimer is an alive charger row that is not is_self, so acting rows and stored packed rows give the same mask.  Thread t takes nodes
+// t, t + 256, ... -- the nodes it takes in every reduction behind, so what it writes here it alone reads until the next barrier.  The
+// block ORs "some alive node is unclaimed" (exact: a __shfl_xor butterfly, then four LDS slots in wave order; no DPP row operation) and,
+// where that holds, every claimed node's sL becomes -inf; where it does not -- every alive node claimed, or none alive -- sL stays: the
+// heuristic's fallback.  Behind the pass -inf IS "no candidate": nothing reads a flag again.  One __syncthreads; `claimed` is formed
+// twice (before and behind it) and not kept, a row holds any number of nodes per thread.  sAny: four int slots nobody else holds now.
+WDEV void wrsn_pp_mask_claimed(float* sL, int* sAny, const float* __restrict__ nrow, const float* __restrict__ mc, const float* __restrict__ env,
+                               int N, int M) {
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float ninf = -__builtin_inff();
+    const float hx = env[0], hy = env[1];
+    float cx[WRSN_MAX_MC], cy[WRSN_MAX_MC]; bool on[WRSN_MAX_MC];
+#pragma unroll
+    for (int o = 0; o < WRSN_MAX_MC; ++o) {
+        const int c = o < M ? o : M - 1;                      // clamped: chargers beyond M are switched off
+        on[o] = o < M && mc[c * WRSN_ENT_MC_F + 4] == 1.f && !(mc[c * WRSN_ENT_MC_F + 3] == 1.f);   // alive and not is_self
+        cx[o] = mc[c * WRSN_ENT_MC_F + 6]; cy[o] = mc[c * WRSN_ENT_MC_F + 7];
+    }
+    int any = 0;
+    for (int n = tid; n < N; n += 256) {
+        const float u = nrow[(size_t)n * WRSN_ENT_NODE_F], v = nrow[(size_t)n * WRSN_ENT_NODE_F + 1];
+        bool claimed = false;
+#pragma unroll
+        for (int o = 0; o < WRSN_MAX_MC; ++o) claimed = claimed || (on[o] && wrsn_eh_claims(u, v, cx[o], cy[o], hx, hy));
+        any |= (sL[n] > ninf && !claimed) ? 1 : 0;
+    }
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) any |= __shfl_xor(any, d);
+    if (lane == 0) sAny[wave] = any;
+    __syncthreads();
+    if (!(sAny[0] | sAny[1] | sAny[2] | sAny[3])) return;     // block-uniform: no alive node is unclaimed, the alive nodes stay
+    for (int n = tid; n < N; n += 256) {
+        const float u = nrow[(size_t)n * WRSN_ENT_NODE_F], v = nrow[(size_t)n * WRSN_ENT_NODE_F + 1];
+        bool claimed = false;
+#pragma unroll
+        for (int o = 0; o < WRSN_MAX_MC; ++o) claimed = claimed || (on[o] && wrsn_eh_claims(u, v, cx[o], cy[o], hx, hy));
+        if (claimed) sL[n] = ninf;
+    }
+}
+
 struct WrsnEntPtrOut { int32_t* node; float* stored; float* action; double* action_f64; float* logp; float* node_logp; float* charge_mean; float* charge_log_std; };   // mirrors wrsn_entity_pointer_out
 
 __global__ void __launch_bounds__(256) wrsn_entptr_head_kernel(int B, int M, const float* __restrict__ actors, const float* __restrict__ feat,
@@ -736,7 +779,7 @@ __global__ void __launch_bounds__(256) wrsn_entptr_score_kernel(int B, int M, in
                                                                 const int32_t* __restrict__ agent_id, WrsnEntityOut ent,
                                                                 const float* __restrict__ zbuf, const float* __restrict__ qbuf,
                                                                 const float* __restrict__ gumbel, const float* __restrict__ eps,
-                                                                float min_charge, WrsnEntPtrOut out) {
+                                                                float min_charge, WrsnEntPtrOut out, int mask) {
     extern __shared__ double smem[];
     float* sW = (float*)smem;
     float* sQ = sW + WRSN_PP_S_Q;
@@ -806,6 +849,8 @@ __global__ void __launch_bounds__(256) wrsn_entptr_score_kernel(int B, int M, in
         if (on && h == 0 && n < N) sL[n] = (alive && l > ninf) ? l : ninf;   // a select: whatever a dead or padded node row holds never enters; -inf IS "not alive" below
     }
     __syncthreads();
+    if (mask)                                                 // block-uniform: the candidates among the alive nodes; behind it -inf IS "no candidate"
+        wrsn_pp_mask_claimed(sL, sK + 12, nrow, ent.mc + (size_t)e * M * WRSN_ENT_MC_F, ent.env + (size_t)e * WRSN_ENT_ENV_F, N, M);
     // ---- over the alive nodes: the maximum of l and the maximum of l + g -- thread t takes nodes t, t + 256, ...
     const float* grow = gumbel ? gumbel + (size_t)e * N : nullptr;
     float mx = ninf, bs = ninf;

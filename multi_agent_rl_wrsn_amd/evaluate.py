@@ -10,7 +10,7 @@ policy through `wrsn_entity_pointer_act`, likewise), `HeuristicPolicy` (the dete
 `wrsn_entity_heuristic_act`) and `UniformPolicy` (`torch.rand`)."""
 import numpy as np
 
-from ._lib import ENDED_FELL_OFF, ENDED_TERMINAL, ENDED_TIME_LIMIT
+from ._lib import ENDED_FELL_OFF, ENDED_TERMINAL, ENDED_TIME_LIMIT, POINTER_MASK_CLAIMED, POINTER_MASK_NONE
 
 ENDED_NAMES = {ENDED_TERMINAL: "terminal", ENDED_TIME_LIMIT: "time_limit", ENDED_FELL_OFF: "fell_off"}
 
@@ -35,12 +35,16 @@ class PointerPolicy:
     """The node-pointer actors `packed_actors` ([M, P], `EntityPointerPPOLearner.packed_actors()`) through `VecWRSN.entity_pointer_act`:
     the most probable node and the mode of the charge variable (`deterministic=True`), or a sample with Gumbel noise -log(-log(u)), u
     from `torch.rand`, and `torch.randn` draws of `generator`.  The third component of every action is at least `min_charge`: with
-    min_charge > 0 every decision spends simulated time, so the policy cannot stand still."""
+    min_charge > 0 every decision spends simulated time, so the policy cannot stand still.  mask_claimed: the candidate mask the actors
+    act under (`VecWRSN.set_entity_pointer_mask`), set on the environment at every call -- True for actors trained with it, False (the
+    default) for every alive node."""
 
-    def __init__(self, packed_actors, deterministic=True, generator=None, min_charge=0.02):
+    def __init__(self, packed_actors, deterministic=True, generator=None, min_charge=0.02, mask_claimed=False):
         self.packed, self.deterministic, self.generator, self.min_charge = packed_actors, bool(deterministic), generator, float(min_charge)
+        self.mask_claimed = bool(mask_claimed)
 
     def __call__(self, env, ids):
+        env._h.set_entity_pointer_mask(POINTER_MASK_CLAIMED if self.mask_claimed else POINTER_MASK_NONE)   # what `VecWRSN.set_entity_pointer_mask` calls
         g = eps = None
         if not self.deterministic:
             t = env.torch

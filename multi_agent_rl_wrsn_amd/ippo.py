@@ -832,18 +832,25 @@ def build_entity_networks(n_agent_rows):
 LOG_SQRT_2PI = 0.5 * math.log(2.0 * math.pi)
 
 
-def build_entity_pointer_networks(n_agent_rows):
+def build_entity_pointer_networks(n_agent_rows, mask_claimed=False):
     """Returns (EntityPointerActor, EntityCritic) classes over packed entity rows [n, R] of `n_agent_rows` chargers; the critic is the
     class `build_entity_networks` returns.  The actor names a node: on the set policy's trunk (z [n, 128] and the per-node embeddings
     h [n, N, 64]) a query q = query(z) scores every alive node, l_i = 0.125 <h_i, q>, the decision is one alive node k drawn from
     softmax(l) and a charge variable x ~ N(mu, exp(log_std)) with (mu, log_std) = charge([z, the chosen node's eight features]); the
     action is (u_k, v_k, min_charge + (1 - min_charge) sigmoid(x)).  A row with no alive node has k = -1, no node term in
     log-probability and entropy, zeros for the node's features and the asking charger's own position as destination.  Like the set
-    policy, nothing couples the rows of a batch (`lin` / `bmm`), and dead or padded node rows have no influence whatever they hold."""
+    policy, nothing couples the rows of a batch (`lin` / `bmm`), and dead or padded node rows have no influence whatever they hold.
+
+    mask_claimed=True: the choice runs over the CANDIDATES of a row instead of its alive nodes (`EntityPointerActor.candidates`, the rule
+    of `wrsn_set_entity_pointer_mask` in include/wrsn_hip.h): the alive nodes outside the charging disc around every other live
+    charger's destination, and every alive node when that leaves none.  Logits, node_logp, log-sum-exp, arg-max, the categorical
+    entropy and the node term of a stored decision see candidates only; the pools behind z still run over all alive nodes and the
+    charge head reads the stored node's features as they stand.  The parameters are the same: a block packs and unpacks either way."""
     torch, lin, _Trunk = _entity_parts(n_agent_rows)
     nn = torch.nn
     M = int(n_agent_rows)
-    c_self, e_agent = _lib.ENT_MC["is_self"], _lib.ENT_ENV["agent"]
+    c_self, c_alive, e_agent = _lib.ENT_MC["is_self"], _lib.ENT_MC["alive"], _lib.ENT_ENV["agent"]
+    masked = bool(mask_claimed)
     _, EntityCritic = build_entity_networks(n_agent_rows)
 
     class EntityPointerActor(nn.Module):
@@ -853,10 +860,31 @@ def build_entity_pointer_networks(n_agent_rows):
             self.query = _ortho(nn.Linear(128, 64), std=0.01)
             self.charge = _ortho(nn.Linear(128 + _lib.ENT_NODE_F, 2), std=0.01)
 
+        mask_claimed = masked
+
+        @staticmethod
+        def candidates(alive, nodes, mcs, env):
+            """cand [n, N] of the views of packed rows: alive and not claimed, or alive where a row holds no such node.  Formed in float32
+            from float32 copies of the row slices whatever dtype the rows have, one elementwise operation at a time -- the bits the
+            device forms (wrsn_eh_claims), so a float64 reference sees the mask the kernel sees.  A claimer is a charger row with
+            alive == 1 and is_self != 1; a NaN compares false and claims nothing."""
+            f = torch.float32
+            u, v = nodes[..., 0].detach().to(f).unsqueeze(2), nodes[..., 1].detach().to(f).unsqueeze(2)          # [n, N, 1]
+            cx, cy = mcs[..., 6].detach().to(f).unsqueeze(1), mcs[..., 7].detach().to(f).unsqueeze(1)            # [n, 1, M]: destinations
+            hx, hy = env[:, 0].detach().to(f).view(-1, 1, 1), env[:, 1].detach().to(f).view(-1, 1, 1)            # the disc's half-axes
+            dx, dy = (u - cx) / hx, (v - cy) / hy
+            inside = (dx * dx + dy * dy) <= 1.0                                                                   # [n, N, M]
+            claimer = (mcs[..., c_alive] == 1) & ~(mcs[..., c_self] == 1)                                         # [n, M]
+            free = alive & ~(inside & claimer.unsqueeze(1)).any(2)
+            return torch.where(free.any(1, keepdim=True), free, alive)
+
         def scores(self, rows):
             """(z [n, 1, 128], logits l [n, N] with -inf for nodes that are not alive, node_logp [n, N] likewise, alive [n, N], the views
-            nodes, mcs, env of `rows`).  Every -inf is put in by a select on finite numbers: no NaN, forward or backward."""
+            nodes, mcs, env of `rows`).  Every -inf is put in by a select on finite numbers: no NaN, forward or backward.  With
+            `mask_claimed` "alive" is "candidate" in everything returned: z alone is pooled over all alive nodes."""
             z, h, alive, nodes, mcs, env = self.trunk.embed(rows)
+            if self.mask_claimed:
+                alive = self.candidates(alive, nodes, mcs, env)
             q = lin(self.query, z)                                                       # [n, 1, 64]
             raw = 0.125 * torch.bmm(h, q.transpose(1, 2)).squeeze(2)                     # [n, N], finite everywhere: h of a dead node comes from zeros
             ninf = torch.full_like(raw, float("-inf"))
@@ -1296,9 +1324,11 @@ class EntityPointerPPOLearner(EntityPPOLearner):
     node's index (-1: no node was alive) and the raw charge variable; `evaluate` recomputes its log-probability from them and the stored
     row.  `minibatch_loss`, `update`, the data-parallel gradient exchange and the checkpoints are inherited."""
 
+    mask_claimed = False                                      # BatchedEntityPointerIPPO sets it before the networks are built
+
     def _build_networks(self):
         self._cl = False
-        Actor, Critic = build_entity_pointer_networks(self.num_agent)
+        Actor, Critic = build_entity_pointer_networks(self.num_agent, self.mask_claimed)
         return ([Actor().to(self.device) for _ in range(self.num_agent)], [Critic().to(self.device) for _ in range(self.num_agent)])
 
     def get_action(self, agent_id, states):
@@ -1355,13 +1385,20 @@ class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
                    the uploaded index by one torch gather.  The batch dicts are bit for bit the default path's.  False (the default):
                    the per-charger `index_select`s and `cal_rt_adv`.
 
+    mask_claimed : True = the actors choose among the candidates of a row, not its alive nodes (`build_entity_pointer_networks`,
+                   `VecWRSN.set_entity_pointer_mask`): never a node inside the charging disc around another live charger's destination
+                   while another alive node is left.  The modules are built with the flag and the mode is set on `env` at construction
+                   and on the evaluation batch by `evaluate_episodes`, so every path -- acting in PyTorch or on the device, the update
+                   in PyTorch or on the device, per charger or joint -- recomputes under the mask what acting stored.  False (the
+                   default): every alive node, and `env` is set to that.
+
     `fused_update` is the set policy's option (BatchedEntityIPPO) and always raises here: this actor's is `device_update`."""
 
     _check_status = True
 
     def __init__(self, args, env, device=None, model_path=None, capacity=None, infer_chunk=1024, process_group=None, log=None, min_bucket=16,
                  min_charge=0.02, fused_policy=False, log_episodes=False, episode_slots=64, fused_update=False, joint_update=False,
-                 fused_prepare=False, device_update=False):
+                 fused_prepare=False, device_update=False, mask_claimed=False):
         if fused_update:
             raise ValueError("BatchedEntityPointerIPPO has no fused_update: that is the Gaussian set policy's option (BatchedEntityIPPO); "
                              "this actor's is device_update")
@@ -1372,8 +1409,10 @@ class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
             raise ValueError("BatchedEntityPointerIPPO needs a VecWRSN with the entity observation (entities=True)")
         if not 0.0 <= float(min_charge) < 1.0:
             raise ValueError("min_charge must lie in [0, 1)")
+        self.mask_claimed = bool(mask_claimed)                # before the networks are built
         super().__init__(args, env.num_agent, device if device is not None else env.device, model_path, infer_chunk, process_group, min_bucket)
         self._attach(env, EntityTransitionBuffers(env, capacity or 2 * self.batch_size, 2), log)
+        env._h.set_entity_pointer_mask(_lib.POINTER_MASK_CLAIMED if self.mask_claimed else _lib.POINTER_MASK_NONE)   # `VecWRSN.set_entity_pointer_mask`
         self.min_charge = float(min_charge)
         self.log_episodes = bool(log_episodes)
         if self.log_episodes:
@@ -1398,7 +1437,8 @@ class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
         from .evaluate import PointerPolicy, evaluate_policy
         if eval_env is self.env:
             raise ValueError("evaluate on a batch of its own: the trainer's environments live across roll-outs")
-        return evaluate_policy(eval_env, PointerPolicy(self.packed_actors(), deterministic, generator, self.min_charge), episodes, **kw)
+        return evaluate_policy(eval_env, PointerPolicy(self.packed_actors(), deterministic, generator, self.min_charge, self.mask_claimed),
+                               episodes, **kw)
 
     def roll_out(self, max_launches=100000, fresh_episodes=False):
         if self.fused_policy:

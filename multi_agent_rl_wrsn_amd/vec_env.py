@@ -275,6 +275,14 @@ class VecWRSN:
                            action=act.data_ptr(), action_f64=act64.data_ptr(), logp=logp.data_ptr())
         return act, act64, logp
 
+    def set_entity_pointer_mask(self, mode):
+        """`wrsn_set_entity_pointer_mask`: the candidate mask of the node-pointer calls that follow on this object -- `entity_pointer_act`,
+        `entity_pointer_eval`, `entity_pointer_ppo_grad`, `entity_pointer_ppo_grad_multi` and `entity_pointer_ppo_update`.
+        `_lib.POINTER_MASK_NONE` (0, the default): every alive node is a candidate.  `_lib.POINTER_MASK_CLAIMED` (1, or True): not the
+        alive nodes inside the charging disc around another live charger's destination, unless that leaves none.  Launches already
+        enqueued keep the mode they were enqueued under."""
+        self._h.set_entity_pointer_mask(int(mode))
+
     def entity_pointer_act(self, agent_ids, packed, gumbel=None, eps=None, min_charge=0.0):
         """`wrsn_entity_pointer_act` on the entity rows this object holds (`entities=True`): the chargers `agent_ids` [B] (< 0: row skipped)
         act with the packed node-pointer actors `packed` [M, P] (`EntityPointerPPOLearner.packed_actors`), the Gumbel draws `gumbel` [B, N]

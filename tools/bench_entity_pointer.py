@@ -9,6 +9,9 @@ on the same rows, the same ids and the same weights (the learner's initial ones)
 
     python tools/bench_entity_pointer.py [--envs 4096] [--windows 5] [--only fused] [--out profiles/entity_pointer_act_bench.json]
 
+--mask-claimed adds a third kind, `masked`: the fused call under wrsn_set_entity_pointer_mask(WRSN_POINTER_MASK_CLAIMED), alternating with
+the others (the mode is set in front of every window); `--only masked` runs it alone.  The torch loop stays unmasked.
+
 What would be a defect rather than a number: the fused call slower than the torch loop of the same run beyond the spread of the windows.
 For context the line carries the ratio to wrsn_entity_act's recorded time (profiles/entity_act_bench.json) when that file is there: the
 second pass over the nodes makes up to about 2 x plausible."""
@@ -33,7 +36,8 @@ def main():
     ap.add_argument("--calls", type=int, default=20, help="timed calls per window")
     ap.add_argument("--warmup", type=int, default=3, help="untimed calls at the start of every window")
     ap.add_argument("--min-charge", type=float, default=0.02)
-    ap.add_argument("--only", default=None, choices=[None, "fused", "torch"], help="run one kind alone (for a kernel trace)")
+    ap.add_argument("--only", default=None, choices=[None, "fused", "torch", "masked"], help="run one kind alone (for a kernel trace)")
+    ap.add_argument("--mask-claimed", action="store_true", help="also time the fused call with the candidate mask on (kind `masked`)")
     ap.add_argument("--out", default=None, help="also write the result line to this file")
     a = ap.parse_args()
     import torch
@@ -75,9 +79,12 @@ def main():
         return (time.perf_counter() - t0) * 1e3 if timed else None
 
     kinds = {k: f for k, f in (("fused", fused), ("torch", loop)) if a.only in (None, k)}
+    if a.only == "masked" or (a.mask_claimed and a.only is None):
+        kinds["masked"] = fused
     res = {k: [] for k in kinds}
     for _ in range(a.windows):
         for kind, f in kinds.items():
+            env.set_entity_pointer_mask(1 if kind == "masked" else 0)
             for _ in range(a.warmup):
                 f(False)
             s = [f(True) for _ in range(a.calls)]
@@ -92,6 +99,8 @@ def main():
         out[kind + "_ms"] = {"windows": w, "median_of_window_medians": statistics.median(x["median"] for x in w), "min": min(x["min"] for x in w),
                              "max": max(x["max"] for x in w)}
     f_ms = out["fused_ms"]["median_of_window_medians"] if "fused" in kinds else None
+    if "masked" in kinds and f_ms is not None:
+        out["masked_over_fused"] = out["masked_ms"]["median_of_window_medians"] / f_ms
     if a.only is None:
         out["torch_over_fused"] = out["torch_ms"]["median_of_window_medians"] / f_ms
     prior = os.path.join(ROOT, "profiles", "entity_act_bench.json")

@@ -8,6 +8,10 @@ actors (mode and sampled) and the actors after `--iters` iterations of BatchedEn
 and sampled), every pointer row with `--min-charge`; it writes profiles/entity_pointer_eval.json.  A policy that uses up `--max-launches` is recorded with its partial log and the number of environments standing still (a
 deterministic policy that repeats an action of zero duration gets the same request again at the same instant).  Writes
 profiles/entity_eval.json.
+`--policy pointer --mask-claimed` runs every pointer row twice in the same run -- without the candidate mask (the names above) and with it
+(`masked_...`; `wrsn_set_entity_pointer_mask`, BatchedEntityPointerIPPO(mask_claimed=True)) --, each trainer on a training batch of its
+own from the same seeds and with the same flags (`--device-update --joint-update --fused-prepare` choose the update; acting is always
+fused), and writes profiles/entity_pointer_mask_eval.json.
 
 --bench: the evaluation loop per launch at `--envs` (4096) x 200 nodes x 3 chargers with the heuristic policy, in two forms: with
 wrsn_episodes_collect, and with the same bookkeeping in elementwise torch on calls that existed before it (`step`, `reset(mask)`).
@@ -118,8 +122,12 @@ def compare(args, make_envs=device_envs):
     pointer = args.policy == "pointer"
     ppo = dict(batch_size=args.batch_size, minibatch_size=args.minibatch_size, n_updates_per_iteration=5)
     if pointer:
-        algo = BatchedEntityPointerIPPO(ppo, train_env, capacity=max(4096, 2 * args.batch_size), fused_policy=True, log_episodes=True,
-                                        min_charge=args.min_charge)
+        def pointer_algo(env, mask):
+            torch.manual_seed(0); np.random.seed(0)           # the same seeds for every trainer of the run
+            return BatchedEntityPointerIPPO(ppo, env, capacity=max(4096, 2 * args.batch_size), fused_policy=True, log_episodes=True,
+                                            min_charge=args.min_charge, device_update=args.device_update, joint_update=args.joint_update,
+                                            fused_prepare=args.fused_prepare, mask_claimed=mask)
+        algo = pointer_algo(train_env, False)
         Policy = lambda det, g=None: PointerPolicy(algo.packed_actors(), det, g, args.min_charge)
     else:
         algo = BatchedEntityIPPO(ppo, train_env, capacity=max(4096, 2 * args.batch_size), fused_policy=True,
@@ -132,6 +140,7 @@ def compare(args, make_envs=device_envs):
            "max_launches": args.max_launches, "policy": args.policy, "policies": {}}
     if pointer:
         out["min_charge"] = args.min_charge
+        out["training_flags"] = {k: bool(getattr(args, k)) for k in ("device_update", "joint_update", "fused_prepare")}
 
     def run(name, policy):
         t0 = time.perf_counter()
@@ -148,28 +157,41 @@ def compare(args, make_envs=device_envs):
     run("uniform", UniformPolicy(gen()))
     run("heuristic", HeuristicPolicy())
     run("heuristic_min_charge", HeuristicPolicy(min_charge=args.min_charge))
-    run("untrained_mode", Policy(True))
-    run("untrained_sampled", Policy(False, gen()))
-    t0 = time.perf_counter()
-    # The trainer raises when a row comes back with a negative status (an environment whose step reported an error: seen after a handful
-    # of iterations at these shapes).  Here such rows are counted, not fatal: they are a few of thousands and ask nobody for an action.
-    algo._check_status = False
-    errors = torch.zeros((), dtype=torch.int64, device=train_env.device)
-    step = train_env.step
+    def train_and_run(algo, train_env, Policy, prefix=""):
+        run(prefix + "untrained_mode", Policy(True))
+        run(prefix + "untrained_sampled", Policy(False, gen()))
+        record = train(algo, train_env)
+        run(prefix + "trained_mode", Policy(True))
+        run(prefix + "trained_sampled", Policy(False, gen()))
+        return record
 
-    def counting_step(ids, act):
-        r = step(ids, act)
-        errors.add_((r["status"] < 0).sum())
-        return r
+    def train(algo, train_env):
+        t0 = time.perf_counter()
+        # The trainer raises when a row comes back with a negative status (an environment whose step reported an error: seen after a handful
+        # of iterations at these shapes).  Here such rows are counted, not fatal: they are a few of thousands and ask nobody for an action.
+        algo._check_status = False
+        errors = torch.zeros((), dtype=torch.int64, device=train_env.device)
+        step = train_env.step
 
-    train_env.step = counting_step
-    rows = algo.train(args.iters - 1) if args.iters > 0 else []
-    train_env.step = step
-    out["training"] = {"iterations": len(rows) // M, "error_status_rows_summed_over_launches": int(errors), "launches": algo.timers["launches"],
-                       "seconds": time.perf_counter() - t0,
-                       "last_rows": [{k: r[k] for k in ("iteration", "agent", "mean_reward", "avg_ep_lifetime", "avg_ep_lens", "episodes")} for r in rows[-M:]]}
-    run("trained_mode", Policy(True))
-    run("trained_sampled", Policy(False, gen()))
+        def counting_step(ids, act):
+            r = step(ids, act)
+            errors.add_((r["status"] < 0).sum())
+            return r
+
+        train_env.step = counting_step
+        rows = algo.train(args.iters - 1) if args.iters > 0 else []
+        train_env.step = step
+        return {"iterations": len(rows) // M, "error_status_rows_summed_over_launches": int(errors), "launches": algo.timers["launches"],
+                "seconds": time.perf_counter() - t0,
+                "last_rows": [{k: r[k] for k in ("iteration", "agent", "mean_reward", "avg_ep_lifetime", "avg_ep_lens", "episodes")} for r in rows[-M:]]}
+
+    out["training"] = train_and_run(algo, train_env, Policy)
+    if pointer and args.mask_claimed:
+        train_m, spare = make_envs(args)                      # a training batch of its own, from the same seeds
+        spare.close() if hasattr(spare, "close") else None
+        algo_m = pointer_algo(train_m, True)
+        out["masked_training"] = train_and_run(algo_m, train_m, lambda det, g=None: PointerPolicy(algo_m.packed_actors(), det, g, args.min_charge, True),
+                                               "masked_")
     return out
 
 
@@ -185,6 +207,10 @@ def main(argv=None):
     ap.add_argument("--eval-envs", type=int, default=256)
     ap.add_argument("--max-launches", type=int, default=4000)
     ap.add_argument("--min-charge", type=float, default=0.02)
+    ap.add_argument("--mask-claimed", action="store_true", help="pointer: every pointer row also with the candidate mask (masked_...)")
+    for k in ("device-update", "joint-update", "fused-prepare"):
+        ap.add_argument("--" + k, action="store_true", help="pointer: BatchedEntityPointerIPPO(%s=True)" % k.replace("-", "_"))
+    ap.add_argument("--fused-policy", action="store_true", help="pointer: accepted for symmetry with bench_ippo.py; the tool always acts fused")
     ap.add_argument("--bench", action="store_true")
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--launches", type=int, default=50)
@@ -193,6 +219,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     out = bench(args) if args.bench else compare(args)
     path = args.out or os.path.join(ROOT, "profiles", "episodes_bench.json" if args.bench else
+                                    "entity_pointer_mask_eval.json" if args.policy == "pointer" and args.mask_claimed else
                                     "entity_pointer_eval.json" if args.policy == "pointer" else "entity_eval.json")
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as w:
