@@ -410,8 +410,9 @@ int wrsn_entity_pointer_act(wrsn_t *h, const float *actors /* [n_mc, floats] */,
  * opt-in mask on the pointer's choice.  Handle state, WRSN_POINTER_MASK_NONE by default; not part of an environment record.  Allowed
  * between any two calls: it is read when a call enqueues its launches, so the launches enqueued so far keep theirs (as
  * wrsn_set_obs_format).  Read by wrsn_entity_pointer_act, wrsn_entity_pointer_eval, wrsn_entity_pointer_ppo_grad,
- * wrsn_entity_pointer_ppo_grad_multi and wrsn_entity_pointer_ppo_update (once, before its loop).  With WRSN_POINTER_MASK_NONE every
- * call gives the bytes it gave before the mask existed.
+ * wrsn_entity_pointer_ppo_grad_multi and wrsn_entity_pointer_ppo_update (once, before its loop), and by the behaviour-cloning calls
+ * wrsn_entity_pointer_bc_grad, wrsn_entity_pointer_bc_grad_multi and wrsn_entity_pointer_bc_update (once, before its loop).  With
+ * WRSN_POINTER_MASK_NONE every call gives the bytes it gave before the mask existed.
  * WRSN_POINTER_MASK_CLAIMED.  A pure function of the row's content (node, mc, env -- acting rows and stored packed rows alike), in
  * float32, every operation rounded on its own (no contraction into an FMA):
  *     claimer o    : charger row o with mc[o][4] (alive) == 1 and mc[o][3] (is_self) != 1.  No agent_id enters, so the update forms it
@@ -453,6 +454,32 @@ int wrsn_set_entity_pointer_mask(wrsn_t *h, int32_t mode);
  * not 16-byte aligned.  Asynchronous on the handle's stream. */
 int wrsn_entity_heuristic_act(wrsn_t *h, const int32_t *agent_id, const wrsn_entity_out *ent, float charge_scale, float *action,
                               double *action_f64);
+
+/* THE HEURISTIC'S DECISION AS A POINTER LABEL: what wrsn_entity_heuristic_act decides, kept as the node-pointer policy stores a decision
+ * (wrsn_entity_pointer_act's `stored`, the [*, 2] pair of EntityTransitionBuffers(action_elems=2)), so that the pointer can be trained on
+ * it (wrsn_entity_pointer_bc_grad below).  For row e with a = agent_id[e] in [0, n_mc), in float32, every operation rounded on its own
+ * (no contraction into an FMA):
+ *     n         = the pick of wrsn_entity_heuristic_act on the row (self, alive, claimed, score, ties and the fallback as stated there)
+ *     stored[0] = (float) n;  -1 when no node is alive
+ *     c         = the heuristic's charging time: t = charge_scale * (1 - node[n][3]), c = t > 0 ? (t < 1 ? t : 1) : 0
+ *     cm        = c > min_charge ? c : min_charge
+ *     u         = (cm - min_charge) / (1 - min_charge)
+ *     u_lo      = 1 / (1 + expf(x_clip));  u_hi = 1 - u_lo;  u = u < u_lo ? u_lo : (u > u_hi ? u_hi : u)
+ *     stored[1] = logf(u / (1 - u))           -x_clip when no node is alive
+ * stored[1] is the x for which the pointer's c = min_charge + (1 - min_charge) * sigmoid(x) is the heuristic's c, up to the clamp: it lies
+ * in [-x_clip, x_clip] up to rounding, so c == 0, c == 1 and c < min_charge give the ends.
+ * action / action_f64, when not NULL, receive THE BYTES wrsn_entity_heuristic_act writes for the row: (u_n, v_n, c) with the heuristic's
+ * own c, not the squashed one; (mc[self][0], mc[self][1], 0) when no node is alive.
+ * Under WRSN_POINTER_MASK_CLAIMED the label's node is a candidate of the masked pointer on every row that holds exactly one is_self flag
+ * (there the mask's claimers are the heuristic's), so the update's kv holds for it; rows with no or several is_self flags are the
+ * exception stated with the mask.
+ * Rows with agent_id outside [0, n_mc) are skipped: every output byte is kept.  A row's output depends on its own entity rows only; two
+ * calls on equal inputs give equal bytes.  `ent` NULL: the registered buffers.  Needs no scenario.  Asynchronous on the handle's stream.
+ * WRSN_ERR_ARG, with every buffer untouched: h, agent_id or stored NULL; ent == NULL and nothing registered; node, mc or env NULL or not
+ * 16-byte aligned; min_charge not finite or outside [0, 1); x_clip not finite or <= 0. */
+int wrsn_entity_heuristic_label(wrsn_t *h, const int32_t *agent_id, const wrsn_entity_out *ent, float charge_scale, float min_charge,
+                                float x_clip, float *stored /* [B,2] */, float *action /* [B,3] or NULL */,
+                                double *action_f64 /* [B,3] or NULL */);
 
 /* EPISODE LEDGER: whole episodes, per environment, on the device.  wrsn_rollout_table sums over whatever ran; this keeps one entry per
  * finished episode -- lifetime (env.now of the closing return), return and decisions per charger, why it ended, the pool record it ran
@@ -668,6 +695,48 @@ int wrsn_entity_pointer_adam_multi(wrsn_t *h, const wrsn_entity_group *groups, i
 int wrsn_entity_pointer_ppo_update(wrsn_t *h, const wrsn_entity_group *groups, int32_t n_groups, int32_t n_node, int32_t n_mc,
                                    const int32_t *index, int32_t batch_size, int32_t minibatch, int32_t epochs, const wrsn_ppo_hyper *hyper,
                                    const wrsn_adam_hyper *adam, float *stats);
+
+/* BEHAVIOUR CLONING OF THE NODE-POINTER ACTOR: supervised training on stored pairs ((float) node, x) -- wrsn_entity_heuristic_label's, or
+ * anybody's -- as a warm start that PPO then fine-tunes.  With logp, H, kv and k exactly as wrsn_entity_pointer_eval defines them for a
+ * row and its stored pair,
+ *     loss = -mean(logp) - ent_coef * mean(H)        over the n rows,
+ * so d loss / d logp = -inv_n and d loss / d H = -ent_coef * inv_n with inv_n = 1.f / (float) n.  These are the two floats
+ * wrsn_entity_pointer_ppo_grad hands its backward pass when norm_adv = 0, advantage == 1, vf_coef = 0 and logp_old is the logp
+ * wrsn_entity_pointer_eval writes (ratio exactly 1, equal terms under the max), and the backward pass is the same kernels: grad_actor
+ * holds THE BYTES that call gives under that setting.  No critic is read, written or stepped.
+ * stats, float32 [8]: loss; -mean(logp); the node part, -mean over the rows with kv of node_logp[k]; the charge part, -mean over all
+ * rows of the Gaussian term -t^2 / 2 - s - 1/2 log 2 pi; mean(H); top-1, the share of the rows with kv whose stored node attains the
+ * row's largest node_logp (ties are hits); the share of rows with kv; 0.  The node part and top-1 divide by the number of rows with kv
+ * and are 0 when there is none.  Sums in double in a fixed order.
+ *
+ * wrsn_entity_pointer_bc_grad: one learner; `stored` [*, 2] indexed like the rows; grad_actor (wrsn_entity_pointer_floats() floats) is
+ * overwritten in block layout, the padding with zeros.
+ * wrsn_entity_pointer_bc_grad_multi: the same for G groups of wrsn_entity_group.  Read of a group: actor, grad_actor, rows and
+ * batch.action (the stored pairs).  critic, its moments, grad_critic, batch.logp_old / advantage / ret / value_old may be NULL; where
+ * given they keep their bytes.  index: DEVICE int32 [G][n] or NULL; stats: DEVICE float32 [G][8].  7 + 3 G launches: the kernels whose
+ * grid carries (group, net) are launched per group on the actor's half.
+ * wrsn_entity_pointer_bc_update: `epochs` x ceil(batch_size / minibatch) steps; a step is wrsn_entity_pointer_bc_grad_multi, then the
+ * actor half of wrsn_entity_pointer_adam_multi: group g's (actor, grad_actor, m_actor, v_actor) stepped at adam_step + 1 + k, clipped by
+ * the actor's own norm, bias corrections formed on the host in double.  index: DEVICE int32 [G][epochs][batch_size] (required); stats:
+ * DEVICE float32 [G][steps][8].  The host loop only enqueues: nothing is read back, nothing synchronises, the scratch of the largest step
+ * is taken before the loop.  The caller advances its step counts by the number of steps; PPO continues from the same moments.
+ * The candidate mask (wrsn_set_entity_pointer_mask) is read when the call enqueues, once before the loop of the update.
+ *
+ * CONTRACT, as for the multi calls above: group g's block, moments, gradient and statistics hold the bytes the single-group call (and
+ * wrsn_entity_adam on the actor block) gives, whatever G is, whatever the other groups hold and wherever g stands.  Two calls on equal
+ * inputs give equal bytes.
+ * WRSN_ERR_ARG, everything checked before the first launch and every buffer untouched: h NULL; a pointer the call reads or writes NULL
+ * (actor, grad_actor, rows, the stored pairs, stats; for the update m_actor, v_actor, index, adam); a block, moment, gradient buffer or
+ * rows not 16-byte aligned; n, batch_size, minibatch or epochs < 1; n_mc outside [1, 8]; n_node < 1 or more than the score block's LDS
+ * holds; n_groups outside [1, 8]; adam_step < 0; two groups naming the same actor block, moment or gradient buffer; ent_coef not finite.
+ * OUT OF SCOPE: per-row loss weights, a device-side shuffle, HIP-graph capture, imitation for the Gaussian set policy. */
+int wrsn_entity_pointer_bc_grad(wrsn_t *h, const float *actor, const wrsn_entity_rows *rows, const float *stored, float ent_coef,
+                                float *grad_actor, float *stats);
+int wrsn_entity_pointer_bc_grad_multi(wrsn_t *h, const wrsn_entity_group *groups, int32_t n_groups, int32_t n, int32_t n_node, int32_t n_mc,
+                                      const int32_t *index, float ent_coef, float *stats);
+int wrsn_entity_pointer_bc_update(wrsn_t *h, const wrsn_entity_group *groups, int32_t n_groups, int32_t n_node, int32_t n_mc,
+                                  const int32_t *index, int32_t batch_size, int32_t minibatch, int32_t epochs, float ent_coef,
+                                  const wrsn_adam_hyper *adam, float *stats);
 
 /* THE PPO BATCH OF SEVERAL LEARNERS, PREPARED ON THE DEVICE: the critic's values of the selected transitions, PPOLearner.cal_rt_adv
  * (gae=True) over them and the gathers of the batch tensors, for G groups (1 <= G <= 8) in three launches however large G and n are.

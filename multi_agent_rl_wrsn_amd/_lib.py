@@ -42,8 +42,9 @@ ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max"
 
 # every entry point include/wrsn_hip.h declares
 EXPORTS = ("wrsn_create", "wrsn_destroy", "wrsn_set_stream", "wrsn_set_scenario", "wrsn_set_scenario_seeded", "wrsn_reset", "wrsn_step",
-           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_entity_actor_floats", "wrsn_entity_act", "wrsn_entity_pointer_floats", "wrsn_entity_pointer_eval", "wrsn_entity_pointer_ppo_grad", "wrsn_entity_pointer_act", "wrsn_entity_heuristic_act", "wrsn_episodes_collect", "wrsn_entity_critic_floats", "wrsn_entity_eval", "wrsn_entity_ppo_grad", "wrsn_entity_adam", "wrsn_entity_ppo_grad_multi", "wrsn_entity_adam_multi", "wrsn_entity_ppo_update", "wrsn_entity_pointer_ppo_grad_multi", "wrsn_entity_pointer_adam_multi",
-           "wrsn_entity_pointer_ppo_update", "wrsn_set_entity_pointer_mask", "wrsn_entity_prepare", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
+           "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_entity_actor_floats", "wrsn_entity_act", "wrsn_entity_pointer_floats", "wrsn_entity_pointer_eval", "wrsn_entity_pointer_ppo_grad", "wrsn_entity_pointer_act", "wrsn_entity_heuristic_act", "wrsn_entity_heuristic_label", "wrsn_episodes_collect", "wrsn_entity_critic_floats", "wrsn_entity_eval", "wrsn_entity_ppo_grad", "wrsn_entity_adam", "wrsn_entity_ppo_grad_multi", "wrsn_entity_adam_multi", "wrsn_entity_ppo_update", "wrsn_entity_pointer_ppo_grad_multi", "wrsn_entity_pointer_adam_multi",
+           "wrsn_entity_pointer_ppo_update", "wrsn_entity_pointer_bc_grad", "wrsn_entity_pointer_bc_grad_multi", "wrsn_entity_pointer_bc_update",
+           "wrsn_set_entity_pointer_mask", "wrsn_entity_prepare", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
            "wrsn_clone_envs", "wrsn_pool_set", "wrsn_pool_reset", "wrsn_synth_network",
            "wrsn_last_error",
            "wrsn_version")
@@ -181,6 +182,8 @@ def bind(lib):
     lib.wrsn_entity_pointer_act.restype = C.c_int
     lib.wrsn_entity_heuristic_act.argtypes = [vp, vp, C.POINTER(WrsnEntityOut), C.c_float, vp, vp]
     lib.wrsn_entity_heuristic_act.restype = C.c_int
+    lib.wrsn_entity_heuristic_label.argtypes = [vp, vp, C.POINTER(WrsnEntityOut), C.c_float, C.c_float, C.c_float, vp, vp, vp]
+    lib.wrsn_entity_heuristic_label.restype = C.c_int
     lib.wrsn_episodes_collect.argtypes = [vp, C.POINTER(WrsnEpisodeLog), C.POINTER(WrsnStepOut), C.c_double, vp, vp, C.c_int32]
     lib.wrsn_episodes_collect.restype = C.c_int
     lib.wrsn_entity_critic_floats.argtypes = []
@@ -208,6 +211,13 @@ def bind(lib):
     lib.wrsn_entity_pointer_adam_multi.restype = C.c_int
     lib.wrsn_entity_pointer_ppo_update.argtypes = lib.wrsn_entity_ppo_update.argtypes
     lib.wrsn_entity_pointer_ppo_update.restype = C.c_int
+    lib.wrsn_entity_pointer_bc_grad.argtypes = [vp, vp, C.POINTER(WrsnEntityRows), vp, C.c_float, vp, vp]
+    lib.wrsn_entity_pointer_bc_grad.restype = C.c_int
+    lib.wrsn_entity_pointer_bc_grad_multi.argtypes = [vp, C.POINTER(WrsnEntityGroup), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_float, vp]
+    lib.wrsn_entity_pointer_bc_grad_multi.restype = C.c_int
+    lib.wrsn_entity_pointer_bc_update.argtypes = [vp, C.POINTER(WrsnEntityGroup), C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32,
+                                                  C.c_float, C.POINTER(WrsnAdamHyper), vp]
+    lib.wrsn_entity_pointer_bc_update.restype = C.c_int
     lib.wrsn_entity_prepare.argtypes = [vp, C.POINTER(WrsnPrepareGroup), C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_float, C.c_float]
     lib.wrsn_entity_prepare.restype = C.c_int
     lib.wrsn_set_obs_reuse.argtypes = [vp, C.c_int32]
@@ -430,6 +440,13 @@ class RawHandle:
         check(self.lib, self.lib.wrsn_entity_heuristic_act(self._h, C.c_void_p(agent_ptr or None), self._ent(ent_ptrs), float(charge_scale),
                                                            C.c_void_p(action or None), C.c_void_p(action_f64 or None)))
 
+    def entity_heuristic_label(self, agent_ptr, ent_ptrs=None, charge_scale=1.0, min_charge=0.0, x_clip=4.0, stored=0, action=0, action_f64=0):
+        """wrsn_entity_heuristic_label: the heuristic's decision of every row as the node-pointer policy stores it, ((float) node, x), into
+        stored [B,2] float32; action [B,3] / action_f64 (0: not wanted) receive wrsn_entity_heuristic_act's bytes."""
+        check(self.lib, self.lib.wrsn_entity_heuristic_label(self._h, C.c_void_p(agent_ptr or None), self._ent(ent_ptrs), float(charge_scale),
+                                                             float(min_charge), float(x_clip), C.c_void_p(stored or None),
+                                                             C.c_void_p(action or None), C.c_void_p(action_f64 or None)))
+
     def episodes_collect(self, log, time_limit=0.0, next_agent_ptr=0, restart_ptr=0, consume=True, **out_ptrs):
         """wrsn_episodes_collect: `log` is a WrsnEpisodeLog (None: NULL); out_ptrs the request rows the last environment call wrote."""
         o = self._out(**out_ptrs)
@@ -543,6 +560,28 @@ class RawHandle:
         check(self.lib, self.lib.wrsn_entity_pointer_ppo_update(self._h, self._groups(groups), len(groups) if n_groups is None else int(n_groups),
                                                                 int(n_node), int(n_mc), C.c_void_p(index or None), int(batch_size), int(minibatch),
                                                                 int(epochs), self._hyper(hyper), self._adam(adam), C.c_void_p(stats or None)))
+
+    def entity_pointer_bc_grad(self, actor_ptr, rows_ptr, index_ptr, n, n_node, n_mc, stored, ent_coef, grad_actor, stats):
+        """wrsn_entity_pointer_bc_grad: d / d block of -mean(logp) - ent_coef mean(H) of the stored pairs ([*, 2], indexed like the rows)
+        into grad_actor (wrsn_entity_pointer_floats() floats) and the statistics (float32 [8]: loss, -mean logp, node part, charge part,
+        mean H, top-1, share of rows with a live stored node, 0) into stats.  No critic."""
+        check(self.lib, self.lib.wrsn_entity_pointer_bc_grad(self._h, C.c_void_p(actor_ptr or None), self._rows(rows_ptr, index_ptr, n, n_node, n_mc),
+                                                             C.c_void_p(stored or None), float(ent_coef), C.c_void_p(grad_actor or None),
+                                                             C.c_void_p(stats or None)))
+
+    def entity_pointer_bc_grad_multi(self, groups, n, n_node, n_mc, index, ent_coef, stats, n_groups=None):
+        """wrsn_entity_pointer_bc_grad_multi: `entity_pointer_bc_grad` for every group (dicts, see `_groups`: actor, grad_actor, rows and
+        `action`, the stored pairs, are read; the critic's side may be absent); index: int32 [G][n] or 0; stats: float32 [G][8]."""
+        check(self.lib, self.lib.wrsn_entity_pointer_bc_grad_multi(self._h, self._groups(groups), len(groups) if n_groups is None else int(n_groups),
+                                                                   int(n), int(n_node), int(n_mc), C.c_void_p(index or None), float(ent_coef),
+                                                                   C.c_void_p(stats or None)))
+
+    def entity_pointer_bc_update(self, groups, n_node, n_mc, index, batch_size, minibatch, epochs, ent_coef, adam, stats, n_groups=None):
+        """wrsn_entity_pointer_bc_update: epochs x ceil(batch_size / minibatch) steps of `entity_pointer_bc_grad_multi` and Adam on the actor
+        blocks alone (group g at adam_step + 1 + k); index: int32 [G][epochs][batch_size], stats: float32 [G][steps][8].  Only enqueues."""
+        check(self.lib, self.lib.wrsn_entity_pointer_bc_update(self._h, self._groups(groups), len(groups) if n_groups is None else int(n_groups),
+                                                               int(n_node), int(n_mc), C.c_void_p(index or None), int(batch_size), int(minibatch),
+                                                               int(epochs), float(ent_coef), self._adam(adam), C.c_void_p(stats or None)))
 
     def entity_prepare(self, groups, n, n_node, n_mc, index, gamma, gae_lambda, n_groups=None):
         """wrsn_entity_prepare: values, GAE and gathers of every group's batch in three launches.  groups: dicts of device addresses under

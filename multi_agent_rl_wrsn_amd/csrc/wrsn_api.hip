@@ -1052,6 +1052,22 @@ int wrsn_entity_heuristic_act(wrsn_t* h, const int32_t* agent_id, const wrsn_ent
     return WRSN_OK;
 }
 
+int wrsn_entity_heuristic_label(wrsn_t* h, const int32_t* agent_id, const wrsn_entity_out* ent, float charge_scale, float min_charge, float x_clip,
+                                float* stored, float* action, double* action_f64) {
+    if (!h || !agent_id || !stored) return fail(WRSN_ERR_ARG, "wrsn_entity_heuristic_label needs agent_id and stored");
+    if (!std::isfinite(min_charge) || min_charge < 0.f || min_charge >= 1.f)
+        return fail(WRSN_ERR_ARG, "wrsn_entity_heuristic_label: min_charge must be finite and in [0, 1)");
+    if (!std::isfinite(x_clip) || x_clip <= 0.f) return fail(WRSN_ERR_ARG, "wrsn_entity_heuristic_label: x_clip must be finite and > 0");
+    WrsnEntityOut e{};
+    { const int rc = entity_in(h, ent, &e); if (rc) return rc; }
+    WRSN_ON_DEVICE(h);
+    const int B = h->dev.B;
+    hipLaunchKernelGGL(wrsn_entity_heuristic_label_kernel, entity_row_grid(B), dim3(64 * WRSN_ENT_ROWS), 0, h->stream, B, h->dev.M, h->dev.N, agent_id, e,
+                       charge_scale, min_charge, x_clip, stored, action, action_f64);
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
 int wrsn_episodes_collect(wrsn_t* h, const wrsn_episode_log* log, const wrsn_step_out* out, double time_limit, int32_t* next_agent_id,
                           uint8_t* restart, int32_t consume) {
     if (!h || !log || !out) return fail(WRSN_ERR_ARG, "null argument");
@@ -1488,6 +1504,164 @@ int wrsn_entity_pointer_ppo_update(wrsn_t* h, const wrsn_entity_group* groups, i
             WrsnEtAdamBlocks bs{};
             entity_adam_table(groups, n_groups, k, adam, &bs, WRSN_PP_FLOATS);
             if (const int rc = entity_adam_launch(h, bs, 2 * n_groups, WRSN_PP_FLOATS, adam->beta1, adam->beta2, adam->eps, adam->max_norm)) return rc;
+        }
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+// ------------------------------------------------------------------ behaviour cloning of the node-pointer actor (wrsn_entity_pointer_train.h,
+// at its end): the PPO calls' kernels on a group table without critics, one new loss kernel, Adam on the actor blocks alone
+namespace {
+// what is wrong with the G groups of a behaviour-cloning call, or nullptr: only the actor's side of a group is looked at
+const char* bc_groups_bad(const wrsn_entity_group* groups, int G, bool batch, bool moments) {
+    if (G < 1 || G > WRSN_MAX_MC) return "n_groups must be in [1, 8]";
+    if (!groups) return "groups is required";
+    const void* named[WRSN_MAX_MC][4];
+    const int nn = moments ? 4 : 2;
+    for (int g = 0; g < G; ++g) {
+        const wrsn_entity_group& q = groups[g];
+        if (!q.actor || !q.grad_actor) return "every group needs actor and grad_actor";
+        if ((uintptr_t)q.actor % 16 || (uintptr_t)q.grad_actor % 16) return "blocks and gradient buffers must be 16-byte aligned";
+        if (batch) {
+            if (!q.rows || !q.batch.action) return "every group needs rows and the stored pairs (batch.action)";
+            if ((uintptr_t)q.rows % 16) return "rows must be 16-byte aligned";
+        }
+        if (moments) {
+            if (!q.m_actor || !q.v_actor) return "every group needs m_actor and v_actor";
+            if ((uintptr_t)q.m_actor % 16 || (uintptr_t)q.v_actor % 16) return "moments must be 16-byte aligned";
+            if (q.adam_step < 0) return "adam_step must be >= 0";
+        }
+        const void* mine[4] = {q.actor, q.grad_actor, q.m_actor, q.v_actor};
+        for (int k = 0; k < nn; ++k) {
+            for (int g2 = 0; g2 < g; ++g2)
+                for (int k2 = 0; k2 < nn; ++k2)
+                    if (named[g2][k2] == mine[k]) return "two groups name the same block, moment or gradient buffer";
+            named[g][k] = mine[k];
+        }
+    }
+    return nullptr;
+}
+// entity_group_table without the critics: no kernel of a behaviour-cloning call sees a critic, its gradient buffer or the PPO batch arrays
+void bc_group_table(const wrsn_entity_group* groups, int G, const int32_t* index, size_t index_stride, float* stats, size_t stats_stride, WrsnEtGroups* gs) {
+    for (int g = 0; g < G; ++g) {
+        const wrsn_entity_group& q = groups[g];
+        WrsnEtGroup& d = gs->g[g];
+        d.actor = q.actor; d.grad_actor = q.grad_actor; d.rows = q.rows; d.b.action = q.batch.action;
+        d.index = index ? index + (size_t)g * index_stride : nullptr;
+        d.stats = stats + (size_t)g * stats_stride;
+    }
+}
+// group g's slices of the two scratch areas, formed on the host (wrsn_et_slice / wrsn_etp_slice)
+WrsnEtScratch host_slice(WrsnEtScratch s, int g) {
+    const size_t o = (size_t)g * s.chunk;
+    s.feat += o; s.arg += o; s.cnt += o; s.z1 += o; s.z2 += o; s.dz1 += o; s.dz2 += o; s.dfeat += o; s.part += o; s.raw += o; s.dout += o;
+    return s;
+}
+WrsnEtpScratch host_slice_ptr(WrsnEtpScratch ps, int g) {
+    const size_t o = (size_t)g * ps.chunk;
+    ps.q += o; ps.lp += o; ps.prow += o; ps.dq += o; ps.dch += o; ps.part2 += o;
+    return ps;
+}
+// one behaviour-cloning gradient step of G groups: pointer_grad_launch with wrsn_etp_bc_loss_kernel for the loss and, for the three
+// kernels whose grid carries (group, net), one launch per group on the actor half alone.  7 + 3 G launches.  Arguments are checked by the callers.
+int pointer_bc_launch(wrsn_handle* h, const WrsnEtGroups& gs, int G, const WrsnEtDims& dm, float ent_coef, int mask) {
+    WrsnEtScratch s; WrsnEtpScratch ps;
+    { const int rc = pointer_scratch(h, dm.n, dm.N, true, G, &s, &ps); if (rc) return rc; }
+    const int n = dm.n;
+    pointer_forward(h, gs, G, dm, s, ps, nullptr, nullptr, WrsnEtpEvalOut{}, mask);
+    hipLaunchKernelGGL(wrsn_etp_bc_loss_kernel, dim3(G), dim3(256), 256 * sizeof(double), h->stream, gs, n, dm.N, ent_coef, s, ps);
+    hipLaunchKernelGGL(wrsn_etp_score_bwd_kernel, dim3(G * n), dim3(256), WRSN_ETP_BWD_LDS(dm.N), h->stream, gs, dm, s, ps);
+    for (int g = 0; g < G; ++g) {
+        WrsnEtGroups one{};
+        one.g[0] = gs.g[g];
+        const WrsnEtScratch sg = host_slice(s, g);
+        hipLaunchKernelGGL(wrsn_etp_head_bwd_kernel, dim3(n), dim3(256), 256 * sizeof(float), h->stream, one, n, sg);
+        hipLaunchKernelGGL(wrsn_et_trunk_bwd_kernel, dim3(n), dim3(256), WRSN_ET_B_LDS, h->stream, one, dm, sg);
+    }
+    hipLaunchKernelGGL(wrsn_etp_trunk_bwd_kernel, dim3(G * n), dim3(256), WRSN_ET_B_LDS, h->stream, gs, dm, s, ps);
+    for (int g = 0; g < G; ++g) {
+        WrsnEtGroups one{};
+        one.g[0] = gs.g[g];
+        hipLaunchKernelGGL(wrsn_etp_reduce_kernel, dim3((WRSN_PP_FLOATS + 255) / 256), dim3(256), 0, h->stream, one, dm, host_slice(s, g), host_slice_ptr(ps, g));
+    }
+    return 0;
+}
+// the actor blocks of the groups as an Adam table of G entries, group g at adam_step + 1 + step_offset
+void bc_adam_table(const wrsn_entity_group* groups, int G, int step_offset, const wrsn_adam_hyper* a, WrsnEtAdamBlocks* bs) {
+    for (int g = 0; g < G; ++g) {
+        const wrsn_entity_group& q = groups[g];
+        entity_adam_block(bs, g, q.actor, q.grad_actor, q.m_actor, q.v_actor, nullptr, WRSN_PP_FLOATS, q.adam_step + 1 + step_offset, a->lr, a->beta1, a->beta2);
+    }
+}
+}  // namespace
+
+int wrsn_entity_pointer_bc_grad(wrsn_t* h, const float* actor, const wrsn_entity_rows* rows, const float* stored, float ent_coef, float* grad_actor,
+                                float* stats) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    if (const char* bad = entity_rows_bad(rows)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_bc_grad: ") + bad);
+    if (!actor || !stored || !grad_actor || !stats) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_grad needs actor, stored, grad_actor and stats");
+    if ((uintptr_t)actor % 16 || (uintptr_t)grad_actor % 16)
+        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_grad: the block and the gradient buffer must be 16-byte aligned");
+    if (!std::isfinite(ent_coef)) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_grad: ent_coef must be finite");
+    if (WRSN_ETP_BWD_LDS(rows->n_node) > 65536) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_grad: too many nodes for the score block's LDS");
+    WRSN_ON_DEVICE(h);
+    WrsnEtDims dm; dm.n = rows->n; dm.N = rows->n_node; dm.M = rows->n_mc;
+    WrsnEtGroups gs{};
+    WrsnEtGroup& G = gs.g[0];
+    G.actor = actor; G.grad_actor = grad_actor; G.rows = rows->rows; G.index = rows->index; G.stats = stats; G.b.action = stored;
+    if (const int rc = pointer_bc_launch(h, gs, 1, dm, ent_coef, h->ptr_mask)) return rc;
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+int wrsn_entity_pointer_bc_grad_multi(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, int32_t n, int32_t n_node, int32_t n_mc,
+                                      const int32_t* index, float ent_coef, float* stats) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    if (const char* bad = bc_groups_bad(groups, n_groups, true, false)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_bc_grad_multi: ") + bad);
+    if (const char* bad = entity_dims_bad(n, n_node, n_mc)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_bc_grad_multi: ") + bad);
+    if (!stats) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_grad_multi needs stats");
+    if (!std::isfinite(ent_coef)) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_grad_multi: ent_coef must be finite");
+    if (WRSN_ETP_BWD_LDS(n_node) > 65536) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_grad_multi: too many nodes for the score block's LDS");
+    WRSN_ON_DEVICE(h);
+    WrsnEtGroups gs{};
+    bc_group_table(groups, n_groups, index, (size_t)n, stats, 8, &gs);
+    WrsnEtDims dm; dm.n = n; dm.N = n_node; dm.M = n_mc;
+    if (const int rc = pointer_bc_launch(h, gs, n_groups, dm, ent_coef, h->ptr_mask)) return rc;
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+int wrsn_entity_pointer_bc_update(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, int32_t n_node, int32_t n_mc, const int32_t* index,
+                                  int32_t batch_size, int32_t minibatch, int32_t epochs, float ent_coef, const wrsn_adam_hyper* adam, float* stats) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    if (const char* bad = bc_groups_bad(groups, n_groups, true, true)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_bc_update: ") + bad);
+    if (batch_size < 1 || minibatch < 1 || epochs < 1)
+        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_update: batch_size, minibatch and epochs must be >= 1");
+    if (const char* bad = entity_dims_bad(batch_size, n_node, n_mc)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_bc_update: ") + bad);
+    if (!index || !adam || !stats) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_update needs index, adam and stats");
+    if (!std::isfinite(ent_coef)) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_update: ent_coef must be finite");
+    const int per_epoch = (int)(((int64_t)batch_size + minibatch - 1) / minibatch);
+    const int64_t steps64 = (int64_t)per_epoch * epochs;
+    if (steps64 > INT32_MAX) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_update: too many steps");
+    const int steps = (int)steps64, n_full = minibatch < batch_size ? minibatch : batch_size;
+    if (WRSN_ETP_BWD_LDS(n_node) > 65536) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_update: too many nodes for the score block's LDS");
+    WRSN_ON_DEVICE(h);
+    {   // the scratch area of the largest step, so that no step of the loop allocates
+        WrsnEtScratch s; WrsnEtpScratch ps;
+        const int rc = pointer_scratch(h, n_full, n_node, true, n_groups, &s, &ps); if (rc) return rc;
+    }
+    if (!h->et_norm) { const int rc = dalloc(h, &h->et_norm, (size_t)(2 * WRSN_MAX_MC)); if (rc) return rc; }
+    const int mask = h->ptr_mask;                             // read once: every step of the loop under the same mask
+    int k = 0;
+    for (int e = 0; e < epochs; ++e)
+        for (int start = 0; start < batch_size; start += minibatch, ++k) {   // only enqueues: nothing is read back, nothing synchronises
+            WrsnEtGroups gs{};
+            bc_group_table(groups, n_groups, index + (size_t)e * batch_size + start, (size_t)epochs * batch_size, stats + (size_t)k * 8, (size_t)steps * 8, &gs);
+            WrsnEtDims dm; dm.n = batch_size - start < minibatch ? batch_size - start : minibatch; dm.N = n_node; dm.M = n_mc;
+            if (const int rc = pointer_bc_launch(h, gs, n_groups, dm, ent_coef, mask)) return rc;
+            WrsnEtAdamBlocks bs{};
+            bc_adam_table(groups, n_groups, k, adam, &bs);
+            if (const int rc = entity_adam_launch(h, bs, n_groups, WRSN_PP_FLOATS, adam->beta1, adam->beta2, adam->eps, adam->max_norm)) return rc;
         }
     HIPCHK(hipGetLastError());
     return WRSN_OK;

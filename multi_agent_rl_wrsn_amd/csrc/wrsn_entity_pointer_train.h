@@ -436,3 +436,55 @@ __global__ void __launch_bounds__(256) wrsn_etp_reduce_kernel(WrsnEtGroups gs, W
     const int grp = ((int)blockIdx.x / ((WRSN_PP_FLOATS + 255) / 256)) >> 1;   // the body's own split: (group * 2 + net) * (blocks per net) + ...
     wrsn_et_reduce_body<true>(gs, dm.n, s0, wrsn_etp_slice(ps, grp), dm.N, dm.M);
 }
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Behaviour cloning (wrsn_entity_pointer_bc_grad, _bc_grad_multi, _bc_update): loss = -mean(logp) - ent_coef mean(H) of the stored pairs,
+// the actor alone.  Every kernel above is launched as it stands on a group table WITHOUT critics: the forward kernels skip a net that is
+// not given, the per-row pointer kernels serve the actor anyway (G * n blocks), and the three that index (group, net) by the block --
+// head backward, trunk backward, reduce -- are launched once per group on that group's entry and slice, with the actor half of the grid
+// only (block index / n == 0: group 0, net 0).  New is this loss kernel, one block per group in the place of wrsn_etp_loss_kernel:
+//   dout[0] = -inv_n, dout[1] = -ent_coef inv_n, the other six slots zero (the value slot among them) -- the floats wrsn_et_loss_body
+//   writes for ratio 1, advantage 1 and equal terms under the max, so the backward kernels produce the PPO call's bytes from them;
+//   stats[0..7] = loss, -mean(logp), -mean over the rows with kv of the node term, -mean of the Gaussian term, mean(H), top-1 (the share
+//   of the rows with kv whose stored node attains the row's largest node_logp, ties are hits), the share of rows with kv, 0.  The two
+//   means over "rows with kv" divide by THEIR count (0 when there is none).  node_logp is read from the lp rows the score forward left
+//   in the scratch, before the score backward overwrites them; the row maximum is taken by a wave per row (exact, so no order enters).
+// Sums in double through wrsn_et_block_sum: thread t takes rows t, t + 256, ...; no float atomics.
+__global__ void __launch_bounds__(256) wrsn_etp_bc_loss_kernel(WrsnEtGroups gs, int n, int N, float ent_coef, WrsnEtScratch s0, WrsnEtpScratch ps0) {
+    extern __shared__ double smem[];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = (int)blockIdx.x;   // one block per group
+    float* stats = gs.g[grp].stats;
+    const WrsnEtScratch s = wrsn_et_slice(s0, grp);
+    const WrsnEtpScratch ps = wrsn_etp_slice(ps0, grp);
+    const float ninf = -__builtin_inff();
+    const float inv_n = 1.f / (float)n;
+    double a_lp = 0.0, a_node = 0.0, a_g = 0.0, a_h = 0.0, a_kv = 0.0, a_hit = 0.0;
+    for (int i = tid; i < n; i += 256) {
+        const float* pr = ps.prow + (size_t)i * 8;
+        float* dout = s.dout + (size_t)i * 8;
+        const float sraw = pr[4], t = pr[7], ls = fminf(fmaxf(sraw, -4.f), 1.f);
+        const int k = (int)pr[5];
+        const bool kv = pr[6] == 1.f;
+        a_lp += (double)pr[0]; a_h += (double)pr[1];
+        a_g += (double)(-0.5f * t * t - ls - 0.9189385f);     // the Gaussian term as the score kernel forms it
+        if (kv) { a_node += (double)ps.lp[(size_t)i * ps.ld + k]; a_kv += 1.0; }
+        dout[0] = -inv_n; dout[1] = -ent_coef * inv_n; dout[2] = 0.f; dout[3] = 0.f; dout[4] = 0.f; dout[5] = 0.f; dout[6] = 0.f; dout[7] = 0.f;
+    }
+    for (int i = wave; i < n; i += 4) {                       // wave-uniform: the row's largest node_logp, lanes by a butterfly
+        const float* lrow = ps.lp + (size_t)i * ps.ld;
+        float mx = ninf;
+        for (int j = lane; j < N; j += 64) { const float l = lrow[j]; mx = l > mx ? l : mx; }
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) { const float o = __shfl_xor(mx, d); mx = o > mx ? o : mx; }
+        const float* pr = ps.prow + (size_t)i * 8;
+        const int k = (int)pr[5];
+        if (lane == 0 && pr[6] == 1.f && lrow[k] >= mx) a_hit += 1.0;
+    }
+    const double lp = wrsn_et_block_sum(a_lp, smem, tid) / n, en = wrsn_et_block_sum(a_h, smem, tid) / n, ga = wrsn_et_block_sum(a_g, smem, tid) / n;
+    const double nd = wrsn_et_block_sum(a_node, smem, tid), kc = wrsn_et_block_sum(a_kv, smem, tid), hit = wrsn_et_block_sum(a_hit, smem, tid);
+    if (tid == 0) {
+        stats[0] = (float)(-lp - (double)ent_coef * en);
+        stats[1] = (float)(-lp); stats[2] = kc > 0.0 ? (float)(-nd / kc) : 0.f; stats[3] = (float)(-ga); stats[4] = (float)en;
+        stats[5] = kc > 0.0 ? (float)(hit / kc) : 0.f; stats[6] = (float)(kc / n); stats[7] = 0.f;
+    }
+}

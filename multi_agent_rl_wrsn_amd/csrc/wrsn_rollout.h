@@ -670,6 +670,72 @@ __global__ void __launch_bounds__(64 * WRSN_ENT_ROWS) wrsn_entity_heuristic_kern
     if (action_f64) { double* d = action_f64 + (size_t)e * 3; d[0] = (double)x; d[1] = (double)y; d[2] = (double)t; }
 }
 
+// ------------------------------------------------------------------ the heuristic's decision as a pointer label (wrsn_entity_heuristic_label)
+// The pick of wrsn_entity_heuristic_kernel -- the same loop over the same helpers, so the node is that kernel's node -- kept as the
+// node-pointer policy stores a decision: ((float) node, x), x being the pre-sigmoid charge for which the pointer's
+// min_charge + (1 - min_charge) sigmoid(x) is the heuristic's charging time c, up to the clamp to [-x_clip, x_clip].  A wave per row,
+// no LDS, no __syncthreads; the action, when asked for, is the heuristic's own (u_n, v_n, c).
+WDEV float wrsn_eh_label_x(float c, float min_charge, float x_clip) {
+#pragma clang fp contract(off)
+    const float cm = c > min_charge ? c : min_charge;
+    const float num = cm - min_charge, den = 1.f - min_charge;
+    float u = num / den;
+    const float ex = expf(x_clip);
+    const float u_lo = 1.f / (1.f + ex), u_hi = 1.f - u_lo;
+    u = u < u_lo ? u_lo : (u > u_hi ? u_hi : u);
+    const float om = 1.f - u;
+    return logf(u / om);
+}
+
+__global__ void __launch_bounds__(64 * WRSN_ENT_ROWS) wrsn_entity_heuristic_label_kernel(int B, int M, int N, const int32_t* __restrict__ agent_id, WrsnEntityOut ent,
+                                                                                          float charge_scale, float min_charge, float x_clip,
+                                                                                          float* __restrict__ stored, float* __restrict__ action,
+                                                                                          double* __restrict__ action_f64) {
+    const int lane = (int)threadIdx.x & 63;
+    const int e = (int)blockIdx.x * WRSN_ENT_ROWS + ((int)threadIdx.x >> 6);
+    if (e >= B) return;
+    const int a = wrsn_wave_first(agent_id[e]);
+    if (a < 0 || a >= M) return;
+    const float* mc = ent.mc + (size_t)e * M * WRSN_ENT_MC_F;
+    const float hx = ent.env[(size_t)e * WRSN_ENT_ENV_F], hy = ent.env[(size_t)e * WRSN_ENT_ENV_F + 1];
+    int self = a;
+    for (int o = M - 1; o >= 0; --o) if (mc[o * WRSN_ENT_MC_F + 3] == 1.f) self = o;
+    float cx[WRSN_MAX_MC], cy[WRSN_MAX_MC]; bool on[WRSN_MAX_MC];
+#pragma unroll
+    for (int o = 0; o < WRSN_MAX_MC; ++o) {
+        const int c = o < M ? o : M - 1;                      // clamped: chargers beyond M are switched off
+        on[o] = o < M && o != self && mc[c * WRSN_ENT_MC_F + 4] == 1.f;
+        cx[o] = mc[c * WRSN_ENT_MC_F + 6]; cy[o] = mc[c * WRSN_ENT_MC_F + 7];
+    }
+    const auto node = wrsn_global((const WrsnU4*)(ent.node + (size_t)e * N * WRSN_ENT_NODE_F));
+    const float ninf = -__builtin_inff();
+    float sA = ninf, sU = ninf; int iA = WRSN_EH_NONE, iU = WRSN_EH_NONE;
+    for (int n0 = 0; n0 < N; n0 += 64) {
+        const int n = n0 + lane, c = n < N ? n : N - 1;       // clamped: nodes beyond N are no candidates
+        const WrsnU4 p = wrsn_ld_u4(node + 2 * c), q = wrsn_ld_u4(node + 2 * c + 1);
+        const float u = __int_as_float((int)p.x), v = __int_as_float((int)p.y), w = __int_as_float((int)p.z);
+        const bool alive = n < N && __int_as_float((int)q.w) == 1.f;
+        bool claimed = false;
+#pragma unroll
+        for (int o = 0; o < WRSN_MAX_MC; ++o) claimed = claimed || (on[o] && wrsn_eh_claims(u, v, cx[o], cy[o], hx, hy));
+        const float s = w > ninf ? w : ninf;                  // a NaN never beats a number
+        if (alive && (iA == WRSN_EH_NONE || s > sA)) { sA = s; iA = n; }
+        if (alive && !claimed && (iU == WRSN_EH_NONE || s > sU)) { sU = s; iU = n; }
+    }
+    const int bU = wrsn_eh_wave_best(sU, iU), bA = wrsn_eh_wave_best(sA, iA);
+    const int n = bU != WRSN_EH_NONE ? bU : bA;
+    if (lane != 0) return;
+    float x, y, t, kf, xs;
+    if (n != WRSN_EH_NONE) {
+        const float* r = ent.node + ((size_t)e * N + n) * WRSN_ENT_NODE_F;
+        x = r[0]; y = r[1]; t = wrsn_eh_charge(charge_scale, r[3]);
+        kf = (float)n; xs = wrsn_eh_label_x(t, min_charge, x_clip);
+    } else { x = mc[self * WRSN_ENT_MC_F]; y = mc[self * WRSN_ENT_MC_F + 1]; t = 0.f; kf = -1.f; xs = -x_clip; }
+    stored[(size_t)e * 2] = kf; stored[(size_t)e * 2 + 1] = xs;
+    if (action) { float* o = action + (size_t)e * 3; o[0] = x; o[1] = y; o[2] = t; }
+    if (action_f64) { double* d = action_f64 + (size_t)e * 3; d[0] = (double)x; d[1] = (double)y; d[2] = (double)t; }
+}
+
 // ------------------------------------------------------------------ node-pointer entity policy: acting (wrsn_entity_pointer_act)
 // The actor of build_entity_pointer_networks (ippo.py): the trunk of the set policy, a categorical choice of ONE alive node by a score per
 // node, and a charge head on the chosen node's features.  The query needs z, z needs the pools over all nodes: the nodes are visited

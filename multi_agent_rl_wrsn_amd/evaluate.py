@@ -7,7 +7,8 @@ launch and the restart mask; the host reads one flag every `poll` launches.
 Policies are callables `policy(env, ids) -> float64 [B, 3]` (rows with ids outside [0, M) are ignored by `env.step`):
 `EntityPolicy` (the learned set policy through `wrsn_entity_act`, its mode or a sample), `PointerPolicy` (the learned node-pointer
 policy through `wrsn_entity_pointer_act`, likewise), `HeuristicPolicy` (the deterministic baseline of
-`wrsn_entity_heuristic_act`) and `UniformPolicy` (`torch.rand`)."""
+`wrsn_entity_heuristic_act`), `HeuristicLabelPolicy` (the same decision squashed the pointer's way, `wrsn_entity_heuristic_label`) and
+`UniformPolicy` (`torch.rand`)."""
 import numpy as np
 
 from ._lib import ENDED_FELL_OFF, ENDED_TERMINAL, ENDED_TIME_LIMIT, POINTER_MASK_CLAIMED, POINTER_MASK_NONE
@@ -68,6 +69,22 @@ class HeuristicPolicy:
         act = env.entity_heuristic_act(ids, self.charge_scale)[1]
         if self.min_charge > 0.0:
             act[:, 2].clamp_(min=self.min_charge)
+        return act
+
+
+class HeuristicLabelPolicy:
+    """The heuristic's decision acted out the node-pointer policy's way (`VecWRSN.entity_heuristic_label`): the heuristic's node, and the
+    charging time min_charge + (1 - min_charge) * sigmoid(x) of the label's x, x clamped to [-x_clip, x_clip].  What a pointer that
+    reproduced its labels exactly would do: against `HeuristicPolicy` it shows what the clamp and the squashing alone cost.  The charging
+    time is at least min_charge + (1 - min_charge) * sigmoid(-x_clip) > 0, so this policy cannot stand still either."""
+
+    def __init__(self, charge_scale=1.0, min_charge=0.02, x_clip=4.0):
+        self.charge_scale, self.min_charge, self.x_clip = float(charge_scale), float(min_charge), float(x_clip)
+
+    def __call__(self, env, ids):
+        t = env.torch
+        stored, _, act = env.entity_heuristic_label(ids, self.charge_scale, self.min_charge, self.x_clip)
+        act[:, 2] = self.min_charge + (1.0 - self.min_charge) * t.sigmoid(stored[:, 1].double())
         return act
 
 

@@ -1424,6 +1424,8 @@ class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
         self.fused_prepare = bool(fused_prepare)
         self._joint_per_step = False                          # tests: the per-step path of `update_all` (the data-parallel one) at world == 1
         self.first_minibatch_stats = [None] * self.num_agent  # device_update: (loss, pg, v_loss, entropy, approx_kl, clipfrac) of an update's first minibatch
+        self._bc = None                                       # `pretrain`: the imitation settings while it collects, else None
+        self._critic_only = False                             # `pretrain(critic_iters=...)`: `_update_device` skips the actor's Adam call
         if self.device_update:
             torch = self.torch
             self._pa, self._pc = _lib.ENTITY_POINTER_FLOATS, _lib.ENTITY_CRITIC_FLOATS
@@ -1499,7 +1501,8 @@ class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
                     torch.distributed.all_reduce(self._grad, group=self.group)
                     self._grad /= self.world
                 st["step"] += 1
-                env.entity_adam(blk_a, ga, st["m_a"], st["v_a"], st["step"], lr, self.max_grad_norm)
+                if not self._critic_only:                             # `pretrain(critic_iters=...)`: the actor's block and moments stay as they are
+                    env.entity_adam(blk_a, ga, st["m_a"], st["v_a"], st["step"], lr, self.max_grad_norm)
                 env.entity_adam(blk_c, gc, st["m_c"], st["v_c"], st["step"], lr, self.max_grad_norm)
                 k += 1
         unpack_entity_pointer_actor(blk_a, self.actors[id]); unpack_entity_critic(blk_c, self.critics[id])
@@ -1508,7 +1511,123 @@ class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
         self.first_minibatch_stats[id] = tuple(float(x) for x in t[0, :6])
         return (float(t[-1, 1]), float(t[-1, 2]), float(t[-1, 3]), float(t[-1, 4]), float(np.mean(t[:, 5])))
 
+    def pretrain(self, iters, beta=1.0, beta_end=None, epochs=None, ent_coef=0.0, charge_scale=1.0, x_clip=4.0, critic_iters=0, max_launches=100000):
+        """Imitation pretraining from the heuristic (`wrsn_entity_heuristic_label`, `wrsn_entity_pointer_bc_update`): `iters` iterations of
+        collect-and-clone as a warm start that `train` then fine-tunes.  Needs device_update=True; works with and without mask_claimed,
+        fused_policy, joint_update and fused_prepare.
+
+        Collection goes through `step_batch` and the transition buffers.  Per launch `entity_heuristic_label` gives the expert's stored
+        pair and action for the requesting rows; a per-row uniform draw executes the expert's action with probability beta_i and the
+        learner's sampled action (`entity_pointer_act` with fused_policy, `get_action` without) otherwise, beta_i going linearly from
+        `beta` in the first iteration to `beta_end` (default: `beta`) in the last.  With beta_i == 1 the learner is never asked and no
+        draw is made.  The pair RECORDED for a row is always the expert's (DAgger; beta = 1 throughout is plain behaviour cloning on the
+        heuristic's own trajectories).  The buffers' rules stay: each charger's first transition is dropped, and pending decisions are
+        discarded at a terminal return -- so the decisions just before a network dies are never cloned.  Rewards ride along unused; the
+        stored log-probabilities are zeros.  Pending decisions from before the call are dropped at its start and its own at its end, so
+        no PPO batch ever holds a label and no cloning batch a learner's decision.  The executed expert action is the heuristic's own
+        (its c, not the squashed one): on networks where the heuristic stands still (a full node under the charger, c = 0: DESIGN.md
+        section 19) a row asks again at the same instant for ever, the other chargers of that environment never ask, and the
+        collection ends at `max_launches` with a RuntimeError.
+
+        Per iteration, once every charger holds batch_size transitions, its first batch_size stored transitions are the batch;
+        `epochs` (default n_updates_per_iteration) uniform random permutations per charger are drawn from `np.random` (not
+        `select_batch`, which is reward-driven) and ONE `entity_pointer_bc_update` steps every charger's actor block: minibatch_size,
+        lr and max_grad_norm are the trainer's, the Adam moments and step counts are the block-layout state `device_update` keeps, so
+        PPO continues from them.  No critic is touched.  The blocks are unpacked into the modules at the end (and after every iteration
+        in which the unfused learner may be asked).
+
+        critic_iters > 0: afterwards that many ordinary iterations (`roll_out`, then `_update_device` per charger -- also with
+        joint_update=True) in which the actor's Adam call is skipped, so that fine-tuning does not start from an untrained value
+        function.  The shared step count of a charger advances in them as in any update.
+
+        Returns one dict per iteration and charger: iteration, agent, beta, `first` and `last` -- the first and last row of the device
+        table (loss, -mean logp, node part, charge part, mean entropy, top-1, share of rows with a live stored node, 0), read once per
+        iteration."""
+        if not self.device_update:
+            raise ValueError("pretrain needs device_update=True")
+        torch, env = self.torch, self.env
+        if not env.auto_reset:
+            raise ValueError("%s needs VecWRSN(auto_reset=True)" % type(self).__name__)
+        iters, dev, M, bs, mb = int(iters), env.device, self.num_agent, self.batch_size, self.minibatch_size
+        beta_end = beta if beta_end is None else beta_end
+        epochs = self.n_updates_per_iteration if epochs is None else int(epochs)
+        steps = epochs * ((bs + mb - 1) // mb)
+        if self._grad_all is None:
+            self._grad_all = torch.zeros((M, self._pa + self._pc), dtype=torch.float32, device=dev)
+        blocks = self.packed_actors().to(device=dev, dtype=torch.float32).contiguous()      # [M, P]: stepped in place
+        if self._req is None:
+            self.buffers.clear(); self._req = env.reset()
+            if self._ledger is not None:
+                env.episodes_collect(self._ledger, 0.0, consume=False)
+        out = []
+        try:
+            for i in range(iters):
+                b = float(beta) if iters <= 1 else float(beta) + (float(beta_end) - float(beta)) * i / (iters - 1)
+                self._bc = dict(beta=b, charge_scale=float(charge_scale), x_clip=float(x_clip))
+                self._packed = blocks if self.fused_policy else None      # the learner acts with the blocks as the last update left them
+                self.buffers.clear(keep_pending=i > 0)                    # pending decisions from before the call are no labels: dropped
+                for _ in range(max_launches):
+                    self.step_batch()
+                    if min(self.buffers.counts()) >= bs:
+                        break
+                if min(self.buffers.stored()) < bs:
+                    raise RuntimeError("pretrain stopped after %d launches with %s transitions per charger, fewer than batch_size %d (buffer "
+                                       "capacity %d)" % (max_launches, self.buffers.stored(), bs, self.buffers.capacity))
+                idx_np = np.stack([np.stack([np.random.permutation(bs) for _ in range(epochs)]) for _ in range(M)]).astype(np.int32)
+                idx = torch.from_numpy(idx_np).to(dev)                    # the one upload of the iteration
+                groups = [dict(actor=blocks[a], grad=self._grad_all[a], rows=self.buffers.state[a, :bs], stored=self.buffers.action[a, :bs],
+                               m_a=self._adam[a]["m_a"], v_a=self._adam[a]["v_a"], step=self._adam[a]["step"]) for a in range(M)]
+                table = torch.zeros((M, steps, 8), dtype=torch.float32, device=dev)
+                env.entity_pointer_bc_update(groups, idx, mb, float(ent_coef), table, self.args["lr"], self.max_grad_norm)
+                for st in self._adam:
+                    st["step"] += steps
+                self.bc_index = idx_np                                    # the permutations of the last update (tests, logging)
+                ends = table[:, [0, steps - 1]].cpu().numpy().astype(np.float64)      # the one read of the iteration
+                for a in range(M):
+                    out.append(dict(iteration=i, agent=a, beta=b, first=tuple(float(x) for x in ends[a, 0]), last=tuple(float(x) for x in ends[a, 1])))
+                    if self.log:
+                        self.log(out[-1])
+                if not self.fused_policy and (float(beta) < 1.0 or float(beta_end) < 1.0):
+                    for a in range(M):
+                        unpack_entity_pointer_actor(blocks[a], self.actors[a])
+        finally:
+            self._bc = None
+            self._packed = None
+        for a in range(M):
+            unpack_entity_pointer_actor(blocks[a], self.actors[a])
+        self.buffers.clear()                                              # the pending labels: not a PPO roll-out's business
+        self._critic_only = True
+        try:
+            for _ in range(int(critic_iters)):
+                batches = self.roll_out(max_launches)
+                for a in range(M):
+                    self._packed = None
+                    self._update_device(a, batches[a], np.random.shuffle)
+        finally:
+            self._critic_only = False
+        return out
+
+    def _choose_bc(self, r, ids):
+        """`_choose` while `pretrain` collects: the expert's stored pair is recorded, the executed action is the expert's with probability
+        beta per row and the learner's sample otherwise."""
+        torch, env, bc = self.torch, self.env, self._bc
+        stored, _, act64 = env.entity_heuristic_label(ids, bc["charge_scale"], self.min_charge, bc["x_clip"])
+        stored, act64 = stored.clone(), act64.clone()                     # the environment writes its own tensors again at the next call
+        logp = torch.zeros((env.num_env,), dtype=torch.float32, device=env.device)
+        if bc["beta"] < 1.0:
+            mine, _, handed = self._choose_learner(r, ids)
+            own = handed if handed is not None else self.stored_action3(mine).double()
+            expert = torch.rand((env.num_env,), dtype=torch.float32, device=env.device) < bc["beta"]
+            act64 = torch.where(expert.unsqueeze(1), act64, own)
+        self._handed = act64
+        return stored, logp, act64
+
     def _choose(self, r, ids):
+        if self._bc is not None:
+            return self._choose_bc(r, ids)
+        return self._choose_learner(r, ids)
+
+    def _choose_learner(self, r, ids):
         torch, env = self.torch, self.env
         if not self.fused_policy:
             return self._choose_per_charger(ids, 2, lambda rows: EntityTransitionBuffers.pack(
@@ -1523,7 +1642,7 @@ class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
 
     def _action3(self, ids, stored):
         """The 3-vector of a launch: the device's own when it chose (fused_policy), else `stored_action3`."""
-        return self._handed if self.fused_policy else self.stored_action3(stored)
+        return self._handed if self.fused_policy or self._bc is not None else self.stored_action3(stored)
 
     def stored_action3(self, stored):
         """(u, v) of the stored node from the request's node rows -- the asking charger's own position for node -1 --, and the squashed x:

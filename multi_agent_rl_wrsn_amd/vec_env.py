@@ -277,7 +277,8 @@ class VecWRSN:
 
     def set_entity_pointer_mask(self, mode):
         """`wrsn_set_entity_pointer_mask`: the candidate mask of the node-pointer calls that follow on this object -- `entity_pointer_act`,
-        `entity_pointer_eval`, `entity_pointer_ppo_grad`, `entity_pointer_ppo_grad_multi` and `entity_pointer_ppo_update`.
+        `entity_pointer_eval`, `entity_pointer_ppo_grad`, `entity_pointer_ppo_grad_multi`, `entity_pointer_ppo_update` and the
+        behaviour-cloning calls `entity_pointer_bc_grad`, `entity_pointer_bc_grad_multi`, `entity_pointer_bc_update`.
         `_lib.POINTER_MASK_NONE` (0, the default): every alive node is a candidate.  `_lib.POINTER_MASK_CLAIMED` (1, or True): not the
         alive nodes inside the charging disc around another live charger's destination, unless that leaves none.  Launches already
         enqueued keep the mode they were enqueued under."""
@@ -341,6 +342,28 @@ class VecWRSN:
         act, act64 = self._heur
         self._h.entity_heuristic_act(a.data_ptr(), None, charge_scale, action=act.data_ptr(), action_f64=act64.data_ptr())
         return act, act64
+
+    def entity_heuristic_label(self, agent_ids, charge_scale=1.0, min_charge=0.0, x_clip=4.0):
+        """`wrsn_entity_heuristic_label` on the entity rows this object holds (`entities=True`): the heuristic's decision for the chargers
+        `agent_ids` [B] as the node-pointer policy stores a decision.  Returns (stored float32 [B,2] = ((float) node, x), action float32
+        [B,3], action_f64 float64 [B,3] -- `entity_heuristic_act`'s bytes): tensors this object owns and writes again at the next call;
+        skipped rows keep what they held."""
+        t = self.torch
+        if not self.entities:
+            raise ValueError("entity_heuristic_label needs a VecWRSN with the entity observation (entities=True)")
+        self._bind_stream()
+        a = agent_ids
+        if not (a.dtype == t.int32 and a.device == self.device and a.is_contiguous() and a.numel() == self.num_env):
+            a = a.to(device=self.device, dtype=t.int32).reshape(-1).contiguous()
+        if getattr(self, "_label", None) is None:
+            B = self.num_env
+            self._label = (t.zeros((B, 2), dtype=t.float32, device=self.device), t.zeros((B, 3), dtype=t.float32, device=self.device),
+                           t.zeros((B, 3), dtype=t.float64, device=self.device))
+        self._keep_label = a                                  # alive until the launch has run
+        stored, act, act64 = self._label
+        self._h.entity_heuristic_label(a.data_ptr(), None, charge_scale, min_charge, x_clip, stored=stored.data_ptr(), action=act.data_ptr(),
+                                       action_f64=act64.data_ptr())
+        return stored, act, act64
 
     def new_episode_log(self, episodes, quota=0):
         """An `EpisodeLog` for this batch: `episodes` finished episodes stored per environment; quota 0 = never park, else an environment
@@ -631,6 +654,55 @@ class VecWRSN:
         epochs, batch_size = int(index.shape[1]), int(index.shape[2])
         self._h.entity_pointer_ppo_update(raw, N, M, ip, batch_size, minibatch, epochs, hyper,
                                           dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, max_norm=max_norm), stats.data_ptr())
+
+    # -- behaviour cloning of node-pointer actors (wrsn_entity_pointer_bc_grad / _bc_grad_multi / _bc_update): the actor's side alone
+    def _entity_bc_groups(self, groups, moments):
+        """Raw groups from groups of tensors: `actor` (pointer block), `grad` (a contiguous float32 tensor whose first
+        wrsn_entity_pointer_floats() floats receive the gradient), `rows` [*, R], `stored` [*, 2], and with `moments` `m_a`, `v_a`, `step`.
+        No critic is named.  Returns (raw groups, N, M)."""
+        t = self.torch
+        raw, N = [], 0
+        for g in groups:
+            rp, _, _, n_node, _ = self._entity_rows(g["rows"], None)
+            if N and n_node != N:
+                raise ValueError("the groups' rows must hold the same number of nodes")
+            N = n_node
+            st = g["stored"]
+            if not (st.dtype == t.float32 and st.is_contiguous() and st.dim() == 2 and st.shape[1] == 2 and st.shape[0] == g["rows"].shape[0]):
+                raise ValueError("stored must be a contiguous float32 tensor [rows, 2]")
+            q = dict(actor=g["actor"].data_ptr(), grad_actor=g["grad"].data_ptr(), rows=rp, action=st.data_ptr(), adam_step=int(g.get("step", 0)))
+            if moments:
+                q.update(m_actor=g["m_a"].data_ptr(), v_actor=g["v_a"].data_ptr())
+            raw.append(q)
+        return raw, N, self.num_agent
+
+    def entity_pointer_bc_grad(self, actor, rows, stored, index, ent_coef, grad, stats):
+        """`wrsn_entity_pointer_bc_grad`: -mean(logp) - ent_coef * mean(H) of the stored pairs `stored` [*, 2] (indexed like the rows) under
+        the packed node-pointer actor, its gradient into the first wrsn_entity_pointer_floats() floats of `grad` and the statistics
+        (loss, -mean logp, node part, charge part, mean H, top-1, share of rows with a live stored node, 0) into stats, float32 [8]."""
+        self._bind_stream()
+        rp, ip, n, N, M = self._entity_rows(rows, index)
+        self._h.entity_pointer_bc_grad(actor.data_ptr(), rp, ip, n, N, M, stored.data_ptr(), ent_coef, grad.data_ptr(), stats.data_ptr())
+
+    def entity_pointer_bc_grad_multi(self, groups, index, ent_coef, stats):
+        """`wrsn_entity_pointer_bc_grad_multi`: `entity_pointer_bc_grad` for every group (see `_entity_bc_groups`).  index: int32 [G, n] or
+        None: all rows of every group; stats: float32 [G, 8]."""
+        self._bind_stream()
+        raw, N, M = self._entity_bc_groups(groups, False)
+        n = groups[0]["rows"].shape[0] if index is None else index.shape[1]
+        ip = 0 if index is None else self._entity_index(index, (len(groups), n))
+        self._h.entity_pointer_bc_grad_multi(raw, n, N, M, ip, ent_coef, stats.data_ptr())
+
+    def entity_pointer_bc_update(self, groups, index, minibatch, ent_coef, stats, lr, max_norm, beta1=0.9, beta2=0.999, eps=1e-8):
+        """`wrsn_entity_pointer_bc_update`: every epoch and minibatch of a behaviour-cloning update for every group behind one call, Adam on
+        the actor blocks alone (group g from `step` + 1 on).  index: int32 [G, epochs, batch_size], the shuffles; stats: float32
+        [G, epochs * ceil(batch_size / minibatch), 8].  Only enqueues; the caller advances its step counts by stats.shape[1]."""
+        self._bind_stream()
+        raw, N, M = self._entity_bc_groups(groups, True)
+        ip = self._entity_index(index, (len(groups),) + tuple(index.shape[1:3]))
+        epochs, batch_size = int(index.shape[1]), int(index.shape[2])
+        self._h.entity_pointer_bc_update(raw, N, M, ip, batch_size, minibatch, epochs, ent_coef,
+                                         dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, max_norm=max_norm), stats.data_ptr())
 
     def entity_prepare(self, groups, index, gamma, gae_lambda):
         """`wrsn_entity_prepare`: the PPO batch of every group -- the critic's values, `PPOLearner.cal_rt_adv` (gae=True) and the gathers --

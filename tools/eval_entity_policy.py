@@ -12,6 +12,12 @@ profiles/entity_eval.json.
 (`masked_...`; `wrsn_set_entity_pointer_mask`, BatchedEntityPointerIPPO(mask_claimed=True)) --, each trainer on a training batch of its
 own from the same seeds and with the same flags (`--device-update --joint-update --fused-prepare` choose the update; acting is always
 fused), and writes profiles/entity_pointer_mask_eval.json.
+`--policy pointer --device-update --pretrain N [--beta B] [--beta-end B] [--critic-iters K]` adds, in the same run and from the same seeds,
+the heuristic acted out as its pointer label (`heuristic_as_label`, HeuristicLabelPolicy) and a second trainer on a training batch of its
+own: the pointer after N iterations of `BatchedEntityPointerIPPO.pretrain` alone (`bc_mode`, `bc_sampled`) and after `--iters` PPO
+iterations on top (`bc_ppo_mode`, `bc_ppo_sampled`), next to the PPO-only rows (`trained_...`); with `--mask-claimed` all of them once
+more under the mask (`masked_...`).  The cloning statistics of every iteration are kept as a compact table (`pretrain_table`): loss and
+top-1 of the device table's first and last row per charger, the loss parts and the entropy of its last row.  Writes profiles/entity_pointer_bc_eval.json.
 
 --bench: the evaluation loop per launch at `--envs` (4096) x 200 nodes x 3 chargers with the heuristic policy, in two forms: with
 wrsn_episodes_collect, and with the same bookkeeping in elementwise torch on calls that existed before it (`step`, `reset(mask)`).
@@ -101,6 +107,25 @@ def bench(args):
     return out
 
 
+def pretrain_table(stats, names, M):
+    """The rows `pretrain` returns as a compact table: per statistic and charger ONE string of the iterations' values ("%.3g", space
+    separated, iteration 0 first), for the first and the last row of every iteration's device table; `beta` likewise, one value per
+    iteration."""
+    fmt = lambda xs: " ".join("%.3g" % x for x in xs)
+    rows = sorted(stats, key=lambda r: (r["agent"], r["iteration"]))
+    tab = {"layout": "per statistic: first / last row of each iteration's table (first: loss and top1 only), one string per charger, iterations in order",
+           "beta": fmt(r["beta"] for r in rows if r["agent"] == 0)}
+    for j, name in enumerate(names):
+        if name == "nll":                                      # loss + ent_coef * entropy: not kept twice
+            continue
+        if name == "kv_share":                                 # 1 wherever the labels are the heuristic's on live networks: its minimum is kept
+            tab["kv_share_min"] = [min(min(r["first"][j], r["last"][j]) for r in rows if r["agent"] == a) for a in range(M)]
+            continue
+        rows_kept = ("first", "last") if name in ("loss", "top1") else ("last",)      # the parts and the entropy: after the iteration's update only
+        tab[name] = {w: [fmt(r[w][j] for r in rows if r["agent"] == a) for a in range(M)] for w in rows_kept}
+    return tab
+
+
 def device_envs(args, N=200, M=3):
     """(training batch, held-out evaluation batch) on the device."""
     from multi_agent_rl_wrsn_amd import VecWRSN, synth_scenario
@@ -113,8 +138,8 @@ def compare(args, make_envs=device_envs):
     """The policy comparison; `make_envs(args)` gives the two batches (the tests pass emulated ones)."""
     import numpy as np
     import torch
-    from multi_agent_rl_wrsn_amd import (BatchedEntityIPPO, BatchedEntityPointerIPPO, EntityPolicy, HeuristicPolicy, PointerPolicy, UniformPolicy,
-                                         evaluate_policy)
+    from multi_agent_rl_wrsn_amd import (BatchedEntityIPPO, BatchedEntityPointerIPPO, EntityPolicy, HeuristicLabelPolicy, HeuristicPolicy, PointerPolicy,
+                                         UniformPolicy, evaluate_policy)
     from multi_agent_rl_wrsn_amd.evaluate import LaunchCapReached
     torch.manual_seed(0); np.random.seed(0)
     train_env, eval_env = make_envs(args)
@@ -157,6 +182,8 @@ def compare(args, make_envs=device_envs):
     run("uniform", UniformPolicy(gen()))
     run("heuristic", HeuristicPolicy())
     run("heuristic_min_charge", HeuristicPolicy(min_charge=args.min_charge))
+    if pointer and args.pretrain > 0:
+        run("heuristic_as_label", HeuristicLabelPolicy(1.0, args.min_charge, args.x_clip))
     def train_and_run(algo, train_env, Policy, prefix=""):
         run(prefix + "untrained_mode", Policy(True))
         run(prefix + "untrained_sampled", Policy(False, gen()))
@@ -185,13 +212,38 @@ def compare(args, make_envs=device_envs):
                 "seconds": time.perf_counter() - t0,
                 "last_rows": [{k: r[k] for k in ("iteration", "agent", "mean_reward", "avg_ep_lifetime", "avg_ep_lens", "episodes")} for r in rows[-M:]]}
 
+    def pretrain_and_run(mask, prefix):
+        """A trainer of its own from the same seeds: cloning alone, then PPO on top."""
+        env_b, spare = make_envs(args)
+        spare.close() if hasattr(spare, "close") else None
+        algo_b = pointer_algo(env_b, mask)
+        algo_b._check_status = False                          # as `train` below: rows with an error status are not fatal here
+        Pol = lambda det, g=None: PointerPolicy(algo_b.packed_actors(), det, g, args.min_charge, mask)
+        t0 = time.perf_counter()
+        stats = algo_b.pretrain(args.pretrain, beta=args.beta, beta_end=args.beta_end, critic_iters=args.critic_iters, x_clip=args.x_clip,
+                                max_launches=25 * args.max_launches)
+        names = ("loss", "nll", "node_part", "charge_part", "entropy", "top1", "kv_share")
+        record = {"iterations": args.pretrain, "beta": args.beta, "beta_end": args.beta if args.beta_end is None else args.beta_end,
+                  "critic_iters": args.critic_iters, "x_clip": args.x_clip, "seconds": time.perf_counter() - t0,
+                  "per_iteration": pretrain_table(stats, names, M)}
+        run(prefix + "bc_mode", Pol(True))
+        run(prefix + "bc_sampled", Pol(False, gen()))
+        record["fine_tuning"] = train(algo_b, env_b)
+        run(prefix + "bc_ppo_mode", Pol(True))
+        run(prefix + "bc_ppo_sampled", Pol(False, gen()))
+        return record
+
     out["training"] = train_and_run(algo, train_env, Policy)
+    if pointer and args.pretrain > 0:
+        out["pretraining"] = pretrain_and_run(False, "")
     if pointer and args.mask_claimed:
         train_m, spare = make_envs(args)                      # a training batch of its own, from the same seeds
         spare.close() if hasattr(spare, "close") else None
         algo_m = pointer_algo(train_m, True)
         out["masked_training"] = train_and_run(algo_m, train_m, lambda det, g=None: PointerPolicy(algo_m.packed_actors(), det, g, args.min_charge, True),
                                                "masked_")
+        if args.pretrain > 0:
+            out["masked_pretraining"] = pretrain_and_run(True, "masked_")
     return out
 
 
@@ -210,6 +262,11 @@ def main(argv=None):
     ap.add_argument("--mask-claimed", action="store_true", help="pointer: every pointer row also with the candidate mask (masked_...)")
     for k in ("device-update", "joint-update", "fused-prepare"):
         ap.add_argument("--" + k, action="store_true", help="pointer: BatchedEntityPointerIPPO(%s=True)" % k.replace("-", "_"))
+    ap.add_argument("--pretrain", type=int, default=0, help="pointer, with --device-update: iterations of imitation pretraining from the heuristic")
+    ap.add_argument("--beta", type=float, default=1.0, help="pretraining: the share of decisions the expert executes in the first iteration")
+    ap.add_argument("--beta-end", type=float, default=None, help="pretraining: the share in the last iteration (default: --beta)")
+    ap.add_argument("--critic-iters", type=int, default=0, help="pretraining: critic-only iterations after it")
+    ap.add_argument("--x-clip", type=float, default=4.0, help="pretraining: the clamp of the label's charge variable")
     ap.add_argument("--fused-policy", action="store_true", help="pointer: accepted for symmetry with bench_ippo.py; the tool always acts fused")
     ap.add_argument("--bench", action="store_true")
     ap.add_argument("--windows", type=int, default=3)
@@ -217,8 +274,11 @@ def main(argv=None):
     ap.add_argument("--only", default=None, choices=[None, "fused", "torch"])
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
+    if args.pretrain > 0 and not (args.policy == "pointer" and args.device_update):
+        ap.error("--pretrain needs --policy pointer --device-update")
     out = bench(args) if args.bench else compare(args)
     path = args.out or os.path.join(ROOT, "profiles", "episodes_bench.json" if args.bench else
+                                    "entity_pointer_bc_eval.json" if args.policy == "pointer" and args.pretrain > 0 else
                                     "entity_pointer_mask_eval.json" if args.policy == "pointer" and args.mask_claimed else
                                     "entity_pointer_eval.json" if args.policy == "pointer" else "entity_eval.json")
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
