@@ -524,6 +524,73 @@ typedef struct wrsn_episode_log {      /* DEVICE, caller-owned */
 int wrsn_episodes_collect(wrsn_t *h, const wrsn_episode_log *log, const wrsn_step_out *out, double time_limit,
                           int32_t *next_agent_id, uint8_t *restart, int32_t consume);
 
+/* ONE-STEP LOOKAHEAD OVER THE HEURISTIC: for every request try the heuristic's K best nodes, each on a clone of the environment that is
+ * rolled forward under the heuristic for `horizon` simulated seconds, and keep the best.  Two handles: the REAL one (batch B), which is
+ * only read, and a SIMULATION handle of K * B environments of the same geometry (auto_reset 0); slot r = k * B + b of every k-major
+ * array below is candidate k of real row b, and environment r of the simulation handle.  Per request:
+ *     wrsn_lookahead_candidates (real handle)  ->  wrsn_clone_envs_from (src b -> dst k * B + b)  ->  wrsn_step(sim, sim_agent_id, sim_action)
+ *     then repeat { wrsn_lookahead_collect (sim) ; wrsn_step(sim, next_agent_id, the heuristic's action for next_agent_id) }
+ *     then wrsn_lookahead_collect(close_all = 1) ; wrsn_lookahead_pick (real handle).
+ * All state is caller-owned DEVICE memory; all four calls are asynchronous on the handle's stream and read nothing back.
+ *
+ * wrsn_lookahead_candidates: the heuristic's RANKING, not only its first pick.  For row b with a = agent_id[b] in [0, n_mc), with self,
+ * alive, claimed and score as wrsn_entity_heuristic_act states them, float32, every operation rounded on its own: the order is the alive
+ * unclaimed nodes by score descending, then index ascending, followed by the alive claimed nodes in the same order; candidate k is its
+ * k-th entry (K passes over the row, each leaving out the nodes already taken).  Candidate 0 is the pick of wrsn_entity_heuristic_act.
+ * Fewer than K alive nodes: the remaining slots are INVALID.  No alive node: candidate 0 is the heuristic's stand-still action and is
+ * valid, the others are invalid.  For slot r = k * B + b:
+ *     node[r]         the node; -1 for an invalid slot and for the stand-still action
+ *     sim_agent_id[r] a when valid, -2 when not (wrsn_step of the simulation handle then leaves the slot alone)
+ *     sim_action[r]   valid slots only: (u_n, v_n, max((double) c, min_charge)), c the heuristic's own charging time for that node -- the
+ *                     bytes of wrsn_entity_heuristic_act's action_f64 but for the clamp, which is taken in float64 as
+ *                     HeuristicPolicy(min_charge) takes it; ((double) mc[self][0], (double) mc[self][1], min_charge) standing still
+ *     stored[r]       valid slots only: the pair wrsn_entity_heuristic_label forms for that node with (float) min_charge and x_clip,
+ *                     ((float) n, x); (-1, -x_clip) standing still
+ * and the lookahead state of the slot: t0[r] = now[b], t_end[r] = now[b] + horizon, last_now[r] = now[b], ret[r] = 0, died[r] = 0,
+ * done[r] = !valid (survived[r] keeps its bytes).  `now` is the real handle's out->now.  Rows with agent_id outside [0, n_mc) are
+ * skipped: every output byte and every state element of their K slots is kept.  A row's outputs depend on its own entity rows only;
+ * two calls on equal inputs give equal bytes.  K = state->K; state->B must be the handle's batch.  Needs no scenario.
+ * WRSN_ERR_ARG, with every buffer untouched: a NULL pointer (ent NULL: the registered buffers, and none registered); K outside
+ * [1, WRSN_LOOKAHEAD_MAX_K]; state->B not the batch; an entity buffer not 16-byte aligned, another array not aligned to its element;
+ * horizon not finite or <= 0; min_charge not finite or outside [0, 1); x_clip not finite or <= 0.
+ *
+ * wrsn_lookahead_collect: on the SIMULATION handle after every wrsn_step of it, keyed on what that launch did with the slot exactly as
+ * wrsn_episodes_collect is.  Per slot r:
+ *   done[r] != 0               next_agent_id[r] = -2, nothing else;
+ *   step in flight (status 4)  next_agent_id[r] = -1;
+ *   fresh request of charger a ret[r] += out->reward[r] (float64, one add), last_now[r] = out->now[r]; the slot CLOSES when
+ *                              out->status[r] == 1 or out->now[r] >= t_end[r]; otherwise next_agent_id[r] = a;
+ *   terminal return            died[r] = 1, last_now[r] = out->now[r], and the slot closes; no reward is added, as in the ledger;
+ *   untouched, or reset        nothing is written, next_agent_id[r] keeps its bytes.
+ * Closing: survived[r] = min(last_now[r], t_end[r]) - t0[r], done[r] = 1, next_agent_id[r] = -2.  close_all != 0 (the call after the last
+ * launch): every slot still open after the above is closed the same way, with the last_now it has.  The row state is always consumed
+ * (a second call after the same launch finds nothing).  One thread per slot, no atomics, nothing written outside the stated extents.
+ * WRSN_ERR_ARG: a NULL pointer; a bad state; K * B of the state is not the handle's batch; out->agent_id, reward, now or status NULL;
+ * next_agent_id == out->agent_id.
+ *
+ * wrsn_lookahead_pick: on the REAL handle.  For each row b with agent_id[b] in [0, n_mc): over the slots k with sim_agent_id[r] >= 0 and
+ * done[r] != 0 the lexicographic best by (1) survived descending, (2) ret descending, (3) k ascending; a NaN never beats a number; when
+ * no slot qualifies k = 0.  No weight joins the two keys: slots that outlive the horizon have survived = t_end - t0 from the same two
+ * doubles for every k of a row, so they tie exactly and ret decides.  Writes choice[b] = k, action_f64[b] = sim_action[r] and action[b]
+ * (the same, narrowed) when given, stored[b] = cand_stored[r] when given (ready for the [*, 2] pair of the pointer's transition
+ * buffers).  Skipped rows keep every byte.
+ * WRSN_ERR_ARG: h, agent_id, sim_agent_id, sim_action or choice NULL; stored without cand_stored; a bad state; state->B not the batch. */
+#define WRSN_LOOKAHEAD_MAX_K 8
+typedef struct wrsn_lookahead_state {   /* DEVICE, caller-owned; r = k * B + b, B = the REAL handle's batch */
+    int32_t K, B;
+    double *t0, *t_end, *last_now, *ret, *survived;   /* [K*B] */
+    uint8_t *done, *died;                              /* [K*B] */
+} wrsn_lookahead_state;
+int wrsn_lookahead_candidates(wrsn_t *h, const int32_t *agent_id, const wrsn_entity_out *ent, const double *now /* [B] */,
+                              const wrsn_lookahead_state *state, double horizon, float charge_scale, double min_charge, float x_clip,
+                              int32_t *node /* [K,B] */, int32_t *sim_agent_id /* [K,B] */, double *sim_action /* [K,B,3] */,
+                              float *stored /* [K,B,2] */);
+int wrsn_lookahead_collect(wrsn_t *sim_h, const wrsn_lookahead_state *state, const wrsn_step_out *out, int32_t *next_agent_id /* [K*B] */,
+                           int32_t close_all);
+int wrsn_lookahead_pick(wrsn_t *h, const int32_t *agent_id, const wrsn_lookahead_state *state, const int32_t *sim_agent_id,
+                        const double *sim_action, const float *cand_stored /* [K,B,2] or NULL */, int32_t *choice /* [B] */,
+                        double *action_f64 /* [B,3] or NULL */, float *action /* [B,3] or NULL */, float *stored /* [B,2] or NULL */);
+
 /* THE PPO UPDATE OF THE ENTITY POLICY.  One minibatch step of PPOLearner.update (ippo.py) for the set networks of build_entity_networks:
  * forward, PPO loss, backward, gradient clipping and Adam as a handful of launches on the handle's stream, nothing read back on the host.
  * None of the three calls needs a scenario: the handle supplies the stream and a scratch area that grows on demand and is freed by
@@ -842,6 +909,23 @@ int wrsn_load_envs(wrsn_t *h, const int32_t *env, int32_t n, const void *src, co
 /* dst[i] becomes a copy of src[i] (device to device), and row src[i] of out is copied to row dst[i] (obs rendered as for a load;
  * needs out->agent_id then).  Asynchronous on the handle's stream. */
 int wrsn_clone_envs(wrsn_t *h, const int32_t *src, const int32_t *dst, int32_t n, const wrsn_step_out *out);
+
+/* The clone ACROSS TWO HANDLES: environment dst[i] of dst_h becomes a copy of environment src[i] of src_h, and row src[i] of src_req (the
+ * source's request rows: agent_id, reward, terminal, now and status non-NULL, obs ignored) is copied to row dst[i] of dst_out (NULL fields
+ * are skipped).  Everything else is the contract of wrsn_clone_envs: what is carried and what is not (the destination keeps its counters
+ * since create, map 1 reuse starts afresh, a following collect finds nothing for the row), and the cloned rows are rendered -- dst_out->obs
+ * when set, the destination's registered entity rows -- which needs dst_out->agent_id.  The pool record of a destination (WRSN_PEEK_POOL)
+ * becomes -1, as after a load: a pool belongs to its handle.  `src` may repeat (fan-out: one source, many destinations); `dst` entries
+ * are distinct; both are HOST int32 [n].  The source handle is only read: no byte of its environments or request rows changes.
+ * Asynchronous on the handles' common stream, no host read; when the source's connected-node bound or stochastic kernels ask for a new
+ * launch configuration of the destination (never between handles created on the same scenarios) that one call synchronises first.
+ * Mechanism: the distinct sources are packed into records in an area the destination owns and unpacked from there, so a call moves
+ * 2 * (u + n) record sizes for u distinct sources and n pairs.
+ * WRSN_ERR_ARG with a message, nothing changed: a NULL pointer or n < 1; the two handles are one; different devices; different streams;
+ * NP, TP, ECAP, CCAP or M differ; the source handle's n_node or n_target is larger than the destination's; one handle keeps generators
+ * and the other does not; an index out of range; a source that holds no scenario; a destination twice. */
+int wrsn_clone_envs_from(wrsn_t *dst_h, wrsn_t *src_h, const int32_t *src, const int32_t *dst, int32_t n,
+                         const wrsn_step_out *src_req, const wrsn_step_out *dst_out);
 
 /* SCENARIO POOLS: restart finished episodes in another network, on the device.  A record saved right after wrsn_reset is a prepared
  * scenario (topology, constants, post-warm-up snapshot, reset request); a pool is P of them.

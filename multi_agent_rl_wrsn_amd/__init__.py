@@ -7,8 +7,8 @@ from .scenario import (DEFAULT_MC_SPEC, DEFAULT_NODE_SPEC, Scenario, load_mc_yam
                        scenario_from_golden, synth_batch, synth_scenario)
 from .sharding import RolloutStats, init_distributed, launch_ranks, shard_range  # noqa: F401
 from ._lib import ENT_ENV, ENT_ENV_F, ENT_MC, ENT_MC_F, ENT_NODE, ENT_NODE_F, pool_draw  # noqa: F401
-from .vec_env import EpisodeLog, VecWRSN, build_scenario_pool  # noqa: F401
-from .evaluate import EntityPolicy, HeuristicLabelPolicy, HeuristicPolicy, PointerPolicy, UniformPolicy, evaluate_policy  # noqa: F401
+from .vec_env import EpisodeLog, Lookahead, VecWRSN, build_scenario_pool  # noqa: F401
+from .evaluate import EntityPolicy, HeuristicLabelPolicy, HeuristicPolicy, LookaheadPolicy, PointerPolicy, UniformPolicy, evaluate_policy  # noqa: F401
 from .wrsn import WRSN  # noqa: F401
 from .ippo import (BatchedEntityIPPO, BatchedEntityPointerIPPO, BatchedIPPO, EntityPointerPPOLearner, EntityPPOLearner, EntityTransitionBuffers, PPOLearner, TransitionBuffers,  # noqa: F401
                    build_entity_networks, build_networks, entity_row_elems, pack_entity_actor, pack_entity_critic, select_batch, unpack_entity_actor, unpack_entity_critic,
@@ -20,4 +20,4 @@ __all__ = ["Scenario", "load_scenario_yaml", "load_mc_yaml", "synth_scenario", "
            "EntityTransitionBuffers", "EntityPPOLearner", "BatchedEntityIPPO", "build_entity_networks", "entity_row_elems", "pack_entity_actor", "pack_entity_critic", "unpack_entity_actor",
            "unpack_entity_critic", "EpisodeLog", "evaluate_policy", "EntityPolicy", "HeuristicPolicy", "HeuristicLabelPolicy", "UniformPolicy",
            "build_entity_pointer_networks", "pack_entity_pointer_actor", "unpack_entity_pointer_actor", "EntityPointerPPOLearner", "BatchedEntityPointerIPPO",
-           "PointerPolicy"]
+           "PointerPolicy", "Lookahead", "LookaheadPolicy"]

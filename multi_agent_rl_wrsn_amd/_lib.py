@@ -45,7 +45,7 @@ EXPORTS = ("wrsn_create", "wrsn_destroy", "wrsn_set_stream", "wrsn_set_scenario"
            "wrsn_set_step_budget", "wrsn_set_step_deadline", "wrsn_density_action", "wrsn_rollout_table", "wrsn_rollout_record", "wrsn_rollout_collect", "wrsn_rollout_record_entities", "wrsn_rollout_collect_entities", "wrsn_entity_actor_floats", "wrsn_entity_act", "wrsn_entity_pointer_floats", "wrsn_entity_pointer_eval", "wrsn_entity_pointer_ppo_grad", "wrsn_entity_pointer_act", "wrsn_entity_heuristic_act", "wrsn_entity_heuristic_label", "wrsn_episodes_collect", "wrsn_entity_critic_floats", "wrsn_entity_eval", "wrsn_entity_ppo_grad", "wrsn_entity_adam", "wrsn_entity_ppo_grad_multi", "wrsn_entity_adam_multi", "wrsn_entity_ppo_update", "wrsn_entity_pointer_ppo_grad_multi", "wrsn_entity_pointer_adam_multi",
            "wrsn_entity_pointer_ppo_update", "wrsn_entity_pointer_bc_grad", "wrsn_entity_pointer_bc_grad_multi", "wrsn_entity_pointer_bc_update",
            "wrsn_set_entity_pointer_mask", "wrsn_entity_prepare", "wrsn_render", "wrsn_set_entity_out", "wrsn_entities", "wrsn_set_obs_reuse", "wrsn_set_obs_format", "wrsn_set_timing", "wrsn_kernel_times", "wrsn_peek", "wrsn_sync", "wrsn_counters", "wrsn_env_record_bytes", "wrsn_save_envs", "wrsn_load_envs",
-           "wrsn_clone_envs", "wrsn_pool_set", "wrsn_pool_reset", "wrsn_synth_network",
+           "wrsn_clone_envs", "wrsn_clone_envs_from", "wrsn_lookahead_candidates", "wrsn_lookahead_collect", "wrsn_lookahead_pick", "wrsn_pool_set", "wrsn_pool_reset", "wrsn_synth_network",
            "wrsn_last_error",
            "wrsn_version")
 
@@ -90,6 +90,15 @@ ENDED_TERMINAL, ENDED_TIME_LIMIT, ENDED_FELL_OFF = 1, 2, 3     # wrsn_episode_lo
 class WrsnEpisodeLog(C.Structure):
     """wrsn_episode_log: the episode ledger of wrsn_episodes_collect (device addresses)."""
     _fields_ = [("episodes", C.c_int32), ("quota", C.c_int32)] + [(k, C.c_void_p) for k in EPISODE_LOG_ARRAYS]
+
+
+LOOKAHEAD_MAX_K = 8          # WRSN_LOOKAHEAD_MAX_K
+LOOKAHEAD_F64, LOOKAHEAD_U8 = ("t0", "t_end", "last_now", "ret", "survived"), ("done", "died")
+
+
+class WrsnLookaheadState(C.Structure):
+    """wrsn_lookahead_state: the per-slot state of the lookahead calls (device addresses), slot r = k * B + b."""
+    _fields_ = [("K", C.c_int32), ("B", C.c_int32)] + [(k, C.c_void_p) for k in LOOKAHEAD_F64 + LOOKAHEAD_U8]
 
 
 class WrsnEntityRows(C.Structure):
@@ -250,6 +259,15 @@ def bind(lib):
     lib.wrsn_load_envs.restype = C.c_int
     lib.wrsn_clone_envs.argtypes = [vp, vp, vp, C.c_int32, C.POINTER(WrsnStepOut)]
     lib.wrsn_clone_envs.restype = C.c_int
+    lib.wrsn_clone_envs_from.argtypes = [vp, vp, vp, vp, C.c_int32, C.POINTER(WrsnStepOut), C.POINTER(WrsnStepOut)]
+    lib.wrsn_clone_envs_from.restype = C.c_int
+    lib.wrsn_lookahead_candidates.argtypes = [vp, vp, C.POINTER(WrsnEntityOut), vp, C.POINTER(WrsnLookaheadState), C.c_double, C.c_float, C.c_double,
+                                              C.c_float, vp, vp, vp, vp]
+    lib.wrsn_lookahead_candidates.restype = C.c_int
+    lib.wrsn_lookahead_collect.argtypes = [vp, C.POINTER(WrsnLookaheadState), C.POINTER(WrsnStepOut), vp, C.c_int32]
+    lib.wrsn_lookahead_collect.restype = C.c_int
+    lib.wrsn_lookahead_pick.argtypes = [vp, vp, C.POINTER(WrsnLookaheadState), vp, vp, vp, vp, vp, vp, vp]
+    lib.wrsn_lookahead_pick.restype = C.c_int
     lib.wrsn_pool_set.argtypes = [vp, vp, C.c_int32, C.c_uint64]
     lib.wrsn_pool_set.restype = C.c_int
     lib.wrsn_pool_reset.argtypes = [vp, vp, vp, vp, C.POINTER(WrsnStepOut)]
@@ -718,6 +736,38 @@ class RawHandle:
             raise ValueError("src and dst differ in length (%d, %d)" % (len(s), len(d)))
         o = self._out(**out_ptrs)
         check(self.lib, self.lib.wrsn_clone_envs(self._h, s.ctypes.data, d.ctypes.data, len(s), C.byref(o)))
+
+    def clone_envs_from(self, src_handle, src_idx, dst_idx, src_req, **out_ptrs):
+        """wrsn_clone_envs_from: environment dst_idx[i] of THIS handle becomes a copy of environment src_idx[i] of `src_handle` (a RawHandle
+        of the same library; only read); src_req: dict of the source's request-row addresses, out_ptrs: this handle's rows."""
+        s, d = self._idx(src_idx), self._idx(dst_idx)
+        if len(s) != len(d):
+            raise ValueError("src and dst differ in length (%d, %d)" % (len(s), len(d)))
+        q, o = (None if src_req is None else self._out(**src_req)), self._out(**out_ptrs)
+        check(self.lib, self.lib.wrsn_clone_envs_from(self._h, None if src_handle is None else src_handle._h, s.ctypes.data, d.ctypes.data, len(s),
+                                                      None if q is None else C.byref(q), C.byref(o)))
+
+    # -- one-step lookahead over the heuristic (wrsn_lookahead_*); `state` is a WrsnLookaheadState (None: NULL), arrays are device addresses
+    def lookahead_candidates(self, agent_ptr, now_ptr, state, horizon, charge_scale=1.0, min_charge=0.0, x_clip=4.0, ent_ptrs=None, node=0,
+                             sim_agent_id=0, sim_action=0, stored=0):
+        """wrsn_lookahead_candidates: the heuristic's state.K best nodes of every row into the k-major node / sim_agent_id [K,B] int32,
+        sim_action [K,B,3] float64 and stored [K,B,2] float32, and the slots of `state` initialised for a roll-forward of `horizon` s."""
+        p = lambda x: C.c_void_p(x or None)
+        check(self.lib, self.lib.wrsn_lookahead_candidates(self._h, p(agent_ptr), self._ent(ent_ptrs), p(now_ptr), None if state is None else C.byref(state),
+                                                           float(horizon), float(charge_scale), float(min_charge), float(x_clip), p(node),
+                                                           p(sim_agent_id), p(sim_action), p(stored)))
+
+    def lookahead_collect(self, state, next_agent_ptr, close_all=False, **out_ptrs):
+        """wrsn_lookahead_collect on the simulation handle: books the requests of its last step into `state`, ids of the next step."""
+        o = self._out(**out_ptrs)
+        check(self.lib, self.lib.wrsn_lookahead_collect(self._h, None if state is None else C.byref(state), C.byref(o), C.c_void_p(next_agent_ptr or None),
+                                                        1 if close_all else 0))
+
+    def lookahead_pick(self, agent_ptr, state, sim_agent_id, sim_action, cand_stored=0, choice=0, action_f64=0, action=0, stored=0):
+        """wrsn_lookahead_pick: the best finished slot of every row by (survived, ret, k) -> choice [B], its action and stored pair."""
+        p = lambda x: C.c_void_p(x or None)
+        check(self.lib, self.lib.wrsn_lookahead_pick(self._h, p(agent_ptr), None if state is None else C.byref(state), p(sim_agent_id), p(sim_action),
+                                                     p(cand_stored), p(choice), p(action_f64), p(action), p(stored)))
 
     # -- scenario pools (wrsn_pool_set / wrsn_pool_reset); every array argument is a device address
     def pool_set(self, records_ptr, n_records, seed=0):

@@ -118,6 +118,9 @@ struct wrsn_handle {
     // wrsn_entity_eval / wrsn_entity_ppo_grad / wrsn_entity_adam: the scratch area (grown on demand, the old one kept until wrsn_destroy: launches
     // in flight may still use it) and the gradient norm of the Adam call
     float* et_scratch = nullptr; size_t et_cap = 0; float* et_norm = nullptr;
+    // wrsn_clone_envs_from, on the DESTINATION handle: the records of the distinct sources of a call (grown on demand, the old area kept
+    // until wrsn_destroy: launches in flight may still read it)
+    uint8_t* xfer = nullptr; size_t xfer_cap = 0;
 };
 
 namespace {
@@ -1938,6 +1941,160 @@ int wrsn_clone_envs(wrsn_t* h, const int32_t* src, const int32_t* dst, int32_t n
     if ((rc = launch_rec_copy(h, WRSN_REC_CLONE, h->d_idx, h->d_idx + n, nullptr, n))) return rc;
     if ((rc = launch_rec_rows(h, nullptr, h->d_idx, h->d_idx + n, n, out))) return rc;
     for (int i = 0; i < n; ++i) h->filled[dst[i]] = 1;
+    return WRSN_OK;
+}
+
+// Across two handles: the distinct sources are packed into records in an area the destination owns (wrsn_rec_header_kernel and the pack
+// direction of the copy loop, on the SOURCE's segment table), then unpacked into the destinations by wrsn_pool_copy_kernel on the
+// destination's table, whose record index is the fan-out; wrsn_rec_rows_kernel takes the request rows from the records' headers.  No new
+// copy kernel, no host read; every check comes before the first launch.
+int wrsn_clone_envs_from(wrsn_t* dst_h, wrsn_t* src_h, const int32_t* src, const int32_t* dst, int32_t n, const wrsn_step_out* src_req,
+                         const wrsn_step_out* dst_out) {
+    if (!dst_h || !src_h || !src || !dst || !src_req || !dst_out || n < 1) return fail(WRSN_ERR_ARG, "wrsn_clone_envs_from: null argument or n < 1");
+    if (dst_h == src_h) return fail(WRSN_ERR_ARG, "wrsn_clone_envs_from: source and destination are the same handle (wrsn_clone_envs clones inside one)");
+    if (!src_req->agent_id || !src_req->reward || !src_req->terminal || !src_req->now || !src_req->status)
+        return fail(WRSN_ERR_ARG, "wrsn_clone_envs_from needs the source's request rows: agent_id, reward, terminal, now and status");
+    if ((dst_out->obs || dst_h->ent.node) && !dst_out->agent_id) return fail(WRSN_ERR_ARG, "rendering the cloned rows needs dst_out->agent_id");
+    if (src_h->cfg.device != dst_h->cfg.device) return fail(WRSN_ERR_ARG, "wrsn_clone_envs_from: the handles are on different devices");
+    if (src_h->stream != dst_h->stream) return fail(WRSN_ERR_ARG, "wrsn_clone_envs_from: the handles run on different streams (wrsn_set_stream)");
+    {
+        const WrsnDev &s = src_h->dev, &d = dst_h->dev;
+        auto bad = [&](const char* field, long long got, long long want) {
+            return fail(WRSN_ERR_ARG, std::string("wrsn_clone_envs_from: ") + field + " of the source is " + std::to_string(got) + ", the destination needs " + std::to_string(want));
+        };
+        if (s.NP != d.NP) return bad("NP", s.NP, d.NP);
+        if (s.TP != d.TP) return bad("TP", s.TP, d.TP);
+        if (s.ECAP != d.ECAP) return bad("ECAP", s.ECAP, d.ECAP);
+        if (s.CCAP != d.CCAP) return bad("CCAP", s.CCAP, d.CCAP);
+        if (s.M != d.M) return bad("M", s.M, d.M);
+        if (s.N > d.N) return bad("n_node", s.N, d.N);
+        if (s.T > d.T) return bad("n_target", s.T, d.T);
+    }
+    if ((src_h->sd.mt_live != nullptr) != (dst_h->sd.mt_live != nullptr))
+        return fail(WRSN_ERR_ARG, "wrsn_clone_envs_from: one handle keeps generators and the other does not");
+    if (src_h->rec_bytes != dst_h->rec_bytes || src_h->nseg != dst_h->nseg) return fail(WRSN_ERR_ARG, "wrsn_clone_envs_from: the record layouts of the handles differ");
+    int rc = check_envs(src_h, src, n, false, true, "src"); if (rc) return rc;
+    if ((rc = check_envs(dst_h, dst, n, true, false, "dst"))) return rc;
+    // ---- everything fits.  Host index arrays, staged in the destination's area: dst [n], record of pair i [n], distinct sources [u], n
+    std::vector<int32_t> rec_of((size_t)src_h->dev.B, -1), idx((size_t)2 * n);
+    std::vector<int32_t> uniq;
+    for (int i = 0; i < n; ++i) {
+        if (rec_of[src[i]] < 0) { rec_of[src[i]] = (int32_t)uniq.size(); uniq.push_back(src[i]); }
+        idx[i] = dst[i]; idx[(size_t)n + i] = rec_of[src[i]];
+    }
+    const int u = (int)uniq.size();
+    idx.insert(idx.end(), uniq.begin(), uniq.end());
+    idx.push_back(n);
+    WRSN_ON_DEVICE(dst_h);
+    wrsn_handle* h = dst_h;
+    if (src_h->cc_bound > h->cc_bound || (src_h->stoch && !h->stoch)) {   // a new launch configuration, as a load's: once at most
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if ((rc = fit_launch(h, src_h->cc_bound, src_h->stoch != 0))) return rc;
+    }
+    const size_t need = (size_t)u * (size_t)h->rec_bytes;
+    if (need > h->xfer_cap) {
+        void* q = nullptr;
+        HIPCHK(hipMalloc(&q, need));
+        h->allocs.push_back(q);                               // the old area stays allocated: it is in h->allocs already
+        h->xfer = (uint8_t*)q; h->xfer_cap = need;
+    }
+    if ((rc = ensure_idx(h, idx.size()))) return rc;
+    HIPCHK(hipMemcpyAsync(h->d_idx, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    const int32_t *d_dst = h->d_idx, *d_rec = h->d_idx + n, *d_uniq = h->d_idx + 2 * (size_t)n, *d_n = h->d_idx + 2 * (size_t)n + u;
+    hipLaunchKernelGGL(wrsn_rec_header_kernel, dim3((u + 255) / 256), dim3(256), 0, h->stream, src_h->dev, (const double*)src_h->sd.pgp, rec_template(src_h),
+                       d_uniq, u, h->xfer, (long long)h->rec_bytes, step_out_dev(src_req, false));
+    HIPCHK(hipGetLastError());
+    if ((rc = launch_rec_copy(src_h, WRSN_REC_PACK, d_uniq, nullptr, h->xfer, u))) return rc;
+    {
+        const int chunks = (int)(h->rec_bytes / 16), per = chunks - WRSN_REC_HDR / 16;
+        const long long want = ((long long)n * per + 255) / 256;
+        const int blocks = (int)(want < (long long)h->cus * 8 ? want : (long long)h->cus * 8);
+        hipLaunchKernelGGL(wrsn_pool_copy_kernel, dim3(blocks), dim3(256), (size_t)h->nseg * sizeof(WrsnSeg), h->stream, (const WrsnSeg*)h->d_segs, h->nseg,
+                           d_dst, d_rec, d_n, (const uint8_t*)h->xfer, (long long)h->rec_bytes, chunks);
+        HIPCHK(hipGetLastError());
+    }
+    const bool renders = dst_out->obs || h->ent.node;
+    if (renders) HIPCHK(hipMemsetAsync(h->d_rend, 0xFF, (size_t)h->dev.B * sizeof(int32_t), h->stream));
+    hipLaunchKernelGGL(wrsn_rec_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, h->dev, (const uint8_t*)h->xfer, (long long)h->rec_bytes, d_rec,
+                       (const int32_t*)nullptr, d_dst, (int)n, (const int32_t*)nullptr, step_out_dev(dst_out), renders ? h->d_rend : (int32_t*)nullptr, -1, 0,
+                       h->d_pool_cur);
+    HIPCHK(hipGetLastError());
+    if (renders && (rc = launch_render_all(h, h->d_rend, dst_out->obs))) return rc;
+    for (int i = 0; i < n; ++i) h->filled[dst[i]] = 1;
+    h->scenario_set = 1;
+    return WRSN_OK;
+}
+
+// ------------------------------------------------------------------ one-step lookahead over the heuristic's K best picks (wrsn_rollout.h)
+namespace {
+const char* lookahead_bad(const wrsn_lookahead_state* st) {
+    if (!st) return "wrsn_lookahead_state is NULL";
+    if (st->K < 1 || st->K > WRSN_LOOKAHEAD_MAX_K) return "wrsn_lookahead_state: K must lie in [1, WRSN_LOOKAHEAD_MAX_K]";
+    if (st->B < 1) return "wrsn_lookahead_state: B must be at least 1";
+    if (!st->t0 || !st->t_end || !st->last_now || !st->ret || !st->survived || !st->done || !st->died) return "wrsn_lookahead_state: every array is required";
+    const void* f8[] = {st->t0, st->t_end, st->last_now, st->ret, st->survived};
+    for (const void* p : f8) if ((uintptr_t)p % 8) return "wrsn_lookahead_state: a float64 array is not 8-byte aligned";
+    return nullptr;
+}
+WrsnLookahead lookahead_dev(const wrsn_lookahead_state* st) {
+    WrsnLookahead L;
+    L.K = st->K; L.B = st->B; L.t0 = st->t0; L.t_end = st->t_end; L.last_now = st->last_now; L.ret = st->ret; L.survived = st->survived;
+    L.done = st->done; L.died = st->died;
+    return L;
+}
+}  // namespace
+
+int wrsn_lookahead_candidates(wrsn_t* h, const int32_t* agent_id, const wrsn_entity_out* ent, const double* now, const wrsn_lookahead_state* st,
+                              double horizon, float charge_scale, double min_charge, float x_clip, int32_t* node, int32_t* sim_agent_id,
+                              double* sim_action, float* stored) {
+    if (!h || !agent_id || !now || !node || !sim_agent_id || !sim_action || !stored)
+        return fail(WRSN_ERR_ARG, "wrsn_lookahead_candidates needs agent_id, now, node, sim_agent_id, sim_action and stored");
+    if (const char* m = lookahead_bad(st)) return fail(WRSN_ERR_ARG, m);
+    if (st->B != h->dev.B) return fail(WRSN_ERR_ARG, "wrsn_lookahead_candidates: wrsn_lookahead_state.B is not the handle's batch");
+    if ((uintptr_t)agent_id % 4 || (uintptr_t)node % 4 || (uintptr_t)sim_agent_id % 4 || (uintptr_t)stored % 4 || (uintptr_t)now % 8 || (uintptr_t)sim_action % 8)
+        return fail(WRSN_ERR_ARG, "wrsn_lookahead_candidates: an array is not aligned to its element size");
+    if (!std::isfinite(horizon) || horizon <= 0.0) return fail(WRSN_ERR_ARG, "wrsn_lookahead_candidates: horizon must be finite and > 0");
+    if (!std::isfinite(min_charge) || min_charge < 0.0 || min_charge >= 1.0)
+        return fail(WRSN_ERR_ARG, "wrsn_lookahead_candidates: min_charge must be finite and in [0, 1)");
+    if (!std::isfinite(x_clip) || x_clip <= 0.f) return fail(WRSN_ERR_ARG, "wrsn_lookahead_candidates: x_clip must be finite and > 0");
+    WrsnEntityOut e{};
+    { const int rc = entity_in(h, ent, &e); if (rc) return rc; }
+    WRSN_ON_DEVICE(h);
+    const int B = h->dev.B;
+    hipLaunchKernelGGL(wrsn_lookahead_candidates_kernel, entity_row_grid(B), dim3(64 * WRSN_ENT_ROWS), 0, h->stream, B, h->dev.M, h->dev.N, (int)st->K, agent_id, e,
+                       now, lookahead_dev(st), horizon, charge_scale, min_charge, x_clip, node, sim_agent_id, sim_action, stored);
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+int wrsn_lookahead_collect(wrsn_t* sim_h, const wrsn_lookahead_state* st, const wrsn_step_out* out, int32_t* next_agent_id, int32_t close_all) {
+    if (!sim_h || !out || !next_agent_id) return fail(WRSN_ERR_ARG, "wrsn_lookahead_collect needs the handle, out and next_agent_id");
+    if (const char* m = lookahead_bad(st)) return fail(WRSN_ERR_ARG, m);
+    if ((long long)st->K * st->B != (long long)sim_h->dev.B)
+        return fail(WRSN_ERR_ARG, "wrsn_lookahead_collect: the handle's batch is not K * B of wrsn_lookahead_state");
+    if (!out->agent_id || !out->reward || !out->now || !out->status)
+        return fail(WRSN_ERR_ARG, "wrsn_lookahead_collect needs agent_id, reward, now and status of wrsn_step_out");
+    if (next_agent_id == out->agent_id) return fail(WRSN_ERR_ARG, "wrsn_lookahead_collect: next_agent_id must not be out->agent_id");
+    WRSN_ON_DEVICE(sim_h);
+    const int R = sim_h->dev.B;
+    hipLaunchKernelGGL(wrsn_lookahead_collect_kernel, dim3((R + 255) / 256), dim3(256), 0, sim_h->stream, R, lookahead_dev(st), (const int32_t*)out->agent_id,
+                       (const double*)out->reward, (const double*)out->now, (const int32_t*)out->status, sim_h->dev.row_state, next_agent_id,
+                       (int)(close_all != 0));
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+int wrsn_lookahead_pick(wrsn_t* h, const int32_t* agent_id, const wrsn_lookahead_state* st, const int32_t* sim_agent_id, const double* sim_action,
+                        const float* cand_stored, int32_t* choice, double* action_f64, float* action, float* stored) {
+    if (!h || !agent_id || !sim_agent_id || !sim_action || !choice) return fail(WRSN_ERR_ARG, "wrsn_lookahead_pick needs agent_id, sim_agent_id, sim_action and choice");
+    if (stored && !cand_stored) return fail(WRSN_ERR_ARG, "wrsn_lookahead_pick: stored needs the candidates' stored pairs");
+    if (const char* m = lookahead_bad(st)) return fail(WRSN_ERR_ARG, m);
+    if (st->B != h->dev.B) return fail(WRSN_ERR_ARG, "wrsn_lookahead_pick: wrsn_lookahead_state.B is not the handle's batch");
+    WRSN_ON_DEVICE(h);
+    const int B = h->dev.B;
+    hipLaunchKernelGGL(wrsn_lookahead_pick_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, B, h->dev.M, agent_id, lookahead_dev(st), sim_agent_id, sim_action,
+                       cand_stored, choice, action_f64, action, stored);
+    HIPCHK(hipGetLastError());
     return WRSN_OK;
 }
 

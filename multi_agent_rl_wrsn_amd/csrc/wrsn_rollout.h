@@ -736,6 +736,91 @@ __global__ void __launch_bounds__(64 * WRSN_ENT_ROWS) wrsn_entity_heuristic_labe
     if (action_f64) { double* d = action_f64 + (size_t)e * 3; d[0] = (double)x; d[1] = (double)y; d[2] = (double)t; }
 }
 
+// ------------------------------------------------------------------ the heuristic's K best picks (wrsn_lookahead_candidates)
+// The ranking wrsn_entity_heuristic_label_kernel takes the head of: the alive unclaimed nodes by (score descending, index ascending), then
+// the alive claimed ones in the same order.  The shape of that kernel -- a wave per row, WRSN_ENT_ROWS rows per block, no LDS, no
+// __syncthreads, __shfl_xor butterflies -- with its loop over the nodes run K times: pass k leaves out the k nodes taken so far (wave-uniform
+// registers; the loops over them are unrolled, so nothing is indexed at run time) and keeps two candidates per lane, the best unclaimed and
+// the best claimed node, both reduced by every wave.  Pass 0 is the heuristic's own pick: with no unclaimed node every alive node is
+// claimed, so "best claimed" is its fallback over all alive nodes.  The row is fetched from HBM once; passes 1 .. K - 1 read it from the
+// cache.  Lane 0 writes slot r = k * B + e of the k-major outputs and of the lookahead state after every pass.
+#define WRSN_LOOKAHEAD_MAX_K 8
+
+struct WrsnLookahead {                                        // mirrors wrsn_lookahead_state of include/wrsn_hip.h (device pointers)
+    int32_t K, B;
+    double *t0, *t_end, *last_now, *ret, *survived;
+    uint8_t *done, *died;
+};
+
+__global__ void __launch_bounds__(64 * WRSN_ENT_ROWS) wrsn_lookahead_candidates_kernel(int B, int M, int N, int K, const int32_t* __restrict__ agent_id,
+                                                                                        WrsnEntityOut ent, const double* __restrict__ now, WrsnLookahead L,
+                                                                                        double horizon, float charge_scale, double min_charge, float x_clip,
+                                                                                        int32_t* __restrict__ cand_node, int32_t* __restrict__ sim_agent_id,
+                                                                                        double* __restrict__ sim_action, float* __restrict__ stored) {
+    const int lane = (int)threadIdx.x & 63;
+    const int e = (int)blockIdx.x * WRSN_ENT_ROWS + ((int)threadIdx.x >> 6);
+    if (e >= B) return;
+    const int a = wrsn_wave_first(agent_id[e]);
+    if (a < 0 || a >= M) return;
+    const float* mc = ent.mc + (size_t)e * M * WRSN_ENT_MC_F;
+    const float hx = ent.env[(size_t)e * WRSN_ENT_ENV_F], hy = ent.env[(size_t)e * WRSN_ENT_ENV_F + 1];
+    int self = a;
+    for (int o = M - 1; o >= 0; --o) if (mc[o * WRSN_ENT_MC_F + 3] == 1.f) self = o;
+    float cx[WRSN_MAX_MC], cy[WRSN_MAX_MC]; bool on[WRSN_MAX_MC];
+#pragma unroll
+    for (int o = 0; o < WRSN_MAX_MC; ++o) {
+        const int c = o < M ? o : M - 1;                      // clamped: chargers beyond M are switched off
+        on[o] = o < M && o != self && mc[c * WRSN_ENT_MC_F + 4] == 1.f;
+        cx[o] = mc[c * WRSN_ENT_MC_F + 6]; cy[o] = mc[c * WRSN_ENT_MC_F + 7];
+    }
+    const auto node = wrsn_global((const WrsnU4*)(ent.node + (size_t)e * N * WRSN_ENT_NODE_F));
+    const float ninf = -__builtin_inff();
+    const float mcf = (float)min_charge;                      // the label's min_charge, as wrsn_entity_heuristic_label takes it
+    const double t_now = now[e];
+    int taken[WRSN_LOOKAHEAD_MAX_K];
+#pragma unroll
+    for (int j = 0; j < WRSN_LOOKAHEAD_MAX_K; ++j) taken[j] = WRSN_EH_NONE;
+#pragma unroll
+    for (int k = 0; k < WRSN_LOOKAHEAD_MAX_K; ++k) {
+        if (k >= K) break;                                    // (uniform over the grid)
+        float sC = ninf, sU = ninf; int iC = WRSN_EH_NONE, iU = WRSN_EH_NONE;
+        for (int n0 = 0; n0 < N; n0 += 64) {
+            const int n = n0 + lane, c = n < N ? n : N - 1;   // clamped: nodes beyond N are no candidates
+            const WrsnU4 p = wrsn_ld_u4(node + 2 * c), q = wrsn_ld_u4(node + 2 * c + 1);
+            const float u = __int_as_float((int)p.x), v = __int_as_float((int)p.y), w = __int_as_float((int)p.z);
+            bool free = n < N && __int_as_float((int)q.w) == 1.f;   // alive and not taken by an earlier pass
+#pragma unroll
+            for (int j = 0; j < WRSN_LOOKAHEAD_MAX_K; ++j) free = free && !(j < k && taken[j] == n);
+            bool claimed = false;
+#pragma unroll
+            for (int o = 0; o < WRSN_MAX_MC; ++o) claimed = claimed || (on[o] && wrsn_eh_claims(u, v, cx[o], cy[o], hx, hy));
+            const float s = w > ninf ? w : ninf;              // a NaN never beats a number
+            if (free && claimed && (iC == WRSN_EH_NONE || s > sC)) { sC = s; iC = n; }
+            if (free && !claimed && (iU == WRSN_EH_NONE || s > sU)) { sU = s; iU = n; }
+        }
+        const int bU = wrsn_eh_wave_best(sU, iU), bC = wrsn_eh_wave_best(sC, iC);
+        const int n = bU != WRSN_EH_NONE ? bU : bC;
+        taken[k] = n;
+        if (lane != 0) continue;
+        const bool valid = n != WRSN_EH_NONE || k == 0;       // no alive node: slot 0 stands still, as the heuristic does
+        const size_t r = (size_t)k * B + e;
+        if (valid) {
+            float x, y, t, kf, xs;
+            if (n != WRSN_EH_NONE) {
+                const float* row = ent.node + ((size_t)e * N + n) * WRSN_ENT_NODE_F;
+                x = row[0]; y = row[1]; t = wrsn_eh_charge(charge_scale, row[3]);
+                kf = (float)n; xs = wrsn_eh_label_x(t, mcf, x_clip);
+            } else { x = mc[self * WRSN_ENT_MC_F]; y = mc[self * WRSN_ENT_MC_F + 1]; t = 0.f; kf = -1.f; xs = -x_clip; }
+            const double td = (double)t;
+            cand_node[r] = n != WRSN_EH_NONE ? n : -1; sim_agent_id[r] = a;
+            double* d = sim_action + r * 3; d[0] = (double)x; d[1] = (double)y; d[2] = td > min_charge ? td : min_charge;
+            stored[r * 2] = kf; stored[r * 2 + 1] = xs;
+        } else { cand_node[r] = -1; sim_agent_id[r] = -2; }
+        L.t0[r] = t_now; L.t_end[r] = t_now + horizon; L.last_now[r] = t_now; L.ret[r] = 0.0;
+        L.died[r] = 0; L.done[r] = valid ? 0 : 1;
+    }
+}
+
 // ------------------------------------------------------------------ node-pointer entity policy: acting (wrsn_entity_pointer_act)
 // The actor of build_entity_pointer_networks (ippo.py): the trunk of the set policy, a categorical choice of ONE alive node by a score per
 // node, and a charge head on the chosen node's features.  The query needs z, z needs the pools over all nodes: the nodes are visited
@@ -1057,4 +1142,69 @@ __global__ void __launch_bounds__(256) wrsn_episodes_kernel(int B, int M, WrsnEp
     if (next_agent_id && has_next) next_agent_id[e] = next;
     if (restart) restart[e] = again;
     if (consume && (st == 1 || st == 2 || st == 4)) row_state[e] = 0;
+}
+
+// ------------------------------------------------------------------ lookahead bookkeeping and choice (wrsn_lookahead_collect, wrsn_lookahead_pick)
+// The roll-forward of the K * B cloned environments of a simulation handle, booked per slot as the episode ledger books an environment:
+// one thread per slot, 256 per block, keyed on WrsnDev.row_state exactly as wrsn_episodes_kernel; a slot's state lives in its own elements
+// of the caller's arrays, so there is no atomic, no reduction and no order to fix.  The rules are in include/wrsn_hip.h.  The row state is
+// always consumed.
+__global__ void __launch_bounds__(256) wrsn_lookahead_collect_kernel(int R, WrsnLookahead L, const int32_t* __restrict__ agent_id,
+                                                                     const double* __restrict__ reward, const double* __restrict__ now,
+                                                                     const int32_t* __restrict__ status, int32_t* __restrict__ row_state,
+                                                                     int32_t* __restrict__ next_agent_id, int close_all) {
+    const int r = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (r >= R) return;
+    const int st = row_state[r];
+    if (st == 1 || st == 2 || st == 4) row_state[r] = 0;
+    if (L.done[r]) { next_agent_id[r] = -2; return; }
+    double last = L.last_now[r];
+    bool close = false;
+    if (st == 3) next_agent_id[r] = -1;                                       // step in flight
+    else if (st == 1) {                                                       // fresh request
+        L.ret[r] += reward[r];
+        last = now[r]; L.last_now[r] = last;
+        if (status[r] == 1 || last >= L.t_end[r]) close = true;
+        else next_agent_id[r] = agent_id[r];
+    } else if (st == 4) {                                                     // terminal return: no reward, as in the ledger
+        L.died[r] = 1;
+        last = now[r]; L.last_now[r] = last;
+        close = true;
+    }
+    if (close || close_all) {
+        const double te = L.t_end[r];
+        L.survived[r] = (last < te ? last : te) - L.t0[r];
+        L.done[r] = 1;
+        next_agent_id[r] = -2;
+    }
+}
+
+// One thread per row of the REAL batch: the lexicographic best over the row's valid, finished slots -- survived descending, then ret
+// descending, then k ascending; anything that is not > -inf (a NaN) counts as -inf, so a NaN never beats a number.  No weight between
+// the two keys.  Nothing qualifies: k = 0.
+__global__ void __launch_bounds__(256) wrsn_lookahead_pick_kernel(int B, int M, const int32_t* __restrict__ agent_id, WrsnLookahead L,
+                                                                  const int32_t* __restrict__ sim_agent_id, const double* __restrict__ sim_action,
+                                                                  const float* __restrict__ cand_stored, int32_t* __restrict__ choice,
+                                                                  double* __restrict__ action_f64, float* __restrict__ action,
+                                                                  float* __restrict__ stored) {
+    const int e = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (e >= B) return;
+    const int a = agent_id[e];
+    if (a < 0 || a >= M) return;
+    const double ninf = -__builtin_inf();
+    int best = -1; double bs = ninf, br = ninf;
+    for (int k = 0; k < L.K; ++k) {
+        const size_t r = (size_t)k * B + e;
+        if (sim_agent_id[r] < 0 || !L.done[r]) continue;
+        const double sv = L.survived[r], rt = L.ret[r];
+        const double s = sv > ninf ? sv : ninf, q = rt > ninf ? rt : ninf;
+        if (best < 0 || s > bs || (s == bs && q > br)) { best = k; bs = s; br = q; }
+    }
+    if (best < 0) best = 0;
+    const size_t r = (size_t)best * B + e;
+    choice[e] = best;
+    const double x = sim_action[r * 3], y = sim_action[r * 3 + 1], t = sim_action[r * 3 + 2];
+    if (action_f64) { double* d = action_f64 + (size_t)e * 3; d[0] = x; d[1] = y; d[2] = t; }
+    if (action) { float* o = action + (size_t)e * 3; o[0] = (float)x; o[1] = (float)y; o[2] = (float)t; }
+    if (stored) { stored[(size_t)e * 2] = cand_stored[r * 2]; stored[(size_t)e * 2 + 1] = cand_stored[r * 2 + 1]; }
 }

@@ -7,8 +7,9 @@ launch and the restart mask; the host reads one flag every `poll` launches.
 Policies are callables `policy(env, ids) -> float64 [B, 3]` (rows with ids outside [0, M) are ignored by `env.step`):
 `EntityPolicy` (the learned set policy through `wrsn_entity_act`, its mode or a sample), `PointerPolicy` (the learned node-pointer
 policy through `wrsn_entity_pointer_act`, likewise), `HeuristicPolicy` (the deterministic baseline of
-`wrsn_entity_heuristic_act`), `HeuristicLabelPolicy` (the same decision squashed the pointer's way, `wrsn_entity_heuristic_label`) and
-`UniformPolicy` (`torch.rand`)."""
+`wrsn_entity_heuristic_act`), `HeuristicLabelPolicy` (the same decision squashed the pointer's way, `wrsn_entity_heuristic_label`),
+`LookaheadPolicy` (the heuristic's K best picks scored on clones in a second batch, `wrsn_lookahead_candidates` / `_collect` / `_pick`)
+and `UniformPolicy` (`torch.rand`)."""
 import numpy as np
 
 from ._lib import ENDED_FELL_OFF, ENDED_TERMINAL, ENDED_TIME_LIMIT, POINTER_MASK_CLAIMED, POINTER_MASK_NONE
@@ -85,6 +86,52 @@ class HeuristicLabelPolicy:
         t = env.torch
         stored, _, act = env.entity_heuristic_label(ids, self.charge_scale, self.min_charge, self.x_clip)
         act[:, 2] = self.min_charge + (1.0 - self.min_charge) * t.sigmoid(stored[:, 1].double())
+        return act
+
+
+class LookaheadPolicy:
+    """One step of policy improvement over the heuristic: for every request the heuristic's K best nodes (`VecWRSN.lookahead_candidates`)
+    are each tried on a clone of the environment in `sim_env` -- a `VecWRSN(entities=True, render=False, auto_reset=False)` of
+    K * env.num_env environments of the same geometry, created on the same scenarios (tiled K times) so that the capacities agree --
+    the clones run on under `HeuristicPolicy(charge_scale, min_charge)` for `horizon` simulated seconds, and the candidate whose clone
+    survived longest, then collected the largest return, then has the lowest rank, is played (`VecWRSN.lookahead_pick`).  The real `env`
+    is only read.  At most `max_launches` launches of `sim_env` per call; whether every slot has finished is read once every `poll`
+    launches, the only host read.  Slots still open after the last launch are closed as they stand, so a step budget on `sim_env` works.
+    K = 1 plays `HeuristicPolicy(charge_scale, min_charge)`'s bytes.  After a call: `choice` int32 [B] (the rank played), `stored`
+    float32 [B, 2] (the played decision as the node-pointer policy stores one), `look` (the `Lookahead`) and `sim_launches`."""
+
+    def __init__(self, sim_env, K=4, horizon=30.0, charge_scale=1.0, min_charge=0.02, x_clip=4.0, max_launches=64, poll=8):
+        self.sim_env, self.K, self.horizon = sim_env, int(K), float(horizon)
+        self.charge_scale, self.min_charge, self.x_clip = float(charge_scale), float(min_charge), float(x_clip)
+        self.max_launches, self.poll = max(1, int(max_launches)), max(1, int(poll))
+        self.rollout = HeuristicPolicy(charge_scale, min_charge)
+        self.look = self.choice = self.stored = None
+        self.sim_launches = self.calls = 0
+
+    def __call__(self, env, ids):
+        sim, K, B = self.sim_env, self.K, env.num_env
+        if sim.num_env != K * B or sim.auto_reset or not sim.entities:
+            raise ValueError("LookaheadPolicy needs sim_env = VecWRSN(entities=True, auto_reset=False) of K * env.num_env = %d environments" % (K * B))
+        if self.look is None or self.look.B != B:
+            self.look = env.new_lookahead(K)
+            self._src, self._dst = np.tile(np.arange(B, dtype=np.int32), K), np.arange(K * B, dtype=np.int32)
+        look = self.look
+        look.clear()                                          # rows the candidates call skips: invalid and finished
+        env.lookahead_candidates(look, ids, self.horizon, self.charge_scale, self.min_charge, self.x_clip)
+        sim.clone_envs_from(env, self._src, self._dst)
+        sim.step(look.sim_agent_id.view(-1), look.sim_action.view(-1, 3))
+        launches = 1
+        while True:
+            nxt = sim.lookahead_collect(look)
+            if launches % self.poll == 0 and bool(look.done.all()):   # the one host read, every `poll` launches
+                break
+            if launches >= self.max_launches:
+                break
+            sim.step(nxt, self.rollout(sim, nxt))
+            launches += 1
+        sim.lookahead_collect(look, close_all=True)
+        self.choice, act, self.stored = env.lookahead_pick(look, ids)
+        self.sim_launches += launches; self.calls += 1
         return act
 
 

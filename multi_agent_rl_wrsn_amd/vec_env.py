@@ -55,6 +55,33 @@ class EpisodeLog:
                 getattr(self, k).zero_()
 
 
+class Lookahead:
+    """The state of the lookahead calls for K candidates per row of a real batch of B environments (`wrsn_lookahead_state`: `t0`, `t_end`,
+    `last_now`, `ret`, `survived` float64 and `done`, `died` uint8, all [K, B]), the k-major candidate tensors -- `node`, `sim_agent_id`
+    int32 [K, B], `sim_action` float64 [K, B, 3], `cand_stored` float32 [K, B, 2]: the simulation batch's step inputs as they stand --
+    `next_agent_id` int32 [K * B], and the choice per real row: `choice` int32 [B], `action_f64` [B, 3], `action` [B, 3], `stored` [B, 2].
+    `clear()` marks every slot invalid and finished (asynchronously), which is what rows a candidates call skips must hold."""
+
+    def __init__(self, torch, device, K, B):
+        if not 1 <= K <= _lib.LOOKAHEAD_MAX_K:
+            raise ValueError("K must lie in [1, %d], got %d" % (_lib.LOOKAHEAD_MAX_K, K))
+        self.K, self.B = K, B
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
+        for k in _lib.LOOKAHEAD_F64:
+            setattr(self, k, z((K, B), torch.float64))
+        for k in _lib.LOOKAHEAD_U8:
+            setattr(self, k, z((K, B), torch.uint8))
+        self.node, self.sim_agent_id = z((K, B), torch.int32), z((K, B), torch.int32)
+        self.sim_action, self.cand_stored = z((K, B, 3), torch.float64), z((K, B, 2), torch.float32)
+        self.next_agent_id = z((K * B,), torch.int32)
+        self.choice, self.action_f64, self.action, self.stored = z((B,), torch.int32), z((B, 3), torch.float64), z((B, 3), torch.float32), z((B, 2), torch.float32)
+        self.raw = _lib.WrsnLookaheadState(K, B, *(getattr(self, k).data_ptr() for k in _lib.LOOKAHEAD_F64 + _lib.LOOKAHEAD_U8))
+        self.clear()
+
+    def clear(self):
+        self.node.fill_(-1); self.sim_agent_id.fill_(-2); self.next_agent_id.fill_(-2); self.done.fill_(1)
+
+
 class VecWRSN:
     """Batched WRSN environment on one MI355X.
 
@@ -454,6 +481,61 @@ class VecWRSN:
         d = np.asarray(dst, dtype=np.int64).reshape(-1).astype(np.int32)
         self._h.clone_envs(s, d, **self._out_ptrs())
         return self._result()
+
+    def clone_envs_from(self, src_env, src, dst):
+        """Environment dst[i] of THIS batch becomes a copy of environment src[i] of `src_env`, another batch of the same geometry on the
+        same device and stream (`wrsn_clone_envs_from`; device to device, asynchronous, no host read); `src` may repeat.  `src_env` is
+        only read.  Its request rows follow into this batch's rows.  Returns this batch's request tensors."""
+        self._bind_stream(); src_env._bind_stream()
+        s = np.asarray(src, dtype=np.int64).reshape(-1).astype(np.int32)
+        d = np.asarray(dst, dtype=np.int64).reshape(-1).astype(np.int32)
+        q = dict(src_env._out_ptrs()); q.pop("obs", None)
+        self._h.clone_envs_from(src_env._h, s, d, q, **self._out_ptrs())
+        return self._result()
+
+    # -- one-step lookahead over the heuristic's K best picks (wrsn_lookahead_candidates / _collect / _pick) --------------------------
+    def new_lookahead(self, K):
+        """The state and the k-major tensors of a lookahead over K candidates per row of THIS (the real) batch: a `Lookahead`."""
+        return Lookahead(self.torch, self.device, int(K), self.num_env)
+
+    def lookahead_candidates(self, look, agent_ids, horizon, charge_scale=1.0, min_charge=0.0, x_clip=4.0):
+        """`wrsn_lookahead_candidates` on the entity rows this object holds (`entities=True`) for the chargers `agent_ids` [B]: the
+        heuristic's K best nodes per row into `look.node`, `look.sim_agent_id`, `look.sim_action`, `look.cand_stored`, and the slots of
+        `look` initialised at this batch's `now`.  Rows outside [0, M) are skipped and keep what they held.  Returns `look`."""
+        t = self.torch
+        if not self.entities:
+            raise ValueError("lookahead_candidates needs a VecWRSN with the entity observation (entities=True)")
+        self._bind_stream()
+        a = agent_ids
+        if not (a.dtype == t.int32 and a.device == self.device and a.is_contiguous() and a.numel() == self.num_env):
+            a = a.to(device=self.device, dtype=t.int32).reshape(-1).contiguous()
+        look._keep = a                                        # alive until the launch has run
+        self._h.lookahead_candidates(a.data_ptr(), self._out_ptrs()["now"], look.raw, horizon, charge_scale, min_charge, x_clip, None,
+                                     node=look.node.data_ptr(), sim_agent_id=look.sim_agent_id.data_ptr(), sim_action=look.sim_action.data_ptr(),
+                                     stored=look.cand_stored.data_ptr())
+        return look
+
+    def lookahead_collect(self, look, close_all=False):
+        """`wrsn_lookahead_collect` after a `step` of THIS (the simulation) batch of K * B environments: books its requests into `look`
+        and returns `look.next_agent_id` [K * B], the ids of the next `step` (-2: slot closed, -1: step in flight)."""
+        self._bind_stream()
+        p = self._out_ptrs(); p.pop("obs", None)
+        self._h.lookahead_collect(look.raw, look.next_agent_id.data_ptr(), close_all, **p)
+        return look.next_agent_id
+
+    def lookahead_pick(self, look, agent_ids):
+        """`wrsn_lookahead_pick` on THIS (the real) batch: per row the finished slot with the longest survival, then the largest return,
+        then the lowest k.  Returns (choice int32 [B], action_f64 float64 [B,3], stored float32 [B,2]): tensors of `look`."""
+        t = self.torch
+        self._bind_stream()
+        a = agent_ids
+        if not (a.dtype == t.int32 and a.device == self.device and a.is_contiguous() and a.numel() == self.num_env):
+            a = a.to(device=self.device, dtype=t.int32).reshape(-1).contiguous()
+        look._keep = a
+        self._h.lookahead_pick(a.data_ptr(), look.raw, look.sim_agent_id.data_ptr(), look.sim_action.data_ptr(), look.cand_stored.data_ptr(),
+                               choice=look.choice.data_ptr(), action_f64=look.action_f64.data_ptr(), action=look.action.data_ptr(),
+                               stored=look.stored.data_ptr())
+        return look.choice, look.action_f64, look.stored
 
     # -- scenario pools: finished episodes restart in another network, on the device (wrsn_pool_set / wrsn_pool_reset) ----------------
     def set_pool(self, records, seed=0):

@@ -19,6 +19,13 @@ iterations on top (`bc_ppo_mode`, `bc_ppo_sampled`), next to the PPO-only rows (
 more under the mask (`masked_...`).  The cloning statistics of every iteration are kept as a compact table (`pretrain_table`): loss and
 top-1 of the device table's first and last row per charger, the loss parts and the entropy of its last row.  Writes profiles/entity_pointer_bc_eval.json.
 
+`--lookahead K [--lookahead K ...] [--horizon T ...]`: the lookahead expert against the heuristic it improves on, in one run on the held-out
+set: `heuristic_min_charge`, then `LookaheadPolicy(K, horizon)` for every K and horizon (default horizons: 1, 3 and 10 times the
+heuristic's mean interval between requests in this run, lifetime / decisions from its own ledger) on a simulation batch of K * eval-envs
+environments.  Per row: the lifetime summary, the share of decisions with choice != 0 and which key decided them (a longer survival, or
+the return at equal survival), launches of the simulation batch per real launch and wall time per real launch against the heuristic's.
+Writes profiles/lookahead_eval.json.
+
 --bench: the evaluation loop per launch at `--envs` (4096) x 200 nodes x 3 chargers with the heuristic policy, in two forms: with
 wrsn_episodes_collect, and with the same bookkeeping in elementwise torch on calls that existed before it (`step`, `reset(mask)`).
 Alternating windows of `--launches` launches (synchronised wall time of a window / launches), medians of the window medians.  Writes
@@ -247,6 +254,72 @@ def compare(args, make_envs=device_envs):
     return out
 
 
+def lookahead_compare(args):
+    """The heuristic and the lookahead policy over it on the held-out set, in the same run."""
+    import numpy as np
+    import torch
+    from multi_agent_rl_wrsn_amd import HeuristicPolicy, LookaheadPolicy, VecWRSN, evaluate_policy, synth_scenario
+    from multi_agent_rl_wrsn_amd.evaluate import LaunchCapReached
+    N, M = 200, 3
+    scs = [synth_scenario(1_000_000 + e, N, N) for e in range(args.eval_envs)]
+    env = VecWRSN(scs, None, M, render=False, entities=True, step_budget=1250)
+    out = {"eval_set": "%d synthetic %d-node networks, seeds 1000000.., %d chargers, %d episode(s) each, time limit %g s, ONE seed" %
+                       (args.eval_envs, N, M, args.episodes, min(s.max_time for s in scs)),
+           "device": torch.cuda.get_device_name(env.device), "max_launches": args.max_launches, "min_charge": args.min_charge, "record_bytes": env.record_bytes(), "policies": {}}
+
+    def run(name, policy, extra=None):
+        torch.cuda.synchronize(env.device); t0 = time.perf_counter()
+        try:
+            res, capped = evaluate_policy(env, policy, episodes=args.episodes, max_launches=args.max_launches), False
+        except LaunchCapReached as ex:
+            res, capped = ex.result, True
+        torch.cuda.synchronize(env.device)
+        sec = time.perf_counter() - t0
+        row = dict(res["summary"], launches=int(res["launches"]), launch_cap_reached=capped, seconds=sec, ms_per_real_launch=1e3 * sec / max(1, int(res["launches"])))
+        row["decisions_per_episode"] = float(res["decisions"].sum(-1).mean())
+        row.update(extra() if extra else {})
+        out["policies"][name] = row
+        print(name, json.dumps(row), flush=True)
+        if args.out:                                           # kept row by row: a long comparison that is cut short leaves what it has
+            with open(args.out, "w") as w:
+                json.dump(out, w, indent=1)
+        return row
+
+    base = run("heuristic_min_charge", HeuristicPolicy(min_charge=args.min_charge))
+    interval = base["lifetime_mean"] / max(1.0, base["decisions_per_episode"])
+    out["heuristic_mean_request_interval_s"] = interval
+    horizons = args.horizon or [interval, 3 * interval, 10 * interval]
+    out["horizons_s"] = horizons
+    for K in args.lookahead:
+        sim = VecWRSN(scs * K, None, M, render=False, entities=True, step_budget=1250)
+        for T in horizons:
+            pol = LookaheadPolicy(sim, K=K, horizon=T, min_charge=args.min_charge, max_launches=args.sim_launches)
+            cnt = torch.zeros(3, dtype=torch.int64, device=env.device)   # decisions, choice != 0 by survival, by return at equal survival
+
+            def counting(e, ids, pol=pol, cnt=cnt):
+                if args.label_yardstick:                       # wrsn_entity_heuristic_label on the same rows, for a kernel trace
+                    e.entity_heuristic_label(ids, 1.0, args.min_charge, args.x_clip)
+                act = pol(e, ids)
+                rows = (ids >= 0) & (ids < M)
+                c = pol.choice.long()
+                sv = pol.look.survived
+                better = sv.gather(0, c[None, :])[0] > sv[0]
+                cnt.add_(torch.stack([rows.sum(), (rows & (c != 0) & better).sum(), (rows & (c != 0) & ~better).sum()]))
+                return act
+
+            def extra(pol=pol, cnt=cnt):
+                d, a, b = (int(x) for x in cnt.cpu())
+                return {"K": pol.K, "horizon_s": pol.horizon, "decisions": d, "share_choice_not_0": (a + b) / max(1, d), "decided_by_survival": a,
+                        "decided_by_return": b, "sim_launches_per_real_launch": pol.sim_launches / max(1, pol.calls),
+                        "wall_per_real_launch_over_heuristic": None}
+
+            row = run("lookahead_K%d_T%g" % (K, T), counting, extra)
+            row["wall_per_real_launch_over_heuristic"] = row["ms_per_real_launch"] / base["ms_per_real_launch"]
+            row["lifetime_mean_over_heuristic"] = row["lifetime_mean"] / base["lifetime_mean"]
+        sim.close()
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--policy", default="gaussian", choices=["gaussian", "pointer"], help="gaussian: the set policy (BatchedEntityIPPO, the default); "
@@ -268,6 +341,11 @@ def main(argv=None):
     ap.add_argument("--critic-iters", type=int, default=0, help="pretraining: critic-only iterations after it")
     ap.add_argument("--x-clip", type=float, default=4.0, help="pretraining: the clamp of the label's charge variable")
     ap.add_argument("--fused-policy", action="store_true", help="pointer: accepted for symmetry with bench_ippo.py; the tool always acts fused")
+    ap.add_argument("--lookahead", type=int, action="append", default=None, help="K: compare LookaheadPolicy(K) with the heuristic (repeatable)")
+    ap.add_argument("--horizon", type=float, action="append", default=None, help="lookahead: a horizon in simulated seconds (repeatable; default 1, 3, "
+                    "10 times the heuristic's mean request interval)")
+    ap.add_argument("--label-yardstick", action="store_true", help="lookahead: also run wrsn_entity_heuristic_label at every decision (kernel traces)")
+    ap.add_argument("--sim-launches", type=int, default=64, help="lookahead: launches of the simulation batch per decision, at most")
     ap.add_argument("--bench", action="store_true")
     ap.add_argument("--windows", type=int, default=3)
     ap.add_argument("--launches", type=int, default=50)
@@ -276,8 +354,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.pretrain > 0 and not (args.policy == "pointer" and args.device_update):
         ap.error("--pretrain needs --policy pointer --device-update")
-    out = bench(args) if args.bench else compare(args)
-    path = args.out or os.path.join(ROOT, "profiles", "episodes_bench.json" if args.bench else
+    out = bench(args) if args.bench else lookahead_compare(args) if args.lookahead else compare(args)
+    path = args.out or os.path.join(ROOT, "profiles", "episodes_bench.json" if args.bench else "lookahead_eval.json" if args.lookahead else
                                     "entity_pointer_bc_eval.json" if args.policy == "pointer" and args.pretrain > 0 else
                                     "entity_pointer_mask_eval.json" if args.policy == "pointer" and args.mask_claimed else
                                     "entity_pointer_eval.json" if args.policy == "pointer" else "entity_eval.json")
