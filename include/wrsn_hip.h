@@ -93,9 +93,12 @@ enum wrsn_peek_what {
     WRSN_PEEK_NODE_STATUS = 3,   /* int32  [B,N]   Node.status                                    */
     WRSN_PEEK_NODE_LEVEL = 4,    /* int32  [B,N]   Node.level                                     */
     WRSN_PEEK_MC = 5,            /* double [B,M,16] loc_x, loc_y, energy, status, charging, cur_x, cur_y,
-                                                    cur_t, n_conn, excl, prev_minfit, act0, act1, act2, error, 0
+                                                    cur_t, n_conn, excl, prev_minfit, act0, act1, act2, error, safe
                                                     (error: the ENVIRONMENT's error code behind a row of status
-                                                    WRSN_ERR_CAPACITY, 0 = none, the same in every charger's row) */
+                                                    WRSN_ERR_CAPACITY, 0 = none; safe: the seconds the ENVIRONMENT may
+                                                    advance before a node can reach its threshold, -1 once the network is
+                                                    declared dead -- what the launch-order estimate reads; both the same
+                                                    in every charger's row) */
     WRSN_PEEK_ENV = 6,           /* double [B,16]  xmin,xmax,ymin,ymax,density,moving_time_max,charging_time_max,
                                                     avg_nodes_agent,now,alive,ticks,exact_ticks,events,min_fitness,
                                                     n_edges,n_cover                                 */
@@ -108,6 +111,13 @@ enum wrsn_peek_what {
     WRSN_PEEK_POOL = 13,         /* int32  [B,2]   scenario pool: the pool record the environment runs (-1 after wrsn_set_scenario* /
                                                     wrsn_load_envs, the source's value after wrsn_clone_envs) and its swaps since
                                                     wrsn_pool_set                                  */
+    WRSN_PEEK_ORDER = 14,        /* uint32 [2,B]   launch order of the last wrsn_step: row 0 the keys the estimate wrote,
+                                                    (0xFFFF - work in quarter seconds) << 13 | environment, from the states
+                                                    and actions the call started with; row 1 the environments in launch
+                                                    order, longest job first, ties by environment index.  A time-sliced call
+                                                    (wrsn_set_step_deadline) walks its cyclic order and computes neither: the
+                                                    peek then shows what the last call without a deadline left.  WRSN_ERR_STATE
+                                                    on handles whose batch is too large to be sorted (the order is 0..B-1). */
     WRSN_PEEK_RNG_STATE = 12     /* uint32 [B,627] the environment's MT19937: the 624 state words and the index as
                                                     random.getstate()[1] lists them, then the draws since the last reset
                                                     (low, high word).  Handles that run the stochastic kernels only

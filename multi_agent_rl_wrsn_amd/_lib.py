@@ -21,6 +21,7 @@ PEEK_TARGETS_ACTIVE = 11
 REC_CONN_BOUND_OFFSET = 44   # byte offset of WrsnRecHeader.conn_bound (int32) in an environment record (csrc/wrsn_state.h)
 PEEK_POOL = 13               # int32 [B, 2]: the pool record the environment runs (-1: none), its swaps since wrsn_pool_set
 STATUS_POOL_INDEX = -5       # per-row status of wrsn_pool_reset: pool_index outside the pool, row left as it was
+PEEK_ORDER = 14              # uint32 [2, B]: keys and launch order of the last step call (longest job first, ties by environment index)
 PEEK_RNG_STATE = 12          # uint32 [B, 627]: MT19937 words, index (random.getstate()[1]), draws since reset (low, high word)
 OBS_F32, OBS_BF16 = 0, 1     # wrsn_set_obs_format: float32 cells / bfloat16 bit patterns (uint16) behind every observation pointer
 # entity observation (wrsn_set_entity_out / wrsn_entities): floats per node, charger and environment row, and what each slot holds
@@ -36,7 +37,7 @@ POINTER_MASK_NONE, POINTER_MASK_CLAIMED = 0, 1   # wrsn_set_entity_pointer_mask:
 ENTITY_POINTER_FLOATS = 56980   # wrsn_entity_pointer_floats(): the block of the node-pointer actor (include/wrsn_hip.h)
 ENTPOL_FEAT = 200            # wrsn_entity_act: inputs of the actor's head (64 mean + 64 max + 32 charger mean + 32 own + 8 env)
 MC_FIELDS = ("loc_x", "loc_y", "energy", "status", "type_charging", "cur_x", "cur_y", "cur_t", "n_conn",
-             "excl", "prev_minfit", "act0", "act1", "act2", "error", "_r1")
+             "excl", "prev_minfit", "act0", "act1", "act2", "error", "safe")
 ENV_FIELDS = ("xmin", "xmax", "ymin", "ymax", "nodes_density", "moving_time_max", "charging_time_max",
               "avg_nodes_agent", "now", "alive", "n_ticks", "n_exact", "n_events", "min_fitness", "n_edges", "n_cover")
 
@@ -670,6 +671,8 @@ class RawHandle:
             a = np.empty((B, 627), dtype=np.uint32)
         elif what == PEEK_POOL:
             a = np.empty((B, 2), dtype=np.int32)
+        elif what == PEEK_ORDER:
+            a = np.empty((2, B), dtype=np.uint32)
         else:
             raise ValueError("unknown peek selector %r" % (what,))
         check(self.lib, self.lib.wrsn_peek(self._h, int(what), a.ctypes.data))
@@ -700,6 +703,12 @@ class RawHandle:
         import numpy as np
         a = self.peek(PEEK_RNG_STATE)
         return a[:, :625].copy(), a[:, 625].astype(np.int64) | (a[:, 626].astype(np.int64) << 32)
+
+    def launch_order(self):
+        """(keys uint32 [B], order int64 [B]) of the last step call: see WRSN_PEEK_ORDER."""
+        import numpy as np
+        a = self.peek(PEEK_ORDER)
+        return a[0].copy(), a[1].astype(np.int64)
 
     def pool_info(self):
         """Per environment: the pool record it runs (-1: its own scenario or a loaded record) and its swaps since wrsn_pool_set."""

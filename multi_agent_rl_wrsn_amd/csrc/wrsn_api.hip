@@ -309,9 +309,7 @@ void launch_order(wrsn_handle* h, const StepCall& c) {
     switch (kpt) {
     case 2: WRSN_SORT(2); break;
     case 4: WRSN_SORT(4); break;
-    case 8: WRSN_SORT(8); break;
-    case 16: WRSN_SORT(16); break;
-    case 32: WRSN_SORT(32); break;
+    case 8: WRSN_SORT(8); break;                               // the most there is: wrsn_create sorts on the device up to 8 keys per thread
     default: WRSN_SORT(1); break;
     }
 #undef WRSN_SORT
@@ -618,7 +616,7 @@ int wrsn_create(const wrsn_cfg* cfg, wrsn_t** out) {
     do {
         if ((rc = alloc_env_arrays(h, ENV_ARRAYS_DEV))) break;
         if ((rc = dalloc(h, &d.counters, B * 25))) break;
-        { int p2 = 1; while (p2 < d.B) p2 <<= 1; h->bp2 = d.B <= 8192 ? p2 : 0; }
+        { int p2 = 1; while (p2 < d.B) p2 <<= 1; h->bp2 = (d.B <= 8192 && p2 <= 8 * WRSN_SORT_THREADS) ? p2 : 0; }   // 8 keys per sort thread at most (launch_order)
         if ((rc = dalloc(h, &d.order_key, (size_t)(h->bp2 > 0 ? h->bp2 : 1)))) break;
         if ((rc = dalloc(h, &d.order, (size_t)(h->bp2 > d.B ? h->bp2 : d.B)))) break;
         if ((rc = dalloc(h, &d.launch_t0, 1))) break;
@@ -1784,7 +1782,7 @@ int wrsn_peek(wrsn_t* h, int32_t what, void* dst) {
                 const WrsnAgent& a = dy[e].ag[m]; double* q = o + (e * d.M + m) * 16;
                 q[0] = a.loc[0]; q[1] = a.loc[1]; q[2] = a.energy; q[3] = a.status; q[4] = a.type_charging;
                 q[5] = a.cur[0]; q[6] = a.cur[1]; q[7] = a.cur[2]; q[8] = a.n_conn; q[9] = a.excl; q[10] = a.prev_minfit;
-                q[11] = a.action[0]; q[12] = a.action[1]; q[13] = a.action[2]; q[14] = dy[e].error; q[15] = 0;
+                q[11] = a.action[0]; q[12] = a.action[1]; q[13] = a.action[2]; q[14] = dy[e].error; q[15] = dy[e].frozen ? -1.0 : (double)dy[e].safe_ticks;
             }
         return 0; }
     case WRSN_PEEK_ENV: {
@@ -1836,6 +1834,12 @@ int wrsn_peek(wrsn_t* h, int32_t what, void* dst) {
         HIPCHK(hipMemcpy(sw.data(), h->d_pool_swaps, B * 4, hipMemcpyDeviceToHost));
         int32_t* o = (int32_t*)dst;
         for (size_t e = 0; e < B; ++e) { o[2 * e] = cur[e]; o[2 * e + 1] = sw[e]; }
+        return 0; }
+    case WRSN_PEEK_ORDER: {
+        if (h->bp2 <= 0) return fail(WRSN_ERR_STATE, "the launch order of this handle is not sorted (more environments than the sort workgroup takes)");
+        uint32_t* o = (uint32_t*)dst;
+        HIPCHK(hipMemcpy(o, d.order_key, B * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(o + B, d.order, B * 4, hipMemcpyDeviceToHost));
         return 0; }
     default: return fail(WRSN_ERR_ARG, "unknown peek selector");
     }

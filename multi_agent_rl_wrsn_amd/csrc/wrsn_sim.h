@@ -2128,12 +2128,6 @@ struct Sim : SimStochRegs<STOCH> {
         return f;
     }
 
-    WDEV static bool key_less(double t1, int p1, int64_t s1, double t2, int p2, int64_t s2) {
-        if (t1 != t2) return t1 < t2;
-        if (p1 != p2) return p1 < p2;
-        return s1 < s2;
-    }
-
     // Fire charger / condition events in order until the wave has to do something: run the grid up to the next
     // event (REQ_GRID), an O(N) service (REQ_PRECHECK / REQ_CONN), or the run stops (REQ_STOP).
     // The cached "next event" lives in registers while lane 0 runs and in the LDS Scalar block between two services.
@@ -2257,13 +2251,8 @@ struct Sim : SimStochRegs<STOCH> {
                 *pend_out = REQ_GRID; return REQ_GRID;
             }
             if (use_limit && !(have_ev && bt < limit)) { now = limit; return REQ_STOP; }
-            if (have_grid && have_ev && gt == bt && key_less(gt, WRSN_NORMAL, gs, bt, bp, bs)) {
-                const int uf = ev.uf;
-                if (uf & 2) { ff_sync_all(gt); ur_build(); }
-                *arg = 1; *t_lim_out = t_lim; *flags_out = uf & 1;
-                WRSN_PROF_EV(22, 1)
-                *pend_out = REQ_GRID; return REQ_GRID;            // tie at one instant: exactly one grid item goes first
-            }
+            // (a grid item AT the event's instant with the smaller key was taken above: the event is NORMAL then -- an URGENT one precedes
+            //  every grid item of its instant --, t_lim == bt here, so tie_ok held)
             now = bt; ev.fired++; ev.valid = 0;
             WRSN_P4_MARK(q10_) WRSN_P4_SPAN(10, q4_, q10_)
             if (kind == 3) {
@@ -2505,18 +2494,6 @@ __device__ __forceinline__ void wrsn_step_env(const WrsnDev* __restrict__ dp, in
     Sim<NPL, STOCH> s;
     s.bind(dp, env, lane, smem);
     if (handoff == 3) { s.t_deadline = t_end; s.t_exact = t_end - (deadline / 2 < WRSN_EXACT_MARGIN ? deadline / 2 : WRSN_EXACT_MARGIN); }   // the time-sliced launch stamped its start itself
-    else if (deadline > 0 && budget > 0 && !reset_call) {    // common deadline of the launch: `deadline` ticks after its first wave started
-        long long t0 = 0;
-        const long long tn = (long long)wall_clock64();      // wave-uniform (s_memrealtime)
-        if (lane == 0) {
-            const unsigned long long old = atomicCAS((unsigned long long*)dp->launch_t0, 0ull, (unsigned long long)tn);
-            t0 = old ? (long long)old : tn;
-        }
-        {   // lane 0's stamp for the whole wave (v_readlane: the other lanes hold nothing)
-            const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(t0 & 0xffffffffll), 0); const int hi = __builtin_amdgcn_readlane((int)(t0 >> 32), 0);
-            s.t_deadline = (((long long)hi << 32) | (long long)lo) + deadline;
-        }
-    }
 #ifdef WRSN_PROFILE
     for (int q_ = 0; q_ < 24; ++q_) s.prof_[q_] = 0;
     const long long kt0_ = clock64();
@@ -2822,7 +2799,6 @@ __global__ void __launch_bounds__(WRSN_SORT_THREADS) wrsn_sort_kernel(WrsnDev d,
     int* hist = (int*)smem; int* wsum = hist + NBK + 1;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     for (int i = tid; i <= NBK; i += T) hist[i] = 0;
-    if (tid == 0) *d.launch_t0 = 0;
     __syncthreads();
     unsigned key[K]; int bk[K];
 #pragma unroll
@@ -2852,7 +2828,8 @@ __global__ void __launch_bounds__(WRSN_SORT_THREADS) wrsn_sort_kernel(WrsnDev d,
             for (int j = 0; j < K; ++j) {
                 const int e = wave * 64 * K + j * 64 + lane;
                 if (e < BP2) { const int pos = atomicAdd(&hist[bk[j]], 1); d.order[pos] = (int)(key[j] & 0x1FFFu); }
-            }
+                __builtin_amdgcn_wave_barrier();             // the wave's 64 environments of one j before those of the next (no instruction: the
+            }                                                // lanes run in lockstep; the fibers of the CPU emulator of tests/emu do not)
         }
         __syncthreads();
     }

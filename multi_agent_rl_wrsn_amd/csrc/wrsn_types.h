@@ -112,8 +112,8 @@ struct WrsnDev {
     int32_t *order;                   // [BP2]  sorted ascending; order[b] = environment of block b (BP2 = B rounded up to a power of two)
     int32_t *row_state;               // [B]    what the last environment launch did with the row: 0 left untouched, 1 WRSN.step completed
                                       //        (fresh request), 2 reset / auto-reset request, 3 step still in flight, 4 terminal return
-    long long *launch_t0;             // [1]    wall clock (100 MHz) at which the first wave of the current step launch started; zeroed by the
-                                      //        sort kernel in front of it (wrsn_set_step_deadline)
+    long long *launch_t0;             // [1]    wall clock (100 MHz) at which the time slice of the current step launch started: stamped by
+                                      //        wrsn_latch_kernel in front of it, read by the blocks of a time-sliced launch (wrsn_set_step_deadline)
     // time-sliced launches: queue[1] = environment the cyclic order of this launch starts at, queue[8 + (b & 63)] = 1 + the last block b that
     // took its environment (spread over 64 words: one word is a serial point for thousands of starting blocks)
     int32_t *queue;                   // [8 + 64]

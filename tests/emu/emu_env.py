@@ -11,8 +11,13 @@ _EMU = None
 
 
 def emu_lib():
+    """The emulated library, built on demand -- or, as WRSN_HIP_LIB does for the product library, the build that WRSN_EMU_LIB names
+    (tools/emu_coverage.py points it at an instrumented one); a named build that is missing is an error, never a rebuild."""
     global _EMU
     if _EMU is None:
-        subprocess.check_call(["make", "-s", "-C", _HERE, "libwrsn_emu.so"])
-        _EMU = _lib.bind(C.CDLL(os.path.join(_HERE, "libwrsn_emu.so")))
+        path = os.environ.get("WRSN_EMU_LIB")
+        if not path:
+            subprocess.check_call(["make", "-s", "-C", _HERE, "libwrsn_emu.so"])
+            path = os.path.join(_HERE, "libwrsn_emu.so")
+        _EMU = _lib.bind(C.CDLL(path))
     return _EMU

@@ -10,7 +10,7 @@ of that module runs it on EmuSide and the test of the `_gpu` module (marked gpu)
     def test_x(...): body.x_matches(VecSide, ...)              # tests/test_x_gpu.py
 
 What a side offers: reset / step / view / decision / rows / density_action / render_state / save_envs / load_envs / clone_envs /
-set_pool / pool_reset / pool_info / entity_buffers / set_entity_out / entities / handle / close.  EmuVec puts the part of VecWRSN's
+set_pool / pool_reset / pool_info / out_ptrs / entity_buffers / set_entity_out / entities / handle / close.  EmuVec puts the part of VecWRSN's
 interface that the trainers of ippo.py use on top of an EmuSide."""
 import glob
 import os
@@ -169,6 +169,10 @@ class EmuSide(_Side):
     def _host(self):
         return {k: getattr(self, k).copy() for k in FIELDS}
 
+    def out_ptrs(self):
+        """Addresses of the request rows by field, and obs = 0: what the raw handle's calls take as their `out`."""
+        return self._ptrs(False)
+
     def obs_row(self, e):
         o = self.obs[e]
         if o.dtype == np.uint16:
@@ -295,6 +299,9 @@ class VecSide(_Side):
 
     def obs_row(self, e):
         return self.env.state[e].double().cpu().numpy()
+
+    def out_ptrs(self):
+        return dict(self.env._out_ptrs(), obs=0)
 
     def reset(self, mask=None):
         self.env.reset(None if mask is None else self._t(mask, np.uint8)); self.env.synchronize()

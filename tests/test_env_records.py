@@ -260,3 +260,44 @@ def test_record_format_version_1_is_pinned(hip_lib):
         magic, version = struct.unpack_from("<II", rec[0].tobytes(), 0)
         assert (magic, version) == (0x52534E57, 1), name
         assert struct.unpack_from("<iiq", rec[0].tobytes(), 48) == (has_gen, nseg, nbytes), name
+
+
+def clone_skips_the_request_fields_the_caller_leaves_out(Side):
+    """wrsn_clone_envs with NULL fields in `out` (wrsn_rec_rows_kernel: "NULL fields of `out` are skipped"): the environment is copied
+    whatever rows are given; a row that is given follows the source, one that is not keeps every byte -- here and on the device (the
+    body runs there from tests/test_env_records_gpu.py).  The reference is the numpy copy of the rows."""
+    from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, synth_scenario
+    scs = [synth_scenario(48000 + e, 30, 20) for e in range(4)]
+    side = Side(scs, DEFAULT_MC_SPEC, 2, map_size=8, render=False)
+    side.reset()
+    rng = np.random.RandomState(48)
+    for _ in range(2):
+        side.step(side._host()["agent_id"], rng.rand(4, 3) * [1.0, 1.0, 0.02])
+    before = side._host(); nodes = side.nodes()["energy"].copy()
+    assert len({float(before["now"][e]) for e in range(4)}) == 4 and not np.array_equal(nodes[0], nodes[2])   # the rows and states differ
+    ptrs = side.out_ptrs()
+    given = ("agent_id", "terminal", "status")
+    side.handle.clone_envs([0, 1], [2, 3], **{k: (v if k in given else 0) for k, v in ptrs.items()})
+    side.handle.sync()
+    after = side._host(); got = side.nodes()["energy"]
+    for k in before:
+        want = before[k].copy()
+        if k in given:
+            want[2:] = before[k][:2]
+        assert np.array_equal(after[k], want), (k, after[k], want)
+    assert np.array_equal(got[2:], nodes[:2]) and np.array_equal(got[:2], nodes[:2])
+    # the other way round: only the clock and the reward follow
+    side.handle.clone_envs([3], [0], **{k: (v if k in ("now", "reward") else 0) for k, v in ptrs.items()})
+    side.handle.sync()
+    last = side._host()
+    for k in after:
+        want = after[k].copy()
+        if k in ("now", "reward"):
+            want[0] = after[k][3]
+        assert np.array_equal(last[k], want), (k, last[k], want)
+    assert np.array_equal(side.nodes()["energy"][0], nodes[1])
+    side.close()
+
+
+def test_emulated_clone_skips_the_request_fields_the_caller_leaves_out(hip_lib):
+    clone_skips_the_request_fields_the_caller_leaves_out(EmuSide)

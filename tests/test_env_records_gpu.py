@@ -267,3 +267,9 @@ def test_facade_lookahead_restores_the_request(tmp_path):
             assert np.array_equal(x, y), k
         else:
             assert x == y, k
+
+
+def test_clone_skips_the_request_fields_the_caller_leaves_out():
+    import test_env_records as body
+    from sides import VecSide
+    body.clone_skips_the_request_fields_the_caller_leaves_out(VecSide)

@@ -311,8 +311,20 @@ def _tr_arrays(B, M, S, CAP, obs_dtype):
 def test_bf16_rollout_buffers_hold_the_observation_rows():
     """5. wrsn_rollout_record / wrsn_rollout_collect with bf16 buffers (a canary behind each): every stored state / next_state row is the
     bf16 observation row it was taken from; counts, rewards, now, env equal those of the same run in float32."""
+    _rollout_buffers_hold_the_observation_rows(12)
+
+
+def test_bf16_rollout_buffers_hold_rows_that_are_not_16_byte_aligned():
+    """5 at an odd map size: a bf16 row is 8 G^2 bytes, so every second row of the buffers starts 8 bytes past a 16-byte boundary and
+    the copy of wrsn_tr_copy goes element by element instead of in 16-byte accesses (no other roll-out test has such rows)."""
+    G = 7
+    assert (4 * G * G * 2) % 16 == 8
+    _rollout_buffers_hold_the_observation_rows(G)
+
+
+def _rollout_buffers_hold_the_observation_rows(G):
     from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, _lib, synth_scenario
-    B, M, G, CAP, K = 3, 2, 12, 64, 20
+    B, M, CAP, K = 3, 2, 64, 20
     S = 4 * G * G
     scs = [synth_scenario(300 + e, 70, 60) for e in range(B)]
     runs = {}

@@ -247,6 +247,16 @@ def test_bf16_reuse_and_format_switch_on_device():
 def test_bf16_transition_buffers_on_device():
     """11 / 5. TransitionBuffers of a bf16 environment (canaries behind the three state tensors) against the same run in float32: stored
     state / next_state rows are the rounded float32 rows; counts, rewards, now, env, actions, log-probabilities are equal."""
+    _transition_buffers_on_device(100)
+
+
+def test_bf16_transition_buffers_with_rows_that_are_not_16_byte_aligned_on_device():
+    """The same at an odd map size: every second bf16 row of the buffers starts 8 bytes past a 16-byte boundary, and the roll-out copies
+    go element by element."""
+    _transition_buffers_on_device(7)
+
+
+def _transition_buffers_on_device(G):
     torch = need_gpu()
     from multi_agent_rl_wrsn_amd import TransitionBuffers, VecWRSN, _lib, synth_scenario
     from test_ippo import _policy
@@ -254,7 +264,7 @@ def test_bf16_transition_buffers_on_device():
     scs = [synth_scenario(4300 + e, 100, 80) for e in range(B)]
     runs = []
     for dt in ("float32", "bfloat16"):
-        env = VecWRSN(scs, None, M, auto_reset=True, step_budget=200, obs_dtype=dt)
+        env = VecWRSN(scs, None, M, map_size=G, auto_reset=True, step_budget=200, obs_dtype=dt)
         buf = TransitionBuffers(env, CAP, 3)
         assert buf.state.dtype == env.state.dtype == buf.pend_state.dtype == buf.next_state.dtype
         raws = {}

@@ -7,6 +7,7 @@ reward, reward, observation, and the provenance of prev_minfit.
     instantiated for (1, 2, 4, 8, 16), 256 / 257 also being the switch of the level search from node-set masks to the pushed
     frontier; target counts on both sides of the 64-padding;
   * environments of different slot counts in one handle, blocking and budgeted;
+  * the pushed level search over a node that lives on the neighbour list (more than eight neighbours in a handle of more than 256 nodes);
   * tests/parity_sweep.py: whole episodes with masked resets, a table of cases per side.
 Where the two sides differ it is in size only: the emulator steps single environments with the residue hatch off (its seeds were kept
 because their runs need none), the device steps four networks per handle and allows the sweep's share of residue-dependent rewards."""
@@ -144,6 +145,28 @@ def d4_packet_cost_on_the_neighbour_list_path(Side):
     assert chk.n_cmp >= 6 and chk.n_noise == 0
 
 
+def pushed_level_search_takes_the_neighbour_list(Side):
+    """The level search of handles with more than 256 nodes is pushed from the frontier, and a frontier node with more than eight
+    neighbours pushes along its neighbour list instead of its packed words: the crowded relay (14 nodes) next to a 257-node network, whose
+    size puts the handle on that search.  Reset state and every request against the oracle -- the levels of the nine leaves come through
+    the relay alone."""
+    from multi_agent_rl_wrsn_amd import DEFAULT_MC_SPEC, synth_scenario
+    from wrsn_oracle import OracleWRSN
+    scs = [crowded_relay_scenario(), synth_scenario(SLOT_SEED + 57, 257, 129)]
+    sc = scs[0]
+    o = OracleWRSN(sc.node_xy, sc.target_xy, sc.bs_xy, sc.node_spec, DEFAULT_MC_SPEC, sc.max_time, 2); o.reset()
+    lv, deg = o.nodes()["level"], o.topology()["degree"]
+    # the branch is reached: a node on the neighbour list is on a frontier (it has a level) and is the only way to nodes one level up
+    assert max(s.n_node for s in scs) > 256 and deg[1] > 8 and lv[1] >= 1
+    d = np.sqrt(((sc.node_xy[:, None] - sc.node_xy[None]) ** 2).sum(2))
+    leaves = [i for i in range(2, 11) if lv[i] == lv[1] + 1 and not any(lv[j] == lv[1] and j != 1 and d[i, j] <= 100.0 for j in range(sc.n_node))]
+    assert len(leaves) == 9, (lv, leaves)
+    side = Side(scs, DEFAULT_MC_SPEC, 2)
+    chk, _ = run_requests(side, scs, DEFAULT_MC_SPEC, 2, K=8, seed=11, third=0.3, check_topology=True, hatch=Side.name == "gpu")
+    side.close()
+    assert chk.n_cmp >= 8 and chk.n_noise <= (0 if Side.name == "emu" else 2)
+
+
 RAGGED_BUDGETS = [0, 1250, 40]
 
 
@@ -204,6 +227,10 @@ def test_emulated_d4_packet_cost_matches_oracle(seed, n, t, hip_lib):
 
 def test_emulated_d4_packet_cost_on_the_neighbour_list_path(hip_lib):
     d4_packet_cost_on_the_neighbour_list_path(EmuSide)
+
+
+def test_emulated_pushed_level_search_takes_the_neighbour_list(hip_lib):
+    pushed_level_search_takes_the_neighbour_list(EmuSide)
 
 
 @pytest.mark.parametrize("budget", RAGGED_BUDGETS)

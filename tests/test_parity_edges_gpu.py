@@ -27,6 +27,10 @@ def test_d4_packet_cost_on_the_neighbour_list_path():
     body.d4_packet_cost_on_the_neighbour_list_path(VecSide)
 
 
+def test_pushed_level_search_takes_the_neighbour_list():
+    body.pushed_level_search_takes_the_neighbour_list(VecSide)
+
+
 @pytest.mark.parametrize("budget", body.RAGGED_BUDGETS)
 def test_ragged_slot_counts_in_one_handle_match_oracle(budget):
     body.ragged_slot_counts_in_one_handle_match_oracle(VecSide, budget)
