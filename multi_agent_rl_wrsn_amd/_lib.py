@@ -483,15 +483,21 @@ class RawHandle:
                                                   self._rows(rows_ptr, index_ptr, n, n_node, n_mc), C.c_void_p(mean or None),
                                                   C.c_void_p(log_std or None), C.c_void_p(value or None)))
 
+    def _ppo_grad(self, symbol, batch_cls, actor_ptr, critic_ptr, rows_ptr, index_ptr, n, n_node, n_mc, action, logp_old, advantage, ret, value_old,
+                  clip, ent_coef, vf_coef, norm_adv, clip_vloss, grad_actor, grad_critic, stats):
+        """The single-group PPO gradient `symbol`; batch_cls: WrsnPpoBatch or WrsnPointerBatch (one layout, `action` is its first field)."""
+        b = batch_cls(action or None, logp_old or None, advantage or None, ret or None, value_old or None)
+        hp = WrsnPpoHyper(float(clip), float(ent_coef), float(vf_coef), 1 if norm_adv else 0, 1 if clip_vloss else 0)
+        check(self.lib, getattr(self.lib, symbol)(self._h, C.c_void_p(actor_ptr or None), C.c_void_p(critic_ptr or None),
+                                                  self._rows(rows_ptr, index_ptr, n, n_node, n_mc), C.byref(b), C.byref(hp),
+                                                  C.c_void_p(grad_actor or None), C.c_void_p(grad_critic or None), C.c_void_p(stats or None)))
+
     def entity_ppo_grad(self, actor_ptr, critic_ptr, rows_ptr, index_ptr, n, n_node, n_mc, action, logp_old, advantage, ret, value_old,
                         clip, ent_coef, vf_coef, norm_adv, clip_vloss, grad_actor, grad_critic, stats):
         """wrsn_entity_ppo_grad: loss of PPOLearner.minibatch_loss on the n rows, d loss / d block into grad_actor / grad_critic (block
         layout, overwritten) and the statistics (float32 [8]: loss, pg, v_loss, entropy, approx_kl, clipfrac, 0, 0) into stats."""
-        b = WrsnPpoBatch(action or None, logp_old or None, advantage or None, ret or None, value_old or None)
-        hp = WrsnPpoHyper(float(clip), float(ent_coef), float(vf_coef), 1 if norm_adv else 0, 1 if clip_vloss else 0)
-        check(self.lib, self.lib.wrsn_entity_ppo_grad(self._h, C.c_void_p(actor_ptr or None), C.c_void_p(critic_ptr or None),
-                                                      self._rows(rows_ptr, index_ptr, n, n_node, n_mc), C.byref(b), C.byref(hp),
-                                                      C.c_void_p(grad_actor or None), C.c_void_p(grad_critic or None), C.c_void_p(stats or None)))
+        self._ppo_grad("wrsn_entity_ppo_grad", WrsnPpoBatch, actor_ptr, critic_ptr, rows_ptr, index_ptr, n, n_node, n_mc, action, logp_old, advantage,
+                       ret, value_old, clip, ent_coef, vf_coef, norm_adv, clip_vloss, grad_actor, grad_critic, stats)
 
     def entity_pointer_eval(self, actor_ptr, critic_ptr, rows_ptr, index_ptr, n, n_node, n_mc, stored=0, logp=0, entropy=0, node_logp=0,
                             charge_mean=0, charge_log_std=0, value=0):
@@ -504,12 +510,8 @@ class RawHandle:
     def entity_pointer_ppo_grad(self, actor_ptr, critic_ptr, rows_ptr, index_ptr, n, n_node, n_mc, stored, logp_old, advantage, ret, value_old,
                                 clip, ent_coef, vf_coef, norm_adv, clip_vloss, grad_actor, grad_critic, stats):
         """wrsn_entity_pointer_ppo_grad: `entity_ppo_grad` for the node-pointer actor (grad_actor: wrsn_entity_pointer_floats() floats)."""
-        b = WrsnPointerBatch(stored or None, logp_old or None, advantage or None, ret or None, value_old or None)
-        hp = WrsnPpoHyper(float(clip), float(ent_coef), float(vf_coef), 1 if norm_adv else 0, 1 if clip_vloss else 0)
-        check(self.lib, self.lib.wrsn_entity_pointer_ppo_grad(self._h, C.c_void_p(actor_ptr or None), C.c_void_p(critic_ptr or None),
-                                                              self._rows(rows_ptr, index_ptr, n, n_node, n_mc), C.byref(b), C.byref(hp),
-                                                              C.c_void_p(grad_actor or None), C.c_void_p(grad_critic or None),
-                                                              C.c_void_p(stats or None)))
+        self._ppo_grad("wrsn_entity_pointer_ppo_grad", WrsnPointerBatch, actor_ptr, critic_ptr, rows_ptr, index_ptr, n, n_node, n_mc, stored, logp_old,
+                       advantage, ret, value_old, clip, ent_coef, vf_coef, norm_adv, clip_vloss, grad_actor, grad_critic, stats)
 
     def entity_adam(self, param, grad, m, v, n_floats, step, lr, beta1=0.9, beta2=0.999, eps=1e-8, max_norm=0.5, norm_out=0):
         """wrsn_entity_adam: clip_grad_norm_(max_norm) then one torch.optim.Adam step, in place on the block of n_floats at `param`."""
@@ -518,17 +520,20 @@ class RawHandle:
                                                   float(max_norm), C.c_void_p(norm_out or None)))
 
     @staticmethod
-    def _groups(groups):
+    def _groups(groups, cls=WrsnEntityGroup):
         """A ctypes array of wrsn_entity_group from dicts of device addresses: actor, critic, m_actor, v_actor, m_critic, v_critic,
-        grad_actor, grad_critic, rows, action, logp_old, advantage, ret, value_old (absent or 0: NULL) and adam_step (default 0).  None: NULL."""
+        grad_actor, grad_critic, rows, action, logp_old, advantage, ret, value_old (absent or 0: NULL) and adam_step (default 0).  None: NULL.
+        cls=WrsnPrepareGroup: of wrsn_prepare_group, from dicts under its field names."""
         if groups is None:
             return None
-        arr = (WrsnEntityGroup * max(1, len(groups)))()
+        arr = (cls * max(1, len(groups)))()
         for q, g in zip(arr, groups):
-            for k in ("actor", "critic", "m_actor", "v_actor", "m_critic", "v_critic", "grad_actor", "grad_critic", "rows"):
-                setattr(q, k, g.get(k) or None)
-            q.batch = WrsnPpoBatch(*(g.get(k) or None for k in ("action", "logp_old", "advantage", "ret", "value_old")))
-            q.adam_step = int(g.get("adam_step", 0))
+            for k, t in cls._fields_:
+                if t is C.c_void_p:
+                    setattr(q, k, g.get(k) or None)
+            if cls is WrsnEntityGroup:
+                q.batch = WrsnPpoBatch(*(g.get(k) or None for k in ("action", "logp_old", "advantage", "ret", "value_old")))
+                q.adam_step = int(g.get("adam_step", 0))
         return arr
 
     @staticmethod
@@ -541,44 +546,47 @@ class RawHandle:
         return None if adam is None else C.byref(WrsnAdamHyper(float(adam["lr"]), float(adam.get("beta1", 0.9)), float(adam.get("beta2", 0.999)),
                                                                float(adam.get("eps", 1e-8)), float(adam["max_norm"])))
 
+    def _multi(self, symbol, groups, n_groups, *mid, cls=WrsnEntityGroup):
+        """One multi-group call `symbol`(handle, groups, n_groups, *mid); n_groups None: the call is told len(groups)."""
+        check(self.lib, getattr(self.lib, symbol)(self._h, self._groups(groups, cls),
+                                                  (0 if groups is None else len(groups)) if n_groups is None else int(n_groups), *mid))
+
+    def _grad_multi(self, symbol, groups, n, n_node, n_mc, index, what, stats, n_groups):
+        self._multi(symbol, groups, n_groups, int(n), int(n_node), int(n_mc), C.c_void_p(index or None), what, C.c_void_p(stats or None))
+
+    def _update(self, symbol, groups, n_node, n_mc, index, batch_size, minibatch, epochs, what, adam, stats, n_groups):
+        self._multi(symbol, groups, n_groups, int(n_node), int(n_mc), C.c_void_p(index or None), int(batch_size), int(minibatch), int(epochs), what,
+                    self._adam(adam), C.c_void_p(stats or None))
+
     def entity_ppo_grad_multi(self, groups, n, n_node, n_mc, index, hyper, stats, n_groups=None):
         """wrsn_entity_ppo_grad_multi: wrsn_entity_ppo_grad for every group (dicts, see `_groups`) in six launches; index: int32 [G][n] or 0,
         hyper: dict clip, ent_coef, vf_coef, norm_adv, clip_vloss; stats: float32 [G][8].  n_groups: what the call is told (default len)."""
-        check(self.lib, self.lib.wrsn_entity_ppo_grad_multi(self._h, self._groups(groups), len(groups) if n_groups is None else int(n_groups), int(n),
-                                                            int(n_node), int(n_mc), C.c_void_p(index or None), self._hyper(hyper),
-                                                            C.c_void_p(stats or None)))
+        self._grad_multi("wrsn_entity_ppo_grad_multi", groups, n, n_node, n_mc, index, self._hyper(hyper), stats, n_groups)
 
     def entity_adam_multi(self, groups, adam, n_groups=None):
         """wrsn_entity_adam_multi: clip_grad_norm_ and Adam on the 2 G blocks of the groups in two launches, group g at adam_step + 1.
         adam: dict lr, max_norm and optionally beta1, beta2, eps."""
-        check(self.lib, self.lib.wrsn_entity_adam_multi(self._h, self._groups(groups), len(groups) if n_groups is None else int(n_groups),
-                                                        self._adam(adam)))
+        self._multi("wrsn_entity_adam_multi", groups, n_groups, self._adam(adam))
 
     def entity_ppo_update(self, groups, n_node, n_mc, index, batch_size, minibatch, epochs, hyper, adam, stats, n_groups=None):
         """wrsn_entity_ppo_update: the whole of PPOLearner.update for the groups; index: int32 [G][epochs][batch_size], stats: float32
         [G][epochs * ceil(batch_size / minibatch)][8].  Only enqueues."""
-        check(self.lib, self.lib.wrsn_entity_ppo_update(self._h, self._groups(groups), len(groups) if n_groups is None else int(n_groups), int(n_node),
-                                                        int(n_mc), C.c_void_p(index or None), int(batch_size), int(minibatch), int(epochs),
-                                                        self._hyper(hyper), self._adam(adam), C.c_void_p(stats or None)))
+        self._update("wrsn_entity_ppo_update", groups, n_node, n_mc, index, batch_size, minibatch, epochs, self._hyper(hyper), adam, stats, n_groups)
 
     def entity_pointer_ppo_grad_multi(self, groups, n, n_node, n_mc, index, hyper, stats, n_groups=None):
         """wrsn_entity_pointer_ppo_grad_multi: `entity_ppo_grad_multi` for node-pointer actors in ten launches.  The groups' actor, m_actor,
         v_actor and grad_actor hold wrsn_entity_pointer_floats() floats, `action` is the [*, 2] stored pair."""
-        check(self.lib, self.lib.wrsn_entity_pointer_ppo_grad_multi(self._h, self._groups(groups), len(groups) if n_groups is None else int(n_groups),
-                                                                    int(n), int(n_node), int(n_mc), C.c_void_p(index or None), self._hyper(hyper),
-                                                                    C.c_void_p(stats or None)))
+        self._grad_multi("wrsn_entity_pointer_ppo_grad_multi", groups, n, n_node, n_mc, index, self._hyper(hyper), stats, n_groups)
 
     def entity_pointer_adam_multi(self, groups, adam, n_groups=None):
         """wrsn_entity_pointer_adam_multi: `entity_adam_multi` on pointer blocks (the actor's block: wrsn_entity_pointer_floats() floats)."""
-        check(self.lib, self.lib.wrsn_entity_pointer_adam_multi(self._h, self._groups(groups), len(groups) if n_groups is None else int(n_groups),
-                                                                self._adam(adam)))
+        self._multi("wrsn_entity_pointer_adam_multi", groups, n_groups, self._adam(adam))
 
     def entity_pointer_ppo_update(self, groups, n_node, n_mc, index, batch_size, minibatch, epochs, hyper, adam, stats, n_groups=None):
         """wrsn_entity_pointer_ppo_update: `entity_ppo_update` for node-pointer actors; index: int32 [G][epochs][batch_size], stats: float32
         [G][epochs * ceil(batch_size / minibatch)][8].  Only enqueues."""
-        check(self.lib, self.lib.wrsn_entity_pointer_ppo_update(self._h, self._groups(groups), len(groups) if n_groups is None else int(n_groups),
-                                                                int(n_node), int(n_mc), C.c_void_p(index or None), int(batch_size), int(minibatch),
-                                                                int(epochs), self._hyper(hyper), self._adam(adam), C.c_void_p(stats or None)))
+        self._update("wrsn_entity_pointer_ppo_update", groups, n_node, n_mc, index, batch_size, minibatch, epochs, self._hyper(hyper), adam, stats,
+                     n_groups)
 
     def entity_pointer_bc_grad(self, actor_ptr, rows_ptr, index_ptr, n, n_node, n_mc, stored, ent_coef, grad_actor, stats):
         """wrsn_entity_pointer_bc_grad: d / d block of -mean(logp) - ent_coef mean(H) of the stored pairs ([*, 2], indexed like the rows)
@@ -591,28 +599,18 @@ class RawHandle:
     def entity_pointer_bc_grad_multi(self, groups, n, n_node, n_mc, index, ent_coef, stats, n_groups=None):
         """wrsn_entity_pointer_bc_grad_multi: `entity_pointer_bc_grad` for every group (dicts, see `_groups`: actor, grad_actor, rows and
         `action`, the stored pairs, are read; the critic's side may be absent); index: int32 [G][n] or 0; stats: float32 [G][8]."""
-        check(self.lib, self.lib.wrsn_entity_pointer_bc_grad_multi(self._h, self._groups(groups), len(groups) if n_groups is None else int(n_groups),
-                                                                   int(n), int(n_node), int(n_mc), C.c_void_p(index or None), float(ent_coef),
-                                                                   C.c_void_p(stats or None)))
+        self._grad_multi("wrsn_entity_pointer_bc_grad_multi", groups, n, n_node, n_mc, index, float(ent_coef), stats, n_groups)
 
     def entity_pointer_bc_update(self, groups, n_node, n_mc, index, batch_size, minibatch, epochs, ent_coef, adam, stats, n_groups=None):
         """wrsn_entity_pointer_bc_update: epochs x ceil(batch_size / minibatch) steps of `entity_pointer_bc_grad_multi` and Adam on the actor
         blocks alone (group g at adam_step + 1 + k); index: int32 [G][epochs][batch_size], stats: float32 [G][steps][8].  Only enqueues."""
-        check(self.lib, self.lib.wrsn_entity_pointer_bc_update(self._h, self._groups(groups), len(groups) if n_groups is None else int(n_groups),
-                                                               int(n_node), int(n_mc), C.c_void_p(index or None), int(batch_size), int(minibatch),
-                                                               int(epochs), float(ent_coef), self._adam(adam), C.c_void_p(stats or None)))
+        self._update("wrsn_entity_pointer_bc_update", groups, n_node, n_mc, index, batch_size, minibatch, epochs, float(ent_coef), adam, stats, n_groups)
 
     def entity_prepare(self, groups, n, n_node, n_mc, index, gamma, gae_lambda, n_groups=None):
         """wrsn_entity_prepare: values, GAE and gathers of every group's batch in three launches.  groups: dicts of device addresses under
         the field names of wrsn_prepare_group (absent or 0: NULL), None: NULL; index: int32 [G][n] or 0.  n_groups: what the call is told."""
-        arr = None
-        if groups is not None:
-            arr = (WrsnPrepareGroup * max(1, len(groups)))()
-            for q, g in zip(arr, groups):
-                for k, _ in WrsnPrepareGroup._fields_:
-                    setattr(q, k, g.get(k) or None)
-        check(self.lib, self.lib.wrsn_entity_prepare(self._h, arr, (0 if groups is None else len(groups)) if n_groups is None else int(n_groups), int(n),
-                                                     int(n_node), int(n_mc), C.c_void_p(index or None), float(gamma), float(gae_lambda)))
+        self._multi("wrsn_entity_prepare", groups, n_groups, int(n), int(n_node), int(n_mc), C.c_void_p(index or None), float(gamma), float(gae_lambda),
+                    cls=WrsnPrepareGroup)
 
     def set_obs_reuse(self, on):
         check(self.lib, self.lib.wrsn_set_obs_reuse(self._h, 1 if on else 0))

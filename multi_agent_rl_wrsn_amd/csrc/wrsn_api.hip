@@ -1164,34 +1164,38 @@ WrsnEtHyper entity_hyper(const wrsn_ppo_hyper* hyper) {
     hp.clip_vloss = hyper->clip_vloss != 0;
     return hp;
 }
-// what is wrong with the G groups of a multi call, or nullptr.  batch: the gradient's inputs are needed; moments: Adam's
-const char* entity_groups_bad(const wrsn_entity_group* groups, int G, bool batch, bool moments) {
+// what is wrong with the G groups of a multi call, or nullptr.  batch: the gradient's inputs are needed; moments: Adam's; critic: the
+// call has a critic side (a call without one looks at the actor's side of a group alone, and of its batch at the stored pairs)
+const char* groups_bad(const wrsn_entity_group* groups, int G, bool batch, bool moments, bool critic) {
     if (G < 1 || G > WRSN_MAX_MC) return "n_groups must be in [1, 8]";
     if (!groups) return "groups is required";
     const void* named[WRSN_MAX_MC][8];
-    const int nn = moments ? 8 : 4;
+    const int sides = critic ? 2 : 1, per = moments ? 4 : 2, nn = sides * per;
     for (int g = 0; g < G; ++g) {
         const wrsn_entity_group& q = groups[g];
-        if (!q.actor || !q.critic || !q.grad_actor || !q.grad_critic) return "every group needs actor, critic, grad_actor and grad_critic";
-        if ((uintptr_t)q.actor % 16 || (uintptr_t)q.critic % 16 || (uintptr_t)q.grad_actor % 16 || (uintptr_t)q.grad_critic % 16)
+        if (!q.actor || !q.grad_actor || (critic && (!q.critic || !q.grad_critic)))
+            return critic ? "every group needs actor, critic, grad_actor and grad_critic" : "every group needs actor and grad_actor";
+        if ((uintptr_t)q.actor % 16 || (uintptr_t)q.grad_actor % 16 || (critic && ((uintptr_t)q.critic % 16 || (uintptr_t)q.grad_critic % 16)))
             return "blocks and gradient buffers must be 16-byte aligned";
         if (batch) {
-            if (!q.rows || !q.batch.action || !q.batch.logp_old || !q.batch.advantage || !q.batch.ret || !q.batch.value_old)
-                return "every group needs rows and every batch array";
+            if (!q.rows || !q.batch.action || (critic && (!q.batch.logp_old || !q.batch.advantage || !q.batch.ret || !q.batch.value_old)))
+                return critic ? "every group needs rows and every batch array" : "every group needs rows and the stored pairs (batch.action)";
             if ((uintptr_t)q.rows % 16) return "rows must be 16-byte aligned";
         }
         if (moments) {
-            if (!q.m_actor || !q.v_actor || !q.m_critic || !q.v_critic) return "every group needs m_actor, v_actor, m_critic and v_critic";
-            if ((uintptr_t)q.m_actor % 16 || (uintptr_t)q.v_actor % 16 || (uintptr_t)q.m_critic % 16 || (uintptr_t)q.v_critic % 16)
+            if (!q.m_actor || !q.v_actor || (critic && (!q.m_critic || !q.v_critic)))
+                return critic ? "every group needs m_actor, v_actor, m_critic and v_critic" : "every group needs m_actor and v_actor";
+            if ((uintptr_t)q.m_actor % 16 || (uintptr_t)q.v_actor % 16 || (critic && ((uintptr_t)q.m_critic % 16 || (uintptr_t)q.v_critic % 16)))
                 return "moments must be 16-byte aligned";
             if (q.adam_step < 0) return "adam_step must be >= 0";
         }
-        const void* mine[8] = {q.actor, q.critic, q.grad_actor, q.grad_critic, q.m_actor, q.v_actor, q.m_critic, q.v_critic};
-        for (int k = 0; k < nn; ++k) {
+        const void* mine[2][4] = {{q.actor, q.grad_actor, q.m_actor, q.v_actor}, {q.critic, q.grad_critic, q.m_critic, q.v_critic}};
+        for (int k = 0; k < nn; ++k) {                        // the 2, 4 or 8 buffers the call names: none of them in an earlier group
+            const void* mk = mine[k / per][k % per];
             for (int g2 = 0; g2 < g; ++g2)
                 for (int k2 = 0; k2 < nn; ++k2)
-                    if (named[g2][k2] == mine[k]) return "two groups name the same block, moment or gradient buffer";
-            named[g][k] = mine[k];
+                    if (named[g2][k2] == mk) return "two groups name the same block, moment or gradient buffer";
+            named[g][k] = mk;
         }
     }
     return nullptr;
@@ -1202,14 +1206,15 @@ const char* entity_dims_bad(int n, int n_node, int n_mc) {
     if (n_node < 1) return "n_node must be >= 1";
     return nullptr;
 }
-void entity_adam_table(const wrsn_entity_group* groups, int G, int step_offset, const wrsn_adam_hyper* a, WrsnEtAdamBlocks* bs,
-                       int actor_floats = WRSN_EP_FLOATS) {
-    for (int g = 0; g < G; ++g) {
-        const wrsn_entity_group& q = groups[g];
-        const int step = q.adam_step + 1 + step_offset;
-        entity_adam_block(bs, 2 * g, q.actor, q.grad_actor, q.m_actor, q.v_actor, nullptr, actor_floats, step, a->lr, a->beta1, a->beta2);
-        entity_adam_block(bs, 2 * g + 1, q.critic, q.grad_critic, q.m_critic, q.v_critic, nullptr, WRSN_EC_FLOATS, step, a->lr, a->beta1, a->beta2);
-    }
+WrsnEtDims dims_of(int n, int n_node, int n_mc) { WrsnEtDims dm; dm.n = n; dm.N = n_node; dm.M = n_mc; return dm; }
+// the table of a single-group call
+WrsnEtGroups one_group(const float* actor, const float* critic, const wrsn_entity_rows* rows, WrsnEtBatch b = WrsnEtBatch{}, float* grad_actor = nullptr,
+                       float* grad_critic = nullptr, float* stats = nullptr) {
+    WrsnEtGroups gs{};
+    WrsnEtGroup& G = gs.g[0];
+    G.actor = actor; G.critic = critic; G.grad_actor = grad_actor; G.grad_critic = grad_critic; G.rows = rows->rows; G.index = rows->index; G.b = b;
+    G.stats = stats;
+    return gs;
 }
 }  // namespace
 
@@ -1223,11 +1228,8 @@ int wrsn_entity_eval(wrsn_t* h, const float* actor, const float* critic, const w
     WRSN_ON_DEVICE(h);
     WrsnEtScratch s;
     { const int rc = entity_scratch(h, rows->n, false, 1, &s); if (rc) return rc; }
-    WrsnEtGroups gs{};
-    gs.g[0].actor = actor; gs.g[0].critic = critic; gs.g[0].rows = rows->rows; gs.g[0].index = rows->index;
-    WrsnEtDims dm; dm.n = rows->n; dm.N = rows->n_node; dm.M = rows->n_mc;
     WrsnEtEvalOut o; o.mean = mean; o.log_std = log_std; o.value = value;
-    entity_forward(h, gs, 1, dm, s, o);
+    entity_forward(h, one_group(actor, critic, rows), 1, dims_of(rows->n, rows->n_node, rows->n_mc), s, o);
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }
@@ -1243,12 +1245,9 @@ int wrsn_entity_ppo_grad(wrsn_t* h, const float* actor, const float* critic, con
         return fail(WRSN_ERR_ARG, "wrsn_entity_ppo_grad: blocks and gradient buffers must be 16-byte aligned");
     if (hyper->norm_adv && rows->n < 2) return fail(WRSN_ERR_ARG, "wrsn_entity_ppo_grad: norm_adv needs n >= 2");
     WRSN_ON_DEVICE(h);
-    WrsnEtGroups gs{};
-    WrsnEtGroup& G = gs.g[0];
-    G.actor = actor; G.critic = critic; G.grad_actor = grad_actor; G.grad_critic = grad_critic; G.rows = rows->rows; G.index = rows->index; G.stats = stats;
-    G.b.action = batch->action; G.b.logp_old = batch->logp_old; G.b.advantage = batch->advantage; G.b.ret = batch->ret; G.b.value_old = batch->value_old;
-    WrsnEtDims dm; dm.n = rows->n; dm.N = rows->n_node; dm.M = rows->n_mc;
-    if (const int rc = entity_grad_launch(h, gs, 1, dm, entity_hyper(hyper))) return rc;
+    const WrsnEtBatch b{batch->action, batch->logp_old, batch->advantage, batch->ret, batch->value_old};
+    const WrsnEtGroups gs = one_group(actor, critic, rows, b, grad_actor, grad_critic, stats);
+    if (const int rc = entity_grad_launch(h, gs, 1, dims_of(rows->n, rows->n_node, rows->n_mc), entity_hyper(hyper))) return rc;
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }
@@ -1315,243 +1314,6 @@ int pointer_grad_launch(wrsn_handle* h, const WrsnEtGroups& gs, int G, const Wrs
     hipLaunchKernelGGL(wrsn_etp_reduce_kernel, dim3(2 * G * ((WRSN_PP_FLOATS + 255) / 256)), dim3(256), 0, h->stream, gs, dm, s, ps);
     return 0;
 }
-}  // namespace
-
-int wrsn_entity_pointer_eval(wrsn_t* h, const float* actor, const float* critic, const wrsn_entity_rows* rows, const float* stored, float* logp,
-                             float* entropy, float* node_logp, float* charge_mean, float* charge_log_std, float* value) {
-    if (!h) return fail(WRSN_ERR_ARG, "null handle");
-    if (const char* bad = entity_rows_bad(rows)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_eval: ") + bad);
-    if (!actor && !critic) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_eval needs an actor or a critic");
-    if (actor && !stored) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_eval: an actor needs stored");
-    if ((actor && !logp && !entropy && !node_logp && !charge_mean && !charge_log_std) || (critic && !value))
-        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_eval: a net that is given needs an output");
-    if ((!actor && (logp || entropy || node_logp || charge_mean || charge_log_std)) || (!critic && value))
-        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_eval: outputs of a net that is not given must be NULL");
-    if ((uintptr_t)actor % 16 || (uintptr_t)critic % 16) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_eval: blocks must be 16-byte aligned");
-    if (WRSN_PP_SCORE_LDS(rows->n_node) > 65536) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_eval: too many nodes for the score block's LDS");
-    WRSN_ON_DEVICE(h);
-    WrsnEtScratch s; WrsnEtpScratch ps;
-    { const int rc = pointer_scratch(h, rows->n, rows->n_node, false, 1, &s, &ps); if (rc) return rc; }
-    WrsnEtGroups gs{};
-    gs.g[0].actor = actor; gs.g[0].critic = critic; gs.g[0].rows = rows->rows; gs.g[0].index = rows->index;
-    WrsnEtDims dm; dm.n = rows->n; dm.N = rows->n_node; dm.M = rows->n_mc;
-    WrsnEtpEvalOut o; o.logp = logp; o.entropy = entropy; o.node_logp = node_logp; o.charge_mean = charge_mean; o.charge_log_std = charge_log_std;
-    pointer_forward(h, gs, 1, dm, s, ps, stored, value, o, h->ptr_mask);
-    HIPCHK(hipGetLastError());
-    return WRSN_OK;
-}
-
-int wrsn_entity_pointer_ppo_grad(wrsn_t* h, const float* actor, const float* critic, const wrsn_entity_rows* rows, const wrsn_pointer_batch* batch,
-                                 const wrsn_ppo_hyper* hyper, float* grad_actor, float* grad_critic, float* stats) {
-    if (!h) return fail(WRSN_ERR_ARG, "null handle");
-    if (const char* bad = entity_rows_bad(rows)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_ppo_grad: ") + bad);
-    if (!actor || !critic || !batch || !hyper || !grad_actor || !grad_critic || !stats || !batch->stored || !batch->logp_old || !batch->advantage ||
-        !batch->ret || !batch->value_old)
-        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_grad needs actor, critic, every batch array, hyper, grad_actor, grad_critic and stats");
-    if ((uintptr_t)actor % 16 || (uintptr_t)critic % 16 || (uintptr_t)grad_actor % 16 || (uintptr_t)grad_critic % 16)
-        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_grad: blocks and gradient buffers must be 16-byte aligned");
-    if (hyper->norm_adv && rows->n < 2) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_grad: norm_adv needs n >= 2");
-    if (WRSN_ETP_BWD_LDS(rows->n_node) > 65536) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_grad: too many nodes for the score block's LDS");
-    WRSN_ON_DEVICE(h);
-    WrsnEtDims dm; dm.n = rows->n; dm.N = rows->n_node; dm.M = rows->n_mc;
-    WrsnEtGroups gs{};
-    WrsnEtGroup& G = gs.g[0];
-    G.actor = actor; G.critic = critic; G.grad_actor = grad_actor; G.grad_critic = grad_critic; G.rows = rows->rows; G.index = rows->index; G.stats = stats;
-    G.b.action = batch->stored; G.b.logp_old = batch->logp_old; G.b.advantage = batch->advantage; G.b.ret = batch->ret; G.b.value_old = batch->value_old;
-    if (const int rc = pointer_grad_launch(h, gs, 1, dm, entity_hyper(hyper), h->ptr_mask)) return rc;
-    HIPCHK(hipGetLastError());
-    return WRSN_OK;
-}
-
-namespace {
-// the device table of the groups for one step: minibatch rows index + g * index_stride (NULL: rows 0 .. n - 1), statistics stats + g * stats_stride
-void entity_group_table(const wrsn_entity_group* groups, int G, const int32_t* index, size_t index_stride, float* stats, size_t stats_stride,
-                        WrsnEtGroups* gs) {
-    for (int g = 0; g < G; ++g) {
-        const wrsn_entity_group& q = groups[g];
-        WrsnEtGroup& d = gs->g[g];
-        d.actor = q.actor; d.critic = q.critic; d.grad_actor = q.grad_actor; d.grad_critic = q.grad_critic; d.rows = q.rows;
-        d.index = index ? index + (size_t)g * index_stride : nullptr;
-        d.b.action = q.batch.action; d.b.logp_old = q.batch.logp_old; d.b.advantage = q.batch.advantage; d.b.ret = q.batch.ret;
-        d.b.value_old = q.batch.value_old;
-        d.stats = stats + (size_t)g * stats_stride;
-    }
-}
-}  // namespace
-
-int wrsn_entity_ppo_grad_multi(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, int32_t n, int32_t n_node, int32_t n_mc,
-                               const int32_t* index, const wrsn_ppo_hyper* hyper, float* stats) {
-    if (!h) return fail(WRSN_ERR_ARG, "null handle");
-    if (const char* bad = entity_groups_bad(groups, n_groups, true, false)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_ppo_grad_multi: ") + bad);
-    if (const char* bad = entity_dims_bad(n, n_node, n_mc)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_ppo_grad_multi: ") + bad);
-    if (!hyper || !stats) return fail(WRSN_ERR_ARG, "wrsn_entity_ppo_grad_multi needs hyper and stats");
-    if (hyper->norm_adv && n < 2) return fail(WRSN_ERR_ARG, "wrsn_entity_ppo_grad_multi: norm_adv needs n >= 2");
-    WRSN_ON_DEVICE(h);
-    WrsnEtGroups gs{};
-    entity_group_table(groups, n_groups, index, (size_t)n, stats, 8, &gs);
-    WrsnEtDims dm; dm.n = n; dm.N = n_node; dm.M = n_mc;
-    if (const int rc = entity_grad_launch(h, gs, n_groups, dm, entity_hyper(hyper))) return rc;
-    HIPCHK(hipGetLastError());
-    return WRSN_OK;
-}
-
-int wrsn_entity_adam_multi(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, const wrsn_adam_hyper* adam) {
-    if (!h) return fail(WRSN_ERR_ARG, "null handle");
-    if (const char* bad = entity_groups_bad(groups, n_groups, false, true)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_adam_multi: ") + bad);
-    if (!adam) return fail(WRSN_ERR_ARG, "wrsn_entity_adam_multi needs the Adam hyper-parameters");
-    WRSN_ON_DEVICE(h);
-    WrsnEtAdamBlocks bs{};
-    entity_adam_table(groups, n_groups, 0, adam, &bs);
-    if (const int rc = entity_adam_launch(h, bs, 2 * n_groups, WRSN_EP_FLOATS, adam->beta1, adam->beta2, adam->eps, adam->max_norm)) return rc;
-    HIPCHK(hipGetLastError());
-    return WRSN_OK;
-}
-
-int wrsn_entity_ppo_update(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, int32_t n_node, int32_t n_mc, const int32_t* index,
-                           int32_t batch_size, int32_t minibatch, int32_t epochs, const wrsn_ppo_hyper* hyper, const wrsn_adam_hyper* adam,
-                           float* stats) {
-    if (!h) return fail(WRSN_ERR_ARG, "null handle");
-    if (const char* bad = entity_groups_bad(groups, n_groups, true, true)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_ppo_update: ") + bad);
-    if (batch_size < 1 || minibatch < 1 || epochs < 1) return fail(WRSN_ERR_ARG, "wrsn_entity_ppo_update: batch_size, minibatch and epochs must be >= 1");
-    if (const char* bad = entity_dims_bad(batch_size, n_node, n_mc)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_ppo_update: ") + bad);
-    if (!index || !hyper || !adam || !stats) return fail(WRSN_ERR_ARG, "wrsn_entity_ppo_update needs index, hyper, adam and stats");
-    const int per_epoch = (int)(((int64_t)batch_size + minibatch - 1) / minibatch);
-    const int64_t steps64 = (int64_t)per_epoch * epochs;
-    if (steps64 > INT32_MAX) return fail(WRSN_ERR_ARG, "wrsn_entity_ppo_update: too many steps");
-    const int steps = (int)steps64, n_full = minibatch < batch_size ? minibatch : batch_size, n_last = batch_size - (per_epoch - 1) * minibatch;
-    if (hyper->norm_adv && (n_full < 2 || n_last < 2)) return fail(WRSN_ERR_ARG, "wrsn_entity_ppo_update: norm_adv needs every minibatch to hold >= 2 rows");
-    WRSN_ON_DEVICE(h);
-    {   // the scratch area of the largest step, so that no step of the loop allocates
-        WrsnEtScratch s;
-        const int rc = entity_scratch(h, n_full, true, n_groups, &s); if (rc) return rc;
-    }
-    const WrsnEtHyper hp = entity_hyper(hyper);
-    int k = 0;
-    for (int e = 0; e < epochs; ++e)
-        for (int start = 0; start < batch_size; start += minibatch, ++k) {   // only enqueues: nothing is read back, nothing synchronises
-            WrsnEtGroups gs{};
-            entity_group_table(groups, n_groups, index + (size_t)e * batch_size + start, (size_t)epochs * batch_size, stats + (size_t)k * 8, (size_t)steps * 8, &gs);
-            WrsnEtDims dm; dm.n = batch_size - start < minibatch ? batch_size - start : minibatch; dm.N = n_node; dm.M = n_mc;
-            if (const int rc = entity_grad_launch(h, gs, n_groups, dm, hp)) return rc;
-            WrsnEtAdamBlocks bs{};
-            entity_adam_table(groups, n_groups, k, adam, &bs);
-            if (const int rc = entity_adam_launch(h, bs, 2 * n_groups, WRSN_EP_FLOATS, adam->beta1, adam->beta2, adam->eps, adam->max_norm)) return rc;
-        }
-    HIPCHK(hipGetLastError());
-    return WRSN_OK;
-}
-
-// ------------------------------------------------------------------ the node-pointer policy's multi-group calls: as the three above, on
-// pointer blocks (WRSN_PP_FLOATS floats) and stored pairs, through pointer_grad_launch
-int wrsn_entity_pointer_ppo_grad_multi(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, int32_t n, int32_t n_node, int32_t n_mc,
-                                       const int32_t* index, const wrsn_ppo_hyper* hyper, float* stats) {
-    if (!h) return fail(WRSN_ERR_ARG, "null handle");
-    if (const char* bad = entity_groups_bad(groups, n_groups, true, false)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_ppo_grad_multi: ") + bad);
-    if (const char* bad = entity_dims_bad(n, n_node, n_mc)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_ppo_grad_multi: ") + bad);
-    if (!hyper || !stats) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_grad_multi needs hyper and stats");
-    if (hyper->norm_adv && n < 2) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_grad_multi: norm_adv needs n >= 2");
-    if (WRSN_ETP_BWD_LDS(n_node) > 65536) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_grad_multi: too many nodes for the score block's LDS");
-    WRSN_ON_DEVICE(h);
-    WrsnEtGroups gs{};
-    entity_group_table(groups, n_groups, index, (size_t)n, stats, 8, &gs);
-    WrsnEtDims dm; dm.n = n; dm.N = n_node; dm.M = n_mc;
-    if (const int rc = pointer_grad_launch(h, gs, n_groups, dm, entity_hyper(hyper), h->ptr_mask)) return rc;
-    HIPCHK(hipGetLastError());
-    return WRSN_OK;
-}
-
-int wrsn_entity_pointer_adam_multi(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, const wrsn_adam_hyper* adam) {
-    if (!h) return fail(WRSN_ERR_ARG, "null handle");
-    if (const char* bad = entity_groups_bad(groups, n_groups, false, true)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_adam_multi: ") + bad);
-    if (!adam) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_adam_multi needs the Adam hyper-parameters");
-    WRSN_ON_DEVICE(h);
-    WrsnEtAdamBlocks bs{};
-    entity_adam_table(groups, n_groups, 0, adam, &bs, WRSN_PP_FLOATS);
-    if (const int rc = entity_adam_launch(h, bs, 2 * n_groups, WRSN_PP_FLOATS, adam->beta1, adam->beta2, adam->eps, adam->max_norm)) return rc;
-    HIPCHK(hipGetLastError());
-    return WRSN_OK;
-}
-
-int wrsn_entity_pointer_ppo_update(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, int32_t n_node, int32_t n_mc, const int32_t* index,
-                                   int32_t batch_size, int32_t minibatch, int32_t epochs, const wrsn_ppo_hyper* hyper, const wrsn_adam_hyper* adam,
-                                   float* stats) {
-    if (!h) return fail(WRSN_ERR_ARG, "null handle");
-    if (const char* bad = entity_groups_bad(groups, n_groups, true, true)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_ppo_update: ") + bad);
-    if (batch_size < 1 || minibatch < 1 || epochs < 1)
-        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_update: batch_size, minibatch and epochs must be >= 1");
-    if (const char* bad = entity_dims_bad(batch_size, n_node, n_mc)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_ppo_update: ") + bad);
-    if (!index || !hyper || !adam || !stats) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_update needs index, hyper, adam and stats");
-    const int per_epoch = (int)(((int64_t)batch_size + minibatch - 1) / minibatch);
-    const int64_t steps64 = (int64_t)per_epoch * epochs;
-    if (steps64 > INT32_MAX) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_update: too many steps");
-    const int steps = (int)steps64, n_full = minibatch < batch_size ? minibatch : batch_size, n_last = batch_size - (per_epoch - 1) * minibatch;
-    if (hyper->norm_adv && (n_full < 2 || n_last < 2))
-        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_update: norm_adv needs every minibatch to hold >= 2 rows");
-    if (WRSN_ETP_BWD_LDS(n_node) > 65536) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_update: too many nodes for the score block's LDS");
-    WRSN_ON_DEVICE(h);
-    {   // the scratch area of the largest step, so that no step of the loop allocates
-        WrsnEtScratch s; WrsnEtpScratch ps;
-        const int rc = pointer_scratch(h, n_full, n_node, true, n_groups, &s, &ps); if (rc) return rc;
-    }
-    const WrsnEtHyper hp = entity_hyper(hyper);
-    const int mask = h->ptr_mask;                             // read once: every step of the loop under the same mask
-    int k = 0;
-    for (int e = 0; e < epochs; ++e)
-        for (int start = 0; start < batch_size; start += minibatch, ++k) {   // only enqueues: nothing is read back, nothing synchronises
-            WrsnEtGroups gs{};
-            entity_group_table(groups, n_groups, index + (size_t)e * batch_size + start, (size_t)epochs * batch_size, stats + (size_t)k * 8, (size_t)steps * 8, &gs);
-            WrsnEtDims dm; dm.n = batch_size - start < minibatch ? batch_size - start : minibatch; dm.N = n_node; dm.M = n_mc;
-            if (const int rc = pointer_grad_launch(h, gs, n_groups, dm, hp, mask)) return rc;
-            WrsnEtAdamBlocks bs{};
-            entity_adam_table(groups, n_groups, k, adam, &bs, WRSN_PP_FLOATS);
-            if (const int rc = entity_adam_launch(h, bs, 2 * n_groups, WRSN_PP_FLOATS, adam->beta1, adam->beta2, adam->eps, adam->max_norm)) return rc;
-        }
-    HIPCHK(hipGetLastError());
-    return WRSN_OK;
-}
-
-// ------------------------------------------------------------------ behaviour cloning of the node-pointer actor (wrsn_entity_pointer_train.h,
-// at its end): the PPO calls' kernels on a group table without critics, one new loss kernel, Adam on the actor blocks alone
-namespace {
-// what is wrong with the G groups of a behaviour-cloning call, or nullptr: only the actor's side of a group is looked at
-const char* bc_groups_bad(const wrsn_entity_group* groups, int G, bool batch, bool moments) {
-    if (G < 1 || G > WRSN_MAX_MC) return "n_groups must be in [1, 8]";
-    if (!groups) return "groups is required";
-    const void* named[WRSN_MAX_MC][4];
-    const int nn = moments ? 4 : 2;
-    for (int g = 0; g < G; ++g) {
-        const wrsn_entity_group& q = groups[g];
-        if (!q.actor || !q.grad_actor) return "every group needs actor and grad_actor";
-        if ((uintptr_t)q.actor % 16 || (uintptr_t)q.grad_actor % 16) return "blocks and gradient buffers must be 16-byte aligned";
-        if (batch) {
-            if (!q.rows || !q.batch.action) return "every group needs rows and the stored pairs (batch.action)";
-            if ((uintptr_t)q.rows % 16) return "rows must be 16-byte aligned";
-        }
-        if (moments) {
-            if (!q.m_actor || !q.v_actor) return "every group needs m_actor and v_actor";
-            if ((uintptr_t)q.m_actor % 16 || (uintptr_t)q.v_actor % 16) return "moments must be 16-byte aligned";
-            if (q.adam_step < 0) return "adam_step must be >= 0";
-        }
-        const void* mine[4] = {q.actor, q.grad_actor, q.m_actor, q.v_actor};
-        for (int k = 0; k < nn; ++k) {
-            for (int g2 = 0; g2 < g; ++g2)
-                for (int k2 = 0; k2 < nn; ++k2)
-                    if (named[g2][k2] == mine[k]) return "two groups name the same block, moment or gradient buffer";
-            named[g][k] = mine[k];
-        }
-    }
-    return nullptr;
-}
-// entity_group_table without the critics: no kernel of a behaviour-cloning call sees a critic, its gradient buffer or the PPO batch arrays
-void bc_group_table(const wrsn_entity_group* groups, int G, const int32_t* index, size_t index_stride, float* stats, size_t stats_stride, WrsnEtGroups* gs) {
-    for (int g = 0; g < G; ++g) {
-        const wrsn_entity_group& q = groups[g];
-        WrsnEtGroup& d = gs->g[g];
-        d.actor = q.actor; d.grad_actor = q.grad_actor; d.rows = q.rows; d.b.action = q.batch.action;
-        d.index = index ? index + (size_t)g * index_stride : nullptr;
-        d.stats = stats + (size_t)g * stats_stride;
-    }
-}
 // group g's slices of the two scratch areas, formed on the host (wrsn_et_slice / wrsn_etp_slice)
 WrsnEtScratch host_slice(WrsnEtScratch s, int g) {
     const size_t o = (size_t)g * s.chunk;
@@ -1587,15 +1349,50 @@ int pointer_bc_launch(wrsn_handle* h, const WrsnEtGroups& gs, int G, const WrsnE
     }
     return 0;
 }
-// the actor blocks of the groups as an Adam table of G entries, group g at adam_step + 1 + step_offset
-void bc_adam_table(const wrsn_entity_group* groups, int G, int step_offset, const wrsn_adam_hyper* a, WrsnEtAdamBlocks* bs) {
-    for (int g = 0; g < G; ++g) {
-        const wrsn_entity_group& q = groups[g];
-        entity_adam_block(bs, g, q.actor, q.grad_actor, q.m_actor, q.v_actor, nullptr, WRSN_PP_FLOATS, q.adam_step + 1 + step_offset, a->lr, a->beta1, a->beta2);
-    }
-}
 }  // namespace
 
+int wrsn_entity_pointer_eval(wrsn_t* h, const float* actor, const float* critic, const wrsn_entity_rows* rows, const float* stored, float* logp,
+                             float* entropy, float* node_logp, float* charge_mean, float* charge_log_std, float* value) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    if (const char* bad = entity_rows_bad(rows)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_eval: ") + bad);
+    if (!actor && !critic) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_eval needs an actor or a critic");
+    if (actor && !stored) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_eval: an actor needs stored");
+    if ((actor && !logp && !entropy && !node_logp && !charge_mean && !charge_log_std) || (critic && !value))
+        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_eval: a net that is given needs an output");
+    if ((!actor && (logp || entropy || node_logp || charge_mean || charge_log_std)) || (!critic && value))
+        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_eval: outputs of a net that is not given must be NULL");
+    if ((uintptr_t)actor % 16 || (uintptr_t)critic % 16) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_eval: blocks must be 16-byte aligned");
+    if (WRSN_PP_SCORE_LDS(rows->n_node) > 65536) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_eval: too many nodes for the score block's LDS");
+    WRSN_ON_DEVICE(h);
+    WrsnEtScratch s; WrsnEtpScratch ps;
+    { const int rc = pointer_scratch(h, rows->n, rows->n_node, false, 1, &s, &ps); if (rc) return rc; }
+    WrsnEtpEvalOut o; o.logp = logp; o.entropy = entropy; o.node_logp = node_logp; o.charge_mean = charge_mean; o.charge_log_std = charge_log_std;
+    pointer_forward(h, one_group(actor, critic, rows), 1, dims_of(rows->n, rows->n_node, rows->n_mc), s, ps, stored, value, o, h->ptr_mask);
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+int wrsn_entity_pointer_ppo_grad(wrsn_t* h, const float* actor, const float* critic, const wrsn_entity_rows* rows, const wrsn_pointer_batch* batch,
+                                 const wrsn_ppo_hyper* hyper, float* grad_actor, float* grad_critic, float* stats) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    if (const char* bad = entity_rows_bad(rows)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_ppo_grad: ") + bad);
+    if (!actor || !critic || !batch || !hyper || !grad_actor || !grad_critic || !stats || !batch->stored || !batch->logp_old || !batch->advantage ||
+        !batch->ret || !batch->value_old)
+        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_grad needs actor, critic, every batch array, hyper, grad_actor, grad_critic and stats");
+    if ((uintptr_t)actor % 16 || (uintptr_t)critic % 16 || (uintptr_t)grad_actor % 16 || (uintptr_t)grad_critic % 16)
+        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_grad: blocks and gradient buffers must be 16-byte aligned");
+    if (hyper->norm_adv && rows->n < 2) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_grad: norm_adv needs n >= 2");
+    if (WRSN_ETP_BWD_LDS(rows->n_node) > 65536) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_ppo_grad: too many nodes for the score block's LDS");
+    WRSN_ON_DEVICE(h);
+    const WrsnEtBatch b{batch->stored, batch->logp_old, batch->advantage, batch->ret, batch->value_old};
+    const WrsnEtGroups gs = one_group(actor, critic, rows, b, grad_actor, grad_critic, stats);
+    if (const int rc = pointer_grad_launch(h, gs, 1, dims_of(rows->n, rows->n_node, rows->n_mc), entity_hyper(hyper), h->ptr_mask)) return rc;
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+// ------------------------------------------------------------------ behaviour cloning of the node-pointer actor (wrsn_entity_pointer_train.h,
+// at its end): the PPO calls' kernels on a group table without critics, one new loss kernel, Adam on the actor blocks alone
 int wrsn_entity_pointer_bc_grad(wrsn_t* h, const float* actor, const wrsn_entity_rows* rows, const float* stored, float ent_coef, float* grad_actor,
                                 float* stats) {
     if (!h) return fail(WRSN_ERR_ARG, "null handle");
@@ -1606,66 +1403,181 @@ int wrsn_entity_pointer_bc_grad(wrsn_t* h, const float* actor, const wrsn_entity
     if (!std::isfinite(ent_coef)) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_grad: ent_coef must be finite");
     if (WRSN_ETP_BWD_LDS(rows->n_node) > 65536) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_grad: too many nodes for the score block's LDS");
     WRSN_ON_DEVICE(h);
-    WrsnEtDims dm; dm.n = rows->n; dm.N = rows->n_node; dm.M = rows->n_mc;
-    WrsnEtGroups gs{};
-    WrsnEtGroup& G = gs.g[0];
-    G.actor = actor; G.grad_actor = grad_actor; G.rows = rows->rows; G.index = rows->index; G.stats = stats; G.b.action = stored;
-    if (const int rc = pointer_bc_launch(h, gs, 1, dm, ent_coef, h->ptr_mask)) return rc;
+    WrsnEtBatch b{}; b.action = stored;
+    const WrsnEtGroups gs = one_group(actor, nullptr, rows, b, grad_actor, nullptr, stats);
+    if (const int rc = pointer_bc_launch(h, gs, 1, dims_of(rows->n, rows->n_node, rows->n_mc), ent_coef, h->ptr_mask)) return rc;
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }
 
-int wrsn_entity_pointer_bc_grad_multi(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, int32_t n, int32_t n_node, int32_t n_mc,
-                                      const int32_t* index, float ent_coef, float* stats) {
+// ------------------------------------------------------------------ the multi-group calls of the three training kinds: one host path
+namespace {
+// What tells the set policy's PPO, the node-pointer policy's PPO and the node-pointer actor's cloning apart on the host.  A new training
+// kind is a new entry here and a new case in grad_step.
+enum GradLaunch { GRAD_SET_PPO, GRAD_POINTER_PPO, GRAD_POINTER_BC };
+struct TrainKind {
+    int actor_floats;      // WRSN_EP_FLOATS (set block) or WRSN_PP_FLOATS (pointer block)
+    bool critic;           // the groups have a critic side and the call takes a wrsn_ppo_hyper; without: the actor alone and an ent_coef
+    GradLaunch grad;       // entity_grad_launch, pointer_grad_launch or pointer_bc_launch
+    bool lds_limit;        // n_node is bounded by the score block's LDS
+};
+const TrainKind SET_PPO{WRSN_EP_FLOATS, true, GRAD_SET_PPO, false}, POINTER_PPO{WRSN_PP_FLOATS, true, GRAD_POINTER_PPO, true},
+    POINTER_BC{WRSN_PP_FLOATS, false, GRAD_POINTER_BC, true};
+
+// one gradient step of G groups; hp: entity_hyper of the call's hyper, of a cloning call only its ent_coef
+int grad_step(wrsn_handle* h, const TrainKind& K, const WrsnEtGroups& gs, int G, const WrsnEtDims& dm, const WrsnEtHyper& hp, int mask) {
+    switch (K.grad) {
+    case GRAD_SET_PPO: return entity_grad_launch(h, gs, G, dm, hp);
+    case GRAD_POINTER_PPO: return pointer_grad_launch(h, gs, G, dm, hp, mask);
+    default: return pointer_bc_launch(h, gs, G, dm, hp.ent_coef, mask);
+    }
+}
+WrsnEtHyper kind_hyper(const TrainKind& K, const wrsn_ppo_hyper* hyper, float ent_coef) {
+    if (K.critic) return entity_hyper(hyper);
+    WrsnEtHyper hp{}; hp.ent_coef = ent_coef;
+    return hp;
+}
+// the device table of the groups for one step: minibatch rows index + g * index_stride (NULL: rows 0 .. n - 1), statistics stats + g *
+// stats_stride.  Without a critic no kernel sees a critic, its gradient buffer or the PPO batch arrays, whatever the caller's group names.
+void group_table(const TrainKind& K, const wrsn_entity_group* groups, int G, const int32_t* index, size_t index_stride, float* stats, size_t stats_stride,
+                 WrsnEtGroups* gs) {
+    for (int g = 0; g < G; ++g) {
+        const wrsn_entity_group& q = groups[g];
+        WrsnEtGroup& d = gs->g[g];
+        d.actor = q.actor; d.grad_actor = q.grad_actor; d.rows = q.rows; d.b.action = q.batch.action;
+        if (K.critic) {
+            d.critic = q.critic; d.grad_critic = q.grad_critic;
+            d.b.logp_old = q.batch.logp_old; d.b.advantage = q.batch.advantage; d.b.ret = q.batch.ret; d.b.value_old = q.batch.value_old;
+        }
+        d.index = index ? index + (size_t)g * index_stride : nullptr;
+        d.stats = stats + (size_t)g * stats_stride;
+    }
+}
+// the Adam table of the groups, group g at adam_step + 1 + step_offset, and its number of entries: with a critic 2 G, the actor at 2 g and
+// the critic at 2 g + 1; without, the G actor blocks
+int adam_table(const TrainKind& K, const wrsn_entity_group* groups, int G, int step_offset, const wrsn_adam_hyper* a, WrsnEtAdamBlocks* bs) {
+    const int per = K.critic ? 2 : 1;
+    for (int g = 0; g < G; ++g) {
+        const wrsn_entity_group& q = groups[g];
+        const int step = q.adam_step + 1 + step_offset;
+        entity_adam_block(bs, per * g, q.actor, q.grad_actor, q.m_actor, q.v_actor, nullptr, K.actor_floats, step, a->lr, a->beta1, a->beta2);
+        if (K.critic) entity_adam_block(bs, 2 * g + 1, q.critic, q.grad_critic, q.m_critic, q.v_critic, nullptr, WRSN_EC_FLOATS, step, a->lr, a->beta1, a->beta2);
+    }
+    return per * G;
+}
+int adam_step(wrsn_handle* h, const TrainKind& K, const wrsn_entity_group* groups, int G, int step_offset, const wrsn_adam_hyper* a) {
+    WrsnEtAdamBlocks bs{};
+    const int nb = adam_table(K, groups, G, step_offset, a, &bs);
+    return entity_adam_launch(h, bs, nb, K.actor_floats, a->beta1, a->beta2, a->eps, a->max_norm);
+}
+// the arguments a kind's calls share, beyond the groups: fn names the exported function in the messages
+int kind_args_bad(const TrainKind& K, const char* fn, int n, int n_node, int n_mc, float ent_coef) {
+    const std::string at = std::string(fn) + ": ";
+    if (const char* bad = entity_dims_bad(n, n_node, n_mc)) return fail(WRSN_ERR_ARG, at + bad);
+    if (!K.critic && !std::isfinite(ent_coef)) return fail(WRSN_ERR_ARG, at + "ent_coef must be finite");
+    if (K.lds_limit && WRSN_ETP_BWD_LDS(n_node) > 65536) return fail(WRSN_ERR_ARG, at + "too many nodes for the score block's LDS");
+    return 0;
+}
+
+int grad_multi(wrsn_t* h, const TrainKind& K, const char* fn, const wrsn_entity_group* groups, int n_groups, int n, int n_node, int n_mc,
+               const int32_t* index, const wrsn_ppo_hyper* hyper, float ent_coef, float* stats) {
     if (!h) return fail(WRSN_ERR_ARG, "null handle");
-    if (const char* bad = bc_groups_bad(groups, n_groups, true, false)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_bc_grad_multi: ") + bad);
-    if (const char* bad = entity_dims_bad(n, n_node, n_mc)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_bc_grad_multi: ") + bad);
-    if (!stats) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_grad_multi needs stats");
-    if (!std::isfinite(ent_coef)) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_grad_multi: ent_coef must be finite");
-    if (WRSN_ETP_BWD_LDS(n_node) > 65536) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_grad_multi: too many nodes for the score block's LDS");
+    const std::string at = std::string(fn) + ": ";
+    if (const char* bad = groups_bad(groups, n_groups, true, false, K.critic)) return fail(WRSN_ERR_ARG, at + bad);
+    if ((K.critic && !hyper) || !stats) return fail(WRSN_ERR_ARG, std::string(fn) + (K.critic ? " needs hyper and stats" : " needs stats"));
+    if (const int rc = kind_args_bad(K, fn, n, n_node, n_mc, ent_coef)) return rc;
+    if (K.critic && hyper->norm_adv && n < 2) return fail(WRSN_ERR_ARG, at + "norm_adv needs n >= 2");
     WRSN_ON_DEVICE(h);
     WrsnEtGroups gs{};
-    bc_group_table(groups, n_groups, index, (size_t)n, stats, 8, &gs);
-    WrsnEtDims dm; dm.n = n; dm.N = n_node; dm.M = n_mc;
-    if (const int rc = pointer_bc_launch(h, gs, n_groups, dm, ent_coef, h->ptr_mask)) return rc;
+    group_table(K, groups, n_groups, index, (size_t)n, stats, 8, &gs);
+    if (const int rc = grad_step(h, K, gs, n_groups, dims_of(n, n_node, n_mc), kind_hyper(K, hyper, ent_coef), h->ptr_mask)) return rc;
     HIPCHK(hipGetLastError());
     return WRSN_OK;
 }
 
-int wrsn_entity_pointer_bc_update(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, int32_t n_node, int32_t n_mc, const int32_t* index,
-                                  int32_t batch_size, int32_t minibatch, int32_t epochs, float ent_coef, const wrsn_adam_hyper* adam, float* stats) {
+int adam_multi(wrsn_t* h, const TrainKind& K, const char* fn, const wrsn_entity_group* groups, int n_groups, const wrsn_adam_hyper* adam) {
     if (!h) return fail(WRSN_ERR_ARG, "null handle");
-    if (const char* bad = bc_groups_bad(groups, n_groups, true, true)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_bc_update: ") + bad);
-    if (batch_size < 1 || minibatch < 1 || epochs < 1)
-        return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_update: batch_size, minibatch and epochs must be >= 1");
-    if (const char* bad = entity_dims_bad(batch_size, n_node, n_mc)) return fail(WRSN_ERR_ARG, std::string("wrsn_entity_pointer_bc_update: ") + bad);
-    if (!index || !adam || !stats) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_update needs index, adam and stats");
-    if (!std::isfinite(ent_coef)) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_update: ent_coef must be finite");
+    if (const char* bad = groups_bad(groups, n_groups, false, true, K.critic)) return fail(WRSN_ERR_ARG, std::string(fn) + ": " + bad);
+    if (!adam) return fail(WRSN_ERR_ARG, std::string(fn) + " needs the Adam hyper-parameters");
+    WRSN_ON_DEVICE(h);
+    if (const int rc = adam_step(h, K, groups, n_groups, 0, adam)) return rc;
+    HIPCHK(hipGetLastError());
+    return WRSN_OK;
+}
+
+// epochs x ceil(batch_size / minibatch) steps of gradient and Adam for every group: the whole of a kind's update call
+int update_loop(wrsn_t* h, const TrainKind& K, const char* fn, const wrsn_entity_group* groups, int n_groups, int n_node, int n_mc, const int32_t* index,
+                int batch_size, int minibatch, int epochs, const wrsn_ppo_hyper* hyper, float ent_coef, const wrsn_adam_hyper* adam, float* stats) {
+    if (!h) return fail(WRSN_ERR_ARG, "null handle");
+    const std::string at = std::string(fn) + ": ";
+    if (const char* bad = groups_bad(groups, n_groups, true, true, K.critic)) return fail(WRSN_ERR_ARG, at + bad);
+    if (batch_size < 1 || minibatch < 1 || epochs < 1) return fail(WRSN_ERR_ARG, at + "batch_size, minibatch and epochs must be >= 1");
+    if (!index || (K.critic && !hyper) || !adam || !stats)
+        return fail(WRSN_ERR_ARG, std::string(fn) + (K.critic ? " needs index, hyper, adam and stats" : " needs index, adam and stats"));
+    if (const int rc = kind_args_bad(K, fn, batch_size, n_node, n_mc, ent_coef)) return rc;
     const int per_epoch = (int)(((int64_t)batch_size + minibatch - 1) / minibatch);
     const int64_t steps64 = (int64_t)per_epoch * epochs;
-    if (steps64 > INT32_MAX) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_update: too many steps");
-    const int steps = (int)steps64, n_full = minibatch < batch_size ? minibatch : batch_size;
-    if (WRSN_ETP_BWD_LDS(n_node) > 65536) return fail(WRSN_ERR_ARG, "wrsn_entity_pointer_bc_update: too many nodes for the score block's LDS");
+    if (steps64 > INT32_MAX) return fail(WRSN_ERR_ARG, at + "too many steps");
+    const int steps = (int)steps64, n_full = minibatch < batch_size ? minibatch : batch_size, n_last = batch_size - (per_epoch - 1) * minibatch;
+    if (K.critic && hyper->norm_adv && (n_full < 2 || n_last < 2)) return fail(WRSN_ERR_ARG, at + "norm_adv needs every minibatch to hold >= 2 rows");
     WRSN_ON_DEVICE(h);
-    {   // the scratch area of the largest step, so that no step of the loop allocates
+    {   // the scratch area of the largest step and Adam's norms, so that no step of the loop allocates
         WrsnEtScratch s; WrsnEtpScratch ps;
-        const int rc = pointer_scratch(h, n_full, n_node, true, n_groups, &s, &ps); if (rc) return rc;
+        int rc = K.grad == GRAD_SET_PPO ? entity_scratch(h, n_full, true, n_groups, &s) : pointer_scratch(h, n_full, n_node, true, n_groups, &s, &ps);
+        if (!rc && !h->et_norm) rc = dalloc(h, &h->et_norm, (size_t)(2 * WRSN_MAX_MC));
+        if (rc) return rc;
     }
-    if (!h->et_norm) { const int rc = dalloc(h, &h->et_norm, (size_t)(2 * WRSN_MAX_MC)); if (rc) return rc; }
+    const WrsnEtHyper hp = kind_hyper(K, hyper, ent_coef);
     const int mask = h->ptr_mask;                             // read once: every step of the loop under the same mask
     int k = 0;
     for (int e = 0; e < epochs; ++e)
         for (int start = 0; start < batch_size; start += minibatch, ++k) {   // only enqueues: nothing is read back, nothing synchronises
             WrsnEtGroups gs{};
-            bc_group_table(groups, n_groups, index + (size_t)e * batch_size + start, (size_t)epochs * batch_size, stats + (size_t)k * 8, (size_t)steps * 8, &gs);
-            WrsnEtDims dm; dm.n = batch_size - start < minibatch ? batch_size - start : minibatch; dm.N = n_node; dm.M = n_mc;
-            if (const int rc = pointer_bc_launch(h, gs, n_groups, dm, ent_coef, mask)) return rc;
-            WrsnEtAdamBlocks bs{};
-            bc_adam_table(groups, n_groups, k, adam, &bs);
-            if (const int rc = entity_adam_launch(h, bs, n_groups, WRSN_PP_FLOATS, adam->beta1, adam->beta2, adam->eps, adam->max_norm)) return rc;
+            group_table(K, groups, n_groups, index + (size_t)e * batch_size + start, (size_t)epochs * batch_size, stats + (size_t)k * 8, (size_t)steps * 8, &gs);
+            const int n = batch_size - start < minibatch ? batch_size - start : minibatch;
+            if (const int rc = grad_step(h, K, gs, n_groups, dims_of(n, n_node, n_mc), hp, mask)) return rc;
+            if (const int rc = adam_step(h, K, groups, n_groups, k, adam)) return rc;
         }
     HIPCHK(hipGetLastError());
     return WRSN_OK;
+}
+}  // namespace
+
+int wrsn_entity_ppo_grad_multi(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, int32_t n, int32_t n_node, int32_t n_mc,
+                               const int32_t* index, const wrsn_ppo_hyper* hyper, float* stats) {
+    return grad_multi(h, SET_PPO, "wrsn_entity_ppo_grad_multi", groups, n_groups, n, n_node, n_mc, index, hyper, 0.f, stats);
+}
+int wrsn_entity_adam_multi(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, const wrsn_adam_hyper* adam) {
+    return adam_multi(h, SET_PPO, "wrsn_entity_adam_multi", groups, n_groups, adam);
+}
+int wrsn_entity_ppo_update(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, int32_t n_node, int32_t n_mc, const int32_t* index,
+                           int32_t batch_size, int32_t minibatch, int32_t epochs, const wrsn_ppo_hyper* hyper, const wrsn_adam_hyper* adam,
+                           float* stats) {
+    return update_loop(h, SET_PPO, "wrsn_entity_ppo_update", groups, n_groups, n_node, n_mc, index, batch_size, minibatch, epochs, hyper, 0.f, adam, stats);
+}
+
+int wrsn_entity_pointer_ppo_grad_multi(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, int32_t n, int32_t n_node, int32_t n_mc,
+                                       const int32_t* index, const wrsn_ppo_hyper* hyper, float* stats) {
+    return grad_multi(h, POINTER_PPO, "wrsn_entity_pointer_ppo_grad_multi", groups, n_groups, n, n_node, n_mc, index, hyper, 0.f, stats);
+}
+int wrsn_entity_pointer_adam_multi(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, const wrsn_adam_hyper* adam) {
+    return adam_multi(h, POINTER_PPO, "wrsn_entity_pointer_adam_multi", groups, n_groups, adam);
+}
+int wrsn_entity_pointer_ppo_update(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, int32_t n_node, int32_t n_mc, const int32_t* index,
+                                   int32_t batch_size, int32_t minibatch, int32_t epochs, const wrsn_ppo_hyper* hyper, const wrsn_adam_hyper* adam,
+                                   float* stats) {
+    return update_loop(h, POINTER_PPO, "wrsn_entity_pointer_ppo_update", groups, n_groups, n_node, n_mc, index, batch_size, minibatch, epochs, hyper, 0.f,
+                       adam, stats);
+}
+
+int wrsn_entity_pointer_bc_grad_multi(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, int32_t n, int32_t n_node, int32_t n_mc,
+                                      const int32_t* index, float ent_coef, float* stats) {
+    return grad_multi(h, POINTER_BC, "wrsn_entity_pointer_bc_grad_multi", groups, n_groups, n, n_node, n_mc, index, nullptr, ent_coef, stats);
+}
+int wrsn_entity_pointer_bc_update(wrsn_t* h, const wrsn_entity_group* groups, int32_t n_groups, int32_t n_node, int32_t n_mc, const int32_t* index,
+                                  int32_t batch_size, int32_t minibatch, int32_t epochs, float ent_coef, const wrsn_adam_hyper* adam, float* stats) {
+    return update_loop(h, POINTER_BC, "wrsn_entity_pointer_bc_update", groups, n_groups, n_node, n_mc, index, batch_size, minibatch, epochs, nullptr, ent_coef,
+                       adam, stats);
 }
 
 namespace {
@@ -1718,9 +1630,8 @@ int wrsn_entity_prepare(wrsn_t* h, const wrsn_prepare_group* groups, int32_t n_g
         p.value = q.value; p.advantage = q.advantage; p.ret = q.ret; p.out_state = q.out_state; p.out_next_state = q.out_next_state;
         p.out_action = q.out_action; p.out_logp = q.out_logp; p.out_reward = q.out_reward;
     }
-    WrsnEtDims dm; dm.n = n; dm.N = n_node; dm.M = n_mc;
     WrsnEtEvalOut o; o.mean = nullptr; o.log_std = nullptr; o.value = nullptr;
-    entity_forward(h, gs, 2 * G, dm, s, o);
+    entity_forward(h, gs, 2 * G, dims_of(n, n_node, n_mc), s, o);
     const int row_u4 = (WRSN_ENT_NODE_F * n_node + WRSN_ENT_MC_F * n_mc + WRSN_ENT_ENV_F) / 4;   // R is a multiple of 4 floats
     hipLaunchKernelGGL(wrsn_et_prepare_kernel, dim3((unsigned)G * ((unsigned)n + 1u)), dim3(256), WRSN_ET_PREP_LDS, h->stream, ps, (int)n, row_u4, index,
                        gamma, (float)((double)gamma * (double)gae_lambda), s);

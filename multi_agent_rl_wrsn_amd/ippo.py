@@ -1064,107 +1064,206 @@ class EntityPPOLearner(PPOLearner):
         return self.torch.stack([pack_entity_actor(a) for a in self.actors]).contiguous()
 
 
-def _fused_prepare_batches(self, width):
-    """The fused tail of `roll_out` for both entity trainers (fused_prepare): see `BatchedEntityIPPO`.  width: floats of a stored action.
-    3 (the set policy): `wrsn_entity_prepare` gathers the actions itself.  2 (the node-pointer policy): its `out_action` stays NULL and
-    the [M, batch_size, 2] stored pairs are gathered from `buffers.action` with the uploaded index by one torch gather on the device."""
-    torch, env, buf = self.torch, self.env, self.buffers
-    dev, M, bs = env.device, self.num_agent, self.batch_size
-    if not self.gae:                                      # the reference's plain branch raises (`cal_rt_adv`): the same, before any launch
-        raise IndexError("index %d is out of bounds for dimension 0 with size %d" % (bs, bs))
-    stored = buf.stored()
-    host = buf.reward[:, :max(stored)].cpu().numpy()      # the one host read
-    idx_np = np.empty((M, bs), dtype=np.int32)
-    for a in range(M):                                    # in charger order: the `np.random` stream of the default path
-        idx_np[a] = select_batch(host[a, :stored[a]], bs)
-    idx = torch.from_numpy(idx_np).to(dev)                # the one upload
-    critics = torch.stack([pack_entity_critic(c) for c in self.critics]).to(device=dev, dtype=torch.float32).contiguous()
-    new = lambda *sh: torch.empty((M, bs) + sh, dtype=torch.float32, device=dev)
-    R = buf.row_elems
-    o = dict(value=new(), advantage=new(), ret=new(), out_state=new(R), out_next_state=new(R))
-    if width == 3:
-        o["out_action"] = new(3)
-    o.update(out_logp=new(),
-             out_reward=torch.empty((M, (-bs) % 64 + bs), dtype=torch.float32, device=dev)[:, :bs])    # every charger's rewards start on a 256-byte boundary, as a tensor of their own would
-    groups = []
-    for a in range(M):
-        g = dict(critic=critics[a], state=buf.state[a], next_state=buf.next_state[a], reward=buf.reward[a], logp=buf.logp[a])
-        if width == 3:
-            g["action"] = buf.action[a]
-        g.update({k: v[a] for k, v in o.items()})
-        groups.append(g)
-    env.entity_prepare(groups, idx, self.gamma, self.gae_lambda)       # stored terminal flags are all 0: terminal = NULL
-    acts = o["out_action"] if width == 3 else buf.action.gather(1, idx.long().unsqueeze(2).expand(M, bs, width))
-    out = [dict(states=o["out_state"][a], actions=self._stored_actions(acts[a]), log_probs=o["out_logp"][a], rewards=o["out_reward"][a],
-                next_states=o["out_next_state"][a], advantages=o["advantage"][a], returns=o["ret"][a], values=o["value"][a]) for a in range(M)]
-    # the logged mean is torch's float32 reduction of the gathered rewards -- the default path's `float(rew.mean())` on the same floats
-    means = torch.stack([b["rewards"].mean() for b in out]).cpu()
-    for a in range(M):
-        self.loggers[a]["rewards"].append(float(means[a]))
-    return out
+class DeviceUpdateDriver(RolloutDriver):
+    """`RolloutDriver` for the two entity trainers, whose `update` may run on the device: the options' state, the block-layout Adam state and
+    gradient tensors, `_values`, `update` per charger, `update_all`, the fused `_prepare_batches` and the packing at the start of
+    `roll_out`.  The options are documented at the trainers.  A trainer says what differs:"""
 
+    _update_option = None                                      # the name of its public option: "fused_update" / "device_update"
+    _action_width = None                                       # floats of a stored action
+    _pack_actor = _unpack_actor = None                         # the actor's block layout (staticmethods); the critic's is pack_entity_critic
+    _pa, _pc = None, _lib.ENTITY_CRITIC_FLOATS                 # floats of the actor's and the critic's block
+    _env_calls = None                                          # the names of env's (gradient, gradient multi, Adam multi, update) calls
+    _critic_only = False                                       # `pretrain(critic_iters=...)`: `_update_charger` skips the actor's Adam call
 
-def _joint_update_all(self, batches, shuffle, width, pack_actor, unpack_actor, ppo_update, grad_multi, adam_multi):
-    """`update_all` of both entity trainers (joint_update): see `BatchedEntityIPPO.update_all`.  width: floats of a stored action;
-    pack_actor / unpack_actor: the actor's block layout; ppo_update, grad_multi, adam_multi: the three environment calls."""
-    self._packed = None
-    torch, env = self.torch, self.env
-    dev, M = env.device, self.num_agent
-    f32 = lambda x: x.to(device=dev, dtype=torch.float32).contiguous()
-    epochs, bs, mb = self.n_updates_per_iteration, self.batch_size, self.minibatch_size
-    per_epoch = (bs + mb - 1) // mb
-    steps = epochs * per_epoch
-    if self._grad_all is None:
-        self._grad_all = torch.zeros((M, self._pa + self._pc), dtype=torch.float32, device=dev)   # ONE tensor: what the exchange reduces
-    groups = []
-    for id in range(M):
-        batch, st = batches[id], self._adam[id]
-        b = {"actions": f32(batch["actions"]).reshape(-1, width), "log_probs": f32(batch["log_probs"]), "advantages": f32(batch["advantages"]),
+    def _init_options(self, env, fused_policy, on_device, joint_update, fused_prepare, log_episodes, episode_slots):
+        """The tail of both constructors, after `_attach`; on_device: the value of the `_update_option` argument."""
+        opt = self._update_option
+        self.log_episodes = bool(log_episodes)
+        if self.log_episodes:
+            self._ledger = env.new_episode_log(episode_slots, quota=0)
+        self.fused_policy = bool(fused_policy)
+        self._packed = None                                   # packed_actors() of the weights as they are now, or None: rebuilt before use
+        setattr(self, opt, bool(on_device))
+        self.joint_update = bool(joint_update)
+        self.fused_prepare = bool(fused_prepare)               # needs the device update: the values must be the HIP critic's for the two paths to agree
+        for k in ("joint_update", "fused_prepare"):
+            if getattr(self, k) and not on_device:
+                raise ValueError("%s=True needs %s=True" % (k, opt))
+        self._joint_per_step = False                          # tests: the per-step path of `update_all` (the data-parallel one) at world == 1
+        self.first_minibatch_stats = [None] * self.num_agent  # device update: (loss, pg, v_loss, entropy, approx_kl, clipfrac) of an update's first minibatch
+        if on_device:
+            z = lambda n: self.torch.zeros(n, dtype=self.torch.float32, device=env.device)
+            self._grad = z(self._pa + self._pc)               # ONE tensor: what the data-parallel exchange reduces
+            self._grad_all = None                             # joint_update: the same for every charger, [M, P_actor + P_critic], at first use
+            self._adam = [dict(m_a=z(self._pa), v_a=z(self._pa), m_c=z(self._pc), v_c=z(self._pc), step=0) for _ in range(self.num_agent)]
+
+    @property
+    def _on_device(self):
+        return getattr(self, self._update_option)
+
+    def roll_out(self, max_launches=100000, fresh_episodes=False):
+        if self.fused_policy:
+            self._packed = self.packed_actors()
+        return super().roll_out(max_launches, fresh_episodes)
+
+    def update(self, id, batch, shuffle=np.random.shuffle):
+        self._packed = None                                   # the weights change: never carried across an update
+        if self._on_device:
+            return self._update_charger(id, batch, shuffle)
+        return super().update(id, batch, shuffle)
+
+    def _values(self, agent_id, states):
+        if not self._on_device:
+            return super()._values(agent_id, states)
+        torch = self.torch
+        blk = pack_entity_critic(self.critics[agent_id]).to(self.env.device)
+        return self.env.entity_eval(states.to(torch.float32).contiguous(), critic=blk)[2]
+
+    def _update_charger(self, id, batch, shuffle):
+        """`PPOLearner.update` of one charger on the device: the same epochs, the same shuffles and minibatches, the same return value."""
+        torch, env = self.torch, self.env
+        ppo_grad = getattr(env, self._env_calls[0])
+        dev = env.device
+        f32 = lambda x: x.to(device=dev, dtype=torch.float32).contiguous()
+        blk_a, blk_c = f32(self._pack_actor(self.actors[id])), f32(pack_entity_critic(self.critics[id]))
+        rows = f32(batch["states"])
+        b = {"actions": f32(batch["actions"]).reshape(-1, self._action_width), "log_probs": f32(batch["log_probs"]), "advantages": f32(batch["advantages"]),
              "returns": f32(batch["returns"]), "values": f32(batch["values"])}
-        groups.append(dict(actor=f32(pack_actor(self.actors[id])), critic=f32(pack_entity_critic(self.critics[id])), grad=self._grad_all[id],
-                           rows=f32(batch["states"]), batch=b, m_a=st["m_a"], v_a=st["v_a"], m_c=st["m_c"], v_c=st["v_c"], step=st["step"]))
-    idx_np = np.empty((M, epochs, bs), dtype=np.int32)
-    for id in range(M):
-        b_inds = np.arange(bs)
-        for e in range(epochs):
-            shuffle(b_inds)
-            idx_np[id, e] = b_inds
-    idx = torch.from_numpy(idx_np).to(dev)                       # the one upload of the update
-    hyper = dict(clip=self.clip, ent_coef=self.ent_coef, vf_coef=self.vf_coef, norm_adv=self.norm_adv, clip_vloss=self.clip_vloss)
-    lr = self.args["lr"]
-    if self.world == 1 and not self._joint_per_step:
-        table = torch.zeros((M, steps, 8), dtype=torch.float32, device=dev)
-        ppo_update(groups, idx, mb, hyper, table, lr, self.max_grad_norm)
-        for st in self._adam:
-            st["step"] += steps
-    else:
-        by_step = torch.zeros((steps, M, 8), dtype=torch.float32, device=dev)
+        hyper = dict(clip=self.clip, ent_coef=self.ent_coef, vf_coef=self.vf_coef, norm_adv=self.norm_adv, clip_vloss=self.clip_vloss)
+        per_epoch = (self.batch_size + self.minibatch_size - 1) // self.minibatch_size
+        table = torch.zeros((self.n_updates_per_iteration * per_epoch, 8), dtype=torch.float32, device=dev)
+        st, ga, gc, lr = self._adam[id], self._grad[:self._pa], self._grad[self._pa:], self.args["lr"]
+        b_inds = np.arange(self.batch_size)
         k, keep = 0, []
-        for e in range(epochs):
-            for start in range(0, bs, mb):
-                mbi = idx[:, e, start:start + mb].contiguous()
-                keep.append(mbi)                                  # the launches are asynchronous: alive until the table is read
-                grad_multi(groups, mbi, hyper, by_step[k])
+        for _ in range(self.n_updates_per_iteration):
+            shuffle(b_inds)
+            idx = torch.from_numpy(b_inds.astype(np.int32)).to(dev)      # uploaded once per epoch
+            keep.append(idx)                                          # the launches are asynchronous: alive until the table is read
+            for start in range(0, self.batch_size, self.minibatch_size):
+                ppo_grad(blk_a, blk_c, rows, idx[start:start + self.minibatch_size], b, hyper, self._grad, table[k])
                 if self.world > 1:
-                    torch.distributed.all_reduce(self._grad_all, group=self.group)
-                    self._grad_all /= self.world
-                adam_multi(groups, lr, self.max_grad_norm)
-                for g, st in zip(groups, self._adam):
-                    st["step"] += 1; g["step"] = st["step"]
+                    torch.distributed.all_reduce(self._grad, group=self.group)
+                    self._grad /= self.world
+                st["step"] += 1
+                if not self._critic_only:                             # `pretrain(critic_iters=...)`: the actor's block and moments stay as they are
+                    env.entity_adam(blk_a, ga, st["m_a"], st["v_a"], st["step"], lr, self.max_grad_norm)
+                env.entity_adam(blk_c, gc, st["m_c"], st["v_c"], st["step"], lr, self.max_grad_norm)
                 k += 1
-        table = by_step.permute(1, 0, 2)
-    for id, g in enumerate(groups):
-        unpack_actor(g["actor"], self.actors[id]); unpack_entity_critic(g["critic"], self.critics[id])
-    t = table.cpu().numpy().astype(np.float64)                   # the one read of the update
-    out = []
-    for id in range(M):
-        self.loggers[id]["losses"].extend(float(x) for x in t[id, :, 0])
-        self.first_minibatch_stats[id] = tuple(float(x) for x in t[id, 0, :6])
-        out.append((float(t[id, -1, 1]), float(t[id, -1, 2]), float(t[id, -1, 3]), float(t[id, -1, 4]), float(np.mean(t[id, :, 5]))))
-    return out
+        self._unpack_actor(blk_a, self.actors[id]); unpack_entity_critic(blk_c, self.critics[id])
+        t = table.cpu().numpy().astype(np.float64)                   # the one read of the update
+        self.loggers[id]["losses"].extend(float(x) for x in t[:, 0])
+        self.first_minibatch_stats[id] = tuple(float(x) for x in t[0, :6])
+        return (float(t[-1, 1]), float(t[-1, 2]), float(t[-1, 3]), float(t[-1, 4]), float(np.mean(t[:, 5])))
+
+    def update_all(self, batches, shuffle=np.random.shuffle):
+        """`update(id, batches[id])` for every charger at once (joint_update): the list of the tuples `update` returns.  The shuffles are
+        drawn in the order the per-charger loop draws them (charger 0's epochs, then charger 1's, ...), so under one seed the two paths
+        give the same bytes.  One process: one index upload and one update call of the environment (`entity_ppo_update` /
+        `entity_pointer_ppo_update`).  Data-parallel (or `_joint_per_step`): per minibatch step one multi-group gradient call into one
+        flat [M (P_actor + P_critic)] tensor, one all-reduce of it, one multi-group Adam call."""
+        if not self.joint_update:
+            raise ValueError("update_all needs joint_update=True")
+        self._packed = None
+        torch, env = self.torch, self.env
+        _, grad_multi, adam_multi, ppo_update = (getattr(env, k) for k in self._env_calls)
+        dev, M = env.device, self.num_agent
+        f32 = lambda x: x.to(device=dev, dtype=torch.float32).contiguous()
+        epochs, bs, mb = self.n_updates_per_iteration, self.batch_size, self.minibatch_size
+        per_epoch = (bs + mb - 1) // mb
+        steps = epochs * per_epoch
+        if self._grad_all is None:
+            self._grad_all = torch.zeros((M, self._pa + self._pc), dtype=torch.float32, device=dev)   # ONE tensor: what the exchange reduces
+        groups = []
+        for id in range(M):
+            batch, st = batches[id], self._adam[id]
+            b = {"actions": f32(batch["actions"]).reshape(-1, self._action_width), "log_probs": f32(batch["log_probs"]), "advantages": f32(batch["advantages"]),
+                 "returns": f32(batch["returns"]), "values": f32(batch["values"])}
+            groups.append(dict(actor=f32(self._pack_actor(self.actors[id])), critic=f32(pack_entity_critic(self.critics[id])), grad=self._grad_all[id],
+                               rows=f32(batch["states"]), batch=b, m_a=st["m_a"], v_a=st["v_a"], m_c=st["m_c"], v_c=st["v_c"], step=st["step"]))
+        idx_np = np.empty((M, epochs, bs), dtype=np.int32)
+        for id in range(M):
+            b_inds = np.arange(bs)
+            for e in range(epochs):
+                shuffle(b_inds)
+                idx_np[id, e] = b_inds
+        idx = torch.from_numpy(idx_np).to(dev)                       # the one upload of the update
+        hyper = dict(clip=self.clip, ent_coef=self.ent_coef, vf_coef=self.vf_coef, norm_adv=self.norm_adv, clip_vloss=self.clip_vloss)
+        lr = self.args["lr"]
+        if self.world == 1 and not self._joint_per_step:
+            table = torch.zeros((M, steps, 8), dtype=torch.float32, device=dev)
+            ppo_update(groups, idx, mb, hyper, table, lr, self.max_grad_norm)
+            for st in self._adam:
+                st["step"] += steps
+        else:
+            by_step = torch.zeros((steps, M, 8), dtype=torch.float32, device=dev)
+            k, keep = 0, []
+            for e in range(epochs):
+                for start in range(0, bs, mb):
+                    mbi = idx[:, e, start:start + mb].contiguous()
+                    keep.append(mbi)                                  # the launches are asynchronous: alive until the table is read
+                    grad_multi(groups, mbi, hyper, by_step[k])
+                    if self.world > 1:
+                        torch.distributed.all_reduce(self._grad_all, group=self.group)
+                        self._grad_all /= self.world
+                    adam_multi(groups, lr, self.max_grad_norm)
+                    for g, st in zip(groups, self._adam):
+                        st["step"] += 1; g["step"] = st["step"]
+                    k += 1
+            table = by_step.permute(1, 0, 2)
+        for id, g in enumerate(groups):
+            self._unpack_actor(g["actor"], self.actors[id]); unpack_entity_critic(g["critic"], self.critics[id])
+        t = table.cpu().numpy().astype(np.float64)                   # the one read of the update
+        out = []
+        for id in range(M):
+            self.loggers[id]["losses"].extend(float(x) for x in t[id, :, 0])
+            self.first_minibatch_stats[id] = tuple(float(x) for x in t[id, 0, :6])
+            out.append((float(t[id, -1, 1]), float(t[id, -1, 2]), float(t[id, -1, 3]), float(t[id, -1, 4]), float(np.mean(t[id, :, 5]))))
+        return out
+
+    def _prepare_batches(self):
+        """With fused_prepare the tail of `roll_out` on the device.  Stored actions of 3 floats (the set policy): `wrsn_entity_prepare`
+        gathers the actions itself.  Of 2 (the node-pointer policy): its `out_action` stays NULL and the [M, batch_size, 2] stored pairs
+        are gathered from `buffers.action` with the uploaded index by one torch gather on the device."""
+        if not self.fused_prepare:
+            return super()._prepare_batches()
+        torch, env, buf, width = self.torch, self.env, self.buffers, self._action_width
+        dev, M, bs = env.device, self.num_agent, self.batch_size
+        if not self.gae:                                      # the reference's plain branch raises (`cal_rt_adv`): the same, before any launch
+            raise IndexError("index %d is out of bounds for dimension 0 with size %d" % (bs, bs))
+        stored = buf.stored()
+        host = buf.reward[:, :max(stored)].cpu().numpy()      # the one host read
+        idx_np = np.empty((M, bs), dtype=np.int32)
+        for a in range(M):                                    # in charger order: the `np.random` stream of the default path
+            idx_np[a] = select_batch(host[a, :stored[a]], bs)
+        idx = torch.from_numpy(idx_np).to(dev)                # the one upload
+        critics = torch.stack([pack_entity_critic(c) for c in self.critics]).to(device=dev, dtype=torch.float32).contiguous()
+        new = lambda *sh: torch.empty((M, bs) + sh, dtype=torch.float32, device=dev)
+        R = buf.row_elems
+        o = dict(value=new(), advantage=new(), ret=new(), out_state=new(R), out_next_state=new(R))
+        if width == 3:
+            o["out_action"] = new(3)
+        o.update(out_logp=new(),
+                 out_reward=torch.empty((M, (-bs) % 64 + bs), dtype=torch.float32, device=dev)[:, :bs])    # every charger's rewards start on a 256-byte boundary, as a tensor of their own would
+        groups = []
+        for a in range(M):
+            g = dict(critic=critics[a], state=buf.state[a], next_state=buf.next_state[a], reward=buf.reward[a], logp=buf.logp[a])
+            if width == 3:
+                g["action"] = buf.action[a]
+            g.update({k: v[a] for k, v in o.items()})
+            groups.append(g)
+        env.entity_prepare(groups, idx, self.gamma, self.gae_lambda)       # stored terminal flags are all 0: terminal = NULL
+        acts = o["out_action"] if width == 3 else buf.action.gather(1, idx.long().unsqueeze(2).expand(M, bs, width))
+        out = [dict(states=o["out_state"][a], actions=self._stored_actions(acts[a]), log_probs=o["out_logp"][a], rewards=o["out_reward"][a],
+                    next_states=o["out_next_state"][a], advantages=o["advantage"][a], returns=o["ret"][a], values=o["value"][a]) for a in range(M)]
+        # the logged mean is torch's float32 reduction of the gathered rewards -- the default path's `float(rew.mean())` on the same floats
+        means = torch.stack([b["rewards"].mean() for b in out]).cpu()
+        for a in range(M):
+            self.loggers[a]["rewards"].append(float(means[a]))
+        return out
 
 
-class BatchedEntityIPPO(RolloutDriver, EntityPPOLearner):
+class BatchedEntityIPPO(DeviceUpdateDriver, EntityPPOLearner):
     """The roll-out of `BatchedIPPO` on entity rows: `VecWRSN(entities=True)` (no image needed: `render=False`), the set policy's
     3-vector is the action `env.step` takes, and the transitions live in `EntityTransitionBuffers`.
 
@@ -1197,6 +1296,9 @@ class BatchedEntityIPPO(RolloutDriver, EntityPPOLearner):
     `evaluate` itself is the reference's `evaluate(agent, states, actions)` of the learner)."""
 
     _check_status = True
+    _update_option, _action_width, _pa = "fused_update", 3, _lib.ENTITY_ACTOR_FLOATS
+    _pack_actor, _unpack_actor = staticmethod(pack_entity_actor), staticmethod(unpack_entity_actor)
+    _env_calls = ("entity_ppo_grad", "entity_ppo_grad_multi", "entity_adam_multi", "entity_ppo_update")
 
     def __init__(self, args, env, device=None, model_path=None, capacity=None, infer_chunk=1024, process_group=None, log=None, min_bucket=16,
                  fused_policy=False, fused_update=False, joint_update=False, fused_prepare=False, log_episodes=False, episode_slots=64):
@@ -1204,27 +1306,7 @@ class BatchedEntityIPPO(RolloutDriver, EntityPPOLearner):
             raise ValueError("BatchedEntityIPPO needs a VecWRSN with the entity observation (entities=True)")
         super().__init__(args, env.num_agent, device if device is not None else env.device, model_path, infer_chunk, process_group, min_bucket)
         self._attach(env, EntityTransitionBuffers(env, capacity or 2 * self.batch_size, 3), log)
-        self.log_episodes = bool(log_episodes)
-        if self.log_episodes:
-            self._ledger = env.new_episode_log(episode_slots, quota=0)
-        self.fused_policy = bool(fused_policy)
-        self._packed = None                                   # packed_actors() of the weights as they are now, or None: rebuilt before use
-        self.fused_update = bool(fused_update)
-        self.joint_update = bool(joint_update)
-        if self.joint_update and not self.fused_update:
-            raise ValueError("joint_update=True needs fused_update=True")
-        self.fused_prepare = bool(fused_prepare)
-        if self.fused_prepare and not self.fused_update:
-            raise ValueError("fused_prepare=True needs fused_update=True")
-        self._joint_per_step = False                          # tests: the per-step path of `update_all` (the data-parallel one) at world == 1
-        self.first_minibatch_stats = [None] * self.num_agent  # fused_update: (loss, pg, v_loss, entropy, approx_kl, clipfrac) of an update's first minibatch
-        if self.fused_update:
-            torch = self.torch
-            self._pa, self._pc = _lib.ENTITY_ACTOR_FLOATS, _lib.ENTITY_CRITIC_FLOATS
-            z = lambda n: torch.zeros(n, dtype=torch.float32, device=env.device)
-            self._grad = z(self._pa + self._pc)               # ONE tensor: what the data-parallel exchange reduces
-            self._grad_all = None                             # joint_update: the same for every charger, [M, P_actor + P_critic], at first use
-            self._adam = [dict(m_a=z(self._pa), v_a=z(self._pa), m_c=z(self._pc), v_c=z(self._pc), step=0) for _ in range(self.num_agent)]
+        self._init_options(env, fused_policy, fused_update, joint_update, fused_prepare, log_episodes, episode_slots)
 
     def evaluate_episodes(self, eval_env, episodes=1, deterministic=True, generator=None, **kw):
         """`evaluate_policy` of the actors as they are now -- their mode, or with deterministic=False a sample per decision -- on
@@ -1234,75 +1316,6 @@ class BatchedEntityIPPO(RolloutDriver, EntityPPOLearner):
         if eval_env is self.env:
             raise ValueError("evaluate on a batch of its own: the trainer's environments live across roll-outs")
         return evaluate_policy(eval_env, EntityPolicy(self.packed_actors(), deterministic, generator), episodes, **kw)
-
-    def roll_out(self, max_launches=100000, fresh_episodes=False):
-        if self.fused_policy:
-            self._packed = self.packed_actors()
-        return super().roll_out(max_launches, fresh_episodes)
-
-    def _prepare_batches(self):
-        if not self.fused_prepare:
-            return super()._prepare_batches()
-        return _fused_prepare_batches(self, 3)
-
-    def update(self, id, batch, shuffle=np.random.shuffle):
-        self._packed = None                                   # the weights change: never carried across an update
-        if self.fused_update:
-            return self._update_fused(id, batch, shuffle)
-        return super().update(id, batch, shuffle)
-
-    def _values(self, agent_id, states):
-        if not self.fused_update:
-            return super()._values(agent_id, states)
-        torch = self.torch
-        blk = pack_entity_critic(self.critics[agent_id]).to(self.env.device)
-        return self.env.entity_eval(states.to(torch.float32).contiguous(), critic=blk)[2]
-
-    def _update_fused(self, id, batch, shuffle):
-        """`PPOLearner.update` on the device: the same epochs, the same shuffles and minibatches, the same return value."""
-        torch, env = self.torch, self.env
-        dev = env.device
-        f32 = lambda x: x.to(device=dev, dtype=torch.float32).contiguous()
-        blk_a, blk_c = f32(pack_entity_actor(self.actors[id])), f32(pack_entity_critic(self.critics[id]))
-        rows = f32(batch["states"])
-        b = {"actions": f32(batch["actions"]).reshape(-1, 3), "log_probs": f32(batch["log_probs"]), "advantages": f32(batch["advantages"]),
-             "returns": f32(batch["returns"]), "values": f32(batch["values"])}
-        hyper = dict(clip=self.clip, ent_coef=self.ent_coef, vf_coef=self.vf_coef, norm_adv=self.norm_adv, clip_vloss=self.clip_vloss)
-        per_epoch = (self.batch_size + self.minibatch_size - 1) // self.minibatch_size
-        table = torch.zeros((self.n_updates_per_iteration * per_epoch, 8), dtype=torch.float32, device=dev)
-        st, ga, gc, lr = self._adam[id], self._grad[:self._pa], self._grad[self._pa:], self.args["lr"]
-        b_inds = np.arange(self.batch_size)
-        k, keep = 0, []
-        for _ in range(self.n_updates_per_iteration):
-            shuffle(b_inds)
-            idx = torch.from_numpy(b_inds.astype(np.int32)).to(dev)      # uploaded once per epoch
-            keep.append(idx)                                          # the launches are asynchronous: alive until the table is read
-            for start in range(0, self.batch_size, self.minibatch_size):
-                env.entity_ppo_grad(blk_a, blk_c, rows, idx[start:start + self.minibatch_size], b, hyper, self._grad, table[k])
-                if self.world > 1:
-                    torch.distributed.all_reduce(self._grad, group=self.group)
-                    self._grad /= self.world
-                st["step"] += 1
-                env.entity_adam(blk_a, ga, st["m_a"], st["v_a"], st["step"], lr, self.max_grad_norm)
-                env.entity_adam(blk_c, gc, st["m_c"], st["v_c"], st["step"], lr, self.max_grad_norm)
-                k += 1
-        unpack_entity_actor(blk_a, self.actors[id]); unpack_entity_critic(blk_c, self.critics[id])
-        t = table.cpu().numpy().astype(np.float64)                   # the one read of the update
-        self.loggers[id]["losses"].extend(float(x) for x in t[:, 0])
-        self.first_minibatch_stats[id] = tuple(float(x) for x in t[0, :6])
-        return (float(t[-1, 1]), float(t[-1, 2]), float(t[-1, 3]), float(t[-1, 4]), float(np.mean(t[:, 5])))
-
-    def update_all(self, batches, shuffle=np.random.shuffle):
-        """`update(id, batches[id])` for every charger at once (joint_update): the list of the tuples `update` returns.  The shuffles are
-        drawn in the order the per-charger loop draws them (charger 0's epochs, then charger 1's, ...), so under one seed the two paths
-        give the same bytes.  One process: one index upload and one `entity_ppo_update` call.  Data-parallel (or `_joint_per_step`):
-        per minibatch step one `entity_ppo_grad_multi` into one flat [M (P_actor + P_critic)] tensor, one all-reduce of it, one
-        `entity_adam_multi`."""
-        if not self.joint_update:
-            raise ValueError("update_all needs joint_update=True")
-        env = self.env
-        return _joint_update_all(self, batches, shuffle, 3, pack_entity_actor, unpack_entity_actor, env.entity_ppo_update,
-                                 env.entity_ppo_grad_multi, env.entity_adam_multi)
 
     def _choose(self, r, ids):
         if not self.fused_policy:
@@ -1354,7 +1367,7 @@ class EntityPointerPPOLearner(EntityPPOLearner):
         return self.torch.stack([pack_entity_pointer_actor(a) for a in self.actors]).contiguous()
 
 
-class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
+class BatchedEntityPointerIPPO(DeviceUpdateDriver, EntityPointerPPOLearner):
     """The roll-out of `BatchedEntityIPPO` with the node-pointer policy: `VecWRSN(entities=True)`, transitions in
     `EntityTransitionBuffers(action_elems=2)` -- (node, x) per decision --, the PyTorch update of `PPOLearner`.
 
@@ -1395,6 +1408,9 @@ class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
     `fused_update` is the set policy's option (BatchedEntityIPPO) and always raises here: this actor's is `device_update`."""
 
     _check_status = True
+    _update_option, _action_width, _pa = "device_update", 2, _lib.ENTITY_POINTER_FLOATS
+    _pack_actor, _unpack_actor = staticmethod(pack_entity_pointer_actor), staticmethod(unpack_entity_pointer_actor)
+    _env_calls = ("entity_pointer_ppo_grad", "entity_pointer_ppo_grad_multi", "entity_pointer_adam_multi", "entity_pointer_ppo_update")
 
     def __init__(self, args, env, device=None, model_path=None, capacity=None, infer_chunk=1024, process_group=None, log=None, min_bucket=16,
                  min_charge=0.02, fused_policy=False, log_episodes=False, episode_slots=64, fused_update=False, joint_update=False,
@@ -1402,9 +1418,6 @@ class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
         if fused_update:
             raise ValueError("BatchedEntityPointerIPPO has no fused_update: that is the Gaussian set policy's option (BatchedEntityIPPO); "
                              "this actor's is device_update")
-        for k, v in (("joint_update", joint_update), ("fused_prepare", fused_prepare)):
-            if v and not device_update:
-                raise ValueError("%s=True needs device_update=True" % k)
         if not getattr(env, "entities", False):
             raise ValueError("BatchedEntityPointerIPPO needs a VecWRSN with the entity observation (entities=True)")
         if not 0.0 <= float(min_charge) < 1.0:
@@ -1414,25 +1427,8 @@ class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
         self._attach(env, EntityTransitionBuffers(env, capacity or 2 * self.batch_size, 2), log)
         env._h.set_entity_pointer_mask(_lib.POINTER_MASK_CLAIMED if self.mask_claimed else _lib.POINTER_MASK_NONE)   # `VecWRSN.set_entity_pointer_mask`
         self.min_charge = float(min_charge)
-        self.log_episodes = bool(log_episodes)
-        if self.log_episodes:
-            self._ledger = env.new_episode_log(episode_slots, quota=0)
-        self.fused_policy = bool(fused_policy)
-        self._packed = None                                   # packed_actors() of the weights as they are now, or None: rebuilt before use
-        self.device_update = bool(device_update)
-        self.joint_update = bool(joint_update)
-        self.fused_prepare = bool(fused_prepare)
-        self._joint_per_step = False                          # tests: the per-step path of `update_all` (the data-parallel one) at world == 1
-        self.first_minibatch_stats = [None] * self.num_agent  # device_update: (loss, pg, v_loss, entropy, approx_kl, clipfrac) of an update's first minibatch
         self._bc = None                                       # `pretrain`: the imitation settings while it collects, else None
-        self._critic_only = False                             # `pretrain(critic_iters=...)`: `_update_device` skips the actor's Adam call
-        if self.device_update:
-            torch = self.torch
-            self._pa, self._pc = _lib.ENTITY_POINTER_FLOATS, _lib.ENTITY_CRITIC_FLOATS
-            z = lambda n: torch.zeros(n, dtype=torch.float32, device=env.device)
-            self._grad = z(self._pa + self._pc)               # ONE tensor: what the data-parallel exchange reduces
-            self._grad_all = None                             # joint_update: the same for every charger, [M, P_pointer + P_critic], at first use
-            self._adam = [dict(m_a=z(self._pa), v_a=z(self._pa), m_c=z(self._pc), v_c=z(self._pc), step=0) for _ in range(self.num_agent)]
+        self._init_options(env, fused_policy, device_update, joint_update, fused_prepare, log_episodes, episode_slots)
 
     def evaluate_episodes(self, eval_env, episodes=1, deterministic=True, generator=None, **kw):
         """`evaluate_policy` of the actors as they are now (`evaluate.PointerPolicy`) on `eval_env`, another batch than the trainer's."""
@@ -1441,75 +1437,6 @@ class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
             raise ValueError("evaluate on a batch of its own: the trainer's environments live across roll-outs")
         return evaluate_policy(eval_env, PointerPolicy(self.packed_actors(), deterministic, generator, self.min_charge, self.mask_claimed),
                                episodes, **kw)
-
-    def roll_out(self, max_launches=100000, fresh_episodes=False):
-        if self.fused_policy:
-            self._packed = self.packed_actors()
-        return super().roll_out(max_launches, fresh_episodes)
-
-    def update(self, id, batch, shuffle=np.random.shuffle):
-        self._packed = None                                   # the weights change: never carried across an update
-        if self.device_update:
-            return self._update_device(id, batch, shuffle)
-        return super().update(id, batch, shuffle)
-
-    def _values(self, agent_id, states):
-        if not self.device_update:
-            return super()._values(agent_id, states)
-        torch = self.torch
-        blk = pack_entity_critic(self.critics[agent_id]).to(self.env.device)
-        return self.env.entity_eval(states.to(torch.float32).contiguous(), critic=blk)[2]
-
-    def _prepare_batches(self):
-        if not self.fused_prepare:
-            return super()._prepare_batches()
-        return _fused_prepare_batches(self, 2)
-
-    def update_all(self, batches, shuffle=np.random.shuffle):
-        """`update(id, batches[id])` for every charger at once (joint_update), the counterpart of `BatchedEntityIPPO.update_all`: the list
-        of the tuples `update` returns, the shuffles drawn in the per-charger order.  One process: one index upload and one
-        `entity_pointer_ppo_update`.  Data-parallel (or `_joint_per_step`): per minibatch step one `entity_pointer_ppo_grad_multi` into one
-        flat [M (P_pointer + P_critic)] tensor, one all-reduce of it, one `entity_pointer_adam_multi`."""
-        if not self.joint_update:
-            raise ValueError("update_all needs joint_update=True")
-        env = self.env
-        return _joint_update_all(self, batches, shuffle, 2, pack_entity_pointer_actor, unpack_entity_pointer_actor, env.entity_pointer_ppo_update,
-                                 env.entity_pointer_ppo_grad_multi, env.entity_pointer_adam_multi)
-
-    def _update_device(self, id, batch, shuffle):
-        """`PPOLearner.update` on the device, as `BatchedEntityIPPO._update_fused`: the same epochs, shuffles, minibatches and return value."""
-        torch, env = self.torch, self.env
-        dev = env.device
-        f32 = lambda x: x.to(device=dev, dtype=torch.float32).contiguous()
-        blk_a, blk_c = f32(pack_entity_pointer_actor(self.actors[id])), f32(pack_entity_critic(self.critics[id]))
-        rows = f32(batch["states"])
-        b = {"actions": f32(batch["actions"]).reshape(-1, 2), "log_probs": f32(batch["log_probs"]), "advantages": f32(batch["advantages"]),
-             "returns": f32(batch["returns"]), "values": f32(batch["values"])}
-        hyper = dict(clip=self.clip, ent_coef=self.ent_coef, vf_coef=self.vf_coef, norm_adv=self.norm_adv, clip_vloss=self.clip_vloss)
-        per_epoch = (self.batch_size + self.minibatch_size - 1) // self.minibatch_size
-        table = torch.zeros((self.n_updates_per_iteration * per_epoch, 8), dtype=torch.float32, device=dev)
-        st, ga, gc, lr = self._adam[id], self._grad[:self._pa], self._grad[self._pa:], self.args["lr"]
-        b_inds = np.arange(self.batch_size)
-        k, keep = 0, []
-        for _ in range(self.n_updates_per_iteration):
-            shuffle(b_inds)
-            idx = torch.from_numpy(b_inds.astype(np.int32)).to(dev)      # uploaded once per epoch
-            keep.append(idx)                                          # the launches are asynchronous: alive until the table is read
-            for start in range(0, self.batch_size, self.minibatch_size):
-                env.entity_pointer_ppo_grad(blk_a, blk_c, rows, idx[start:start + self.minibatch_size], b, hyper, self._grad, table[k])
-                if self.world > 1:
-                    torch.distributed.all_reduce(self._grad, group=self.group)
-                    self._grad /= self.world
-                st["step"] += 1
-                if not self._critic_only:                             # `pretrain(critic_iters=...)`: the actor's block and moments stay as they are
-                    env.entity_adam(blk_a, ga, st["m_a"], st["v_a"], st["step"], lr, self.max_grad_norm)
-                env.entity_adam(blk_c, gc, st["m_c"], st["v_c"], st["step"], lr, self.max_grad_norm)
-                k += 1
-        unpack_entity_pointer_actor(blk_a, self.actors[id]); unpack_entity_critic(blk_c, self.critics[id])
-        t = table.cpu().numpy().astype(np.float64)                   # the one read of the update
-        self.loggers[id]["losses"].extend(float(x) for x in t[:, 0])
-        self.first_minibatch_stats[id] = tuple(float(x) for x in t[0, :6])
-        return (float(t[-1, 1]), float(t[-1, 2]), float(t[-1, 3]), float(t[-1, 4]), float(np.mean(t[:, 5])))
 
     def pretrain(self, iters, beta=1.0, beta_end=None, epochs=None, ent_coef=0.0, charge_scale=1.0, x_clip=4.0, critic_iters=0, max_launches=100000):
         """Imitation pretraining from the heuristic (`wrsn_entity_heuristic_label`, `wrsn_entity_pointer_bc_update`): `iters` iterations of
@@ -1536,7 +1463,7 @@ class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
         PPO continues from them.  No critic is touched.  The blocks are unpacked into the modules at the end (and after every iteration
         in which the unfused learner may be asked).
 
-        critic_iters > 0: afterwards that many ordinary iterations (`roll_out`, then `_update_device` per charger -- also with
+        critic_iters > 0: afterwards that many ordinary iterations (`roll_out`, then `_update_charger` per charger -- also with
         joint_update=True) in which the actor's Adam call is skipped, so that fine-tuning does not start from an untrained value
         function.  The shared step count of a charger advances in them as in any update.
 
@@ -1602,7 +1529,7 @@ class BatchedEntityPointerIPPO(RolloutDriver, EntityPointerPPOLearner):
                 batches = self.roll_out(max_launches)
                 for a in range(M):
                     self._packed = None
-                    self._update_device(a, batches[a], np.random.shuffle)
+                    self._update_charger(a, batches[a], np.random.shuffle)
         finally:
             self._critic_only = False
         return out

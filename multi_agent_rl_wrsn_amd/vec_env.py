@@ -602,17 +602,20 @@ class VecWRSN:
         self._h.entity_eval(ptr(actor), ptr(critic), rp, ip, n, N, M, ptr(mean), ptr(log_std), ptr(value))
         return mean, log_std, value
 
+    def _ppo_grad(self, pointer, actor, critic, rows, index, batch, hyper, grad, stats):
+        self._bind_stream()
+        rp, ip, n, N, M = self._entity_rows(rows, index)
+        call, Pa = (self._h.entity_pointer_ppo_grad, self._h.lib.wrsn_entity_pointer_floats()) if pointer else \
+                   (self._h.entity_ppo_grad, self._h.lib.wrsn_entity_actor_floats())
+        call(actor.data_ptr(), critic.data_ptr(), rp, ip, n, N, M, batch["actions"].data_ptr(), batch["log_probs"].data_ptr(),
+             batch["advantages"].data_ptr(), batch["returns"].data_ptr(), batch["values"].data_ptr(), hyper["clip"], hyper["ent_coef"],
+             hyper["vf_coef"], hyper["norm_adv"], hyper["clip_vloss"], grad.data_ptr(), grad.data_ptr() + 4 * Pa, stats.data_ptr())
+
     def entity_ppo_grad(self, actor, critic, rows, index, batch, hyper, grad, stats):
         """`wrsn_entity_ppo_grad`: loss and gradient of one minibatch.  batch: float32 tensors `actions` [*,3], `log_probs`, `advantages`,
         `returns`, `values`, indexed like the rows; hyper: clip, ent_coef, vf_coef, norm_adv, clip_vloss; grad: ONE contiguous float32
         tensor [P_actor + P_critic] (overwritten), stats: float32 [8] (loss, pg, v_loss, entropy, approx_kl, clipfrac, 0, 0)."""
-        self._bind_stream()
-        rp, ip, n, N, M = self._entity_rows(rows, index)
-        Pa = self._h.lib.wrsn_entity_actor_floats()
-        self._h.entity_ppo_grad(actor.data_ptr(), critic.data_ptr(), rp, ip, n, N, M, batch["actions"].data_ptr(), batch["log_probs"].data_ptr(),
-                                batch["advantages"].data_ptr(), batch["returns"].data_ptr(), batch["values"].data_ptr(), hyper["clip"],
-                                hyper["ent_coef"], hyper["vf_coef"], hyper["norm_adv"], hyper["clip_vloss"], grad.data_ptr(),
-                                grad.data_ptr() + 4 * Pa, stats.data_ptr())
+        VecWRSN._ppo_grad(self, False, actor, critic, rows, index, batch, hyper, grad, stats)
 
     def entity_pointer_eval(self, rows, stored=None, actor=None, critic=None, index=None, node_logp=False):
         """`wrsn_entity_pointer_eval`: the packed node-pointer actor and / or critic block on packed entity rows [*, R] and the stored
@@ -640,13 +643,7 @@ class VecWRSN:
     def entity_pointer_ppo_grad(self, actor, critic, rows, index, batch, hyper, grad, stats):
         """`wrsn_entity_pointer_ppo_grad`: `entity_ppo_grad` for the node-pointer actor; batch["actions"] is the stored decisions [*, 2] and
         grad ONE contiguous float32 tensor [wrsn_entity_pointer_floats() + wrsn_entity_critic_floats()] (overwritten)."""
-        self._bind_stream()
-        rp, ip, n, N, M = self._entity_rows(rows, index)
-        Pa = self._h.lib.wrsn_entity_pointer_floats()
-        self._h.entity_pointer_ppo_grad(actor.data_ptr(), critic.data_ptr(), rp, ip, n, N, M, batch["actions"].data_ptr(),
-                                        batch["log_probs"].data_ptr(), batch["advantages"].data_ptr(), batch["returns"].data_ptr(),
-                                        batch["values"].data_ptr(), hyper["clip"], hyper["ent_coef"], hyper["vf_coef"], hyper["norm_adv"],
-                                        hyper["clip_vloss"], grad.data_ptr(), grad.data_ptr() + 4 * Pa, stats.data_ptr())
+        VecWRSN._ppo_grad(self, True, actor, critic, rows, index, batch, hyper, grad, stats)
 
     def entity_adam(self, param, grad, m, v, step, lr, max_norm, beta1=0.9, beta2=0.999, eps=1e-8, norm_out=None):
         """`wrsn_entity_adam`: clip_grad_norm_(max_norm) and one Adam step in place on the block `param` with moments m, v."""
@@ -655,27 +652,36 @@ class VecWRSN:
                             0 if norm_out is None else norm_out.data_ptr())
 
     # -- the same for several independent learners at once (wrsn_entity_ppo_grad_multi / wrsn_entity_adam_multi / wrsn_entity_ppo_update)
-    def _entity_groups(self, groups, need_batch, pointer=False):
+    def _entity_groups(self, groups, need_batch, pointer=False, critic=True):
         """Raw groups (dicts of addresses) from groups of tensors: `actor`, `critic`, `grad` (ONE contiguous float32 tensor [P_actor +
         P_critic]), `m_a`, `v_a`, `m_c`, `v_c`, `step`, and with need_batch `rows` [*, R] and `batch` (the tensors `entity_ppo_grad` takes).
         pointer: the actors are node-pointer blocks (P_actor = wrsn_entity_pointer_floats()) and `actions` the [*, 2] stored pairs.
-        Returns (raw groups, N, M)."""
+        critic=False, the cloning calls: no critic is named, only the first P_actor floats of `grad` receive a gradient, and the stored
+        pairs are the group's `stored` [rows, 2] in place of a batch.  Returns (raw groups, N, M)."""
+        t = self.torch
         Pa = self._h.lib.wrsn_entity_pointer_floats() if pointer else self._h.lib.wrsn_entity_actor_floats()
         raw, N = [], 0
         for g in groups:
-            q = dict(actor=g["actor"].data_ptr(), critic=g["critic"].data_ptr(), grad_actor=g["grad"].data_ptr(), grad_critic=g["grad"].data_ptr() + 4 * Pa,
-                     adam_step=int(g.get("step", 0)))
-            for k, name in (("m_a", "m_actor"), ("v_a", "v_actor"), ("m_c", "m_critic"), ("v_c", "v_critic")):
+            q = dict(actor=g["actor"].data_ptr(), grad_actor=g["grad"].data_ptr(), adam_step=int(g.get("step", 0)))
+            if critic:
+                q.update(critic=g["critic"].data_ptr(), grad_critic=g["grad"].data_ptr() + 4 * Pa)
+            for k, name in (("m_a", "m_actor"), ("v_a", "v_actor")) + ((("m_c", "m_critic"), ("v_c", "v_critic")) if critic else ()):
                 if g.get(k) is not None:
                     q[name] = g[k].data_ptr()
             if need_batch:
-                rp, _, _, n_node, _ = self._entity_rows(g["rows"], None)
+                q["rows"], _, _, n_node, _ = self._entity_rows(g["rows"], None)
                 if N and n_node != N:
                     raise ValueError("the groups' rows must hold the same number of nodes")
                 N = n_node
-                b = g["batch"]
-                q.update(rows=rp, action=b["actions"].data_ptr(), logp_old=b["log_probs"].data_ptr(), advantage=b["advantages"].data_ptr(),
-                         ret=b["returns"].data_ptr(), value_old=b["values"].data_ptr())
+                if critic:
+                    b = g["batch"]
+                    q.update(action=b["actions"].data_ptr(), logp_old=b["log_probs"].data_ptr(), advantage=b["advantages"].data_ptr(),
+                             ret=b["returns"].data_ptr(), value_old=b["values"].data_ptr())
+                else:
+                    st = g["stored"]
+                    if not (st.dtype == t.float32 and st.is_contiguous() and st.dim() == 2 and st.shape[1] == 2 and st.shape[0] == g["rows"].shape[0]):
+                        raise ValueError("stored must be a contiguous float32 tensor [rows, 2]")
+                    q["action"] = st.data_ptr()
             raw.append(q)
         return raw, N, self.num_agent
 
@@ -685,79 +691,61 @@ class VecWRSN:
             raise ValueError("index must be a contiguous int32 tensor %s" % (tuple(shape),))
         return index.data_ptr()
 
+    # One implementation per shape of call.  `call`: the RawHandle method; `what`: the hyper dict or the cloning calls' ent_coef; `kind`: the
+    # (pointer, critic) switches of `_entity_groups`.  The public wrappers reach them through the class, so that an object that borrows
+    # single public methods of VecWRSN (the emulator adapters of tests/) needs none of them.
+    def _grad_multi(self, call, groups, index, what, stats, *kind):
+        self._bind_stream()
+        raw, N, M = self._entity_groups(groups, True, *kind)
+        n = groups[0]["rows"].shape[0] if index is None else index.shape[1]
+        ip = 0 if index is None else self._entity_index(index, (len(groups), n))
+        call(raw, n, N, M, ip, what, stats.data_ptr())
+
+    def _adam_multi(self, call, groups, adam, *kind):
+        self._bind_stream()
+        raw, _, _ = self._entity_groups(groups, False, *kind)
+        call(raw, adam)
+
+    def _update(self, call, groups, index, minibatch, what, stats, adam, *kind):
+        self._bind_stream()
+        raw, N, M = self._entity_groups(groups, True, *kind)
+        ip = self._entity_index(index, (len(groups),) + tuple(index.shape[1:3]))
+        epochs, batch_size = int(index.shape[1]), int(index.shape[2])
+        call(raw, N, M, ip, batch_size, minibatch, epochs, what, adam, stats.data_ptr())
+
     def entity_ppo_grad_multi(self, groups, index, hyper, stats):
         """`wrsn_entity_ppo_grad_multi`: loss and gradient of one minibatch for every group (see `_entity_groups`) in six launches.  index:
         int32 [G, n] (row index[g, i] of group g's rows) or None: all rows of every group; stats: float32 [G, 8]."""
-        self._bind_stream()
-        raw, N, M = self._entity_groups(groups, True)
-        n = groups[0]["rows"].shape[0] if index is None else index.shape[1]
-        ip = 0 if index is None else self._entity_index(index, (len(groups), n))
-        self._h.entity_ppo_grad_multi(raw, n, N, M, ip, hyper, stats.data_ptr())
+        VecWRSN._grad_multi(self, self._h.entity_ppo_grad_multi, groups, index, hyper, stats)
 
     def entity_adam_multi(self, groups, lr, max_norm, beta1=0.9, beta2=0.999, eps=1e-8):
         """`wrsn_entity_adam_multi`: clip_grad_norm_(max_norm) and one Adam step on both blocks of every group, group g at `step` + 1."""
-        self._bind_stream()
-        raw, _, _ = self._entity_groups(groups, False)
-        self._h.entity_adam_multi(raw, dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, max_norm=max_norm))
+        VecWRSN._adam_multi(self, self._h.entity_adam_multi, groups, dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, max_norm=max_norm))
 
     def entity_ppo_update(self, groups, index, minibatch, hyper, stats, lr, max_norm, beta1=0.9, beta2=0.999, eps=1e-8):
         """`wrsn_entity_ppo_update`: every epoch and minibatch of `PPOLearner.update` for every group behind one call.  index: int32
         [G, epochs, batch_size], the shuffles; stats: float32 [G, epochs * ceil(batch_size / minibatch), 8].  Only enqueues; the caller
         advances its step counts by stats.shape[1]."""
-        self._bind_stream()
-        raw, N, M = self._entity_groups(groups, True)
-        ip = self._entity_index(index, (len(groups),) + tuple(index.shape[1:3]))
-        epochs, batch_size = int(index.shape[1]), int(index.shape[2])
-        self._h.entity_ppo_update(raw, N, M, ip, batch_size, minibatch, epochs, hyper,
-                                  dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, max_norm=max_norm), stats.data_ptr())
+        VecWRSN._update(self, self._h.entity_ppo_update, groups, index, minibatch, hyper, stats,
+                        dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, max_norm=max_norm))
 
     # -- and for node-pointer actors (wrsn_entity_pointer_ppo_grad_multi / wrsn_entity_pointer_adam_multi / wrsn_entity_pointer_ppo_update)
     def entity_pointer_ppo_grad_multi(self, groups, index, hyper, stats):
         """`wrsn_entity_pointer_ppo_grad_multi`: `entity_ppo_grad_multi` for node-pointer actors, ten launches.  The groups' `actor` holds
         wrsn_entity_pointer_floats() floats, `grad` is [P_pointer + P_critic] and the batch's `actions` the [*, 2] stored pairs."""
-        self._bind_stream()
-        raw, N, M = self._entity_groups(groups, True, pointer=True)
-        n = groups[0]["rows"].shape[0] if index is None else index.shape[1]
-        ip = 0 if index is None else self._entity_index(index, (len(groups), n))
-        self._h.entity_pointer_ppo_grad_multi(raw, n, N, M, ip, hyper, stats.data_ptr())
+        VecWRSN._grad_multi(self, self._h.entity_pointer_ppo_grad_multi, groups, index, hyper, stats, True)
 
     def entity_pointer_adam_multi(self, groups, lr, max_norm, beta1=0.9, beta2=0.999, eps=1e-8):
         """`wrsn_entity_pointer_adam_multi`: `entity_adam_multi` on pointer blocks, group g at `step` + 1."""
-        self._bind_stream()
-        raw, _, _ = self._entity_groups(groups, False, pointer=True)
-        self._h.entity_pointer_adam_multi(raw, dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, max_norm=max_norm))
+        VecWRSN._adam_multi(self, self._h.entity_pointer_adam_multi, groups, dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, max_norm=max_norm), True)
 
     def entity_pointer_ppo_update(self, groups, index, minibatch, hyper, stats, lr, max_norm, beta1=0.9, beta2=0.999, eps=1e-8):
         """`wrsn_entity_pointer_ppo_update`: `entity_ppo_update` for node-pointer actors.  index: int32 [G, epochs, batch_size]; stats:
         float32 [G, epochs * ceil(batch_size / minibatch), 8].  Only enqueues; the caller advances its step counts by stats.shape[1]."""
-        self._bind_stream()
-        raw, N, M = self._entity_groups(groups, True, pointer=True)
-        ip = self._entity_index(index, (len(groups),) + tuple(index.shape[1:3]))
-        epochs, batch_size = int(index.shape[1]), int(index.shape[2])
-        self._h.entity_pointer_ppo_update(raw, N, M, ip, batch_size, minibatch, epochs, hyper,
-                                          dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, max_norm=max_norm), stats.data_ptr())
+        VecWRSN._update(self, self._h.entity_pointer_ppo_update, groups, index, minibatch, hyper, stats,
+                        dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, max_norm=max_norm), True)
 
     # -- behaviour cloning of node-pointer actors (wrsn_entity_pointer_bc_grad / _bc_grad_multi / _bc_update): the actor's side alone
-    def _entity_bc_groups(self, groups, moments):
-        """Raw groups from groups of tensors: `actor` (pointer block), `grad` (a contiguous float32 tensor whose first
-        wrsn_entity_pointer_floats() floats receive the gradient), `rows` [*, R], `stored` [*, 2], and with `moments` `m_a`, `v_a`, `step`.
-        No critic is named.  Returns (raw groups, N, M)."""
-        t = self.torch
-        raw, N = [], 0
-        for g in groups:
-            rp, _, _, n_node, _ = self._entity_rows(g["rows"], None)
-            if N and n_node != N:
-                raise ValueError("the groups' rows must hold the same number of nodes")
-            N = n_node
-            st = g["stored"]
-            if not (st.dtype == t.float32 and st.is_contiguous() and st.dim() == 2 and st.shape[1] == 2 and st.shape[0] == g["rows"].shape[0]):
-                raise ValueError("stored must be a contiguous float32 tensor [rows, 2]")
-            q = dict(actor=g["actor"].data_ptr(), grad_actor=g["grad"].data_ptr(), rows=rp, action=st.data_ptr(), adam_step=int(g.get("step", 0)))
-            if moments:
-                q.update(m_actor=g["m_a"].data_ptr(), v_actor=g["v_a"].data_ptr())
-            raw.append(q)
-        return raw, N, self.num_agent
-
     def entity_pointer_bc_grad(self, actor, rows, stored, index, ent_coef, grad, stats):
         """`wrsn_entity_pointer_bc_grad`: -mean(logp) - ent_coef * mean(H) of the stored pairs `stored` [*, 2] (indexed like the rows) under
         the packed node-pointer actor, its gradient into the first wrsn_entity_pointer_floats() floats of `grad` and the statistics
@@ -767,24 +755,16 @@ class VecWRSN:
         self._h.entity_pointer_bc_grad(actor.data_ptr(), rp, ip, n, N, M, stored.data_ptr(), ent_coef, grad.data_ptr(), stats.data_ptr())
 
     def entity_pointer_bc_grad_multi(self, groups, index, ent_coef, stats):
-        """`wrsn_entity_pointer_bc_grad_multi`: `entity_pointer_bc_grad` for every group (see `_entity_bc_groups`).  index: int32 [G, n] or
-        None: all rows of every group; stats: float32 [G, 8]."""
-        self._bind_stream()
-        raw, N, M = self._entity_bc_groups(groups, False)
-        n = groups[0]["rows"].shape[0] if index is None else index.shape[1]
-        ip = 0 if index is None else self._entity_index(index, (len(groups), n))
-        self._h.entity_pointer_bc_grad_multi(raw, n, N, M, ip, ent_coef, stats.data_ptr())
+        """`wrsn_entity_pointer_bc_grad_multi`: `entity_pointer_bc_grad` for every group (see `_entity_groups`, critic=False).  index: int32
+        [G, n] or None: all rows of every group; stats: float32 [G, 8]."""
+        VecWRSN._grad_multi(self, self._h.entity_pointer_bc_grad_multi, groups, index, ent_coef, stats, True, False)
 
     def entity_pointer_bc_update(self, groups, index, minibatch, ent_coef, stats, lr, max_norm, beta1=0.9, beta2=0.999, eps=1e-8):
         """`wrsn_entity_pointer_bc_update`: every epoch and minibatch of a behaviour-cloning update for every group behind one call, Adam on
         the actor blocks alone (group g from `step` + 1 on).  index: int32 [G, epochs, batch_size], the shuffles; stats: float32
         [G, epochs * ceil(batch_size / minibatch), 8].  Only enqueues; the caller advances its step counts by stats.shape[1]."""
-        self._bind_stream()
-        raw, N, M = self._entity_bc_groups(groups, True)
-        ip = self._entity_index(index, (len(groups),) + tuple(index.shape[1:3]))
-        epochs, batch_size = int(index.shape[1]), int(index.shape[2])
-        self._h.entity_pointer_bc_update(raw, N, M, ip, batch_size, minibatch, epochs, ent_coef,
-                                         dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, max_norm=max_norm), stats.data_ptr())
+        VecWRSN._update(self, self._h.entity_pointer_bc_update, groups, index, minibatch, ent_coef, stats,
+                        dict(lr=lr, beta1=beta1, beta2=beta2, eps=eps, max_norm=max_norm), True, False)
 
     def entity_prepare(self, groups, index, gamma, gae_lambda):
         """`wrsn_entity_prepare`: the PPO batch of every group -- the critic's values, `PPOLearner.cal_rt_adv` (gae=True) and the gathers --

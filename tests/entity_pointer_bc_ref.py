@@ -456,7 +456,7 @@ def emu_bc_vec(side):
     base = type(K.mask_vec(side))
 
     class EmuPointerBcVec(base):
-        def _entity_bc_groups(self, *a, **kw): return VecWRSN._entity_bc_groups(self, *a, **kw)
+        def _entity_groups(self, *a, **kw): return VecWRSN._entity_groups(self, *a, **kw)
         def entity_heuristic_act(self, *a, **kw): return VecWRSN.entity_heuristic_act(self, *a, **kw)
         def entity_heuristic_label(self, *a, **kw): return VecWRSN.entity_heuristic_label(self, *a, **kw)
         def entity_pointer_bc_grad(self, *a, **kw): return VecWRSN.entity_pointer_bc_grad(self, *a, **kw)

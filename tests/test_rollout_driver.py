@@ -128,8 +128,9 @@ def test_both_trainers_are_learners_on_one_driver():
     from multi_agent_rl_wrsn_amd import BatchedEntityIPPO, BatchedIPPO, EntityPPOLearner, PPOLearner, ippo
     assert issubclass(BatchedIPPO, PPOLearner) and not issubclass(BatchedIPPO, EntityPPOLearner)
     assert issubclass(BatchedEntityIPPO, EntityPPOLearner) and not issubclass(BatchedEntityIPPO, BatchedIPPO)
-    for cls in (BatchedIPPO, BatchedEntityIPPO):
-        assert cls.__mro__[1] is ippo.RolloutDriver
+    assert ippo.DeviceUpdateDriver.__mro__[1] is ippo.RolloutDriver      # the entity trainers' driver: RolloutDriver and the device update
+    for cls, driver in ((BatchedIPPO, ippo.RolloutDriver), (BatchedEntityIPPO, ippo.DeviceUpdateDriver)):
+        assert cls.__mro__[1] is driver
         for name in ("step_batch", "train", "_sync_time"):
             assert getattr(cls, name) is getattr(ippo.RolloutDriver, name), (cls, name)
     assert BatchedIPPO.roll_out is ippo.RolloutDriver.roll_out

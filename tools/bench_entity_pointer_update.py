@@ -2,7 +2,7 @@
 (batch 512, minibatch 64, 5 epochs) and 200 nodes.  Three parts:
   step     one minibatch step of ONE charger at n = 64, M = 3: `entity_pointer_ppo_grad` + two `entity_adam` (device) against
            `minibatch_loss` + backward + `apply_gradients` (torch) on the same rows
-  update   a whole update of every charger, M = 3 and M = 8: M `update` calls (per_charger: `_update_device`, three calls per minibatch step and
+  update   a whole update of every charger, M = 3 and M = 8: M `update` calls (per_charger: `DeviceUpdateDriver._update_charger`, three calls per minibatch step and
            charger) against one `update_all` (joint: one wrsn_entity_pointer_ppo_update).  Both sides include packing the modules, writing
            them back and the one read of the statistics table
   prepare  the tail of a roll-out on the SAME filled transition buffers, M = 3 and M = 8: `_prepare_batches` of the default path (default)

@@ -1,6 +1,6 @@
 """A whole PPO update of every charger's entity policy, joint against per-charger, at bench_ippo.py's hyper-parameters (batch 512, minibatch 64,
 5 epochs) and 200 nodes, for M = 3 and M = 8 chargers: `BatchedEntityIPPO.update_all` (one wrsn_entity_ppo_update for all chargers) against M
-`update` calls (`_update_fused`: three calls per minibatch step and charger) on the same batches.  Both sides include packing the modules,
+`update` calls (`DeviceUpdateDriver._update_charger`: three calls per minibatch step and charger) on the same batches.  Both sides include packing the modules,
 writing them back and the one read of the statistics table.  Alternating windows, 1 warm-up update per side, `--updates` timed updates per window
 (synchronised wall time per update); median, minimum and maximum per window, and the medians of the window medians.  Writes
 profiles/entity_update_joint_bench.json.
